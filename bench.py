@@ -12,6 +12,11 @@ given teacher image embedding, symmetric InfoNCE over the (all-gathered) similar
 for N > 1, and the AdamW update.  Inputs are resident in HBM before the timed region.  fp32 throughout.
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the line can carry,
+all measured after the timed region: forward+backward without the optimizer, the HIP-graph replay, the N > 1 calibration
+legs, the other BASELINE configs (`extra_configs`) and the CPU baselines.  `--dump-outputs DIR` writes what the last timed
+step left its caller (loss, sampled parameters and AdamW moments) to DIR/*.npy, for output-by-output comparisons of builds.
 """
 from __future__ import annotations
 
@@ -264,6 +269,37 @@ def cpu_baseline(seconds: float = 12.0, regime: str = "north_star"):
                       f"(oracle/dclip_oracle.py, torch {torch.__version__} CPU)"}
 
 
+DUMP_ELEMS_PER_ARRAY = 4 << 20      # float32 elements per sampled array: three arrays of 16 MiB, under 64 MB in all
+
+
+def dump_outputs(out_dir, params, opt, loss):
+    """What the timed path hands its caller after its last step, as .npy files in `out_dir`: `loss` (float64), the trainable
+    parameters the optimizer updated (`params`), AdamW's two moments, which carry the gradients (`adam_exp_avg`,
+    `adam_exp_avg_sq`), and the pre-clip global gradient norm (`grad_norm`).  A tensor larger than its share of
+    DUMP_ELEMS_PER_ARRAY is sampled at positions drawn from a fixed seed; the samples are concatenated in parameter order,
+    so the same arguments give the same positions and two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = max(1, DUMP_ELEMS_PER_ARRAY // max(1, len(params)))
+    gen = torch.Generator().manual_seed(1234)
+    names = ("params",) if opt is None else ("params", "adam_exp_avg", "adam_exp_avg_sq")
+    cols = {k: [] for k in names}
+    for p in params:
+        n = p.numel()
+        idx = (torch.arange(n) if n <= share else torch.randint(n, (share,), generator=gen).sort().values).to(p.device)
+        st = opt.state.get(p, {}) if opt is not None else {}
+        for k, t in zip(names, (p, st.get("exp_avg"), st.get("exp_avg_sq"))):
+            # a parameter that never received a gradient has no optimizer state: its moments are zero
+            cols[k].append(torch.zeros(idx.numel()) if t is None else t.detach().reshape(-1)[idx].float().cpu())
+    arrays = {k: torch.cat(v).numpy() for k, v in cols.items()}
+    arrays["loss"] = np.array([loss], dtype=np.float64)
+    if opt is not None and opt.last_grad_norm is not None:
+        arrays["grad_norm"] = np.array([float(opt.last_grad_norm)], dtype=np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def build_workload(workload, model, teacher_model, batch_size, regions, student_precision, tower_precision, dev, group, rank,
                    fast_teacher_init: bool = False):
     """The distillation module of one BASELINE config on synthetic inputs resident in HBM -> (module, student config, teacher
@@ -468,12 +504,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (weak scaling)")
     ap.add_argument("--model", default="ViT-B/32", choices=list(dcfg.NAMED))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline figure does not need: the extra legs, "
+                         "the N > 1 calibration legs, the other BASELINE configs (extra_configs) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left its caller to DIR/<name>.npy (loss, sampled "
+                         "parameters and AdamW moments at fixed seeded positions)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-optimizer", action="store_true", help="time forward+backward only")
     ap.add_argument("--no-gemm-events", action="store_true", help="do not bracket GEMM launches with HIP events")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the untimed-by-the-contract extra measurements after the timed region (forward+backward "
-                         "without the optimizer; HIP-graph replay)")
+                    help="with --full: skip the untimed-by-the-contract extra measurements after the timed region "
+                         "(forward+backward without the optimizer; HIP-graph replay; extra_configs)")
     ap.add_argument("--eager", action="store_true",
                     help="launch every step kernel by kernel — the default since round 3 (kept as a flag for scripts that pass it)")
     ap.add_argument("--hybrid-graph", action="store_true",
@@ -500,6 +542,8 @@ def main():
                     help="c3 / c5: GEMM input precision of the FROZEN teacher towers (student is always fp32); default "
                          "fp32 for c3, bf16 for c5")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.workload == "c5":
         args.teacher_model = args.teacher_model or "ViT-L/14"
         args.tower_precision = args.tower_precision or "bf16"
@@ -709,8 +753,12 @@ def main():
     last_loss = float(last.detach())
     del last
     note(f"timed region done: {elapsed * 1e3 / args.steps:.2f} ms/step")
+    if args.dump_outputs and rank == 0:
+        # before any leg below: the graph-replay leg steps the optimizer again
+        dump_outputs(args.dump_outputs, trainable, opt, last_loss)
+        note("outputs written")
     comm = sync.stats() if sync is not None else None
-    if sync is not None:
+    if sync is not None and args.full:
         # calibration leg (every rank): each gradient bucket all-reduced alone -> ms per bucket and the bus rate
         # 2(N-1)/N x bytes / time the collective reaches with nothing beside it
         per_bucket = sync.bucket_allreduce_ms()
@@ -722,9 +770,9 @@ def main():
         comm["allreduce_busbw_GBps_alone"] = round(2.0 * (world - 1) / world * tot_b / (tot_ms * 1e-3) / 1e9, 2) if tot_ms else None
         note("bucket calibration done")
 
-    # ---- extra legs, outside the contract's timed region ("optimizer excluded and reported separately")
+    # ---- extra legs (--full), outside the contract's timed region ("optimizer excluded and reported separately")
     extra = {}
-    if not args.no_extra_legs and graphed is None:
+    if args.full and not args.no_extra_legs and graphed is None:
         n_x = max(3, min(args.steps, 10))
         if opt is not None:
             el, _ = timed(n_x, lambda: step(with_opt=False))
@@ -757,7 +805,7 @@ def main():
             except Exception as exc:            # a graph variant is informative only; never fail the bench line on it
                 extra["graph_error"] = f"{type(exc).__name__}: {exc}"[:200]
 
-    if world > 1 and not args.no_extra_legs:
+    if world > 1 and args.full and not args.no_extra_legs:
         # The same step WITHOUT the data-parallel parts, launched the same way (eagerly) on every rank at once: local
         # negatives only, no gradient all-reduce.  N-rank `value` / (N x this) is the scaling efficiency of like with like
         # (the N = 1 default line replays a HIP graph, ~3 % faster than eager launches).  After the timed region: the
@@ -889,10 +937,10 @@ def main():
         if comm is not None:
             line["comm"] = dict(comm, backend=backend, ranks=dist.get_world_size(group),
                                 embedding_all_gather_bytes_per_rank=2 * B * cfg.projection_dim * 4)
-        if world == 1 and not meta and not args.no_extra_legs and args.student_precision == "fp32" \
+        if args.full and world == 1 and not meta and not args.no_extra_legs and args.student_precision == "fp32" \
                 and cfg.name == "ViT-B/32" and B == 256 and not args.no_gemm_events:
-            # the default run also times the other BASELINE configs for a few steps each (outside the contract's timed region):
-            # c3 as quoted, and one GPU's share of the 8-GPU configs c4 and c5
+            # the default workload with --full also times the other BASELINE configs for a few steps each (outside the
+            # contract's timed region): c3 as quoted, and one GPU's share of the 8-GPU configs c4 and c5
             line["extra_configs"] = {}
             for name, which, st_, wu_ in (("c3_bf16", "c3", 5, 2), ("c4_per_gpu", "c4", 3, 1), ("c5_per_gpu_bf16", "c5", 3, 1)):
                 if os.environ.get("DCLIP_BENCH_EXTRA", "c3,c4,c5").find(which) < 0:
@@ -901,7 +949,7 @@ def main():
                     line["extra_configs"][name] = extra_config(dev, timer, which, st_, wu_)
                 except Exception as exc:          # informative only: never fail the bench line on it
                     line["extra_configs"][name] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             secs = float(os.environ.get("DCLIP_BENCH_CPU_SECONDS", "8"))
             line["cpu_baseline"] = cpu_baseline(secs, "north_star")          # same regime as `value`
             line["cpu_baseline_c1"] = cpu_baseline(secs, "as_written")       # BASELINE config c1 as the reference runs it

@@ -10,9 +10,9 @@ if [ "$1" != "--no-tests" ]; then
   [ $TRC -eq 0 ] || grep -n "^E " $O/tests.log | head -30
   python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 && echo "smoke ok" || tail -5 $O/smoke.log
 fi
-T0=$(date +%s); python3 bench.py > $O/bench.json 2> $O/bench.err; echo "default bench.py wall time $(( $(date +%s) - T0 )) s"
+T0=$(date +%s); python3 bench.py --full > $O/bench.json 2> $O/bench.err; echo "default bench.py wall time $(( $(date +%s) - T0 )) s"
 python3 -c "import json;d=json.load(open('$O/bench.json'));print(d['value'],d['ms_per_step'],d['roofline']['frac'],d['roofline_step'],d['extra_configs']['c3_bf16']['value'],d['extra_configs']['c3_bf16']['ms_per_step'],d['extra_configs']['c3_bf16']['roofline_bf16'])"
-python3 bench.py --workload c3 --tower-precision bf16 --student-precision bf16 --no-cpu-baseline > $O/bench_c3_bf16.json 2> $O/bench_c3.err
+python3 bench.py --full --workload c3 --tower-precision bf16 --student-precision bf16 --no-cpu-baseline > $O/bench_c3_bf16.json 2> $O/bench_c3.err
 python3 bench.py --workload c5 --batch 512 --steps 4 --warmup 1 --student-precision bf16 --no-cpu-baseline --no-extra-legs > $O/bench_c5_b512.json 2> $O/bench_c5.err
 C3="--eager --no-cpu-baseline --no-extra-legs --workload c3 --tower-precision bf16 --student-precision bf16"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c3b -o s -- python3 bench.py $C3 --steps 4 --warmup 1 > $O/c3b.log 2>&1

@@ -33,8 +33,8 @@ python3 tools/summarize_traffic.py $O/c3fetch $O/c3write $O/c3_hbm.json > /dev/n
 python3 tools/summarize_profile.py $O/c3b /nonexistent /nonexistent $O/c3b_sum > /dev/null
 python3 tools/summarize_profile.py $O/c5b /nonexistent /nonexistent $O/c5b_sum > /dev/null
 find $O -name "*counter_collection.csv" -delete
-python3 bench.py --workload c3 --tower-precision bf16 --student-precision bf16 --no-cpu-baseline > $O/bench_c3_bf16.json 2> $O/bench_c3b.err
+python3 bench.py --full --workload c3 --tower-precision bf16 --student-precision bf16 --no-cpu-baseline > $O/bench_c3_bf16.json 2> $O/bench_c3b.err
 python3 bench.py --workload c5 --batch 512 --steps 4 --warmup 1 --student-precision bf16 --no-cpu-baseline --no-extra-legs > $O/bench_c5_b512.json 2> $O/bench_c5.err
-python3 bench.py --model ViT-B/16 --batch 128 --no-cpu-baseline > $O/bench_c4_pergpu.json 2> $O/bench_c4.err
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --model ViT-B/16 --batch 128 --no-cpu-baseline > $O/bench_c4_pergpu.json 2> $O/bench_c4.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 300 $O/bench.json
