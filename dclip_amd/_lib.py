@@ -100,6 +100,12 @@ SIGNATURES = {
     "dclip_mt_adam_f32": (I, [P, I, I, F, F, F, F, F, P, P]),
     "dclip_axpby": (I, [P, P, F, F, Z, P]),
     "dclip_fill": (I, [P, F, Z, P]),
+    "dclip_gemm_f16": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "dclip_cast_f32_f16": (I, [P, P, I, I, I, I, P]),
+    "dclip_layernorm_fwd_f16": (I, [P, P, P, P, I, I, F, P]),
+    "dclip_im2col_f16": (I, [P, P, I, I, I, I, I, I, P]),
+    "dclip_attention_fwd_f16": (I, [P, P, I, I, I, I, P]),
+    "dclip_attention_row_fwd_f16": (I, [P, P, P, I, I, I, P]),
 }
 
 _lib = None

@@ -167,7 +167,9 @@ class HipCLIPModel(nn.Module):
 
     # ------------------------------------------------------------------ reference call surface
     def get_image_features(self, pixel_values: torch.Tensor = None, precision: str = "fp32", **kwargs) -> torch.Tensor:
-        """precision="bf16" (opt-in, frozen use only): GEMM inputs in bf16 on the bf16 MFMA path, everything else fp32."""
+        """precision="bf16" (opt-in): GEMM inputs in bf16 on the bf16 MFMA path, everything else fp32 — frozen forward, or
+        the bf16 training path when grad is enabled and a parameter is trainable.  precision="fp16" (opt-in, frozen use
+        only): the same forward with fp16 GEMM inputs (3 more mantissa bits at the bf16 rate)."""
         if pixel_values is None:
             raise ValueError("You have to specify pixel_values")
         v = self.config.vision
@@ -183,6 +185,11 @@ class HipCLIPModel(nn.Module):
                                                           *p.tensors())
             pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)
             return engine.vision_fwd_bf16(pd, pixel_values.float().contiguous(), v, self._bf16_cache())
+        if precision == "fp16":
+            if torch.is_grad_enabled() and any(t.requires_grad for t in p.tensors()):
+                raise RuntimeError("precision='fp16' is a forward-only path for frozen towers: call it under torch.no_grad()")
+            pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)
+            return engine.vision_fwd_bf16(pd, pixel_values.float().contiguous(), v, self._f16_cache(), torch.float16)
         if precision != "fp32":
             raise ValueError(f"precision {precision!r}")
         return functional.VisionTowerFn.apply(pixel_values.float(), v, v.num_hidden_layers, *p.tensors())
@@ -196,26 +203,36 @@ class HipCLIPModel(nn.Module):
             object.__setattr__(self, "_bf16_w", c)
         return c
 
+    def _f16_cache(self) -> dict:
+        """fp16 copies of the GEMM weights (precision="fp16"), kept apart from the bf16 ones: the keys are the same."""
+        c = getattr(self, "_f16_w", None)
+        if c is None:
+            c = {}
+            object.__setattr__(self, "_f16_w", c)
+        return c
+
     def invalidate_bf16_of_trainable(self) -> int:
-        """Mark the bf16 copies of every TRAINABLE parameter stale (frozen towers keep theirs).  graph.GraphedStep calls
+        """Mark the bf16 (and fp16) copies of every TRAINABLE parameter stale (frozen towers keep theirs).  graph.GraphedStep calls
         this between its eager warm-up and the capture: the weight casts / transposes are then part of the captured step
         and every replay converts the CURRENT fp32 masters — without it a replay would multiply by the copies made
         at warm-up while the optimizer keeps updating the masters.  Returns the number of entries marked."""
-        c = getattr(self, "_bf16_w", None)
-        if not c:
+        caches = [c for c in (getattr(self, "_bf16_w", None), getattr(self, "_f16_w", None)) if c]
+        if not caches:
             return 0
         ptrs = {p.data_ptr() for p in self.parameters() if p.requires_grad}
         n = 0
-        for e in c.values():
-            if isinstance(e, list) and e[2] in ptrs:
-                e[1] = -1
-                n += 1
+        for c in caches:
+            for e in c.values():
+                if isinstance(e, list) and e[2] in ptrs:
+                    e[1] = -1
+                    n += 1
         return n
 
     def get_text_features(self, input_ids: torch.Tensor = None, attention_mask=None, precision: str = "fp32",
                           **kwargs) -> torch.Tensor:
         """`attention_mask` is accepted and ignored: under the causal mask trailing pads cannot influence the
-        first-EOS row that is pooled.  precision="bf16": see get_image_features."""
+        first-EOS row that is pooled.  precision="bf16" / "fp16": frozen forward only (see
+        get_image_features)."""
         if input_ids is None:
             raise ValueError("You have to specify input_ids")
         t = self.config.text
@@ -228,6 +245,11 @@ class HipCLIPModel(nn.Module):
                 raise RuntimeError("precision='bf16' is a forward-only path for frozen towers: call it under torch.no_grad()")
             return engine.text_fwd_frozen_bf16(self.text_params_detached(), input_ids.long().contiguous(), t,
                                                self._bf16_cache())
+        if precision == "fp16":
+            if torch.is_grad_enabled() and any(x.requires_grad for x in p.tensors()):
+                raise RuntimeError("precision='fp16' is a forward-only path for frozen towers: call it under torch.no_grad()")
+            return engine.text_fwd_frozen_bf16(self.text_params_detached(), input_ids.long().contiguous(), t,
+                                               self._f16_cache(), torch.float16)
         if precision != "fp32":
             raise ValueError(f"precision {precision!r}")
         return functional.TextTowerFn.apply(input_ids.long(), t, t.num_hidden_layers, *p.tensors())
@@ -239,6 +261,9 @@ class HipCLIPModel(nn.Module):
         ids = input_ids.long().contiguous()
         if precision == "bf16":
             sent, tokens, eos = engine.text_token_level_bf16(self.text_params_detached(), ids, t, self._bf16_cache())
+        elif precision == "fp16":
+            sent, tokens, eos = engine.text_token_level_bf16(self.text_params_detached(), ids, t, self._f16_cache(),
+                                                             torch.float16)
         elif precision == "fp32":
             sent, tokens, eos = engine.text_token_level(self.text_params_detached(), ids, t)
         else:

@@ -11,6 +11,10 @@
 // lane already holds in registers r = 8t..8t+7 — P goes register -> bf16 -> B operand with no LDS round trip — and
 // the matching A operand V^T[d][those keys] is read straight out of the row-major V tile with the gfx950 transposing
 // LDS read (ds_read_b64_tr_b16: 4 keys x 16 head dims per 16 lanes).
+//
+// The forward kernels (tiled, whole-head, one-row) are templates over the 16-bit type (common.h, Bf16T / F16T): the fp16
+// instances serve dclip_attention_fwd_f16 / dclip_attention_row_fwd_f16 with P rounded to fp16.  The training forms (lse,
+// backward) are bf16 only.
 #include "common.h"
 #include <stdlib.h>
 
@@ -37,9 +41,10 @@ __device__ __forceinline__ s16x4 lds_tr16(const unsigned char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
 }
 
-template <bool CAUSAL>
+template <class T, bool CAUSAL>
 __global__ void __launch_bounds__(128) attn_fwd_bf16_kernel(const unsigned short* __restrict__ qkv, unsigned short* __restrict__ out,
                                                             int S, int H) {
+  typedef typename T::x8 V8;
   __shared__ __attribute__((aligned(16))) unsigned char Ks[KT * 128];
   __shared__ __attribute__((aligned(16))) unsigned char Vs[KT * 128];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -51,11 +56,11 @@ __global__ void __launch_bounds__(128) attn_fwd_bf16_kernel(const unsigned short
   const unsigned short* base = qkv + (size_t)b * S * ld + h * HD;
 
   // Q fragments (B operand): Q[query][16 s + 8 half .. +7]
-  bf16x8 qf[4];
+  V8 qf[4];
   {
     const unsigned short* qrow = base + (size_t)min(query, S - 1) * ld + 8 * half;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qrow + 16 * s));
+    for (int s = 0; s < 4; ++s) qf[s] = __builtin_bit_cast(V8, *reinterpret_cast<const u32x4*>(qrow + 16 * s));
   }
   f32x16 o[2];
 #pragma unroll
@@ -93,8 +98,8 @@ __global__ void __launch_bounds__(128) attn_fwd_bf16_kernel(const unsigned short
       for (int r = 0; r < 16; ++r) st[sub][r] = 0.f;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const bf16x8 kf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(Ks + gran_off(32 * sub + l31, 2 * s + half)));
-        st[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], st[sub], 0, 0, 0);
+        const V8 kf = __builtin_bit_cast(V8, *reinterpret_cast<const u32x4*>(Ks + gran_off(32 * sub + l31, 2 * s + half)));
+        st[sub] = T::mfma32(kf, qf[s], st[sub]);
       }
     }
     float mx = -INFINITY;
@@ -135,9 +140,9 @@ __global__ void __launch_bounds__(128) attn_fwd_bf16_kernel(const unsigned short
     for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        bf16x8 pf;
+        V8 pf;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) pf[e] = (__bf16)st[sub][8 * t + e];
+        for (int e = 0; e < 8; ++e) pf[e] = T::cvt_unit(st[sub][8 * t + e]);
         const int k0 = 32 * sub + 16 * t + 4 * half;
         // transposing read: lane i = 4 q + p of each 16-lane group addresses row (key) k + q, head dims d0 + 4 p .. + 3,
         // and receives V[k .. k+3][d0 + i]
@@ -151,7 +156,7 @@ __global__ void __launch_bounds__(128) attn_fwd_bf16_kernel(const unsigned short
           const s16x4 hi = lds_tr16(Vs + gran_off(kb, dcol >> 3) + (dcol & 7) * 2);
           typedef short s16x8 __attribute__((ext_vector_type(8)));
           const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, both), pf, o[dt], 0, 0, 0);
+          o[dt] = T::mfma32(__builtin_bit_cast(V8, both), pf, o[dt]);
         }
       }
   }
@@ -162,8 +167,8 @@ __global__ void __launch_bounds__(128) attn_fwd_bf16_kernel(const unsigned short
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        u16x4 v = {bf16_bits(o[dt][4 * j + 0] * inv), bf16_bits(o[dt][4 * j + 1] * inv), bf16_bits(o[dt][4 * j + 2] * inv),
-                   bf16_bits(o[dt][4 * j + 3] * inv)};
+        u16x4 v = {T::bits(o[dt][4 * j + 0] * inv), T::bits(o[dt][4 * j + 1] * inv), T::bits(o[dt][4 * j + 2] * inv),
+                   T::bits(o[dt][4 * j + 3] * inv)};
         *reinterpret_cast<u16x4*>(orow + 32 * dt + 8 * j + 4 * half) = v;
       }
   }
@@ -184,10 +189,11 @@ __global__ void __launch_bounds__(128) attn_fwd_bf16_kernel(const unsigned short
 // at 4 per SIMD); with 8 waves two fit.  Wave w forms the last query's scores against key block w (wave 0 also the block
 // that holds the last key) with that query in every column of the B operand, its local maximum / sum / P V go to LDS, and
 // after one barrier wave 0 merges the NB + 1 partial results (the flash-attention merge, once per head).
-template <int NB, bool CAUSAL, bool XQ>
+template <class T, int NB, bool CAUSAL, bool XQ>
 __global__ void __launch_bounds__(64 * NB, (XQ ? 4 : 1)) attn_fwd_bf16_head_kernel(const unsigned short* __restrict__ qkv,
                                                                      unsigned short* __restrict__ out, int S, int H,
                                                                      float* __restrict__ lse = nullptr) {
+  typedef typename T::x8 V8;
   constexpr int KB = NB + (XQ ? 1 : 0);            // 32-key blocks staged
   constexpr int CHUNKS = KB * 256, NTHR = 64 * NB, ITER = (CHUNKS + NTHR - 1) / NTHR;
   __shared__ __attribute__((aligned(16))) unsigned char Ks[KB * 32 * 128];
@@ -204,11 +210,11 @@ __global__ void __launch_bounds__(64 * NB, (XQ ? 4 : 1)) attn_fwd_bf16_head_kern
 
   // Q fragments (B operand): Q[query][16 s + 8 half .. +7] — requested FIRST, in front of the K / V staging loads, so
   // that they do not become a second round trip to memory behind the barrier
-  bf16x8 qf[4];
+  V8 qf[4];
   {
     const unsigned short* qrow = base + (size_t)min(query, S - 1) * ld + 8 * half;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qrow + 16 * s));
+    for (int s = 0; s < 4; ++s) qf[s] = __builtin_bit_cast(V8, *reinterpret_cast<const u32x4*>(qrow + 16 * s));
   }
   __builtin_amdgcn_sched_barrier(0);
   // all eight 16-byte loads of a thread go out together (rows past the end read the last row and are zeroed after: a
@@ -244,18 +250,18 @@ __global__ void __launch_bounds__(64 * NB, (XQ ? 4 : 1)) attn_fwd_bf16_head_kern
   // K fragments of one 32-key block (A operand of S^T = K Q^T): 4 x ds_read_b128 into the SAME registers every block —
   // issued right after the block's score MFMAs have consumed the previous contents, so they land behind the softmax
   // VALU work and the P V MFMAs instead of in front of the next score chain.
-  bf16x8 kf[4];
+  V8 kf[4];
   auto load_k = [&](int kb) {
 #pragma unroll
     for (int s = 0; s < 4; ++s)
-      kf[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(Ks + gran_off(32 * kb + l31, 2 * s + half)));
+      kf[s] = __builtin_bit_cast(V8, *reinterpret_cast<const u32x4*>(Ks + gran_off(32 * kb + l31, 2 * s + half)));
   };
-  auto qk_with = [&](const bf16x8 (&q)[4]) {
+  auto qk_with = [&](const V8 (&q)[4]) {
     f32x16 st;
 #pragma unroll
     for (int r = 0; r < 16; ++r) st[r] = 0.f;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[s], q[s], st, 0, 0, 0);
+    for (int s = 0; s < 4; ++s) st = T::mfma32(kf[s], q[s], st);
     return st;
   };
   auto qk = [&]() { return qk_with(qf); };
@@ -319,12 +325,12 @@ __global__ void __launch_bounds__(64 * NB, (XQ ? 4 : 1)) attn_fwd_bf16_head_kern
   auto pv = [&](const f32x16& st) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      bf16x8 pf;
+      V8 pf;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) pf[e] = (__bf16)st[8 * t + e];
+      for (int e = 0; e < 8; ++e) pf[e] = T::cvt_unit(st[8 * t + e]);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[t][dt]), pf, o[dt], 0, 0, 0);
+        o[dt] = T::mfma32(__builtin_bit_cast(V8, vf[t][dt]), pf, o[dt]);
     }
   };
   for (int kb = 0; kb < nfull; ++kb) {
@@ -362,16 +368,16 @@ __global__ void __launch_bounds__(64 * NB, (XQ ? 4 : 1)) attn_fwd_bf16_head_kern
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        u16x4 v = {bf16_bits(o[dt][4 * j + 0] * inv), bf16_bits(o[dt][4 * j + 1] * inv), bf16_bits(o[dt][4 * j + 2] * inv),
-                   bf16_bits(o[dt][4 * j + 3] * inv)};
+        u16x4 v = {T::bits(o[dt][4 * j + 0] * inv), T::bits(o[dt][4 * j + 1] * inv), T::bits(o[dt][4 * j + 2] * inv),
+                   T::bits(o[dt][4 * j + 3] * inv)};
         *reinterpret_cast<u16x4*>(orow + 32 * dt + 8 * j + 4 * half) = v;
       }
   }
   if (XQ) {
     // ---- the shared last query: this wave's key block(s), that query in every column of the B operand
-    bf16x8 qx[4];
+    V8 qx[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) qx[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(xq_row + 16 * s + 8 * half));
+    for (int s = 0; s < 4; ++s) qx[s] = __builtin_bit_cast(V8, *reinterpret_cast<const u32x4*>(xq_row + 16 * s + 8 * half));
     const int nx = wave == 0 ? 2 : 1;
     for (int x = 0; x < nx; ++x) {
       const int xb = x == 0 ? wave : NB;             // wave 0 also takes the block with the last key
@@ -421,16 +427,16 @@ __global__ void __launch_bounds__(64 * NB, (XQ ? 4 : 1)) attn_fwd_bf16_head_kern
         den += w * xpart[xb * 68 + 1];
         num += w * xpart[xb * 68 + 4 + lane];
       }
-      out[((size_t)b * S + (S - 1)) * D + h * HD + lane] = bf16_bits(num / den);
+      out[((size_t)b * S + (S - 1)) * D + h * HD + lane] = T::bits(num / den);
     }
   }
 }
 
-template <int NB>
+template <class T, int NB>
 void launch_head(const unsigned short* qkv, unsigned short* out, int B, int S, int H, int causal, hipStream_t st,
                  float* lse = nullptr) {
-  if (causal) hipLaunchKernelGGL((attn_fwd_bf16_head_kernel<NB, true, false>), dim3(B * H), dim3(64 * NB), 0, st, qkv, out, S, H, lse);
-  else hipLaunchKernelGGL((attn_fwd_bf16_head_kernel<NB, false, false>), dim3(B * H), dim3(64 * NB), 0, st, qkv, out, S, H, lse);
+  if (causal) hipLaunchKernelGGL((attn_fwd_bf16_head_kernel<T, NB, true, false>), dim3(B * H), dim3(64 * NB), 0, st, qkv, out, S, H, lse);
+  else hipLaunchKernelGGL((attn_fwd_bf16_head_kernel<T, NB, false, false>), dim3(B * H), dim3(64 * NB), 0, st, qkv, out, S, H, lse);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -639,6 +645,7 @@ __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short
 // reading K and V once: 2 x 2 B x S x 64 per (sequence, head) — the generic fp32 kernel it replaces here padded the one
 // query row to a 64-row tile (390 us at 2048 crops x 12 heads x 50 tokens, against ~60 us of bytes).
 constexpr int ROW_MAXI = 8;        // keys per lane: S <= 512
+template <class T>
 __global__ void __launch_bounds__(256) attn_row_fwd_bf16_kernel(const unsigned short* __restrict__ qkv, const int* __restrict__ rows,
                                                                 unsigned short* __restrict__ out, int B, int S, int H) {
   const int lane = threadIdx.x & 63;
@@ -657,8 +664,8 @@ __global__ void __launch_bounds__(256) attn_row_fwd_bf16_kernel(const unsigned s
       const u32x4 w = *reinterpret_cast<const u32x4*>(qp + 8 * c);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        q[8 * c + 2 * e] = __builtin_bit_cast(float, w[e] << 16);
-        q[8 * c + 2 * e + 1] = __builtin_bit_cast(float, w[e] & 0xffff0000u);
+        q[8 * c + 2 * e] = T::lo_f32(w[e]);
+        q[8 * c + 2 * e + 1] = T::hi_f32(w[e]);
       }
     }
   }
@@ -676,8 +683,8 @@ __global__ void __launch_bounds__(256) attn_row_fwd_bf16_kernel(const unsigned s
         const u32x4 w = *reinterpret_cast<const u32x4*>(kp + 8 * c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          a0 += q[8 * c + 2 * e] * __builtin_bit_cast(float, w[e] << 16);
-          a1 += q[8 * c + 2 * e + 1] * __builtin_bit_cast(float, w[e] & 0xffff0000u);
+          a0 += q[8 * c + 2 * e] * T::lo_f32(w[e]);
+          a1 += q[8 * c + 2 * e + 1] * T::hi_f32(w[e]);
         }
       }
       if (j < nkeys) sc[i] = (a0 + a1) * kScale;
@@ -705,29 +712,41 @@ __global__ void __launch_bounds__(256) attn_row_fwd_bf16_kernel(const unsigned s
     int jj = 0;
     for (; jj + 1 < n; jj += 2) {
       const float p0 = __shfl(sc[i], jj), p1 = __shfl(sc[i], jj + 1);
-      const float v0 = __builtin_bit_cast(float, (unsigned int)vp[(size_t)(64 * i + jj) * ld] << 16);
-      const float v1 = __builtin_bit_cast(float, (unsigned int)vp[(size_t)(64 * i + jj + 1) * ld] << 16);
+      const float v0 = T::to_f32(vp[(size_t)(64 * i + jj) * ld]);
+      const float v1 = T::to_f32(vp[(size_t)(64 * i + jj + 1) * ld]);
       acc0 += p0 * v0;
       acc1 += p1 * v1;
     }
-    if (jj < n) acc0 += __shfl(sc[i], jj) * __builtin_bit_cast(float, (unsigned int)vp[(size_t)(64 * i + jj) * ld] << 16);
+    if (jj < n) acc0 += __shfl(sc[i], jj) * T::to_f32(vp[(size_t)(64 * i + jj) * ld]);
   }
-  out[(size_t)b * D + h * HD + lane] = bf16_bits((acc0 + acc1) * inv);
+  out[(size_t)b * D + h * HD + lane] = T::bits((acc0 + acc1) * inv);
 }
 
+}  // namespace
+
+namespace {
+template <class T>
+int attention_row16(const char* name, const void* qkv, const int32_t* rows, void* out, int B, int S, int H, void* stream) {
+  DCLIP_REQUIRE(qkv && out, "%s: null pointer", name);
+  DCLIP_REQUIRE(B > 0 && S > 0 && S <= 64 * ROW_MAXI && H > 0, "%s: B=%d S=%d (<= 512) H=%d", name, B, S, H);
+  DCLIP_REQUIRE((uintptr_t)qkv % 16 == 0, "%s: 16-byte alignment", name);
+  hipLaunchKernelGGL(attn_row_fwd_bf16_kernel<T>, dim3(cdiv(B * H, 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)qkv,
+                     (const int*)rows, (unsigned short*)out, B, S, H);
+  DCLIP_CHECK_LAUNCH(name);
+  return DCLIP_OK;
+}
 }  // namespace
 
 // One attention output row per sequence, bf16 in / bf16 out (the LAST layer of a frozen bf16 tower): rows == NULL: query row 0
 // against all S keys (the CLS row of a vision tower); rows [B] int32: query row rows[b] against keys 0..rows[b] (the first-EOS
 // row of a causal text tower).  qkv [B*S][3*H*64] bf16, out [B][H*64] bf16.  S <= 512.
 DCLIP_API int dclip_attention_row_fwd_bf16(const void* qkv, const int32_t* rows, void* out, int B, int S, int H, void* stream) {
-  DCLIP_REQUIRE(qkv && out, "attention_row_fwd_bf16: null pointer");
-  DCLIP_REQUIRE(B > 0 && S > 0 && S <= 64 * ROW_MAXI && H > 0, "attention_row_fwd_bf16: B=%d S=%d (<= 512) H=%d", B, S, H);
-  DCLIP_REQUIRE((uintptr_t)qkv % 16 == 0, "attention_row_fwd_bf16: 16-byte alignment");
-  hipLaunchKernelGGL(attn_row_fwd_bf16_kernel, dim3(cdiv(B * H, 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)qkv,
-                     (const int*)rows, (unsigned short*)out, B, S, H);
-  DCLIP_CHECK_LAUNCH("attention_row_fwd_bf16");
-  return DCLIP_OK;
+  return attention_row16<Bf16T>("attention_row_fwd_bf16", qkv, rows, out, B, S, H, stream);
+}
+
+// The same with fp16 q / k / v and an fp16 result (frozen fp16 towers).
+DCLIP_API int dclip_attention_row_fwd_f16(const void* qkv, const int32_t* rows, void* out, int B, int S, int H, void* stream) {
+  return attention_row16<F16T>("attention_row_fwd_f16", qkv, rows, out, B, S, H, stream);
 }
 
 // Training forms (bf16 student, configs c3 / c5): the forward also leaves the log-sum-exp of the scaled scores (S <= 288,
@@ -740,15 +759,15 @@ DCLIP_API int dclip_attention_fwd_bf16_lse(const void* qkv, void* out, float* ls
   const unsigned short* q = (const unsigned short*)qkv;
   unsigned short* o = (unsigned short*)out;
   switch (cdiv(S, 32)) {
-    case 1: launch_head<1>(q, o, B, S, H, causal, st, lse); break;
-    case 2: launch_head<2>(q, o, B, S, H, causal, st, lse); break;
-    case 3: launch_head<3>(q, o, B, S, H, causal, st, lse); break;
-    case 4: launch_head<4>(q, o, B, S, H, causal, st, lse); break;
-    case 5: launch_head<5>(q, o, B, S, H, causal, st, lse); break;
-    case 6: launch_head<6>(q, o, B, S, H, causal, st, lse); break;
-    case 7: launch_head<7>(q, o, B, S, H, causal, st, lse); break;
-    case 8: launch_head<8>(q, o, B, S, H, causal, st, lse); break;
-    default: launch_head<9>(q, o, B, S, H, causal, st, lse); break;
+    case 1: launch_head<Bf16T, 1>(q, o, B, S, H, causal, st, lse); break;
+    case 2: launch_head<Bf16T, 2>(q, o, B, S, H, causal, st, lse); break;
+    case 3: launch_head<Bf16T, 3>(q, o, B, S, H, causal, st, lse); break;
+    case 4: launch_head<Bf16T, 4>(q, o, B, S, H, causal, st, lse); break;
+    case 5: launch_head<Bf16T, 5>(q, o, B, S, H, causal, st, lse); break;
+    case 6: launch_head<Bf16T, 6>(q, o, B, S, H, causal, st, lse); break;
+    case 7: launch_head<Bf16T, 7>(q, o, B, S, H, causal, st, lse); break;
+    case 8: launch_head<Bf16T, 8>(q, o, B, S, H, causal, st, lse); break;
+    default: launch_head<Bf16T, 9>(q, o, B, S, H, causal, st, lse); break;
   }
   DCLIP_CHECK_LAUNCH("attention_fwd_bf16_lse");
   return DCLIP_OK;
@@ -770,10 +789,12 @@ DCLIP_API int dclip_attention_bwd_bf16(const void* qkv, const void* out, const v
   return DCLIP_OK;
 }
 
-DCLIP_API int dclip_attention_fwd_bf16(const void* qkv, void* out, int B, int S, int H, int causal, void* stream) {
-  DCLIP_REQUIRE(qkv && out, "attention_fwd_bf16: null pointer");
-  DCLIP_REQUIRE(B > 0 && S > 0 && H > 0, "attention_fwd_bf16: bad shape B=%d S=%d H=%d", B, S, H);
-  DCLIP_REQUIRE(((uintptr_t)qkv | (uintptr_t)out) % 16 == 0, "attention_fwd_bf16: 16-byte alignment");
+namespace {
+template <class T>
+int attention_fwd16(const char* name, const void* qkv, void* out, int B, int S, int H, int causal, void* stream) {
+  DCLIP_REQUIRE(qkv && out, "%s: null pointer", name);
+  DCLIP_REQUIRE(B > 0 && S > 0 && H > 0, "%s: bad shape B=%d S=%d H=%d", name, B, S, H);
+  DCLIP_REQUIRE(((uintptr_t)qkv | (uintptr_t)out) % 16 == 0, "%s: 16-byte alignment", name);
   hipStream_t st = (hipStream_t)stream;
   static const bool tiled_only = getenv("DCLIP_ATTN16_TILED") && atoi(getenv("DCLIP_ATTN16_TILED")) != 0;   // A/B switch
   if (S <= 288 && !tiled_only) {                    // whole-head kernel: every CLIP tower (50 / 77 / 197 / 257 tokens)
@@ -781,27 +802,38 @@ DCLIP_API int dclip_attention_fwd_bf16(const void* qkv, void* out, int B, int S,
     unsigned short* o = (unsigned short*)out;
     static const bool no_xq = getenv("DCLIP_ATTN16_NO_XQ") && atoi(getenv("DCLIP_ATTN16_NO_XQ")) != 0;   // A/B switch
     if (S == 257 && !causal && !no_xq) {            // 8 waves sharing the 257th query: two workgroups per CU instead of one
-      hipLaunchKernelGGL((attn_fwd_bf16_head_kernel<8, false, true>), dim3(B * H), dim3(512), 0, st, q, o, S, H);
-      DCLIP_CHECK_LAUNCH("attention_fwd_bf16.head_xq");
+      hipLaunchKernelGGL((attn_fwd_bf16_head_kernel<T, 8, false, true>), dim3(B * H), dim3(512), 0, st, q, o, S, H);
+      DCLIP_CHECK_LAUNCH(name);
       return DCLIP_OK;
     }
     switch (cdiv(S, 32)) {
-      case 1: launch_head<1>(q, o, B, S, H, causal, st); break;
-      case 2: launch_head<2>(q, o, B, S, H, causal, st); break;
-      case 3: launch_head<3>(q, o, B, S, H, causal, st); break;
-      case 4: launch_head<4>(q, o, B, S, H, causal, st); break;
-      case 5: launch_head<5>(q, o, B, S, H, causal, st); break;
-      case 6: launch_head<6>(q, o, B, S, H, causal, st); break;
-      case 7: launch_head<7>(q, o, B, S, H, causal, st); break;
-      case 8: launch_head<8>(q, o, B, S, H, causal, st); break;
-      default: launch_head<9>(q, o, B, S, H, causal, st); break;
+      case 1: launch_head<T, 1>(q, o, B, S, H, causal, st); break;
+      case 2: launch_head<T, 2>(q, o, B, S, H, causal, st); break;
+      case 3: launch_head<T, 3>(q, o, B, S, H, causal, st); break;
+      case 4: launch_head<T, 4>(q, o, B, S, H, causal, st); break;
+      case 5: launch_head<T, 5>(q, o, B, S, H, causal, st); break;
+      case 6: launch_head<T, 6>(q, o, B, S, H, causal, st); break;
+      case 7: launch_head<T, 7>(q, o, B, S, H, causal, st); break;
+      case 8: launch_head<T, 8>(q, o, B, S, H, causal, st); break;
+      default: launch_head<T, 9>(q, o, B, S, H, causal, st); break;
     }
-    DCLIP_CHECK_LAUNCH("attention_fwd_bf16.head");
+    DCLIP_CHECK_LAUNCH(name);
     return DCLIP_OK;
   }
   dim3 grid(B * H, cdiv(S, 64)), block(128);
-  if (causal) hipLaunchKernelGGL((attn_fwd_bf16_kernel<true>), grid, block, 0, st, (const unsigned short*)qkv, (unsigned short*)out, S, H);
-  else hipLaunchKernelGGL((attn_fwd_bf16_kernel<false>), grid, block, 0, st, (const unsigned short*)qkv, (unsigned short*)out, S, H);
-  DCLIP_CHECK_LAUNCH("attention_fwd_bf16");
+  if (causal) hipLaunchKernelGGL((attn_fwd_bf16_kernel<T, true>), grid, block, 0, st, (const unsigned short*)qkv, (unsigned short*)out, S, H);
+  else hipLaunchKernelGGL((attn_fwd_bf16_kernel<T, false>), grid, block, 0, st, (const unsigned short*)qkv, (unsigned short*)out, S, H);
+  DCLIP_CHECK_LAUNCH(name);
   return DCLIP_OK;
+}
+}  // namespace
+
+DCLIP_API int dclip_attention_fwd_bf16(const void* qkv, void* out, int B, int S, int H, int causal, void* stream) {
+  return attention_fwd16<Bf16T>("attention_fwd_bf16", qkv, out, B, S, H, causal, stream);
+}
+
+// fp16 q / k / v in, fp16 context out; same kernels, limits and A/B switches as the bf16 entry.  P is rounded to fp16 for
+// the P V product.
+DCLIP_API int dclip_attention_fwd_f16(const void* qkv, void* out, int B, int S, int H, int causal, void* stream) {
+  return attention_fwd16<F16T>("attention_fwd_f16", qkv, out, B, S, H, causal, stream);
 }

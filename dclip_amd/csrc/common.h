@@ -77,3 +77,53 @@ __device__ __forceinline__ float quick_gelu_grad_f(float x) {
   float s = __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x));
   return s * (1.0f + 1.702f * x * (1.0f - s));
 }
+
+// ---- 16-bit element types of the frozen-tower forward.  The 16-bit kernels are templates over one of these traits; loads,
+// LDS layouts, the transposing LDS read and the MFMA C/D layouts do not depend on the type, only the MFMA instruction and
+// the fp32 -> 16-bit rounding do.
+//   Bf16T: round to nearest even (v_cvt_pk_bf16_f32); bf16 has fp32's range, NaN stays NaN.
+//   F16T:  round to nearest even; a FINITE value beyond +-65504 saturates to +-65504 (a frozen forward degrades instead of
+//          turning an embedding into NaN), +-inf stays +-inf and NaN stays NaN (no fminf / fmaxf clamp: those return the
+//          other operand for a NaN, and the meta-teacher's NaN guards must see what the bf16 path would give them).
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+
+struct Bf16T {
+  typedef __bf16 elem;
+  typedef bf16x8_t x8;
+  // rounding of a value that is a probability (attention's P, in [0, 1] or NaN): no range handling needed
+  static __device__ __forceinline__ elem cvt_unit(float x) { return (__bf16)x; }
+  static __device__ __forceinline__ unsigned short bits(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
+  static __device__ __forceinline__ float to_f32(unsigned int h) { return __builtin_bit_cast(float, h << 16); }
+  // the element in the low / high half of a dword
+  static __device__ __forceinline__ float lo_f32(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
+  static __device__ __forceinline__ float hi_f32(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
+  static __device__ __forceinline__ f32x16 mfma32(x8 a, x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ f32x4 mfma16(x8 a, x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+};
+
+struct F16T {
+  typedef _Float16 elem;
+  typedef f16x8_t x8;
+  static __device__ __forceinline__ elem cvt_unit(float x) { return (_Float16)x; }
+  static __device__ __forceinline__ unsigned short bits(float x) {
+    const float a = __builtin_fabsf(x);
+    const float s = (a > 65504.f && a != __builtin_inff()) ? __builtin_copysignf(65504.f, x) : x;   // false for NaN
+    return __builtin_bit_cast(unsigned short, (_Float16)s);
+  }
+  static __device__ __forceinline__ float to_f32(unsigned int h) {
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
+  }
+  static __device__ __forceinline__ float lo_f32(unsigned int w) { return to_f32(w & 0xffffu); }
+  static __device__ __forceinline__ float hi_f32(unsigned int w) { return to_f32(w >> 16); }
+  static __device__ __forceinline__ f32x16 mfma32(x8 a, x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ f32x4 mfma16(x8 a, x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+  }
+};

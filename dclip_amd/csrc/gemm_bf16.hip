@@ -7,12 +7,16 @@
 // = the same 128-byte rows: a lane (row = lane&31, half = lane>>5) reads 16-byte slot 2s+half and holds
 // k = 16s + 8*half + {0..7}, exactly one MFMA operand per ds_read_b128.  At 16x the fp32 MFMA rate the kernel is
 // bounded by L2 -> LDS traffic (64 KB per 512 MFMA cycles per workgroup), not by the matrix pipes.
+//
+// fp16: every kernel of the FORWARD plan is a template over the 16-bit type (common.h, Bf16T / F16T) and has an fp16
+// instance, reached through dclip_gemm_f16 / dclip_cast_f32_f16 / dclip_layernorm_fwd_f16.  Only the MFMA
+// (v_mfma_f32_{32x32x16,16x16x32}_f16) and the rounding differ; the training forms (split-K, token-major weight gradient,
+// DGELU, saved pre-activation) are bf16 only.
 #include "common.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -35,18 +39,14 @@ struct GemmBf16Params {
   float* slab;           // split-K partials [split][M][N] fp32 (raw accumulators), or nullptr
 };
 
-// 4 consecutive bf16 at p (8-byte aligned) -> 4 floats
-__device__ __forceinline__ f32x4 load_bf16x4(const unsigned short* p) {
+// 4 consecutive 16-bit values at p (8-byte aligned) -> 4 floats
+template <class T>
+__device__ __forceinline__ f32x4 load16x4(const unsigned short* p) {
   const u16x4 b = *reinterpret_cast<const u16x4*>(p);
   f32x4 v;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = __builtin_bit_cast(float, (unsigned int)b[e] << 16);
+  for (int e = 0; e < 4; ++e) v[e] = T::to_f32(b[e]);
   return v;
-}
-
-__device__ __forceinline__ unsigned short f32_to_bf16_bits(float x) {
-  __bf16 b = (__bf16)x;  // v_cvt_pk_bf16_f32: round-to-nearest-even, NaN stays NaN
-  return __builtin_bit_cast(unsigned short, b);
 }
 
 // Diagnostic build only (`make stamps`, never the product library): per-workgroup shader-clock stamps of the ping-pong
@@ -73,8 +73,9 @@ __device__ __forceinline__ int xcd_remap16(int bid, int nwg) {
   return base + i;
 }
 
-template <int BM, int BN>
+template <class T, int BM, int BN>
 __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
+  typedef typename T::x8 V8;
   constexpr int WM = 2, WN = 2;
   constexpr int TM = BM / WM, TN = BN / WN;
   constexpr int MT = TM / 32, NT = TN / 32;
@@ -166,16 +167,16 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
       *reinterpret_cast<u32x4*>(Bs + buf * BN * ROW + row * ROW + ((slot ^ ((row >> 1) & 7)) << 3)) = v;
     }
   };
-  auto read_frags = [&](const __bf16* a, const __bf16* b, int s, bf16x8 (&fa)[MT], bf16x8 (&fb)[NT]) {
+  auto read_frags = [&](const __bf16* a, const __bf16* b, int s, V8 (&fa)[MT], V8 (&fb)[NT]) {
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       const int row = wm * TM + i * 32 + l31;
-      fa[i] = *reinterpret_cast<const bf16x8*>(a + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
+      fa[i] = *reinterpret_cast<const V8*>(a + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
     }
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int row = wn * TN + j * 32 + l31;
-      fb[j] = *reinterpret_cast<const bf16x8*>(b + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
+      fb[j] = *reinterpret_cast<const V8*>(b + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
     }
   };
   // One K-tile: 4 k-steps of MT*NT MFMAs; with `stage`, the next tile's loads go out first and its LDS writes are
@@ -184,7 +185,7 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
     const __bf16* a = As + buf * BM * ROW;
     const __bf16* b = Bs + buf * BN * ROW;
     constexpr int NCH = A_CHUNKS + B_CHUNKS;
-    bf16x8 fa[2][MT], fb[2][NT];
+    V8 fa[2][MT], fb[2][NT];
     read_frags(a, b, 0, fa[0], fb[0]);
     __builtin_amdgcn_sched_barrier(0);
     if (stage) load_tile(kt + 1);
@@ -196,7 +197,7 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s & 1][i], fb[s & 1][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = T::mfma32(fa[s & 1][i], fb[s & 1][j], acc[i][j]);
       if (stage && s >= 1) {  // a third of the chunks goes out behind each of k-steps 1..3
         const int lo = NCH * (s - 1) / 3, hi = (s == 3) ? NCH : NCH * s / 3;
 #pragma unroll
@@ -244,22 +245,22 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
     const size_t off = (size_t)row * p.ldc + col;
     if (p.epilogue & DCLIP_EPI_GELU) {
       if (p.aux) {
-        u16x4 h = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
+        u16x4 h = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
         *reinterpret_cast<u16x4*>(p.aux + off) = h;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = __builtin_bit_cast(float, (unsigned int)h[e] << 16);   // gelu of what was saved
+        for (int e = 0; e < 4; ++e) v[e] = T::to_f32(h[e]);   // gelu of what was saved
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
     }
     if (p.epilogue & DCLIP_EPI_DGELU) {
-      const f32x4 h = load_bf16x4(p.aux + off);
+      const f32x4 h = load16x4<T>(p.aux + off);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(h[e]);
     }
     if (p.epilogue & DCLIP_EPI_RESIDUAL) v += *reinterpret_cast<const f32x4*>(p.residual + off);
     if (p.out_bf16) {
-      u16x4 o = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
+      u16x4 o = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
       *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned short*>(p.C) + off) = o;
     } else {
       *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + off) = v;
@@ -286,8 +287,9 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, __bf16* lds_d
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
 }
 
-template <int BM, int BN, int WM, int WN>
+template <class T, int BM, int BN, int WM, int WN>
 __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Params p) {
+  typedef typename T::x8 V8;
   constexpr int NW = WM * WN, NTHR = NW * 64;
   constexpr int TM = BM / WM, TN = BN / WN, MT = TM / 32, NT = TN / 32;
   constexpr int ROW = BKH;
@@ -350,16 +352,16 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  auto read_frags = [&](const __bf16* a, const __bf16* b, int s, bf16x8 (&fa)[MT], bf16x8 (&fb)[NT]) {
+  auto read_frags = [&](const __bf16* a, const __bf16* b, int s, V8 (&fa)[MT], V8 (&fb)[NT]) {
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       const int row = wm * TM + i * 32 + l31;
-      fa[i] = *reinterpret_cast<const bf16x8*>(a + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
+      fa[i] = *reinterpret_cast<const V8*>(a + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
     }
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int row = wn * TN + j * 32 + l31;
-      fb[j] = *reinterpret_cast<const bf16x8*>(b + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
+      fb[j] = *reinterpret_cast<const V8*>(b + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
     }
   };
 
@@ -372,7 +374,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
     const bool more = kt + 1 < nk;
     const __bf16* a = lds + buf * STAGE;
     const __bf16* b = a + BM * ROW;
-    bf16x8 fa[2][MT], fb[2][NT];
+    V8 fa[2][MT], fb[2][NT];
     read_frags(a, b, 0, fa[0], fb[0]);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -384,7 +386,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
       for (int i = 0; i < MT; ++i) {
 #pragma unroll
         for (int j = 0; j < NT; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s & 1][i], fb[s & 1][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = T::mfma32(fa[s & 1][i], fb[s & 1][j], acc[i][j]);
         if (i == MT / 2 - 1 || i == MT - 1) {
           __builtin_amdgcn_sched_barrier(0);
           if (more) issue_piece(buf ^ 1, kt + 1, 2 * s + (i == MT - 1 ? 1 : 0));
@@ -426,22 +428,22 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
       const size_t off = (size_t)row * p.ldc + col;
       if (p.epilogue & DCLIP_EPI_GELU) {
         if (p.aux) {
-          u16x4 h = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
+          u16x4 h = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
           *reinterpret_cast<u16x4*>(p.aux + off) = h;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = __builtin_bit_cast(float, (unsigned int)h[e] << 16);
+          for (int e = 0; e < 4; ++e) v[e] = T::to_f32(h[e]);
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
       }
       if (p.epilogue & DCLIP_EPI_DGELU) {
-        const f32x4 h = load_bf16x4(p.aux + off);
+        const f32x4 h = load16x4<T>(p.aux + off);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(h[e]);
       }
       if (p.epilogue & DCLIP_EPI_RESIDUAL) v += *reinterpret_cast<const f32x4*>(p.residual + off);
       if (p.out_bf16) {
-        u16x4 o = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
+        u16x4 o = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
         *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned short*>(p.C) + off) = o;
       } else {
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + off) = v;
@@ -451,11 +453,11 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
   }
 }
 
-template <int BM, int BN, int WM, int WN>
+template <class T, int BM, int BN, int WM, int WN>
 int launch_dma(GemmBf16Params p, hipStream_t st) {
   p.tiles_m = cdiv(p.M, BM);
   p.tiles_n = cdiv(p.N, BN);
-  hipLaunchKernelGGL((gemm_bf16_dma_kernel<BM, BN, WM, WN>), dim3(p.tiles_m * p.tiles_n), dim3(WM * WN * 64), 0, st, p);
+  hipLaunchKernelGGL((gemm_bf16_dma_kernel<T, BM, BN, WM, WN>), dim3(p.tiles_m * p.tiles_n), dim3(WM * WN * 64), 0, st, p);
   return DCLIP_OK;
 }
 
@@ -474,7 +476,7 @@ int launch_dma(GemmBf16Params p, hipStream_t st) {
 // KIND 0 bias only, 1 quick-GELU (pre-activation saved to aux when given), 2 x dGELU(aux), 3 + residual.
 // The MFMAs form C^T blocks (W fragment as the A operand): accumulator register r of block (i, j) is
 // C[row 16 i + l15][column 16 j + 4 quad + r] — four consecutive columns per lane, one ds_write_b128 per block.
-template <int KIND, bool OUT16>
+template <class T, int KIND, bool OUT16>
 __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4 (&acc)[8][4], float* ct, int m0, int n0,
                                             int tid, int wr, int wc, int quad, int l15) {
   constexpr int BN = 256;
@@ -515,22 +517,22 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
       const bool ok = row < p.M && colok;
       if (KIND == 1) {
         if (p.aux) {
-          u16x4 h = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
+          u16x4 h = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
           if (ok) *reinterpret_cast<u16x4*>(p.aux + off) = h;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = __builtin_bit_cast(float, (unsigned int)h[e] << 16);   // gelu of what was saved
+          for (int e = 0; e < 4; ++e) v[e] = T::to_f32(h[e]);   // gelu of what was saved
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
       }
       if (KIND == 2) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(__builtin_bit_cast(float, (unsigned int)side16[q][e] << 16));
+        for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(T::to_f32(side16[q][e]));
       }
       if (KIND == 3) v += side[q];
       if (!ok) continue;
       if (OUT16) {
-        u16x4 o = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
+        u16x4 o = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
         *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned short*>(p.C) + off) = o;
       } else {
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + off) = v;
@@ -557,7 +559,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
 // 8-byte unit u of row r is stored at u ^ (r & 15): the 16 rows of a ds_write_b64 lane group cover 32 banks.
 // SAVE: the staged value is the pre-activation h (written to aux); C = bf16(gelu(h)) is formed in the copy loop from the
 // rounded h, as in the two-pass form.
-template <bool GELU, bool SAVE>
+template <class T, bool GELU, bool SAVE>
 __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f32x4 (&acc)[8][4], unsigned short* ct, int m0,
                                                 int n0, int tid, int wr, int wc, int quad, int l15) {
   constexpr int BN = 256;
@@ -578,7 +580,7 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
         }
-        const u16x4 h = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
+        const u16x4 h = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
         const int row = 128 * wr + 16 * i + l15, unit = 16 * wc + 4 * j + quad;
         *reinterpret_cast<u16x4*>(ct + row * BN + ((unit ^ (row & 15)) << 2)) = h;
       }
@@ -601,7 +603,7 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
       if (full) *reinterpret_cast<u16x8*>(p.aux + off) = o;
       else *reinterpret_cast<u16x4*>(p.aux + off) = lo;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = f32_to_bf16_bits(quick_gelu_f(__builtin_bit_cast(float, (unsigned int)o[e] << 16)));
+      for (int e = 0; e < 8; ++e) o[e] = T::bits(quick_gelu_f(T::to_f32(o[e])));
     }
     unsigned short* c = reinterpret_cast<unsigned short*>(p.C) + off;
     if (full) *reinterpret_cast<u16x8*>(c) = o;
@@ -644,8 +646,9 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 // two lane groups of a half-wave (k-rows 8 apart) land on 32 different 8-byte bank pairs.  Same phases and barriers; the
 // DMA order is A1(kt+1) | - | A0(kt+2) | B0, B1(kt+2) (every half re-staged at least two phases after its last read, so
 // no lgkmcnt before a barrier is needed: phase 1 issues 24 reads, more than the 4-bit counter can express).
-template <bool TOK>
+template <class T, bool TOK>
 __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
+  typedef typename T::x8 V8;
   constexpr int BM = 256, BN = 256, ROW = BKH;
   constexpr int BUF = (BM + BN) * ROW;   // bf16 elements per K-tile buffer: 256 A rows then 256 B rows of 128 bytes
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[2 * BUF * 2];   // 128 KiB: the ONLY LDS object
@@ -753,7 +756,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
     typedef short s16x8_t __attribute__((ext_vector_type(8)));
     const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(lds8 + byte_off));
     const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(lds8 + byte_off + 1024));
-    return __builtin_bit_cast(bf16x8, s16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+    return __builtin_bit_cast(V8, s16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
   };
 
   f32x4 acc[8][4];
@@ -761,7 +764,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 fa[4][2], fb0[2][2], fb1[2][2];
+  V8 fa[4][2], fb0[2][2], fb1[2][2];
 
 #define PP_READ_A(qm, off)                                                                          \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                   \
@@ -769,8 +772,8 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
       fa[i][0] = tr8((off) * 2 + (qm) * (HALF * 2) + ta[i]);                                        \
       fa[i][1] = tr8((off) * 2 + (qm) * (HALF * 2) + ta[i] + 32 * 256);                             \
     } else {                                                                                        \
-      fa[i][0] = *reinterpret_cast<const bf16x8*>(pa0 + (off) + (64 * (qm) + 16 * i) * ROW);        \
-      fa[i][1] = *reinterpret_cast<const bf16x8*>(pa1 + (off) + (64 * (qm) + 16 * i) * ROW);        \
+      fa[i][0] = *reinterpret_cast<const V8*>(pa0 + (off) + (64 * (qm) + 16 * i) * ROW);        \
+      fa[i][1] = *reinterpret_cast<const V8*>(pa1 + (off) + (64 * (qm) + 16 * i) * ROW);        \
     }                                                                                               \
   }
 #define PP_READ_B(fb, qn, off)                                                                      \
@@ -779,8 +782,8 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
       fb[j][0] = tr8((off) * 2 + (2 + (qn)) * (HALF * 2) + tb[j]);                                  \
       fb[j][1] = tr8((off) * 2 + (2 + (qn)) * (HALF * 2) + tb[j] + 32 * 256);                       \
     } else {                                                                                        \
-      fb[j][0] = *reinterpret_cast<const bf16x8*>(pb0 + (off) + (32 * (qn) + 16 * j) * ROW);        \
-      fb[j][1] = *reinterpret_cast<const bf16x8*>(pb1 + (off) + (32 * (qn) + 16 * j) * ROW);        \
+      fb[j][0] = *reinterpret_cast<const V8*>(pb0 + (off) + (32 * (qn) + 16 * j) * ROW);        \
+      fb[j][1] = *reinterpret_cast<const V8*>(pb1 + (off) + (32 * (qn) + 16 * j) * ROW);        \
     }                                                                                               \
   }
 #define PP_MFMA(qm, qn, fb)                                                                                         \
@@ -790,7 +793,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                   \
       acc[4 * (qm) + i][2 * (qn) + j] =                                                                             \
-          __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][s], fa[i][s], acc[4 * (qm) + i][2 * (qn) + j], 0, 0, 0);    \
+          T::mfma16(fb[j][s], fa[i][s], acc[4 * (qm) + i][2 * (qn) + j]);    \
     __builtin_amdgcn_s_setprio(0);                                                                                  \
   } while (0)
 
@@ -872,20 +875,20 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
     ps.C = p.slab + (size_t)blockIdx.y * p.M * p.N;
     ps.ldc = p.N;
     ps.epilogue = 0;
-    pp_epilogue<0, false>(ps, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    pp_epilogue<T, 0, false>(ps, acc, ct, m0, n0, tid, wr, wc, quad, l15);
     return;
   }
   if (p.out_bf16) {
     unsigned short* ct16 = reinterpret_cast<unsigned short*>(lds_raw);
-    if (kind == 0) pp_epilogue_b16<false, false>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
-    else if (kind == 1 && p.aux) pp_epilogue_b16<true, true>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
-    else if (kind == 1) pp_epilogue_b16<true, false>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
-    else pp_epilogue<2, true>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);          // RESIDUAL needs an fp32 output (host check)
+    if (kind == 0) pp_epilogue_b16<T, false, false>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 1 && p.aux) pp_epilogue_b16<T, true, true>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 1) pp_epilogue_b16<T, true, false>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
+    else pp_epilogue<T, 2, true>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);          // RESIDUAL needs an fp32 output (host check)
   } else {
-    if (kind == 0) pp_epilogue<0, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
-    else if (kind == 1) pp_epilogue<1, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
-    else if (kind == 2) pp_epilogue<2, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
-    else pp_epilogue<3, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    if (kind == 0) pp_epilogue<T, 0, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 1) pp_epilogue<T, 1, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 2) pp_epilogue<T, 2, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else pp_epilogue<T, 3, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
   }
 }
 #undef PP_BARRIER
@@ -921,7 +924,9 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
     __builtin_amdgcn_sched_barrier(0);    \
   } while (0)
 
+template <class T>
 __global__ void __launch_bounds__(512) gemm_bf16_ppp_kernel(GemmBf16Params p) {
+  typedef typename T::x8 V8;
   constexpr int BM = 256, BN = 256, ROW = BKH;
   constexpr int BUF = (BM + BN) * ROW;
   constexpr int WIN = 32768;                                                    // the epilogue's window
@@ -953,7 +958,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_ppp_kernel(GemmBf16Params p) {
   const __bf16* pb1 = lds + (BM + 64 * wc + l15) * ROW + (((4 + quad) ^ sw) << 3);
 
   f32x4 acc[8][4];
-  bf16x8 fa[4][2], fb0[2][2], fb1[2][2];
+  V8 fa[4][2], fb0[2][2], fb1[2][2];
   // the tile whose results sit in the accumulators (stored at the top of the next iteration)
   int pm0 = 0, pn0 = 0;
   bool pending = false;
@@ -972,13 +977,13 @@ __global__ void __launch_bounds__(512) gemm_bf16_ppp_kernel(GemmBf16Params p) {
   } while (0)
 #define PPP_READ_A(qm, off)                                                                         \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                   \
-    fa[i][0] = *reinterpret_cast<const bf16x8*>(pa0 + (off) + (64 * (qm) + 16 * i) * ROW);          \
-    fa[i][1] = *reinterpret_cast<const bf16x8*>(pa1 + (off) + (64 * (qm) + 16 * i) * ROW);          \
+    fa[i][0] = *reinterpret_cast<const V8*>(pa0 + (off) + (64 * (qm) + 16 * i) * ROW);          \
+    fa[i][1] = *reinterpret_cast<const V8*>(pa1 + (off) + (64 * (qm) + 16 * i) * ROW);          \
   }
 #define PPP_READ_B(fb, qn, off)                                                                     \
   _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                   \
-    fb[j][0] = *reinterpret_cast<const bf16x8*>(pb0 + (off) + (32 * (qn) + 16 * j) * ROW);          \
-    fb[j][1] = *reinterpret_cast<const bf16x8*>(pb1 + (off) + (32 * (qn) + 16 * j) * ROW);          \
+    fb[j][0] = *reinterpret_cast<const V8*>(pb0 + (off) + (32 * (qn) + 16 * j) * ROW);          \
+    fb[j][1] = *reinterpret_cast<const V8*>(pb1 + (off) + (32 * (qn) + 16 * j) * ROW);          \
   }
 #define PPP_MFMA(qm, qn, fb)                                                                                        \
   do {                                                                                                              \
@@ -987,13 +992,13 @@ __global__ void __launch_bounds__(512) gemm_bf16_ppp_kernel(GemmBf16Params p) {
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                   \
       acc[4 * (qm) + i][2 * (qn) + j] =                                                                             \
-          __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][s], fa[i][s], acc[4 * (qm) + i][2 * (qn) + j], 0, 0, 0);    \
+          T::mfma16(fb[j][s], fa[i][s], acc[4 * (qm) + i][2 * (qn) + j]);    \
     __builtin_amdgcn_s_setprio(0);                                                                                  \
   } while (0)
 
   // The finished tile (pm0, pn0) out of the accumulators through the window.  Block (i, j) of this wave = rows
   // 128 wr + 16 i + l15, columns 64 wc + 16 j + 4 quad .. +3 of the tile.
-  auto store_tile = [&](const f32x4 (&bias4)[4]) {
+  auto store_tile = [&](const f32x4 (&bias4)[4]) __attribute__((always_inline)) {
     const int rows_left = p.M - pm0;                                   // >= 1
     const int trows = min(rows_left, BM);
     const size_t org = (size_t)pm0 * p.ldc;
@@ -1020,7 +1025,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_ppp_kernel(GemmBf16Params p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
               }
-              const u16x4 h = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
+              const u16x4 h = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
               const int row = 16 * ii + l15, unit = 16 * wc + 4 * j + quad;
               *reinterpret_cast<u16x4*>(w16 + row * BN + ((unit ^ (row & 15)) << 2)) = h;
             }
@@ -1038,7 +1043,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_ppp_kernel(GemmBf16Params p) {
           if (save) {
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), x_rsrc, el * 2, 0, 0);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = f32_to_bf16_bits(quick_gelu_f(__builtin_bit_cast(float, (unsigned int)o[e] << 16)));
+            for (int e = 0; e < 8; ++e) o[e] = T::bits(quick_gelu_f(T::to_f32(o[e])));
           }
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), c_rsrc, el * 2, 0, 0);
         }
@@ -1231,20 +1236,21 @@ __global__ void __launch_bounds__(512) gemm_bf16_ppp_kernel(GemmBf16Params p) {
 // cached: tests and A/B runs switch it inside one process.
 bool persistent_enabled() { return getenv("DCLIP_BF16_PERSIST") && atoi(getenv("DCLIP_BF16_PERSIST")) != 0; }
 
+template <class T>
 int launch_ppp(GemmBf16Params p, hipStream_t st) {
   p.tiles_m = cdiv(p.M, 256);
   p.tiles_n = cdiv(p.N, 256);
   const int tiles = p.tiles_m * p.tiles_n;
   int grid = tiles < 256 ? ((tiles + 7) / 8) * 8 : 256;      // a multiple of 8: 32 (or fewer) workgroups per XCD
-  hipLaunchKernelGGL(gemm_bf16_ppp_kernel, dim3(grid), dim3(512), 0, st, p);
+  hipLaunchKernelGGL(gemm_bf16_ppp_kernel<T>, dim3(grid), dim3(512), 0, st, p);
   return DCLIP_OK;
 }
 
-int launch_pp(GemmBf16Params p, hipStream_t st, int splits = 1, bool tok_major = false) {
+template <class T, bool TOK = false>
+int launch_pp(GemmBf16Params p, hipStream_t st, int splits = 1) {
   p.tiles_m = cdiv(p.M, 256);
   p.tiles_n = cdiv(p.N, 256);
-  if (tok_major) hipLaunchKernelGGL(gemm_bf16_pp_kernel<true>, dim3(p.tiles_m * p.tiles_n, splits), dim3(512), 0, st, p);
-  else hipLaunchKernelGGL(gemm_bf16_pp_kernel<false>, dim3(p.tiles_m * p.tiles_n, splits), dim3(512), 0, st, p);
+  hipLaunchKernelGGL((gemm_bf16_pp_kernel<T, TOK>), dim3(p.tiles_m * p.tiles_n, splits), dim3(512), 0, st, p);
   return DCLIP_OK;
 }
 
@@ -1255,6 +1261,7 @@ bool pingpong_enabled() {
 }
 
 // y[i] = bf16(x[i]); rows of `cols` floats written with leading dimension ldy (>= cols, zero padded)
+template <class T>
 __global__ void __launch_bounds__(256) cast_bf16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, int rows,
                                                         int cols, int ldx, int ldy) {
   const int ld4 = ldy >> 2;
@@ -1265,17 +1272,17 @@ __global__ void __launch_bounds__(256) cast_bf16_kernel(const float* __restrict_
     u16x4 o = {0, 0, 0, 0};
     if (c + 3 < cols) {
       f32x4 v = *reinterpret_cast<const f32x4*>(x + r * ldx + c);
-      o = u16x4{f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
+      o = u16x4{T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
     } else {
       for (int e = 0; e < 4; ++e)
-        if (c + e < cols) o[e] = f32_to_bf16_bits(x[r * ldx + c + e]);
+        if (c + e < cols) o[e] = T::bits(x[r * ldx + c + e]);
     }
     *reinterpret_cast<u16x4*>(y + r * ldy + c) = o;
   }
 }
 
 // LayerNorm with bf16 output (fp32 statistics and affine): one wave per row
-template <int NC, bool EXACT>   // EXACT: D == 256 NC, no per-chunk bounds tests; loads hoisted into one group (see layernorm.hip)
+template <class T, int NC, bool EXACT>   // EXACT: D == 256 NC, no per-chunk bounds tests; loads hoisted into one group (see layernorm.hip)
 __global__ void __launch_bounds__(256) ln_fwd_bf16_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, unsigned short* __restrict__ y,
                                                           int rows, int D, float eps, float* __restrict__ mean_out,
@@ -1318,7 +1325,7 @@ __global__ void __launch_bounds__(256) ln_fwd_bf16_kernel(const float* __restric
     const int i = lane + 64 * c;
     if (EXACT || i < d4) {
       f32x4 o = (v[c] - mu) * rs * g[c] + bt[c];
-      u16x4 b = {f32_to_bf16_bits(o[0]), f32_to_bf16_bits(o[1]), f32_to_bf16_bits(o[2]), f32_to_bf16_bits(o[3])};
+      u16x4 b = {T::bits(o[0]), T::bits(o[1]), T::bits(o[2]), T::bits(o[3])};
       *reinterpret_cast<u16x4*>(y + (size_t)row * D + i * 4) = b;
     }
   }
@@ -1355,19 +1362,24 @@ DCLIP_API int dclip_gemm_bf16(const void* A, const void* W, void* C, const float
   return dclip_gemm_bf16_ex(A, W, C, bias, residual, nullptr, M, N, K, lda, ldw, ldc, epilogue, out_bf16, stream);
 }
 
-DCLIP_API int dclip_gemm_bf16_ex(const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux,
-                                 int M, int N, int K, int lda, int ldw, int ldc, int epilogue, int out_bf16, void* stream) {
-  DCLIP_REQUIRE(A && W && C, "gemm_bf16: null operand");
-  DCLIP_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_bf16: bad shape M=%d N=%d K=%d", M, N, K);
-  DCLIP_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "gemm_bf16: lda/ldw must be multiples of 8 and >= K");
-  DCLIP_REQUIRE(N % 4 == 0 && ldc % 4 == 0 && ldc >= N, "gemm_bf16: N / ldc must be multiples of 4");
-  DCLIP_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 == 0, "gemm_bf16: operands must be 16-byte aligned");
+namespace {
+// The forward dispatcher of both 16-bit types: same checks, same plan.  Every kernel it can pick — register-staged 128x128 /
+// 64x64, LDS-DMA 128x128 (DCLIP_BF16_MID_DMA) and 256x256 (DCLIP_BF16_PP=0), ping-pong, persistent (DCLIP_BF16_PERSIST) — has
+// an instance per type, and the DCLIP_BF16_* switches select among them for fp16 exactly as for bf16.
+template <class T>
+int gemm16(const char* name, const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux, int M,
+           int N, int K, int lda, int ldw, int ldc, int epilogue, int out_bf16, void* stream) {
+  DCLIP_REQUIRE(A && W && C, "%s: null operand", name);
+  DCLIP_REQUIRE(M > 0 && N > 0 && K > 0, "%s: bad shape M=%d N=%d K=%d", name, M, N, K);
+  DCLIP_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "%s: lda/ldw must be multiples of 8 and >= K", name);
+  DCLIP_REQUIRE(N % 4 == 0 && ldc % 4 == 0 && ldc >= N, "%s: N / ldc must be multiples of 4", name);
+  DCLIP_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 == 0, "%s: operands must be 16-byte aligned", name);
   DCLIP_REQUIRE(!(epilogue & ~(DCLIP_EPI_BIAS | DCLIP_EPI_GELU | DCLIP_EPI_DGELU | DCLIP_EPI_RESIDUAL)),
-                "gemm_bf16: unsupported epilogue bits");
-  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (aux && !(epilogue & DCLIP_EPI_GELU)), "gemm_bf16: DGELU needs aux (and no GELU)");
-  DCLIP_REQUIRE(!aux || (uintptr_t)aux % 8 == 0, "gemm_bf16: aux must be 8-byte aligned");
-  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_BIAS) || bias, "gemm_bf16: BIAS without bias");
-  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_RESIDUAL) || (residual && !out_bf16), "gemm_bf16: RESIDUAL needs an fp32 output");
+                "%s: unsupported epilogue bits", name);
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (aux && !(epilogue & DCLIP_EPI_GELU)), "%s: DGELU needs aux (and no GELU)", name);
+  DCLIP_REQUIRE(!aux || (uintptr_t)aux % 8 == 0, "%s: aux must be 8-byte aligned", name);
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_BIAS) || bias, "%s: BIAS without bias", name);
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_RESIDUAL) || (residual && !out_bf16), "%s: RESIDUAL needs an fp32 output", name);
   hipStream_t st = (hipStream_t)stream;
   // LDS-DMA kernel (K % 64 == 0, at least 128 workgroups): measured faster than the register-staged 128x128
   // kernel AND than a 128x128 LDS-DMA variant (two workgroups per CU) on every tower shape, short K included
@@ -1382,10 +1394,10 @@ DCLIP_API int dclip_gemm_bf16_ex(const void* A, const void* W, void* C, const fl
     const int persist_min = getenv("DCLIP_BF16_PERSIST_MIN") ? atoi(getenv("DCLIP_BF16_PERSIST_MIN")) : 512;
     const bool persist = pingpong_enabled() && persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && ldc % 8 == 0 && N % 8 == 0 &&
                          (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min;
-    if (persist) launch_ppp(pb, st);
-    else if (pingpong_enabled()) launch_pp(pb, st);
-    else launch_dma<256, 256, 2, 4>(pb, st);
-    DCLIP_CHECK_LAUNCH("gemm_bf16.dma");
+    if (persist) launch_ppp<T>(pb, st);
+    else if (pingpong_enabled()) launch_pp<T>(pb, st);
+    else launch_dma<T, 256, 256, 2, 4>(pb, st);
+    DCLIP_CHECK_LAUNCH(name);
     return DCLIP_OK;
   }
   // A/B aid: DCLIP_BF16_MID_DMA=1 sends what falls below the big-tile threshold (K % 64 == 0) to the 128x128 LDS-DMA kernel,
@@ -1394,8 +1406,8 @@ DCLIP_API int dclip_gemm_bf16_ex(const void* A, const void* W, void* C, const fl
   if (mid_dma && K % BKH == 0 && (long)cdiv(M, 128) * cdiv(N, 128) >= 256) {
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
                       (unsigned short*)aux, 0, nullptr};
-    launch_dma<128, 128, 2, 2>(pb, st);
-    DCLIP_CHECK_LAUNCH("gemm_bf16.dma128");
+    launch_dma<T, 128, 128, 2, 2>(pb, st);
+    DCLIP_CHECK_LAUNCH(name);
     return DCLIP_OK;
   }
   const bool small = (long)cdiv(M, 128) * cdiv(N, 128) < 256;  // fewer tiles than CUs: use the finer tile
@@ -1403,10 +1415,24 @@ DCLIP_API int dclip_gemm_bf16_ex(const void* A, const void* W, void* C, const fl
   GemmBf16Params p{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16,
                    cdiv(M, bm), cdiv(N, bn), (unsigned short*)aux, 0, nullptr};
   const size_t lds = (size_t)2 * (bm + bn) * BKH * 2;
-  if (small) hipLaunchKernelGGL((gemm_bf16_kernel<64, 64>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((gemm_bf16_kernel<128, 128>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
-  DCLIP_CHECK_LAUNCH("gemm_bf16");
+  if (small) hipLaunchKernelGGL((gemm_bf16_kernel<T, 64, 64>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
+  else hipLaunchKernelGGL((gemm_bf16_kernel<T, 128, 128>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
+  DCLIP_CHECK_LAUNCH(name);
   return DCLIP_OK;
+}
+}  // namespace
+
+DCLIP_API int dclip_gemm_bf16_ex(const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux,
+                                 int M, int N, int K, int lda, int ldw, int ldc, int epilogue, int out_bf16, void* stream) {
+  return gemm16<Bf16T>("gemm_bf16", A, W, C, bias, residual, aux, M, N, K, lda, ldw, ldc, epilogue, out_bf16, stream);
+}
+
+// fp16 forward of the frozen towers: dclip_gemm_bf16's arguments and limits, fp16 A / W / 16-bit C (rounding: common.h, F16T).
+// No saved pre-activation or DGELU (training-only epilogues): aux is not an argument.
+DCLIP_API int dclip_gemm_f16(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
+                             int lda, int ldw, int ldc, int epilogue, int out_f16, void* stream) {
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU), "gemm_f16: DGELU is a training epilogue (bf16 only)");
+  return gemm16<F16T>("gemm_f16", A, W, C, bias, residual, nullptr, M, N, K, lda, ldw, ldc, epilogue, out_f16, stream);
 }
 
 // dW[M = out][N = in] fp32 = dY^T X from the operands as the backward has them: dY [K = tokens][lddy >= M], X [K][ldx >= N],
@@ -1437,7 +1463,7 @@ DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor(const void* dY, const void* X, floa
   hipStream_t st = (hipStream_t)stream;
   if (s_eff == 1) {
     GemmBf16Params pb{(const __bf16*)dY, (const __bf16*)X, C, nullptr, nullptr, M, N, K, lddy, ldx, ldc, 0, 0, 0, 0, nullptr, 0, nullptr};
-    launch_pp(pb, st, 1, true);
+    launch_pp<Bf16T, true>(pb, st, 1);
     DCLIP_CHECK_LAUNCH("gemm_bf16_wgrad_tokmajor");
     return DCLIP_OK;
   }
@@ -1449,7 +1475,7 @@ DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor(const void* dY, const void* X, floa
   DCLIP_REQUIRE((uintptr_t)workspace % 16 == 0, "gemm_bf16_wgrad_tokmajor: workspace must be 16-byte aligned");
   GemmBf16Params pb{(const __bf16*)dY, (const __bf16*)X, C, nullptr, nullptr, M, N, K, lddy, ldx, ldc, 0, 0, 0, 0, nullptr, kps,
                     (float*)workspace};
-  launch_pp(pb, st, s_eff, true);
+  launch_pp<Bf16T, true>(pb, st, s_eff);
   DCLIP_CHECK_LAUNCH("gemm_bf16_wgrad_tokmajor");
   hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, st, (const float*)workspace, C, M,
                      N, ldc, s_eff);
@@ -1457,31 +1483,29 @@ DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor(const void* dY, const void* X, floa
   return DCLIP_OK;
 }
 
-DCLIP_API int dclip_cast_f32_bf16(const float* x, void* y, int rows, int cols, int ldx, int ldy, void* stream) {
-  DCLIP_REQUIRE(x && y && rows > 0 && cols > 0, "cast_f32_bf16: bad arguments");
-  DCLIP_REQUIRE(ldx >= cols && ldy >= cols && ldy % 4 == 0 && ldx % 4 == 0, "cast_f32_bf16: ldx/ldy must be multiples of 4");
-  DCLIP_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)y % 8 == 0, "cast_f32_bf16: alignment");
-  hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for((size_t)rows * (ldy / 4))), dim3(256), 0, (hipStream_t)stream, x,
+namespace {
+template <class T>
+int cast16(const char* name, const float* x, void* y, int rows, int cols, int ldx, int ldy, void* stream) {
+  DCLIP_REQUIRE(x && y && rows > 0 && cols > 0, "%s: bad arguments", name);
+  DCLIP_REQUIRE(ldx >= cols && ldy >= cols && ldy % 4 == 0 && ldx % 4 == 0, "%s: ldx/ldy must be multiples of 4", name);
+  DCLIP_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)y % 8 == 0, "%s: alignment", name);
+  hipLaunchKernelGGL(cast_bf16_kernel<T>, dim3(grid_for((size_t)rows * (ldy / 4))), dim3(256), 0, (hipStream_t)stream, x,
                      (unsigned short*)y, rows, cols, ldx, ldy);
-  DCLIP_CHECK_LAUNCH("cast_f32_bf16");
+  DCLIP_CHECK_LAUNCH(name);
   return DCLIP_OK;
 }
 
-DCLIP_API int dclip_layernorm_fwd_bf16(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,
-                                       float eps, void* stream) {
-  return dclip_layernorm_fwd_bf16_stats(x, gamma, beta, y, nullptr, nullptr, rows, D, eps, stream);
-}
-
-DCLIP_API int dclip_layernorm_fwd_bf16_stats(const float* x, const float* gamma, const float* beta, void* y, float* mean,
-                                             float* rstd, int rows, int D, float eps, void* stream) {
-  DCLIP_REQUIRE(x && gamma && beta && y, "layernorm_fwd_bf16: null pointer");
-  DCLIP_REQUIRE((mean == nullptr) == (rstd == nullptr), "layernorm_fwd_bf16: mean and rstd go together");
-  DCLIP_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 2048, "layernorm_fwd_bf16: bad D=%d", D);
+template <class T>
+int layernorm16(const char* name, const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                int rows, int D, float eps, void* stream) {
+  DCLIP_REQUIRE(x && gamma && beta && y, "%s: null pointer", name);
+  DCLIP_REQUIRE((mean == nullptr) == (rstd == nullptr), "%s: mean and rstd go together", name);
+  DCLIP_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 2048, "%s: bad D=%d", name, D);
   dim3 grid(cdiv(rows, 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
   const int nc = cdiv(D / 4, 64);
   unsigned short* yy = (unsigned short*)y;
-#define LN16(NC, EX) hipLaunchKernelGGL((ln_fwd_bf16_kernel<NC, EX>), grid, block, 0, st, x, gamma, beta, yy, rows, D, eps, mean, rstd)
+#define LN16(NC, EX) hipLaunchKernelGGL((ln_fwd_bf16_kernel<T, NC, EX>), grid, block, 0, st, x, gamma, beta, yy, rows, D, eps, mean, rstd)
   if (D == 512) LN16(2, true);
   else if (D == 768) LN16(3, true);
   else if (D == 1024) LN16(4, true);
@@ -1491,8 +1515,32 @@ DCLIP_API int dclip_layernorm_fwd_bf16_stats(const float* x, const float* gamma,
   else if (nc == 4) LN16(4, false);
   else LN16(8, false);
 #undef LN16
-  DCLIP_CHECK_LAUNCH("layernorm_fwd_bf16");
+  DCLIP_CHECK_LAUNCH(name);
   return DCLIP_OK;
+}
+}  // namespace
+
+DCLIP_API int dclip_cast_f32_bf16(const float* x, void* y, int rows, int cols, int ldx, int ldy, void* stream) {
+  return cast16<Bf16T>("cast_f32_bf16", x, y, rows, cols, ldx, ldy, stream);
+}
+
+DCLIP_API int dclip_cast_f32_f16(const float* x, void* y, int rows, int cols, int ldx, int ldy, void* stream) {
+  return cast16<F16T>("cast_f32_f16", x, y, rows, cols, ldx, ldy, stream);
+}
+
+DCLIP_API int dclip_layernorm_fwd_bf16(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,
+                                       float eps, void* stream) {
+  return dclip_layernorm_fwd_bf16_stats(x, gamma, beta, y, nullptr, nullptr, rows, D, eps, stream);
+}
+
+DCLIP_API int dclip_layernorm_fwd_bf16_stats(const float* x, const float* gamma, const float* beta, void* y, float* mean,
+                                             float* rstd, int rows, int D, float eps, void* stream) {
+  return layernorm16<Bf16T>("layernorm_fwd_bf16", x, gamma, beta, y, mean, rstd, rows, D, eps, stream);
+}
+
+DCLIP_API int dclip_layernorm_fwd_f16(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,
+                                      float eps, void* stream) {
+  return layernorm16<F16T>("layernorm_fwd_f16", x, gamma, beta, y, nullptr, nullptr, rows, D, eps, stream);
 }
 
 // Split-K form for products with few output tiles and a long contraction — the weight gradients of the bf16 training
@@ -1540,7 +1588,7 @@ DCLIP_API int dclip_gemm_bf16_splitk(const void* A, const void* W, float* C, int
   if (K % BKH == 0 && pingpong_enabled() && (long)cdiv(M, 256) * cdiv(N, 256) * s_eff >= 128) {
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, 0, nullptr, kps,
                       (float*)workspace};
-    launch_pp(pb, (hipStream_t)stream, s_eff);
+    launch_pp<Bf16T>(pb, (hipStream_t)stream, s_eff);
     DCLIP_CHECK_LAUNCH("gemm_bf16_splitk.pp");
     hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const float*)workspace, C, M, N, ldc, s_eff);
@@ -1551,7 +1599,7 @@ DCLIP_API int dclip_gemm_bf16_splitk(const void* A, const void* W, float* C, int
                    cdiv(M, 128), cdiv(N, 128), nullptr, kps, (float*)workspace};
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)2 * (128 + 128) * BKH * 2;
-  hipLaunchKernelGGL((gemm_bf16_kernel<128, 128>), dim3(p.tiles_m * p.tiles_n, s_eff), dim3(256), lds, st, p);
+  hipLaunchKernelGGL((gemm_bf16_kernel<Bf16T, 128, 128>), dim3(p.tiles_m * p.tiles_n, s_eff), dim3(256), lds, st, p);
   DCLIP_CHECK_LAUNCH("gemm_bf16_splitk");
   hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, st, (const float*)workspace, C,
                      M, N, ldc, s_eff);

@@ -289,12 +289,37 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
     return [grads[n] for n in names]
 
 
-# --------------------------------------------------------------------------------------------- frozen towers in bf16
+# --------------------------------------------------------------------------------------------- frozen towers in bf16 / fp16
 # Opt-in mixed precision for towers that never receive gradients (the teacher's region encoder, the frozen text
-# tower; BASELINE configs c3 / c5): GEMM inputs are bf16 (weights converted once, activations converted by the
-# producing kernel), accumulation, residual stream, LayerNorm statistics, softmax and biases stay fp32.
+# tower; BASELINE configs c3 / c5): GEMM inputs are bf16 or fp16 (weights converted once, activations converted by the
+# producing kernel), accumulation, residual stream, LayerNorm statistics, softmax and biases stay fp32.  The forward
+# functions below take the 16-bit type as `dtype` and reach the kernels of that type through _Ops16; the caller keeps one
+# weight cache per type (the cache keys do not name the type).
 
-def _w16(cache: dict, key: str, w: torch.Tensor) -> torch.Tensor:
+
+class _Ops16:
+    """The forward kernels of one 16-bit type (ops.*_bf16 or ops.*_f16)."""
+
+    def __init__(self, dtype, gemm, layernorm, attention, attention_row, cast, im2col):
+        self.dtype, self._gemm, self.layernorm, self.attention = dtype, gemm, layernorm, attention
+        self.attention_row, self.cast, self.im2col = attention_row, cast, im2col
+
+    def gemm(self, a, w, out16: bool = False, **kw):
+        """y = epilogue(a w^T), a 16-bit result with `out16`."""
+        if self.dtype == torch.bfloat16:
+            return self._gemm(a, w, out_bf16=out16, **kw)
+        return self._gemm(a, w, out_f16=out16, **kw)
+
+
+_OPS16 = {
+    torch.bfloat16: _Ops16(torch.bfloat16, ops.gemm_bf16, ops.layernorm_fwd_bf16, ops.attention_fwd_bf16,
+                           ops.attention_row_fwd_bf16, ops.cast_bf16, ops.im2col_bf16),
+    torch.float16: _Ops16(torch.float16, ops.gemm_f16, ops.layernorm_fwd_f16, ops.attention_fwd_f16,
+                          ops.attention_row_fwd_f16, ops.cast_f16, ops.im2col_f16),
+}
+
+
+def _w16(cache: dict, key: str, w: torch.Tensor, cast=ops.cast_bf16) -> torch.Tensor:
     """bf16 copy of a GEMM weight, PERSISTENT: entry = [tensor, version of `w` it was made from, data pointer of `w`].
     When the optimizer (or load_state_dict) has written `w` since — the version counter is shared with the Parameter a
     detached view came from — the copy is refreshed IN PLACE, so the buffer a captured HIP graph reads stays the one
@@ -303,51 +328,55 @@ def _w16(cache: dict, key: str, w: torch.Tensor) -> torch.Tensor:
     e = cache.get(key)
     src = w.detach().reshape(w.shape[0], -1)
     if e is None:
-        e = [ops.cast_bf16(src.contiguous()), w._version, w.data_ptr()]
+        e = [cast(src.contiguous()), w._version, w.data_ptr()]
         cache[key] = e
     elif e[1] != w._version or e[2] != w.data_ptr():
-        ops.cast_bf16(src.contiguous(), out=e[0])
+        cast(src.contiguous(), out=e[0])
         e[1], e[2] = w._version, w.data_ptr()
     return e[0]
 
 
-def _layer_fwd_bf16(x, p: LayerParams, c: dict, pre: str, B: int, S: int, H: int, causal: bool, eps: float):
-    ln1 = ops.layernorm_fwd_bf16(x, p.ln1_w, p.ln1_b, eps)
-    qkv = ops.gemm_bf16(ln1, _w16(c, pre + "qkv", p.qkv_w), bias=p.qkv_b, out_bf16=True)
-    attn = ops.attention_fwd_bf16(qkv, B, S, H, causal)       # bf16 q/k/v in, bf16 context out: no cast pass
-    x1 = ops.gemm_bf16(attn, _w16(c, pre + "out", p.out_w), bias=p.out_b, residual=x)
-    ln2 = ops.layernorm_fwd_bf16(x1, p.ln2_w, p.ln2_b, eps)
-    g = ops.gemm_bf16(ln2, _w16(c, pre + "fc1", p.fc1_w), bias=p.fc1_b, gelu=True, out_bf16=True)
-    return ops.gemm_bf16(g, _w16(c, pre + "fc2", p.fc2_w), bias=p.fc2_b, residual=x1)
+def _layer_fwd_bf16(x, p: LayerParams, c: dict, pre: str, B: int, S: int, H: int, causal: bool, eps: float,
+                    dtype=torch.bfloat16):
+    k = _OPS16[dtype]
+    ln1 = k.layernorm(x, p.ln1_w, p.ln1_b, eps)
+    qkv = k.gemm(ln1, _w16(c, pre + "qkv", p.qkv_w, k.cast), bias=p.qkv_b, out16=True)
+    attn = k.attention(qkv, B, S, H, causal)                  # 16-bit q/k/v in, 16-bit context out: no cast pass
+    x1 = k.gemm(attn, _w16(c, pre + "out", p.out_w, k.cast), bias=p.out_b, residual=x)
+    ln2 = k.layernorm(x1, p.ln2_w, p.ln2_b, eps)
+    g = k.gemm(ln2, _w16(c, pre + "fc1", p.fc1_w, k.cast), bias=p.fc1_b, gelu=True, out16=True)
+    return k.gemm(g, _w16(c, pre + "fc2", p.fc2_w, k.cast), bias=p.fc2_b, residual=x1)
 
 
-def vision_fwd_bf16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict) -> torch.Tensor:
-    """Frozen get_image_features with bf16 GEMM inputs; `cache` keeps the converted weights between calls."""
+def vision_fwd_bf16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16) -> torch.Tensor:
+    """Frozen get_image_features with 16-bit GEMM inputs (`dtype` bf16 or fp16); `cache` keeps the converted weights
+    between calls (one cache per dtype)."""
     v = cfg
+    k = _OPS16[dtype]
     B = pixel_values.shape[0]
     S, D, H = v.seq_len, v.hidden_size, v.num_attention_heads
-    cols = (ops.im2col_bf16(pixel_values, v.patch_size) if v.patch_size % 4 == 0        # one pass: gather + round
-            else ops.cast_bf16(ops.im2col(pixel_values, v.patch_size)))
-    patch = ops.gemm_bf16(cols, _w16(cache, "patch", p.patch_w), k=v.patch_dim)
+    cols = (k.im2col(pixel_values, v.patch_size) if v.patch_size % 4 == 0              # one pass: gather + round
+            else k.cast(ops.im2col(pixel_values, v.patch_size)))
+    patch = k.gemm(cols, _w16(cache, "patch", p.patch_w, k.cast), k=v.patch_dim)
     x, _, _ = ops.layernorm_fwd(ops.vision_assemble_fwd(patch, p.class_embedding, p.pos, B, S, D), p.pre_w, p.pre_b,
                                 v.layer_norm_eps, save_stats=False)
     for li, lp in enumerate(p.layers[:-1]):
-        x = _layer_fwd_bf16(x, lp, cache, f"v{li}.", B, S, H, False, v.layer_norm_eps)
+        x = _layer_fwd_bf16(x, lp, cache, f"v{li}.", B, S, H, False, v.layer_norm_eps, dtype)
     lp, pre = p.layers[-1], f"v{len(p.layers) - 1}."
     # last layer on the CLS rows only (see last_layer_fwd_cls)
-    ln1 = ops.layernorm_fwd_bf16(x, lp.ln1_w, lp.ln1_b, v.layer_norm_eps)
+    ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, v.layer_norm_eps)
     if S <= 512 and os.environ.get("DCLIP_BF16_ROW_ATTN", "1") != "0":
-        # q | k | v written as bf16 (half the bytes of the 2304-wide projection's output), one-row kernel on them
-        qkv = ops.gemm_bf16(ln1, _w16(cache, pre + "qkv", lp.qkv_w), bias=lp.qkv_b, out_bf16=True)
-        attn16 = ops.attention_row_fwd_bf16(qkv, None, B, S, H)
+        # q | k | v written as 16-bit (half the bytes of the 2304-wide projection's output), one-row kernel on them
+        qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b, out16=True)
+        attn16 = k.attention_row(qkv, None, B, S, H)
     else:
-        qkv = ops.gemm_bf16(ln1, _w16(cache, pre + "qkv", lp.qkv_w), bias=lp.qkv_b)
-        attn16 = ops.cast_bf16(ops.attention_cls_fwd(qkv, B, S, H)[0])
-    x1 = ops.gemm_bf16(attn16, _w16(cache, pre + "out", lp.out_w), bias=lp.out_b,
-                       residual=ops.gather_rows(x, None, B, S, D))
-    ln2 = ops.layernorm_fwd_bf16(x1, lp.ln2_w, lp.ln2_b, v.layer_norm_eps)
-    g = ops.gemm_bf16(ln2, _w16(cache, pre + "fc1", lp.fc1_w), bias=lp.fc1_b, gelu=True, out_bf16=True)
-    cls_tok = ops.gemm_bf16(g, _w16(cache, pre + "fc2", lp.fc2_w), bias=lp.fc2_b, residual=x1)
+        qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)
+        attn16 = k.cast(ops.attention_cls_fwd(qkv, B, S, H)[0])
+    x1 = k.gemm(attn16, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b,
+                residual=ops.gather_rows(x, None, B, S, D))
+    ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, v.layer_norm_eps)
+    g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+    cls_tok = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
     pooled, _, _ = ops.layernorm_fwd(cls_tok, p.post_w, p.post_b, v.layer_norm_eps, save_stats=False)
     return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)          # [B,D] x [P,D]: tiny, kept in exact fp32
 
@@ -882,46 +911,48 @@ def text_bwd(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool]):
     return [grads[n] for n in names]
 
 
-def _text_stack_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict, n_layers: int):
+def _text_stack_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict, n_layers: int, dtype=torch.bfloat16):
     t = cfg
     B, T = input_ids.shape
     x = ops.text_embed_fwd(input_ids, p.tok, p.pos)
     for li, lp in enumerate(p.layers[:n_layers]):
-        x = _layer_fwd_bf16(x, lp, cache, f"t{li}.", B, T, t.num_attention_heads, True, t.layer_norm_eps)
+        x = _layer_fwd_bf16(x, lp, cache, f"t{li}.", B, T, t.num_attention_heads, True, t.layer_norm_eps, dtype)
     return x
 
 
-def text_fwd_frozen_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict) -> torch.Tensor:
-    """text_fwd_frozen with bf16 GEMM inputs (see the bf16 note above vision_fwd_bf16)."""
+def text_fwd_frozen_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16) -> torch.Tensor:
+    """text_fwd_frozen with 16-bit GEMM inputs (see the note above vision_fwd_bf16)."""
     t = cfg
+    k = _OPS16[dtype]
     B, T = input_ids.shape
     D, H = t.hidden_size, t.num_attention_heads
     eos = ops.first_eos(input_ids, t.eos_token_id)
-    x = _text_stack_bf16(p, input_ids, cfg, cache, len(p.layers) - 1)
+    x = _text_stack_bf16(p, input_ids, cfg, cache, len(p.layers) - 1, dtype)
     lp, pre = p.layers[-1], f"t{len(p.layers) - 1}."
-    ln1 = ops.layernorm_fwd_bf16(x, lp.ln1_w, lp.ln1_b, t.layer_norm_eps)
+    ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, t.layer_norm_eps)
     if T <= 512 and os.environ.get("DCLIP_BF16_ROW_ATTN", "1") != "0":
-        qkv = ops.gemm_bf16(ln1, _w16(cache, pre + "qkv", lp.qkv_w), bias=lp.qkv_b, out_bf16=True)
-        attn16 = ops.attention_row_fwd_bf16(qkv, eos, B, T, H)
+        qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b, out16=True)
+        attn16 = k.attention_row(qkv, eos, B, T, H)
     else:
-        qkv = ops.gemm_bf16(ln1, _w16(cache, pre + "qkv", lp.qkv_w), bias=lp.qkv_b)
-        attn16 = ops.cast_bf16(ops.attention_row_fwd(qkv, eos, B, T, H))
-    x1 = ops.gemm_bf16(attn16, _w16(cache, pre + "out", lp.out_w), bias=lp.out_b,
-                       residual=ops.gather_rows(x, eos, B, T, D))
-    ln2 = ops.layernorm_fwd_bf16(x1, lp.ln2_w, lp.ln2_b, t.layer_norm_eps)
-    g = ops.gemm_bf16(ln2, _w16(cache, pre + "fc1", lp.fc1_w), bias=lp.fc1_b, gelu=True, out_bf16=True)
-    rows = ops.gemm_bf16(g, _w16(cache, pre + "fc2", lp.fc2_w), bias=lp.fc2_b, residual=x1)
+        qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)
+        attn16 = k.cast(ops.attention_row_fwd(qkv, eos, B, T, H))
+    x1 = k.gemm(attn16, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b,
+                residual=ops.gather_rows(x, eos, B, T, D))
+    ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, t.layer_norm_eps)
+    g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+    rows = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
     pooled, _, _ = ops.layernorm_fwd(rows, p.final_w, p.final_b, t.layer_norm_eps, save_stats=False)
     return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
 
 
-def text_token_level_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict):
-    """text_token_level with bf16 GEMM inputs; the token projection ([B*T,D] x [P,D]) runs in bf16 too."""
+def text_token_level_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16):
+    """text_token_level with 16-bit GEMM inputs; the token projection ([B*T,D] x [P,D]) runs in that type too."""
     t = cfg
+    k = _OPS16[dtype]
     B, T = input_ids.shape
-    x = _text_stack_bf16(p, input_ids, cfg, cache, len(p.layers))
-    ln = ops.layernorm_fwd_bf16(x, p.final_w, p.final_b, t.layer_norm_eps)
-    tokens = ops.gemm_bf16(ln, _w16(cache, "tproj", p.proj_w))
+    x = _text_stack_bf16(p, input_ids, cfg, cache, len(p.layers), dtype)
+    ln = k.layernorm(x, p.final_w, p.final_b, t.layer_norm_eps)
+    tokens = k.gemm(ln, _w16(cache, "tproj", p.proj_w, k.cast))
     eos = ops.first_eos(input_ids, t.eos_token_id)
     sentence = ops.gather_rows(tokens, eos, B, T, tokens.shape[1])
     return sentence, tokens, eos

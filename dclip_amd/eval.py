@@ -60,11 +60,26 @@ def calculate_retrieval_metrics(image_embeddings, caption_embeddings, image_ids:
             for d, r in (("t2i", t2i_ranks), ("i2t", i2t_ranks))}
 
 
+def encoders(model, precision: str = "fp32"):
+    """(image encoder, text encoder) of a CLIPImageDistillation (forward(image=)/forward(text=)) or a HipCLIPModel.
+    `precision` "bf16" / "fp16": the frozen 16-bit forward of the towers (HipCLIPModel.get_*_features; the student's
+    towers for a CLIPImageDistillation) — evaluation never needs gradients."""
+    if precision == "fp32":
+        enc_i = (lambda x: model(image=x)) if hasattr(model, "student") else (lambda x: model.get_image_features(pixel_values=x))
+        enc_t = (lambda x: model(text=x)) if hasattr(model, "student") else (lambda x: model.get_text_features(input_ids=x))
+        return enc_i, enc_t
+    if precision not in ("bf16", "fp16"):
+        raise ValueError(f"precision {precision!r}")
+    clip = model.student if hasattr(model, "student") else model
+    dev = next(clip.parameters()).device
+    return (lambda x: clip.get_image_features(pixel_values=x.to(dev), precision=precision),
+            lambda x: clip.get_text_features(input_ids=x.to(dev), precision=precision))
+
+
 @torch.no_grad()
-def evaluate_retrieval(model, pixel_batches, id_batches, image_ids, caption_image_ids):
-    """`model` is a CLIPImageDistillation (forward(image=)/forward(text=)) or a HipCLIPModel."""
-    enc_i = (lambda x: model(image=x)) if hasattr(model, "student") else (lambda x: model.get_image_features(pixel_values=x))
-    enc_t = (lambda x: model(text=x)) if hasattr(model, "student") else (lambda x: model.get_text_features(input_ids=x))
+def evaluate_retrieval(model, pixel_batches, id_batches, image_ids, caption_image_ids, precision: str = "fp32"):
+    """`model` is a CLIPImageDistillation (forward(image=)/forward(text=)) or a HipCLIPModel; `precision`: see encoders."""
+    enc_i, enc_t = encoders(model, precision)
     img = torch.cat([enc_i(b) for b in pixel_batches])
     cap = torch.cat([enc_t(b) for b in id_batches])
     return calculate_retrieval_metrics(img, cap, image_ids, caption_image_ids)
@@ -79,10 +94,12 @@ def zero_shot_ranks(image_features: torch.Tensor, class_text_features: torch.Ten
 
 
 @torch.no_grad()
-def evaluate_zero_shot(clip_model, image_batches, label_batches, class_input_ids, normalize_images: bool = True):
-    """top-1 / top-5 accuracy; images in [0,1] are normalised with CLIP mean/std as the reference does (:69-71)."""
+def evaluate_zero_shot(clip_model, image_batches, label_batches, class_input_ids, normalize_images: bool = True,
+                       precision: str = "fp32"):
+    """top-1 / top-5 accuracy; images in [0,1] are normalised with CLIP mean/std as the reference does (:69-71).
+    `precision`: that of the frozen towers' forward ("fp32", "bf16" or "fp16")."""
     dev = next(clip_model.parameters()).device
-    text = clip_model.get_text_features(input_ids=class_input_ids.to(dev))
+    text = clip_model.get_text_features(input_ids=class_input_ids.to(dev), precision=precision)
     mean = torch.tensor(CLIP_MEAN, device=dev).view(1, 3, 1, 1)
     std = torch.tensor(CLIP_STD, device=dev).view(1, 3, 1, 1)
     top1 = top5 = total = 0
@@ -90,7 +107,7 @@ def evaluate_zero_shot(clip_model, image_batches, label_batches, class_input_ids
         images = images.to(dev)
         if normalize_images:
             images = (images - mean) / std
-        ranks = zero_shot_ranks(clip_model.get_image_features(pixel_values=images), text, labels)
+        ranks = zero_shot_ranks(clip_model.get_image_features(pixel_values=images, precision=precision), text, labels)
         top1 += int((ranks == 0).sum())
         top5 += int((ranks < 5).sum())
         total += len(labels)

@@ -51,7 +51,7 @@ def _pixel_batch(arrs, device, size):
 @torch.no_grad()
 def evaluate_model(model_name: str, device, max_images: int = 1000, dataset_json: Optional[str] = None,
                    clip_model=None, clip_path: Optional[str] = None, checkpoint: Optional[str] = None,
-                   tokenizer: Optional[Callable] = None, batch_size: int = 64):
+                   tokenizer: Optional[Callable] = None, batch_size: int = 64, precision: str = "fp32"):
     from PIL import Image
     from .CLIP_image_distillation import CLIPImageDistillation, _as_hip_model
     print(f"\n=== Evaluating {model_name} Model ===")
@@ -75,11 +75,9 @@ def evaluate_model(model_name: str, device, max_images: int = 1000, dataset_json
             raise ValueError("--model custom needs --checkpoint")
         model = CLIPImageDistillation.load_from_checkpoint(checkpoint, map_location=device, clip_model=base,
                                                            clip_preprocess=ClipImagePreprocess(size), strict=False).to(device)
-        enc_i, enc_t = (lambda x: model(image=x)), (lambda x: model(text=x))
     else:
         model = base
-        enc_i = lambda x: model.get_image_features(pixel_values=x)
-        enc_t = lambda x: model.get_text_features(input_ids=x)
+    enc_i, enc_t = E.encoders(model, precision)     # precision: the frozen encoders' forward (fp32 / bf16 / fp16)
     model.eval()
 
     print("Processing images...")
@@ -135,6 +133,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--checkpoint", type=str, default=None, help="Path to custom model checkpoint")
     parser.add_argument("--dataset_json", type=str, required=True, help="flickr30k_test_karpathy.json (local path)")
     parser.add_argument("--clip_path", type=str, required=True, help="local directory with HF CLIP weights + tokenizer")
+    parser.add_argument("--precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
+                        help="arithmetic of the frozen encoders' forward (fp32: exact; bf16 / fp16: 16-bit GEMM inputs)")
     return parser
 
 
@@ -144,10 +144,11 @@ def main(argv=None, **kw):
     print(f"Using device: {device}")
     res = {}
     if args.model in ("base", "both"):
-        res["base"] = evaluate_model("base", device, args.max_images, args.dataset_json, clip_path=args.clip_path, **kw)
+        res["base"] = evaluate_model("base", device, args.max_images, args.dataset_json, clip_path=args.clip_path,
+                                     precision=args.precision, **kw)
     if args.model in ("custom", "both"):
         res["custom"] = evaluate_model("custom", device, args.max_images, args.dataset_json, clip_path=args.clip_path,
-                                       checkpoint=args.checkpoint, **kw)
+                                       checkpoint=args.checkpoint, precision=args.precision, **kw)
     if len(res) == 2:
         b, c = res["base"], res["custom"]
         print("\n=== Model Comparison ===")

@@ -909,6 +909,118 @@ def colsum_bf16(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     return out
 
 
+# ------------------------------------------------------------------------------------------- fp16 frozen-tower path
+# The bf16 forward wrappers above with fp16 tensors (include/dclip_hip.h, "fp16 forward path"): same shapes and limits,
+# rounding to nearest even with finite values beyond +-65504 saturated.  Forward only: no save_preact / dgelu_of / stats.
+
+def _f16(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not (t.is_cuda and t.dtype == torch.float16 and t.is_contiguous()):
+        raise ValueError(f"{name}: expected a contiguous float16 CUDA tensor")
+    return t
+
+
+def cast_f16(x: torch.Tensor, pad_to: int = 8, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[rows, cols] fp32 -> fp16, row length rounded up to `pad_to` (zero filled); `out`: refresh an existing copy in place."""
+    lib = _lib.load()
+    _f32(x, "x")
+    if x.dim() != 2:
+        raise ValueError("cast_f16: x must be 2-D")
+    rows, cols = x.shape
+    ld = (cols + pad_to - 1) // pad_to * pad_to
+    if out is not None:
+        if tuple(_f16(out, "out").shape) != (rows, ld):
+            raise ValueError(f"cast_f16: out shape {tuple(out.shape)} != {(rows, ld)}")
+        y = out
+    else:
+        y = torch.empty((rows, ld), dtype=torch.float16, device=x.device)
+    _lib.check(lib.dclip_cast_f32_f16(x.data_ptr(), y.data_ptr(), rows, cols, cols, ld, _stream()), "cast_f32_f16")
+    return y
+
+
+def layernorm_fwd_f16(x, gamma, beta, eps: float) -> torch.Tensor:
+    """nn.LayerNorm with fp32 statistics and an fp16 result."""
+    lib = _lib.load()
+    _f32(x, "x"), _f32(gamma, "gamma"), _f32(beta, "beta")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    y = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    _lib.check(lib.dclip_layernorm_fwd_f16(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), rows, D, float(eps),
+                                           _stream()), "layernorm_fwd_f16")
+    return y
+
+
+def im2col_f16(pixels: torch.Tensor, patch: int) -> torch.Tensor:
+    """im2col with an fp16 result (rows padded to a multiple of 8 columns, zero filled); patch % 4 == 0."""
+    lib = _lib.load()
+    _f32(pixels, "pixel_values")
+    B, Cc, Hh, Ww = pixels.shape
+    if Hh != Ww or Hh % patch or patch % 4:
+        raise ValueError(f"im2col_f16: image {Hh}x{Ww}, patch {patch}")
+    g, kdim = Hh // patch, Cc * patch * patch
+    ld = (kdim + 7) // 8 * 8
+    alloc = torch.zeros if ld != kdim else torch.empty
+    cols = alloc((B * g * g, ld), dtype=torch.float16, device=pixels.device)
+    _lib.check(lib.dclip_im2col_f16(pixels.data_ptr(), cols.data_ptr(), B, Cc, Hh, Ww, patch, ld, _stream()), "im2col_f16")
+    return cols
+
+
+def attention_fwd_f16(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool) -> torch.Tensor:
+    """qkv [B*S, 3*H*64] fp16 -> context [B*S, H*64] fp16 (frozen towers, forward only)."""
+    lib = _lib.load()
+    _f16(qkv, "qkv")
+    if tuple(qkv.shape) != (B * S, 3 * H * 64):
+        raise ValueError(f"attention_fwd_f16: qkv shape {tuple(qkv.shape)} != {(B * S, 3 * H * 64)}")
+    out = torch.empty((B * S, H * 64), dtype=torch.float16, device=qkv.device)
+    _lib.check(lib.dclip_attention_fwd_f16(qkv.data_ptr(), out.data_ptr(), B, S, H, int(causal), _stream()), "attention_fwd_f16")
+    return out
+
+
+def attention_row_fwd_f16(qkv: torch.Tensor, rows: Optional[torch.Tensor], B: int, S: int, H: int) -> torch.Tensor:
+    """attention_row_fwd_bf16 on an fp16 qkv: [B, H*64] fp16."""
+    lib = _lib.load()
+    _f16(qkv, "qkv")
+    if tuple(qkv.shape) != (B * S, 3 * H * 64):
+        raise ValueError(f"attention_row_fwd_f16: qkv shape {tuple(qkv.shape)} != {(B * S, 3 * H * 64)}")
+    if rows is not None and not (rows.is_cuda and rows.dtype == torch.int32 and rows.numel() == B and rows.is_contiguous()):
+        raise ValueError("attention_row_fwd_f16: rows must be a contiguous int32 CUDA tensor [B]")
+    out = torch.empty((B, H * 64), dtype=torch.float16, device=qkv.device)
+    _lib.check(lib.dclip_attention_row_fwd_f16(qkv.data_ptr(), None if rows is None else rows.data_ptr(), out.data_ptr(),
+                                               B, S, H, _stream()), "attention_row_fwd_f16")
+    return out
+
+
+def gemm_f16(a: torch.Tensor, w: torch.Tensor, *, n: Optional[int] = None, k: Optional[int] = None,
+             bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, gelu: bool = False,
+             out_f16: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = epilogue(a @ w^T): a [M, lda>=K] and w [N, ldw>=K] fp16 (K-major), fp32 accumulation; y fp32 or fp16."""
+    lib = _lib.load()
+    _f16(a, "a"), _f16(w, "w")
+    M, lda = a.shape
+    N, ldw = w.shape
+    K = k if k is not None else min(lda, ldw)
+    if n is not None:
+        N = n
+    epi = 0
+    if bias is not None:
+        epi |= EPI_BIAS
+        if _f32(bias, "bias").numel() != N:
+            raise ValueError("gemm_f16: bias size")
+    if gelu:
+        epi |= EPI_GELU
+    if residual is not None:
+        epi |= EPI_RESIDUAL
+        if tuple(_f32(residual, "residual").shape) != (M, N):
+            raise ValueError("gemm_f16: residual shape")
+    odt = torch.float16 if out_f16 else torch.float32
+    if out is None:
+        out = torch.empty((M, N), dtype=odt, device=a.device)
+    elif tuple(out.shape) != (M, N) or out.dtype != odt or not out.is_contiguous():
+        raise ValueError("gemm_f16: out shape / dtype")
+    _lib.check(lib.dclip_gemm_f16(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual), M, N, K, lda, ldw, N,
+                                  epi, int(out_f16), _stream()), "gemm_f16")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- crop front end
 
 def crop_resize(images_u8: torch.Tensor, dims: torch.Tensor, boxes: torch.Tensor, size: int,

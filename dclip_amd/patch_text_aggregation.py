@@ -193,7 +193,7 @@ class CLIPTextTokenizer:
         self.model = model
         self.tokenizer = tokenizer
         self.max_chunk_size = max_chunk_size
-        self.precision = precision          # "bf16": opt-in bf16-input GEMMs for this frozen tower
+        self.precision = precision          # "bf16" / "fp16": opt-in 16-bit GEMM inputs for this frozen tower
 
     @property
     def device(self):
@@ -326,13 +326,13 @@ class PatchTextAggregation(nn.Module):
                  faiss_index_path=None, embeddings_json_path=None, clip_model: Optional[HipCLIPModel] = None,
                  tokenizer=None, tower_precision: str = "fp32", owns_clip: bool = False,
                  text_twin: Optional[HipCLIPModel] = None):
-        """`tower_precision` ("fp32" default = the reference's arithmetic; "bf16" opt-in) selects how the FROZEN
+        """`tower_precision` ("fp32" default = the reference's arithmetic; "bf16" / "fp16" opt-in) selects how the FROZEN
         region / text towers multiply; the trainable cross_modal_attention always runs in fp32.
         `owns_clip`: the towers are this teacher's private frozen copy (they follow `.to()` / `.cuda()` although they
         stay out of `state_dict()`).  `text_twin`: a model whose text tower held the SAME weights as `clip_model`'s
         when this teacher was built (the student a snapshot was taken from) — see shares_text_tower_with."""
         super().__init__()
-        if tower_precision not in ("fp32", "bf16"):
+        if tower_precision not in ("fp32", "bf16", "fp16"):
             raise ValueError(f"tower_precision {tower_precision!r}")
         if all([projection_model_path, faiss_index_path, embeddings_json_path]):
             raise NotImplementedError("the KNN + projection tokenizer is outside the distillation step "

@@ -116,7 +116,8 @@ def build_teacher(args, device) -> PatchTextAggregation:
     tok = CLIPTokenizer.from_pretrained(path, local_files_only=True)
     return PatchTextAggregation(embed_dim=clip.config.projection_dim, num_heads=clip.config.projection_dim // 64,
                                 similarity_threshold=0.85, projection_model_path="", faiss_index_path="",
-                                embeddings_json_path="", clip_model=clip, tokenizer=tok).to(device)
+                                embeddings_json_path="", clip_model=clip, tokenizer=tok,
+                                tower_precision=getattr(args, "tower_precision", "fp32")).to(device)
 
 
 def main(args, teacher: Optional[PatchTextAggregation] = None, train_batches: Optional[Iterable] = None,
@@ -240,6 +241,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Path to save the trained teacher model")
     parser.add_argument("--clip_path", type=str, default=None, help="LOCAL directory with HF CLIP weights + tokenizer")
     parser.add_argument("--devices", type=int, default=1, help="GPUs of this node (one process per GPU, RCCL)")
+    parser.add_argument("--tower_precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
+                        help="arithmetic of the FROZEN CLIP towers (fp32: exact; bf16 / fp16: 16-bit GEMM inputs); "
+                             "the cross-modal block always trains in fp32")
     return parser
 
 

@@ -90,20 +90,21 @@ def make_prompts(classnames: Sequence[str], dataset_name: Optional[str] = None) 
 
 @torch.no_grad()
 def evaluate_zero_shot(model_name: str, model, processor: Callable, dataloader, classnames: Sequence[str],
-                       dataset_name: Optional[str] = None):
-    """Evaluate a single model for zero-shot classification (reference signature; see the module docstring)."""
+                       dataset_name: Optional[str] = None, precision: str = "fp32"):
+    """Evaluate a single model for zero-shot classification (reference signature; see the module docstring).
+    `precision`: the frozen towers' forward ("fp32" default, "bf16" or "fp16": HipCLIPModel.get_*_features)."""
     print(f"\nEvaluating {model_name}" + (f" on {dataset_name}" if dataset_name else "") + "...")
     clip = model if model_name == "base" or not hasattr(model, "student") else model.student
     dev = next(clip.parameters()).device
     tok = processor(text=make_prompts(classnames, dataset_name), return_tensors="pt", padding=True)
     ids = tok["input_ids"] if isinstance(tok, dict) or hasattr(tok, "keys") else tok
-    text_features = clip.get_text_features(input_ids=ids.to(dev))
+    text_features = clip.get_text_features(input_ids=ids.to(dev), precision=precision)
     mean = torch.tensor(E.CLIP_MEAN, device=dev).view(1, 3, 1, 1)
     std = torch.tensor(E.CLIP_STD, device=dev).view(1, 3, 1, 1)
     correct_top1 = correct_top5 = total = 0
     for images, labels in dataloader:
         images = (images.to(dev).float() - mean) / std
-        ranks = E.zero_shot_ranks(clip.get_image_features(pixel_values=images), text_features, labels)
+        ranks = E.zero_shot_ranks(clip.get_image_features(pixel_values=images, precision=precision), text_features, labels)
         correct_top1 += int((ranks == 0).sum())
         correct_top5 += int((ranks < 5).sum())
         total += len(labels)
@@ -113,7 +114,7 @@ def evaluate_zero_shot(model_name: str, model, processor: Callable, dataloader, 
     return {"top1": top1, "top5": top5}
 
 
-def main(argv=None, clip_model=None, processor=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Zero-shot evaluation (ImageNet / CIFAR folder layouts) on dclip_amd")
     ap.add_argument("--data_root", required=True, help="ImageFolder layout: one sub-directory per class")
     ap.add_argument("--classnames", default=None, help="text file, one class name per line (default: the folder names)")
@@ -123,7 +124,13 @@ def main(argv=None, clip_model=None, processor=None):
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--max_images", type=int, default=0)
     ap.add_argument("--results", default=None, help="results text file (default <dataset>_zero_shot_results.txt)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "fp16"],
+                    help="arithmetic of the frozen encoders' forward (fp32: exact; bf16 / fp16: 16-bit GEMM inputs)")
+    return ap
+
+
+def main(argv=None, clip_model=None, processor=None):
+    args = build_parser().parse_args(argv)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     from .CLIP_image_distillation import CLIPImageDistillation, _as_hip_model
     if clip_model is None:
@@ -140,13 +147,14 @@ def main(argv=None, clip_model=None, processor=None):
     else:
         classnames = list(ds.classes)
     print(f"Dataset contains {len(ds)} images with {len(ds.classes)} classes; {len(classnames)} class names")
-    results = {"base": evaluate_zero_shot("base", base, processor, batches(ds, args.batch_size), classnames, args.dataset)}
+    results = {"base": evaluate_zero_shot("base", base, processor, batches(ds, args.batch_size), classnames, args.dataset,
+                                          args.precision)}
     if args.checkpoint:
         import copy
         custom = CLIPImageDistillation.load_from_checkpoint(args.checkpoint, map_location=device, clip_model=copy.deepcopy(base),
                                                             clip_preprocess=processor, strict=False).to(device).eval()
         results["custom"] = evaluate_zero_shot("custom", custom, processor, batches(ds, args.batch_size), classnames,
-                                               args.dataset)
+                                               args.dataset, args.precision)
     out = args.results or f"{args.dataset}_zero_shot_results.txt"
     with open(out, "w") as f:
         f.write(f"Zero-Shot {args.dataset} Results\n")

@@ -401,6 +401,23 @@ int dclip_mt_adam_f32(const void* refs, int ntensors, int total_chunks, float lr
                       float eps, float weight_decay, const float* grad_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * fp16 forward path for FROZEN towers (opt-in precision="fp16"): the bf16 forward entries above with fp16 in place of
+ * bf16 — same arguments, limits and kernels (one source, templated over the 16-bit type), v_mfma_f32_*_f16 with fp32
+ * accumulation at the bf16 rate, 3 more mantissa bits.  Every fp32 -> fp16 rounding is round-to-nearest-even; a FINITE
+ * value beyond +-65504 saturates to +-65504, +-inf and NaN pass through unchanged.  What stays fp32 is what stays fp32 on
+ * the bf16 path (scores, softmax, LayerNorm statistics, residual stream, bias, epilogue).  No training forms.
+ *   gemm_f16: dclip_gemm_bf16 with fp16 A / W and, with out_f16, an fp16 C (epilogue BIAS | GELU | RESIDUAL).
+ *   cast_f32_f16, layernorm_fwd_f16, im2col_f16, attention_fwd_f16, attention_row_fwd_f16: their bf16 twins, fp16 out. */
+int dclip_gemm_f16(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
+                   int lda, int ldw, int ldc, int epilogue, int out_f16, void* stream);
+int dclip_cast_f32_f16(const float* x, void* y, int rows, int cols, int ldx, int ldy, void* stream);
+int dclip_layernorm_fwd_f16(const float* x, const float* gamma, const float* beta, void* y, int rows, int D, float eps,
+                            void* stream);
+int dclip_im2col_f16(const float* pixels, void* cols, int B, int C, int Himg, int Wimg, int patch, int ldc, void* stream);
+int dclip_attention_fwd_f16(const void* qkv, void* out, int B, int S, int H, int causal, void* stream);
+int dclip_attention_row_fwd_f16(const void* qkv, const int32_t* rows, void* out, int B, int S, int H, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Small elementwise helpers used between the ops above (all fp32, 16-byte vectorised).
  */
 int dclip_axpby(const float* x, float* y, float a, float b, size_t n, void* stream); /* y = a*x + b*y */
