@@ -28,6 +28,7 @@ def main(args, clip_model=None, clip_preprocess=None, train_batches=None, val_ba
         from transformers import CLIPModel, CLIPProcessor
         clip_model = CLIPModel.from_pretrained(args.clip_path, local_files_only=True).to(device)
         clip_preprocess = CLIPProcessor.from_pretrained(args.clip_path, local_files_only=True)
+    module_kwargs.setdefault("student_precision", getattr(args, "student_precision", "fp32"))
     model = CLIPImageDistillation(args, clip_model, clip_preprocess, **module_kwargs).to(device)
     trainer = Trainer(max_epochs=args.phase1_epochs, accelerator="gpu", devices=devices, precision=32,
                       gradient_clip_val=0.5, accumulate_grad_batches=4, checkpoint_dir=args.checkpoint_dir,
@@ -43,6 +44,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--phase1_epochs", type=int, default=2)                          # :51
     parser.add_argument("--clip_path", type=str, default=None)
     parser.add_argument("--devices", type=int, default=1, help="GPUs of this node (one process per GPU, RCCL)")
+    parser.add_argument("--student_precision", choices=("fp32", "bf16", "fp16"), default="fp32",
+                        help="GEMM inputs of the student's vision tower: fp32 (the reference), bf16, or fp16 with a dynamic "
+                             "loss scale (Lightning's precision='16-mixed')")
     return parser
 
 

@@ -76,9 +76,11 @@ class CLIPImageDistillation(LightningLikeModule):
         """`student_precision`: "fp32" (default: the reference's `precision=32`,
         training/CLIP_image_distill_training.py:40, and the benched config c2) or "bf16" — the student's VISION tower
         multiplies in bf16 (forward, dgrad, wgrad) with fp32 master weights, fp32 accumulation and fp32
-        LayerNorm / softmax / losses: what BASELINE configs c3 / c5 quote ("bf16 MFMA")."""
+        LayerNorm / softmax / losses: what BASELINE configs c3 / c5 quote ("bf16 MFMA"), or "fp16" — the same with fp16
+        GEMM inputs (IEEE rounding) and a dynamic loss scale that Trainer.fit applies (amp.DynamicLossScaler; Lightning's
+        precision="16-mixed"), within the 1e-3 embedding bar."""
         super().__init__()
-        if student_precision not in ("fp32", "bf16"):
+        if student_precision not in ("fp32", "bf16", "fp16"):
             raise ValueError(f"student_precision {student_precision!r}")
         self.student_precision = student_precision
         # Run the FROZEN text tower's forward on a second HIP stream beside the vision tower's forward (they share nothing
@@ -111,6 +113,7 @@ class CLIPImageDistillation(LightningLikeModule):
             E = self.student.config.projection_dim               # 512 / 8 heads in the reference (:446-452)
             snapshot = copy.deepcopy(self.student)
             object.__setattr__(snapshot, "_bf16_w", None)
+            object.__setattr__(snapshot, "_f16_w", None)
             for p in snapshot.parameters():
                 p.requires_grad = False
             teacher = PatchTextAggregation(embed_dim=E, num_heads=max(1, E // 64), clip_model=snapshot,
@@ -227,8 +230,14 @@ class CLIPImageDistillation(LightningLikeModule):
         self._prefetched = None
         return False
 
+    def _image_precision(self) -> str:
+        """What the student's get_image_features is called with: fp16 training is "fp16-mixed" (frozen "fp16" is forward only)."""
+        return "fp16-mixed" if self.student_precision == "fp16" else self.student_precision
+
     def _teacher_beside_student(self, images) -> bool:
         import os
+        if self.student_precision == "fp16" and not self._teacher_frozen():
+            return False           # the fp16 path keeps the teacher off its side stream when it reads trained weights
         on = self.overlap_teacher
         if on is None:
             env = os.environ.get("DCLIP_TEACHER_STREAM")
@@ -266,7 +275,7 @@ class CLIPImageDistillation(LightningLikeModule):
                     main = torch.cuda.current_stream(dev)
                     with torch.set_grad_enabled(grad_on):
                         early_student_image = self.student.get_image_features(
-                            pixel_values=images, precision=self.student_precision).float()
+                            pixel_values=images, precision=self._image_precision()).float()
                     main.wait_stream(self._teacher_stream)                       # join
                     teacher_image.record_stream(main)
                     self.teacher.last_sentence_embedding = sentence
@@ -283,7 +292,7 @@ class CLIPImageDistillation(LightningLikeModule):
                     self._teacher_stream.wait_stream(main)                       # fork: the batch is resident
                     with torch.set_grad_enabled(grad_on):
                         early_student_image = self.student.get_image_features(
-                            pixel_values=images, precision=self.student_precision).float()
+                            pixel_values=images, precision=self._image_precision()).float()
                     with torch.cuda.stream(self._teacher_stream), ops.workspace_lane(3):
                         teacher_image = self.teacher.compute_global_embedding_tensors(
                             regions, tokens, batch.get("region_counts"), batch.get("max_tokens")).float()
@@ -319,7 +328,8 @@ class CLIPImageDistillation(LightningLikeModule):
             shared_sentence = self.teacher.last_sentence_embedding
         text_frozen = not any(p.requires_grad for p in self.student.text_model.parameters()) \
             and not self.student.text_projection.weight.requires_grad
-        text_precision = "bf16" if (self.student_precision == "bf16" and text_frozen) else "fp32"
+        # a frozen text tower runs the frozen 16-bit forward of the student's type (bf16 or fp16); a trainable one stays fp32
+        text_precision = self.student_precision if (self.student_precision in ("bf16", "fp16") and text_frozen) else "fp32"
         text_job = None
         text_beside = self.overlap_frozen_text
         if text_beside is None:
@@ -334,7 +344,7 @@ class CLIPImageDistillation(LightningLikeModule):
             with torch.cuda.stream(self._text_stream), torch.no_grad(), ops.workspace_lane(1):     # own scratch: concurrent
                 text_job = self.student.get_text_features(input_ids=tokens, precision=text_precision).float()
         student_image = early_student_image if early_student_image is not None else \
-            self.student.get_image_features(pixel_values=images, precision=self.student_precision).float()
+            self.student.get_image_features(pixel_values=images, precision=self._image_precision()).float()
         loss_image = self.cosine_distillation_loss(student_image, teacher_image)
         if shared_sentence is not None:
             student_text = shared_sentence.float()

@@ -106,6 +106,24 @@ SIGNATURES = {
     "dclip_im2col_f16": (I, [P, P, I, I, I, I, I, I, P]),
     "dclip_attention_fwd_f16": (I, [P, P, I, I, I, I, P]),
     "dclip_attention_row_fwd_f16": (I, [P, P, P, I, I, I, P]),
+    "dclip_gemm_f16_ex": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "dclip_gemm_f16_wgrad_tokmajor_plan": (I, [I, I, I]),
+    "dclip_gemm_f16_wgrad_tokmajor": (I, [P, P, P, I, I, I, I, I, I, I, P, Z, P]),
+    "dclip_gemm_f16_splitk_plan": (I, [I, I, I]),
+    "dclip_gemm_f16_splitk_workspace": (Z, [I, I, I]),
+    "dclip_gemm_f16_splitk": (I, [P, P, P, I, I, I, I, I, I, I, P, Z, P]),
+    "dclip_cast_f32_f16_ieee": (I, [P, P, I, I, I, I, P]),
+    "dclip_layernorm_fwd_f16_stats": (I, [P, P, P, P, P, P, I, I, F, P]),
+    "dclip_layernorm_bwd_ex_f16": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, Z, P]),
+    "dclip_transpose_to_f16": (I, [P, I, P, P, I, I, I, I, I, P]),
+    "dclip_rowsum_f16": (I, [P, P, I, I, I, P]),
+    "dclip_colsum_f16": (I, [P, P, I, I, I, I, P, Z, P]),
+    "dclip_mt_weights_f16": (I, [P, I, I, P]),
+    "dclip_attention_fwd_f16_lse": (I, [P, P, P, I, I, I, I, P]),
+    "dclip_attention_bwd_f16": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "dclip_clip_coef_scaled": (I, [P, I, F, P, P, P]),
+    "dclip_mt_adamw_f32_skip": (I, [P, I, I, F, F, F, F, F, P, P]),
+    "dclip_amp_update_scale": (I, [P, P, P, F, F, I, P]),
 }
 
 _lib = None

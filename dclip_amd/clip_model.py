@@ -169,7 +169,10 @@ class HipCLIPModel(nn.Module):
     def get_image_features(self, pixel_values: torch.Tensor = None, precision: str = "fp32", **kwargs) -> torch.Tensor:
         """precision="bf16" (opt-in): GEMM inputs in bf16 on the bf16 MFMA path, everything else fp32 — frozen forward, or
         the bf16 training path when grad is enabled and a parameter is trainable.  precision="fp16" (opt-in, frozen use
-        only): the same forward with fp16 GEMM inputs (3 more mantissa bits at the bf16 rate)."""
+        only): the same forward with fp16 GEMM inputs (3 more mantissa bits at the bf16 rate).  precision="fp16-mixed"
+        (opt-in): the fp16 TRAINING path (Lightning's "16-mixed": fp16 GEMM inputs with IEEE rounding, fp32 master weights;
+        the caller scales the loss, amp.DynamicLossScaler) when grad is enabled and a parameter is trainable, otherwise the
+        frozen "fp16" forward."""
         if pixel_values is None:
             raise ValueError("You have to specify pixel_values")
         v = self.config.vision
@@ -182,12 +185,16 @@ class HipCLIPModel(nn.Module):
                 # TRAINING in bf16 (configs c3 / c5): forward, dgrad and wgrad GEMMs on the bf16 MFMA kernels, fp32
                 # master weights and fp32 everything else (engine.vision_fwd_bf16_train)
                 return functional.VisionTowerBf16Fn.apply(pixel_values.float(), v, v.num_hidden_layers, self._bf16_cache(),
-                                                          *p.tensors())
+                                                          torch.bfloat16, *p.tensors())
             pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)
             return engine.vision_fwd_bf16(pd, pixel_values.float().contiguous(), v, self._bf16_cache())
-        if precision == "fp16":
+        if precision in ("fp16", "fp16-mixed"):
             if torch.is_grad_enabled() and any(t.requires_grad for t in p.tensors()):
-                raise RuntimeError("precision='fp16' is a forward-only path for frozen towers: call it under torch.no_grad()")
+                if precision == "fp16":
+                    raise RuntimeError("precision='fp16' is a forward-only path for frozen towers: call it under torch.no_grad()"
+                                       " (training: precision='fp16-mixed')")
+                return functional.VisionTowerBf16Fn.apply(pixel_values.float(), v, v.num_hidden_layers, self._f16_cache(),
+                                                          torch.float16, *p.tensors())
             pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)
             return engine.vision_fwd_bf16(pd, pixel_values.float().contiguous(), v, self._f16_cache(), torch.float16)
         if precision != "fp32":

@@ -14,9 +14,11 @@
 //
 // The forward kernels (tiled, whole-head, one-row) are templates over the 16-bit type (common.h, Bf16T / F16T): the fp16
 // instances serve dclip_attention_fwd_f16 / dclip_attention_row_fwd_f16 with P rounded to fp16.  The training forms (lse,
-// backward) are bf16 only.
+// backward, S <= 64) have fp16 instances with IEEE rounding (common.h, F16IeeeT): dclip_attention_fwd_f16_lse /
+// dclip_attention_bwd_f16, DESIGN.md §13b.
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -28,11 +30,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int HD = 64;             // head dim
 constexpr int KT = 64;             // keys per LDS tile
 constexpr float kScale = 0.125f;   // 64^-0.5
-
-__device__ __forceinline__ unsigned short bf16_bits(float x) {
-  __bf16 b = (__bf16)x;
-  return __builtin_bit_cast(unsigned short, b);
-}
 
 // byte offset of 16-byte granule g (0..7) of row `row` in a [rows][64] bf16 tile
 __device__ __forceinline__ int gran_off(int row, int g) { return row * 128 + ((g ^ ((row >> 1) & 7)) << 4); }
@@ -453,7 +450,7 @@ void launch_head(const unsigned short* qkv, unsigned short* out, int B, int S, i
 //          (lse and delta are per-lane scalars) and its registers are the B operand of dQ^T[d][q] = K^T[d][key] dS^T[key][q].
 // S and dP are formed twice (once per layout): 8 extra MFMAs per block pair against an LDS transpose of dS and a second
 // barrier — at the bf16 rate the whole kernel is ~60 MFMAs per wave and is bound by its loads.
-template <bool CAUSAL>
+template <class T, bool CAUSAL>
 __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short* __restrict__ qkv, const unsigned short* __restrict__ out,
                                                             const unsigned short* __restrict__ dout, const float* __restrict__ lse,
                                                             unsigned short* __restrict__ dqkv, int S, int H) {
@@ -494,8 +491,8 @@ __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const unsigned int o2 = ov[c][e], d2 = dv[c][e];
-        dl += __builtin_bit_cast(float, o2 << 16) * __builtin_bit_cast(float, d2 << 16);
-        dl += __builtin_bit_cast(float, o2 & 0xffff0000u) * __builtin_bit_cast(float, d2 & 0xffff0000u);
+        dl += T::lo_f32(o2) * T::lo_f32(d2);
+        dl += T::hi_f32(o2) * T::hi_f32(d2);
       }
       dl += __shfl_xor(dl, 1);
       dl += __shfl_xor(dl, 2);
@@ -517,16 +514,17 @@ __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short
   const int i16 = lane & 15, qq = i16 >> 2, pp = i16 & 3;
   typedef short s16x8 __attribute__((ext_vector_type(8)));
   // row fragment (A or B operand of a K = 64 contraction over head dims): X[row][16 s + 8 half .. +7], s = 0..3
-  auto row_frag = [&](const unsigned char* tile, int row, bf16x8 (&f)[4]) {
+  typedef typename T::x8 x8;
+  auto row_frag = [&](const unsigned char* tile, int row, x8 (&f)[4]) {
 #pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) f[s4] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(tile + gran_off(row, 2 * s4 + half)));
+    for (int s4 = 0; s4 < 4; ++s4) f[s4] = __builtin_bit_cast(x8, *reinterpret_cast<const u32x4*>(tile + gran_off(row, 2 * s4 + half)));
   };
-  auto mm4 = [&](const bf16x8 (&a)[4], const bf16x8 (&bq)[4]) {
+  auto mm4 = [&](const x8 (&a)[4], const x8 (&bq)[4]) {
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s4], bq[s4], acc, 0, 0, 0);
+    for (int s4 = 0; s4 < 4; ++s4) acc = T::mfma32(a[s4], bq[s4], acc);
     return acc;
   };
   // X^T fragments for a contraction over the 32 rows r0..r0+31 of a row-major tile: [t][dt] = X^T[32 dt + ..][the rows that MFMA
@@ -544,15 +542,15 @@ __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short
       }
     }
   };
-  auto acc_xt = [&](f32x16 (&o)[2], const s16x8 (&xt)[2][2], const f32x16& w) {     // o[dt] += X^T (A) x w (B, rounded to bf16)
+  auto acc_xt = [&](f32x16 (&o)[2], const s16x8 (&xt)[2][2], const f32x16& w) {     // o[dt] += X^T (A) x w (B, rounded to T)
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      bf16x8 wf;
+      x8 wf;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) wf[e] = (__bf16)w[8 * t + e];
+      for (int e = 0; e < 8; ++e) wf[e] = (typename T::elem)w[8 * t + e];
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, xt[t][dt]), wf, o[dt], 0, 0, 0);
+        o[dt] = T::mfma32(__builtin_bit_cast(x8, xt[t][dt]), wf, o[dt]);
     }
   };
   auto store_rows = [&](const f32x16 (&o)[2], int row, int part) {   // o[dt][4 j + e] = X[row][32 dt + 8 j + 4 half + e]
@@ -561,7 +559,7 @@ __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const u16x4 v = {bf16_bits(o[dt][4 * j + 0]), bf16_bits(o[dt][4 * j + 1]), bf16_bits(o[dt][4 * j + 2]), bf16_bits(o[dt][4 * j + 3])};
+        const u16x4 v = {T::bits(o[dt][4 * j + 0]), T::bits(o[dt][4 * j + 1]), T::bits(o[dt][4 * j + 2]), T::bits(o[dt][4 * j + 3])};
         *reinterpret_cast<u16x4*>(orow + 32 * dt + 8 * j + 4 * half) = v;
       }
   };
@@ -569,7 +567,7 @@ __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short
   // ---- role 1: this wave's KEYS (rows 32 wave + l31 of K and V), every query block -> dK, dV
   {
     const int key = 32 * wave + l31;
-    bf16x8 kf[4], vf[4];
+    x8 kf[4], vf[4];
     row_frag(Ks, key, kf);
     row_frag(Vs, key, vf);
     f32x16 dk[2], dvv[2];
@@ -578,7 +576,7 @@ __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short
 #pragma unroll
       for (int r = 0; r < 16; ++r) dk[dt][r] = dvv[dt][r] = 0.f;
     for (int qb = CAUSAL ? wave : 0; qb < nblk; ++qb) {    // causal: query blocks before the key block hold no pair key <= query
-      bf16x8 qf[4], df[4];
+      x8 qf[4], df[4];
       row_frag(Qs, 32 * qb + l31, qf);
       row_frag(dOs, 32 * qb + l31, df);
       f32x16 st = mm4(qf, kf);                             // S[query][key]
@@ -605,7 +603,7 @@ __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short
   // ---- role 2: this wave's QUERIES, every key block -> dQ
   {
     const int query = 32 * wave + l31;
-    bf16x8 qf[4], df[4];
+    x8 qf[4], df[4];
     row_frag(Qs, query, qf);
     row_frag(dOs, query, df);
     const float nl = -lse_s[query] * l2e, dl = dl_s[query];
@@ -616,7 +614,7 @@ __global__ void __launch_bounds__(128) attn_bwd_bf16_kernel(const unsigned short
       for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
     const int nkb = CAUSAL ? wave + 1 : nblk;
     for (int kb = 0; kb < nkb; ++kb) {
-      bf16x8 kf[4], vf[4];
+      x8 kf[4], vf[4];
       row_frag(Ks, 32 * kb + l31, kf);
       row_frag(Vs, 32 * kb + l31, vf);
       f32x16 st = mm4(kf, qf);                             // S^T[key][query]
@@ -749,44 +747,74 @@ DCLIP_API int dclip_attention_row_fwd_f16(const void* qkv, const int32_t* rows, 
   return attention_row16<F16T>("attention_row_fwd_f16", qkv, rows, out, B, S, H, stream);
 }
 
-// Training forms (bf16 student, configs c3 / c5): the forward also leaves the log-sum-exp of the scaled scores (S <= 288,
-// the whole-head kernel), the backward (S <= 64) returns dq | dk | dv as bf16 [B*S][3*H*64].
-DCLIP_API int dclip_attention_fwd_bf16_lse(const void* qkv, void* out, float* lse, int B, int S, int H, int causal, void* stream) {
-  DCLIP_REQUIRE(qkv && out && lse, "attention_fwd_bf16_lse: null pointer");
-  DCLIP_REQUIRE(B > 0 && S > 0 && S <= 288 && S != 257 && H > 0, "attention_fwd_bf16_lse: B=%d S=%d (<= 288, not 257) H=%d", B, S, H);
-  DCLIP_REQUIRE(((uintptr_t)qkv | (uintptr_t)out) % 16 == 0, "attention_fwd_bf16_lse: 16-byte alignment");
+namespace {
+// Training forms (bf16 student, configs c3 / c5): the forward also leaves the log-sum-exp of the scaled scores (S <= 288 for
+// bf16; S <= 64 for fp16, the backward's limit and the only whole-head instances built for the fp16 training type), the
+// backward (S <= 64) returns dq | dk | dv as 16-bit [B*S][3*H*64].
+template <class T>
+int attention_fwd16_lse(const char* name, const void* qkv, void* out, float* lse, int B, int S, int H, int causal, void* stream) {
+  constexpr int smax = std::is_same<T, F16IeeeT>::value ? 64 : 288;
+  DCLIP_REQUIRE(qkv && out && lse, "%s: null pointer", name);
+  DCLIP_REQUIRE(B > 0 && S > 0 && S <= smax && S != 257 && H > 0, "%s: B=%d S=%d (<= %d, not 257) H=%d", name, B, S, smax, H);
+  DCLIP_REQUIRE(((uintptr_t)qkv | (uintptr_t)out) % 16 == 0, "%s: 16-byte alignment", name);
   hipStream_t st = (hipStream_t)stream;
   const unsigned short* q = (const unsigned short*)qkv;
   unsigned short* o = (unsigned short*)out;
-  switch (cdiv(S, 32)) {
-    case 1: launch_head<Bf16T, 1>(q, o, B, S, H, causal, st, lse); break;
-    case 2: launch_head<Bf16T, 2>(q, o, B, S, H, causal, st, lse); break;
-    case 3: launch_head<Bf16T, 3>(q, o, B, S, H, causal, st, lse); break;
-    case 4: launch_head<Bf16T, 4>(q, o, B, S, H, causal, st, lse); break;
-    case 5: launch_head<Bf16T, 5>(q, o, B, S, H, causal, st, lse); break;
-    case 6: launch_head<Bf16T, 6>(q, o, B, S, H, causal, st, lse); break;
-    case 7: launch_head<Bf16T, 7>(q, o, B, S, H, causal, st, lse); break;
-    case 8: launch_head<Bf16T, 8>(q, o, B, S, H, causal, st, lse); break;
-    default: launch_head<Bf16T, 9>(q, o, B, S, H, causal, st, lse); break;
+  if constexpr (smax == 64) {
+    if (S <= 32) launch_head<T, 1>(q, o, B, S, H, causal, st, lse);
+    else launch_head<T, 2>(q, o, B, S, H, causal, st, lse);
+  } else {
+    switch (cdiv(S, 32)) {
+      case 1: launch_head<T, 1>(q, o, B, S, H, causal, st, lse); break;
+      case 2: launch_head<T, 2>(q, o, B, S, H, causal, st, lse); break;
+      case 3: launch_head<T, 3>(q, o, B, S, H, causal, st, lse); break;
+      case 4: launch_head<T, 4>(q, o, B, S, H, causal, st, lse); break;
+      case 5: launch_head<T, 5>(q, o, B, S, H, causal, st, lse); break;
+      case 6: launch_head<T, 6>(q, o, B, S, H, causal, st, lse); break;
+      case 7: launch_head<T, 7>(q, o, B, S, H, causal, st, lse); break;
+      case 8: launch_head<T, 8>(q, o, B, S, H, causal, st, lse); break;
+      default: launch_head<T, 9>(q, o, B, S, H, causal, st, lse); break;
+    }
   }
-  DCLIP_CHECK_LAUNCH("attention_fwd_bf16_lse");
+  DCLIP_CHECK_LAUNCH(name);
   return DCLIP_OK;
+}
+
+template <class T>
+int attention_bwd16(const char* name, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
+                    int S, int H, int causal, void* stream) {
+  DCLIP_REQUIRE(qkv && out && dout && lse && dqkv, "%s: null pointer", name);
+  DCLIP_REQUIRE(B > 0 && S > 0 && S <= 64 && H > 0, "%s: B=%d S=%d (<= 64) H=%d", name, B, S, H);
+  DCLIP_REQUIRE(((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) % 16 == 0, "%s: 16-byte alignment", name);
+  hipStream_t st = (hipStream_t)stream;
+  if (causal)
+    hipLaunchKernelGGL((attn_bwd_bf16_kernel<T, true>), dim3(B * H), dim3(128), 0, st, (const unsigned short*)qkv,
+                       (const unsigned short*)out, (const unsigned short*)dout, lse, (unsigned short*)dqkv, S, H);
+  else
+    hipLaunchKernelGGL((attn_bwd_bf16_kernel<T, false>), dim3(B * H), dim3(128), 0, st, (const unsigned short*)qkv,
+                       (const unsigned short*)out, (const unsigned short*)dout, lse, (unsigned short*)dqkv, S, H);
+  DCLIP_CHECK_LAUNCH(name);
+  return DCLIP_OK;
+}
+}  // namespace
+
+DCLIP_API int dclip_attention_fwd_bf16_lse(const void* qkv, void* out, float* lse, int B, int S, int H, int causal, void* stream) {
+  return attention_fwd16_lse<Bf16T>("attention_fwd_bf16_lse", qkv, out, lse, B, S, H, causal, stream);
 }
 
 DCLIP_API int dclip_attention_bwd_bf16(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
                                        int S, int H, int causal, void* stream) {
-  DCLIP_REQUIRE(qkv && out && dout && lse && dqkv, "attention_bwd_bf16: null pointer");
-  DCLIP_REQUIRE(B > 0 && S > 0 && S <= 64 && H > 0, "attention_bwd_bf16: B=%d S=%d (<= 64) H=%d", B, S, H);
-  DCLIP_REQUIRE(((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) % 16 == 0, "attention_bwd_bf16: 16-byte alignment");
-  hipStream_t st = (hipStream_t)stream;
-  if (causal)
-    hipLaunchKernelGGL((attn_bwd_bf16_kernel<true>), dim3(B * H), dim3(128), 0, st, (const unsigned short*)qkv,
-                       (const unsigned short*)out, (const unsigned short*)dout, lse, (unsigned short*)dqkv, S, H);
-  else
-    hipLaunchKernelGGL((attn_bwd_bf16_kernel<false>), dim3(B * H), dim3(128), 0, st, (const unsigned short*)qkv,
-                       (const unsigned short*)out, (const unsigned short*)dout, lse, (unsigned short*)dqkv, S, H);
-  DCLIP_CHECK_LAUNCH("attention_bwd_bf16");
-  return DCLIP_OK;
+  return attention_bwd16<Bf16T>("attention_bwd_bf16", qkv, out, dout, lse, dqkv, B, S, H, causal, stream);
+}
+
+// fp16 twins (training path; P and dS rounded to fp16, dq / dk / dv with IEEE rounding, common.h F16IeeeT): S <= 64 both ways
+DCLIP_API int dclip_attention_fwd_f16_lse(const void* qkv, void* out, float* lse, int B, int S, int H, int causal, void* stream) {
+  return attention_fwd16_lse<F16IeeeT>("attention_fwd_f16_lse", qkv, out, lse, B, S, H, causal, stream);
+}
+
+DCLIP_API int dclip_attention_bwd_f16(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
+                                      int S, int H, int causal, void* stream) {
+  return attention_bwd16<F16IeeeT>("attention_bwd_f16", qkv, out, dout, lse, dqkv, B, S, H, causal, stream);
 }
 
 namespace {

@@ -127,3 +127,10 @@ struct F16T {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
   }
 };
+
+// fp16 of the TRAINING path (student_precision="fp16"): F16T with plain IEEE round-to-nearest-even, as
+// (_Float16)x does — a finite value beyond +-65504 becomes +-inf and NaN stays NaN.  An overflow of a loss-scaled gradient
+// then reaches the global gradient norm, and the loss scaler skips the step and lowers its scale (torch GradScaler).
+struct F16IeeeT : F16T {
+  static __device__ __forceinline__ unsigned short bits(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
+};

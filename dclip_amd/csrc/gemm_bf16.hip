@@ -10,10 +10,14 @@
 //
 // fp16: every kernel of the FORWARD plan is a template over the 16-bit type (common.h, Bf16T / F16T) and has an fp16
 // instance, reached through dclip_gemm_f16 / dclip_cast_f32_f16 / dclip_layernorm_fwd_f16.  Only the MFMA
-// (v_mfma_f32_{32x32x16,16x16x32}_f16) and the rounding differ; the training forms (split-K, token-major weight gradient,
-// DGELU, saved pre-activation) are bf16 only.
+// (v_mfma_f32_{32x32x16,16x16x32}_f16) and the rounding differ.  The training forms (split-K, token-major weight gradient,
+// DGELU, saved pre-activation) have a second fp16 instance with IEEE rounding (common.h, F16IeeeT), reached
+// through dclip_gemm_f16_ex / _splitk / _wgrad_tokmajor / dclip_cast_f32_f16_ieee / dclip_layernorm_fwd_f16_stats: only the
+// kernels of the default plans (ping-pong, register-staged 128x128 / 64x64) are instantiated for it, so the A/B switches
+// DCLIP_BF16_PP / _MID_DMA / _PERSIST do not apply there.
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -1363,6 +1367,12 @@ DCLIP_API int dclip_gemm_bf16(const void* A, const void* W, void* C, const float
 }
 
 namespace {
+// fp16 of the training path (F16IeeeT): the ping-pong and register-staged kernels only, whatever the A/B switches say
+template <class T>
+constexpr bool kTrain16 = std::is_same<T, F16IeeeT>::value;
+template <class T>
+bool pp16() { return kTrain16<T> || pingpong_enabled(); }
+
 // The forward dispatcher of both 16-bit types: same checks, same plan.  Every kernel it can pick — register-staged 128x128 /
 // 64x64, LDS-DMA 128x128 (DCLIP_BF16_MID_DMA) and 256x256 (DCLIP_BF16_PP=0), ping-pong, persistent (DCLIP_BF16_PERSIST) — has
 // an instance per type, and the DCLIP_BF16_* switches select among them for fp16 exactly as for bf16.
@@ -1392,23 +1402,30 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
     // persistent form when a CU gets several tiles (the towers' M = 100k shapes: 14 per CU): the epilogue of one tile
     // overlaps the K loop of the next.  DGELU (an extra side operand in the epilogue) stays on the one-tile kernel.
     const int persist_min = getenv("DCLIP_BF16_PERSIST_MIN") ? atoi(getenv("DCLIP_BF16_PERSIST_MIN")) : 512;
-    const bool persist = pingpong_enabled() && persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && ldc % 8 == 0 && N % 8 == 0 &&
+    const bool persist = !kTrain16<T> && pingpong_enabled() && persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && ldc % 8 == 0 && N % 8 == 0 &&
                          (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min;
-    if (persist) launch_ppp<T>(pb, st);
-    else if (pingpong_enabled()) launch_pp<T>(pb, st);
-    else launch_dma<T, 256, 256, 2, 4>(pb, st);
+    if constexpr (kTrain16<T>) {
+      (void)persist;
+      launch_pp<T>(pb, st);
+    } else {
+      if (persist) launch_ppp<T>(pb, st);
+      else if (pingpong_enabled()) launch_pp<T>(pb, st);
+      else launch_dma<T, 256, 256, 2, 4>(pb, st);
+    }
     DCLIP_CHECK_LAUNCH(name);
     return DCLIP_OK;
   }
   // A/B aid: DCLIP_BF16_MID_DMA=1 sends what falls below the big-tile threshold (K % 64 == 0) to the 128x128 LDS-DMA kernel,
   // two workgroups per CU, instead of the register-staged 128x128 one
-  const bool mid_dma = getenv("DCLIP_BF16_MID_DMA") && atoi(getenv("DCLIP_BF16_MID_DMA")) != 0;
-  if (mid_dma && K % BKH == 0 && (long)cdiv(M, 128) * cdiv(N, 128) >= 256) {
-    GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
-                      (unsigned short*)aux, 0, nullptr};
-    launch_dma<T, 128, 128, 2, 2>(pb, st);
-    DCLIP_CHECK_LAUNCH(name);
-    return DCLIP_OK;
+  if constexpr (!kTrain16<T>) {
+    const bool mid_dma = getenv("DCLIP_BF16_MID_DMA") && atoi(getenv("DCLIP_BF16_MID_DMA")) != 0;
+    if (mid_dma && K % BKH == 0 && (long)cdiv(M, 128) * cdiv(N, 128) >= 256) {
+      GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
+                        (unsigned short*)aux, 0, nullptr};
+      launch_dma<T, 128, 128, 2, 2>(pb, st);
+      DCLIP_CHECK_LAUNCH(name);
+      return DCLIP_OK;
+    }
   }
   const bool small = (long)cdiv(M, 128) * cdiv(N, 128) < 256;  // fewer tiles than CUs: use the finer tile
   const int bm = small ? 64 : 128, bn = bm;
@@ -1435,12 +1452,21 @@ DCLIP_API int dclip_gemm_f16(const void* A, const void* W, void* C, const float*
   return gemm16<F16T>("gemm_f16", A, W, C, bias, residual, nullptr, M, N, K, lda, ldw, ldc, epilogue, out_f16, stream);
 }
 
+// fp16 TRAINING path: dclip_gemm_bf16_ex's arguments, epilogues and limits with fp16 A / W / aux / 16-bit C, IEEE rounding
+// (common.h, F16IeeeT: an overflow becomes +-inf).  The ping-pong / register-staged kernels only (DCLIP_BF16_PP, _MID_DMA and
+// _PERSIST do not apply).
+DCLIP_API int dclip_gemm_f16_ex(const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux,
+                                int M, int N, int K, int lda, int ldw, int ldc, int epilogue, int out_f16, void* stream) {
+  return gemm16<F16IeeeT>("gemm_f16_ex", A, W, C, bias, residual, aux, M, N, K, lda, ldw, ldc, epilogue, out_f16, stream);
+}
+
 // dW[M = out][N = in] fp32 = dY^T X from the operands as the backward has them: dY [K = tokens][lddy >= M], X [K][ldx >= N],
 // bf16, token-major — no transposes.  Split-K over the tokens on the ping-pong kernel (token-major form), fixed-order reduce.
 // dclip_gemm_bf16_wgrad_tokmajor_plan = the split count to pass, 0 when this form does not apply (K % 64, M / N % 8, too few
 // work items for the chip, or DCLIP_BF16_PP=0): the caller then transposes and uses dclip_gemm_bf16_splitk.
-DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor_plan(int M, int N, int K) {
-  if (K % BKH != 0 || M % 8 != 0 || N % 8 != 0 || !pingpong_enabled()) return 0;
+namespace {
+int tokmajor_plan(int M, int N, int K, bool pp) {
+  if (K % BKH != 0 || M % 8 != 0 || N % 8 != 0 || !pp) return 0;
   const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
   int s = t256 >= 256 ? 1 : (int)(256 / t256);
   const int kmax = K / 512 > 0 ? K / 512 : 1;                 // at least 8 K-tiles per work item
@@ -1449,38 +1475,56 @@ DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor_plan(int M, int N, int K) {
   return t256 * s >= 128 ? s : 0;
 }
 
-DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor(const void* dY, const void* X, float* C, int M, int N, int K, int lddy, int ldx,
-                                             int ldc, int splits, void* workspace, size_t workspace_bytes, void* stream) {
-  DCLIP_REQUIRE(dY && X && C, "gemm_bf16_wgrad_tokmajor: null operand");
+template <class T>
+int wgrad_tokmajor16(const char* name, const void* dY, const void* X, float* C, int M, int N, int K, int lddy, int ldx, int ldc,
+                     int splits, void* workspace, size_t workspace_bytes, void* stream) {
+  DCLIP_REQUIRE(dY && X && C, "%s: null operand", name);
   DCLIP_REQUIRE(M > 0 && N > 0 && K > 0 && K % BKH == 0 && M % 8 == 0 && N % 8 == 0 && splits >= 1 && splits <= 64,
-                "gemm_bf16_wgrad_tokmajor: M=%d N=%d (multiples of 8) K=%d (multiple of 64) splits=%d", M, N, K, splits);
-  DCLIP_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0 && lddy >= M && ldx >= N && ldc % 4 == 0 && ldc >= N,
-                "gemm_bf16_wgrad_tokmajor: leading dimensions");
-  DCLIP_REQUIRE(((uintptr_t)dY | (uintptr_t)X | (uintptr_t)C) % 16 == 0, "gemm_bf16_wgrad_tokmajor: operands must be 16-byte aligned");
-  DCLIP_REQUIRE(pingpong_enabled(), "gemm_bf16_wgrad_tokmajor: needs the ping-pong kernel (DCLIP_BF16_PP=0 is set)");
+                "%s: M=%d N=%d (multiples of 8) K=%d (multiple of 64) splits=%d", name, M, N, K, splits);
+  DCLIP_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0 && lddy >= M && ldx >= N && ldc % 4 == 0 && ldc >= N, "%s: leading dimensions", name);
+  DCLIP_REQUIRE(((uintptr_t)dY | (uintptr_t)X | (uintptr_t)C) % 16 == 0, "%s: operands must be 16-byte aligned", name);
+  DCLIP_REQUIRE(pp16<T>(), "%s: needs the ping-pong kernel (DCLIP_BF16_PP=0 is set)", name);
   const int kps = cdiv(cdiv(K, splits), BKH) * BKH;
   const int s_eff = cdiv(K, kps);
   hipStream_t st = (hipStream_t)stream;
   if (s_eff == 1) {
     GemmBf16Params pb{(const __bf16*)dY, (const __bf16*)X, C, nullptr, nullptr, M, N, K, lddy, ldx, ldc, 0, 0, 0, 0, nullptr, 0, nullptr};
-    launch_pp<Bf16T, true>(pb, st, 1);
-    DCLIP_CHECK_LAUNCH("gemm_bf16_wgrad_tokmajor");
+    launch_pp<T, true>(pb, st, 1);
+    DCLIP_CHECK_LAUNCH(name);
     return DCLIP_OK;
   }
   const size_t need = (size_t)s_eff * M * N * sizeof(float);
   if (!workspace || workspace_bytes < need) {
-    dclip_set_error("gemm_bf16_wgrad_tokmajor: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+    dclip_set_error("%s: needs %zu workspace bytes, got %zu", name, need, workspace_bytes);
     return DCLIP_EWORKSPACE;
   }
-  DCLIP_REQUIRE((uintptr_t)workspace % 16 == 0, "gemm_bf16_wgrad_tokmajor: workspace must be 16-byte aligned");
+  DCLIP_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", name);
   GemmBf16Params pb{(const __bf16*)dY, (const __bf16*)X, C, nullptr, nullptr, M, N, K, lddy, ldx, ldc, 0, 0, 0, 0, nullptr, kps,
                     (float*)workspace};
-  launch_pp<Bf16T, true>(pb, st, s_eff);
-  DCLIP_CHECK_LAUNCH("gemm_bf16_wgrad_tokmajor");
+  launch_pp<T, true>(pb, st, s_eff);
+  DCLIP_CHECK_LAUNCH(name);
   hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, st, (const float*)workspace, C, M,
                      N, ldc, s_eff);
-  DCLIP_CHECK_LAUNCH("gemm_bf16_wgrad_tokmajor.reduce");
+  DCLIP_CHECK_LAUNCH(name);
   return DCLIP_OK;
+}
+}  // namespace
+
+DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor_plan(int M, int N, int K) { return tokmajor_plan(M, N, K, pingpong_enabled()); }
+
+DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor(const void* dY, const void* X, float* C, int M, int N, int K, int lddy, int ldx,
+                                             int ldc, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+  return wgrad_tokmajor16<Bf16T>("gemm_bf16_wgrad_tokmajor", dY, X, C, M, N, K, lddy, ldx, ldc, splits, workspace,
+                                 workspace_bytes, stream);
+}
+
+// fp16 twins (training path, IEEE rounding is not involved: fp16 operands in, fp32 out); DCLIP_BF16_PP does not apply
+DCLIP_API int dclip_gemm_f16_wgrad_tokmajor_plan(int M, int N, int K) { return tokmajor_plan(M, N, K, true); }
+
+DCLIP_API int dclip_gemm_f16_wgrad_tokmajor(const void* dY, const void* X, float* C, int M, int N, int K, int lddy, int ldx,
+                                            int ldc, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+  return wgrad_tokmajor16<F16IeeeT>("gemm_f16_wgrad_tokmajor", dY, X, C, M, N, K, lddy, ldx, ldc, splits, workspace,
+                                    workspace_bytes, stream);
 }
 
 namespace {
@@ -1528,6 +1572,11 @@ DCLIP_API int dclip_cast_f32_f16(const float* x, void* y, int rows, int cols, in
   return cast16<F16T>("cast_f32_f16", x, y, rows, cols, ldx, ldy, stream);
 }
 
+// fp16 training path: the same cast with IEEE rounding (beyond +-65504 -> +-inf; dclip_cast_f32_f16 saturates)
+DCLIP_API int dclip_cast_f32_f16_ieee(const float* x, void* y, int rows, int cols, int ldx, int ldy, void* stream) {
+  return cast16<F16IeeeT>("cast_f32_f16_ieee", x, y, rows, cols, ldx, ldy, stream);
+}
+
 DCLIP_API int dclip_layernorm_fwd_bf16(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,
                                        float eps, void* stream) {
   return dclip_layernorm_fwd_bf16_stats(x, gamma, beta, y, nullptr, nullptr, rows, D, eps, stream);
@@ -1543,12 +1592,15 @@ DCLIP_API int dclip_layernorm_fwd_f16(const float* x, const float* gamma, const 
   return layernorm16<F16T>("layernorm_fwd_f16", x, gamma, beta, y, nullptr, nullptr, rows, D, eps, stream);
 }
 
-// Split-K form for products with few output tiles and a long contraction — the weight gradients of the bf16 training
-// path, dW[out,in] = (dY^T)[out,tok] (X^T)[in,tok]^T with tok = batch x sequence (12,800 .. 25,600): `splits` work items
-// per 128x128 tile write fp32 partials to the caller's workspace, a second kernel sums them in fixed order.  fp32 C, no
-// epilogue.  dclip_gemm_bf16_splitk_plan returns the split count this library would choose (1 = use dclip_gemm_bf16).
-DCLIP_API int dclip_gemm_bf16_splitk_plan(int M, int N, int K) {
-  if (K % BKH == 0 && pingpong_enabled()) {                   // 256x256 ping-pong kernel, one workgroup per CU
+// fp16 training path: layernorm_fwd_bf16_stats with an fp16 result, IEEE rounding
+DCLIP_API int dclip_layernorm_fwd_f16_stats(const float* x, const float* gamma, const float* beta, void* y, float* mean,
+                                            float* rstd, int rows, int D, float eps, void* stream) {
+  return layernorm16<F16IeeeT>("layernorm_fwd_f16_stats", x, gamma, beta, y, mean, rstd, rows, D, eps, stream);
+}
+
+namespace {
+int splitk_plan(int M, int N, int K, bool pp) {
+  if (K % BKH == 0 && pp) {                                  // 256x256 ping-pong kernel, one workgroup per CU
     const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
     if (t256 >= 128 || K < 2048) return 1;
     int s = (int)(256 / t256);
@@ -1565,44 +1617,69 @@ DCLIP_API int dclip_gemm_bf16_splitk_plan(int M, int N, int K) {
   return s < 2 ? 1 : (s > 64 ? 64 : s);
 }
 
-DCLIP_API size_t dclip_gemm_bf16_splitk_workspace(int M, int N, int splits) {
-  return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
-}
-
-DCLIP_API int dclip_gemm_bf16_splitk(const void* A, const void* W, float* C, int M, int N, int K, int lda, int ldw, int ldc,
-                                     int splits, void* workspace, size_t workspace_bytes, void* stream) {
-  DCLIP_REQUIRE(A && W && C, "gemm_bf16_splitk: null operand");
-  DCLIP_REQUIRE(M > 0 && N > 0 && K > 0 && splits >= 1 && splits <= 1024, "gemm_bf16_splitk: bad shape");
-  DCLIP_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "gemm_bf16_splitk: lda/ldw must be multiples of 8 and >= K");
-  DCLIP_REQUIRE(N % 4 == 0 && ldc % 4 == 0 && ldc >= N, "gemm_bf16_splitk: N / ldc must be multiples of 4");
-  DCLIP_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 == 0, "gemm_bf16_splitk: operands must be 16-byte aligned");
-  if (splits == 1) return dclip_gemm_bf16_ex(A, W, C, nullptr, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, stream);
+template <class T>
+int splitk16(const char* name, const void* A, const void* W, float* C, int M, int N, int K, int lda, int ldw, int ldc, int splits,
+             void* workspace, size_t workspace_bytes, void* stream) {
+  DCLIP_REQUIRE(A && W && C, "%s: null operand", name);
+  DCLIP_REQUIRE(M > 0 && N > 0 && K > 0 && splits >= 1 && splits <= 1024, "%s: bad shape", name);
+  DCLIP_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "%s: lda/ldw must be multiples of 8 and >= K", name);
+  DCLIP_REQUIRE(N % 4 == 0 && ldc % 4 == 0 && ldc >= N, "%s: N / ldc must be multiples of 4", name);
+  DCLIP_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 == 0, "%s: operands must be 16-byte aligned", name);
+  if (splits == 1) return gemm16<T>(name, A, W, C, nullptr, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, stream);
   const int kps = cdiv(cdiv(K, splits), BKH) * BKH;
   const int s_eff = cdiv(K, kps);
   const size_t need = (size_t)s_eff * M * N * sizeof(float);
   if (!workspace || workspace_bytes < need) {
-    dclip_set_error("gemm_bf16_splitk: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+    dclip_set_error("%s: needs %zu workspace bytes, got %zu", name, need, workspace_bytes);
     return DCLIP_EWORKSPACE;
   }
-  DCLIP_REQUIRE((uintptr_t)workspace % 16 == 0, "gemm_bf16_splitk: workspace must be 16-byte aligned");
-  if (K % BKH == 0 && pingpong_enabled() && (long)cdiv(M, 256) * cdiv(N, 256) * s_eff >= 128) {
+  DCLIP_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", name);
+  if (K % BKH == 0 && pp16<T>() && (long)cdiv(M, 256) * cdiv(N, 256) * s_eff >= 128) {
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, 0, nullptr, kps,
                       (float*)workspace};
-    launch_pp<Bf16T>(pb, (hipStream_t)stream, s_eff);
-    DCLIP_CHECK_LAUNCH("gemm_bf16_splitk.pp");
+    launch_pp<T>(pb, (hipStream_t)stream, s_eff);
+    DCLIP_CHECK_LAUNCH(name);
     hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const float*)workspace, C, M, N, ldc, s_eff);
-    DCLIP_CHECK_LAUNCH("gemm_bf16_splitk.reduce");
+    DCLIP_CHECK_LAUNCH(name);
     return DCLIP_OK;
   }
   GemmBf16Params p{(const __bf16*)A, (const __bf16*)W, C, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0,
                    cdiv(M, 128), cdiv(N, 128), nullptr, kps, (float*)workspace};
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)2 * (128 + 128) * BKH * 2;
-  hipLaunchKernelGGL((gemm_bf16_kernel<Bf16T, 128, 128>), dim3(p.tiles_m * p.tiles_n, s_eff), dim3(256), lds, st, p);
-  DCLIP_CHECK_LAUNCH("gemm_bf16_splitk");
+  hipLaunchKernelGGL((gemm_bf16_kernel<T, 128, 128>), dim3(p.tiles_m * p.tiles_n, s_eff), dim3(256), lds, st, p);
+  DCLIP_CHECK_LAUNCH(name);
   hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, st, (const float*)workspace, C,
                      M, N, ldc, s_eff);
-  DCLIP_CHECK_LAUNCH("gemm_bf16_splitk.reduce");
+  DCLIP_CHECK_LAUNCH(name);
   return DCLIP_OK;
+}
+}  // namespace
+
+// Split-K form for products with few output tiles and a long contraction — the weight gradients of the bf16 training
+// path, dW[out,in] = (dY^T)[out,tok] (X^T)[in,tok]^T with tok = batch x sequence (12,800 .. 25,600): `splits` work items
+// per 128x128 tile write fp32 partials to the caller's workspace, a second kernel sums them in fixed order.  fp32 C, no
+// epilogue.  dclip_gemm_bf16_splitk_plan returns the split count this library would choose (1 = use dclip_gemm_bf16).
+DCLIP_API int dclip_gemm_bf16_splitk_plan(int M, int N, int K) { return splitk_plan(M, N, K, pingpong_enabled()); }
+
+DCLIP_API size_t dclip_gemm_bf16_splitk_workspace(int M, int N, int splits) {
+  return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
+}
+
+DCLIP_API int dclip_gemm_bf16_splitk(const void* A, const void* W, float* C, int M, int N, int K, int lda, int ldw, int ldc,
+                                     int splits, void* workspace, size_t workspace_bytes, void* stream) {
+  return splitk16<Bf16T>("gemm_bf16_splitk", A, W, C, M, N, K, lda, ldw, ldc, splits, workspace, workspace_bytes, stream);
+}
+
+// fp16 twins of the split-K form (training path; DCLIP_BF16_PP does not apply)
+DCLIP_API int dclip_gemm_f16_splitk_plan(int M, int N, int K) { return splitk_plan(M, N, K, true); }
+
+DCLIP_API size_t dclip_gemm_f16_splitk_workspace(int M, int N, int splits) {
+  return dclip_gemm_bf16_splitk_workspace(M, N, splits);
+}
+
+DCLIP_API int dclip_gemm_f16_splitk(const void* A, const void* W, float* C, int M, int N, int K, int lda, int ldw, int ldc,
+                                    int splits, void* workspace, size_t workspace_bytes, void* stream) {
+  return splitk16<F16IeeeT>("gemm_f16_splitk", A, W, C, M, N, K, lda, ldw, ldc, splits, workspace, workspace_bytes, stream);
 }

@@ -63,7 +63,8 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
 // bf16 training path (NS == 3 / dx16): the same pass also leaves what the NEXT two launches of the backward would
 // otherwise re-read dx for — its bf16 copy (the A operand of the following data- and weight-gradient GEMMs: no cast
 // launch) and its column sums (the bias gradient of the Linear whose output gradient dx is: no colsum launch).
-template <int NC, bool EXACT>
+// T: the 16-bit type of dx16 (common.h; Bf16T, or F16IeeeT for the fp16 training path).
+template <class T, int NC, bool EXACT>
 __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const float* __restrict__ dres,
@@ -127,7 +128,7 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ d
           typedef unsigned short u16x4_t __attribute__((ext_vector_type(4)));
           u16x4_t b;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) b[e] = __builtin_bit_cast(unsigned short, (__bf16)o[e]);
+          for (int e = 0; e < 4; ++e) b[e] = T::bits(o[e]);
           *reinterpret_cast<u16x4_t*>(dx16 + (size_t)row * D + i * 4) = b;
         }
       }
@@ -187,7 +188,8 @@ __global__ void __launch_bounds__(1024) reduce_partials_kernel(const float* __re
 }
 
 // column sums: block = 64 float4-columns x 4 row lanes; grid.y splits the rows
-// bf16 form (the fc1 bias gradient of the bf16 training path: dh exists only as bf16 [tokens][I])
+// 16-bit form (the fc1 bias gradient of the 16-bit training path: dh exists only as bf16 / fp16 [tokens][I])
+template <class T>
 __global__ void __launch_bounds__(256) colsum_bf16_kernel(const unsigned short* __restrict__ X, float* __restrict__ partial, int M,
                                                           int N, int ldx) {
   typedef unsigned short u16x4_t __attribute__((ext_vector_type(4)));
@@ -202,7 +204,7 @@ __global__ void __launch_bounds__(256) colsum_bf16_kernel(const unsigned short* 
     for (int r = r0 + rl; r < r1; r += 4) {
       const u16x4_t b = *reinterpret_cast<const u16x4_t*>(X + (size_t)r * ldx + c4 * 4);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] += __builtin_bit_cast(float, (unsigned int)b[e] << 16);
+      for (int e = 0; e < 4; ++e) s[e] += T::to_f32(b[e]);
     }
   }
   red[rl][cl] = s;
@@ -278,18 +280,18 @@ DCLIP_API int dclip_layernorm_bwd(const float* dy, const float* x, const float* 
                                 accumulate_param_grads, workspace, workspace_bytes, stream);
 }
 
-DCLIP_API int dclip_layernorm_bwd_ex(const float* dy, const float* x, const float* gamma, const float* mean,
-                                     const float* rstd, const float* dresidual, float* dx, void* dx_bf16, float* dgamma,
-                                     float* dbeta, float* dx_colsum, int rows, int D, int accumulate_param_grads,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-  DCLIP_REQUIRE(dy && x && gamma && mean && rstd && dx, "layernorm_bwd: null pointer");
-  DCLIP_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 256 * MAXC, "layernorm_bwd: bad D=%d", D);
-  DCLIP_REQUIRE(!dx_bf16 || (uintptr_t)dx_bf16 % 8 == 0, "layernorm_bwd: dx_bf16 must be 8-byte aligned");
+namespace {
+template <class T>
+int layernorm_bwd16(const char* name, const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                    const float* dresidual, float* dx, void* dx_16, float* dgamma, float* dbeta, float* dx_colsum, int rows, int D,
+                    int accumulate_param_grads, void* workspace, size_t workspace_bytes, void* stream) {
+  DCLIP_REQUIRE(dy && x && gamma && mean && rstd && dx, "%s: null pointer", name);
+  DCLIP_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 256 * MAXC, "%s: bad D=%d", name, D);
+  DCLIP_REQUIRE(!dx_16 || (uintptr_t)dx_16 % 8 == 0, "%s: the 16-bit dx must be 8-byte aligned", name);
   const bool want_params = dgamma || dbeta || dx_colsum;
   const int blocks = ln_bwd_blocks(rows);
   if (want_params && (!workspace || workspace_bytes < dclip_layernorm_bwd_workspace(rows, D))) {
-    dclip_set_error("layernorm_bwd: workspace too small (%zu < %zu)", workspace_bytes,
-                    dclip_layernorm_bwd_workspace(rows, D));
+    dclip_set_error("%s: workspace too small (%zu < %zu)", name, workspace_bytes, dclip_layernorm_bwd_workspace(rows, D));
     return DCLIP_EWORKSPACE;
   }
   float* partial = want_params ? (float*)workspace : nullptr;
@@ -297,10 +299,10 @@ DCLIP_API int dclip_layernorm_bwd_ex(const float* dy, const float* x, const floa
   const int ns = dx_colsum ? 3 : 2;
   const size_t lds = want_params ? (size_t)4 * ns * D * sizeof(float) : 0;
   const int nc = cdiv(D / 4, 64);
-  unsigned short* dx16 = (unsigned short*)dx_bf16;
+  unsigned short* dx16 = (unsigned short*)dx_16;
 #define LN_BWD(NC, EX)                                                                                                      \
-  hipLaunchKernelGGL((ln_bwd_kernel<NC, EX>), dim3(blocks), dim3(256), lds, st, dy, x, gamma, mean, rstd, dresidual, dx, partial, \
-                     rows, D, dx16, ns)
+  hipLaunchKernelGGL((ln_bwd_kernel<T, NC, EX>), dim3(blocks), dim3(256), lds, st, dy, x, gamma, mean, rstd, dresidual, dx,     \
+                     partial, rows, D, dx16, ns)
   if (D == 512) LN_BWD(2, true);
   else if (D == 768) LN_BWD(3, true);
   else if (D == 1024) LN_BWD(4, true);
@@ -310,13 +312,52 @@ DCLIP_API int dclip_layernorm_bwd_ex(const float* dy, const float* x, const floa
   else if (nc == 4) LN_BWD(4, false);
   else LN_BWD(8, false);
 #undef LN_BWD
-  DCLIP_CHECK_LAUNCH("layernorm_bwd");
+  DCLIP_CHECK_LAUNCH(name);
   if (want_params) {
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(cdiv(ns * D, RP_COLS)), dim3(1024), 0, st, partial, dgamma, dbeta, blocks, D,
                        D, accumulate_param_grads, dx_colsum, dx_colsum ? D : 0);
-    DCLIP_CHECK_LAUNCH("layernorm_bwd.reduce");
+    DCLIP_CHECK_LAUNCH(name);
   }
   return DCLIP_OK;
+}
+
+template <class T>
+int colsum16(const char* name, const void* X, float* out, int M, int N, int ldx, int accumulate, void* workspace,
+             size_t workspace_bytes, void* stream) {
+  DCLIP_REQUIRE(X && out, "%s: null pointer", name);
+  DCLIP_REQUIRE(M > 0 && N > 0 && N % 4 == 0 && ldx % 4 == 0 && ldx >= N, "%s: bad shape M=%d N=%d ldx=%d", name, M, N, ldx);
+  DCLIP_REQUIRE((uintptr_t)X % 8 == 0, "%s: alignment", name);
+  const int splits = colsum_splits(M);
+  if (!workspace || workspace_bytes < (size_t)splits * N * sizeof(float)) {
+    dclip_set_error("%s: workspace too small", name);
+    return DCLIP_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(colsum_bf16_kernel<T>, dim3(cdiv(N / 4, 64), splits), dim3(256), 0, st, (const unsigned short*)X,
+                     (float*)workspace, M, N, ldx);
+  DCLIP_CHECK_LAUNCH(name);
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3(cdiv(N, RP_COLS)), dim3(1024), 0, st, (const float*)workspace, out,
+                     (float*)nullptr, splits, N, 0, accumulate);
+  DCLIP_CHECK_LAUNCH(name);
+  return DCLIP_OK;
+}
+}  // namespace
+
+DCLIP_API int dclip_layernorm_bwd_ex(const float* dy, const float* x, const float* gamma, const float* mean,
+                                     const float* rstd, const float* dresidual, float* dx, void* dx_bf16, float* dgamma,
+                                     float* dbeta, float* dx_colsum, int rows, int D, int accumulate_param_grads,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  return layernorm_bwd16<Bf16T>("layernorm_bwd", dy, x, gamma, mean, rstd, dresidual, dx, dx_bf16, dgamma, dbeta, dx_colsum,
+                                rows, D, accumulate_param_grads, workspace, workspace_bytes, stream);
+}
+
+// fp16 training path: dclip_layernorm_bwd_ex with an fp16 copy of dx (IEEE rounding: beyond +-65504 -> +-inf)
+DCLIP_API int dclip_layernorm_bwd_ex_f16(const float* dy, const float* x, const float* gamma, const float* mean,
+                                         const float* rstd, const float* dresidual, float* dx, void* dx_f16, float* dgamma,
+                                         float* dbeta, float* dx_colsum, int rows, int D, int accumulate_param_grads,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return layernorm_bwd16<F16IeeeT>("layernorm_bwd_f16", dy, x, gamma, mean, rstd, dresidual, dx, dx_f16, dgamma, dbeta, dx_colsum,
+                                   rows, D, accumulate_param_grads, workspace, workspace_bytes, stream);
 }
 
 DCLIP_API size_t dclip_colsum_f32_workspace(int M, int N) { return (size_t)colsum_splits(M) * N * sizeof(float); }
@@ -342,20 +383,11 @@ DCLIP_API int dclip_colsum_f32(const float* X, float* out, int M, int N, int ldx
 // out[n] = sum_m X[m][n] over a bf16 matrix [M][ldx] (same workspace size as dclip_colsum_f32_workspace(M, N))
 DCLIP_API int dclip_colsum_bf16(const void* X, float* out, int M, int N, int ldx, int accumulate, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-  DCLIP_REQUIRE(X && out, "colsum_bf16: null pointer");
-  DCLIP_REQUIRE(M > 0 && N > 0 && N % 4 == 0 && ldx % 4 == 0 && ldx >= N, "colsum_bf16: bad shape M=%d N=%d ldx=%d", M, N, ldx);
-  DCLIP_REQUIRE((uintptr_t)X % 8 == 0, "colsum_bf16: alignment");
-  const int splits = colsum_splits(M);
-  if (!workspace || workspace_bytes < (size_t)splits * N * sizeof(float)) {
-    dclip_set_error("colsum_bf16: workspace too small");
-    return DCLIP_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(colsum_bf16_kernel, dim3(cdiv(N / 4, 64), splits), dim3(256), 0, st, (const unsigned short*)X,
-                     (float*)workspace, M, N, ldx);
-  DCLIP_CHECK_LAUNCH("colsum_bf16");
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3(cdiv(N, RP_COLS)), dim3(1024), 0, st, (const float*)workspace, out,
-                     (float*)nullptr, splits, N, 0, accumulate);
-  DCLIP_CHECK_LAUNCH("colsum_bf16.reduce");
-  return DCLIP_OK;
+  return colsum16<Bf16T>("colsum_bf16", X, out, M, N, ldx, accumulate, workspace, workspace_bytes, stream);
+}
+
+// the same over an fp16 matrix (fp16 training path)
+DCLIP_API int dclip_colsum_f16(const void* X, float* out, int M, int N, int ldx, int accumulate, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  return colsum16<F16IeeeT>("colsum_f16", X, out, M, N, ldx, accumulate, workspace, workspace_bytes, stream);
 }

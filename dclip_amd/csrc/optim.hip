@@ -38,6 +38,50 @@ __global__ void __launch_bounds__(256) clip_coef_kernel(const float* __restrict_
   }
 }
 
+// Loss-scaled form of clip_coef_kernel: the partial sums are those of the SCALED gradients.  out[0] = the unscaled norm,
+// out[1] = found_inf (1 when that norm is not finite: an inf / NaN gradient, or a sum of squares beyond fp32's range),
+// out[2] = min(1, max_norm / (norm + 1e-6)) / scale — unscaling folded into the clip coefficient — or 0 with found_inf.
+__global__ void __launch_bounds__(256) clip_coef_scaled_kernel(const float* __restrict__ partial, int n, float max_norm,
+                                                               const float* __restrict__ scale, float* __restrict__ out) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float sc = *scale;
+    const float nrm = sqrtf((red[0] + red[1]) + (red[2] + red[3])) / sc;
+    const bool bad = !__builtin_isfinite(nrm);
+    out[0] = nrm;
+    out[1] = bad ? 1.0f : 0.0f;
+    out[2] = bad ? 0.0f : fminf(1.0f, max_norm / (nrm + 1e-6f)) / sc;
+  }
+}
+
+// torch._amp_update_scale_ (aten/src/ATen/native/cuda/AmpKernels.cu): one lane, plain stores.
+//   found_inf: scale *= backoff, tracker = 0;  else tracker + 1 == interval: scale *= growth (kept only if finite),
+//   tracker = 0;  else tracker += 1.
+__global__ void __launch_bounds__(64) amp_update_scale_kernel(float* __restrict__ scale, int* __restrict__ tracker,
+                                                              const float* __restrict__ found_inf, float growth, float backoff,
+                                                              int interval) {
+  if (threadIdx.x != 0) return;
+  const float s = *scale;
+  if (*found_inf != 0.0f) {
+    *scale = s * backoff;
+    *tracker = 0;
+    return;
+  }
+  const int t = *tracker + 1;
+  if (t == interval) {
+    const float g = s * growth;
+    if (__builtin_isfinite(g)) *scale = g;
+    *tracker = 0;
+  } else {
+    *tracker = t;
+  }
+}
+
 __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, size_t n, float lr, float beta1, float beta2,
                                                     float eps, float wd, float bc1, float bc2_sqrt,
@@ -121,17 +165,25 @@ __global__ void __launch_bounds__(256) mt_sumsq_kernel(const TensorRef* __restri
 }
 
 // COUPLED = false: AdamW (decoupled decay, torch.optim.AdamW);  COUPLED = true: Adam with L2 folded into the gradient
-// (g += wd * p, torch.optim.Adam — the teacher trainer's optimizer, training/train_contrastive_teacher.py:245-248)
-template <bool COUPLED>
+// (g += wd * p, torch.optim.Adam — the teacher trainer's optimizer, training/train_contrastive_teacher.py:245-248).
+// SKIP (dclip_mt_adamw_f32_skip, the loss-scaled step of amp.DynamicLossScaler): grad_scale points at dclip_clip_coef_scaled's
+// {norm, found_inf, coefficient}; with found_inf set the kernel returns before writing anything (GradScaler skips
+// optimizer.step), otherwise the coefficient is grad_scale[2].  Its beta1 / beta2 arguments carry 1 - beta1 / 1 - beta2 as the
+// host computes them in double (torch's `1 - beta2`: fp32's 1.0f - 0.999f is off by 1.3e-5), and the bias corrections
+// 1 - beta^step come from expm1 / log1p of them.  The SKIP differences are written in place (constant-condition selects), so
+// the other instances compile to the instructions they had before the flag existed (tools/disasm_compare.py).
+template <bool COUPLED, bool SKIP = false>
 __global__ void __launch_bounds__(256) mt_adamw_kernel(const TensorRef* __restrict__ refs, int ntensors, float lr, float beta1,
                                                        float beta2, float eps, float wd, const float* __restrict__ grad_scale) {
+  if (SKIP && grad_scale[1] != 0.0f) return;
+  if (SKIP) grad_scale += 2;
   const int chunk = blockIdx.x;
   const TensorRef t = refs[find_tensor(refs, ntensors, chunk)];
   const size_t beg = (size_t)(chunk - t.chunk0) * MT_CHUNK;
   const size_t end = beg + MT_CHUNK < t.n ? beg + MT_CHUNK : (size_t)t.n;
   const float gs = grad_scale ? *grad_scale : 1.0f;
-  const float bc1 = 1.0f - powf(beta1, (float)t.step);
-  const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)t.step));
+  const float bc1 = SKIP ? -expm1f((float)t.step * log1pf(-beta1)) : 1.0f - powf(beta1, (float)t.step);
+  const float bc2_sqrt = sqrtf(SKIP ? -expm1f((float)t.step * log1pf(-beta2)) : 1.0f - powf(beta2, (float)t.step));
   const float decay = COUPLED ? 1.0f : 1.0f - lr * wd, step = lr / bc1;
   const bool vec = (((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) % 16) == 0;
   size_t e4 = vec ? beg + ((end - beg) & ~(size_t)3) : beg;
@@ -144,8 +196,8 @@ __global__ void __launch_bounds__(256) mt_adamw_kernel(const TensorRef* __restri
     }
     f32x4 mv = *reinterpret_cast<f32x4*>(t.m + i);
     f32x4 vv = *reinterpret_cast<f32x4*>(t.v + i);
-    mv = mv * beta1 + gv * (1.0f - beta1);
-    vv = vv * beta2 + gv * gv * (1.0f - beta2);
+    mv = mv * (SKIP ? 1.0f - beta1 : beta1) + gv * (SKIP ? beta1 : 1.0f - beta1);
+    vv = vv * (SKIP ? 1.0f - beta2 : beta2) + gv * gv * (SKIP ? beta2 : 1.0f - beta2);
     f32x4 out;
 #pragma unroll
     for (int e = 0; e < 4; ++e) out[e] = pv[e] * decay - step * mv[e] / (sqrtf(vv[e]) / bc2_sqrt + eps);
@@ -156,8 +208,8 @@ __global__ void __launch_bounds__(256) mt_adamw_kernel(const TensorRef* __restri
   for (size_t i = e4 + threadIdx.x; i < end; i += 256) {
     const float gsc = t.g[i] * gs;            // the product first, then ONE fma: the same rounding as the vector path above
     const float gg = COUPLED ? __builtin_fmaf(t.p[i], wd, gsc) : gsc;
-    const float mm = t.m[i] * beta1 + gg * (1.0f - beta1);
-    const float vv = t.v[i] * beta2 + gg * gg * (1.0f - beta2);
+    const float mm = t.m[i] * (SKIP ? 1.0f - beta1 : beta1) + gg * (SKIP ? beta1 : 1.0f - beta1);
+    const float vv = t.v[i] * (SKIP ? 1.0f - beta2 : beta2) + gg * gg * (SKIP ? beta2 : 1.0f - beta2);
     t.p[i] = t.p[i] * decay - step * mm / (sqrtf(vv) / bc2_sqrt + eps);
     t.m[i] = mm;
     t.v[i] = vv;
@@ -229,5 +281,31 @@ DCLIP_API int dclip_mt_adam_f32(const void* refs, int ntensors, int total_chunks
   hipLaunchKernelGGL(mt_adamw_kernel<true>, dim3(total_chunks), dim3(256), 0, (hipStream_t)stream, (const TensorRef*)refs,
                      ntensors, lr, beta1, beta2, eps, weight_decay, grad_scale);
   DCLIP_CHECK_LAUNCH("mt_adam");
+  return DCLIP_OK;
+}
+
+// ---- dynamic loss scaling (fp16 training, amp.DynamicLossScaler) ----------------------------------------
+DCLIP_API int dclip_clip_coef_scaled(const float* partial, int n, float max_norm, const float* scale, float* out, void* stream) {
+  DCLIP_REQUIRE(partial && scale && out && n > 0, "clip_coef_scaled: bad arguments");
+  hipLaunchKernelGGL(clip_coef_scaled_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, n, max_norm, scale, out);
+  DCLIP_CHECK_LAUNCH("clip_coef_scaled");
+  return DCLIP_OK;
+}
+
+DCLIP_API int dclip_mt_adamw_f32_skip(const void* refs, int ntensors, int total_chunks, float lr, float one_minus_beta1,
+                                      float one_minus_beta2, float eps, float weight_decay, const float* coef3, void* stream) {
+  DCLIP_REQUIRE(refs && coef3 && ntensors > 0 && total_chunks > 0, "mt_adamw_skip: bad arguments");
+  hipLaunchKernelGGL((mt_adamw_kernel<false, true>), dim3(total_chunks), dim3(256), 0, (hipStream_t)stream,
+                     (const TensorRef*)refs, ntensors, lr, one_minus_beta1, one_minus_beta2, eps, weight_decay, coef3);
+  DCLIP_CHECK_LAUNCH("mt_adamw_skip");
+  return DCLIP_OK;
+}
+
+DCLIP_API int dclip_amp_update_scale(float* scale, int* growth_tracker, const float* found_inf, float growth_factor,
+                                     float backoff_factor, int growth_interval, void* stream) {
+  DCLIP_REQUIRE(scale && growth_tracker && found_inf && growth_interval > 0, "amp_update_scale: bad arguments");
+  hipLaunchKernelGGL(amp_update_scale_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scale, growth_tracker, found_inf,
+                     growth_factor, backoff_factor, growth_interval);
+  DCLIP_CHECK_LAUNCH("amp_update_scale");
   return DCLIP_OK;
 }

@@ -5,6 +5,8 @@
 //   transpose_to_bf16 : x [rows][cols] (fp32 or bf16) -> x^T [cols][ld >= rows] bf16, zero padded to ld, and optionally the
 //                       untransposed bf16 copy in the same pass (dgrad's A operand) — HBM-bound, 64x64 tiles through LDS.
 //   rowsum_bf16       : out[r] = sum_c x[r][c] over a bf16 matrix (bias gradient from an already transposed dY^T).
+// Every kernel is a template over the 16-bit type (common.h): Bf16T for the bf16 entries, F16IeeeT for their fp16 twins
+// (dclip_transpose_to_f16, dclip_mt_weights_f16, dclip_rowsum_f16; fp16 training path).
 #include "common.h"
 
 namespace {
@@ -12,16 +14,11 @@ namespace {
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ unsigned short bf16_bits(float x) {
-  __bf16 b = (__bf16)x;  // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
-  return __builtin_bit_cast(unsigned short, b);
-}
-
 constexpr int TT = 64;        // tile edge
 constexpr int TPAD = TT + 2;  // LDS row stride in 16-bit elements: 132 bytes -> a column walk hits 32 distinct banks
 
-// grid (ceil(cols/64), ceil(rows/64)); 256 threads.  X_BF16: input element type.
-template <bool X_BF16>
+// grid (ceil(cols/64), ceil(rows/64)); 256 threads.  X_BF16: the input is already of the 16-bit type T (else fp32).
+template <class T, bool X_BF16>
 __global__ void __launch_bounds__(256) transpose_to_bf16_kernel(const void* __restrict__ xv, unsigned short* __restrict__ yT,
                                                                 unsigned short* __restrict__ ycopy, int rows, int cols, int ldx,
                                                                 int ldyT, int ldy) {
@@ -45,10 +42,10 @@ __global__ void __launch_bounds__(256) transpose_to_bf16_kernel(const void* __re
         const float* x = reinterpret_cast<const float*>(xv) + (size_t)r * ldx + c;
         if (c + 3 < cols) {
           const f32x4 v = *reinterpret_cast<const f32x4*>(x);
-          b = u16x4{bf16_bits(v[0]), bf16_bits(v[1]), bf16_bits(v[2]), bf16_bits(v[3])};
+          b = u16x4{T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
         } else {
           for (int e = 0; e < 4; ++e)
-            if (c + e < cols) b[e] = bf16_bits(x[e]);
+            if (c + e < cols) b[e] = T::bits(x[e]);
         }
       }
       if (ycopy && c < cols) {
@@ -90,6 +87,7 @@ struct WeightRef {
   int tile0, tiles_c;     // first tile index of this tensor; tiles per tile-row
 };
 
+template <class T>
 __global__ void __launch_bounds__(256) mt_weights_bf16_kernel(const WeightRef* __restrict__ refs, int ntensors) {
   __shared__ unsigned short tile[TT * TPAD];
   int lo = 0, hi = ntensors - 1;                      // last record with tile0 <= blockIdx.x (uniform: scalar code)
@@ -111,10 +109,10 @@ __global__ void __launch_bounds__(256) mt_weights_bf16_kernel(const WeightRef* _
       const float* x = t.src + (size_t)r * t.cols + c;
       if (c + 3 < t.cols) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(x);
-        b = u16x4{bf16_bits(v[0]), bf16_bits(v[1]), bf16_bits(v[2]), bf16_bits(v[3])};
+        b = u16x4{T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
       } else {
         for (int e = 0; e < 4; ++e)
-          if (c + e < t.cols) b[e] = bf16_bits(x[e]);
+          if (c + e < t.cols) b[e] = T::bits(x[e]);
       }
       if (t.dst && c < t.ld) *reinterpret_cast<u16x4*>(t.dst + (size_t)r * t.ld + c) = b;   // ld % 4 == 0; zeros past cols
     }
@@ -137,6 +135,7 @@ __global__ void __launch_bounds__(256) mt_weights_bf16_kernel(const WeightRef* _
 }
 
 // one wave per row
+template <class T>
 __global__ void __launch_bounds__(256) rowsum_bf16_kernel(const unsigned short* __restrict__ x, float* __restrict__ out, int R,
                                                           int n, int ld) {
   const int lane = threadIdx.x & 63;
@@ -148,50 +147,82 @@ __global__ void __launch_bounds__(256) rowsum_bf16_kernel(const unsigned short* 
   for (int i = lane * 8; i < n8; i += 512) {
     const u16x8 b = *reinterpret_cast<const u16x8*>(xr + i);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s += __builtin_bit_cast(float, (unsigned int)b[e] << 16);
+    for (int e = 0; e < 8; ++e) s += T::to_f32(b[e]);
   }
-  for (int i = n8 + lane; i < n; i += 64) s += __builtin_bit_cast(float, (unsigned int)xr[i] << 16);
+  for (int i = n8 + lane; i < n; i += 64) s += T::to_f32(xr[i]);
   s = wave_sum(s);
   if (lane == 0) out[row] = s;
 }
 
 }  // namespace
 
-DCLIP_API int dclip_transpose_to_bf16(const void* x, int x_is_bf16, void* yT, void* y_copy, int rows, int cols, int ldx,
-                                      int ldyT, int ldy, void* stream) {
-  DCLIP_REQUIRE(x && yT && rows > 0 && cols > 0, "transpose_to_bf16: bad arguments");
-  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "transpose_to_bf16: ldx must be >= cols and a multiple of 4");
-  DCLIP_REQUIRE(ldyT >= rows && ldyT % 8 == 0, "transpose_to_bf16: ldyT must be >= rows and a multiple of 8");
-  DCLIP_REQUIRE(!y_copy || (ldy >= cols && ldy % 4 == 0), "transpose_to_bf16: ldy must be >= cols and a multiple of 4");
-  DCLIP_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)yT % 16 == 0 && (uintptr_t)y_copy % 8 == 0, "transpose_to_bf16: alignment");
+namespace {
+template <class T>
+int transpose16(const char* name, const void* x, int x_is_16, void* yT, void* y_copy, int rows, int cols, int ldx, int ldyT,
+                int ldy, void* stream) {
+  DCLIP_REQUIRE(x && yT && rows > 0 && cols > 0, "%s: bad arguments", name);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "%s: ldx must be >= cols and a multiple of 4", name);
+  DCLIP_REQUIRE(ldyT >= rows && ldyT % 8 == 0, "%s: ldyT must be >= rows and a multiple of 8", name);
+  DCLIP_REQUIRE(!y_copy || (ldy >= cols && ldy % 4 == 0), "%s: ldy must be >= cols and a multiple of 4", name);
+  DCLIP_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)yT % 16 == 0 && (uintptr_t)y_copy % 8 == 0, "%s: alignment", name);
   // the padded tail columns rows..ldyT-1 of every output row are written as zeros by the last row-tile
   dim3 grid(cdiv(cols, TT), cdiv(ldyT, TT));
   hipStream_t st = (hipStream_t)stream;
-  if (x_is_bf16)
-    hipLaunchKernelGGL((transpose_to_bf16_kernel<true>), grid, dim3(256), 0, st, x, (unsigned short*)yT, (unsigned short*)y_copy,
+  if (x_is_16)
+    hipLaunchKernelGGL((transpose_to_bf16_kernel<T, true>), grid, dim3(256), 0, st, x, (unsigned short*)yT, (unsigned short*)y_copy,
                        rows, cols, ldx, ldyT, ldy);
   else
-    hipLaunchKernelGGL((transpose_to_bf16_kernel<false>), grid, dim3(256), 0, st, x, (unsigned short*)yT,
+    hipLaunchKernelGGL((transpose_to_bf16_kernel<T, false>), grid, dim3(256), 0, st, x, (unsigned short*)yT,
                        (unsigned short*)y_copy, rows, cols, ldx, ldyT, ldy);
-  DCLIP_CHECK_LAUNCH("transpose_to_bf16");
+  DCLIP_CHECK_LAUNCH(name);
   return DCLIP_OK;
+}
+
+template <class T>
+int mt_weights16(const char* name, const void* refs, int ntensors, int total_tiles, void* stream) {
+  DCLIP_REQUIRE(refs && ntensors > 0 && total_tiles > 0, "%s: bad arguments", name);
+  hipLaunchKernelGGL(mt_weights_bf16_kernel<T>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const WeightRef*)refs,
+                     ntensors);
+  DCLIP_CHECK_LAUNCH(name);
+  return DCLIP_OK;
+}
+
+template <class T>
+int rowsum16(const char* name, const void* x, float* out, int R, int n, int ld, void* stream) {
+  DCLIP_REQUIRE(x && out && R > 0 && n > 0 && ld >= n && ld % 8 == 0, "%s: bad arguments", name);
+  DCLIP_REQUIRE((uintptr_t)x % 16 == 0, "%s: alignment", name);
+  hipLaunchKernelGGL(rowsum_bf16_kernel<T>, dim3(cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, out, R,
+                     n, ld);
+  DCLIP_CHECK_LAUNCH(name);
+  return DCLIP_OK;
+}
+}  // namespace
+
+DCLIP_API int dclip_transpose_to_bf16(const void* x, int x_is_bf16, void* yT, void* y_copy, int rows, int cols, int ldx,
+                                      int ldyT, int ldy, void* stream) {
+  return transpose16<Bf16T>("transpose_to_bf16", x, x_is_bf16, yT, y_copy, rows, cols, ldx, ldyT, ldy, stream);
 }
 
 DCLIP_API int dclip_mt_weights_record_bytes(void) { return (int)sizeof(WeightRef); }
 
 DCLIP_API int dclip_mt_weights_bf16(const void* refs, int ntensors, int total_tiles, void* stream) {
-  DCLIP_REQUIRE(refs && ntensors > 0 && total_tiles > 0, "mt_weights_bf16: bad arguments");
-  hipLaunchKernelGGL(mt_weights_bf16_kernel, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const WeightRef*)refs,
-                     ntensors);
-  DCLIP_CHECK_LAUNCH("mt_weights_bf16");
-  return DCLIP_OK;
+  return mt_weights16<Bf16T>("mt_weights_bf16", refs, ntensors, total_tiles, stream);
 }
 
 DCLIP_API int dclip_rowsum_bf16(const void* x, float* out, int R, int n, int ld, void* stream) {
-  DCLIP_REQUIRE(x && out && R > 0 && n > 0 && ld >= n && ld % 8 == 0, "rowsum_bf16: bad arguments");
-  DCLIP_REQUIRE((uintptr_t)x % 16 == 0, "rowsum_bf16: alignment");
-  hipLaunchKernelGGL(rowsum_bf16_kernel, dim3(cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, out, R,
-                     n, ld);
-  DCLIP_CHECK_LAUNCH("rowsum_bf16");
-  return DCLIP_OK;
+  return rowsum16<Bf16T>("rowsum_bf16", x, out, R, n, ld, stream);
+}
+
+// fp16 twins (training path): x fp32 or fp16, fp16 outputs with IEEE rounding (common.h, F16IeeeT)
+DCLIP_API int dclip_transpose_to_f16(const void* x, int x_is_f16, void* yT, void* y_copy, int rows, int cols, int ldx,
+                                     int ldyT, int ldy, void* stream) {
+  return transpose16<F16IeeeT>("transpose_to_f16", x, x_is_f16, yT, y_copy, rows, cols, ldx, ldyT, ldy, stream);
+}
+
+DCLIP_API int dclip_mt_weights_f16(const void* refs, int ntensors, int total_tiles, void* stream) {
+  return mt_weights16<F16IeeeT>("mt_weights_f16", refs, ntensors, total_tiles, stream);
+}
+
+DCLIP_API int dclip_rowsum_f16(const void* x, float* out, int R, int n, int ld, void* stream) {
+  return rowsum16<F16IeeeT>("rowsum_f16", x, out, R, n, ld, stream);
 }

@@ -392,15 +392,51 @@ def vision_fwd_bf16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dic
 # fp32; every encoder layer is run at full size (the CLS-row pruning of the fp32 schedule would keep a full-size fp32 qkv
 # projection).
 
-def _w16t(cache: dict, key: str, w: torch.Tensor) -> torch.Tensor:
-    """bf16 W^T [in, ld >= out] of an nn.Linear weight [out, in]: the `W` operand of the dgrad GEMM dX = dY (W^T)^T."""
+class _Train16:
+    """The training-path kernels of one 16-bit type: ops.*_bf16, or their fp16 twins with IEEE rounding (ops.*_f16*,
+    student_precision="fp16").  `plan_tokmajor` / `io16_pair` are the library plan entry and the fp32-arithmetic
+    attention pair of DCLIP_BF16_ATTN_MFMA=0 (bf16 only: None for fp16, which always takes the MFMA pair)."""
+
+    def __init__(self, dtype, gemm, cast, layernorm_stats, transpose, wgrad, wgrad_tokmajor, colsum, rowsum, attention_lse,
+                 attention_bwd, mt_weights, im2col, plan_tokmajor, io16_pair):
+        self.dtype, self._gemm, self.cast, self._layernorm_stats = dtype, gemm, cast, layernorm_stats
+        self.transpose, self.wgrad, self.wgrad_tokmajor, self.colsum, self.rowsum = transpose, wgrad, wgrad_tokmajor, colsum, rowsum
+        self.attention_lse, self.attention_bwd, self.mt_weights, self.im2col = attention_lse, attention_bwd, mt_weights, im2col
+        self.plan_tokmajor, self.io16_pair = plan_tokmajor, io16_pair
+
+    def gemm(self, a, w, out16: bool = False, **kw):
+        if self.dtype == torch.bfloat16:
+            return self._gemm(a, w, out_bf16=out16, **kw)
+        return self._gemm(a, w, out_f16=out16, **kw)
+
+    def layernorm_stats(self, x, gamma, beta, eps):
+        if self.dtype == torch.bfloat16:
+            return self._layernorm_stats(x, gamma, beta, eps, save_stats=True)
+        return self._layernorm_stats(x, gamma, beta, eps)
+
+
+_TRAIN16 = {
+    torch.bfloat16: _Train16(torch.bfloat16, ops.gemm_bf16, ops.cast_bf16, ops.layernorm_fwd_bf16, ops.transpose_bf16,
+                             ops.gemm_bf16_wgrad, ops.gemm_bf16_wgrad_tokmajor, ops.colsum_bf16, ops.rowsum_bf16,
+                             ops.attention_fwd_bf16_lse, ops.attention_bwd_bf16, ops.mt_weights_bf16, ops.im2col_bf16,
+                             "dclip_gemm_bf16_wgrad_tokmajor_plan", (ops.attention_fwd_io16, ops.attention_bwd_io16)),
+    torch.float16: _Train16(torch.float16, ops.gemm_f16_train, ops.cast_f16_ieee, ops.layernorm_fwd_f16_stats, ops.transpose_f16,
+                            ops.gemm_f16_wgrad, ops.gemm_f16_wgrad_tokmajor, ops.colsum_f16, ops.rowsum_f16,
+                            ops.attention_fwd_f16_lse, ops.attention_bwd_f16, ops.mt_weights_f16, ops.im2col_f16,
+                            "dclip_gemm_f16_wgrad_tokmajor_plan", None),
+}
+
+
+def _w16t(cache: dict, key: str, w: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """16-bit W^T [in, ld >= out] of an nn.Linear weight [out, in]: the `W` operand of the dgrad GEMM dX = dY (W^T)^T."""
+    transpose = _TRAIN16[dtype].transpose
     e = cache.get(key + ".T")
     src = w.detach().reshape(w.shape[0], -1)
     if e is None:
-        e = [ops.transpose_bf16(src.contiguous()), w._version, w.data_ptr()]
+        e = [transpose(src.contiguous()), w._version, w.data_ptr()]
         cache[key + ".T"] = e
     elif e[1] != w._version or e[2] != w.data_ptr():
-        ops.transpose_bf16(src.contiguous(), out=e[0])
+        transpose(src.contiguous(), out=e[0])
         e[1], e[2] = w._version, w.data_ptr()
     return e[0]
 
@@ -408,11 +444,13 @@ def _w16t(cache: dict, key: str, w: torch.Tensor) -> torch.Tensor:
 _TRAIN_WEIGHTS = (("qkv", "qkv_w"), ("out", "out_w"), ("fc1", "fc1_w"), ("fc2", "fc2_w"))
 
 
-def refresh_train_weights(cache: dict, layers: List[LayerParams], prefix: str = "v") -> None:
+def refresh_train_weights(cache: dict, layers: List[LayerParams], prefix: str = "v", dtype=torch.bfloat16) -> None:
     """Bring the bf16 copies W and W^T of every encoder-layer GEMM weight of a TRAINING tower up to date before its
     forward — in ONE launch (ops.mt_weights_bf16) when, as after every optimizer step, all of them are stale: the
     per-weight path is 48 casts + 48 transposes per step for ViT-B.  The record table lives on the device next to the
-    persistent copies (uploaded once, so the launch is capturable in a HIP graph)."""
+    persistent copies (uploaded once, so the launch is capturable in a HIP graph).  `dtype`: the 16-bit type of the copies
+    (one cache per type)."""
+    t16 = _TRAIN16[dtype]
     stale = []
     for li, lp in enumerate(layers):
         for short, field in _TRAIN_WEIGHTS:
@@ -427,16 +465,16 @@ def refresh_train_weights(cache: dict, layers: List[LayerParams], prefix: str = 
     keys = tuple(k for k, _ in stale)
     tab = tables.get(keys)
     if tab is not None and all(cache[k][2] == w.data_ptr() for k, w in stale):
-        ops.mt_weights_bf16(tab["dev"], tab["n"], tab["tiles"])
+        t16.mt_weights(tab["dev"], tab["n"], tab["tiles"])
         for k, w in stale:
             cache[k][1] = w._version
         return
     # first time this set is stale: the per-weight kernels allocate / refresh the copies ...
     for key, w in stale:
         if key.endswith(".T"):
-            _w16t(cache, key[:-2], w)
+            _w16t(cache, key[:-2], w, dtype)
         else:
-            _w16(cache, key, w)
+            _w16(cache, key, w, t16.cast)
     # ... and a table for exactly this set (all weights after an optimizer step; the trainable subset under a freeze rule)
     # is built for the following steps — not while a stream is capturing: the upload is a synchronous copy
     if torch.cuda.is_current_stream_capturing():
@@ -446,56 +484,58 @@ def refresh_train_weights(cache: dict, layers: List[LayerParams], prefix: str = 
         base = key[:-2] if key.endswith(".T") else key
         r = recs.setdefault(base, [w, None, None])
         r[2 if key.endswith(".T") else 1] = cache[key][0]
-    dev, n, tiles = ops.mt_weights_table([tuple(r) for r in recs.values()])
+    dev, n, tiles = ops.mt_weights_table([tuple(r) for r in recs.values()], dtype)
     tables[keys] = {"dev": dev, "n": n, "tiles": tiles}
 
 
-def _attention_io16(M: int, S: int, D: int, I: int) -> bool:
+def _attention_io16(M: int, S: int, D: int, I: int, dtype=torch.bfloat16) -> bool:
     """Short sequences on the token-major backward schedule keep q/k/v, the attention output and their gradients in bf16
     between the GEMMs and the attention kernels: the qkv projection writes bf16, no cast launches either side of the
     attention.  DCLIP_BF16_ATTN_IO16=0: fp32 attention I/O (casts) instead."""
-    return S <= 64 and _tokmajor_wgrads(M, D, I) and os.environ.get("DCLIP_BF16_ATTN_IO16", "1") != "0"
+    return S <= 64 and _tokmajor_wgrads(M, D, I, dtype) and os.environ.get("DCLIP_BF16_ATTN_IO16", "1") != "0"
 
 
-def _attention_mfma16() -> bool:
+def _attention_mfma16(dtype=torch.bfloat16) -> bool:
     """Which kernels serve the bf16-I/O attention of the training student: the bf16 MFMA pair (ops.attention_fwd_bf16_lse /
     attention_bwd_bf16: P and dS rounded to bf16 for the products they feed — the default) or, DCLIP_BF16_ATTN_MFMA=0, the
-    fp32-arithmetic kernels with bf16 loads and stores (ops.attention_*_io16)."""
-    return os.environ.get("DCLIP_BF16_ATTN_MFMA", "1") != "0"
+    fp32-arithmetic kernels with bf16 loads and stores (ops.attention_*_io16).  fp16 always takes its MFMA pair."""
+    return dtype != torch.bfloat16 or os.environ.get("DCLIP_BF16_ATTN_MFMA", "1") != "0"
 
 
-def layer_fwd_bf16_train(x, p: LayerParams, c: dict, pre: str, B: int, S: int, H: int, causal: bool, eps: float):
-    ln1, m1, r1 = ops.layernorm_fwd_bf16(x, p.ln1_w, p.ln1_b, eps, save_stats=True)
-    if _attention_io16(x.shape[0], S, x.shape[1], p.fc1_w.shape[0]):
-        qkv = ops.gemm_bf16(ln1, _w16(c, pre + "qkv", p.qkv_w), bias=p.qkv_b, out_bf16=True)
-        attn16, lse = (ops.attention_fwd_bf16_lse if _attention_mfma16() else ops.attention_fwd_io16)(qkv, B, S, H, causal)
+def layer_fwd_bf16_train(x, p: LayerParams, c: dict, pre: str, B: int, S: int, H: int, causal: bool, eps: float,
+                         dtype=torch.bfloat16):
+    k = _TRAIN16[dtype]
+    ln1, m1, r1 = k.layernorm_stats(x, p.ln1_w, p.ln1_b, eps)
+    if _attention_io16(x.shape[0], S, x.shape[1], p.fc1_w.shape[0], dtype):
+        qkv = k.gemm(ln1, _w16(c, pre + "qkv", p.qkv_w, k.cast), bias=p.qkv_b, out16=True)
+        attn16, lse = (k.attention_lse if _attention_mfma16(dtype) else k.io16_pair[0])(qkv, B, S, H, causal)
         attn = None
     else:
-        qkv = ops.gemm_bf16(ln1, _w16(c, pre + "qkv", p.qkv_w), bias=p.qkv_b)        # fp32 out: the attention core is fp32
+        qkv = k.gemm(ln1, _w16(c, pre + "qkv", p.qkv_w, k.cast), bias=p.qkv_b)        # fp32 out: the attention core is fp32
         attn, lse = ops.attention_fwd(qkv, B, S, H, causal)
-        attn16 = ops.cast_bf16(attn)
-    x1 = ops.gemm_bf16(attn16, _w16(c, pre + "out", p.out_w), bias=p.out_b, residual=x)
-    ln2, m2, r2 = ops.layernorm_fwd_bf16(x1, p.ln2_w, p.ln2_b, eps, save_stats=True)
-    g16, h16 = ops.gemm_bf16(ln2, _w16(c, pre + "fc1", p.fc1_w), bias=p.fc1_b, gelu=True, out_bf16=True, save_preact=True)
-    x2 = ops.gemm_bf16(g16, _w16(c, pre + "fc2", p.fc2_w), bias=p.fc2_b, residual=x1)
+        attn16 = k.cast(attn)
+    x1 = k.gemm(attn16, _w16(c, pre + "out", p.out_w, k.cast), bias=p.out_b, residual=x)
+    ln2, m2, r2 = k.layernorm_stats(x1, p.ln2_w, p.ln2_b, eps)
+    g16, h16 = k.gemm(ln2, _w16(c, pre + "fc1", p.fc1_w, k.cast), bias=p.fc1_b, gelu=True, out16=True, save_preact=True)
+    x2 = k.gemm(g16, _w16(c, pre + "fc2", p.fc2_w, k.cast), bias=p.fc2_b, residual=x1)
     return x2, (x, m1, r1, ln1, qkv, attn, attn16, lse, x1, m2, r2, ln2, h16, g16)
 
 
 _TOKMAJOR_PLAN: Dict[tuple, bool] = {}
 
 
-def _tokmajor_wgrads(M: int, D: int, I: int) -> bool:
+def _tokmajor_wgrads(M: int, D: int, I: int, dtype=torch.bfloat16) -> bool:
     """Can the four weight gradients of a layer take the token-major form (no transposes)?  One answer per layer so that
     the backward below has two straight schedules; decided once per (M, D, I) (four plan calls + an environment lookup
     per layer per backward otherwise).  DCLIP_BF16_WGRAD_TN=0, read at the first use, forces the transposing schedule."""
-    key = (M, D, I)
+    key = (M, D, I, dtype)
     hit = _TOKMAJOR_PLAN.get(key)
     if hit is None:
         if os.environ.get("DCLIP_BF16_WGRAD_TN", "1") == "0":
             hit = False
         else:
-            lib = _lib.load()
-            hit = all(lib.dclip_gemm_bf16_wgrad_tokmajor_plan(m, n, M) > 0 for m, n in ((D, I), (I, D), (D, D), (3 * D, D)))
+            plan = getattr(_lib.load(), _TRAIN16[dtype].plan_tokmajor)
+            hit = all(plan(m, n, M) > 0 for m, n in ((D, I), (I, D), (D, D), (3 * D, D)))
         _TOKMAJOR_PLAN[key] = hit
     return hit
 
@@ -535,7 +575,8 @@ class _SideWgrads:
 
 
 def layer_bwd_bf16_tokmajor(dx2, p: LayerParams, c: dict, pre: str, saved, B: int, S: int, H: int, causal: bool,
-                            need: Dict[str, bool], alloc=None, dx2_16=None, fc2_b=None, below_fc2_b=None, want_dx16=False):
+                            need: Dict[str, bool], alloc=None, dx2_16=None, fc2_b=None, below_fc2_b=None, want_dx16=False,
+                            dtype=torch.bfloat16):
     """layer_bwd_bf16 with the weight gradients read from the operands as they lie — dW = dY^T X on the token-major form of
     the ping-pong GEMM (ops.gemm_bf16_wgrad_tokmajor): the saved bf16 activations are used as they are, no transposed
     copies are written, and the bf16 copies of the fp32 gradients come out of the kernels that PRODUCE those gradients:
@@ -544,6 +585,7 @@ def layer_bwd_bf16_tokmajor(dx2, p: LayerParams, c: dict, pre: str, saved, B: in
       below_fc2_b  where THIS layer's LayerNorm1 backward leaves the column sums of its dx (the layer below's fc2_b);
       want_dx16    ... and whether it writes the bf16 copy of dx for the layer below.
     Returns (dx, dx16 or None, grads)."""
+    k = _TRAIN16[dtype]
     x, m1, r1, ln1, qkv, attn, attn16, lse, x1, m2, r2, ln2, h16, g16 = saved
     D = x.shape[1]
     I = g16.shape[1]
@@ -552,21 +594,21 @@ def layer_bwd_bf16_tokmajor(dx2, p: LayerParams, c: dict, pre: str, saved, B: in
     wg = _SideWgrads(dev)
     # ---- fc2
     if dx2_16 is None:
-        dx2_16 = ops.cast_bf16(dx2)
+        dx2_16 = k.cast(dx2)
     if need.get("fc2_w"):
         o_ = _galloc(alloc, "fc2_w", (D, I), dev)
-        gr["fc2_w"] = wg.run(lambda a_=dx2_16, b_=g16: ops.gemm_bf16_wgrad_tokmajor(a_, b_, out=o_), dx2_16, g16)
+        gr["fc2_w"] = wg.run(lambda a_=dx2_16, b_=g16: k.wgrad_tokmajor(a_, b_, out=o_), dx2_16, g16)
     if need.get("fc2_b"):
         gr["fc2_b"] = fc2_b if fc2_b is not None else ops.colsum(dx2, out=_galloc(alloc, "fc2_b", (D,), dev))
-    dh16 = ops.gemm_bf16(dx2_16, _w16t(c, pre + "fc2", p.fc2_w), k=D, dgelu_of=h16, out_bf16=True)       # [M, I]
+    dh16 = k.gemm(dx2_16, _w16t(c, pre + "fc2", p.fc2_w, dtype), k=D, dgelu_of=h16, out16=True)         # [M, I]
     del dx2_16
     # ---- fc1
     if need.get("fc1_w"):
         o1_ = _galloc(alloc, "fc1_w", (I, D), dev)
-        gr["fc1_w"] = wg.run(lambda a_=dh16, b_=ln2: ops.gemm_bf16_wgrad_tokmajor(a_, b_, out=o1_), dh16, ln2)
+        gr["fc1_w"] = wg.run(lambda a_=dh16, b_=ln2: k.wgrad_tokmajor(a_, b_, out=o1_), dh16, ln2)
     if need.get("fc1_b"):
-        gr["fc1_b"] = ops.colsum_bf16(dh16, out=_galloc(alloc, "fc1_b", (I,), dev))
-    dln2 = ops.gemm_bf16(dh16, _w16t(c, pre + "fc1", p.fc1_w), k=dh16.shape[1])                          # [M, D] fp32
+        gr["fc1_b"] = k.colsum(dh16, out=_galloc(alloc, "fc1_b", (I,), dev))
+    dln2 = k.gemm(dh16, _w16t(c, pre + "fc1", p.fc1_w, dtype), k=dh16.shape[1])                          # [M, D] fp32
     del dh16
     # LayerNorm2 backward: dx1 (+ the skip connection's dx2), its bf16 copy, and out_proj's bias gradient = colsum(dx1)
     want_ln2 = bool(need.get("ln2_w") or need.get("ln2_b"))
@@ -574,7 +616,7 @@ def layer_bwd_bf16_tokmajor(dx2, p: LayerParams, c: dict, pre: str, saved, B: in
     dg = _galloc(alloc, "ln2_w", (D,), dev) if want_ln2 else None
     db = _galloc(alloc, "ln2_b", (D,), dev) if want_ln2 else None
     dx1, dg, db, dx1_16 = ops.layernorm_bwd(dln2, x1, p.ln2_w, m2, r2, dresidual=dx2, dgamma=dg, dbeta=db,
-                                            need_param_grads=want_ln2, want_bf16=True, dx_colsum=out_b)
+                                            need_param_grads=want_ln2, want_bf16=True, dx_colsum=out_b, dtype16=dtype)
     if want_ln2:
         gr["ln2_w"], gr["ln2_b"] = dg, db
     if out_b is not None:
@@ -582,34 +624,33 @@ def layer_bwd_bf16_tokmajor(dx2, p: LayerParams, c: dict, pre: str, saved, B: in
     # ---- out_proj
     if need.get("out_w"):
         o2_ = _galloc(alloc, "out_w", (D, D), dev)
-        gr["out_w"] = wg.run(lambda a_=dx1_16, b_=attn16: ops.gemm_bf16_wgrad_tokmajor(a_, b_, out=o2_), dx1_16, attn16)
-    if qkv.dtype == torch.bfloat16:          # bf16 I/O attention: dO arrives as bf16, dq / dk / dv leave as bf16
-        dattn16 = ops.gemm_bf16(dx1_16, _w16t(c, pre + "out", p.out_w), k=D, out_bf16=True)
+        gr["out_w"] = wg.run(lambda a_=dx1_16, b_=attn16: k.wgrad_tokmajor(a_, b_, out=o2_), dx1_16, attn16)
+    if qkv.dtype != torch.float32:           # 16-bit I/O attention: dO arrives as 16-bit, dq / dk / dv leave as 16-bit
+        dattn16 = k.gemm(dx1_16, _w16t(c, pre + "out", p.out_w, dtype), k=D, out16=True)
         del dx1_16
-        dqkv16 = (ops.attention_bwd_bf16 if _attention_mfma16() else ops.attention_bwd_io16)(qkv, attn16, dattn16, lse, B, S, H,
-                                                                                             causal)
+        dqkv16 = (k.attention_bwd if _attention_mfma16(dtype) else k.io16_pair[1])(qkv, attn16, dattn16, lse, B, S, H, causal)
         del dattn16
         if need.get("qkv_b"):
-            gr["qkv_b"] = ops.colsum_bf16(dqkv16, out=_galloc(alloc, "qkv_b", (3 * D,), dev))
+            gr["qkv_b"] = k.colsum(dqkv16, out=_galloc(alloc, "qkv_b", (3 * D,), dev))
     else:
-        dattn = ops.gemm_bf16(dx1_16, _w16t(c, pre + "out", p.out_w), k=D)                               # [M, D] fp32
+        dattn = k.gemm(dx1_16, _w16t(c, pre + "out", p.out_w, dtype), k=D)                               # [M, D] fp32
         del dx1_16
         dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal)                                 # fp32 [M, 3D]
-        dqkv16 = ops.cast_bf16(dqkv)
+        dqkv16 = k.cast(dqkv)
         if need.get("qkv_b"):
             gr["qkv_b"] = ops.colsum(dqkv, out=_galloc(alloc, "qkv_b", (3 * D,), dev))
         del dqkv
     # ---- qkv projection
     if need.get("qkv_w"):
         o3_ = _galloc(alloc, "qkv_w", (3 * D, D), dev)
-        gr["qkv_w"] = wg.run(lambda a_=dqkv16, b_=ln1: ops.gemm_bf16_wgrad_tokmajor(a_, b_, out=o3_), dqkv16, ln1)
-    dln1 = ops.gemm_bf16(dqkv16, _w16t(c, pre + "qkv", p.qkv_w), k=3 * D)
+        gr["qkv_w"] = wg.run(lambda a_=dqkv16, b_=ln1: k.wgrad_tokmajor(a_, b_, out=o3_), dqkv16, ln1)
+    dln1 = k.gemm(dqkv16, _w16t(c, pre + "qkv", p.qkv_w, dtype), k=3 * D)
     del dqkv16
     want_ln1 = bool(need.get("ln1_w") or need.get("ln1_b"))
     dg = _galloc(alloc, "ln1_w", (D,), dev) if want_ln1 else None
     db = _galloc(alloc, "ln1_b", (D,), dev) if want_ln1 else None
     res = ops.layernorm_bwd(dln1, x, p.ln1_w, m1, r1, dresidual=dx1, dgamma=dg, dbeta=db, need_param_grads=want_ln1,
-                            want_bf16=want_dx16, dx_colsum=below_fc2_b)
+                            want_bf16=want_dx16, dx_colsum=below_fc2_b, dtype16=dtype)
     dx, dg, db = res[0], res[1], res[2]
     if want_ln1:
         gr["ln1_w"], gr["ln1_b"] = dg, db
@@ -618,53 +659,55 @@ def layer_bwd_bf16_tokmajor(dx2, p: LayerParams, c: dict, pre: str, saved, B: in
 
 
 def layer_bwd_bf16(dx2, p: LayerParams, c: dict, pre: str, saved, B: int, S: int, H: int, causal: bool, need: Dict[str, bool],
-                   alloc=None, dx2_16=None, fc2_b=None, below_fc2_b=None, want_dx16=False):
+                   alloc=None, dx2_16=None, fc2_b=None, below_fc2_b=None, want_dx16=False, dtype=torch.bfloat16):
     """Backward of layer_fwd_bf16_train -> (dx, dx16 or None, grads).  `alloc(field, shape)`: see _galloc — under data
     parallelism every parameter gradient (split-K weight gradients, bias column sums, LayerNorm dγ/dβ) is written straight
     into its bucket slice.  dx2_16 / fc2_b / below_fc2_b / want_dx16: see layer_bwd_bf16_tokmajor (the transposing
-    schedule below ignores them, except that it fills below_fc2_b so the caller's bookkeeping holds)."""
+    schedule below ignores them, except that it fills below_fc2_b so the caller's bookkeeping holds).  `dtype`: the 16-bit
+    type of the layer's forward (layer_fwd_bf16_train)."""
+    k = _TRAIN16[dtype]
     x, m1, r1, ln1, qkv, attn, attn16, lse, x1, m2, r2, ln2, h16, g16 = saved
     M = x.shape[0]
     D = x.shape[1]
     I = g16.shape[1]
     dev = x.device
-    if _tokmajor_wgrads(M, D, I):
+    if _tokmajor_wgrads(M, D, I, dtype):
         return layer_bwd_bf16_tokmajor(dx2, p, c, pre, saved, B, S, H, causal, need, alloc, dx2_16, fc2_b, below_fc2_b,
-                                       want_dx16)
+                                       want_dx16, dtype)
     gr: Dict[str, torch.Tensor] = {}
     # ---- fc2
-    dx2T, dx2_16 = ops.transpose_bf16(dx2, want_copy=True)
+    dx2T, dx2_16 = k.transpose(dx2, want_copy=True)
     if need.get("fc2_w"):
-        gr["fc2_w"] = ops.gemm_bf16_wgrad(dx2T, ops.transpose_bf16(g16), M, out=_galloc(alloc, "fc2_w", (D, I), dev))
+        gr["fc2_w"] = k.wgrad(dx2T, k.transpose(g16), M, out=_galloc(alloc, "fc2_w", (D, I), dev))
     if need.get("fc2_b"):
         gr["fc2_b"] = fc2_b if fc2_b is not None else ops.colsum(dx2, out=_galloc(alloc, "fc2_b", (D,), dev))
-    dh16 = ops.gemm_bf16(dx2_16, _w16t(c, pre + "fc2", p.fc2_w), k=D, dgelu_of=h16, out_bf16=True)       # [M, I]
+    dh16 = k.gemm(dx2_16, _w16t(c, pre + "fc2", p.fc2_w, dtype), k=D, dgelu_of=h16, out16=True)         # [M, I]
     del dx2T, dx2_16
     # ---- fc1
-    dhT = ops.transpose_bf16(dh16)
+    dhT = k.transpose(dh16)
     if need.get("fc1_w"):
-        gr["fc1_w"] = ops.gemm_bf16_wgrad(dhT, ops.transpose_bf16(ln2), M, out=_galloc(alloc, "fc1_w", (I, D), dev))
+        gr["fc1_w"] = k.wgrad(dhT, k.transpose(ln2), M, out=_galloc(alloc, "fc1_w", (I, D), dev))
     if need.get("fc1_b"):
-        gr["fc1_b"] = ops.rowsum_bf16(dhT, M, out=_galloc(alloc, "fc1_b", (I,), dev))
-    dln2 = ops.gemm_bf16(dh16, _w16t(c, pre + "fc1", p.fc1_w), k=dh16.shape[1])                          # [M, D] fp32
+        gr["fc1_b"] = k.rowsum(dhT, M, out=_galloc(alloc, "fc1_b", (I,), dev))
+    dln2 = k.gemm(dh16, _w16t(c, pre + "fc1", p.fc1_w, dtype), k=dh16.shape[1])                          # [M, D] fp32
     del dh16, dhT
     dx1 = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc)
     # ---- out_proj
-    dx1T, dx1_16 = ops.transpose_bf16(dx1, want_copy=True)
+    dx1T, dx1_16 = k.transpose(dx1, want_copy=True)
     if need.get("out_w"):
-        gr["out_w"] = ops.gemm_bf16_wgrad(dx1T, ops.transpose_bf16(attn16), M, out=_galloc(alloc, "out_w", (D, D), dev))
+        gr["out_w"] = k.wgrad(dx1T, k.transpose(attn16), M, out=_galloc(alloc, "out_w", (D, D), dev))
     if need.get("out_b"):
         gr["out_b"] = ops.colsum(dx1, out=_galloc(alloc, "out_b", (D,), dev))
-    dattn = ops.gemm_bf16(dx1_16, _w16t(c, pre + "out", p.out_w), k=D)                                   # [M, D] fp32
+    dattn = k.gemm(dx1_16, _w16t(c, pre + "out", p.out_w, dtype), k=D)                                   # [M, D] fp32
     del dx1T, dx1_16
     dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal)                                     # fp32 [M, 3D]
     # ---- qkv projection
-    dqkvT, dqkv16 = ops.transpose_bf16(dqkv, want_copy=True)
+    dqkvT, dqkv16 = k.transpose(dqkv, want_copy=True)
     if need.get("qkv_w"):
-        gr["qkv_w"] = ops.gemm_bf16_wgrad(dqkvT, ops.transpose_bf16(ln1), M, out=_galloc(alloc, "qkv_w", (3 * D, D), dev))
+        gr["qkv_w"] = k.wgrad(dqkvT, k.transpose(ln1), M, out=_galloc(alloc, "qkv_w", (3 * D, D), dev))
     if need.get("qkv_b"):
         gr["qkv_b"] = ops.colsum(dqkv, out=_galloc(alloc, "qkv_b", (3 * D,), dev))
-    dln1 = ops.gemm_bf16(dqkv16, _w16t(c, pre + "qkv", p.qkv_w), k=3 * D)
+    dln1 = k.gemm(dqkv16, _w16t(c, pre + "qkv", p.qkv_w, dtype), k=3 * D)
     del dqkv, dqkvT, dqkv16
     dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dx1, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc)
     if below_fc2_b is not None:
@@ -675,38 +718,40 @@ def layer_bwd_bf16(dx2, p: LayerParams, c: dict, pre: str, saved, B: int, S: int
 _PATCH_BF16_PLAN: Dict[tuple, bool] = {}
 
 
-def _patch_embed_bf16(v, rows: int) -> bool:
+def _patch_embed_bf16(v, rows: int, dtype=torch.bfloat16) -> bool:
     """Does the patch embedding of the TRAINING tower (the convolution as a GEMM: [rows = images x patches][3 p p] x
     [D][3 p p]^T, and its weight gradient) run on the bf16 MFMAs like the encoder layers?  Yes when the one-pass bf16
     im2col and the token-major weight-gradient kernel both apply to the shape (`DCLIP_BF16_PATCH=0`: keep it fp32, as
     rounds 2-3 had it: 0.44 + 0.43 ms of fp32 GEMM per step at 256 images against 0.05 + 0.07)."""
-    key = (v.hidden_size, v.patch_dim, v.patch_size, rows)
+    key = (v.hidden_size, v.patch_dim, v.patch_size, rows, dtype)
     hit = _PATCH_BF16_PLAN.get(key)
     if hit is None:
         hit = (os.environ.get("DCLIP_BF16_PATCH", "1") != "0" and v.patch_size % 4 == 0 and v.patch_dim % 64 == 0
-               and _lib.load().dclip_gemm_bf16_wgrad_tokmajor_plan(v.hidden_size, v.patch_dim, rows) > 0)
+               and getattr(_lib.load(), _TRAIN16[dtype].plan_tokmajor)(v.hidden_size, v.patch_dim, rows) > 0)
         _PATCH_BF16_PLAN[key] = hit
     return hit
 
 
-def vision_fwd_bf16_train(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict):
-    """get_image_features with gradients, bf16 GEMM inputs in the patch embedding and the encoder layers."""
+def vision_fwd_bf16_train(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16):
+    """get_image_features with gradients, 16-bit GEMM inputs (`dtype` bf16, or fp16 with IEEE rounding) in the patch
+    embedding and the encoder layers; `cache` holds the weight copies of that type."""
     v = cfg
+    k = _TRAIN16[dtype]
     B = pixel_values.shape[0]
     S, D, H = v.seq_len, v.hidden_size, v.num_attention_heads
-    if _patch_embed_bf16(v, B * (S - 1)):
-        cols = ops.im2col_bf16(pixel_values, v.patch_size)                    # one pass: gather + round; kept for the wgrad
-        patch = ops.gemm_bf16(cols, _w16(cache, "vpatch", p.patch_w), k=v.patch_dim)
+    if _patch_embed_bf16(v, B * (S - 1), dtype):
+        cols = k.im2col(pixel_values, v.patch_size)                           # one pass: gather + round; kept for the wgrad
+        patch = k.gemm(cols, _w16(cache, "vpatch", p.patch_w, k.cast), k=v.patch_dim)
     else:
         cols = ops.im2col(pixel_values, v.patch_size)
         patch = ops.gemm(cols, p.patch_w.view(D, -1), ops.LAYOUT_NT)
     emb = ops.vision_assemble_fwd(patch, p.class_embedding, p.pos, B, S, D)
     del patch
     x, m0, r0 = ops.layernorm_fwd(emb, p.pre_w, p.pre_b, v.layer_norm_eps, save_stats=True)
-    refresh_train_weights(cache, p.layers, "v")          # W and W^T of all layers, one launch per optimizer step
+    refresh_train_weights(cache, p.layers, "v", dtype)   # W and W^T of all layers, one launch per optimizer step
     saved_layers = []
     for li, lp in enumerate(p.layers):
-        x, sv = layer_fwd_bf16_train(x, lp, cache, f"v{li}.", B, S, H, False, v.layer_norm_eps)
+        x, sv = layer_fwd_bf16_train(x, lp, cache, f"v{li}.", B, S, H, False, v.layer_norm_eps, dtype)
         saved_layers.append(sv)
     cls_tok = ops.gather_rows(x, None, B, S, D)
     pooled, mp, rp = ops.layernorm_fwd(cls_tok, p.post_w, p.post_b, v.layer_norm_eps, save_stats=True)
@@ -714,10 +759,12 @@ def vision_fwd_bf16_train(p: VisionParams, pixel_values: torch.Tensor, cfg, cach
     return out, (cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled)
 
 
-def vision_bwd_bf16(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool], cache: dict, on_ready=None, alloc=None):
-    """Backward of vision_fwd_bf16_train; same contract as vision_bwd (`on_ready` per gradient group, `alloc` naming the
-    tensor each parameter gradient is written into)."""
+def vision_bwd_bf16(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool], cache: dict, on_ready=None, alloc=None,
+                    dtype=torch.bfloat16):
+    """Backward of vision_fwd_bf16_train (of the same `dtype`); same contract as vision_bwd (`on_ready` per gradient group,
+    `alloc` naming the tensor each parameter gradient is written into)."""
     v = cfg
+    k = _TRAIN16[dtype]
     cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled = saved
     B = cls_tok.shape[0]
     S, D, H = v.seq_len, v.hidden_size, v.num_attention_heads
@@ -751,7 +798,7 @@ def vision_bwd_bf16(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List
         if i > bottom and needd[f"layers.{i - 1}.fc2_b"]:
             below = _galloc(alloc, f"layers.{i - 1}.fc2_b", (D,), dev)
         dx, dx16, gr = layer_bwd_bf16(dx, p.layers[i], cache, f"v{i}.", saved_layers[i], B, S, H, False, lneed, lalloc,
-                                      dx2_16=dx16, fc2_b=fc2_b, below_fc2_b=below, want_dx16=i > bottom)
+                                      dx2_16=dx16, fc2_b=fc2_b, below_fc2_b=below, want_dx16=i > bottom, dtype=dtype)
         fc2_b = below
         saved_layers[i] = None
         for f, t in gr.items():
@@ -771,10 +818,10 @@ def vision_bwd_bf16(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List
         if needd["patch_w"]:
             dpatch = ops.vision_assemble_bwd(demb, B, S, D)
             pw = _galloc(alloc, "patch_w", (D, p.patch_w.numel() // D), dev)
-            if cols.dtype == torch.bfloat16:          # token-major split-K weight gradient from the saved bf16 columns
-                got = ops.gemm_bf16_wgrad_tokmajor(ops.cast_bf16(dpatch), cols, out=pw)
+            if cols.dtype != torch.float32:           # token-major split-K weight gradient from the saved 16-bit columns
+                got = k.wgrad_tokmajor(k.cast(dpatch), cols, out=pw)
                 if got is None:
-                    raise RuntimeError("patch-embedding weight gradient: the token-major bf16 kernel refused a shape its plan accepted")
+                    raise RuntimeError("patch-embedding weight gradient: the token-major 16-bit kernel refused a shape its plan accepted")
                 grads["patch_w"] = got.view_as(p.patch_w)
             else:
                 grads["patch_w"] = ops.gemm(dpatch, cols, ops.LAYOUT_TN, out=pw).view_as(p.patch_w)

@@ -71,14 +71,15 @@ class VisionTowerFn(torch.autograd.Function):
 
 
 class VisionTowerBf16Fn(torch.autograd.Function):
-    """VisionTowerFn with bf16 GEMM inputs in forward, dgrad and wgrad (engine.vision_fwd_bf16_train); `cache` holds the
-    bf16 weight copies (HipCLIPModel._bf16_cache: rebuilt when a parameter version changes)."""
+    """VisionTowerFn with 16-bit GEMM inputs in forward, dgrad and wgrad (engine.vision_fwd_bf16_train): `dtype` bf16, or fp16
+    with IEEE rounding (student_precision="fp16"); `cache` holds the weight copies of that type (HipCLIPModel._bf16_cache /
+    _f16_cache: rebuilt when a parameter version changes)."""
 
     @staticmethod
-    def forward(ctx, pixel_values, cfg, n_layers, cache, *params):
+    def forward(ctx, pixel_values, cfg, n_layers, cache, dtype, *params):
         p = engine.VisionParams.from_tensors([_c(t.detach()) for t in params], n_layers)
-        out, saved = engine.vision_fwd_bf16_train(p, _c(pixel_values.detach()), cfg, cache)
-        ctx.p, ctx.saved, ctx.cfg, ctx.cache = p, saved, cfg, cache
+        out, saved = engine.vision_fwd_bf16_train(p, _c(pixel_values.detach()), cfg, cache, dtype)
+        ctx.p, ctx.saved, ctx.cfg, ctx.cache, ctx.dtype = p, saved, cfg, cache, dtype
         ctx.param_refs = params
         return out
 
@@ -99,12 +100,12 @@ class VisionTowerBf16Fn(torch.autograd.Function):
         if _GRAD_ALLOC is not None:       # bf16 wgrads (split-K reduce), bias sums, LayerNorm dγ/dβ land in the bucket slices
             galloc = _GRAD_ALLOC
             alloc = lambda name, shape: galloc(by_name[name], shape)      # noqa: E731
-        grads = engine.vision_bwd_bf16(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[4:]), ctx.cache,
-                                       on_ready, alloc)
+        grads = engine.vision_bwd_bf16(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[5:]), ctx.cache,
+                                       on_ready, alloc, ctx.dtype)
         ctx.saved = None
         if owned:
             grads = [None if n in owned else g for n, g in zip(ctx.p.names(), grads)]
-        return (None, None, None, None, *grads)
+        return (None, None, None, None, None, *grads)
 
 
 class TextTowerFn(torch.autograd.Function):

@@ -62,10 +62,12 @@ class LightningLikeModule(nn.Module):
 
 
 def save_checkpoint(path: str, module: LightningLikeModule, optimizer=None, scheduler=None, epoch: int = 0,
-                    global_step: int = 0):
+                    global_step: int = 0, scaler=None):
     """Lightning-layout dictionary: state_dict (prefixes `student.` / `teacher.cross_modal_attention.`),
-    epoch, global_step, hyper_parameters, optimizer_states, lr_schedulers, callbacks, pytorch-lightning_version."""
+    epoch, global_step, hyper_parameters, optimizer_states, lr_schedulers, callbacks, pytorch-lightning_version; with a loss
+    `scaler` (fp16 student) its state under `native_amp_scaling_state`, the key Lightning 1.x uses."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    amp_state = scaler.state_dict() if scaler is not None else None    # first: settles a pending skipped step's Adam count
     ckpt = {
         "epoch": epoch,
         "global_step": global_step,
@@ -76,6 +78,8 @@ def save_checkpoint(path: str, module: LightningLikeModule, optimizer=None, sche
         "lr_schedulers": [scheduler.state_dict()] if scheduler is not None else [],
         "callbacks": {},
     }
+    if amp_state is not None:
+        ckpt["native_amp_scaling_state"] = amp_state
     tmp = path + ".tmp"
     torch.save(ckpt, tmp)
     os.replace(tmp, path)
@@ -124,13 +128,16 @@ class Trainer:
     def __init__(self, max_epochs: int = 1, gradient_clip_val: Optional[float] = 0.5, accumulate_grad_batches: int = 4,
                  checkpoint_dir: Optional[str] = None, save_top_k: int = 10, max_steps: Optional[int] = None,
                  use_hip_graph: bool = False, lr_interval: str = "epoch", devices: int = 1, process_group=None,
-                 dist_backend: Optional[str] = None, bucket_mb: float = 25.0, **_ignored):
+                 dist_backend: Optional[str] = None, bucket_mb: float = 25.0, loss_scaler=None, **_ignored):
         """`use_hip_graph`: replay forward+backward from a captured HIP graph (dclip_amd/graph.py) — tensor batches of
         one fixed shape, single process; the update sequence and its results are those of the eager loop.
         `lr_interval`: "epoch" (default) advances the LR schedule once per epoch — what Lightning does with the
         reference's `return [optimizer], [scheduler]` (training/CLIP_image_distillation.py:679-682: a bare scheduler
         gets interval="epoch"), so with the default total_steps=1000 the LR decays by 0.1 % per epoch, as written.
-        "step" advances it after every optimizer step (what the HF warm-up schedule was designed for)."""
+        "step" advances it after every optimizer step (what the HF warm-up schedule was designed for).
+        `loss_scaler`: the amp.DynamicLossScaler of a module whose `student_precision` is "fp16" (default: GradScaler's
+        defaults); the loss is scaled before every backward, the scaler steps and updates at each accumulation boundary
+        (unscale, clip, step — skipped on an overflow — update), the LR schedule and global_step advance either way."""
         if lr_interval not in ("epoch", "step"):
             raise ValueError(f"lr_interval {lr_interval!r}")
         self.lr_interval = lr_interval
@@ -152,6 +159,7 @@ class Trainer:
         self.dist_backend = dist_backend
         self.bucket_mb = bucket_mb
         self.grad_sync = None
+        self.loss_scaler = loss_scaler
 
     def _join_group(self):
         """The data-parallel group of this run: the one passed in, else (devices > 1) the rendezvous in the environment."""
@@ -179,6 +187,21 @@ class Trainer:
             model.process_group = group                   # global negatives + the per-rank loss share (dist.py)
         opts, scheds = model.configure_optimizers()
         opt, sched = opts[0], (scheds[0] if scheds else None)
+        scaler = None
+        if getattr(model, "student_precision", None) == "fp16":
+            if self.use_hip_graph:
+                raise RuntimeError("use_hip_graph does not replay the fp16 student's loss-scaled step: train it eagerly")
+            if not hasattr(opt, "step_scaled"):
+                raise RuntimeError(f"the fp16 student needs an optimizer with the fused loss-scaled step (optim.FusedAdamW), "
+                                   f"got {type(opt).__name__}")
+            if self.loss_scaler is None:
+                from .amp import DynamicLossScaler
+                self.loss_scaler = DynamicLossScaler()
+            scaler = self.loss_scaler
+
+        def scaled(loss):                  # the fp16 student's backward runs on the loss-scaled value
+            return loss if scaler is None else scaler.scale(loss)
+
         # the HIP optimizer clips the global norm itself (device-side coefficient, no host sync, one pass over the grads)
         fused_clip = bool(self.clip) and hasattr(opt, "max_grad_norm")
         if fused_clip:
@@ -231,10 +254,10 @@ class Trainer:
                         prefetch(upcoming)
                     if boundary:
                         with sync.hooks():                     # all-reduce launched from inside this backward
-                            (loss / self.accum).backward()
+                            scaled(loss / self.accum).backward()
                         sync.finish()
                     else:
-                        (loss / self.accum).backward()         # plain accumulation into .grad
+                        scaled(loss / self.accum).backward()   # plain accumulation into .grad
                     last = (loss.detach(), dict(getattr(model, "last_losses", {})))
                 else:
                     loss = model.training_step(batch)
@@ -242,12 +265,16 @@ class Trainer:
                         # the NEXT batch's frozen meta-teacher starts now, on its own stream, and runs beside this batch's
                         # backward and the optimizer (CLIPImageDistillation.prefetch_teacher; tensor batches only)
                         prefetch(upcoming)
-                    (loss / self.accum).backward()
+                    scaled(loss / self.accum).backward()
                     last = loss.detach()
-                if boundary:
+                if boundary and scaler is not None:
+                    scaler.step(opt)                   # unscale + clip (folded into one coefficient) + step, or skip
+                    scaler.update()
+                elif boundary:
                     if self.clip and not fused_clip:
                         torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], self.clip)
                     opt.step()
+                if boundary:
                     if sched is not None and self.lr_interval == "step":
                         sched.step()
                     if graphed is None:            # graph mode: gradients live in the graph's pool and are overwritten
@@ -277,7 +304,7 @@ class Trainer:
                 tl = float(last)
                 path = os.path.join(self.checkpoint_dir, checkpoint_filename(epoch, tl))
                 if rank == 0:
-                    save_checkpoint(path, model, opt, sched, epoch, step)
+                    save_checkpoint(path, model, opt, sched, epoch, step, scaler=scaler)
                     self.saved.append((tl, path))
                     self.saved.sort()
                     for _, stale in self.saved[self.save_top_k:]:

@@ -171,10 +171,12 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, *, dresidual=None, dgamma=None, dbeta=None, accumulate=False,
-                  need_param_grads=True, want_bf16: bool = False, dx_colsum: Optional[torch.Tensor] = None):
+                  need_param_grads=True, want_bf16: bool = False, dx_colsum: Optional[torch.Tensor] = None,
+                  dtype16: torch.dtype = torch.bfloat16):
     """Returns (dx, dgamma, dbeta); dgamma/dbeta are written (or accumulated into) if requested.
-    bf16 training path: `want_bf16` -> returns (dx, dgamma, dbeta, dx16) with the bf16 copy of dx from the same pass;
-    `dx_colsum` [D] receives the column sums of dx (the bias gradient of the Linear that produced LayerNorm's input)."""
+    16-bit training path: `want_bf16` -> returns (dx, dgamma, dbeta, dx16) with the 16-bit copy of dx (`dtype16`: bf16, or
+    fp16 with IEEE rounding) from the same pass; `dx_colsum` [D] receives the column sums of dx (the bias gradient of the
+    Linear that produced LayerNorm's input)."""
     lib = _lib.load()
     _f32(dy, "dy"), _f32(x, "x"), _f32(gamma, "gamma"), _f32(mean, "mean"), _f32(rstd, "rstd")
     D = x.shape[-1]
@@ -203,8 +205,11 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, *, dresidual=None, dgamma=None, dbet
                                            rstd.data_ptr(), _ptr(dresidual), dx.data_ptr(), _ptr(dgamma), _ptr(dbeta),
                                            rows, D, int(accumulate), _ptr(ws), nbytes, _stream()), "layernorm_bwd")
         return dx, dgamma, dbeta
-    dx16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
-    _lib.check(lib.dclip_layernorm_bwd_ex(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+    if dtype16 not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"layernorm_bwd: dtype16 {dtype16}")
+    dx16 = torch.empty(x.shape, dtype=dtype16, device=x.device) if want_bf16 else None
+    entry = lib.dclip_layernorm_bwd_ex if dtype16 == torch.bfloat16 else lib.dclip_layernorm_bwd_ex_f16
+    _lib.check(entry(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                           _ptr(dresidual), dx.data_ptr(), _ptr(dx16), _ptr(dgamma), _ptr(dbeta),
                                           _ptr(dx_colsum), rows, D, int(accumulate), _ptr(ws), nbytes, _stream()),
                "layernorm_bwd_ex")
@@ -681,9 +686,11 @@ def _out_f32(out: Optional[torch.Tensor], shape, device, name: str) -> torch.Ten
     return out
 
 
-def mt_weights_table(recs):
-    """Device table for mt_weights_bf16 from [(w fp32 [rows, cols...], w16 bf16 [rows, ld] or None, w16T bf16 [cols, ldT] or
-    None)]; returns (table tensor, ntensors, total tiles).  One synchronous upload: build it once, outside graph capture."""
+def mt_weights_table(recs, dtype: torch.dtype = torch.bfloat16):
+    """Device table for mt_weights_bf16 (mt_weights_f16 with dtype float16) from [(w fp32 [rows, cols...], w16 [rows, ld] or
+    None, w16T [cols, ldT] or None)], w16 / w16T of `dtype`; returns (table tensor, ntensors, total tiles).  One synchronous
+    upload: build it once, outside graph capture."""
+    chk = _bf16 if dtype == torch.bfloat16 else _f16
     import struct
     lib = _lib.load()
     assert lib.dclip_mt_weights_record_bytes() == 48
@@ -698,9 +705,9 @@ def mt_weights_table(recs):
         ldT = w16T.shape[1] if w16T is not None else rows
         if cols % 4 or ld % 4 or ldT % 8:
             raise ValueError("mt_weights_table: cols / ld must be multiples of 4, ldT of 8")
-        if w16 is not None and (tuple(_bf16(w16, "w16").shape) != (rows, ld)):
+        if w16 is not None and (tuple(chk(w16, "w16").shape) != (rows, ld)):
             raise ValueError("mt_weights_table: w16 shape")
-        if w16T is not None and (tuple(_bf16(w16T, "w16T").shape) != (cols, ldT)):
+        if w16T is not None and (tuple(chk(w16T, "w16T").shape) != (cols, ldT)):
             raise ValueError("mt_weights_table: w16T shape")
         tiles_c = (max(cols, ld) + 63) // 64
         tiles_r = (max(rows, ldT) + 63) // 64
@@ -1018,6 +1025,203 @@ def gemm_f16(a: torch.Tensor, w: torch.Tensor, *, n: Optional[int] = None, k: Op
         raise ValueError("gemm_f16: out shape / dtype")
     _lib.check(lib.dclip_gemm_f16(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual), M, N, K, lda, ldw, N,
                                   epi, int(out_f16), _stream()), "gemm_f16")
+    return out
+
+
+# ------------------------------------------------------------------------------------------- fp16 training path
+# The bf16 training wrappers above with fp16 tensors (include/dclip_hip.h, "fp16 TRAINING path"): same shapes and limits,
+# IEEE rounding — a value beyond +-65504 becomes +-inf (the frozen fp16 wrappers above saturate), so that the overflow of a
+# loss-scaled gradient reaches the gradient norm (amp.DynamicLossScaler).
+
+def cast_f16_ieee(x: torch.Tensor, pad_to: int = 8, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cast_f16 with IEEE rounding: [rows, cols] fp32 -> fp16 [rows, cols rounded up to pad_to]; `out`: refresh in place."""
+    lib = _lib.load()
+    _f32(x, "x")
+    if x.dim() != 2:
+        raise ValueError("cast_f16_ieee: x must be 2-D")
+    rows, cols = x.shape
+    ld = (cols + pad_to - 1) // pad_to * pad_to
+    if out is not None:
+        if tuple(_f16(out, "out").shape) != (rows, ld):
+            raise ValueError(f"cast_f16_ieee: out shape {tuple(out.shape)} != {(rows, ld)}")
+        y = out
+    else:
+        y = torch.empty((rows, ld), dtype=torch.float16, device=x.device)
+    _lib.check(lib.dclip_cast_f32_f16_ieee(x.data_ptr(), y.data_ptr(), rows, cols, cols, ld, _stream()), "cast_f32_f16_ieee")
+    return y
+
+
+def layernorm_fwd_f16_stats(x, gamma, beta, eps: float):
+    """nn.LayerNorm with fp32 statistics and an fp16 result (IEEE rounding) -> (y, mean, rstd) for the backward."""
+    lib = _lib.load()
+    _f32(x, "x"), _f32(gamma, "gamma"), _f32(beta, "beta")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    y = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    _lib.check(lib.dclip_layernorm_fwd_f16_stats(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
+                                                 rstd.data_ptr(), rows, D, float(eps), _stream()), "layernorm_fwd_f16_stats")
+    return y, mean, rstd
+
+
+def transpose_f16(x: torch.Tensor, want_copy: bool = False, out: Optional[torch.Tensor] = None):
+    """transpose_bf16 with fp16 results: x [rows, cols] fp32 or fp16 -> x^T [cols, rows rounded up to 8] (and the copy)."""
+    lib = _lib.load()
+    if not (x.is_cuda and x.is_contiguous() and x.dim() == 2 and x.dtype in (torch.float32, torch.float16)):
+        raise ValueError("transpose_f16: contiguous 2-D float32 / float16 CUDA tensor")
+    rows, cols = x.shape
+    if cols % 4:
+        raise ValueError("transpose_f16: cols must be a multiple of 4")
+    ld = (rows + 7) // 8 * 8
+    if out is not None:
+        if tuple(_f16(out, "out").shape) != (cols, ld):
+            raise ValueError(f"transpose_f16: out shape {tuple(out.shape)} != {(cols, ld)}")
+        yT = out
+    else:
+        yT = torch.empty((cols, ld), dtype=torch.float16, device=x.device)
+    copy = None
+    if want_copy:
+        if cols % 8:
+            raise ValueError("transpose_f16: the fp16 copy feeds a GEMM as A: cols must be a multiple of 8")
+        copy = torch.empty((rows, cols), dtype=torch.float16, device=x.device)
+    _lib.check(lib.dclip_transpose_to_f16(x.data_ptr(), int(x.dtype == torch.float16), yT.data_ptr(), _ptr(copy), rows, cols,
+                                          cols, ld, cols, _stream()), "transpose_to_f16")
+    return (yT, copy) if want_copy else yT
+
+
+def mt_weights_f16(table: torch.Tensor, ntensors: int, total_tiles: int) -> None:
+    lib = _lib.load()
+    _lib.check(lib.dclip_mt_weights_f16(table.data_ptr(), ntensors, total_tiles, _stream()), "mt_weights_f16")
+
+
+def rowsum_f16(x: torch.Tensor, n: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Row sums (fp32) of the first n columns of an fp16 matrix [R, ld]."""
+    lib = _lib.load()
+    _f16(x, "x")
+    R, ld = x.shape
+    n = ld if n is None else n
+    out = _out_f32(out, (R,), x.device, "rowsum_f16")
+    _lib.check(lib.dclip_rowsum_f16(x.data_ptr(), out.data_ptr(), R, n, ld, _stream()), "rowsum_f16")
+    return out
+
+
+def colsum_f16(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Column sums of an fp16 matrix, fp32 result."""
+    lib = _lib.load()
+    _f16(x, "x")
+    M, N = x.shape
+    out = _out_f32(out, (N,), x.device, "colsum_f16")
+    nbytes = lib.dclip_colsum_f32_workspace(M, N)
+    ws = _ws.get(nbytes, x.device)
+    _lib.check(lib.dclip_colsum_f16(x.data_ptr(), out.data_ptr(), M, N, N, 0, _ptr(ws), nbytes, _stream()), "colsum_f16")
+    return out
+
+
+def attention_fwd_f16_lse(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool):
+    """attention_fwd_bf16_lse on fp16 (S <= 64): qkv [B*S, 3*H*64] fp16 -> (context fp16, lse fp32 [B*H, S])."""
+    lib = _lib.load()
+    _f16(qkv, "qkv")
+    if tuple(qkv.shape) != (B * S, 3 * H * 64):
+        raise ValueError(f"attention_fwd_f16_lse: qkv shape {tuple(qkv.shape)} != {(B * S, 3 * H * 64)}")
+    out = torch.empty((B * S, H * 64), dtype=torch.float16, device=qkv.device)
+    lse = torch.empty((B * H, S), dtype=torch.float32, device=qkv.device)
+    _lib.check(lib.dclip_attention_fwd_f16_lse(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, S, H, int(causal), _stream()),
+               "attention_fwd_f16_lse")
+    return out, lse
+
+
+def attention_bwd_f16(qkv, out, dout, lse, B: int, S: int, H: int, causal: bool) -> torch.Tensor:
+    """Backward of attention_fwd_f16_lse on the fp16 MFMAs (S <= 64): returns dqkv [B*S, 3*H*64] fp16."""
+    lib = _lib.load()
+    _f16(qkv, "qkv"), _f16(out, "out"), _f16(dout, "dout"), _f32(lse, "lse")
+    D = H * 64
+    if tuple(qkv.shape) != (B * S, 3 * D) or tuple(out.shape) != (B * S, D) or tuple(dout.shape) != (B * S, D) \
+            or lse.numel() != B * H * S:
+        raise ValueError("attention_bwd_f16: shape mismatch")
+    dqkv = torch.empty_like(qkv)
+    _lib.check(lib.dclip_attention_bwd_f16(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(),
+                                           B, S, H, int(causal), _stream()), "attention_bwd_f16")
+    return dqkv
+
+
+def gemm_f16_train(a: torch.Tensor, w: torch.Tensor, *, n: Optional[int] = None, k: Optional[int] = None,
+                   bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, gelu: bool = False,
+                   out_f16: bool = False, save_preact: bool = False, dgelu_of: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None):
+    """gemm_bf16 with its training epilogues on fp16 operands (dclip_gemm_f16_ex, IEEE rounding of every 16-bit output):
+    `save_preact` (with gelu) also returns the fp16 pre-activation -> (y, h); `dgelu_of=h` multiplies by quick_gelu'(h)."""
+    lib = _lib.load()
+    _f16(a, "a"), _f16(w, "w")
+    M, lda = a.shape
+    N, ldw = w.shape
+    K = k if k is not None else min(lda, ldw)
+    if n is not None:
+        N = n
+    epi = 0
+    if bias is not None:
+        epi |= EPI_BIAS
+        if _f32(bias, "bias").numel() != N:
+            raise ValueError("gemm_f16_train: bias size")
+    if gelu:
+        epi |= EPI_GELU
+    if residual is not None:
+        epi |= EPI_RESIDUAL
+        if tuple(_f32(residual, "residual").shape) != (M, N):
+            raise ValueError("gemm_f16_train: residual shape")
+    odt = torch.float16 if out_f16 else torch.float32
+    if out is None:
+        out = torch.empty((M, N), dtype=odt, device=a.device)
+    elif tuple(out.shape) != (M, N) or out.dtype != odt or not out.is_contiguous():
+        raise ValueError("gemm_f16_train: out shape / dtype")
+    aux = None
+    if save_preact:
+        if not gelu:
+            raise ValueError("gemm_f16_train: save_preact goes with gelu")
+        aux = torch.empty((M, N), dtype=torch.float16, device=a.device)
+    if dgelu_of is not None:
+        if gelu or tuple(_f16(dgelu_of, "dgelu_of").shape) != (M, N):
+            raise ValueError("gemm_f16_train: dgelu_of must be the [M, N] fp16 pre-activation (and excludes gelu)")
+        epi |= EPI_DGELU
+        aux = dgelu_of
+    _lib.check(lib.dclip_gemm_f16_ex(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual), _ptr(aux), M, N, K,
+                                     lda, ldw, N, epi, int(out_f16), _stream()), "gemm_f16_ex")
+    return (out, aux) if save_preact else out
+
+
+def gemm_f16_wgrad(a: torch.Tensor, w: torch.Tensor, k: int, splits: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemm_bf16_wgrad on fp16 token-contiguous operands (a = dY^T [M, ld], w = X^T [N, ld]) -> dW [M, N] fp32."""
+    lib = _lib.load()
+    _f16(a, "a"), _f16(w, "w")
+    M, lda = a.shape
+    N, ldw = w.shape
+    if splits is None:
+        splits = lib.dclip_gemm_f16_splitk_plan(M, N, k)
+    out = _out_f32(out, (M, N), a.device, "gemm_f16_wgrad")
+    nbytes = lib.dclip_gemm_f16_splitk_workspace(M, N, splits)
+    ws = _ws.get(nbytes, a.device)
+    _lib.check(lib.dclip_gemm_f16_splitk(a.data_ptr(), w.data_ptr(), out.data_ptr(), M, N, k, lda, ldw, N, splits,
+                                         _ptr(ws), nbytes, _stream()), "gemm_f16_splitk")
+    return out
+
+
+def gemm_f16_wgrad_tokmajor(dy: torch.Tensor, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """gemm_bf16_wgrad_tokmajor on fp16 operands dy [tokens, out], x [tokens, in]; None when the form does not apply."""
+    lib = _lib.load()
+    _f16(dy, "dy"), _f16(x, "x")
+    K, M = dy.shape
+    K2, N = x.shape
+    if K != K2:
+        raise ValueError("gemm_f16_wgrad_tokmajor: token counts differ")
+    splits = lib.dclip_gemm_f16_wgrad_tokmajor_plan(M, N, K)
+    if splits == 0:
+        return None
+    out = _out_f32(out, (M, N), dy.device, "gemm_f16_wgrad_tokmajor")
+    nbytes = lib.dclip_gemm_f16_splitk_workspace(M, N, splits)
+    ws = _ws.get(nbytes, dy.device)
+    _lib.check(lib.dclip_gemm_f16_wgrad_tokmajor(dy.data_ptr(), x.data_ptr(), out.data_ptr(), M, N, K, M, N, N, splits,
+                                                 _ptr(ws), nbytes, _stream()), "gemm_f16_wgrad_tokmajor")
     return out
 
 

@@ -28,6 +28,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self._coef = None
         self._table = {}
         self.last_grad_norm = None
+        self._amp_flag = None            # pinned copy of the last scaled step's found-inf flag
+        self._amp_pending = None         # (event behind that copy, states whose `step` that step incremented)
 
     def _records(self, group, gi):
         """(device table, ntensors, total_chunks, grads kept alive) for one parameter group."""
@@ -112,6 +114,71 @@ class FusedAdamW(torch.optim.Optimizer):
         if touched:
             torch._C._increment_version(touched)
         return loss
+
+
+    # ---------------------------------------------------------------- loss-scaled step (amp.DynamicLossScaler)
+    def settle_scaled_step(self) -> None:
+        """Take back the `step` increment of the last scaled step if it was skipped.  Its found-inf flag was copied to pinned
+        memory behind an event; by the time the next step builds its table that work has long finished."""
+        pend = self._amp_pending
+        if pend is None:
+            return
+        self._amp_pending = None
+        ev, states = pend
+        ev.synchronize()
+        if float(self._amp_flag[0]) != 0.0:
+            for st in states:
+                st["step"] -= 1
+
+    @torch.no_grad()
+    def step_scaled(self, scaler) -> bool:
+        """GradScaler.step with this optimizer (torch.optim.AdamW semantics): the gradients are loss-scaled by
+        scaler's device scale; the clip coefficient (max_grad_norm, none: no clipping) is divided by that scale and the
+        whole update is skipped on the device when the gradient norm is not finite.  Same launches as step(): one
+        sum-of-squares, one coefficient, one AdamW per group — no host read.  Returns False, launching nothing, when no
+        parameter has a gradient (no found-inf flag was written)."""
+        if self._entry != "dclip_mt_adamw_f32":
+            raise TypeError(f"{type(self).__name__}: the loss-scaled step is AdamW only")
+        self.settle_scaled_step()
+        lib = _lib.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        tables = [(g, self._records(g, gi)) for gi, g in enumerate(self.param_groups)]
+        tables = [(g, t) for g, t in tables if t is not None]
+        if not tables:
+            return False
+        total = sum(t[2] for _, t in tables)
+        dev = tables[0][1][0].device
+        if self._partials is None or self._partials.numel() < total:
+            self._partials = torch.empty(total, dtype=torch.float32, device=dev)
+            self._coef = torch.empty(2, dtype=torch.float32, device=dev)
+        o = 0
+        for _, (tab, nt, nchunks, _keep) in tables:
+            _lib.check(lib.dclip_mt_sumsq_f32(tab.data_ptr(), nt, nchunks, self._partials.data_ptr() + 4 * o, stream), "mt_sumsq")
+            o += nchunks
+        out = scaler._out
+        max_norm = float(self.max_grad_norm) if self.max_grad_norm else float("inf")
+        _lib.check(lib.dclip_clip_coef_scaled(self._partials.data_ptr(), total, max_norm, scaler._scale.data_ptr(),
+                                              out.data_ptr(), stream), "clip_coef_scaled")
+        self.last_grad_norm = out[0]
+        for group, (tab, nt, nchunks, _keep) in tables:
+            b1, b2 = group["betas"]
+            _lib.check(lib.dclip_mt_adamw_f32_skip(tab.data_ptr(), nt, nchunks, float(group["lr"]), 1.0 - float(b1),
+                                                   1.0 - float(b2), float(group["eps"]), float(group["weight_decay"]),
+                                                   out.data_ptr(), stream),
+                       "mt_adamw_skip")
+        touched = [p for group, _t in tables for p in group["params"] if p.grad is not None]
+        torch._C._increment_version(touched)
+        if self._amp_flag is None:
+            self._amp_flag = torch.zeros(1, dtype=torch.float32).pin_memory()
+        self._amp_flag.copy_(out[1:2], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._amp_pending = (ev, [self.state[p] for p in touched])
+        return True
+
+    def state_dict(self):
+        self.settle_scaled_step()
+        return super().state_dict()
 
 
 class FusedAdam(FusedAdamW):

@@ -418,6 +418,58 @@ int dclip_attention_fwd_f16(const void* qkv, void* out, int B, int S, int H, int
 int dclip_attention_row_fwd_f16(const void* qkv, const int32_t* rows, void* out, int B, int S, int H, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * fp16 TRAINING path (opt-in student_precision="fp16" / get_image_features(precision="fp16-mixed")): fp16
+ * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
+ * a finite value beyond +-65504 becomes +-inf (it does NOT saturate as the frozen fp16 entries do), NaN stays NaN, so the
+ * overflow of a loss-scaled gradient reaches the gradient norm and the loss scaler skips the step.  Only the kernels of the
+ * default plans have fp16 training instances: DCLIP_BF16_PP, _MID_DMA and _PERSIST do not apply to these entries.
+ *   gemm_f16_ex                  dclip_gemm_bf16_ex (aux = the fp16 GELU pre-activation / dGELU input).
+ *   gemm_f16_wgrad_tokmajor(_plan), gemm_f16_splitk(_plan, _workspace)   the weight-gradient forms.
+ *   cast_f32_f16_ieee            dclip_cast_f32_f16 with IEEE rounding (fp32 gradients -> fp16).
+ *   layernorm_fwd_f16_stats, layernorm_bwd_ex_f16 (dx_f16 = the fp16 copy of dx), transpose_to_f16, rowsum_f16,
+ *   colsum_f16, mt_weights_f16 (records of dclip_mt_weights_record_bytes(), fp16 destinations).
+ *   attention_fwd_f16_lse / attention_bwd_f16   S <= 64 both; P and dS rounded to fp16 for the products they feed. */
+int dclip_gemm_f16_ex(const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux, int M,
+                      int N, int K, int lda, int ldw, int ldc, int epilogue, int out_f16, void* stream);
+int dclip_gemm_f16_wgrad_tokmajor_plan(int M, int N, int K);
+int dclip_gemm_f16_wgrad_tokmajor(const void* dY, const void* X, float* C, int M, int N, int K, int lddy, int ldx, int ldc,
+                                  int splits, void* workspace, size_t workspace_bytes, void* stream);
+int dclip_gemm_f16_splitk_plan(int M, int N, int K);
+size_t dclip_gemm_f16_splitk_workspace(int M, int N, int splits);
+int dclip_gemm_f16_splitk(const void* A, const void* W, float* C, int M, int N, int K, int lda, int ldw, int ldc, int splits,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int dclip_cast_f32_f16_ieee(const float* x, void* y, int rows, int cols, int ldx, int ldy, void* stream);
+int dclip_layernorm_fwd_f16_stats(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                                  int rows, int D, float eps, void* stream);
+int dclip_layernorm_bwd_ex_f16(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                               const float* dresidual, float* dx, void* dx_f16, float* dgamma, float* dbeta, float* dx_colsum,
+                               int rows, int D, int accumulate_param_grads, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int dclip_transpose_to_f16(const void* x, int x_is_f16, void* yT, void* y_copy, int rows, int cols, int ldx, int ldyT,
+                           int ldy, void* stream);
+int dclip_rowsum_f16(const void* x, float* out, int R, int n, int ld, void* stream);
+int dclip_colsum_f16(const void* X, float* out, int M, int N, int ldx, int accumulate, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int dclip_mt_weights_f16(const void* refs, int ntensors, int total_tiles, void* stream);
+int dclip_attention_fwd_f16_lse(const void* qkv, void* out, float* lse, int B, int S, int H, int causal, void* stream);
+int dclip_attention_bwd_f16(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int S,
+                            int H, int causal, void* stream);
+/* Dynamic loss scaling on the device (torch.amp.GradScaler semantics; dclip_amd/amp.py).  No pass over the gradients of its
+ * own: the partial sums of dclip_mt_sumsq_f32 over the SCALED gradients feed
+ *   clip_coef_scaled  out[3] = { unscaled norm, found_inf (1 when the norm is not finite), min(1, max_norm/(norm+1e-6))/scale
+ *                     or 0 with found_inf }: the unscaling folded into the clip coefficient (*scale is read on the device);
+ *   mt_adamw_f32_skip dclip_mt_adamw_f32 with grad_scale = that out[3]: coefficient out[2]; returns without writing anything
+ *                     (parameters, moments, weight decay) when out[1] is set.  Takes 1 - beta1 / 1 - beta2 (computed in
+ *                     double by the caller, as torch does) in place of the betas;
+ *   amp_update_scale  torch's _amp_update_scale_ on one lane: found_inf -> scale *= backoff, tracker = 0; otherwise
+ *                     tracker + 1 == interval -> scale *= growth (if finite), tracker = 0; else tracker += 1. */
+int dclip_clip_coef_scaled(const float* partial, int n, float max_norm, const float* scale, float* out, void* stream);
+int dclip_mt_adamw_f32_skip(const void* refs, int ntensors, int total_chunks, float lr, float one_minus_beta1,
+                            float one_minus_beta2, float eps, float weight_decay, const float* coef3, void* stream);
+int dclip_amp_update_scale(float* scale, int* growth_tracker, const float* found_inf, float growth_factor,
+                           float backoff_factor, int growth_interval, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Small elementwise helpers used between the ops above (all fp32, 16-byte vectorised).
  */
 int dclip_axpby(const float* x, float* y, float a, float b, size_t n, void* stream); /* y = a*x + b*y */
