@@ -1507,6 +1507,31 @@ __global__ void __launch_bounds__(KT * 64) attn_bwd_rows_kernel(AttnArgs a, cons
   }
 }
 
+// One key per sequence (Sk == 1): the softmax is identically 1, so dQ = dK = 0 and dV = the sum of dO over the queries —
+// exactly.  The general kernels form dS = P (dP - delta) with dP and delta summed in different orders and leave rounding
+// noise (4e-7 .. 1.4e-6 measured) where the gradient is zero.  One workgroup per (batch, head), one lane per head dim.
+// IO16: the bf16-I/O entry (self-attention, so Sq == 1 as well and dV is dO itself, bit for bit).
+template <bool IO16 = false>
+__global__ void __launch_bounds__(64) attn_bwd_one_key_kernel(const float* __restrict__ dout, float* __restrict__ dq, int lddq,
+                                                              float* __restrict__ dk, float* __restrict__ dv, int lddkv, int Sq,
+                                                              int H) {
+  const int b = blockIdx.x / H, h = blockIdx.x % H, d = threadIdx.x;
+  if constexpr (IO16) {
+    reinterpret_cast<unsigned short*>(dq)[(size_t)b * lddq + h * HD + d] = 0;
+    reinterpret_cast<unsigned short*>(dk)[(size_t)b * lddkv + h * HD + d] = 0;
+    reinterpret_cast<unsigned short*>(dv)[(size_t)b * lddkv + h * HD + d] =
+        reinterpret_cast<const unsigned short*>(dout)[(size_t)b * H * HD + h * HD + d];
+    return;
+  }
+  float s = 0.f;
+  for (int q = 0; q < Sq; ++q) {
+    s += dout[((size_t)b * Sq + q) * H * HD + h * HD + d];
+    dq[((size_t)b * Sq + q) * lddq + h * HD + d] = 0.f;
+  }
+  dk[(size_t)b * lddkv + h * HD + d] = 0.f;
+  dv[(size_t)b * lddkv + h * HD + d] = s;
+}
+
 }  // namespace
 
 namespace {
@@ -1551,6 +1576,11 @@ inline bool long_noncausal(int Sq, int Sk, int causal) { return Sq == Sk && Sk >
 int launch_bwd(const AttnArgs& a, const float* out, const float* dout, const float* lse, float* dq, int lddq, float* dk,
                float* dv, int lddkv, float* delta, int B, int causal, hipStream_t st, float* ds = nullptr) {
   dim3 gq(B * a.H, cdiv(a.Sq, TS)), gk(B * a.H, cdiv(a.Sk, TS)), block(256);
+  if (a.Sk == 1) {   // a single key: exact zeros for dQ and dK (see the kernel)
+    hipLaunchKernelGGL((attn_bwd_one_key_kernel<false>), dim3(B * a.H), dim3(HD), 0, st, dout, dq, lddq, dk, dv, lddkv, a.Sq, a.H);
+    DCLIP_CHECK_LAUNCH("attention_bwd.one_key");
+    return DCLIP_OK;
+  }
   if (a.Sq == a.Sk && a.Sk > TS && a.Sk <= 80 && lddq == lddkv && !getenv("DCLIP_ATTN_TILED")) {
     // 65..80 rows (the 77-token text tower when it trains): whole-row kernel, 5 waves.  Measured 214 us vs 362 us for
     // the two-kernel tiled path at B=256, H=8; for S <= 64 the 5-product one-tile kernel below is faster (154 vs 178).
@@ -1702,6 +1732,11 @@ DCLIP_API int dclip_attention_bwd_io16(const void* qkv16, const void* out16, con
   float* dq = reinterpret_cast<float*>(d16);
   float* dk = reinterpret_cast<float*>(d16 + D);
   float* dv = reinterpret_cast<float*>(d16 + 2 * D);
+  if (S == 1) {   // a single key: dQ = dK = 0 exactly, as the fp32 entry does (the two must agree bit for bit on bf16 operands)
+    hipLaunchKernelGGL((attn_bwd_one_key_kernel<true>), dim3(B * H), dim3(HD), 0, st, dO, dq, 3 * D, dk, dv, 3 * D, 1, H);
+    DCLIP_CHECK_LAUNCH("attention_bwd_io16.one_key");
+    return DCLIP_OK;
+  }
   if (causal) hipLaunchKernelGGL((attn_bwd_lean_kernel<true, true>), dim3(B * H), dim3(256), 0, st, a, o, dO, lse, dq, dk, dv, 3 * D);
   else hipLaunchKernelGGL((attn_bwd_lean_kernel<false, true>), dim3(B * H), dim3(256), 0, st, a, o, dO, lse, dq, dk, dv, 3 * D);
   DCLIP_CHECK_LAUNCH("attention_bwd_io16");

@@ -13,6 +13,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 void dclip_set_error(const char* fmt, ...);
+void dclip_note_launch(const char* name);   // what dclip_last_launch() returns; `name` is a string literal
 
 #define DCLIP_REQUIRE(cond, ...)                         \
   do {                                                   \
@@ -22,9 +23,11 @@ void dclip_set_error(const char* fmt, ...);
     }                                                    \
   } while (0)
 
-// Launch check that does not synchronise: hipGetLastError only reports launch-time failures.
+// Launch check that does not synchronise: hipGetLastError only reports launch-time failures.  It also records the launch
+// site's name for dclip_last_launch(): a test that forces a kernel path asserts there that the path was taken.
 #define DCLIP_CHECK_LAUNCH(name)                                                      \
   do {                                                                                \
+    dclip_note_launch(name);                                                          \
     hipError_t e__ = hipGetLastError();                                               \
     if (e__ != hipSuccess) {                                                          \
       dclip_set_error("%s: launch failed: %s", name, hipGetErrorString(e__));         \

@@ -779,10 +779,15 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(GemmParams p, int sp
   }
 }
 
+// Returns the launch-site name of the kernel variant it chose (what dclip_last_launch reports).
 template <int BM, int BN, int WM, int WN>
-int launch_cfg(const GemmParams& p_in, int layout, int splits, hipStream_t st) {
+const char* launch_cfg(const GemmParams& p_in, int layout, int splits, hipStream_t st) {
   GemmParams p = p_in;
-  p.magic_per_group = (unsigned)(0x100000000ull / (unsigned long long)(p.group_m * p.tiles_n));
+  // floor(2^32 / per_group), which is 2^32 itself for one tile per group (DCLIP_GEMM_GROUP_M=1 with a single tile column):
+  // truncated to 0 it sent every workgroup to group 0 or 1 and left the other tiles unwritten.  2^32 - 1 is one short for
+  // every swz >= 1, which is what the kernel's single correction step repairs.
+  const unsigned long long magic = 0x100000000ull / (unsigned long long)(p.group_m * p.tiles_n);
+  p.magic_per_group = magic > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)magic;
 
   dim3 grid(p.tiles_m * p.tiles_n, splits);
   const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(float);
@@ -795,7 +800,7 @@ int launch_cfg(const GemmParams& p_in, int layout, int splits, hipStream_t st) {
     if (dma && ak && p.mode == MODE_GEMM) {
       if (bk) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, true, true>), grid, dim3(WM * WN * 64), lds, st, p);
       else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, false, true>), grid, dim3(WM * WN * 64), lds, st, p);
-      return 0;
+      return "gemm_f32.dma";
     }
   }
   if (ak && bk)
@@ -806,7 +811,7 @@ int launch_cfg(const GemmParams& p_in, int layout, int splits, hipStream_t st) {
     hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, true>), grid, dim3(WM * WN * 64), lds, st, p);
   else
     hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, false>), grid, dim3(WM * WN * 64), lds, st, p);
-  return 0;
+  return WM * WN == 8 ? "gemm_f32.w8" : "gemm_f32";
 }
 
 constexpr int NUM_CU = 256;
@@ -880,11 +885,15 @@ Plan make_plan(int M, int N, int K, int layout, int split_k) {
 DCLIP_API int dclip_debug_set_gemm_stamps(void* buf) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), &buf, sizeof(buf)) == hipSuccess ? DCLIP_OK : DCLIP_ELAUNCH;
 }
-DCLIP_API void dclip_debug_gemm_plan(int M, int N, int K, int layout, int split_k, int* out4) {
-  Plan pl = make_plan(M, N, K, layout, split_k);
-  out4[0] = pl.bm, out4[1] = pl.bn, out4[2] = pl.splits, out4[3] = pl.k_per_split;
-}
 #endif
+
+// The plan dclip_gemm_f32 would run for this problem under the current environment: out = {BM, BN, splits, k_per_split}.
+DCLIP_API int dclip_gemm_f32_plan(int M, int N, int K, int layout, int split_k, int out[4]) {
+  DCLIP_REQUIRE(out && M > 0 && N > 0 && K > 0, "gemm_f32_plan: bad arguments");
+  Plan pl = make_plan(M, N, K, layout, split_k);
+  out[0] = pl.bm, out[1] = pl.bn, out[2] = pl.splits, out[3] = pl.k_per_split;
+  return DCLIP_OK;
+}
 
 DCLIP_API size_t dclip_gemm_f32_workspace(int M, int N, int K, int layout, int split_k) {
   Plan pl = make_plan(M, N, K, layout, split_k);
@@ -935,12 +944,13 @@ DCLIP_API int dclip_gemm_f32(const float* A, const float* B, float* C, const flo
   }
   hipStream_t st = (hipStream_t)stream;
   static const bool w8 = getenv("DCLIP_GEMM_W8") != nullptr;   // experiment: 8-wave 128x128 workgroups
-  if (pl.bm == 128 && pl.bn == 128 && w8) launch_cfg<128, 128, 2, 4>(p, layout, pl.splits, st);
-  else if (pl.bm == 128 && pl.bn == 128) launch_cfg<128, 128, 2, 2>(p, layout, pl.splits, st);
-  else if (pl.bm == 128 && pl.bn == 64) launch_cfg<128, 64, 2, 2>(p, layout, pl.splits, st);
-  else if (pl.bm == 64 && pl.bn == 128) launch_cfg<64, 128, 2, 2>(p, layout, pl.splits, st);
-  else launch_cfg<64, 64, 2, 2>(p, layout, pl.splits, st);
-  DCLIP_CHECK_LAUNCH("gemm_f32");
+  const char* site;
+  if (pl.bm == 128 && pl.bn == 128 && w8) site = launch_cfg<128, 128, 2, 4>(p, layout, pl.splits, st);
+  else if (pl.bm == 128 && pl.bn == 128) site = launch_cfg<128, 128, 2, 2>(p, layout, pl.splits, st);
+  else if (pl.bm == 128 && pl.bn == 64) site = launch_cfg<128, 64, 2, 2>(p, layout, pl.splits, st);
+  else if (pl.bm == 64 && pl.bn == 128) site = launch_cfg<64, 128, 2, 2>(p, layout, pl.splits, st);
+  else site = launch_cfg<64, 64, 2, 2>(p, layout, pl.splits, st);
+  DCLIP_CHECK_LAUNCH(site);   // "gemm_f32", "gemm_f32.dma" (LDS-DMA staging) or "gemm_f32.w8" (8-wave workgroups)
   if (pl.splits > 1) {
     const size_t total4 = (size_t)M * N / 4;
     int blocks = (int)((total4 + 255) / 256);

@@ -2,6 +2,7 @@
 #include "common.h"
 
 static thread_local char g_err[512] = "";
+static thread_local const char* g_last_launch = "";
 
 void dclip_set_error(const char* fmt, ...) {
   va_list ap;
@@ -12,6 +13,9 @@ void dclip_set_error(const char* fmt, ...) {
 
 DCLIP_API int dclip_abi_version(void) { return DCLIP_ABI_VERSION; }
 DCLIP_API const char* dclip_last_error(void) { return g_err; }
+
+void dclip_note_launch(const char* name) { g_last_launch = name; }
+DCLIP_API const char* dclip_last_launch(void) { return g_last_launch; }
 
 namespace {
 

@@ -41,6 +41,12 @@ enum {
 
 int dclip_abi_version(void);
 const char* dclip_last_error(void);
+/* Name of the calling thread's most recent kernel launch site ("" before the first): lets a test that forces a kernel
+ * path with an environment switch assert that the path was taken.  The fp32 GEMM reports "gemm_f32" (register staging),
+ * "gemm_f32.dma" (LDS-DMA staging), "gemm_f32.w8" (8-wave workgroups) or, after a split-K, "gemm_f32.splitk_reduce"; the
+ * attention "attention_fwd.rows" / ".stream" / "" (tiled) and "attention_bwd.rows" / ".lean" / ".fused" / ".stream_ds" /
+ * ".stream" / ".one_key" / "" (tiled). */
+const char* dclip_last_launch(void);
 
 /* ------------------------------------------------------------------------------------------
  * GEMM  C[M,N] = epilogue( sum_k A(m,k) * B(k,n) )           (fp32 MFMA, LDS-tiled)
@@ -82,6 +88,9 @@ const char* dclip_last_error(void);
 #define DCLIP_EPI_A_ROWSUM 32
 
 size_t dclip_gemm_f32_workspace(int M, int N, int K, int layout, int split_k);
+/* The plan dclip_gemm_f32 runs for this problem under the current environment (DCLIP_GEMM_TILE, DCLIP_GEMM_PLAN_TABLE):
+ * out = { tile rows BM, tile columns BN, K splits, K elements per split }. */
+int dclip_gemm_f32_plan(int M, int N, int K, int layout, int split_k, int out[4]);
 int dclip_gemm_f32(const float* A, const float* B, float* C, const float* bias, const float* residual,
                    float* aux, int M, int N, int K, int lda, int ldb, int ldc, int layout, int epilogue,
                    float alpha, int split_k, void* workspace, size_t workspace_bytes, void* stream);

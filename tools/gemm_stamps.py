@@ -30,7 +30,7 @@ _lib.LIB_PATH = os.path.abspath(args.lib)
 lib = _lib.load()
 raw = C.CDLL(_lib.LIB_PATH)
 raw.dclip_debug_set_gemm_stamps.argtypes = [C.c_void_p]
-raw.dclip_debug_gemm_plan.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)]
+raw.dclip_gemm_f32_plan.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)]
 dev = torch.device("cuda:0")
 M = 12800
 SHAPES = {
@@ -48,7 +48,7 @@ for name, layout, m, n, k in SHAPES[args.shapes]:
     b = torch.randn((n, k) if layout & 2 else (k, n), device=dev)
     out = torch.empty(m, n, device=dev)
     plan = (C.c_int * 4)()
-    raw.dclip_debug_gemm_plan(m, n, k, layout, 0, plan)
+    raw.dclip_gemm_f32_plan(m, n, k, layout, 0, plan)
     bm, bn, splits, kps = list(plan)
     raw.dclip_debug_set_gemm_stamps(None)
     for _ in range(3):
