@@ -365,8 +365,8 @@ __global__ void __launch_bounds__(64 * NB, (XQ ? 4 : 1)) attn_fwd_bf16_head_kern
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        u16x4 v = {T::bits(o[dt][4 * j + 0] * inv), T::bits(o[dt][4 * j + 1] * inv), T::bits(o[dt][4 * j + 2] * inv),
-                   T::bits(o[dt][4 * j + 3] * inv)};
+        u16x4 v = {T::bits_prod(o[dt][4 * j + 0], inv), T::bits_prod(o[dt][4 * j + 1], inv), T::bits_prod(o[dt][4 * j + 2], inv),
+                   T::bits_prod(o[dt][4 * j + 3], inv)};
         *reinterpret_cast<u16x4*>(orow + 32 * dt + 8 * j + 4 * half) = v;
       }
   }
@@ -748,6 +748,9 @@ DCLIP_API int dclip_attention_row_fwd_f16(const void* qkv, const int32_t* rows, 
 }
 
 namespace {
+// what dclip_last_launch() appends for the whole-head kernel's NB = cdiv(S, 32) instance
+const char* const kHeadVariant[10] = {"", ".head1", ".head2", ".head3", ".head4", ".head5", ".head6", ".head7", ".head8", ".head9"};
+
 // Training forms (bf16 student, configs c3 / c5): the forward also leaves the log-sum-exp of the scaled scores (S <= 288 for
 // bf16; S <= 64 for fp16, the backward's limit and the only whole-head instances built for the fp16 training type), the
 // backward (S <= 64) returns dq | dk | dv as 16-bit [B*S][3*H*64].
@@ -760,6 +763,7 @@ int attention_fwd16_lse(const char* name, const void* qkv, void* out, float* lse
   hipStream_t st = (hipStream_t)stream;
   const unsigned short* q = (const unsigned short*)qkv;
   unsigned short* o = (unsigned short*)out;
+  const int nb = cdiv(S, 32);
   if constexpr (smax == 64) {
     if (S <= 32) launch_head<T, 1>(q, o, B, S, H, causal, st, lse);
     else launch_head<T, 2>(q, o, B, S, H, causal, st, lse);
@@ -776,7 +780,7 @@ int attention_fwd16_lse(const char* name, const void* qkv, void* out, float* lse
       default: launch_head<T, 9>(q, o, B, S, H, causal, st, lse); break;
     }
   }
-  DCLIP_CHECK_LAUNCH(name);
+  DCLIP_CHECK_LAUNCH_V(name, kHeadVariant[nb]);
   return DCLIP_OK;
 }
 
@@ -787,6 +791,17 @@ int attention_bwd16(const char* name, const void* qkv, const void* out, const vo
   DCLIP_REQUIRE(B > 0 && S > 0 && S <= 64 && H > 0, "%s: B=%d S=%d (<= 64) H=%d", name, B, S, H);
   DCLIP_REQUIRE(((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) % 16 == 0, "%s: 16-byte alignment", name);
   hipStream_t st = (hipStream_t)stream;
+  if (S == 1) {
+    // a single key: P = 1 and dS = P (dP - delta) = 0, so dq = dk = 0 and dv = dO.  The kernel below forms dP (MFMA) and delta
+    // (lane sums) in two summation orders: their fp32 difference is not zero on real data and left dq, dk ~ 1e-6 where the
+    // gradient is identically zero.  The 16-bit I/O entry of attention.hip answers S = 1 with
+    // attn_bwd_one_key_kernel<IO16>, which moves 16-bit words whatever their type: that launch is reused here.
+    const int rc = dclip_attention_bwd_io16(qkv, out, dout, lse, dqkv, B, S, H, causal, stream);
+    if (rc != DCLIP_OK) return rc;
+    dclip_note_launch(name);
+    dclip_note_variant(".one_key");
+    return DCLIP_OK;
+  }
   if (causal)
     hipLaunchKernelGGL((attn_bwd_bf16_kernel<T, true>), dim3(B * H), dim3(128), 0, st, (const unsigned short*)qkv,
                        (const unsigned short*)out, (const unsigned short*)dout, lse, (unsigned short*)dqkv, S, H);
@@ -831,7 +846,7 @@ int attention_fwd16(const char* name, const void* qkv, void* out, int B, int S, 
     static const bool no_xq = getenv("DCLIP_ATTN16_NO_XQ") && atoi(getenv("DCLIP_ATTN16_NO_XQ")) != 0;   // A/B switch
     if (S == 257 && !causal && !no_xq) {            // 8 waves sharing the 257th query: two workgroups per CU instead of one
       hipLaunchKernelGGL((attn_fwd_bf16_head_kernel<T, 8, false, true>), dim3(B * H), dim3(512), 0, st, q, o, S, H);
-      DCLIP_CHECK_LAUNCH(name);
+      DCLIP_CHECK_LAUNCH_V(name, ".head_xq");
       return DCLIP_OK;
     }
     switch (cdiv(S, 32)) {
@@ -845,13 +860,13 @@ int attention_fwd16(const char* name, const void* qkv, void* out, int B, int S, 
       case 8: launch_head<T, 8>(q, o, B, S, H, causal, st); break;
       default: launch_head<T, 9>(q, o, B, S, H, causal, st); break;
     }
-    DCLIP_CHECK_LAUNCH(name);
+    DCLIP_CHECK_LAUNCH_V(name, kHeadVariant[cdiv(S, 32)]);
     return DCLIP_OK;
   }
   dim3 grid(B * H, cdiv(S, 64)), block(128);
   if (causal) hipLaunchKernelGGL((attn_fwd_bf16_kernel<T, true>), grid, block, 0, st, (const unsigned short*)qkv, (unsigned short*)out, S, H);
   else hipLaunchKernelGGL((attn_fwd_bf16_kernel<T, false>), grid, block, 0, st, (const unsigned short*)qkv, (unsigned short*)out, S, H);
-  DCLIP_CHECK_LAUNCH(name);
+  DCLIP_CHECK_LAUNCH_V(name, ".tiled");
   return DCLIP_OK;
 }
 }  // namespace

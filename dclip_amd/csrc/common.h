@@ -14,6 +14,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 void dclip_set_error(const char* fmt, ...);
 void dclip_note_launch(const char* name);   // what dclip_last_launch() returns; `name` is a string literal
+// a kernel-variant suffix (string literal, ".r64", ".head3", ...) appended to the name the last dclip_note_launch recorded
+void dclip_note_variant(const char* variant);
 
 #define DCLIP_REQUIRE(cond, ...)                         \
   do {                                                   \
@@ -33,6 +35,13 @@ void dclip_note_launch(const char* name);   // what dclip_last_launch() returns;
       dclip_set_error("%s: launch failed: %s", name, hipGetErrorString(e__));         \
       return DCLIP_ELAUNCH;                                                           \
     }                                                                                 \
+  } while (0)
+
+// The 16-bit dispatchers share one body per entry family (`name` is the entry's name): they add the variant they launched.
+#define DCLIP_CHECK_LAUNCH_V(name, variant) \
+  do {                                      \
+    DCLIP_CHECK_LAUNCH(name);               \
+    dclip_note_variant(variant);            \
   } while (0)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -97,6 +106,7 @@ struct Bf16T {
   // rounding of a value that is a probability (attention's P, in [0, 1] or NaN): no range handling needed
   static __device__ __forceinline__ elem cvt_unit(float x) { return (__bf16)x; }
   static __device__ __forceinline__ unsigned short bits(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
+  static __device__ __forceinline__ unsigned short bits_prod(float a, float b) { return bits(a * b); }   // see F16IeeeT
   static __device__ __forceinline__ float to_f32(unsigned int h) { return __builtin_bit_cast(float, h << 16); }
   // the element in the low / high half of a dword
   static __device__ __forceinline__ float lo_f32(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
@@ -118,6 +128,7 @@ struct F16T {
     const float s = (a > 65504.f && a != __builtin_inff()) ? __builtin_copysignf(65504.f, x) : x;   // false for NaN
     return __builtin_bit_cast(unsigned short, (_Float16)s);
   }
+  static __device__ __forceinline__ unsigned short bits_prod(float a, float b) { return bits(a * b); }   // see F16IeeeT
   static __device__ __forceinline__ float to_f32(unsigned int h) {
     return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
   }
@@ -136,4 +147,13 @@ struct F16T {
 // then reaches the global gradient norm, and the loss scaler skips the step and lowers its scale (torch GradScaler).
 struct F16IeeeT : F16T {
   static __device__ __forceinline__ unsigned short bits(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
+  // fp16(a b) with the product rounded to fp32 first, as bits(a * b) of the other two types is.  Without the barrier the
+  // compiler fuses the multiply into this type's bare conversion (v_fma_mixlo_f16: ONE rounding), and the attention forward
+  // of the training path differed from the frozen-tower one on the same fp16 input by one ulp in ~1 of 6000 elements
+  // (DESIGN.md §17).
+  static __device__ __forceinline__ unsigned short bits_prod(float a, float b) {
+    float p = a * b;
+    asm volatile("" : "+v"(p));
+    return bits(p);
+  }
 };

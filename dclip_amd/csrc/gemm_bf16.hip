@@ -1400,19 +1400,29 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
                       (unsigned short*)aux, 0, nullptr};
     // persistent form when a CU gets several tiles (the towers' M = 100k shapes: 14 per CU): the epilogue of one tile
-    // overlaps the K loop of the next.  DGELU (an extra side operand in the epilogue) stays on the one-tile kernel.
+    // overlaps the K loop of the next.  DGELU (an extra side operand in the epilogue) stays on the one-tile kernel, and so does
+    // GELU with an fp32 C: the persistent kernel's fp32 store path applies bias and residual only (it returned the
+    // pre-activation and left aux unwritten: tests/test_gemm16_paths_gpu.py).
     const int persist_min = getenv("DCLIP_BF16_PERSIST_MIN") ? atoi(getenv("DCLIP_BF16_PERSIST_MIN")) : 512;
-    const bool persist = !kTrain16<T> && pingpong_enabled() && persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && ldc % 8 == 0 && N % 8 == 0 &&
-                         (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min;
+    const bool gelu_f32 = (epilogue & DCLIP_EPI_GELU) && !out_bf16;
+    const bool persist = !kTrain16<T> && pingpong_enabled() && persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && !gelu_f32 &&
+                         ldc % 8 == 0 && N % 8 == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min;
+    const char* variant = ".pp";
     if constexpr (kTrain16<T>) {
       (void)persist;
       launch_pp<T>(pb, st);
     } else {
-      if (persist) launch_ppp<T>(pb, st);
-      else if (pingpong_enabled()) launch_pp<T>(pb, st);
-      else launch_dma<T, 256, 256, 2, 4>(pb, st);
+      if (persist) {
+        launch_ppp<T>(pb, st);
+        variant = ".ppp";
+      } else if (pingpong_enabled()) {
+        launch_pp<T>(pb, st);
+      } else {
+        launch_dma<T, 256, 256, 2, 4>(pb, st);
+        variant = ".dma256";
+      }
     }
-    DCLIP_CHECK_LAUNCH(name);
+    DCLIP_CHECK_LAUNCH_V(name, variant);
     return DCLIP_OK;
   }
   // A/B aid: DCLIP_BF16_MID_DMA=1 sends what falls below the big-tile threshold (K % 64 == 0) to the 128x128 LDS-DMA kernel,
@@ -1423,7 +1433,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
       GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
                         (unsigned short*)aux, 0, nullptr};
       launch_dma<T, 128, 128, 2, 2>(pb, st);
-      DCLIP_CHECK_LAUNCH(name);
+      DCLIP_CHECK_LAUNCH_V(name, ".dma128");
       return DCLIP_OK;
     }
   }
@@ -1434,7 +1444,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
   const size_t lds = (size_t)2 * (bm + bn) * BKH * 2;
   if (small) hipLaunchKernelGGL((gemm_bf16_kernel<T, 64, 64>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
   else hipLaunchKernelGGL((gemm_bf16_kernel<T, 128, 128>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
-  DCLIP_CHECK_LAUNCH(name);
+  DCLIP_CHECK_LAUNCH_V(name, small ? ".r64" : ".r128");
   return DCLIP_OK;
 }
 }  // namespace
@@ -1490,7 +1500,7 @@ int wgrad_tokmajor16(const char* name, const void* dY, const void* X, float* C, 
   if (s_eff == 1) {
     GemmBf16Params pb{(const __bf16*)dY, (const __bf16*)X, C, nullptr, nullptr, M, N, K, lddy, ldx, ldc, 0, 0, 0, 0, nullptr, 0, nullptr};
     launch_pp<T, true>(pb, st, 1);
-    DCLIP_CHECK_LAUNCH(name);
+    DCLIP_CHECK_LAUNCH_V(name, ".pp_tok");
     return DCLIP_OK;
   }
   const size_t need = (size_t)s_eff * M * N * sizeof(float);
@@ -1502,10 +1512,10 @@ int wgrad_tokmajor16(const char* name, const void* dY, const void* X, float* C, 
   GemmBf16Params pb{(const __bf16*)dY, (const __bf16*)X, C, nullptr, nullptr, M, N, K, lddy, ldx, ldc, 0, 0, 0, 0, nullptr, kps,
                     (float*)workspace};
   launch_pp<T, true>(pb, st, s_eff);
-  DCLIP_CHECK_LAUNCH(name);
+  DCLIP_CHECK_LAUNCH_V(name, ".pp_tok");
   hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, st, (const float*)workspace, C, M,
                      N, ldc, s_eff);
-  DCLIP_CHECK_LAUNCH(name);
+  DCLIP_CHECK_LAUNCH_V(name, ".pp_tok.splitk_reduce");
   return DCLIP_OK;
 }
 }  // namespace
@@ -1549,7 +1559,12 @@ int layernorm16(const char* name, const float* x, const float* gamma, const floa
   hipStream_t st = (hipStream_t)stream;
   const int nc = cdiv(D / 4, 64);
   unsigned short* yy = (unsigned short*)y;
-#define LN16(NC, EX) hipLaunchKernelGGL((ln_fwd_bf16_kernel<T, NC, EX>), grid, block, 0, st, x, gamma, beta, yy, rows, D, eps, mean, rstd)
+  const char* variant;
+#define LN16(NC, EX)                                                                                                         \
+  do {                                                                                                                       \
+    hipLaunchKernelGGL((ln_fwd_bf16_kernel<T, NC, EX>), grid, block, 0, st, x, gamma, beta, yy, rows, D, eps, mean, rstd); \
+    variant = (EX) ? ".nc" #NC ".exact" : ".nc" #NC;                                                                         \
+  } while (0)
   if (D == 512) LN16(2, true);
   else if (D == 768) LN16(3, true);
   else if (D == 1024) LN16(4, true);
@@ -1559,7 +1574,7 @@ int layernorm16(const char* name, const float* x, const float* gamma, const floa
   else if (nc == 4) LN16(4, false);
   else LN16(8, false);
 #undef LN16
-  DCLIP_CHECK_LAUNCH(name);
+  DCLIP_CHECK_LAUNCH_V(name, variant);
   return DCLIP_OK;
 }
 }  // namespace
@@ -1638,10 +1653,10 @@ int splitk16(const char* name, const void* A, const void* W, float* C, int M, in
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, 0, nullptr, kps,
                       (float*)workspace};
     launch_pp<T>(pb, (hipStream_t)stream, s_eff);
-    DCLIP_CHECK_LAUNCH(name);
+    DCLIP_CHECK_LAUNCH_V(name, ".pp");
     hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const float*)workspace, C, M, N, ldc, s_eff);
-    DCLIP_CHECK_LAUNCH(name);
+    DCLIP_CHECK_LAUNCH_V(name, ".pp.splitk_reduce");
     return DCLIP_OK;
   }
   GemmBf16Params p{(const __bf16*)A, (const __bf16*)W, C, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0,
@@ -1649,10 +1664,10 @@ int splitk16(const char* name, const void* A, const void* W, float* C, int M, in
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)2 * (128 + 128) * BKH * 2;
   hipLaunchKernelGGL((gemm_bf16_kernel<T, 128, 128>), dim3(p.tiles_m * p.tiles_n, s_eff), dim3(256), lds, st, p);
-  DCLIP_CHECK_LAUNCH(name);
+  DCLIP_CHECK_LAUNCH_V(name, ".r128");
   hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, st, (const float*)workspace, C,
                      M, N, ldc, s_eff);
-  DCLIP_CHECK_LAUNCH(name);
+  DCLIP_CHECK_LAUNCH_V(name, ".r128.splitk_reduce");
   return DCLIP_OK;
 }
 }  // namespace

@@ -3,6 +3,8 @@
 
 static thread_local char g_err[512] = "";
 static thread_local const char* g_last_launch = "";
+static thread_local const char* g_last_variant = "";
+static thread_local char g_last_launch_full[96] = "";
 
 void dclip_set_error(const char* fmt, ...) {
   va_list ap;
@@ -14,8 +16,17 @@ void dclip_set_error(const char* fmt, ...) {
 DCLIP_API int dclip_abi_version(void) { return DCLIP_ABI_VERSION; }
 DCLIP_API const char* dclip_last_error(void) { return g_err; }
 
-void dclip_note_launch(const char* name) { g_last_launch = name; }
-DCLIP_API const char* dclip_last_launch(void) { return g_last_launch; }
+void dclip_note_launch(const char* name) {
+  g_last_launch = name;
+  g_last_variant = "";
+}
+void dclip_note_variant(const char* variant) { g_last_variant = variant; }
+// the two literals are joined here, on the query, so that a launch costs two pointer stores
+DCLIP_API const char* dclip_last_launch(void) {
+  if (!g_last_variant[0]) return g_last_launch;
+  snprintf(g_last_launch_full, sizeof(g_last_launch_full), "%s%s", g_last_launch, g_last_variant);
+  return g_last_launch_full;
+}
 
 namespace {
 

@@ -45,7 +45,12 @@ const char* dclip_last_error(void);
  * path with an environment switch assert that the path was taken.  The fp32 GEMM reports "gemm_f32" (register staging),
  * "gemm_f32.dma" (LDS-DMA staging), "gemm_f32.w8" (8-wave workgroups) or, after a split-K, "gemm_f32.splitk_reduce"; the
  * attention "attention_fwd.rows" / ".stream" / "" (tiled) and "attention_bwd.rows" / ".lean" / ".fused" / ".stream_ds" /
- * ".stream" / ".one_key" / "" (tiled). */
+ * ".stream" / ".one_key" / "" (tiled).  The 16-bit entries append the kernel variant to their own name: the GEMMs
+ * (gemm_bf16, gemm_f16, gemm_f16_ex, gemm_*_splitk, gemm_*_wgrad_tokmajor) ".r64" / ".r128" (register-staged), ".dma128" /
+ * ".dma256" (LDS-DMA), ".pp" (ping-pong), ".pp_tok" (its token-major form), ".ppp" (persistent) and, after a split-K,
+ * that name + ".splitk_reduce"; attention_fwd_{bf16,f16}[_lse] ".head1" .. ".head9" (whole-head, NB = ceil(S / 32)),
+ * ".head_xq" (257 tokens, shared last query) or ".tiled"; attention_bwd_{bf16,f16} "" or ".one_key" (S = 1);
+ * layernorm_fwd_* ".nc<N>" or ".nc<N>.exact".  The pointer stays valid until the thread's next call of this function. */
 const char* dclip_last_launch(void);
 
 /* ------------------------------------------------------------------------------------------

@@ -119,7 +119,8 @@ def test_meta_teacher_bf16_towers_close_to_fp32():
 @pytest.mark.parametrize("pingpong", ["1", "0"])
 def test_gemm_bf16_big_tile_kernel_matches(pingpong):
     """The 256x256 LDS-DMA kernels (ping-pong schedule, and the lock-step one behind DCLIP_BF16_PP=0), forced onto small
-    shapes (DCLIP_BF16_BIG_MIN=1 is read once per process: this test runs the comparison in a child process), against
+    shapes (DCLIP_BF16_BIG_MIN=1 is read on every call; DCLIP_BF16_PP is read once per process, so this test runs the
+    comparison in a child process), against
     the fp64 product of the rounded inputs.  K = 64 .. 3072 covers 1, 2, 3 (odd), 12 and 48 K-tiles."""
     import subprocess, sys, os, textwrap
     code = textwrap.dedent("""
