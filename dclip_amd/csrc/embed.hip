@@ -146,13 +146,14 @@ DCLIP_API int dclip_im2col(const float* pixels, float* cols, int B, int C, int H
                 Wimg, patch);
   const int g = Himg / patch;
   const size_t total = (size_t)B * g * g * C * patch * patch;
-  if (patch % 4 == 0 && ((uintptr_t)pixels | (uintptr_t)cols) % 16 == 0)
+  const bool vec = patch % 4 == 0 && ((uintptr_t)pixels | (uintptr_t)cols) % 16 == 0;
+  if (vec)
     hipLaunchKernelGGL((im2col_vec_kernel<float>), dim3(grid_for(total / 4)), dim3(256), 0, (hipStream_t)stream, pixels, cols, B,
                        C, Himg, Wimg, patch, g, C * patch * patch, total / 4);
   else
     hipLaunchKernelGGL(im2col_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, pixels, cols, B, C, Himg, Wimg,
                        patch, g, total);
-  DCLIP_CHECK_LAUNCH("im2col");
+  DCLIP_CHECK_LAUNCH_V("im2col", vec ? ".vec" : ".scalar");
   return DCLIP_OK;
 }
 
@@ -219,6 +220,7 @@ DCLIP_API int dclip_text_embed_fwd(const int64_t* ids, const float* tok, const f
 DCLIP_API int dclip_text_embed_bwd(const int64_t* ids, const float* dx, float* dtok, int B, int T, int D, int vocab,
                                    void* stream) {
   DCLIP_REQUIRE(ids && dx && dtok, "text_embed_bwd: null pointer");
+  DCLIP_REQUIRE(B > 0 && T > 0 && D > 0 && D % 4 == 0 && vocab > 0, "text_embed_bwd: bad shape");
   const size_t total = (size_t)B * T * D;
   hipLaunchKernelGGL(text_embed_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, ids, dx, dtok, D, vocab,
                      total);

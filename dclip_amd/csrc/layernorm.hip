@@ -254,7 +254,12 @@ DCLIP_API int dclip_layernorm_fwd(const float* x, const float* gamma, const floa
   dim3 grid(cdiv(rows, 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
   const int nc = cdiv(D / 4, 64);
-#define LN_FWD(NC, EX) hipLaunchKernelGGL((ln_fwd_kernel<NC, EX>), grid, block, 0, st, x, gamma, beta, y, mean, rstd, rows, D, eps)
+  const char* variant;
+#define LN_FWD(NC, EX)                                                                                             \
+  do {                                                                                                             \
+    hipLaunchKernelGGL((ln_fwd_kernel<NC, EX>), grid, block, 0, st, x, gamma, beta, y, mean, rstd, rows, D, eps); \
+    variant = (EX) ? ".nc" #NC ".exact" : ".nc" #NC;                                                               \
+  } while (0)
   if (D == 512) LN_FWD(2, true);            // the CLIP widths: no per-chunk bounds tests
   else if (D == 768) LN_FWD(3, true);
   else if (D == 1024) LN_FWD(4, true);
@@ -264,7 +269,7 @@ DCLIP_API int dclip_layernorm_fwd(const float* x, const float* gamma, const floa
   else if (nc == 4) LN_FWD(4, false);
   else LN_FWD(8, false);
 #undef LN_FWD
-  DCLIP_CHECK_LAUNCH("layernorm_fwd");
+  DCLIP_CHECK_LAUNCH_V("layernorm_fwd", variant);
   return DCLIP_OK;
 }
 
@@ -300,9 +305,13 @@ int layernorm_bwd16(const char* name, const float* dy, const float* x, const flo
   const size_t lds = want_params ? (size_t)4 * ns * D * sizeof(float) : 0;
   const int nc = cdiv(D / 4, 64);
   unsigned short* dx16 = (unsigned short*)dx_16;
+  const char* variant;
 #define LN_BWD(NC, EX)                                                                                                      \
-  hipLaunchKernelGGL((ln_bwd_kernel<T, NC, EX>), dim3(blocks), dim3(256), lds, st, dy, x, gamma, mean, rstd, dresidual, dx,     \
-                     partial, rows, D, dx16, ns)
+  do {                                                                                                                      \
+    hipLaunchKernelGGL((ln_bwd_kernel<T, NC, EX>), dim3(blocks), dim3(256), lds, st, dy, x, gamma, mean, rstd, dresidual, dx,   \
+                       partial, rows, D, dx16, ns);                                                                         \
+    variant = (EX) ? ".nc" #NC ".exact" : ".nc" #NC;                                                                        \
+  } while (0)
   if (D == 512) LN_BWD(2, true);
   else if (D == 768) LN_BWD(3, true);
   else if (D == 1024) LN_BWD(4, true);
@@ -310,13 +319,23 @@ int layernorm_bwd16(const char* name, const float* dy, const float* x, const flo
   else if (nc == 2) LN_BWD(2, false);
   else if (nc == 3) LN_BWD(3, false);
   else if (nc == 4) LN_BWD(4, false);
-  else LN_BWD(8, false);
+  else {
+    // D > 1365 with column sums: 4 x 3 x D floats exceed the 64 KB a kernel may ask for by default (98,304 bytes at D = 2048)
+    static bool big_lds_set = false;
+    if (lds > 64 * 1024 && !big_lds_set) {
+      DCLIP_REQUIRE(hipFuncSetAttribute((const void*)ln_bwd_kernel<T, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        4 * 3 * 256 * MAXC * (int)sizeof(float)) == hipSuccess,
+                    "%s: cannot raise the LDS limit for D=%d with column sums", name, D);
+      big_lds_set = true;
+    }
+    LN_BWD(8, false);
+  }
 #undef LN_BWD
-  DCLIP_CHECK_LAUNCH(name);
+  DCLIP_CHECK_LAUNCH_V(name, variant);
   if (want_params) {
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(cdiv(ns * D, RP_COLS)), dim3(1024), 0, st, partial, dgamma, dbeta, blocks, D,
                        D, accumulate_param_grads, dx_colsum, dx_colsum ? D : 0);
-    DCLIP_CHECK_LAUNCH(name);
+    DCLIP_CHECK_LAUNCH_V(name, variant);        // (the reduce keeps the name of the instance it follows)
   }
   return DCLIP_OK;
 }

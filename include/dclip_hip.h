@@ -50,7 +50,11 @@ const char* dclip_last_error(void);
  * ".dma256" (LDS-DMA), ".pp" (ping-pong), ".pp_tok" (its token-major form), ".ppp" (persistent) and, after a split-K,
  * that name + ".splitk_reduce"; attention_fwd_{bf16,f16}[_lse] ".head1" .. ".head9" (whole-head, NB = ceil(S / 32)),
  * ".head_xq" (257 tokens, shared last query) or ".tiled"; attention_bwd_{bf16,f16} "" or ".one_key" (S = 1);
- * layernorm_fwd_* ".nc<N>" or ".nc<N>.exact".  The pointer stays valid until the thread's next call of this function. */
+ * layernorm_fwd_* ".nc<N>" or ".nc<N>.exact".  The fp32 LayerNorm reports its template instance the same way:
+ * "layernorm_fwd", "layernorm_bwd" (dclip_layernorm_bwd and _bwd_ex) and "layernorm_bwd_f16" + ".nc1" / ".nc2" / ".nc3" /
+ * ".nc4" / ".nc8" (float4 chunks per lane, NC = ceil(D / 256)) or ".nc2.exact" / ".nc3.exact" / ".nc4.exact" (D = 512, 768,
+ * 1024); the partial-sum reduce that follows a backward keeps that name.  "im2col" + ".vec" (patch % 4 == 0 and both
+ * pointers 16-byte aligned) or ".scalar".  The pointer stays valid until the thread's next call of this function. */
 const char* dclip_last_launch(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -172,13 +176,17 @@ int dclip_attention_cls_bwd(const float* qkv, const float* out, const float* dou
  *   column sum of d x viewed as [B, S*D] (dclip_colsum_f32) and d class is its first D entries.
  * text_embed: x[b,t,:] = token_embedding[ids[b,t]] + position_embedding[t] (hf:modeling_clip.py:250-255);
  *   _bwd scatter-adds d x into d token_embedding (float atomics; caller zeroes or accumulates).
+ *   Both clamp an id outside [0, vocab) into the table: id < 0 reads / adds into row 0, id >= vocab row vocab - 1
+ *   (nn.Embedding raises there; a caller that wants the error checks its ids).  Same shape rules for both: B, T, vocab > 0,
+ *   D a positive multiple of 4.
  * first_eos: index of the first EOS id per row, 0 if absent (hf:modeling_clip.py:574-581).
  * gather_rows: out[b,:] = x[b, idx[b], :] (idx == NULL: row 0, the CLS token, hf:modeling_clip.py:650);
  * scatter_rows: its transpose, writing the whole [B,S,D] gradient (zeros off the selected row).
  */
 int dclip_im2col(const float* pixels, float* cols, int B, int C, int Himg, int Wimg, int patch, void* stream);
 /* Same gather with a bf16 destination (row length ldc >= C*patch*patch, multiple of 4; patch % 4 == 0): the A operand
- * of the frozen towers' bf16 patch-embedding GEMM, written in one pass instead of im2col + cast. */
+ * of the frozen towers' bf16 patch-embedding GEMM, written in one pass instead of im2col + cast.  Columns C*patch*patch..ldc
+ * of a row are NOT written (they keep what the caller put there; the GEMM that follows reads K = C*patch*patch columns). */
 int dclip_im2col_bf16(const float* pixels, void* cols, int B, int C, int Himg, int Wimg, int patch, int ldc, void* stream);
 int dclip_vision_assemble_fwd(const float* patch, const float* cls, const float* pos, float* x, int B, int S,
                               int D, void* stream);
@@ -324,7 +332,8 @@ int dclip_cast_f32_bf16(const float* x, void* y, int rows, int cols, int ldx, in
  *   layernorm_fwd_bf16_stats   layernorm_fwd_bf16 that also returns mean / rstd (fp32 [rows]) for the backward.
  *   transpose_to_bf16    x [rows][cols] (fp32, or bf16 when x_is_bf16) -> yT [cols][ldyT] bf16 (ldyT >= rows, multiple
  *                        of 8, zero padded) and, if y_copy != NULL, the untransposed bf16 copy [rows][ldy]: the
- *                        token-contiguous operands of dW = (dY^T)(X^T)^T and the A operand of the dgrad GEMM.
+ *                        token-contiguous operands of dW = (dY^T)(X^T)^T and the A operand of the dgrad GEMM.  Columns
+ *                        rows..ldyT of yT are written as zeros; columns cols..ldy of y_copy are NOT written.
  *   rowsum_bf16          out[r] = sum of row r of a bf16 matrix [R][ld] (a bias gradient from dY^T). */
 int dclip_gemm_bf16_ex(const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux, int M,
                        int N, int K, int lda, int ldw, int ldc, int epilogue, int out_bf16, void* stream);

@@ -40,6 +40,18 @@ def test_argument_errors_do_not_need_a_gpu():
         _lib.check(rc, "gemm")
 
 
+def test_text_embed_bwd_refuses_the_shapes_its_forward_refuses():
+    from dclip_amd import _lib
+    lib = _lib.load()
+    ptr = 4096                                   # never dereferenced: every case below is refused before a launch
+    for B, T, D, vocab in [(0, 8, 64, 100), (2, 0, 64, 100), (2, 8, 0, 100), (2, 8, 6, 100), (2, 8, 64, 0), (-1, 8, 64, 100)]:
+        assert lib.dclip_text_embed_bwd(ptr, ptr, ptr, B, T, D, vocab, None) == -1, (B, T, D, vocab)
+        assert b"text_embed_bwd: bad shape" in lib.dclip_last_error()
+        if D != 0:
+            assert lib.dclip_text_embed_fwd(ptr, ptr, ptr, ptr, B, T, D, vocab, None) == -1, (B, T, D, vocab)
+    assert lib.dclip_text_embed_bwd(None, ptr, ptr, 2, 8, 64, 100, None) == -1 and b"null pointer" in lib.dclip_last_error()
+
+
 def test_product_path_does_not_import_oracle():
     bad = []
     for root, _, files in os.walk(os.path.join(REPO, "dclip_amd")):
