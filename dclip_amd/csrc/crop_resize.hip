@@ -205,8 +205,15 @@ inline Layout layout_for(int NR, int S, int max_h, int max_w, int filter) {
   return L;
 }
 
-int run_resize(const uint8_t* images, const int32_t* dims, float* out, int Hmax, int Wmax, int NR, int S, int max_h,
-               const Layout& L, int filter, const Norm& nm, void* workspace, hipStream_t st) {
+// `names`: what dclip_last_launch reports for the three launches (the entry's own name + .coeffs / .h / .v)
+struct ResizeNames {
+  const char *coeffs, *h, *v;
+};
+constexpr ResizeNames CROP_NAMES{"crop_resize.coeffs", "crop_resize.h", "crop_resize.v"};
+constexpr ResizeNames PREPROCESS_NAMES{"clip_preprocess.coeffs", "clip_preprocess.h", "clip_preprocess.v"};
+
+int run_resize(const ResizeNames& names, const uint8_t* images, const int32_t* dims, float* out, int Hmax, int Wmax, int NR,
+               int S, int max_h, const Layout& L, int filter, const Norm& nm, void* workspace, hipStream_t st) {
   char* ws = (char*)workspace;
   const int32_t* plan = (const int32_t*)(ws + L.plan);
   int32_t* bounds = (int32_t*)(ws + L.bounds);
@@ -214,15 +221,15 @@ int run_resize(const uint8_t* images, const int32_t* dims, float* out, int Hmax,
   uint8_t* tmp = (uint8_t*)(ws + L.tmp);
   hipLaunchKernelGGL(resize_coeffs_kernel, dim3(cdiv(NR * 2 * S, 256)), dim3(256), 0, st, plan, NR, S, L.KS, filter, bounds,
                      kk);
-  DCLIP_CHECK_LAUNCH("crop_resize.coeffs");
+  DCLIP_CHECK_LAUNCH(names.coeffs);
   const size_t nh = (size_t)NR * max_h * S;
   hipLaunchKernelGGL(resize_h_kernel, dim3((unsigned)cdivz(nh, 256)), dim3(256), 0, st, images, dims, plan, bounds, kk, tmp, NR,
                      S, L.KS, Hmax, Wmax, max_h);
-  DCLIP_CHECK_LAUNCH("crop_resize.h");
+  DCLIP_CHECK_LAUNCH(names.h);
   const size_t nv = (size_t)NR * S * S;
   hipLaunchKernelGGL(resize_v_kernel, dim3((unsigned)cdivz(nv, 256)), dim3(256), 0, st, tmp, bounds, kk, out, NR, S, L.KS,
                      max_h, nm);
-  DCLIP_CHECK_LAUNCH("crop_resize.v");
+  DCLIP_CHECK_LAUNCH(names.v);
   return DCLIP_OK;
 }
 
@@ -247,7 +254,7 @@ DCLIP_API int dclip_crop_resize_u8(const uint8_t* images, const int32_t* dims, c
   hipLaunchKernelGGL(plan_from_boxes_kernel, dim3(cdiv(NR, 256)), dim3(256), 0, st, boxes, (int32_t*)workspace, NR, S);
   DCLIP_CHECK_LAUNCH("crop_resize.plan");
   Norm nm{};
-  return run_resize(images, dims, out, Hmax, Wmax, NR, S, max_crop_h, L, DCLIP_FILTER_BILINEAR, nm, workspace, st);
+  return run_resize(CROP_NAMES, images, dims, out, Hmax, Wmax, NR, S, max_crop_h, L, DCLIP_FILTER_BILINEAR, nm, workspace, st);
 }
 
 DCLIP_API size_t dclip_clip_preprocess_workspace(int B, int Hmax, int Wmax, int S) {
@@ -273,5 +280,5 @@ DCLIP_API int dclip_clip_preprocess_u8(const uint8_t* images, const int32_t* dim
     nm.mean[c] = mean[c];   // HOST pointers: three floats each, read here
     nm.stdv[c] = stdv[c];
   }
-  return run_resize(images, dims, out, Hmax, Wmax, B, S, Hmax, L, DCLIP_FILTER_BICUBIC, nm, workspace, st);
+  return run_resize(PREPROCESS_NAMES, images, dims, out, Hmax, Wmax, B, S, Hmax, L, DCLIP_FILTER_BICUBIC, nm, workspace, st);
 }

@@ -270,12 +270,18 @@ int dclip_sanitize_groups(float* x, int32_t* flags, int groups, int rows, int E,
  * The reference materialises caption x image similarities chunk by chunk and argsorts every row / column
  * (eval_scripts/flickr30k_eval.py:16-88, :249-266; eval_scripts/test_zero_shot_ImageNet.py:82-103).  The rank of a
  * ground truth is the number of candidates that score strictly higher, so it is computed without the matrix:
- *   rowdot_gather: out[i] = <a_i, b_{idx[i]}>            (the ground truth's own score; idx NULL = i)
+ *   rowdot_gather: out[i] = <a_i, b_{idx[i]}>            (the ground truth's own score; idx NULL = i.  The row index
+ *                  is clamped to 0 .. Bk-1: idx[i] < 0 reads row 0, idx[i] >= Bk — and row i >= Bk with idx NULL —
+ *                  reads row Bk-1.)
  *   rank_count:    count[i] = #{ j < Bk, j != gt[i] : <q_i, c_j> > thresh[i] }   (MFMA tiles, per-row counts in the
  *                  epilogue; gt NULL = i.  The ground truth itself is excluded so that rounding differences between
  *                  its two evaluations cannot count it as "higher than itself".)
  * Inputs are L2-normalised rows (dclip_normalize_rows_fwd).  Exact ties count as not-higher (argsort's order
- * among equal scores is unspecified in the reference).
+ * among equal scores is unspecified in the reference).  A candidate row that is bit-identical to the ground truth
+ * (Flickr30k has duplicate captions) is such a tie only in exact arithmetic: rowdot_gather and the MFMA tile add the
+ * same products in two different orders, so each duplicate may or may not be counted; nothing else is affected.
+ * gt[i] outside 0 .. Bk-1 (and gt NULL with i >= Bk) excludes nothing.  The workspace holds one fp32 partial count per
+ * (32-column sub-tile, row), all of them written by every call, summed and rounded by the merge launch.
  */
 size_t dclip_rank_count_workspace(int Bq, int Bk);
 int dclip_rowdot_gather(const float* a, const float* b, const int32_t* idx, float* out, int Bq, int Bk, int P,
@@ -289,8 +295,12 @@ int dclip_rank_count(const float* queries, const float* candidates, const float*
  * two-pass BILINEAR in 8-bit fixed point) and `ToTensor()` (uint8/255, CHW, no mean/std) — for all boxes of a
  * batch in three launches, bit-exact with Pillow 12.2.
  *   images [B, Hmax, Wmax, 3] uint8 (HWC, each image in the top-left corner), dims [B,2] = (h, w),
- *   boxes [NR,5] int32 = (image index, x1, y1, x2, y2) with x2 > x1, y2 > y1,  out [NR, 3, S, S] fp32.
- *   max_crop_h / max_crop_w: the largest (y2-y1) / (x2-x1) in `boxes` (sizes the workspace and the tap count).
+ *   boxes [NR,5] int32 = (image index, x1, y1, x2, y2),  out [NR, 3, S, S] fp32.  A box may lie partly or wholly
+ *   outside its image (and outside Hmax x Wmax): what is outside dims[b] reads as zero, never the batch padding.
+ *   A box without extent (x2 <= x1 or y2 <= y1), which Pillow refuses, forms no index and yields three zero planes;
+ *   the other boxes of the call are unaffected.
+ *   max_crop_h / max_crop_w: at least the largest (y2-y1) / (x2-x1) in `boxes`, at least 1 (they size the workspace
+ *   and the tap count; a larger value changes no output bit).
  */
 size_t dclip_crop_resize_workspace(int NR, int S, int max_crop_h, int max_crop_w);
 int dclip_crop_resize_u8(const uint8_t* images, const int32_t* dims, const int32_t* boxes, float* out, int B,
