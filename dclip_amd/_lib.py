@@ -67,6 +67,10 @@ SIGNATURES = {
     "dclip_rank_count_workspace": (Z, [I, I]),
     "dclip_rowdot_gather": (I, [P, P, P, P, I, I, I, P]),
     "dclip_rank_count": (I, [P, P, P, P, P, I, I, I, P, Z, P]),
+    "dclip_topk_ip_workspace": (Z, [I, I, I]),
+    "dclip_topk_ip": (I, [P, P, P, P, I, I, I, I, P, Z, P]),
+    "dclip_relu_f32": (I, [P, Z, P]),
+    "dclip_knn_select": (I, [P, P, P, P, F, P, P, I, I, I, P]),
     "dclip_crop_resize_workspace": (Z, [I, I, I, I]),
     "dclip_crop_resize_u8": (I, [P, P, P, P, I, I, I, I, I, I, I, P, Z, P]),
     "dclip_clip_preprocess_workspace": (Z, [I, I, I, I]),

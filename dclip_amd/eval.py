@@ -60,6 +60,19 @@ def calculate_retrieval_metrics(image_embeddings, caption_embeddings, image_ids:
             for d, r in (("t2i", t2i_ranks), ("i2t", i2t_ranks))}
 
 
+def retrieve_topk(query_embeddings: torch.Tensor, gallery_embeddings: torch.Tensor, k: int):
+    """WHICH gallery rows a query retrieved: (scores [Q,k] fp32, indices [Q,k] int32) of the k best cosine similarities,
+    best first, lowest index first among equal scores (dclip_topk_ip; 1 <= k <= 16).  What the reference reads off
+    `similarity.topk(k)` / `argsort` of the dense matrix, which is not formed here."""
+    return ops.topk_ip(_normalised(query_embeddings), _normalised(gallery_embeddings), k)
+
+
+def zero_shot_topk(image_features: torch.Tensor, class_text_features: torch.Tensor, k: int = 5):
+    """The k classes every image was given, best first (eval_scripts/test_zero_shot_ImageNet.py:95 `similarity.topk(5)`;
+    its `100.0 *` changes no order): (scores [B,k], class indices [B,k])."""
+    return retrieve_topk(image_features, class_text_features, k)
+
+
 def encoders(model, precision: str = "fp32"):
     """(image encoder, text encoder) of a CLIPImageDistillation (forward(image=)/forward(text=)) or a HipCLIPModel.
     `precision` "bf16" / "fp16": the frozen 16-bit forward of the towers (HipCLIPModel.get_*_features; the student's

@@ -1314,6 +1314,55 @@ def rank_count(queries, candidates, thresh, gt=None):
     return count
 
 
+def topk_ip(queries, database, k: int):
+    """(scores [Q,k] fp32, indices [Q,k] int32): the k best database rows per query by fp32 inner product, ordered by
+    (score descending, index ascending); (-inf, -1) where fewer than k rows qualify.  See include/dclip_hip.h."""
+    lib = _lib.load()
+    _f32(queries, "queries"), _f32(database, "database")
+    if queries.dim() != 2 or database.dim() != 2 or database.shape[1] != queries.shape[1]:
+        raise ValueError("topk_ip: expected queries [Q,P] and database [N,P]")
+    if database.device != queries.device:
+        raise ValueError("topk_ip: operands on different devices")
+    Q, Pd = queries.shape
+    N = database.shape[0]
+    k = int(k)
+    scores = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    indices = torch.empty((Q, k), dtype=torch.int32, device=queries.device)
+    nbytes = lib.dclip_topk_ip_workspace(Q, N, k)
+    ws = _ws.get(nbytes, queries.device)
+    _lib.check(lib.dclip_topk_ip(queries.data_ptr(), database.data_ptr(), scores.data_ptr(), indices.data_ptr(), Q, N, Pd, k,
+                                 _ptr(ws), nbytes, _stream()), "topk_ip")
+    return scores, indices
+
+
+def relu_(x):
+    """x = max(x, 0) in place (NaN stays NaN)."""
+    lib = _lib.load()
+    _f32(x, "x")
+    _lib.check(lib.dclip_relu_f32(x.data_ptr(), x.numel(), _stream()), "relu_f32")
+    return x
+
+
+def knn_select(sim, idx, database, fallback, thresh: float):
+    """(out [Q,P], source [Q] int32): database row idx[i] where idx[i] >= 0 and sim[i] >= thresh (source 0), else
+    fallback row i (source 1).  Decided on the device."""
+    lib = _lib.load()
+    _f32(sim, "sim"), _f32(database, "database"), _f32(fallback, "fallback")
+    if fallback.dim() != 2 or database.dim() != 2 or database.shape[1] != fallback.shape[1]:
+        raise ValueError("knn_select: expected database [N,P] and fallback [Q,P]")
+    Q, Pd = fallback.shape
+    if sim.numel() != Q:
+        raise ValueError("knn_select: sim size")
+    if database.device != fallback.device or sim.device != fallback.device:
+        raise ValueError("knn_select: operands on different devices")
+    _idx(idx, Q)
+    out = torch.empty_like(fallback)
+    source = torch.empty((Q,), dtype=torch.int32, device=fallback.device)
+    _lib.check(lib.dclip_knn_select(sim.data_ptr(), idx.data_ptr(), database.data_ptr(), fallback.data_ptr(), float(thresh),
+                                    out.data_ptr(), source.data_ptr(), Q, database.shape[0], Pd, _stream()), "knn_select")
+    return out, source
+
+
 def axpby(x, y, a: float, b: float):
     """y = a*x + b*y (in place on y)."""
     lib = _lib.load()

@@ -13,8 +13,8 @@ What is kept from the reference:
 
 What is deliberately different: the per-sample Python loop (:297-553) is replaced by ONE batched frozen vision
 forward over all regions and ONE batched frozen text forward that yields token-level and sentence embeddings
-together; the KNN / projection tokenizer (disabled when its paths are empty, :78-96) and YOLO detection are out of
-scope — boxes / region crops are inputs.
+together; the KNN / projection tokenizer (enabled by its three paths, :78-96) handles all regions of a batch in one
+exact top-1 search (knn_tokenizer.py); YOLO detection is out of scope — boxes / region crops are inputs.
 """
 from __future__ import annotations
 
@@ -334,9 +334,6 @@ class PatchTextAggregation(nn.Module):
         super().__init__()
         if tower_precision not in ("fp32", "bf16", "fp16"):
             raise ValueError(f"tower_precision {tower_precision!r}")
-        if all([projection_model_path, faiss_index_path, embeddings_json_path]):
-            raise NotImplementedError("the KNN + projection tokenizer is outside the distillation step "
-                                      "(README.md:21: leave these paths blank)")
         if clip_model is None:
             raise ValueError("pass clip_model (a HipCLIPModel holding the teacher's CLIP towers); nothing is "
                              "downloaded by name here")
@@ -352,9 +349,14 @@ class PatchTextAggregation(nn.Module):
         self.patch_tokenizer = CLIPPatchTokenizer(clip_model, precision=tower_precision)
         self.cross_modal_attention = CrossModalAttention(embed_dim, num_heads)
         self.knn_cache = {}
-        self.use_knn_projection = False
+        # :78-96 — all three paths switch the KNN / projection tokenizer on; with any of them empty nothing below runs it
+        self.use_knn_projection = all([projection_model_path, faiss_index_path, embeddings_json_path])
         self.last_sentence_embedding = None
         self.advanced_tokenizer = None
+        if self.use_knn_projection:
+            from .knn_tokenizer import TokenizerWithKNN
+            self.advanced_tokenizer = TokenizerWithKNN(clip_model, projection_model_path, faiss_index_path,
+                                                       embeddings_json_path, similarity_threshold)
         self.full_resolution = False
 
     @property
@@ -369,6 +371,8 @@ class PatchTextAggregation(nn.Module):
         # a private tower copy is a plain attribute (it must stay out of state_dict()), so nn.Module would not move it
         if self._owns_clip:
             self._clip._apply(fn, *args, **kwargs)
+        if self.advanced_tokenizer is not None:         # a plain object as in the reference: its tensors follow the teacher
+            self.advanced_tokenizer.knn_tokenizer._apply(fn)
         return super()._apply(fn, *args, **kwargs)
 
     def shares_text_tower_with(self, student: HipCLIPModel) -> bool:
@@ -384,7 +388,8 @@ class PatchTextAggregation(nn.Module):
         return self._text_twin is student and self._text_twin_versions == self._text_versions(student)
 
     def load_caches(self, knn_cache_path=None):
-        """:104-124 — the KNN cache only feeds the (out-of-scope) KNN tokenizer; kept so callers do not break."""
+        """:104-124 — the md5-keyed cache spares the reference one FAISS call and one CLIP forward per crop; both are
+        batched here, so nothing is cached.  Kept so callers do not break."""
         self.knn_cache = {}
         return self
 
@@ -397,8 +402,11 @@ class PatchTextAggregation(nn.Module):
     # ---- tensor-in variant (synthetic configs, and the body of the path-based method)
     def compute_global_embedding_tensors(self, regions: torch.Tensor, input_ids: torch.Tensor,
                                          region_counts: Optional[torch.Tensor] = None,
-                                         max_tokens: Optional[int] = None) -> torch.Tensor:
+                                         max_tokens: Optional[int] = None,
+                                         region_positions: Optional[torch.Tensor] = None) -> torch.Tensor:
         """regions [B,R,3,S,S] in [0,1] (rows >= region_counts[b] ignored), input_ids [B,T] -> [B,E].
+        With the KNN / projection tokenizer on, every region embedding is replaced by `knn_or_projection`'s
+        (`region_positions` [B,R,4] = (x1/w, y1/h, x2/w, y2/h), None = zeros).
         Gradients flow only into cross_modal_attention (the towers run frozen, as in the reference:
         training/image_tokenizer.py:119, training/text_tokenizer.py:185)."""
         dev = self.device
@@ -420,6 +428,9 @@ class PatchTextAggregation(nn.Module):
                 with torch.cuda.stream(side), ops.workspace_lane(4):
                     sent, tokens, eos = self.text_tokenizer.token_level_ids(input_ids)
             emb = self.patch_tokenizer.encode_regions(regions.reshape(B * R, *regions.shape[2:])).view(B, R, -1)
+            if self.use_knn_projection and self.advanced_tokenizer is not None:
+                pos = None if region_positions is None else region_positions.to(dev).float().reshape(B * R, 4)
+                emb = self.advanced_tokenizer.knn_or_projection(emb.reshape(B * R, -1), pos)[0].view(B, R, -1)
             if region_counts is not None:
                 counts = region_counts.to(dev).to(torch.int32).contiguous()
                 rmax = max(int(region_counts.max()), 1)        # an image without boxes keeps ONE zero row (:489-491)
@@ -462,15 +473,20 @@ class PatchTextAggregation(nn.Module):
             boxes = weighted_boxes_batch
         else:
             boxes = [weighted_boxes_batch.get(p, []) for p in image_paths]
+        knn = self.use_knn_projection and self.advanced_tokenizer is not None
         images = None
-        if images_u8 is None:
+        if images_u8 is None or knn:
             images = []
             for path in image_paths:
                 try:
                     images.append(Image.open(path).convert("RGB"))
                 except Exception:
                     images.append(Image.new("RGB", (224, 224)))        # the reference's fallback (:302)
-        regions, counts = self.patch_tokenizer.crop_boxes_gpu(images, boxes, images_u8, dims)
+        positions = None
+        if knn:
+            regions, counts, positions = self._knn_query_crops(images, boxes)
+        else:
+            regions, counts = self.patch_tokenizer.crop_boxes_gpu(images, boxes, images_u8, dims)
         ids = self.text_tokenizer._ids(texts if isinstance(texts, torch.Tensor) else list(texts), keep_host=True)
         max_tokens = None
         if not ids.is_cuda:
@@ -480,4 +496,29 @@ class PatchTextAggregation(nn.Module):
             first_eos = (ids == eos_id).int().argmax(dim=1)
             max_tokens = max(int(first_eos.max()) - 1, 1)
             ids = ids.to(self.device)
-        return self.compute_global_embedding_tensors(regions, ids, counts, max_tokens)
+        return self.compute_global_embedding_tensors(regions, ids, counts, max_tokens, positions)
+
+    def _knn_query_crops(self, images, boxes_per_image):
+        """The KNN path's queries are the crops as the reference's `get_clip_embedding` sees them (training/
+        image_tokenizer.py:236-251): a PIL crop through the CLIP processor (bicubic shortest edge, centre crop, mean / std)
+        — not `patch_transform`.  Host work, stacked and uploaded once: (regions [B,Rmax,3,S,S], counts [B], positions
+        [B,Rmax,4] = (x1/w, y1/h, x2/w, y2/h), :315).  An image with a box without extent keeps no region, as in
+        crop_boxes_gpu."""
+        from .data import ClipImagePreprocess
+        s = self._clip.config.vision.image_size
+        pre = ClipImagePreprocess(size=s)
+        B = len(images)
+        if len(boxes_per_image) != B:
+            raise ValueError("one box list per image")
+        counts = [0 if any(x2 <= x1 or y2 <= y1 for (x1, y1, x2, y2), _c in bx) else len(bx) for bx in boxes_per_image]
+        rmax = max(max(counts), 1)
+        regions = torch.zeros((B, rmax, 3, s, s), dtype=torch.float32)
+        positions = torch.zeros((B, rmax, 4), dtype=torch.float32)
+        for b, (image, bx) in enumerate(zip(images, boxes_per_image)):
+            w, h = image.size
+            for r in range(counts[b]):
+                x1, y1, x2, y2 = bx[r][0]
+                regions[b, r] = pre.image(image.crop((x1, y1, x2, y2)))
+                positions[b, r] = torch.tensor([x1 / w, y1 / h, x2 / w, y2 / h], dtype=torch.float32)
+        dev = self.device
+        return regions.to(dev), torch.tensor(counts, dtype=torch.int32), positions.to(dev)

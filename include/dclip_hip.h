@@ -290,6 +290,37 @@ int dclip_rank_count(const float* queries, const float* candidates, const float*
                      int32_t* count, int Bq, int Bk, int P, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exact top-k inner-product search (what a flat inner-product index provides) and the two small kernels
+ * of the teacher's KNN region tokenizer (training/image_tokenizer.py:215-300).  The [Q, N] score matrix is never stored.
+ *   topk_ip: scores[i][j], indices[i][j] = the j-th best database row for query i under the TOTAL order (score
+ *            descending, index ascending): rows of equal score come lowest index first, and which of them make the list
+ *            is decided the same way.  The score is the fp32 inner product as the kernel evaluated it: one fmaf chain
+ *            over k = 0 .. P-1 in a fixed order (MFMA tiles, v_mfma_f32_32x32x2_f32), the same for every row whatever
+ *            the split, so the result does not depend on the number of splits (-0.0 counts as +0.0 and is returned as
+ *            +0.0).  A row QUALIFIES when its score is
+ *            greater than -inf: a NaN score (and a -inf one) is never selected.  When fewer than k rows qualify (N < k
+ *            included) the remaining slots hold (-inf, -1).  Every index written lies in [-1, N), whatever the inputs.
+ *            P % 4 == 0, 1 <= k <= 16, operands 16-byte aligned; `database` is addressed with size_t (N * P may pass 2^31).
+ *            Two launches, no atomics: "topk_ip" runs a grid of ceil(Q / 64) query blocks x `splits` database splits and
+ *            writes one sorted partial list per (split, query) into the workspace — every slot of it, every call;
+ *            "topk_ip.merge" merges them.  With tiles = ceil(N / 128) (a workgroup walks the database 128 rows at a time)
+ *              want   = min(ceil(1024 / ceil(Q / 64)), 64, tiles)      1024 = 4 workgroups on each of 256 CUs
+ *              splits = ceil(tiles / ceil(tiles / want))               contiguous, equal but for a shorter last one
+ *              workspace bytes = splits * Q * k * 8                    [splits][Q][k] 64-bit (score, index) keys; 8-byte aligned
+ *            a pure function of (Q, N, k); Q = 2048, N = 10^5 gives 32 x 32 workgroups, and N = 10^6 at k = 16 asks 16 MiB.
+ *   relu_f32:   x[i] = 0 where x[i] < 0, in place; NaN and -0.0 stay as they are.
+ *   knn_select: row i of out = database row idx[i] and source[i] = 0 when 0 <= idx[i] < N and sim[i] >= thresh (false
+ *            for a NaN similarity; the comparison is >= as at training/image_tokenizer.py:278); otherwise row i of
+ *            out = row i of fallback and source[i] = 1.  Decided on the device: no host synchronisation.
+ */
+size_t dclip_topk_ip_workspace(int Q, int N, int k);
+int dclip_topk_ip(const float* queries, const float* database, float* scores, int32_t* indices, int Q, int N, int P, int k,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int dclip_relu_f32(float* x, size_t n, void* stream);
+int dclip_knn_select(const float* sim, const int32_t* idx, const float* database, const float* fallback, float thresh,
+                     float* out, int32_t* source, int Q, int N, int P, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Region-crop front end: what training/image_tokenizer.py:100-110 does per box on the
  * host with PIL — `image.crop(box)` (zero padding outside the image), `Resize((S,S))` (Pillow's antialiased
  * two-pass BILINEAR in 8-bit fixed point) and `ToTensor()` (uint8/255, CHW, no mean/std) — for all boxes of a
