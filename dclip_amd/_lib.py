@@ -49,6 +49,11 @@ SIGNATURES = {
     "dclip_first_eos": (I, [P, P, I, I, L, P]),
     "dclip_gather_rows": (I, [P, P, P, I, I, I, P]),
     "dclip_scatter_rows": (I, [P, P, P, I, I, I, P]),
+    "dclip_pos_interp_fwd": (I, [P, P, I, I, I, I, P]),
+    "dclip_pos_interp_bwd": (I, [P, P, I, I, I, I, I, P]),
+    "dclip_im2col_rect": (I, [P, P, I, I, I, I, I, P]),
+    "dclip_im2col_rect_bf16": (I, [P, P, I, I, I, I, I, I, P]),
+    "dclip_im2col_rect_f16": (I, [P, P, I, I, I, I, I, I, P]),
     "dclip_normalize_rows_fwd": (I, [P, P, P, I, I, F, P]),
     "dclip_normalize_rows_bwd": (I, [P, P, P, P, I, I, F, I, P]),
     "dclip_contrastive_workspace": (Z, [I, I, I]),

@@ -166,40 +166,57 @@ class HipCLIPModel(nn.Module):
                                  tm.final_layer_norm.weight, tm.final_layer_norm.bias, self.text_projection.weight)
 
     # ------------------------------------------------------------------ reference call surface
-    def get_image_features(self, pixel_values: torch.Tensor = None, precision: str = "fp32", **kwargs) -> torch.Tensor:
+    def _vision_grid(self, pixel_values: torch.Tensor, interpolate_pos_encoding: bool):
+        """None for an image of the model's own size; with `interpolate_pos_encoding` the (gh, gw) patch grid of any other
+        H x W (hf CLIPVisionEmbeddings.forward: the size check applies only without the flag, and an image of the model's
+        size takes the plain table either way)."""
+        v = self.config.vision
+        Hh, Ww = pixel_values.shape[-2], pixel_values.shape[-1]
+        if Hh == v.image_size and Ww == v.image_size:
+            return None
+        if not interpolate_pos_encoding:
+            raise ValueError(f"Input image size ({Hh}*{Ww}) doesn't match "
+                             f"model ({v.image_size}*{v.image_size}).")          # hf:modeling_clip.py:204-207
+        if pixel_values.dim() != 4 or Hh < v.patch_size or Ww < v.patch_size:
+            raise ValueError(f"Input image size ({Hh}*{Ww}) is smaller than one patch ({v.patch_size}*{v.patch_size}).")
+        return (Hh // v.patch_size, Ww // v.patch_size)
+
+    def get_image_features(self, pixel_values: torch.Tensor = None, precision: str = "fp32",
+                           interpolate_pos_encoding: bool = False, **kwargs) -> torch.Tensor:
         """precision="bf16" (opt-in): GEMM inputs in bf16 on the bf16 MFMA path, everything else fp32 — frozen forward, or
         the bf16 training path when grad is enabled and a parameter is trainable.  precision="fp16" (opt-in, frozen use
         only): the same forward with fp16 GEMM inputs (3 more mantissa bits at the bf16 rate).  precision="fp16-mixed"
         (opt-in): the fp16 TRAINING path (Lightning's "16-mixed": fp16 GEMM inputs with IEEE rounding, fp32 master weights;
         the caller scales the loss, amp.DynamicLossScaler) when grad is enabled and a parameter is trainable, otherwise the
-        frozen "fp16" forward."""
+        frozen "fp16" forward.  interpolate_pos_encoding=True (as on HF's CLIPModel): any H x W of at least one patch a side;
+        the position table is resampled bicubically to the image's patch grid, rows and columns beyond the
+        last whole patch are ignored.  Without the flag nothing changes, the size check included."""
         if pixel_values is None:
             raise ValueError("You have to specify pixel_values")
         v = self.config.vision
-        if pixel_values.shape[-1] != v.image_size or pixel_values.shape[-2] != v.image_size:
-            raise ValueError(f"Input image size ({pixel_values.shape[-2]}*{pixel_values.shape[-1]}) doesn't match "
-                             f"model ({v.image_size}*{v.image_size}).")          # hf:modeling_clip.py:204-207
+        grid = self._vision_grid(pixel_values, interpolate_pos_encoding)
         p = self.vision_params()
         if precision == "bf16":
             if torch.is_grad_enabled() and any(t.requires_grad for t in p.tensors()):
                 # TRAINING in bf16 (configs c3 / c5): forward, dgrad and wgrad GEMMs on the bf16 MFMA kernels, fp32
                 # master weights and fp32 everything else (engine.vision_fwd_bf16_train)
                 return functional.VisionTowerBf16Fn.apply(pixel_values.float(), v, v.num_hidden_layers, self._bf16_cache(),
-                                                          torch.bfloat16, *p.tensors())
+                                                          torch.bfloat16, grid, *p.tensors())
             pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)
-            return engine.vision_fwd_bf16(pd, pixel_values.float().contiguous(), v, self._bf16_cache())
+            return engine.vision_fwd_bf16(pd, pixel_values.float().contiguous(), v, self._bf16_cache(), grid=grid)
         if precision in ("fp16", "fp16-mixed"):
             if torch.is_grad_enabled() and any(t.requires_grad for t in p.tensors()):
                 if precision == "fp16":
                     raise RuntimeError("precision='fp16' is a forward-only path for frozen towers: call it under torch.no_grad()"
                                        " (training: precision='fp16-mixed')")
                 return functional.VisionTowerBf16Fn.apply(pixel_values.float(), v, v.num_hidden_layers, self._f16_cache(),
-                                                          torch.float16, *p.tensors())
+                                                          torch.float16, grid, *p.tensors())
             pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)
-            return engine.vision_fwd_bf16(pd, pixel_values.float().contiguous(), v, self._f16_cache(), torch.float16)
+            return engine.vision_fwd_bf16(pd, pixel_values.float().contiguous(), v, self._f16_cache(), torch.float16,
+                                          grid=grid)
         if precision != "fp32":
             raise ValueError(f"precision {precision!r}")
-        return functional.VisionTowerFn.apply(pixel_values.float(), v, v.num_hidden_layers, *p.tensors())
+        return functional.VisionTowerFn.apply(pixel_values.float(), v, v.num_hidden_layers, grid, *p.tensors())
 
     def _bf16_cache(self) -> dict:
         """bf16 copies of the GEMM weights: persistent buffers, each refreshed in place when ITS parameter's version
@@ -282,16 +299,17 @@ class HipCLIPModel(nn.Module):
         return engine.TextParams.from_tensors([t.detach() for t in p.tensors()], len(p.layers))
 
     @torch.no_grad()
-    def hidden_states(self, pixel_values=None, input_ids=None) -> List[torch.Tensor]:
+    def hidden_states(self, pixel_values=None, input_ids=None, interpolate_pos_encoding: bool = False) -> List[torch.Tensor]:
         """Per-layer hidden states (parity tests): [embeddings-after-pre-LN, layer 1, ...] for vision,
-        [embeddings, layer 1, ...] (before final_layer_norm) for text."""
+        [embeddings, layer 1, ...] (before final_layer_norm) for text.  `interpolate_pos_encoding`: as in get_image_features."""
         out: List[torch.Tensor] = []
         if pixel_values is not None:
             v = self.config.vision
+            grid = self._vision_grid(pixel_values, interpolate_pos_encoding) if interpolate_pos_encoding else None
             p = engine.VisionParams.from_tensors([t.detach() for t in self.vision_params().tensors()],
                                                  v.num_hidden_layers)
-            engine.vision_fwd(p, pixel_values.float().contiguous(), v, False, out)
-            return [h.view(pixel_values.shape[0], v.seq_len, -1) for h in out]
+            engine.vision_fwd(p, pixel_values.float().contiguous(), v, False, out, grid=grid)
+            return [h.view(pixel_values.shape[0], -1, h.shape[-1]) for h in out]
         t = self.config.text
         engine.text_encoder_fwd(self.text_params_detached(), input_ids.long().contiguous(), t, False, out)
         return [h.view(input_ids.shape[0], input_ids.shape[1], -1) for h in out]

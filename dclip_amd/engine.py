@@ -197,14 +197,41 @@ class VisionParams:
         return out + list(self.TAIL)
 
 
-def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None):
-    """get_image_features: [B,3,H,W] -> [B,P]  (hf:modeling_clip.py:202-218, :641-651, :744-751)."""
+def _grid_seq(v, grid) -> int:
+    """Tokens per image: the configuration's, or 1 + gh*gw on another patch grid (hf interpolate_pos_encoding)."""
+    return v.seq_len if grid is None else 1 + grid[0] * grid[1]
+
+
+def _grid_front(p: VisionParams, pixel_values: torch.Tensor, v, grid):
+    """The position table resampled to a grid (gh, gw) other than the configuration's (one launch).  The pixels must make
+    exactly that grid."""
+    gh, gw = grid
+    if (pixel_values.shape[2] // v.patch_size, pixel_values.shape[3] // v.patch_size) != (gh, gw):
+        raise ValueError(f"pixel_values {tuple(pixel_values.shape)} do not make a {gh}x{gw} grid of {v.patch_size}-px patches")
+    return ops.pos_interp_fwd(p.pos, v.grid, gh, gw)
+
+
+def _grid_pos_grad(dpos_cols: torch.Tensor, p: VisionParams, v, grid, alloc, dev) -> torch.Tensor:
+    """The position table's gradient from the [S*D] column sum taken on another grid: the transpose of the resample,
+    written where `alloc` puts the parameter's gradient."""
+    g, D = v.grid, v.hidden_size
+    out = _galloc(alloc, "pos", (1 + g * g, D), dev)
+    return ops.pos_interp_bwd(dpos_cols.view(-1, D), g, grid[0], grid[1], out=out.view(1 + g * g, D))
+
+
+def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None, grid=None):
+    """get_image_features: [B,3,H,W] -> [B,P]  (hf:modeling_clip.py:202-218, :641-651, :744-751).  `grid` = (gh, gw): run on
+    that patch grid with the position table resampled to it (None: the configuration's image size, as ever)."""
     v = cfg
     B = pixel_values.shape[0]
-    S, D, H = v.seq_len, v.hidden_size, v.num_attention_heads
-    cols = ops.im2col(pixel_values, v.patch_size)
+    S, D, H = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads
+    if grid is None:
+        cols, pos = ops.im2col(pixel_values, v.patch_size), p.pos
+    else:
+        pos = _grid_front(p, pixel_values, v, grid)
+        cols = ops.im2col_rect(pixel_values, v.patch_size)
     patch = ops.gemm(cols, p.patch_w.view(D, -1), ops.LAYOUT_NT)
-    emb = ops.vision_assemble_fwd(patch, p.class_embedding, p.pos, B, S, D)
+    emb = ops.vision_assemble_fwd(patch, p.class_embedding, pos, B, S, D)
     del patch
     x, m0, r0 = ops.layernorm_fwd(emb, p.pre_w, p.pre_b, v.layer_norm_eps, save_stats=save)
     if hidden_out is not None:
@@ -224,7 +251,7 @@ def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hid
         cls_tok = ops.gather_rows(x, None, B, S, D)
     pooled, mp, rp = ops.layernorm_fwd(cls_tok, p.post_w, p.post_b, v.layer_norm_eps, save_stats=save)
     out = ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
-    saved = (cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled, prune) if save else None
+    saved = (cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled, prune, grid) if save else None
     return out, saved
 
 
@@ -234,9 +261,9 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
     data-parallel all-reduce of that group starts while the layers below are still being back-propagated.
     `alloc(name, shape)` may name the tensor a parameter gradient is to be written into (see _galloc)."""
     v = cfg
-    cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled, pruned = saved
+    cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled, pruned, grid = saved
     B = cls_tok.shape[0]
-    S, D, H = v.seq_len, v.hidden_size, v.num_attention_heads
+    S, D, H = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads
     names = p.names()
     needd = dict(zip(names, need))
     grads: Dict[str, Optional[torch.Tensor]] = {n: None for n in names}
@@ -273,9 +300,10 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
     if lowest < 0:
         demb = _ln_bwd(dx, emb, p.pre_w, m0, r0, None, bool(needd["pre_w"] or needd["pre_b"]), grads, "pre_w", "pre_b", alloc)
         if needd["pos"] or needd["class_embedding"]:
-            dpos = ops.colsum(demb.view(B, S * D), out=(_galloc(alloc, "pos", (S * D,), dev) if needd["pos"] else None))
+            dpos = ops.colsum(demb.view(B, S * D),
+                              out=(_galloc(alloc, "pos", (S * D,), dev) if needd["pos"] and grid is None else None))
             if needd["pos"]:
-                grads["pos"] = dpos.view(S, D)
+                grads["pos"] = dpos.view(S, D) if grid is None else _grid_pos_grad(dpos, p, v, grid, alloc, dev)
             if needd["class_embedding"]:
                 ce = _galloc(alloc, "class_embedding", (D,), dev)
                 ce.copy_(dpos[:D])
@@ -300,9 +328,9 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
 class _Ops16:
     """The forward kernels of one 16-bit type (ops.*_bf16 or ops.*_f16)."""
 
-    def __init__(self, dtype, gemm, layernorm, attention, attention_row, cast, im2col):
+    def __init__(self, dtype, gemm, layernorm, attention, attention_row, cast, im2col, im2col_rect):
         self.dtype, self._gemm, self.layernorm, self.attention = dtype, gemm, layernorm, attention
-        self.attention_row, self.cast, self.im2col = attention_row, cast, im2col
+        self.attention_row, self.cast, self.im2col, self.im2col_rect = attention_row, cast, im2col, im2col_rect
 
     def gemm(self, a, w, out16: bool = False, **kw):
         """y = epilogue(a w^T), a 16-bit result with `out16`."""
@@ -313,9 +341,9 @@ class _Ops16:
 
 _OPS16 = {
     torch.bfloat16: _Ops16(torch.bfloat16, ops.gemm_bf16, ops.layernorm_fwd_bf16, ops.attention_fwd_bf16,
-                           ops.attention_row_fwd_bf16, ops.cast_bf16, ops.im2col_bf16),
+                           ops.attention_row_fwd_bf16, ops.cast_bf16, ops.im2col_bf16, ops.im2col_rect_bf16),
     torch.float16: _Ops16(torch.float16, ops.gemm_f16, ops.layernorm_fwd_f16, ops.attention_fwd_f16,
-                          ops.attention_row_fwd_f16, ops.cast_f16, ops.im2col_f16),
+                          ops.attention_row_fwd_f16, ops.cast_f16, ops.im2col_f16, ops.im2col_rect_f16),
 }
 
 
@@ -348,17 +376,24 @@ def _layer_fwd_bf16(x, p: LayerParams, c: dict, pre: str, B: int, S: int, H: int
     return k.gemm(g, _w16(c, pre + "fc2", p.fc2_w, k.cast), bias=p.fc2_b, residual=x1)
 
 
-def vision_fwd_bf16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16) -> torch.Tensor:
+def vision_fwd_bf16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16,
+                    grid=None) -> torch.Tensor:
     """Frozen get_image_features with 16-bit GEMM inputs (`dtype` bf16 or fp16); `cache` keeps the converted weights
-    between calls (one cache per dtype)."""
+    between calls (one cache per dtype).  `grid`: as in vision_fwd."""
     v = cfg
     k = _OPS16[dtype]
     B = pixel_values.shape[0]
-    S, D, H = v.seq_len, v.hidden_size, v.num_attention_heads
-    cols = (k.im2col(pixel_values, v.patch_size) if v.patch_size % 4 == 0              # one pass: gather + round
-            else k.cast(ops.im2col(pixel_values, v.patch_size)))
+    S, D, H = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads
+    if grid is None:
+        pos = p.pos
+        cols = (k.im2col(pixel_values, v.patch_size) if v.patch_size % 4 == 0              # one pass: gather + round
+                else k.cast(ops.im2col(pixel_values, v.patch_size)))
+    else:
+        pos = _grid_front(p, pixel_values, v, grid)
+        cols = (k.im2col_rect(pixel_values, v.patch_size) if v.patch_size % 4 == 0
+                else k.cast(ops.im2col_rect(pixel_values, v.patch_size)))
     patch = k.gemm(cols, _w16(cache, "patch", p.patch_w, k.cast), k=v.patch_dim)
-    x, _, _ = ops.layernorm_fwd(ops.vision_assemble_fwd(patch, p.class_embedding, p.pos, B, S, D), p.pre_w, p.pre_b,
+    x, _, _ = ops.layernorm_fwd(ops.vision_assemble_fwd(patch, p.class_embedding, pos, B, S, D), p.pre_w, p.pre_b,
                                 v.layer_norm_eps, save_stats=False)
     for li, lp in enumerate(p.layers[:-1]):
         x = _layer_fwd_bf16(x, lp, cache, f"v{li}.", B, S, H, False, v.layer_norm_eps, dtype)
@@ -398,11 +433,11 @@ class _Train16:
     attention pair of DCLIP_BF16_ATTN_MFMA=0 (bf16 only: None for fp16, which always takes the MFMA pair)."""
 
     def __init__(self, dtype, gemm, cast, layernorm_stats, transpose, wgrad, wgrad_tokmajor, colsum, rowsum, attention_lse,
-                 attention_bwd, mt_weights, im2col, plan_tokmajor, io16_pair):
+                 attention_bwd, mt_weights, im2col, im2col_rect, plan_tokmajor, io16_pair):
         self.dtype, self._gemm, self.cast, self._layernorm_stats = dtype, gemm, cast, layernorm_stats
         self.transpose, self.wgrad, self.wgrad_tokmajor, self.colsum, self.rowsum = transpose, wgrad, wgrad_tokmajor, colsum, rowsum
         self.attention_lse, self.attention_bwd, self.mt_weights, self.im2col = attention_lse, attention_bwd, mt_weights, im2col
-        self.plan_tokmajor, self.io16_pair = plan_tokmajor, io16_pair
+        self.im2col_rect, self.plan_tokmajor, self.io16_pair = im2col_rect, plan_tokmajor, io16_pair
 
     def gemm(self, a, w, out16: bool = False, **kw):
         if self.dtype == torch.bfloat16:
@@ -419,11 +454,12 @@ _TRAIN16 = {
     torch.bfloat16: _Train16(torch.bfloat16, ops.gemm_bf16, ops.cast_bf16, ops.layernorm_fwd_bf16, ops.transpose_bf16,
                              ops.gemm_bf16_wgrad, ops.gemm_bf16_wgrad_tokmajor, ops.colsum_bf16, ops.rowsum_bf16,
                              ops.attention_fwd_bf16_lse, ops.attention_bwd_bf16, ops.mt_weights_bf16, ops.im2col_bf16,
-                             "dclip_gemm_bf16_wgrad_tokmajor_plan", (ops.attention_fwd_io16, ops.attention_bwd_io16)),
+                             ops.im2col_rect_bf16, "dclip_gemm_bf16_wgrad_tokmajor_plan",
+                             (ops.attention_fwd_io16, ops.attention_bwd_io16)),
     torch.float16: _Train16(torch.float16, ops.gemm_f16_train, ops.cast_f16_ieee, ops.layernorm_fwd_f16_stats, ops.transpose_f16,
                             ops.gemm_f16_wgrad, ops.gemm_f16_wgrad_tokmajor, ops.colsum_f16, ops.rowsum_f16,
                             ops.attention_fwd_f16_lse, ops.attention_bwd_f16, ops.mt_weights_f16, ops.im2col_f16,
-                            "dclip_gemm_f16_wgrad_tokmajor_plan", None),
+                            ops.im2col_rect_f16, "dclip_gemm_f16_wgrad_tokmajor_plan", None),
 }
 
 
@@ -732,20 +768,22 @@ def _patch_embed_bf16(v, rows: int, dtype=torch.bfloat16) -> bool:
     return hit
 
 
-def vision_fwd_bf16_train(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16):
+def vision_fwd_bf16_train(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16, grid=None):
     """get_image_features with gradients, 16-bit GEMM inputs (`dtype` bf16, or fp16 with IEEE rounding) in the patch
-    embedding and the encoder layers; `cache` holds the weight copies of that type."""
+    embedding and the encoder layers; `cache` holds the weight copies of that type.  `grid`: as in vision_fwd."""
     v = cfg
     k = _TRAIN16[dtype]
     B = pixel_values.shape[0]
-    S, D, H = v.seq_len, v.hidden_size, v.num_attention_heads
+    S, D, H = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads
+    pos = p.pos if grid is None else _grid_front(p, pixel_values, v, grid)
     if _patch_embed_bf16(v, B * (S - 1), dtype):
-        cols = k.im2col(pixel_values, v.patch_size)                           # one pass: gather + round; kept for the wgrad
+        # one pass: gather + round; kept for the wgrad
+        cols = (k.im2col if grid is None else k.im2col_rect)(pixel_values, v.patch_size)
         patch = k.gemm(cols, _w16(cache, "vpatch", p.patch_w, k.cast), k=v.patch_dim)
     else:
-        cols = ops.im2col(pixel_values, v.patch_size)
+        cols = (ops.im2col if grid is None else ops.im2col_rect)(pixel_values, v.patch_size)
         patch = ops.gemm(cols, p.patch_w.view(D, -1), ops.LAYOUT_NT)
-    emb = ops.vision_assemble_fwd(patch, p.class_embedding, p.pos, B, S, D)
+    emb = ops.vision_assemble_fwd(patch, p.class_embedding, pos, B, S, D)
     del patch
     x, m0, r0 = ops.layernorm_fwd(emb, p.pre_w, p.pre_b, v.layer_norm_eps, save_stats=True)
     refresh_train_weights(cache, p.layers, "v", dtype)   # W and W^T of all layers, one launch per optimizer step
@@ -756,7 +794,7 @@ def vision_fwd_bf16_train(p: VisionParams, pixel_values: torch.Tensor, cfg, cach
     cls_tok = ops.gather_rows(x, None, B, S, D)
     pooled, mp, rp = ops.layernorm_fwd(cls_tok, p.post_w, p.post_b, v.layer_norm_eps, save_stats=True)
     out = ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
-    return out, (cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled)
+    return out, (cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled, grid)
 
 
 def vision_bwd_bf16(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool], cache: dict, on_ready=None, alloc=None,
@@ -765,9 +803,9 @@ def vision_bwd_bf16(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List
     `alloc` naming the tensor each parameter gradient is written into)."""
     v = cfg
     k = _TRAIN16[dtype]
-    cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled = saved
+    cols, emb, m0, r0, saved_layers, cls_tok, mp, rp, pooled, grid = saved
     B = cls_tok.shape[0]
-    S, D, H = v.seq_len, v.hidden_size, v.num_attention_heads
+    S, D, H = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads
     names = p.names()
     needd = dict(zip(names, need))
     grads: Dict[str, Optional[torch.Tensor]] = {n: None for n in names}
@@ -808,9 +846,10 @@ def vision_bwd_bf16(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List
     if lowest < 0:
         demb = _ln_bwd(dx, emb, p.pre_w, m0, r0, None, bool(needd["pre_w"] or needd["pre_b"]), grads, "pre_w", "pre_b", alloc)
         if needd["pos"] or needd["class_embedding"]:
-            dpos = ops.colsum(demb.view(B, S * D), out=(_galloc(alloc, "pos", (S * D,), dev) if needd["pos"] else None))
+            dpos = ops.colsum(demb.view(B, S * D),
+                              out=(_galloc(alloc, "pos", (S * D,), dev) if needd["pos"] and grid is None else None))
             if needd["pos"]:
-                grads["pos"] = dpos.view(S, D)
+                grads["pos"] = dpos.view(S, D) if grid is None else _grid_pos_grad(dpos, p, v, grid, alloc, dev)
             if needd["class_embedding"]:
                 ce = _galloc(alloc, "class_embedding", (D,), dev)
                 ce.copy_(dpos[:D])

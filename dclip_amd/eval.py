@@ -73,19 +73,21 @@ def zero_shot_topk(image_features: torch.Tensor, class_text_features: torch.Tens
     return retrieve_topk(image_features, class_text_features, k)
 
 
-def encoders(model, precision: str = "fp32"):
+def encoders(model, precision: str = "fp32", interpolate_pos_encoding: bool = False):
     """(image encoder, text encoder) of a CLIPImageDistillation (forward(image=)/forward(text=)) or a HipCLIPModel.
     `precision` "bf16" / "fp16": the frozen 16-bit forward of the towers (HipCLIPModel.get_*_features; the student's
-    towers for a CLIPImageDistillation) — evaluation never needs gradients."""
-    if precision == "fp32":
+    towers for a CLIPImageDistillation) — evaluation never needs gradients.  `interpolate_pos_encoding`: the image encoder
+    takes images of any size (the towers' get_image_features with that flag)."""
+    if precision == "fp32" and not interpolate_pos_encoding:
         enc_i = (lambda x: model(image=x)) if hasattr(model, "student") else (lambda x: model.get_image_features(pixel_values=x))
         enc_t = (lambda x: model(text=x)) if hasattr(model, "student") else (lambda x: model.get_text_features(input_ids=x))
         return enc_i, enc_t
-    if precision not in ("bf16", "fp16"):
+    if precision not in ("fp32", "bf16", "fp16"):
         raise ValueError(f"precision {precision!r}")
     clip = model.student if hasattr(model, "student") else model
     dev = next(clip.parameters()).device
-    return (lambda x: clip.get_image_features(pixel_values=x.to(dev), precision=precision),
+    kw = {"interpolate_pos_encoding": True} if interpolate_pos_encoding else {}
+    return (lambda x: clip.get_image_features(pixel_values=x.to(dev), precision=precision, **kw),
             lambda x: clip.get_text_features(input_ids=x.to(dev), precision=precision))
 
 

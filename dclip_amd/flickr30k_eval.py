@@ -51,7 +51,10 @@ def _pixel_batch(arrs, device, size):
 @torch.no_grad()
 def evaluate_model(model_name: str, device, max_images: int = 1000, dataset_json: Optional[str] = None,
                    clip_model=None, clip_path: Optional[str] = None, checkpoint: Optional[str] = None,
-                   tokenizer: Optional[Callable] = None, batch_size: int = 64, precision: str = "fp32"):
+                   tokenizer: Optional[Callable] = None, batch_size: int = 64, precision: str = "fp32",
+                   image_size: Optional[int] = None):
+    """`image_size`: evaluate at N x N pixels instead of the model's size (the preprocessing resizes to N; when N differs from
+    the model's the position table is resampled, interpolate_pos_encoding)."""
     from PIL import Image
     from .CLIP_image_distillation import CLIPImageDistillation, _as_hip_model
     print(f"\n=== Evaluating {model_name} Model ===")
@@ -77,11 +80,13 @@ def evaluate_model(model_name: str, device, max_images: int = 1000, dataset_json
                                                            clip_preprocess=ClipImagePreprocess(size), strict=False).to(device)
     else:
         model = base
-    enc_i, enc_t = E.encoders(model, precision)     # precision: the frozen encoders' forward (fp32 / bf16 / fp16)
+    eval_size = int(image_size) if image_size else size
+    # precision: the frozen encoders' forward (fp32 / bf16 / fp16)
+    enc_i, enc_t = E.encoders(model, precision, interpolate_pos_encoding=eval_size != size)
     model.eval()
 
     print("Processing images...")
-    image_emb, image_ids, pre = [], [], ClipImagePreprocess(size)
+    image_emb, image_ids, pre = [], [], ClipImagePreprocess(eval_size)
     for i in range(0, len(dataset), batch_size):
         arrs, ids = [], []
         for item in dataset[i:i + batch_size]:
@@ -92,7 +97,7 @@ def evaluate_model(model_name: str, device, max_images: int = 1000, dataset_json
             except Exception as e:
                 print(f"Error loading image {item['image_path']}: {e}")
         if arrs:
-            image_emb.append(enc_i(_pixel_batch(arrs, device, size)).float())
+            image_emb.append(enc_i(_pixel_batch(arrs, device, eval_size)).float())
             image_ids.extend(ids)
     print("Processing captions...")
     caption_emb, caption_image_ids, caps, cap_ids = [], [], [], []
@@ -135,6 +140,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--clip_path", type=str, required=True, help="local directory with HF CLIP weights + tokenizer")
     parser.add_argument("--precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
                         help="arithmetic of the frozen encoders' forward (fp32: exact; bf16 / fp16: 16-bit GEMM inputs)")
+    parser.add_argument("--image_size", type=int, default=None,
+                        help="evaluate at N x N pixels (default: the model's size; another N resamples the position table)")
     return parser
 
 
@@ -145,10 +152,10 @@ def main(argv=None, **kw):
     res = {}
     if args.model in ("base", "both"):
         res["base"] = evaluate_model("base", device, args.max_images, args.dataset_json, clip_path=args.clip_path,
-                                     precision=args.precision, **kw)
+                                     precision=args.precision, image_size=args.image_size, **kw)
     if args.model in ("custom", "both"):
         res["custom"] = evaluate_model("custom", device, args.max_images, args.dataset_json, clip_path=args.clip_path,
-                                       checkpoint=args.checkpoint, precision=args.precision, **kw)
+                                       checkpoint=args.checkpoint, precision=args.precision, image_size=args.image_size, **kw)
     if len(res) == 2:
         b, c = res["base"], res["custom"]
         print("\n=== Model Comparison ===")

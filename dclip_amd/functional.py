@@ -38,10 +38,11 @@ def _c(t: torch.Tensor) -> torch.Tensor:
 
 class VisionTowerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pixel_values, cfg, n_layers, *params):
+    def forward(ctx, pixel_values, cfg, n_layers, grid, *params):
+        """`grid`: None, or the (gh, gw) patch grid of pixel_values when it is not the configuration's (engine.vision_fwd)."""
         p = engine.VisionParams.from_tensors([_c(t.detach()) for t in params], n_layers)
-        save = any(ctx.needs_input_grad[3:])
-        out, saved = engine.vision_fwd(p, _c(pixel_values.detach()), cfg, save)
+        save = any(ctx.needs_input_grad[4:])
+        out, saved = engine.vision_fwd(p, _c(pixel_values.detach()), cfg, save, grid=grid)
         ctx.p, ctx.saved, ctx.cfg = p, saved, cfg
         ctx.param_refs = params if save else None          # the nn.Parameters, for the data-parallel hook
         return out
@@ -63,11 +64,11 @@ class VisionTowerFn(torch.autograd.Function):
         if _GRAD_ALLOC is not None:
             galloc = _GRAD_ALLOC
             alloc = lambda name, shape: galloc(by_name[name], shape)      # noqa: E731
-        grads = engine.vision_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[3:]), on_ready, alloc)
+        grads = engine.vision_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[4:]), on_ready, alloc)
         ctx.saved = None
         if owned:           # handed to the data-parallel reducer: autograd neither accumulates nor clones them
             grads = [None if n in owned else g for n, g in zip(ctx.p.names(), grads)]
-        return (None, None, None, *grads)
+        return (None, None, None, None, *grads)
 
 
 class VisionTowerBf16Fn(torch.autograd.Function):
@@ -76,9 +77,9 @@ class VisionTowerBf16Fn(torch.autograd.Function):
     _f16_cache: rebuilt when a parameter version changes)."""
 
     @staticmethod
-    def forward(ctx, pixel_values, cfg, n_layers, cache, dtype, *params):
+    def forward(ctx, pixel_values, cfg, n_layers, cache, dtype, grid, *params):
         p = engine.VisionParams.from_tensors([_c(t.detach()) for t in params], n_layers)
-        out, saved = engine.vision_fwd_bf16_train(p, _c(pixel_values.detach()), cfg, cache, dtype)
+        out, saved = engine.vision_fwd_bf16_train(p, _c(pixel_values.detach()), cfg, cache, dtype, grid=grid)
         ctx.p, ctx.saved, ctx.cfg, ctx.cache, ctx.dtype = p, saved, cfg, cache, dtype
         ctx.param_refs = params
         return out
@@ -100,12 +101,12 @@ class VisionTowerBf16Fn(torch.autograd.Function):
         if _GRAD_ALLOC is not None:       # bf16 wgrads (split-K reduce), bias sums, LayerNorm dγ/dβ land in the bucket slices
             galloc = _GRAD_ALLOC
             alloc = lambda name, shape: galloc(by_name[name], shape)      # noqa: E731
-        grads = engine.vision_bwd_bf16(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[5:]), ctx.cache,
+        grads = engine.vision_bwd_bf16(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[6:]), ctx.cache,
                                        on_ready, alloc, ctx.dtype)
         ctx.saved = None
         if owned:
             grads = [None if n in owned else g for n, g in zip(ctx.p.names(), grads)]
-        return (None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, *grads)
 
 
 class TextTowerFn(torch.autograd.Function):

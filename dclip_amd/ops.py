@@ -337,6 +337,91 @@ def vision_assemble_bwd(dx, B: int, S: int, D: int) -> torch.Tensor:
     return dpatch
 
 
+def _interp_grids(what: str, g: int, gh: int, gw: int) -> None:
+    if min(g, gh, gw) < 1:
+        raise ValueError(f"{what}: grids must be at least 1x1, got g={g} -> {gh}x{gw}")
+
+
+def pos_interp_fwd(pos: torch.Tensor, g: int, gh: int, gw: int) -> torch.Tensor:
+    """Position table [1 + g*g, D] resampled to [1 + gh*gw, D]: row 0 copied, the g x g grid bicubic (A = -0.75,
+    align_corners=False, no antialiasing; weights from an fp64 evaluation)."""
+    lib = _lib.load()
+    _f32(pos, "position_embedding")
+    _interp_grids("pos_interp_fwd", g, gh, gw)
+    if pos.dim() != 2 or pos.shape[0] != 1 + g * g or pos.shape[1] % 4:
+        raise ValueError(f"pos_interp_fwd: expected [1 + {g}*{g}, D % 4 == 0], got {tuple(pos.shape)}")
+    out = torch.empty((1 + gh * gw, pos.shape[1]), dtype=torch.float32, device=pos.device)
+    _lib.check(lib.dclip_pos_interp_fwd(pos.data_ptr(), out.data_ptr(), g, gh, gw, pos.shape[1], _stream()), "pos_interp_fwd")
+    return out
+
+
+def pos_interp_bwd(dout: torch.Tensor, g: int, gh: int, gw: int, out: Optional[torch.Tensor] = None,
+                   accumulate: bool = False) -> torch.Tensor:
+    """The transpose of pos_interp_fwd: gradient [1 + gh*gw, D] -> [1 + g*g, D], written (or with `accumulate` added) into
+    `out` when given."""
+    lib = _lib.load()
+    _f32(dout, "dout")
+    _interp_grids("pos_interp_bwd", g, gh, gw)
+    if dout.dim() != 2 or dout.shape[0] != 1 + gh * gw or dout.shape[1] % 4:
+        raise ValueError(f"pos_interp_bwd: expected [1 + {gh}*{gw}, D % 4 == 0], got {tuple(dout.shape)}")
+    D = dout.shape[1]
+    if out is None:
+        if accumulate:
+            raise ValueError("pos_interp_bwd: accumulate needs `out`")
+        out = torch.empty((1 + g * g, D), dtype=torch.float32, device=dout.device)
+    else:
+        _f32(out, "out")
+        if out.numel() != (1 + g * g) * D or out.device != dout.device:
+            raise ValueError(f"pos_interp_bwd: out must hold [1 + {g}*{g}, {D}] on {dout.device}, got {tuple(out.shape)}")
+    _lib.check(lib.dclip_pos_interp_bwd(dout.data_ptr(), out.data_ptr(), g, gh, gw, D, int(bool(accumulate)), _stream()),
+               "pos_interp_bwd")
+    return out
+
+
+def _rect_grid(what: str, pixels: torch.Tensor, patch: int):
+    _f32(pixels, "pixel_values")
+    if pixels.dim() != 4:
+        raise ValueError(f"{what}: expected pixel_values [B, C, H, W], got {tuple(pixels.shape)}")
+    Hh, Ww = pixels.shape[2:]
+    if patch < 1 or Hh < patch or Ww < patch or pixels.shape[0] < 1 or pixels.shape[1] < 1:
+        raise ValueError(f"{what}: image {Hh}x{Ww} has a side shorter than one patch ({patch})")
+    return Hh // patch, Ww // patch
+
+
+def im2col_rect(pixels: torch.Tensor, patch: int) -> torch.Tensor:
+    """im2col on a gh x gw grid (gh = H // patch, gw = W // patch; trailing rows and columns are not read)."""
+    lib = _lib.load()
+    gh, gw = _rect_grid("im2col_rect", pixels, patch)
+    B, Cc, Hh, Ww = pixels.shape
+    cols = torch.empty((B * gh * gw, Cc * patch * patch), dtype=torch.float32, device=pixels.device)
+    _lib.check(lib.dclip_im2col_rect(pixels.data_ptr(), cols.data_ptr(), B, Cc, Hh, Ww, patch, _stream()), "im2col_rect")
+    return cols
+
+
+def _im2col_rect16(entry: str, dtype, pixels: torch.Tensor, patch: int) -> torch.Tensor:
+    lib = _lib.load()
+    gh, gw = _rect_grid(entry, pixels, patch)
+    if patch % 4:
+        raise ValueError(f"{entry}: patch {patch} must be a multiple of 4")
+    B, Cc, Hh, Ww = pixels.shape
+    kdim = Cc * patch * patch
+    ld = (kdim + 7) // 8 * 8
+    alloc = torch.zeros if ld != kdim else torch.empty
+    cols = alloc((B * gh * gw, ld), dtype=dtype, device=pixels.device)
+    _lib.check(getattr(lib, "dclip_" + entry)(pixels.data_ptr(), cols.data_ptr(), B, Cc, Hh, Ww, patch, ld, _stream()), entry)
+    return cols
+
+
+def im2col_rect_bf16(pixels: torch.Tensor, patch: int) -> torch.Tensor:
+    """im2col_rect with a bf16 result (rows padded to a multiple of 8 columns, zero filled); patch % 4 == 0."""
+    return _im2col_rect16("im2col_rect_bf16", torch.bfloat16, pixels, patch)
+
+
+def im2col_rect_f16(pixels: torch.Tensor, patch: int) -> torch.Tensor:
+    """im2col_rect with an fp16 result (rows padded to a multiple of 8 columns, zero filled); patch % 4 == 0."""
+    return _im2col_rect16("im2col_rect_f16", torch.float16, pixels, patch)
+
+
 def _ids(ids: torch.Tensor) -> torch.Tensor:
     if not (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.dim() == 2):
         raise ValueError("input_ids: expected a contiguous int64 CUDA tensor [B, T]")

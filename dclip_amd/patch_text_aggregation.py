@@ -306,16 +306,39 @@ class CLIPPatchTokenizer:
         """[N,3,S,S] in [0,1] -> [N,E] (one batched frozen forward)."""
         return self.clip_model.get_image_features(pixel_values=regions.to(self.device).float(), precision=self.precision)
 
+    @staticmethod
+    def full_resolution_transform(pil_patch) -> torch.Tensor:
+        """ToTensor() alone (training/image_tokenizer.py:34): HWC uint8 -> CHW float in [0,1], no resize, no mean/std."""
+        import numpy as np
+        arr = np.asarray(pil_patch.convert("RGB"), dtype=np.float32) / 255.0
+        return torch.from_numpy(arr).permute(2, 0, 1).contiguous()
+
     @torch.no_grad()
     def encode_weighted_bounding_boxes(self, image, weighted_boxes, full_resolution=False):
-        """:86-124 — list of (clip_embedding, confidence)."""
-        if full_resolution:
-            raise NotImplementedError("full_resolution crops are rejected by CLIP without interpolate_pos_encoding "
-                                      "(hf:modeling_clip.py:204-207); the reference never enables it (SURVEY §5)")
+        """:86-124 — list of (clip_embedding, confidence).  `full_resolution`: every crop is encoded at its own size (ToTensor()
+        only), the position table resampled to its patch grid (get_image_features(interpolate_pos_encoding=True)); crops of one
+        (h, w) share a forward.  A crop with a side shorter than one patch raises ValueError, as HF's convolution would."""
         if not weighted_boxes:
             return []
-        crops = torch.stack([self.patch_transform(image.crop(box)) for box, _ in weighted_boxes])
-        embs = self.encode_regions(crops)
+        if not full_resolution:
+            crops = torch.stack([self.patch_transform(image.crop(box)) for box, _ in weighted_boxes])
+            embs = self.encode_regions(crops)
+            return [(e, conf) for e, (_, conf) in zip(embs, weighted_boxes)]
+        patch = self.clip_model.config.vision.patch_size
+        groups = {}
+        for i, (box, _) in enumerate(weighted_boxes):
+            w, h = image.crop(box).size if box[2] > box[0] and box[3] > box[1] else (0, 0)
+            if min(h, w) < patch:
+                raise ValueError(f"full_resolution: the crop of box {tuple(box)} is {h}*{w}, smaller than one patch "
+                                 f"({patch}*{patch})")
+            groups.setdefault((h, w), []).append(i)
+        embs = [None] * len(weighted_boxes)
+        for idx in groups.values():
+            crops = torch.stack([self.full_resolution_transform(image.crop(weighted_boxes[i][0])) for i in idx])
+            out = self.clip_model.get_image_features(pixel_values=crops.to(self.device), precision=self.precision,
+                                                     interpolate_pos_encoding=True)
+            for j, i in enumerate(idx):
+                embs[i] = out[j]
         return [(e, conf) for e, (_, conf) in zip(embs, weighted_boxes)]
 
 
@@ -474,6 +497,11 @@ class PatchTextAggregation(nn.Module):
         else:
             boxes = [weighted_boxes_batch.get(p, []) for p in image_paths]
         knn = self.use_knn_projection and self.advanced_tokenizer is not None
+        if self.full_resolution:
+            if knn:
+                raise NotImplementedError("full_resolution with the KNN / projection tokenizer: its queries are crops at the "
+                                          "model's size (training/image_tokenizer.py:236-251)")
+            return self._global_embedding_full_resolution(image_paths, texts, boxes, images_u8, dims)
         images = None
         if images_u8 is None or knn:
             images = []
@@ -497,6 +525,41 @@ class PatchTextAggregation(nn.Module):
             max_tokens = max(int(first_eos.max()) - 1, 1)
             ids = ids.to(self.device)
         return self.compute_global_embedding_tensors(regions, ids, counts, max_tokens, positions)
+
+    def _global_embedding_full_resolution(self, image_paths, texts, boxes, images_u8=None, dims=None):
+        """`self.full_resolution` (training/CLIP_image_distillation.py:723-729): every box is encoded at its own size, image by
+        image (CLIPPatchTokenizer.encode_weighted_bounding_boxes).  An image with a crop smaller than one patch (ValueError)
+        keeps the single zero patch row; the reference does that for ANY exception inside that call
+        (training/patch_text_aggregation.py:479-491), here every other error is raised."""
+        from PIL import Image
+        dev = self.device
+        images = []
+        for b, path in enumerate(image_paths):
+            if images_u8 is not None:
+                h, w = (int(x) for x in dims[b].tolist())
+                images.append(Image.fromarray(images_u8[b, :h, :w].cpu().numpy()))
+                continue
+            try:
+                images.append(Image.open(path).convert("RGB"))
+            except Exception:
+                images.append(Image.new("RGB", (224, 224)))        # the reference's fallback (:302)
+        per_image = []
+        for image, bx in zip(images, boxes):
+            try:
+                per_image.append([e for e, _ in self.patch_tokenizer.encode_weighted_bounding_boxes(image, bx, True)])
+            except ValueError:             # a crop smaller than one patch; kernel and runtime errors are not swallowed
+                per_image.append([])
+        rmax = max(max(len(e) for e in per_image), 1)
+        emb = torch.zeros((len(images), rmax, self.embed_dim), dtype=torch.float32, device=dev)
+        for b, es in enumerate(per_image):
+            if es:
+                emb[b, :len(es)] = torch.stack(es)
+        ids = self.text_tokenizer._ids(texts if isinstance(texts, torch.Tensor) else list(texts))
+        with torch.no_grad():
+            sent, tokens, eos = self.text_tokenizer.token_level_ids(ids)
+            self.last_sentence_embedding = sent
+            text = ops.pack_tokens(tokens.contiguous(), sent, eos, max(int(eos.max()) - 1, 1))
+        return self.global_embedding_from_tokens(text, emb)
 
     def _knn_query_crops(self, images, boxes_per_image):
         """The KNN path's queries are the crops as the reference's `get_clip_embedding` sees them (training/

@@ -92,7 +92,8 @@ def make_prompts(classnames: Sequence[str], dataset_name: Optional[str] = None) 
 def evaluate_zero_shot(model_name: str, model, processor: Callable, dataloader, classnames: Sequence[str],
                        dataset_name: Optional[str] = None, precision: str = "fp32"):
     """Evaluate a single model for zero-shot classification (reference signature; see the module docstring).
-    `precision`: the frozen towers' forward ("fp32" default, "bf16" or "fp16": HipCLIPModel.get_*_features)."""
+    `precision`: the frozen towers' forward ("fp32" default, "bf16" or "fp16": HipCLIPModel.get_*_features).  Images of
+    another size than the model's (--image_size) are encoded with interpolate_pos_encoding."""
     print(f"\nEvaluating {model_name}" + (f" on {dataset_name}" if dataset_name else "") + "...")
     clip = model if model_name == "base" or not hasattr(model, "student") else model.student
     dev = next(clip.parameters()).device
@@ -102,9 +103,11 @@ def evaluate_zero_shot(model_name: str, model, processor: Callable, dataloader, 
     mean = torch.tensor(E.CLIP_MEAN, device=dev).view(1, 3, 1, 1)
     std = torch.tensor(E.CLIP_STD, device=dev).view(1, 3, 1, 1)
     correct_top1 = correct_top5 = total = 0
+    native = clip.config.vision.image_size
     for images, labels in dataloader:
         images = (images.to(dev).float() - mean) / std
-        ranks = E.zero_shot_ranks(clip.get_image_features(pixel_values=images, precision=precision), text_features, labels)
+        kw = {} if tuple(images.shape[-2:]) == (native, native) else {"interpolate_pos_encoding": True}
+        ranks = E.zero_shot_ranks(clip.get_image_features(pixel_values=images, precision=precision, **kw), text_features, labels)
         correct_top1 += int((ranks == 0).sum())
         correct_top5 += int((ranks < 5).sum())
         total += len(labels)
@@ -126,6 +129,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--results", default=None, help="results text file (default <dataset>_zero_shot_results.txt)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "fp16"],
                     help="arithmetic of the frozen encoders' forward (fp32: exact; bf16 / fp16: 16-bit GEMM inputs)")
+    ap.add_argument("--image_size", type=int, default=None,
+                    help="evaluate at N x N pixels (default: the model's size; another N resamples the position table)")
     return ap
 
 
@@ -140,7 +145,7 @@ def main(argv=None, clip_model=None, processor=None):
         clip_model = CLIPModel.from_pretrained(args.clip_path, local_files_only=True).to(device).eval()
         processor = CLIPProcessor.from_pretrained(args.clip_path, local_files_only=True)
     base = _as_hip_model(clip_model).to(device)
-    ds = ImageFolderDataset(args.data_root, base.config.vision.image_size, args.max_images or None)
+    ds = ImageFolderDataset(args.data_root, args.image_size or base.config.vision.image_size, args.max_images or None)
     if args.classnames:
         with open(args.classnames, "r") as f:
             classnames = [line.strip() for line in f.readlines()]

@@ -200,6 +200,30 @@ int dclip_gather_rows(const float* x, const int32_t* idx, float* out, int B, int
 int dclip_scatter_rows(const float* dout, const int32_t* idx, float* dx, int B, int S, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The vision tower at another input size (hf CLIPVisionEmbeddings.interpolate_pos_encoding).
+ * pos_interp_fwd: out[0] = pos[0] (the class position); out[1 + oy*gw + ox] = the bicubic resample of the g x g grid of
+ *   D-vectors pos[1..] at output cell (oy, ox) of a gh x gw grid, as torch.nn.functional.interpolate(mode="bicubic",
+ *   align_corners=False) DEFINES it: per axis, source coordinate x = (o + 0.5) g / g_out - 0.5, f = floor(x), t = x - f, four
+ *   taps f-1 .. f+2 each clamped to [0, g-1] (taps clamped onto one cell are each added), cubic-convolution weights with
+ *   A = -0.75, no antialiasing.  x, t and the weights are evaluated in double from the integers and each weight is rounded
+ *   to fp32 once (the contract is the fp64 definition, not torch's fp32 coordinate arithmetic); the 16 terms
+ *   (wy[a] wx[b]) pos[iy(a), ix(b)] are added in one fmaf chain, a outer, b inner: a pure function of the inputs.
+ *   (gh, gw) == (g, g) returns the table (the weights are exactly 0, 1, 0, 0).
+ * pos_interp_bwd: the exact transpose, dpos[1 + sy*g + sx] = sum over destination rows in ascending order of the same
+ *   fp32 weights times dout; dpos[0] = dout[0]; `accumulate` adds into dpos.  Gather form, no atomics: run-to-run identical.
+ *   Both: D % 4 == 0, 1 <= g <= 32768, gh, gw >= 1 with gh*gw < 2^30 (row indices are formed in int), 16-byte aligned
+ *   pointers; pos / dpos are [1 + g*g][D], out / dout [1 + gh*gw][D].
+ * im2col_rect{,_bf16,_f16}: dclip_im2col{,_bf16,_f16} on a gh x gw grid, gh = Himg / patch and gw = Wimg / patch by floor
+ *   (both >= 1); image rows >= gh*patch and columns >= gw*patch are never read, as a stride-`patch` convolution ignores
+ *   them.  dclip_last_launch: the entry's name + ".vec" (patch % 4 == 0, Wimg % 4 == 0, 16-byte pointers) or ".scalar".
+ *   The 16-bit forms keep patch % 4 == 0 and the ldc / alignment rules of dclip_im2col_bf16. */
+int dclip_pos_interp_fwd(const float* pos, float* out, int g, int gh, int gw, int D, void* stream);
+int dclip_pos_interp_bwd(const float* dout, float* dpos, int g, int gh, int gw, int D, int accumulate, void* stream);
+int dclip_im2col_rect(const float* pixels, float* cols, int B, int C, int Himg, int Wimg, int patch, void* stream);
+int dclip_im2col_rect_bf16(const float* pixels, void* cols, int B, int C, int Himg, int Wimg, int patch, int ldc, void* stream);
+int dclip_im2col_rect_f16(const float* pixels, void* cols, int B, int C, int Himg, int Wimg, int patch, int ldc, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Losses.
  * normalize_rows: xhat = x / max(||x||, eps), inv[b] = 1/max(||x||,eps)   (F.normalize,
  *   training/CLIP_image_distillation.py:545-546,:569-570; eps = 1e-12).
