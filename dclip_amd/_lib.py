@@ -117,6 +117,10 @@ SIGNATURES = {
     "dclip_im2col_f16": (I, [P, P, I, I, I, I, I, I, P]),
     "dclip_attention_fwd_f16": (I, [P, P, I, I, I, I, P]),
     "dclip_attention_row_fwd_f16": (I, [P, P, P, I, I, I, P]),
+    "dclip_split_f32_f16x3": (I, [P, P, I, I, I, I, F, I, P]),
+    "dclip_layernorm_fwd_f16x3": (I, [P, P, P, P, I, I, F, F, P]),
+    "dclip_gemm_f16_scaled": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, F, P]),
+    "dclip_gemm_f16_scaled_split": (I, [P, P, P, P, I, I, I, I, I, I, I, F, F, P]),
     "dclip_gemm_f16_ex": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "dclip_gemm_f16_wgrad_tokmajor_plan": (I, [I, I, I]),
     "dclip_gemm_f16_wgrad_tokmajor": (I, [P, P, P, I, I, I, I, I, I, I, P, Z, P]),

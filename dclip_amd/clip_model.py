@@ -235,6 +235,15 @@ class HipCLIPModel(nn.Module):
             object.__setattr__(self, "_f16_w", c)
         return c
 
+    def _split16_cache(self) -> dict:
+        """Split-fp16 copies [hi|hi|lo] of the frozen text tower's GEMM weights and the activation scales that go with them
+        (engine.text_fwd_frozen_split16): built at the first frozen fp32 text forward, refreshed when a weight changes."""
+        c = getattr(self, "_split16_w", None)
+        if c is None:
+            c = {}
+            object.__setattr__(self, "_split16_w", c)
+        return c
+
     def invalidate_bf16_of_trainable(self) -> int:
         """Mark the bf16 (and fp16) copies of every TRAINABLE parameter stale (frozen towers keep theirs).  graph.GraphedStep calls
         this between its eager warm-up and the capture: the weight casts / transposes are then part of the captured step
@@ -276,7 +285,7 @@ class HipCLIPModel(nn.Module):
                                                self._f16_cache(), torch.float16)
         if precision != "fp32":
             raise ValueError(f"precision {precision!r}")
-        return functional.TextTowerFn.apply(input_ids.long(), t, t.num_hidden_layers, *p.tensors())
+        return functional.TextTowerFn.apply(input_ids.long(), t, t.num_hidden_layers, self._split16_cache(), *p.tensors())
 
     @torch.no_grad()
     def text_token_level(self, input_ids: torch.Tensor, precision: str = "fp32"):

@@ -41,7 +41,29 @@ struct GemmBf16Params {
   unsigned short* aux;   // bf16 [M][ldc]: GELU writes the pre-activation there, DGELU reads it (training path)
   int k_per_split;       // split-K (gridDim.y > 1): multiple of 64; 0 = whole K
   float* slab;           // split-K partials [split][M][N] fp32 (raw accumulators), or nullptr
+  float alpha = 1.f;     // multiplies the accumulator before bias / GELU / residual (dclip_gemm_f16_scaled; 1 elsewhere)
+  float out_scale = 0.f; // != 0 (dclip_gemm_f16_scaled_split): C is fp16 [M][ldc >= 3N], the [hi|lo|hi] split of out_scale * result
 };
+
+// Split-output store (split16.hip has the stand-alone kernel): v = the final fp32 results of 4 consecutive columns, c = their
+// place in the first third of the row; hi = fp16(v s), lo = fp16(v s - hi), written as [hi | lo | hi], N columns apart.  v is
+// pinned in registers first: it is the value the fp32 epilogue would have stored, rounded to fp32 BEFORE the conversion.
+__device__ __forceinline__ void store_split4(unsigned short* c, int N, f32x4 v, float s) {
+  u16x4 hi, lo;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float x = v[e];
+    asm volatile("" : "+v"(x));
+    x *= s;
+    const _Float16 h = (_Float16)x;
+    const _Float16 l = (_Float16)(x - (float)h);
+    hi[e] = __builtin_bit_cast(unsigned short, h);
+    lo[e] = __builtin_bit_cast(unsigned short, l);
+  }
+  *reinterpret_cast<u16x4*>(c) = hi;
+  *reinterpret_cast<u16x4*>(c + N) = lo;
+  *reinterpret_cast<u16x4*>(c + 2 * N) = hi;
+}
 
 // 4 consecutive 16-bit values at p (8-byte aligned) -> 4 floats
 template <class T>
@@ -245,6 +267,7 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
       *reinterpret_cast<f32x4*>(p.slab + ((size_t)blockIdx.y * p.M + row) * p.N + col) = v;
       continue;
     }
+    v = v * p.alpha;
     if (p.epilogue & DCLIP_EPI_BIAS) v += *reinterpret_cast<const f32x4*>(p.bias + col);
     const size_t off = (size_t)row * p.ldc + col;
     if (p.epilogue & DCLIP_EPI_GELU) {
@@ -263,7 +286,9 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
       for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(h[e]);
     }
     if (p.epilogue & DCLIP_EPI_RESIDUAL) v += *reinterpret_cast<const f32x4*>(p.residual + off);
-    if (p.out_bf16) {
+    if (p.out_scale != 0.f) {
+      store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, p.out_scale);
+    } else if (p.out_bf16) {
       u16x4 o = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
       *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned short*>(p.C) + off) = o;
     } else {
@@ -427,7 +452,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
       const int lr = id / (BN / 4), lc = (id % (BN / 4)) * 4;
       const int row = m0 + hm * PROWS + lr, col = n0 + lc;
       if (row >= p.M || col >= p.N) continue;
-      f32x4 v = *reinterpret_cast<const f32x4*>(ct + lr * BN + lc);
+      f32x4 v = *reinterpret_cast<const f32x4*>(ct + lr * BN + lc) * p.alpha;
       if (p.epilogue & DCLIP_EPI_BIAS) v += *reinterpret_cast<const f32x4*>(p.bias + col);
       const size_t off = (size_t)row * p.ldc + col;
       if (p.epilogue & DCLIP_EPI_GELU) {
@@ -446,7 +471,9 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
         for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(h[e]);
       }
       if (p.epilogue & DCLIP_EPI_RESIDUAL) v += *reinterpret_cast<const f32x4*>(p.residual + off);
-      if (p.out_bf16) {
+      if (p.out_scale != 0.f) {
+        store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, p.out_scale);
+      } else if (p.out_bf16) {
         u16x4 o = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
         *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned short*>(p.C) + off) = o;
       } else {
@@ -516,7 +543,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const int row = rbase + 8 * q;
-      f32x4 v = *reinterpret_cast<const f32x4*>(ct + (lr0 + 8 * q) * BN + (((tid & 63) ^ ((lr0 + 8 * q) & 7)) << 2)) + bias4;
+      f32x4 v = *reinterpret_cast<const f32x4*>(ct + (lr0 + 8 * q) * BN + (((tid & 63) ^ ((lr0 + 8 * q) & 7)) << 2)) * p.alpha + bias4;
       const size_t off = (size_t)row * p.ldc + col;
       const bool ok = row < p.M && colok;
       if (KIND == 1) {
@@ -535,6 +562,10 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
       }
       if (KIND == 3) v += side[q];
       if (!ok) continue;
+      if ((KIND == 0 || KIND == 1) && !OUT16 && p.out_scale != 0.f) {
+        store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, p.out_scale);
+        continue;
+      }
       if (OUT16) {
         u16x4 o = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
         *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned short*>(p.C) + off) = o;
@@ -579,7 +610,7 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        f32x4 v = acc[i][j] + bias4[j];
+        f32x4 v = acc[i][j] * p.alpha + bias4[j];
         if (GELU && !SAVE) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
@@ -879,6 +910,8 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
     ps.C = p.slab + (size_t)blockIdx.y * p.M * p.N;
     ps.ldc = p.N;
     ps.epilogue = 0;
+    ps.alpha = 1.f;
+    ps.out_scale = 0.f;
     pp_epilogue<T, 0, false>(ps, acc, ct, m0, n0, tid, wr, wc, quad, l15);
     return;
   }
@@ -1024,7 +1057,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_ppp_kernel(GemmBf16Params p) {
           for (int ii = 0; ii < 4; ++ii)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              f32x4 v = acc[4 * (q & 1) + ii][j] + bias4[j];
+              f32x4 v = acc[4 * (q & 1) + ii][j] * p.alpha + bias4[j];
               if (kind == 1 && !save) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
@@ -1075,7 +1108,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_ppp_kernel(GemmBf16Params p) {
           for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              const f32x4 v = acc[2 * (q & 3) + ii][j] + bias4[j];
+              const f32x4 v = acc[2 * (q & 3) + ii][j] * p.alpha + bias4[j];
               *reinterpret_cast<f32x4*>(w32 + (16 * ii + l15) * BN + (((16 * wc + 4 * j + quad) ^ (l15 & 7)) << 2)) = v;
             }
         }
@@ -1378,7 +1411,7 @@ bool pp16() { return kTrain16<T> || pingpong_enabled(); }
 // an instance per type, and the DCLIP_BF16_* switches select among them for fp16 exactly as for bf16.
 template <class T>
 int gemm16(const char* name, const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux, int M,
-           int N, int K, int lda, int ldw, int ldc, int epilogue, int out_bf16, void* stream) {
+           int N, int K, int lda, int ldw, int ldc, int epilogue, int out_bf16, void* stream, float alpha = 1.f, float out_scale = 0.f) {
   DCLIP_REQUIRE(A && W && C, "%s: null operand", name);
   DCLIP_REQUIRE(M > 0 && N > 0 && K > 0, "%s: bad shape M=%d N=%d K=%d", name, M, N, K);
   DCLIP_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "%s: lda/ldw must be multiples of 8 and >= K", name);
@@ -1386,6 +1419,8 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
   DCLIP_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 == 0, "%s: operands must be 16-byte aligned", name);
   DCLIP_REQUIRE(!(epilogue & ~(DCLIP_EPI_BIAS | DCLIP_EPI_GELU | DCLIP_EPI_DGELU | DCLIP_EPI_RESIDUAL)),
                 "%s: unsupported epilogue bits", name);
+  DCLIP_REQUIRE(out_scale == 0.f || (!out_bf16 && !aux && !(epilogue & (DCLIP_EPI_RESIDUAL | DCLIP_EPI_DGELU)) && (long)ldc >= 3L * N),
+                "%s: a split output takes BIAS | GELU only and ldc >= 3 N", name);
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (aux && !(epilogue & DCLIP_EPI_GELU)), "%s: DGELU needs aux (and no GELU)", name);
   DCLIP_REQUIRE(!aux || (uintptr_t)aux % 8 == 0, "%s: aux must be 8-byte aligned", name);
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_BIAS) || bias, "%s: BIAS without bias", name);
@@ -1398,7 +1433,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
   const int big_min = getenv("DCLIP_BF16_BIG_MIN") ? atoi(getenv("DCLIP_BF16_BIG_MIN")) : 128;   // tuning aid (read per call)
   if (K % BKH == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= big_min) {
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
-                      (unsigned short*)aux, 0, nullptr};
+                      (unsigned short*)aux, 0, nullptr, alpha, out_scale};
     // persistent form when a CU gets several tiles (the towers' M = 100k shapes: 14 per CU): the epilogue of one tile
     // overlaps the K loop of the next.  DGELU (an extra side operand in the epilogue) stays on the one-tile kernel, and so does
     // GELU with an fp32 C: the persistent kernel's fp32 store path applies bias and residual only (it returned the
@@ -1406,6 +1441,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
     const int persist_min = getenv("DCLIP_BF16_PERSIST_MIN") ? atoi(getenv("DCLIP_BF16_PERSIST_MIN")) : 512;
     const bool gelu_f32 = (epilogue & DCLIP_EPI_GELU) && !out_bf16;
     const bool persist = !kTrain16<T> && pingpong_enabled() && persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && !gelu_f32 &&
+                         out_scale == 0.f &&
                          ldc % 8 == 0 && N % 8 == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min;
     const char* variant = ".pp";
     if constexpr (kTrain16<T>) {
@@ -1431,7 +1467,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
     const bool mid_dma = getenv("DCLIP_BF16_MID_DMA") && atoi(getenv("DCLIP_BF16_MID_DMA")) != 0;
     if (mid_dma && K % BKH == 0 && (long)cdiv(M, 128) * cdiv(N, 128) >= 256) {
       GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
-                        (unsigned short*)aux, 0, nullptr};
+                        (unsigned short*)aux, 0, nullptr, alpha, out_scale};
       launch_dma<T, 128, 128, 2, 2>(pb, st);
       DCLIP_CHECK_LAUNCH_V(name, ".dma128");
       return DCLIP_OK;
@@ -1440,7 +1476,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
   const bool small = (long)cdiv(M, 128) * cdiv(N, 128) < 256;  // fewer tiles than CUs: use the finer tile
   const int bm = small ? 64 : 128, bn = bm;
   GemmBf16Params p{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16,
-                   cdiv(M, bm), cdiv(N, bn), (unsigned short*)aux, 0, nullptr};
+                   cdiv(M, bm), cdiv(N, bn), (unsigned short*)aux, 0, nullptr, alpha, out_scale};
   const size_t lds = (size_t)2 * (bm + bn) * BKH * 2;
   if (small) hipLaunchKernelGGL((gemm_bf16_kernel<T, 64, 64>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
   else hipLaunchKernelGGL((gemm_bf16_kernel<T, 128, 128>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
@@ -1460,6 +1496,29 @@ DCLIP_API int dclip_gemm_f16(const void* A, const void* W, void* C, const float*
                              int lda, int ldw, int ldc, int epilogue, int out_f16, void* stream) {
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU), "gemm_f16: DGELU is a training epilogue (bf16 only)");
   return gemm16<F16T>("gemm_f16", A, W, C, bias, residual, nullptr, M, N, K, lda, ldw, ldc, epilogue, out_f16, stream);
+}
+
+// dclip_gemm_f16 with `alpha`: C = epilogue(alpha * (A W^T)) — the accumulator is scaled BEFORE bias, GELU and residual.  The
+// split-fp16 text tower (split16.hip) feeds operands scaled by powers of two and undoes both scales here;
+// alpha = 1 gives dclip_gemm_f16's output bit for bit.
+DCLIP_API int dclip_gemm_f16_scaled(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N,
+                                    int K, int lda, int ldw, int ldc, int epilogue, int out_f16, float alpha, void* stream) {
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU), "gemm_f16_scaled: DGELU is a training epilogue");
+  DCLIP_REQUIRE(alpha == alpha && alpha - alpha == 0.f, "gemm_f16_scaled: alpha must be finite");
+  return gemm16<F16T>("gemm_f16_scaled", A, W, C, bias, residual, nullptr, M, N, K, lda, ldw, ldc, epilogue, out_f16, stream, alpha);
+}
+
+// dclip_gemm_f16_scaled whose result leaves as the operand of the NEXT split GEMM: C is fp16 [M][ldc >= 3 N], the [hi|lo|hi]
+// split (split16.hip) of out_scale * epilogue(alpha * (A W^T)), epilogue BIAS | GELU — fc1 + quick-GELU of the split-fp16 text
+// tower without the fp32 round trip through memory.  Bit-equal to dclip_split_f32_f16x3 of dclip_gemm_f16_scaled's fp32 output.
+DCLIP_API int dclip_gemm_f16_scaled_split(const void* A, const void* W, void* C, const float* bias, int M, int N, int K, int lda,
+                                          int ldw, int ldc, int epilogue, float alpha, float out_scale, void* stream) {
+  DCLIP_REQUIRE(alpha == alpha && alpha - alpha == 0.f, "gemm_f16_scaled_split: alpha must be finite");
+  DCLIP_REQUIRE(out_scale > 0.f && out_scale - out_scale == 0.f && (__builtin_bit_cast(unsigned int, out_scale) & 0x007fffffu) == 0,
+                "gemm_f16_scaled_split: out_scale must be a power of two");
+  DCLIP_REQUIRE(ldc % 8 == 0, "gemm_f16_scaled_split: ldc must be a multiple of 8");
+  return gemm16<F16T>("gemm_f16_scaled_split", A, W, C, bias, nullptr, nullptr, M, N, K, lda, ldw, ldc, epilogue, 0, stream, alpha,
+                      out_scale);
 }
 
 // fp16 TRAINING path: dclip_gemm_bf16_ex's arguments, epilogues and limits with fp16 A / W / aux / 16-bit C, IEEE rounding

@@ -942,6 +942,171 @@ def text_fwd_frozen(p: TextParams, input_ids: torch.Tensor, cfg):
     return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
 
 
+# --------------------------------------------------------------------------------------------- frozen fp32 text tower, split fp16
+# The frozen fp32 text tower's full-size GEMMs on the fp16 MFMAs with fp32-grade error.  An fp32 value is
+# hi + lo with hi = fp16(v), lo = fp16(v - hi) (22 mantissa bits); fp16 products are exact in the fp32 accumulator, so
+# A W^T = A_hi W_hi^T + A_lo W_hi^T + A_hi W_lo^T up to the dropped lo.lo term — ONE fp16 GEMM along K' = 3K on
+# [A_hi | A_lo | A_hi] and [W_hi | W_hi | W_lo].  Operands are scaled by powers of two (exact) so that they sit high in fp16's
+# range and cannot overflow: weights by 2^f with max|W| 2^f in [2^13, 2^14), activations by 2^e with bound 2^e <= 2^14, where
+# `bound` is a worst case derived from the frozen WEIGHTS alone (never from data: no host sync, no data-dependent branch in
+# the step); the GEMM's alpha = 2^-(e+f) undoes both before bias / GELU / residual.  Residual stream, attention, softmax,
+# LayerNorm statistics, bias and GELU are the fp32 kernels of the plain path.
+
+_SPLIT16 = os.environ.get("DCLIP_TEXT_SPLIT16", "1") != "0"     # read once at import: no getenv on the launch path
+# fc1's quick-GELU output leaves its GEMM already split (dclip_gemm_f16_scaled_split) instead of as fp32 followed by the
+# stand-alone split pass; 0 = the two-launch form (bit-identical results; kept for the A/B of DESIGN.md §9c)
+_SPLIT16_FC1_EPI = os.environ.get("DCLIP_TEXT_SPLIT16_FC1_EPI", "1") != "0"
+_SPLIT16_TOP = 14                                               # operands are kept within 2^14 (fp16 overflows at 2^16)
+_SPLIT16_EMIN, _SPLIT16_EMAX = -14, 24
+_SPLIT16_LOGGED: set = set()
+
+
+def text_split16_enabled() -> bool:
+    return _SPLIT16
+
+
+def _split16_log_once(msg: str) -> None:
+    if msg not in _SPLIT16_LOGGED:
+        _SPLIT16_LOGGED.add(msg)
+        import logging
+        logging.getLogger("dclip_amd").warning(msg)
+
+
+def split16_weight_exp(max_abs: float) -> int:
+    """f with max|W| 2^f in [2^13, 2^14) (0 for an all-zero weight)."""
+    import math
+    if max_abs == 0.0:
+        return 0
+    return _SPLIT16_TOP - math.frexp(max_abs)[1]             # max_abs = m 2^x, m in [0.5, 1)
+
+
+def split16_act_exp(bound: float) -> Optional[int]:
+    """The largest e <= 24 with bound 2^e <= 2^14; None when no e >= -14 satisfies it or the bound is not finite (guard)."""
+    import math
+    if not math.isfinite(bound) or bound < 0.0:
+        return None
+    if bound == 0.0:
+        return _SPLIT16_EMAX
+    m, x = math.frexp(bound)                                  # bound <= 2^x, = 2^(x-1) when m == 0.5
+    e = _SPLIT16_TOP - (x - 1 if m == 0.5 else x)
+    if e < _SPLIT16_EMIN:
+        return None
+    return min(e, _SPLIT16_EMAX)
+
+
+def split16_layer_bounds(st: Dict[str, float], D: int) -> Dict[str, float]:
+    """Worst-case magnitudes of the three split activations of a layer from its weight statistics `st`:
+       LayerNorm output   max|gamma| sqrt(D) + max|beta|            (|x - mu| rstd <= sqrt(D) for every row)
+       attention context  bound_ln1 max_n ||W_v[n,:]||_1 + max|b_v|  (a convex combination of V rows)
+       GELU output        bound_ln2 max_n ||W_fc1[n,:]||_1 + max|b_fc1|   (|quick_gelu(v)| <= |v|)"""
+    import math
+    ln1 = st["ln1_w"] * math.sqrt(D) + st["ln1_b"]
+    ln2 = st["ln2_w"] * math.sqrt(D) + st["ln2_b"]
+    return {"ln1": ln1, "ctx": ln1 * st["v_l1"] + st["v_b"], "ln2": ln2, "g": ln2 * st["fc1_l1"] + st["fc1_b"]}
+
+
+_SPLIT16_STATS = ("ln1_w", "ln1_b", "v_l1", "v_b", "ln2_w", "ln2_b", "fc1_l1", "fc1_b", "qkv", "out", "fc1", "fc2")
+_SPLIT16_WATCHED = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w")
+
+
+def _split16_stamp(layers: List[LayerParams]) -> tuple:
+    return tuple((t._version, t.data_ptr()) for lp in layers for t in (getattr(lp, f) for f in _SPLIT16_WATCHED))
+
+
+def _split16_plan(p: TextParams, cache: dict):
+    """Per weight version: the [hi|hi|lo] fp16 copies of W 2^f and the power-of-two activation scales of every layer, or
+    None when the guard sends the tower to the plain fp32 path.  ONE device -> host read of the weight statistics, at
+    cache-build time (warm-up, before any graph capture); the copies are refreshed in place when a weight changes."""
+    stamp = _split16_stamp(p.layers)
+    plan = cache.get("__split16__")
+    if plan is not None and plan["stamp"] == stamp:
+        return plan["layers"]
+    if torch.cuda.is_current_stream_capturing():
+        _split16_log_once("split-fp16 text tower: weights changed while a graph is being captured; this capture takes the "
+                          "plain fp32 path (run one eager step first)")
+        return None
+    if plan is not None:
+        # frozen weights do not move: a rebuild after the first costs a host read, and one on every call (a parameter that is
+        # written each step, or a non-contiguous one whose contiguous copy has a new address each call) would do so every step
+        _split16_log_once("split-fp16 text tower: a weight's version or storage changed; the split copies and scales are rebuilt "
+                          "(one device-to-host read).  If a weight changes every step, set DCLIP_TEXT_SPLIT16=0")
+    D = p.layers[0].ln1_w.shape[0]
+    rows = []
+    for lp in p.layers:
+        wv, bv = lp.qkv_w[2 * D:], lp.qkv_b[2 * D:]
+        rows.append(torch.stack([lp.ln1_w.abs().max(), lp.ln1_b.abs().max(), wv.abs().sum(1).max(), bv.abs().max(),
+                                 lp.ln2_w.abs().max(), lp.ln2_b.abs().max(), lp.fc1_w.abs().sum(1).max(), lp.fc1_b.abs().max(),
+                                 lp.qkv_w.abs().max(), lp.out_w.abs().max(), lp.fc1_w.abs().max(), lp.fc2_w.abs().max()]))
+    stats = torch.stack(rows).double().cpu().tolist()
+    import math
+    layers = []
+    old = plan["layers"] if plan is not None and plan["layers"] is not None else None
+    for li, (lp, row) in enumerate(zip(p.layers, stats)):
+        st = dict(zip(_SPLIT16_STATS, row))
+        if not all(math.isfinite(v) for v in row):
+            layers = None
+            _split16_log_once(f"split-fp16 text tower: non-finite weight in layer {li}; taking the plain fp32 path")
+            break
+        exps = {k: split16_act_exp(b) for k, b in split16_layer_bounds(st, D).items()}
+        if any(e is None for e in exps.values()):
+            layers = None
+            _split16_log_once(f"split-fp16 text tower: an activation bound of layer {li} does not fit fp16 at any scale >= 2^-14; "
+                              "taking the plain fp32 path")
+            break
+        ent = {"e": exps, "f": {}, "w": {}}
+        for short, field in _TRAIN_WEIGHTS:
+            w = getattr(lp, field)
+            f = split16_weight_exp(st[short])
+            prev = old[li]["w"][short] if old is not None and li < len(old) and tuple(old[li]["w"][short].shape) == (w.shape[0], 3 * w.shape[1]) else None
+            ent["f"][short] = f
+            ent["w"][short] = ops.split_f16x3(w.detach().contiguous(), 2.0 ** f, 1, out=prev)
+        layers.append(ent)
+    cache["__split16__"] = {"stamp": stamp, "layers": layers}
+    return layers
+
+
+def _split16_gemm(a3, ent, short: str, akey: str, **kw):
+    """epilogue(A W^T) from the split operands; alpha undoes the operand scales."""
+    return ops.gemm_f16(a3, ent["w"][short], alpha=2.0 ** -(ent["e"][akey] + ent["f"][short]), **kw)
+
+
+def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict):
+    """text_fwd_frozen with every full-size GEMM evaluated on split-fp16 operands (see above); the last layer's EOS-row
+    GEMMs (M = B), the final LayerNorm and the projection stay on ops.gemm.  `cache`: the split weights and scales, kept
+    between calls.  Falls back to text_fwd_frozen when the switch is off or the guard trips."""
+    t = cfg
+    D = t.hidden_size
+    plan = _split16_plan(p, cache) if _SPLIT16 and len(p.layers) > 0 and D % 8 == 0 and t.intermediate_size % 8 == 0 else None
+    if plan is None:
+        return text_fwd_frozen(p, input_ids, cfg)
+    B, T = input_ids.shape
+    H, eps = t.num_attention_heads, t.layer_norm_eps
+    eos = ops.first_eos(input_ids, t.eos_token_id)
+    x = ops.text_embed_fwd(input_ids, p.tok, p.pos)
+    for lp, ent in zip(p.layers[:-1], plan[:-1]):
+        e = ent["e"]
+        ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** e["ln1"])
+        qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
+        attn, _ = ops.attention_fwd(qkv, B, T, H, True)
+        x1 = _split16_gemm(ops.split_f16x3(attn, 2.0 ** e["ctx"]), ent, "out", "ctx", bias=lp.out_b, residual=x)
+        ln2 = ops.layernorm_fwd_f16x3(x1, lp.ln2_w, lp.ln2_b, eps, 2.0 ** e["ln2"])
+        if _SPLIT16_FC1_EPI:
+            g3 = _split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True, split_out_scale=2.0 ** e["g"])
+        else:
+            g3 = ops.split_f16x3(_split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True), 2.0 ** e["g"])
+        x = _split16_gemm(g3, ent, "fc2", "g", bias=lp.fc2_b, residual=x1)
+    lp, ent = p.layers[-1], plan[-1]
+    ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"])
+    qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
+    attn = ops.attention_row_fwd(qkv, eos, B, T, H)
+    x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows(x, eos, B, T, D))
+    ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
+    g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
+    rows = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
+    pooled, _, _ = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=False)
+    return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+
+
 def text_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None):
     """get_text_features: ids [B,T] -> [B,P]  (hf:modeling_clip.py:541-586, :705-713).  LayerNorm is row-wise, so
     the first-EOS rows are gathered BEFORE final_layer_norm: only B rows are normalised and projected."""

@@ -111,11 +111,15 @@ class VisionTowerBf16Fn(torch.autograd.Function):
 
 class TextTowerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, input_ids, cfg, n_layers, *params):
+    def forward(ctx, input_ids, cfg, n_layers, split16_cache, *params):
+        """`split16_cache`: the model's cache of split-fp16 weights (HipCLIPModel._split16_cache) — the frozen forward takes
+        the split-fp16 path with it (engine.text_fwd_frozen_split16, DCLIP_TEXT_SPLIT16); None: the plain fp32 path."""
         p = engine.TextParams.from_tensors([_c(t.detach()) for t in params], n_layers)
-        save = any(ctx.needs_input_grad[3:])
+        save = any(ctx.needs_input_grad[4:])
         if not save and len(p.layers) > 0:
             ctx.saved = None
+            if split16_cache is not None and engine.text_split16_enabled():
+                return engine.text_fwd_frozen_split16(p, _c(input_ids), cfg, split16_cache)
             return engine.text_fwd_frozen(p, _c(input_ids), cfg)
         out, saved = engine.text_fwd(p, _c(input_ids), cfg, save)
         ctx.p, ctx.saved, ctx.cfg = p, saved, cfg
@@ -125,9 +129,9 @@ class TextTowerFn(torch.autograd.Function):
     def backward(ctx, d_out):
         if ctx.saved is None:
             raise RuntimeError("TextTowerFn.backward called twice, or forward ran without grad")
-        grads = engine.text_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[3:]))
+        grads = engine.text_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[4:]))
         ctx.saved = None
-        return (None, None, None, *grads)
+        return (None, None, None, None, *grads)
 
 
 class CosineDistillationLossFn(torch.autograd.Function):

@@ -1083,8 +1083,11 @@ def attention_row_fwd_f16(qkv: torch.Tensor, rows: Optional[torch.Tensor], B: in
 
 def gemm_f16(a: torch.Tensor, w: torch.Tensor, *, n: Optional[int] = None, k: Optional[int] = None,
              bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, gelu: bool = False,
-             out_f16: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = epilogue(a @ w^T): a [M, lda>=K] and w [N, ldw>=K] fp16 (K-major), fp32 accumulation; y fp32 or fp16."""
+             out_f16: bool = False, out: Optional[torch.Tensor] = None, alpha: Optional[float] = None,
+             split_out_scale: Optional[float] = None) -> torch.Tensor:
+    """y = epilogue(a @ w^T): a [M, lda>=K] and w [N, ldw>=K] fp16 (K-major), fp32 accumulation; y fp32 or fp16.  `alpha`
+    (dclip_gemm_f16_scaled): the accumulator is multiplied by it before bias, GELU and residual.  `split_out_scale`
+    (dclip_gemm_f16_scaled_split; bias / gelu only): y is fp16 [M, 3N], the [hi|lo|hi] split of split_out_scale * result."""
     lib = _lib.load()
     _f16(a, "a"), _f16(w, "w")
     M, lda = a.shape
@@ -1103,14 +1106,60 @@ def gemm_f16(a: torch.Tensor, w: torch.Tensor, *, n: Optional[int] = None, k: Op
         epi |= EPI_RESIDUAL
         if tuple(_f32(residual, "residual").shape) != (M, N):
             raise ValueError("gemm_f16: residual shape")
+    if split_out_scale is not None:
+        if residual is not None or out_f16 or out is not None:
+            raise ValueError("gemm_f16: a split output takes bias / gelu only")
+        y3 = torch.empty((M, 3 * N), dtype=torch.float16, device=a.device)
+        _lib.check(lib.dclip_gemm_f16_scaled_split(a.data_ptr(), w.data_ptr(), y3.data_ptr(), _ptr(bias), M, N, K, lda, ldw, 3 * N,
+                                                   epi, 1.0 if alpha is None else float(alpha), float(split_out_scale), _stream()),
+                   "gemm_f16_scaled_split")
+        return y3
     odt = torch.float16 if out_f16 else torch.float32
     if out is None:
         out = torch.empty((M, N), dtype=odt, device=a.device)
     elif tuple(out.shape) != (M, N) or out.dtype != odt or not out.is_contiguous():
         raise ValueError("gemm_f16: out shape / dtype")
+    if alpha is not None:
+        _lib.check(lib.dclip_gemm_f16_scaled(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual), M, N, K, lda,
+                                             ldw, N, epi, int(out_f16), float(alpha), _stream()), "gemm_f16_scaled")
+        return out
     _lib.check(lib.dclip_gemm_f16(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual), M, N, K, lda, ldw, N,
                                   epi, int(out_f16), _stream()), "gemm_f16")
     return out
+
+
+# ------------------------------------------------------------------------------------------- split-fp16 (frozen fp32 text tower)
+# fp32 x = hi + lo in two fp16 pieces (include/dclip_hip.h, "Split-fp16"; DESIGN.md §9c): the operands of gemm_f16(alpha=...).
+
+def split_f16x3(x: torch.Tensor, scale: float = 1.0, order: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[rows, cols] fp32 -> fp16 [rows, 3 cols] of x * scale (a power of two): order 0 [hi|lo|hi] (activations), 1 [hi|hi|lo]
+    (weights); cols % 8 == 0.  `out`: refresh an existing split in place."""
+    lib = _lib.load()
+    _f32(x, "x")
+    if x.dim() != 2:
+        raise ValueError("split_f16x3: x must be 2-D")
+    rows, cols = x.shape
+    if out is not None:
+        if tuple(_f16(out, "out").shape) != (rows, 3 * cols):
+            raise ValueError(f"split_f16x3: out shape {tuple(out.shape)} != {(rows, 3 * cols)}")
+        y = out
+    else:
+        y = torch.empty((rows, 3 * cols), dtype=torch.float16, device=x.device)
+    _lib.check(lib.dclip_split_f32_f16x3(x.data_ptr(), y.data_ptr(), rows, cols, cols, 3 * cols, float(scale), int(order),
+                                         _stream()), "split_f32_f16x3")
+    return y
+
+
+def layernorm_fwd_f16x3(x, gamma, beta, eps: float, scale: float = 1.0) -> torch.Tensor:
+    """nn.LayerNorm (fp32 statistics and arithmetic) written as the [hi|lo|hi] split of scale * LN(x): [rows, 3 D] fp16."""
+    lib = _lib.load()
+    _f32(x, "x"), _f32(gamma, "gamma"), _f32(beta, "beta")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    y = torch.empty((rows, 3 * D), dtype=torch.float16, device=x.device)
+    _lib.check(lib.dclip_layernorm_fwd_f16x3(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), rows, D, float(eps),
+                                             float(scale), _stream()), "layernorm_fwd_f16x3")
+    return y
 
 
 # ------------------------------------------------------------------------------------------- fp16 training path

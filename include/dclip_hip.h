@@ -506,6 +506,27 @@ int dclip_attention_fwd_f16(const void* qkv, void* out, int B, int S, int H, int
 int dclip_attention_row_fwd_f16(const void* qkv, const int32_t* rows, void* out, int B, int S, int H, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Split-fp16 evaluation of fp32 GEMMs for the FROZEN fp32 text tower (DCLIP_TEXT_SPLIT16): an fp32 value is
+ * written as hi + lo, hi = fp16(v), lo = fp16(v - hi) (22 mantissa bits, IEEE round-to-nearest-even, NO saturation), and
+ * A W^T is the one fp16 GEMM [A_hi | A_lo | A_hi] [W_hi | W_hi | W_lo]^T along K' = 3K with fp32 accumulation.
+ *   split_f32_f16x3      fp32 [rows][cols] (ldx) -> fp16 [rows][3 cols] (ldy >= 3 cols, a multiple of 8; columns past 3 cols
+ *                        are not written) of v = x * scale; order 0 = [hi|lo|hi] (activations), 1 = [hi|hi|lo] (weights).
+ *                        cols % 8 == 0, 16-byte aligned operands, `scale` a power of two (the caller keeps |v| <= 2^14).
+ *   layernorm_fwd_f16x3  dclip_layernorm_fwd's arithmetic with y [rows][3 D] fp16 = the order-0 split of scale * LN(x); the
+ *                        fp32 result is not stored.  Bit-equal to split_f32_f16x3 of dclip_layernorm_fwd's output.
+ *   gemm_f16_scaled      dclip_gemm_f16 with `alpha`: the accumulator is multiplied by alpha BEFORE bias, GELU and residual
+ *                        (alpha = 1 / (scale_A scale_W) undoes the operand scales); alpha = 1 is dclip_gemm_f16 bit for bit.
+ *   gemm_f16_scaled_split  gemm_f16_scaled (epilogue BIAS | GELU) with C fp16 [M][ldc >= 3 N, a multiple of 8] = the order-0
+ *                        split of out_scale * result (a power of two): bit-equal to split_f32_f16x3 of the fp32 output. */
+int dclip_split_f32_f16x3(const float* x, void* y, int rows, int cols, int ldx, int ldy, float scale, int order, void* stream);
+int dclip_layernorm_fwd_f16x3(const float* x, const float* gamma, const float* beta, void* y, int rows, int D, float eps,
+                              float scale, void* stream);
+int dclip_gemm_f16_scaled(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
+                          int lda, int ldw, int ldc, int epilogue, int out_f16, float alpha, void* stream);
+int dclip_gemm_f16_scaled_split(const void* A, const void* W, void* C, const float* bias, int M, int N, int K, int lda, int ldw,
+                                int ldc, int epilogue, float alpha, float out_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * fp16 TRAINING path (opt-in student_precision="fp16" / get_image_features(precision="fp16-mixed")): fp16
  * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
  * a finite value beyond +-65504 becomes +-inf (it does NOT saturate as the frozen fp16 entries do), NaN stays NaN, so the
