@@ -115,6 +115,7 @@ class CLIPImageDistillation(LightningLikeModule):
             object.__setattr__(snapshot, "_bf16_w", None)
             object.__setattr__(snapshot, "_f16_w", None)
             object.__setattr__(snapshot, "_split16_w", None)
+            object.__setattr__(snapshot, "_vsplit16_w", None)
             for p in snapshot.parameters():
                 p.requires_grad = False
             teacher = PatchTextAggregation(embed_dim=E, num_heads=max(1, E // 64), clip_model=snapshot,

@@ -121,6 +121,16 @@ SIGNATURES = {
     "dclip_layernorm_fwd_f16x3": (I, [P, P, P, P, I, I, F, F, P]),
     "dclip_gemm_f16_scaled": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, F, P]),
     "dclip_gemm_f16_scaled_split": (I, [P, P, P, P, I, I, I, I, I, I, I, F, F, P]),
+    "dclip_split_f32_f16x3_dev": (I, [P, P, I, I, I, I, P, I, P]),
+    "dclip_layernorm_fwd_f16x3_dev": (I, [P, P, P, P, P, P, P, I, I, F, P, P]),
+    "dclip_gemm_f16_scaled_dev": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P, P]),
+    "dclip_gemm_f16_scaled_split_dev": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P]),
+    "dclip_split16_record_bytes": (I, []),
+    "dclip_split16_plan_floats": (I, []),
+    "dclip_split16_tile_rows": (I, []),
+    "dclip_split16_stats": (I, [P, I, I, P, P]),
+    "dclip_split16_plan": (I, [P, P, I, I, P]),
+    "dclip_split16_weights": (I, [P, I, I, P, P]),
     "dclip_gemm_f16_ex": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "dclip_gemm_f16_wgrad_tokmajor_plan": (I, [I, I, I]),
     "dclip_gemm_f16_wgrad_tokmajor": (I, [P, P, P, I, I, I, I, I, I, I, P, Z, P]),

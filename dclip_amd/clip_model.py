@@ -216,7 +216,11 @@ class HipCLIPModel(nn.Module):
                                           grid=grid)
         if precision != "fp32":
             raise ValueError(f"precision {precision!r}")
-        return functional.VisionTowerFn.apply(pixel_values.float(), v, v.num_hidden_layers, grid, *p.tensors())
+        # the split-fp16 forward (engine.vision_fwd, DCLIP_VISION_SPLIT16) is the TRAINING forward only: a no-grad call
+        # (evaluation, a teacher beside the student on another stream) never touches the split copies
+        train = torch.is_grad_enabled() and any(t.requires_grad for t in p.tensors())
+        return functional.VisionTowerFn.apply(pixel_values.float(), v, v.num_hidden_layers, grid,
+                                              self._vsplit16_cache() if train else None, *p.tensors())
 
     def _bf16_cache(self) -> dict:
         """bf16 copies of the GEMM weights: persistent buffers, each refreshed in place when ITS parameter's version
@@ -242,6 +246,16 @@ class HipCLIPModel(nn.Module):
         if c is None:
             c = {}
             object.__setattr__(self, "_split16_w", c)
+        return c
+
+    def _vsplit16_cache(self) -> dict:
+        """The vision tower's device-side split-fp16 plan (engine._vision_split16_plan): record table, plan record and the
+        [hi|hi|lo] weight copies, built at the first gradient-enabled fp32 image forward and refreshed on the device whenever
+        a weight has changed.  Per model, so a teacher snapshot never shares the student's copies."""
+        c = getattr(self, "_vsplit16_w", None)
+        if c is None:
+            c = {}
+            object.__setattr__(self, "_vsplit16_w", c)
         return c
 
     def invalidate_bf16_of_trainable(self) -> int:

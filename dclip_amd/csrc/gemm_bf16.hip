@@ -43,7 +43,15 @@ struct GemmBf16Params {
   float* slab;           // split-K partials [split][M][N] fp32 (raw accumulators), or nullptr
   float alpha = 1.f;     // multiplies the accumulator before bias / GELU / residual (dclip_gemm_f16_scaled; 1 elsewhere)
   float out_scale = 0.f; // != 0 (dclip_gemm_f16_scaled_split): C is fp16 [M][ldc >= 3N], the [hi|lo|hi] split of out_scale * result
+  // device-scaled forms (dclip_gemm_f16_scaled_dev / _split_dev; split16.hip's plan record): the scales are read from device memory
+  const float* alpha_p = nullptr;      // non-null: alpha = *alpha_p
+  const float* out_scale_p = nullptr;  // non-null (out_scale != 0 marks the split output): out_scale = *out_scale_p
+  float* h32 = nullptr;                // split output: also the fp32 pre-activation (GELU) [M][N], or nullptr
+  float* g32 = nullptr;                // split output: also the fp32 result [M][N], or nullptr
 };
+
+__device__ __forceinline__ float dev_alpha(const GemmBf16Params& p) { return p.alpha_p ? *p.alpha_p : p.alpha; }
+__device__ __forceinline__ float dev_out_scale(const GemmBf16Params& p) { return p.out_scale_p ? *p.out_scale_p : p.out_scale; }
 
 // Split-output store (split16.hip has the stand-alone kernel): v = the final fp32 results of 4 consecutive columns, c = their
 // place in the first third of the row; hi = fp16(v s), lo = fp16(v s - hi), written as [hi | lo | hi], N columns apart.  v is
@@ -267,10 +275,11 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
       *reinterpret_cast<f32x4*>(p.slab + ((size_t)blockIdx.y * p.M + row) * p.N + col) = v;
       continue;
     }
-    v = v * p.alpha;
+    v = v * dev_alpha(p);
     if (p.epilogue & DCLIP_EPI_BIAS) v += *reinterpret_cast<const f32x4*>(p.bias + col);
     const size_t off = (size_t)row * p.ldc + col;
     if (p.epilogue & DCLIP_EPI_GELU) {
+      if (p.h32) *reinterpret_cast<f32x4*>(p.h32 + (size_t)row * p.N + col) = v;
       if (p.aux) {
         u16x4 h = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
         *reinterpret_cast<u16x4*>(p.aux + off) = h;
@@ -287,7 +296,8 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
     }
     if (p.epilogue & DCLIP_EPI_RESIDUAL) v += *reinterpret_cast<const f32x4*>(p.residual + off);
     if (p.out_scale != 0.f) {
-      store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, p.out_scale);
+      if (p.g32) *reinterpret_cast<f32x4*>(p.g32 + (size_t)row * p.N + col) = v;
+      store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, dev_out_scale(p));
     } else if (p.out_bf16) {
       u16x4 o = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
       *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned short*>(p.C) + off) = o;
@@ -452,10 +462,11 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
       const int lr = id / (BN / 4), lc = (id % (BN / 4)) * 4;
       const int row = m0 + hm * PROWS + lr, col = n0 + lc;
       if (row >= p.M || col >= p.N) continue;
-      f32x4 v = *reinterpret_cast<const f32x4*>(ct + lr * BN + lc) * p.alpha;
+      f32x4 v = *reinterpret_cast<const f32x4*>(ct + lr * BN + lc) * dev_alpha(p);
       if (p.epilogue & DCLIP_EPI_BIAS) v += *reinterpret_cast<const f32x4*>(p.bias + col);
       const size_t off = (size_t)row * p.ldc + col;
       if (p.epilogue & DCLIP_EPI_GELU) {
+        if (p.h32) *reinterpret_cast<f32x4*>(p.h32 + (size_t)row * p.N + col) = v;
         if (p.aux) {
           u16x4 h = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
           *reinterpret_cast<u16x4*>(p.aux + off) = h;
@@ -472,7 +483,8 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
       }
       if (p.epilogue & DCLIP_EPI_RESIDUAL) v += *reinterpret_cast<const f32x4*>(p.residual + off);
       if (p.out_scale != 0.f) {
-        store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, p.out_scale);
+        if (p.g32) *reinterpret_cast<f32x4*>(p.g32 + (size_t)row * p.N + col) = v;
+        store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, dev_out_scale(p));
       } else if (p.out_bf16) {
         u16x4 o = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
         *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned short*>(p.C) + off) = o;
@@ -507,7 +519,9 @@ int launch_dma(GemmBf16Params p, hipStream_t st) {
 // KIND 0 bias only, 1 quick-GELU (pre-activation saved to aux when given), 2 x dGELU(aux), 3 + residual.
 // The MFMAs form C^T blocks (W fragment as the A operand): accumulator register r of block (i, j) is
 // C[row 16 i + l15][column 16 j + 4 quad + r] — four consecutive columns per lane, one ds_write_b128 per block.
-template <class T, int KIND, bool OUT16>
+// DEV (dclip_gemm_f16_scaled_dev / _split_dev): alpha and out_scale are read through p.alpha_p / p.out_scale_p and the fp32
+// side outputs h32 / g32 are written; a kernel instance of its own, so that the code of every other caller is what it was.
+template <class T, int KIND, bool OUT16, bool DEV = false>
 __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4 (&acc)[8][4], float* ct, int m0, int n0,
                                             int tid, int wr, int wc, int quad, int l15) {
   constexpr int BN = 256;
@@ -516,6 +530,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
   const int colc = colok ? col : 0;
   f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
   if (p.epilogue & DCLIP_EPI_BIAS) bias4 = *reinterpret_cast<const f32x4*>(p.bias + colc);
+  const float alpha_d = DEV ? *p.alpha_p : 0.f;        // the DEV instance is launched only with alpha_p set
 #pragma unroll
   for (int hm = 0; hm < 2; ++hm) {
     const int rbase = m0 + hm * 128 + lr0;
@@ -543,10 +558,11 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const int row = rbase + 8 * q;
-      f32x4 v = *reinterpret_cast<const f32x4*>(ct + (lr0 + 8 * q) * BN + (((tid & 63) ^ ((lr0 + 8 * q) & 7)) << 2)) * p.alpha + bias4;
+      f32x4 v = *reinterpret_cast<const f32x4*>(ct + (lr0 + 8 * q) * BN + (((tid & 63) ^ ((lr0 + 8 * q) & 7)) << 2)) * (DEV ? alpha_d : p.alpha) + bias4;
       const size_t off = (size_t)row * p.ldc + col;
       const bool ok = row < p.M && colok;
       if (KIND == 1) {
+        if (DEV && !OUT16 && p.h32 && ok) *reinterpret_cast<f32x4*>(p.h32 + (size_t)row * p.N + col) = v;
         if (p.aux) {
           u16x4 h = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
           if (ok) *reinterpret_cast<u16x4*>(p.aux + off) = h;
@@ -563,7 +579,8 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
       if (KIND == 3) v += side[q];
       if (!ok) continue;
       if ((KIND == 0 || KIND == 1) && !OUT16 && p.out_scale != 0.f) {
-        store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, p.out_scale);
+        if (DEV && p.g32) *reinterpret_cast<f32x4*>(p.g32 + (size_t)row * p.N + col) = v;
+        store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, DEV ? *p.out_scale_p : p.out_scale);
         continue;
       }
       if (OUT16) {
@@ -594,7 +611,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
 // 8-byte unit u of row r is stored at u ^ (r & 15): the 16 rows of a ds_write_b64 lane group cover 32 banks.
 // SAVE: the staged value is the pre-activation h (written to aux); C = bf16(gelu(h)) is formed in the copy loop from the
 // rounded h, as in the two-pass form.
-template <class T, bool GELU, bool SAVE>
+template <class T, bool GELU, bool SAVE, bool DEV = false>
 __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f32x4 (&acc)[8][4], unsigned short* ct, int m0,
                                                 int n0, int tid, int wr, int wc, int quad, int l15) {
   constexpr int BN = 256;
@@ -606,11 +623,12 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
       bias4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (p.epilogue & DCLIP_EPI_BIAS) bias4[j] = *reinterpret_cast<const f32x4*>(p.bias + (col < p.N ? col : 0));
     }
+    const float alpha_d = DEV ? *p.alpha_p : 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        f32x4 v = acc[i][j] * p.alpha + bias4[j];
+        f32x4 v = acc[i][j] * (DEV ? alpha_d : p.alpha) + bias4[j];
         if (GELU && !SAVE) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
@@ -681,7 +699,7 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 // two lane groups of a half-wave (k-rows 8 apart) land on 32 different 8-byte bank pairs.  Same phases and barriers; the
 // DMA order is A1(kt+1) | - | A0(kt+2) | B0, B1(kt+2) (every half re-staged at least two phases after its last read, so
 // no lgkmcnt before a barrier is needed: phase 1 issues 24 reads, more than the 4-bit counter can express).
-template <class T, bool TOK>
+template <class T, bool TOK, bool DEV = false>
 __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   typedef typename T::x8 V8;
   constexpr int BM = 256, BN = 256, ROW = BKH;
@@ -905,27 +923,27 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   // ---- epilogue (pp_epilogue above), one instance per epilogue kind and output type
   const int kind = (p.epilogue & DCLIP_EPI_RESIDUAL) ? 3 : (p.epilogue & DCLIP_EPI_DGELU) ? 2 : (p.epilogue & DCLIP_EPI_GELU) ? 1 : 0;
   float* ct = reinterpret_cast<float*>(lds_raw);
-  if (p.slab) {   // split-K partial: raw accumulators into this split's [M][N] slab, the reduce kernel finishes
+  if (!DEV && p.slab) {   // split-K partial: raw accumulators into this split's [M][N] slab, the reduce kernel finishes
     GemmBf16Params ps = p;
     ps.C = p.slab + (size_t)blockIdx.y * p.M * p.N;
     ps.ldc = p.N;
     ps.epilogue = 0;
     ps.alpha = 1.f;
     ps.out_scale = 0.f;
-    pp_epilogue<T, 0, false>(ps, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    pp_epilogue<T, 0, false, false>(ps, acc, ct, m0, n0, tid, wr, wc, quad, l15);
     return;
   }
   if (p.out_bf16) {
     unsigned short* ct16 = reinterpret_cast<unsigned short*>(lds_raw);
-    if (kind == 0) pp_epilogue_b16<T, false, false>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
-    else if (kind == 1 && p.aux) pp_epilogue_b16<T, true, true>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
-    else if (kind == 1) pp_epilogue_b16<T, true, false>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
-    else pp_epilogue<T, 2, true>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);          // RESIDUAL needs an fp32 output (host check)
+    if (kind == 0) pp_epilogue_b16<T, false, false, DEV>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 1 && p.aux) pp_epilogue_b16<T, true, true, DEV>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 1) pp_epilogue_b16<T, true, false, DEV>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
+    else pp_epilogue<T, 2, true, DEV>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);          // RESIDUAL needs an fp32 output (host check)
   } else {
-    if (kind == 0) pp_epilogue<T, 0, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
-    else if (kind == 1) pp_epilogue<T, 1, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
-    else if (kind == 2) pp_epilogue<T, 2, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
-    else pp_epilogue<T, 3, false>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    if (kind == 0) pp_epilogue<T, 0, false, DEV>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 1) pp_epilogue<T, 1, false, DEV>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 2) pp_epilogue<T, 2, false, DEV>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else pp_epilogue<T, 3, false, DEV>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
   }
 }
 #undef PP_BARRIER
@@ -1287,6 +1305,12 @@ template <class T, bool TOK = false>
 int launch_pp(GemmBf16Params p, hipStream_t st, int splits = 1) {
   p.tiles_m = cdiv(p.M, 256);
   p.tiles_n = cdiv(p.N, 256);
+  if constexpr (std::is_same<T, F16T>::value && !TOK) {   // the device-scaled entries exist for F16T only
+    if (p.alpha_p) {
+      hipLaunchKernelGGL((gemm_bf16_pp_kernel<T, false, true>), dim3(p.tiles_m * p.tiles_n, splits), dim3(512), 0, st, p);
+      return DCLIP_OK;
+    }
+  }
   hipLaunchKernelGGL((gemm_bf16_pp_kernel<T, TOK>), dim3(p.tiles_m * p.tiles_n, splits), dim3(512), 0, st, p);
   return DCLIP_OK;
 }
@@ -1406,12 +1430,24 @@ constexpr bool kTrain16 = std::is_same<T, F16IeeeT>::value;
 template <class T>
 bool pp16() { return kTrain16<T> || pingpong_enabled(); }
 
+// the device-memory operands of the device-scaled entries (GemmBf16Params' last four members)
+struct DevScales {
+  const float* alpha_p;
+  const float* out_scale_p;
+  float* h32;
+  float* g32;
+};
+inline void set_dev(GemmBf16Params& p, const DevScales* d) {
+  if (d) p.alpha_p = d->alpha_p, p.out_scale_p = d->out_scale_p, p.h32 = d->h32, p.g32 = d->g32;
+}
+
 // The forward dispatcher of both 16-bit types: same checks, same plan.  Every kernel it can pick — register-staged 128x128 /
 // 64x64, LDS-DMA 128x128 (DCLIP_BF16_MID_DMA) and 256x256 (DCLIP_BF16_PP=0), ping-pong, persistent (DCLIP_BF16_PERSIST) — has
 // an instance per type, and the DCLIP_BF16_* switches select among them for fp16 exactly as for bf16.
 template <class T>
 int gemm16(const char* name, const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux, int M,
-           int N, int K, int lda, int ldw, int ldc, int epilogue, int out_bf16, void* stream, float alpha = 1.f, float out_scale = 0.f) {
+           int N, int K, int lda, int ldw, int ldc, int epilogue, int out_bf16, void* stream, float alpha = 1.f, float out_scale = 0.f,
+           const DevScales* dev = nullptr) {
   DCLIP_REQUIRE(A && W && C, "%s: null operand", name);
   DCLIP_REQUIRE(M > 0 && N > 0 && K > 0, "%s: bad shape M=%d N=%d K=%d", name, M, N, K);
   DCLIP_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "%s: lda/ldw must be multiples of 8 and >= K", name);
@@ -1434,6 +1470,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
   if (K % BKH == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= big_min) {
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
                       (unsigned short*)aux, 0, nullptr, alpha, out_scale};
+    set_dev(pb, dev);
     // persistent form when a CU gets several tiles (the towers' M = 100k shapes: 14 per CU): the epilogue of one tile
     // overlaps the K loop of the next.  DGELU (an extra side operand in the epilogue) stays on the one-tile kernel, and so does
     // GELU with an fp32 C: the persistent kernel's fp32 store path applies bias and residual only (it returned the
@@ -1441,7 +1478,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
     const int persist_min = getenv("DCLIP_BF16_PERSIST_MIN") ? atoi(getenv("DCLIP_BF16_PERSIST_MIN")) : 512;
     const bool gelu_f32 = (epilogue & DCLIP_EPI_GELU) && !out_bf16;
     const bool persist = !kTrain16<T> && pingpong_enabled() && persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && !gelu_f32 &&
-                         out_scale == 0.f &&
+                         out_scale == 0.f && !dev &&
                          ldc % 8 == 0 && N % 8 == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min;
     const char* variant = ".pp";
     if constexpr (kTrain16<T>) {
@@ -1468,6 +1505,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
     if (mid_dma && K % BKH == 0 && (long)cdiv(M, 128) * cdiv(N, 128) >= 256) {
       GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
                         (unsigned short*)aux, 0, nullptr, alpha, out_scale};
+      set_dev(pb, dev);
       launch_dma<T, 128, 128, 2, 2>(pb, st);
       DCLIP_CHECK_LAUNCH_V(name, ".dma128");
       return DCLIP_OK;
@@ -1477,6 +1515,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
   const int bm = small ? 64 : 128, bn = bm;
   GemmBf16Params p{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16,
                    cdiv(M, bm), cdiv(N, bn), (unsigned short*)aux, 0, nullptr, alpha, out_scale};
+  set_dev(p, dev);
   const size_t lds = (size_t)2 * (bm + bn) * BKH * 2;
   if (small) hipLaunchKernelGGL((gemm_bf16_kernel<T, 64, 64>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
   else hipLaunchKernelGGL((gemm_bf16_kernel<T, 128, 128>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
@@ -1519,6 +1558,37 @@ DCLIP_API int dclip_gemm_f16_scaled_split(const void* A, const void* W, void* C,
   DCLIP_REQUIRE(ldc % 8 == 0, "gemm_f16_scaled_split: ldc must be a multiple of 8");
   return gemm16<F16T>("gemm_f16_scaled_split", A, W, C, bias, nullptr, nullptr, M, N, K, lda, ldw, ldc, epilogue, 0, stream, alpha,
                       out_scale);
+}
+
+// The two entries above with their scales in DEVICE memory (split16.hip's plan record): the weights of a training
+// tower change every step, so alpha / out_scale are recomputed on the device and read through pointers — no host value to go
+// stale in a captured graph.  Same kernels and arithmetic: at equal scales every output equals the scalar entry's bit for bit
+// (the persistent kernel is not used).  _split_dev may also write the fp32 result g [M][N] and, with GELU, the fp32
+// pre-activation h [M][N] (what a training forward saves), each bit-equal to dclip_gemm_f16_scaled's output for that epilogue.
+DCLIP_API int dclip_gemm_f16_scaled_dev(const void* A, const void* W, void* C, const float* bias, const float* residual, int M,
+                                        int N, int K, int lda, int ldw, int ldc, int epilogue, int out_f16, const float* alpha,
+                                        void* stream) {
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU), "gemm_f16_scaled_dev: DGELU is a training epilogue");
+  DCLIP_REQUIRE(alpha && (uintptr_t)alpha % 4 == 0, "gemm_f16_scaled_dev: alpha must be a device pointer");
+  const DevScales dev{alpha, nullptr, nullptr, nullptr};
+  return gemm16<F16T>("gemm_f16_scaled_dev", A, W, C, bias, residual, nullptr, M, N, K, lda, ldw, ldc, epilogue, out_f16, stream, 1.f,
+                      0.f, &dev);
+}
+
+DCLIP_API int dclip_gemm_f16_scaled_split_dev(const void* A, const void* W, void* C, const float* bias, float* h32, float* g32, int M,
+                                              int N, int K, int lda, int ldw, int ldc, int epilogue, const float* alpha,
+                                              const float* out_scale, void* stream) {
+  DCLIP_REQUIRE(alpha && ((uintptr_t)alpha | (uintptr_t)out_scale) % 4 == 0,
+                "gemm_f16_scaled_split_dev: alpha / out_scale must be device pointers");
+  DCLIP_REQUIRE(ldc % 8 == 0, "gemm_f16_scaled_split_dev: ldc must be a multiple of 8");
+  DCLIP_REQUIRE(((uintptr_t)h32 | (uintptr_t)g32) % 16 == 0, "gemm_f16_scaled_split_dev: h32 / g32 must be 16-byte aligned");
+  DCLIP_REQUIRE(!h32 || (epilogue & DCLIP_EPI_GELU), "gemm_f16_scaled_split_dev: h32 is the pre-activation of a GELU epilogue");
+  DCLIP_REQUIRE(!(epilogue & ~(DCLIP_EPI_BIAS | DCLIP_EPI_GELU)), "gemm_f16_scaled_split_dev: the epilogue is BIAS | GELU");
+  // out_scale NULL: no split — C is the fp32 result [M][ldc] itself (the two-launch form: the stand-alone split pass follows)
+  DCLIP_REQUIRE(out_scale || !g32, "gemm_f16_scaled_split_dev: without out_scale C is the fp32 result (g32 must be NULL)");
+  const DevScales dev{alpha, out_scale, h32, g32};
+  return gemm16<F16T>("gemm_f16_scaled_split_dev", A, W, C, bias, nullptr, nullptr, M, N, K, lda, ldw, ldc, epilogue, 0, stream, 1.f,
+                      out_scale ? 1.f : 0.f, &dev);
 }
 
 // fp16 TRAINING path: dclip_gemm_bf16_ex's arguments, epilogues and limits with fp16 A / W / aux / 16-bit C, IEEE rounding

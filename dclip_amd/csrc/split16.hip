@@ -28,7 +28,9 @@ __device__ __forceinline__ void split1(float v, unsigned short& hi, unsigned sho
 // 8 columns per thread: two 16-byte loads, three 16-byte stores
 template <int ORDER>
 __global__ void __launch_bounds__(256) split_f16x3_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, int rows,
-                                                          int cols, int ldx, int ldy, float scale) {
+                                                          int cols, int ldx, int ldy, float scale_v,
+                                                          const float* __restrict__ scale_p) {
+  const float scale = scale_p ? *scale_p : scale_v;   // _dev entry: the scale lives in the device plan record
   const int c8 = cols >> 3;
   const size_t total = (size_t)rows * c8;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -58,7 +60,10 @@ __global__ void __launch_bounds__(256) split_f16x3_kernel(const float* __restric
 template <int NC, bool EXACT>
 __global__ void __launch_bounds__(256) ln_fwd_f16x3_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, unsigned short* __restrict__ y,
-                                                           int rows, int D, float eps, float scale) {
+                                                           int rows, int D, float eps, float scale_v,
+                                                           const float* __restrict__ scale_p, float* __restrict__ y32,
+                                                           float* __restrict__ mean, float* __restrict__ rstd) {
+  const float scale = scale_p ? *scale_p : scale_v;   // _dev entry: the scale lives in the device plan record
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -88,12 +93,17 @@ __global__ void __launch_bounds__(256) ln_fwd_f16x3_kernel(const float* __restri
     }
   }
   const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
+  if (lane == 0) {
+    if (mean) mean[row] = mu;
+    if (rstd) rstd[row] = rs;
+  }
   unsigned short* yr = y + (size_t)row * 3 * D;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const int i = lane + 64 * c;
     if (EXACT || i < d4) {
       f32x4 o = (v[c] - mu) * rs * g[c] + bt[c];
+      if (y32) reinterpret_cast<f32x4*>(y32 + (size_t)row * D)[i] = o;   // ln_fwd_kernel's output, for the backward
       u16x4 hi, lo;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -112,6 +122,224 @@ __global__ void __launch_bounds__(256) ln_fwd_f16x3_kernel(const float* __restri
 
 inline bool pow2(float s) { return s > 0.f && s - s == 0.f && (__builtin_bit_cast(unsigned int, s) & 0x007fffffu) == 0; }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// Device-side plan for a tower whose weights CHANGE (the student's vision tower): the statistics of the
+// encoder-layer weights, the power-of-two scales derived from them and the [hi|hi|lo] copies of the scaled weights are all
+// made on the device, three launches over a table of records built once.  Nothing is read back by the host.
+struct Split16Ref {          // 48 bytes (dclip_split16_record_bytes)
+  const float* src;          // fp32 [rows][cols], cols % 8 == 0, 16-byte aligned
+  unsigned short* dst;       // fp16 [rows][3 cols], the [hi|hi|lo] split of src * plan scale; null = statistics only
+  int rows, cols;
+  int layer;                 // which plan record
+  int max_slot;              // statistic (0..11, engine._SPLIT16_STATS order) receiving max|x|
+  int l1_slot;               // statistic receiving the maximum row L1 norm over rows >= l1_row0, or -1
+  int l1_row0;
+  int scale_slot;            // float of the plan record holding the weight scale (dst != null)
+  int tile0;                 // first tile (SPLIT16_TILE_ROWS rows) of this tensor
+};
+static_assert(sizeof(Split16Ref) == 48, "Split16Ref layout");
+
+constexpr int SPLIT16_TILE_ROWS = 32;
+constexpr int PLAN_FLOATS = 32;   // per layer: [0..3] activation scales ln1 ctx ln2 g | [4..7] weight scales qkv out fc1 fc2 |
+                                  // [8..11] alphas qkv out fc1 fc2 | [12] flags | [16..27] the twelve statistics
+constexpr int NSTAT = 12;
+
+__device__ __forceinline__ const Split16Ref& find_ref(const Split16Ref* refs, int n, int tile) {
+  int lo = 0, hi = n - 1;                              // last record with tile0 <= tile (uniform: scalar code)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (refs[mid].tile0 <= tile) lo = mid;
+    else hi = mid - 1;
+  }
+  return refs[lo];
+}
+
+__device__ __forceinline__ unsigned wave_umax(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned w = (unsigned)__shfl_xor((int)v, o, 64);
+    v = v > w ? v : w;
+  }
+  return v;
+}
+
+// max|x| and (for the rows that count) the largest row L1 norm of every record, one wave per row, into stats[layer][12] as
+// the BIT PATTERNS of non-negative floats under an integer atomic max: the order of the updates cannot matter, NaN (above
+// inf as an integer) survives, and a row sum is one fixed sequence (a lane adds its chunks in order, then the xor tree), so
+// the result is the same in every run.  The plan kernel consumes the accumulators and clears them for the next call.
+__global__ void __launch_bounds__(256) split16_stats_kernel(const Split16Ref* __restrict__ refs, int nrefs,
+                                                            unsigned* __restrict__ stats) {
+  const Split16Ref t = find_ref(refs, nrefs, blockIdx.x);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r0 = ((int)blockIdx.x - t.tile0) * SPLIT16_TILE_ROWS;
+  const int c4 = t.cols >> 2;
+  unsigned mx = 0u, l1 = 0u;
+  for (int r = r0 + wave; r < min(r0 + SPLIT16_TILE_ROWS, t.rows); r += 4) {
+    const f32x4* xr = reinterpret_cast<const f32x4*>(t.src + (size_t)r * t.cols);
+    float s = 0.f;
+    unsigned m = 0u;
+    for (int i = lane; i < c4; i += 64) {
+      const f32x4 v = xr[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float a = __builtin_fabsf(v[e]);
+        const unsigned b = __builtin_bit_cast(unsigned, a);
+        m = m > b ? m : b;
+      }
+      s += (__builtin_fabsf(v[0]) + __builtin_fabsf(v[1])) + (__builtin_fabsf(v[2]) + __builtin_fabsf(v[3]));
+    }
+    mx = mx > m ? mx : m;
+    if (t.l1_slot >= 0 && r >= t.l1_row0) {          // uniform per wave
+      const unsigned b = __builtin_bit_cast(unsigned, __builtin_fabsf(wave_sum(s)));
+      l1 = l1 > b ? l1 : b;
+    }
+  }
+  mx = wave_umax(mx);
+  if (lane == 0) {
+    atomicMax(stats + t.layer * NSTAT + t.max_slot, mx);
+    if (t.l1_slot >= 0) atomicMax(stats + t.layer * NSTAT + t.l1_slot, l1);
+  }
+}
+
+__device__ __forceinline__ float pow2f(int e) {      // 2^e, e clamped to the normal range
+  e = e < -126 ? -126 : (e > 127 ? 127 : e);
+  return __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
+}
+
+// engine.split16_weight_exp: f with max|W| 2^f in [2^13, 2^14); 0 for an all-zero (or, flagged, a non-finite) weight
+__device__ int weight_exp(double max_abs, unsigned& flags) {
+  if (!(max_abs - max_abs == 0.0)) {
+    flags |= 2u;
+    return 0;
+  }
+  if (max_abs == 0.0) return 0;
+  int x;
+  frexp(max_abs, &x);
+  return 14 - x;
+}
+
+// engine.split16_act_exp without its fall-back: the largest e <= 24 with bound 2^e <= 2^14; where the host function returns
+// None (e < -14, or the bound is not finite) the flag is set and e is what the bound asks for (0 when it is not finite).
+__device__ int act_exp(double bound, unsigned& flags) {
+  if (!(bound - bound == 0.0) || bound < 0.0) {
+    flags |= 2u;
+    return 0;
+  }
+  if (bound == 0.0) return 24;
+  int x;
+  const double m = frexp(bound, &x);
+  const int e = 14 - (m == 0.5 ? x - 1 : x);
+  if (e < -14) flags |= 1u;
+  return e < 24 ? e : 24;
+}
+
+// One thread per layer: statistics -> bounds (engine.split16_layer_bounds, in double, products and sums rounded one by one as
+// the host's are) -> exponents -> the plan record; then the accumulators are cleared for the next statistics launch.
+__global__ void split16_plan_kernel(unsigned* __restrict__ stats, float* __restrict__ plan, int nlayers, double sqrt_d) {
+#pragma clang fp contract(off)
+  const int l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= nlayers) return;
+  double st[NSTAT];
+  float* rec = plan + (size_t)l * PLAN_FLOATS;
+  for (int i = 0; i < NSTAT; ++i) {
+    const float f = __builtin_bit_cast(float, stats[l * NSTAT + i]);
+    st[i] = (double)f;
+    rec[16 + i] = f;
+    stats[l * NSTAT + i] = 0u;
+  }
+  // ln1_w ln1_b v_l1 v_b ln2_w ln2_b fc1_l1 fc1_b qkv out fc1 fc2
+  unsigned flags = 0u;
+  const double b_ln1 = __dadd_rn(__dmul_rn(st[0], sqrt_d), st[1]);
+  const double b_ln2 = __dadd_rn(__dmul_rn(st[4], sqrt_d), st[5]);
+  const double b_ctx = __dadd_rn(__dmul_rn(b_ln1, st[2]), st[3]);
+  const double b_g = __dadd_rn(__dmul_rn(b_ln2, st[6]), st[7]);
+  int e[4] = {act_exp(b_ln1, flags), act_exp(b_ctx, flags), act_exp(b_ln2, flags), act_exp(b_g, flags)};
+  int f[4];
+  for (int i = 0; i < 4; ++i) f[i] = weight_exp(st[8 + i], flags);
+  for (int i = 0; i < 4; ++i) {
+    // a scale outside fp32's normal range (a bound beyond 2^140, a weight below 2^-113) is clamped and flagged
+    if (e[i] < -126) e[i] = -126, flags |= 4u;
+    if (f[i] > 127) f[i] = 127, flags |= 4u;
+    if (-(e[i] + f[i]) > 127 || -(e[i] + f[i]) < -126) flags |= 4u;
+    rec[i] = pow2f(e[i]);
+    rec[4 + i] = pow2f(f[i]);
+    rec[8 + i] = pow2f(-(e[i] + f[i]));
+  }
+  rec[12] = __builtin_bit_cast(float, flags);
+  rec[13] = rec[14] = rec[15] = 0.f;
+  rec[28] = rec[29] = rec[30] = rec[31] = 0.f;
+}
+
+// [hi|hi|lo] of src * (the plan's scale for that weight) for every record with a destination: split_f16x3_kernel<1>'s
+// arithmetic, 8 columns per thread, one tile of rows per workgroup.
+__global__ void __launch_bounds__(256) split16_weights_kernel(const Split16Ref* __restrict__ refs, int nrefs,
+                                                              const float* __restrict__ plan) {
+  const Split16Ref t = find_ref(refs, nrefs, blockIdx.x);
+  if (!t.dst) return;                                  // uniform
+  const float scale = plan[(size_t)t.layer * PLAN_FLOATS + t.scale_slot];
+  const int r0 = ((int)blockIdx.x - t.tile0) * SPLIT16_TILE_ROWS;
+  const int nr = min(SPLIT16_TILE_ROWS, t.rows - r0);
+  const int c8 = t.cols >> 3;
+  for (int i = threadIdx.x; i < nr * c8; i += 256) {
+    const int c = (i % c8) * 8;
+    const size_t r = (size_t)(r0 + i / c8);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(t.src + r * t.cols + c);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(t.src + r * t.cols + c + 4);
+    u16x8 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      unsigned short h0, l0, h1, l1;
+      split1(a[e] * scale, h0, l0);
+      split1(b[e] * scale, h1, l1);
+      hi[e] = h0, lo[e] = l0, hi[4 + e] = h1, lo[4 + e] = l1;
+    }
+    unsigned short* yr = t.dst + r * 3 * t.cols + c;
+    *reinterpret_cast<u16x8*>(yr) = hi;
+    *reinterpret_cast<u16x8*>(yr + t.cols) = hi;
+    *reinterpret_cast<u16x8*>(yr + 2 * t.cols) = lo;
+  }
+}
+
+int split_launch(const char* name, const float* x, void* y, int rows, int cols, int ldx, int ldy, float scale,
+                 const float* scale_p, int order, void* stream) {
+  const size_t work = (size_t)rows * (cols / 8);
+  const size_t blocks = (work + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks)));
+  hipStream_t st = (hipStream_t)stream;
+  if (order == 0)
+    hipLaunchKernelGGL(split_f16x3_kernel<0>, grid, dim3(256), 0, st, x, (unsigned short*)y, rows, cols, ldx, ldy, scale, scale_p);
+  else
+    hipLaunchKernelGGL(split_f16x3_kernel<1>, grid, dim3(256), 0, st, x, (unsigned short*)y, rows, cols, ldx, ldy, scale, scale_p);
+  DCLIP_CHECK_LAUNCH_V(name, order == 0 ? ".act" : ".weight");
+  return DCLIP_OK;
+}
+
+int ln_launch(const char* name, const float* x, const float* gamma, const float* beta, void* y, int rows, int D, float eps,
+              float scale, const float* scale_p, float* y32, float* mean, float* rstd, void* stream) {
+  dim3 grid(cdiv(rows, 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const int nc = cdiv(D / 4, 64);
+  unsigned short* yy = (unsigned short*)y;
+  const char* variant;
+#define LN16X3(NC, EX)                                                                                                      \
+  do {                                                                                                                      \
+    hipLaunchKernelGGL((ln_fwd_f16x3_kernel<NC, EX>), grid, block, 0, st, x, gamma, beta, yy, rows, D, eps, scale, scale_p, \
+                       y32, mean, rstd);                                                                                    \
+    variant = (EX) ? ".nc" #NC ".exact" : ".nc" #NC;                                                                        \
+  } while (0)
+  if (D == 512) LN16X3(2, true);
+  else if (D == 768) LN16X3(3, true);
+  else if (D == 1024) LN16X3(4, true);
+  else if (nc <= 1) LN16X3(1, false);
+  else if (nc == 2) LN16X3(2, false);
+  else if (nc == 3) LN16X3(3, false);
+  else if (nc == 4) LN16X3(4, false);
+  else LN16X3(8, false);
+#undef LN16X3
+  DCLIP_CHECK_LAUNCH_V(name, variant);
+  return DCLIP_OK;
+}
+
 }  // namespace
 
 DCLIP_API int dclip_split_f32_f16x3(const float* x, void* y, int rows, int cols, int ldx, int ldy, float scale, int order,
@@ -123,14 +351,19 @@ DCLIP_API int dclip_split_f32_f16x3(const float* x, void* y, int rows, int cols,
   DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0, "split_f32_f16x3: operands must be 16-byte aligned");
   DCLIP_REQUIRE(order == 0 || order == 1, "split_f32_f16x3: order is 0 ([hi|lo|hi]) or 1 ([hi|hi|lo])");
   DCLIP_REQUIRE(pow2(scale), "split_f32_f16x3: scale must be a power of two");
-  const size_t work = (size_t)rows * (cols / 8);
-  const size_t blocks = (work + 255) / 256;
-  const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks)));
-  hipStream_t st = (hipStream_t)stream;
-  if (order == 0) hipLaunchKernelGGL(split_f16x3_kernel<0>, grid, dim3(256), 0, st, x, (unsigned short*)y, rows, cols, ldx, ldy, scale);
-  else hipLaunchKernelGGL(split_f16x3_kernel<1>, grid, dim3(256), 0, st, x, (unsigned short*)y, rows, cols, ldx, ldy, scale);
-  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3", order == 0 ? ".act" : ".weight");
-  return DCLIP_OK;
+  return split_launch("split_f32_f16x3", x, y, rows, cols, ldx, ldy, scale, nullptr, order, stream);
+}
+
+// dclip_split_f32_f16x3 with the scale in device memory (a float of the plan record)
+DCLIP_API int dclip_split_f32_f16x3_dev(const float* x, void* y, int rows, int cols, int ldx, int ldy, const float* scale,
+                                        int order, void* stream) {
+  DCLIP_REQUIRE(x && y && scale && rows > 0 && cols > 0, "split_f32_f16x3_dev: bad arguments");
+  DCLIP_REQUIRE(cols % 8 == 0, "split_f32_f16x3_dev: cols=%d must be a multiple of 8", cols);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0 && ldy % 8 == 0 && (long)ldy >= 3L * cols,
+                "split_f32_f16x3_dev: ldx (multiple of 4, >= cols) / ldy (multiple of 8, >= 3 cols)");
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0 && (uintptr_t)scale % 4 == 0, "split_f32_f16x3_dev: alignment");
+  DCLIP_REQUIRE(order == 0 || order == 1, "split_f32_f16x3_dev: order is 0 ([hi|lo|hi]) or 1 ([hi|hi|lo])");
+  return split_launch("split_f32_f16x3_dev", x, y, rows, cols, ldx, ldy, 1.f, scale, order, stream);
 }
 
 DCLIP_API int dclip_layernorm_fwd_f16x3(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,
@@ -140,25 +373,48 @@ DCLIP_API int dclip_layernorm_fwd_f16x3(const float* x, const float* gamma, cons
   DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0 && (uintptr_t)y % 8 == 0,
                 "layernorm_fwd_f16x3: alignment");
   DCLIP_REQUIRE(pow2(scale), "layernorm_fwd_f16x3: scale must be a power of two");
-  dim3 grid(cdiv(rows, 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const int nc = cdiv(D / 4, 64);
-  unsigned short* yy = (unsigned short*)y;
-  const char* variant;
-#define LN16X3(NC, EX)                                                                                            \
-  do {                                                                                                            \
-    hipLaunchKernelGGL((ln_fwd_f16x3_kernel<NC, EX>), grid, block, 0, st, x, gamma, beta, yy, rows, D, eps, scale); \
-    variant = (EX) ? ".nc" #NC ".exact" : ".nc" #NC;                                                              \
-  } while (0)
-  if (D == 512) LN16X3(2, true);
-  else if (D == 768) LN16X3(3, true);
-  else if (D == 1024) LN16X3(4, true);
-  else if (nc <= 1) LN16X3(1, false);
-  else if (nc == 2) LN16X3(2, false);
-  else if (nc == 3) LN16X3(3, false);
-  else if (nc == 4) LN16X3(4, false);
-  else LN16X3(8, false);
-#undef LN16X3
-  DCLIP_CHECK_LAUNCH_V("layernorm_fwd_f16x3", variant);
+  return ln_launch("layernorm_fwd_f16x3", x, gamma, beta, y, rows, D, eps, scale, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// dclip_layernorm_fwd_f16x3 with the scale in device memory; y32 / mean / rstd (each may be null) also receive what
+// dclip_layernorm_fwd writes — the fp32 output and the row statistics a training forward saves — bit for bit.
+DCLIP_API int dclip_layernorm_fwd_f16x3_dev(const float* x, const float* gamma, const float* beta, void* y, float* y32, float* mean,
+                                            float* rstd, int rows, int D, float eps, const float* scale, void* stream) {
+  DCLIP_REQUIRE(x && gamma && beta && y && scale, "layernorm_fwd_f16x3_dev: null pointer");
+  DCLIP_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 2048, "layernorm_fwd_f16x3_dev: bad D=%d", D);
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y32) % 16 == 0 && (uintptr_t)y % 8 == 0 &&
+                    (uintptr_t)scale % 4 == 0,
+                "layernorm_fwd_f16x3_dev: alignment");
+  return ln_launch("layernorm_fwd_f16x3_dev", x, gamma, beta, y, rows, D, eps, 1.f, scale, y32, mean, rstd, stream);
+}
+
+// ---- device plan (see Split16Ref): record size, and the three launches over a table of `nrefs` records / `tiles` tiles
+DCLIP_API int dclip_split16_record_bytes(void) { return (int)sizeof(Split16Ref); }
+DCLIP_API int dclip_split16_plan_floats(void) { return PLAN_FLOATS; }
+DCLIP_API int dclip_split16_tile_rows(void) { return SPLIT16_TILE_ROWS; }
+
+// stats: uint32 [nlayers][12] accumulators, zero before the first call (the plan launch clears them again)
+DCLIP_API int dclip_split16_stats(const void* refs, int nrefs, int tiles, void* stats, void* stream) {
+  DCLIP_REQUIRE(refs && stats && nrefs > 0 && tiles > 0, "split16_stats: bad arguments");
+  hipLaunchKernelGGL(split16_stats_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, (const Split16Ref*)refs, nrefs,
+                     (unsigned*)stats);
+  DCLIP_CHECK_LAUNCH("split16_stats");
+  return DCLIP_OK;
+}
+
+// plan: float [nlayers][32] records from the statistics; D = the tower's width (LayerNorm's bound is max|gamma| sqrt(D) + max|beta|)
+DCLIP_API int dclip_split16_plan(void* stats, float* plan, int nlayers, int D, void* stream) {
+  DCLIP_REQUIRE(stats && plan && nlayers > 0 && D > 0, "split16_plan: bad arguments");
+  hipLaunchKernelGGL(split16_plan_kernel, dim3(cdiv(nlayers, 64)), dim3(64), 0, (hipStream_t)stream, (unsigned*)stats, plan, nlayers,
+                     __builtin_sqrt((double)D));
+  DCLIP_CHECK_LAUNCH("split16_plan");
+  return DCLIP_OK;
+}
+
+// weights: the [hi|hi|lo] copies of every record with a destination, scaled by the plan
+DCLIP_API int dclip_split16_weights(const void* refs, int nrefs, int tiles, const float* plan, void* stream) {
+  DCLIP_REQUIRE(refs && plan && nrefs > 0 && tiles > 0, "split16_weights: bad arguments");
+  hipLaunchKernelGGL(split16_weights_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, (const Split16Ref*)refs, nrefs, plan);
+  DCLIP_CHECK_LAUNCH("split16_weights");
   return DCLIP_OK;
 }

@@ -43,15 +43,63 @@ class LayerParams:
         return [getattr(self, f) for f in self.FIELDS]
 
 
-def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: float, save: bool):
-    ln1, m1, r1 = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, eps, save_stats=save)
-    qkv = ops.gemm(ln1, p.qkv_w, ops.LAYOUT_NT, bias=p.qkv_b)
+class Split16Layer:
+    """One layer's view of a tower's device-side split-fp16 plan (_vision_split16_plan): the [hi|hi|lo] fp16
+    copies of its four GEMM weights and the ADDRESSES of its scales in the plan record.  Handed to layer_fwd /
+    last_layer_fwd_cls as `sp`: their full-size GEMMs then run on the fp16 MFMAs with split operands; None = plain fp32."""
+    __slots__ = ("w", "base")
+
+    def __init__(self, w: Dict[str, torch.Tensor], base: int):
+        self.w, self.base = w, base
+
+    def act(self, name: str) -> int:
+        return self.base + 4 * ops.SPLIT16_PLAN_ACT[name]
+
+    def alpha(self, name: str) -> int:
+        return self.base + 4 * ops.SPLIT16_PLAN_ALPHA[name]
+
+
+# The three steps of a layer schedule that differ between the plain fp32 path (sp None) and the split-fp16 one: each returns
+# the GEMM operand first (the fp32 tensor itself / its [hi|lo|hi] split) and the fp32 tensors the backward keeps.
+
+def _ln_operand(x, w, b, eps: float, save: bool, sp: Optional[Split16Layer], name: str):
+    if sp is None:
+        ln, m, r = ops.layernorm_fwd(x, w, b, eps, save_stats=save)
+        return ln, ln, m, r
+    return ops.layernorm_fwd_f16x3_dev(x, w, b, eps, sp.act(name), save=save)
+
+
+def _linear(a, w, sp: Optional[Split16Layer], name: str, bias, residual=None):
+    if sp is None:
+        return ops.gemm(a, w, ops.LAYOUT_NT, bias=bias, residual=residual)
+    return ops.gemm_f16_dev(a, sp.w[name], sp.alpha(name), bias=bias, residual=residual)
+
+
+def _fc1_gelu(a, p: LayerParams, save: bool, sp: Optional[Split16Layer]):
+    """(operand of fc2, h, g): g = quick_gelu(h), h = a fc1_w^T + b kept only with `save`."""
+    M, I = a.shape[0], p.fc1_w.shape[0]
+    h = torch.empty((M, I), dtype=torch.float32, device=a.device) if save else None
+    if sp is None:
+        g = ops.gemm(a, p.fc1_w, ops.LAYOUT_NT, bias=p.fc1_b, aux=h, epilogue=ops.EPI_GELU)
+        return g, h, g
+    g = torch.empty((M, I), dtype=torch.float32, device=a.device) if save else None
+    if _VSPLIT16_FC1_EPI:
+        g3 = ops.gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), bias=p.fc1_b, gelu=True, split_out_scale_ptr=sp.act("g"), h32=h, g32=g)
+        return g3, h, g
+    # two-launch form (bit-identical results; kept for the A/B of DESIGN.md §9d): h and g leave the GEMM, g is split after it
+    g = ops.gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), bias=p.fc1_b, gelu=True, h32=h)
+    return ops.split_f16x3_dev(g, sp.act("g")), h, g
+
+
+def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: float, save: bool, sp: Optional[Split16Layer] = None):
+    a, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1")
+    qkv = _linear(a, p.qkv_w, sp, "qkv", p.qkv_b)
     attn, lse = ops.attention_fwd(qkv, B, S, H, causal)
-    x1 = ops.gemm(attn, p.out_w, ops.LAYOUT_NT, bias=p.out_b, residual=x)
-    ln2, m2, r2 = ops.layernorm_fwd(x1, p.ln2_w, p.ln2_b, eps, save_stats=save)
-    h = torch.empty((x.shape[0], p.fc1_w.shape[0]), dtype=torch.float32, device=x.device) if save else None
-    g = ops.gemm(ln2, p.fc1_w, ops.LAYOUT_NT, bias=p.fc1_b, aux=h, epilogue=ops.EPI_GELU)
-    x2 = ops.gemm(g, p.fc2_w, ops.LAYOUT_NT, bias=p.fc2_b, residual=x1)
+    a = attn if sp is None else ops.split_f16x3_dev(attn, sp.act("ctx"))
+    x1 = _linear(a, p.out_w, sp, "out", p.out_b, residual=x)
+    a, ln2, m2, r2 = _ln_operand(x1, p.ln2_w, p.ln2_b, eps, save, sp, "ln2")
+    a, h, g = _fc1_gelu(a, p, save, sp)
+    x2 = _linear(a, p.fc2_w, sp, "fc2", p.fc2_b, residual=x1)
     saved = (x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g) if save else None
     return x2, saved
 
@@ -122,10 +170,11 @@ def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, 
 # zero).  K and V, hence the qkv projection, LayerNorm1 and their gradients, stay full size.  Results are identical
 # to the unpruned schedule (tests/test_model_gpu.py); 9/12 of that layer's GEMM work disappears.
 
-def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, save: bool):
+def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, save: bool, sp: Optional[Split16Layer] = None):
+    """`sp`: the full-size qkv projection takes the split-fp16 path (layer_fwd); the M = B GEMMs stay on ops.gemm."""
     D = x.shape[1]
-    ln1, m1, r1 = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, eps, save_stats=save)
-    qkv = ops.gemm(ln1, p.qkv_w, ops.LAYOUT_NT, bias=p.qkv_b)
+    a, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1")
+    qkv = _linear(a, p.qkv_w, sp, "qkv", p.qkv_b)
     attn, lse = ops.attention_cls_fwd(qkv, B, S, H)                       # [B, D]
     x_cls = ops.gather_rows(x, None, B, S, D)
     x1 = ops.gemm(attn, p.out_w, ops.LAYOUT_NT, bias=p.out_b, residual=x_cls)
@@ -219,9 +268,12 @@ def _grid_pos_grad(dpos_cols: torch.Tensor, p: VisionParams, v, grid, alloc, dev
     return ops.pos_interp_bwd(dpos_cols.view(-1, D), g, grid[0], grid[1], out=out.view(1 + g * g, D))
 
 
-def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None, grid=None):
+def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None, grid=None,
+               split16_cache: Optional[dict] = None):
     """get_image_features: [B,3,H,W] -> [B,P]  (hf:modeling_clip.py:202-218, :641-651, :744-751).  `grid` = (gh, gw): run on
-    that patch grid with the position table resampled to it (None: the configuration's image size, as ever)."""
+    that patch grid with the position table resampled to it (None: the configuration's image size, as ever).
+    `split16_cache` (the model's, HipCLIPModel._vsplit16_cache): a forward that saves for the backward runs the encoder
+    layers' full-size GEMMs on split-fp16 operands (DCLIP_VISION_SPLIT16); a no-grad forward never does."""
     v = cfg
     B = pixel_values.shape[0]
     S, D, H = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads
@@ -238,12 +290,14 @@ def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hid
         hidden_out.append(x)
     saved_layers = []
     prune = hidden_out is None and len(p.layers) > 0          # full hidden states are only materialised on request
+    plan = _vision_split16_plan(p.layers, v, split16_cache) if save and split16_cache is not None and _VSPLIT16 else None
     for li, lp in enumerate(p.layers):
+        sp = plan[li] if plan is not None else None
         if prune and li == len(p.layers) - 1:
-            cls_tok, sv = last_layer_fwd_cls(x, lp, B, S, H, v.layer_norm_eps, save)
+            cls_tok, sv = last_layer_fwd_cls(x, lp, B, S, H, v.layer_norm_eps, save, sp)
             saved_layers.append(sv)
             break
-        x, sv = layer_fwd(x, lp, B, S, H, False, v.layer_norm_eps, save)
+        x, sv = layer_fwd(x, lp, B, S, H, False, v.layer_norm_eps, save, sp)
         saved_layers.append(sv)
         if hidden_out is not None:
             hidden_out.append(x)
@@ -1105,6 +1159,120 @@ def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: 
     rows = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
     pooled, _, _ = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=False)
     return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+
+
+# --------------------------------------------------------------------------------------------- student's vision forward, split fp16
+# The same arithmetic for a tower that TRAINS: its weights change every step, so the host-side plan above (one
+# device -> host read, host floats handed to the kernels) cannot be used — a read per step is a sync in the hot path and a host
+# float captured in a HIP graph is stale after the next optimizer step.  Statistics, scales and the split weight copies are
+# made ON THE DEVICE by three launches (ops.split16_refresh) at the head of a forward whenever a watched parameter's version
+# or address has moved, and the kernels read the scales through pointers into the plan record.  The device applies the rules
+# of split16_layer_bounds / split16_act_exp / split16_weight_exp but has no fall-back: where the host guard would decline, it
+# takes the exponent the bound asks for and raises a flag, which reaches the host by a copy nothing waits for.
+
+_VSPLIT16 = os.environ.get("DCLIP_VISION_SPLIT16", "1") != "0"    # read once at import: no getenv on the launch path
+# fc1 leaves its GEMM as h, g AND the split of g (one launch, three outputs); 0 = h and g from the GEMM, then the split pass
+_VSPLIT16_FC1_EPI = os.environ.get("DCLIP_VISION_SPLIT16_FC1_EPI", "1") != "0"
+
+
+def vision_split16_enabled() -> bool:
+    return _VSPLIT16
+
+
+def split16_plan_host(st: Dict[str, float], D: int) -> Dict[str, object]:
+    """What the device plan kernel (dclip_split16_plan) makes of one layer's statistics `st` (keys _SPLIT16_STATS): the
+    exponents e (activations), f (weights), a = -(e + f) (alphas) and the flag bits.  The host rules above without their
+    fall-back: where split16_act_exp declines, the exponent the bound asks for is taken and a flag is set (1: e < -14,
+    2: a non-finite statistic, 4: a scale outside fp32's normal range, clamped).  The reference of tests/test_vision_split16_*."""
+    import math
+    flags = 0
+    e, f = {}, {}
+    for k, b in split16_layer_bounds(st, D).items():
+        x = split16_act_exp(b)
+        if x is None:
+            if not math.isfinite(b) or b < 0.0:
+                flags |= 2
+                x = 0
+            else:
+                flags |= 1
+                m, ex = math.frexp(b)
+                x = _SPLIT16_TOP - (ex - 1 if m == 0.5 else ex)
+        e[k] = x
+    for short, _ in _TRAIN_WEIGHTS:
+        if math.isfinite(st[short]):
+            f[short] = split16_weight_exp(st[short])
+        else:
+            flags |= 2
+            f[short] = 0
+    a = {}
+    for short, akey in (("qkv", "ln1"), ("out", "ctx"), ("fc1", "ln2"), ("fc2", "g")):
+        if e[akey] < -126:
+            e[akey], flags = -126, flags | 4
+        if f[short] > 127:
+            f[short], flags = 127, flags | 4
+        a[short] = -(e[akey] + f[short])
+        if not -126 <= a[short] <= 127:
+            a[short], flags = max(-126, min(127, a[short])), flags | 4
+    return {"e": e, "f": f, "a": a, "flags": flags}
+
+
+def _vision_split16_flags(ent: dict) -> None:
+    """Look at the flags the LAST refresh left in pinned host memory (never waited for: a flag is seen a step late).  The
+    copy of the current step may be in flight while this reads: a flag is one aligned 32-bit word, so what is read is
+    either the old or the new word, and a flag missed now is seen at the next look."""
+    host = ent["host"]
+    if host is None:
+        return
+    flags = host[:, ops.SPLIT16_PLAN_FLAGS].view(torch.int32)
+    if bool(flags.any()):
+        _split16_log_once("split-fp16 vision tower: a weight statistic is non-finite or an activation bound needs a scale below "
+                          "2^-14 (layer flags " + ", ".join(f"{i}:{int(f)}" for i, f in enumerate(flags.tolist()) if f) +
+                          "); the forward stays on the split path with that scale and may lose accuracy "
+                          "(DCLIP_VISION_SPLIT16=0 selects the plain fp32 path)")
+
+
+def vision_split16_check_flags(cache: Optional[dict]) -> None:
+    """The host's look at the guard flags for a caller that replays a captured step (graph.GraphedStep.step): a replay
+    re-plans on the device and rewrites the pinned copy, but never re-enters _vision_split16_plan."""
+    ent = cache.get("__vsplit16__") if cache else None
+    if ent is not None:
+        _vision_split16_flags(ent)
+
+
+def _vision_split16_plan(layers: List[LayerParams], cfg, cache: dict):
+    """Per layer a Split16Layer over the model's device plan, refreshed (three launches, no host read) when a watched
+    parameter changed; None = the plain path (widths not multiples of 8, or the very first call arrives inside a graph
+    capture).  While a stream is capturing the refresh is always issued, so that it is part of the graph and every replay
+    plans and splits the weights of that moment."""
+    if len(layers) == 0 or cfg.hidden_size % 8 or cfg.intermediate_size % 8:
+        return None
+    capturing = torch.cuda.is_current_stream_capturing()
+    ent = cache.get("__vsplit16__")
+    ptrs = tuple(getattr(lp, f).data_ptr() for lp in layers for f in _SPLIT16_WATCHED)
+    if ent is None or ent["ptrs"] != ptrs:
+        if capturing:
+            _split16_log_once("split-fp16 vision tower: first use inside a graph capture; this capture takes the plain fp32 path "
+                              "(run one eager step first)")
+            return None
+        if any(not getattr(lp, f).is_contiguous() for lp in layers for f in _SPLIT16_WATCHED):
+            return None
+        tab = ops.split16_table([{f: getattr(lp, f) for f in _SPLIT16_WATCHED} for lp in layers])
+        base, stride = tab["plan"].data_ptr(), 4 * tab["plan"].shape[1]
+        ent = {"ptrs": ptrs, "tab": tab, "versions": None, "host": None,
+               "layers": [Split16Layer(w, base + li * stride) for li, w in enumerate(tab["w"])]}
+        try:
+            ent["host"] = torch.zeros(tuple(tab["plan"].shape), dtype=torch.float32).pin_memory()
+        except RuntimeError:
+            ent["host"] = None
+        cache["__vsplit16__"] = ent
+    versions = tuple(getattr(lp, f)._version for lp in layers for f in _SPLIT16_WATCHED)
+    if capturing or ent["versions"] != versions:
+        _vision_split16_flags(ent)
+        ops.split16_refresh(ent["tab"])
+        if ent["host"] is not None:
+            ent["host"].copy_(ent["tab"]["plan"], non_blocking=True)
+        ent["versions"] = None if capturing else versions
+    return ent["layers"]
 
 
 def text_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None):

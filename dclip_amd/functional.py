@@ -38,11 +38,13 @@ def _c(t: torch.Tensor) -> torch.Tensor:
 
 class VisionTowerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pixel_values, cfg, n_layers, grid, *params):
-        """`grid`: None, or the (gh, gw) patch grid of pixel_values when it is not the configuration's (engine.vision_fwd)."""
+    def forward(ctx, pixel_values, cfg, n_layers, grid, split16_cache, *params):
+        """`grid`: None, or the (gh, gw) patch grid of pixel_values when it is not the configuration's (engine.vision_fwd).
+        `split16_cache`: the model's cache of device-planned split-fp16 weights (HipCLIPModel._vsplit16_cache) — a forward that
+        saves for the backward runs its full-size GEMMs with it (DCLIP_VISION_SPLIT16); None: the plain fp32 path."""
         p = engine.VisionParams.from_tensors([_c(t.detach()) for t in params], n_layers)
-        save = any(ctx.needs_input_grad[4:])
-        out, saved = engine.vision_fwd(p, _c(pixel_values.detach()), cfg, save, grid=grid)
+        save = any(ctx.needs_input_grad[5:])
+        out, saved = engine.vision_fwd(p, _c(pixel_values.detach()), cfg, save, grid=grid, split16_cache=split16_cache)
         ctx.p, ctx.saved, ctx.cfg = p, saved, cfg
         ctx.param_refs = params if save else None          # the nn.Parameters, for the data-parallel hook
         return out
@@ -64,11 +66,11 @@ class VisionTowerFn(torch.autograd.Function):
         if _GRAD_ALLOC is not None:
             galloc = _GRAD_ALLOC
             alloc = lambda name, shape: galloc(by_name[name], shape)      # noqa: E731
-        grads = engine.vision_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[4:]), on_ready, alloc)
+        grads = engine.vision_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[5:]), on_ready, alloc)
         ctx.saved = None
         if owned:           # handed to the data-parallel reducer: autograd neither accumulates nor clones them
             grads = [None if n in owned else g for n, g in zip(ctx.p.names(), grads)]
-        return (None, None, None, None, *grads)
+        return (None, None, None, None, None, *grads)
 
 
 class VisionTowerBf16Fn(torch.autograd.Function):

@@ -50,6 +50,9 @@ class GraphedStep:
             self.loss = module.training_step(self.static)
             self.loss.backward()
         self.losses = dict(getattr(module, "last_losses", {}))
+        # split-fp16 vision forward: every replay re-plans on the device and copies the guard flags to pinned memory; the
+        # host looks at them here, once per step, without waiting for anything
+        self._vsplit16 = [m._vsplit16_cache() for m in module.modules() if hasattr(m, "_vsplit16_cache")]
 
     def load(self, batch: Dict[str, torch.Tensor]):
         for k, v in batch.items():
@@ -69,6 +72,10 @@ class GraphedStep:
         if batch is not None:
             self.load(batch)
         self.graph.replay()
+        if self._vsplit16:
+            from . import engine
+            for c in self._vsplit16:
+                engine.vision_split16_check_flags(c)
         return self.loss
 
     __call__ = step

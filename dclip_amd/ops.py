@@ -1162,6 +1162,164 @@ def layernorm_fwd_f16x3(x, gamma, beta, eps: float, scale: float = 1.0) -> torch
     return y
 
 
+# ------------------------------------------------------------------------------------------- split-fp16, scales on the device
+# The wrappers above for a tower whose weights change every step (the student's vision forward): every scale
+# is the ADDRESS of a float of the device plan record (split16_refresh computes it on the device), passed as an int.
+
+def split_f16x3_dev(x: torch.Tensor, scale_ptr: int, order: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """split_f16x3 with the scale read from device memory."""
+    lib = _lib.load()
+    _f32(x, "x")
+    if x.dim() != 2:
+        raise ValueError("split_f16x3_dev: x must be 2-D")
+    rows, cols = x.shape
+    if out is not None:
+        if tuple(_f16(out, "out").shape) != (rows, 3 * cols):
+            raise ValueError(f"split_f16x3_dev: out shape {tuple(out.shape)} != {(rows, 3 * cols)}")
+        y = out
+    else:
+        y = torch.empty((rows, 3 * cols), dtype=torch.float16, device=x.device)
+    _lib.check(lib.dclip_split_f32_f16x3_dev(x.data_ptr(), y.data_ptr(), rows, cols, cols, 3 * cols, scale_ptr, int(order),
+                                             _stream()), "split_f32_f16x3_dev")
+    return y
+
+
+def layernorm_fwd_f16x3_dev(x, gamma, beta, eps: float, scale_ptr: int, save: bool = False):
+    """layernorm_fwd_f16x3 with the scale read from device memory -> (y3, y, mean, rstd); with `save`, y / mean / rstd are what
+    layernorm_fwd returns (bit for bit), otherwise None."""
+    lib = _lib.load()
+    _f32(x, "x"), _f32(gamma, "gamma"), _f32(beta, "beta")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    if gamma.numel() != D or beta.numel() != D:
+        raise ValueError("layernorm_fwd_f16x3_dev: gamma/beta size")
+    y3 = torch.empty((rows, 3 * D), dtype=torch.float16, device=x.device)
+    y = torch.empty_like(x) if save else None
+    mean = torch.empty((rows,), dtype=torch.float32, device=x.device) if save else None
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device) if save else None
+    _lib.check(lib.dclip_layernorm_fwd_f16x3_dev(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y3.data_ptr(), _ptr(y), _ptr(mean),
+                                                 _ptr(rstd), rows, D, float(eps), scale_ptr, _stream()), "layernorm_fwd_f16x3_dev")
+    return y3, y, mean, rstd
+
+
+def gemm_f16_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, *, bias: Optional[torch.Tensor] = None,
+                 residual: Optional[torch.Tensor] = None, gelu: bool = False, out_f16: bool = False,
+                 split_out_scale_ptr: Optional[int] = None, h32: Optional[torch.Tensor] = None,
+                 g32: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemm_f16(alpha=..., split_out_scale=...) with both scales read from device memory.  With a split output, `h32` / `g32`
+    [M, N] fp32 also receive the pre-activation (gelu only) and the result."""
+    lib = _lib.load()
+    _f16(a, "a"), _f16(w, "w")
+    M, lda = a.shape
+    N, ldw = w.shape
+    K = min(lda, ldw)
+    epi = 0
+    if bias is not None:
+        epi |= EPI_BIAS
+        if _f32(bias, "bias").numel() != N:
+            raise ValueError("gemm_f16_dev: bias size")
+    if gelu:
+        epi |= EPI_GELU
+    if residual is not None:
+        epi |= EPI_RESIDUAL
+        if tuple(_f32(residual, "residual").shape) != (M, N):
+            raise ValueError("gemm_f16_dev: residual shape")
+    if split_out_scale_ptr is not None:
+        if residual is not None or out_f16:
+            raise ValueError("gemm_f16_dev: a split output takes bias / gelu only")
+        for t, nm in ((h32, "h32"), (g32, "g32")):
+            if t is not None and tuple(_f32(t, nm).shape) != (M, N):
+                raise ValueError(f"gemm_f16_dev: {nm} shape")
+        if h32 is not None and not gelu:
+            raise ValueError("gemm_f16_dev: h32 is the pre-activation of a gelu epilogue")
+        y3 = torch.empty((M, 3 * N), dtype=torch.float16, device=a.device)
+        _lib.check(lib.dclip_gemm_f16_scaled_split_dev(a.data_ptr(), w.data_ptr(), y3.data_ptr(), _ptr(bias), _ptr(h32), _ptr(g32), M, N,
+                                                       K, lda, ldw, 3 * N, epi, alpha_ptr, split_out_scale_ptr, _stream()),
+                   "gemm_f16_scaled_split_dev")
+        return y3
+    if g32 is not None:
+        raise ValueError("gemm_f16_dev: g32 goes with a split output")
+    out = torch.empty((M, N), dtype=torch.float16 if out_f16 else torch.float32, device=a.device)
+    if h32 is not None:      # fp32 result and fp32 pre-activation, no split
+        if not gelu or residual is not None or out_f16 or tuple(_f32(h32, "h32").shape) != (M, N) or N % 8:
+            raise ValueError("gemm_f16_dev: h32 [M, N] is the pre-activation of a bias / gelu epilogue with an fp32 result")
+        _lib.check(lib.dclip_gemm_f16_scaled_split_dev(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), h32.data_ptr(), None, M,
+                                                       N, K, lda, ldw, N, epi, alpha_ptr, None, _stream()),
+                   "gemm_f16_scaled_split_dev")
+        return out
+    _lib.check(lib.dclip_gemm_f16_scaled_dev(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual), M, N, K, lda, ldw,
+                                             N, epi, int(out_f16), alpha_ptr, _stream()), "gemm_f16_scaled_dev")
+    return out
+
+
+SPLIT16_STATS = ("ln1_w", "ln1_b", "v_l1", "v_b", "ln2_w", "ln2_b", "fc1_l1", "fc1_b", "qkv", "out", "fc1", "fc2")
+SPLIT16_PLAN_ACT = {"ln1": 0, "ctx": 1, "ln2": 2, "g": 3}          # floats of a plan record: activation scales,
+SPLIT16_PLAN_W = {"qkv": 4, "out": 5, "fc1": 6, "fc2": 7}          # weight scales,
+SPLIT16_PLAN_ALPHA = {"qkv": 8, "out": 9, "fc1": 10, "fc2": 11}    # alphas; 12 = flags, 16..27 = the statistics
+SPLIT16_PLAN_FLAGS, SPLIT16_PLAN_STATS = 12, 16
+
+
+def split16_table(layers):
+    """The device state of split16_refresh for encoder layers given as dicts of fp32 tensors ln1_w, ln1_b, qkv_w [3D, D],
+    qkv_b, out_w, ln2_w, ln2_b, fc1_w, fc1_b, fc2_w (widths multiples of 8): the record table, the statistics accumulators,
+    the plan [L, 32] fp32, and per layer the [hi|hi|lo] fp16 copies {"qkv", "out", "fc1", "fc2"}.  One synchronous upload:
+    build it once, outside graph capture."""
+    import struct
+    lib = _lib.load()
+    assert lib.dclip_split16_record_bytes() == 48
+    nplan, trows = lib.dclip_split16_plan_floats(), lib.dclip_split16_tile_rows()
+    slot = {n: i for i, n in enumerate(SPLIT16_STATS)}
+    mats, vecs, copies = [], [], []            # the matrices come first in the table: the weight-split launch covers only them
+    dev = layers[0]["qkv_w"].device
+
+    def rec(li, src, rows, cols, max_slot, l1_slot=-1, l1_row0=0, dst=None, scale_slot=-1):
+        if cols % 8 or src.data_ptr() % 16:
+            raise ValueError("split16_table: widths must be multiples of 8 and tensors 16-byte aligned")
+        (vecs if dst is None else mats).append((src.data_ptr(), _ptr(dst) or 0, rows, cols, li, max_slot, l1_slot, l1_row0, scale_slot))
+
+    for li, L in enumerate(layers):
+        for n in ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w"):
+            _f32(L[n], n)
+        D = L["ln1_w"].numel()
+        if tuple(L["qkv_w"].shape) != (3 * D, D) or L["qkv_b"].numel() != 3 * D:
+            raise ValueError("split16_table: qkv_w must be [3D, D]")
+        w = {}
+        for short in ("qkv", "out", "fc1", "fc2"):
+            src = L[short + "_w"]
+            w[short] = torch.empty((src.shape[0], 3 * src.shape[1]), dtype=torch.float16, device=dev)
+        copies.append(w)
+        vb = L["qkv_b"][2 * D:]                # an address inside qkv_b: the caller re-builds the table when a tensor moves
+        for n in ("ln1_w", "ln1_b", "ln2_w", "ln2_b", "fc1_b"):
+            rec(li, L[n], 1, L[n].numel(), slot[n])
+        rec(li, vb, 1, D, slot["v_b"])
+        rec(li, L["qkv_w"], 3 * D, D, slot["qkv"], slot["v_l1"], 2 * D, w["qkv"], SPLIT16_PLAN_W["qkv"])
+        rec(li, L["out_w"], L["out_w"].shape[0], L["out_w"].shape[1], slot["out"], dst=w["out"], scale_slot=SPLIT16_PLAN_W["out"])
+        rec(li, L["fc1_w"], L["fc1_w"].shape[0], L["fc1_w"].shape[1], slot["fc1"], slot["fc1_l1"], 0, w["fc1"], SPLIT16_PLAN_W["fc1"])
+        rec(li, L["fc2_w"], L["fc2_w"].shape[0], L["fc2_w"].shape[1], slot["fc2"], dst=w["fc2"], scale_slot=SPLIT16_PLAN_W["fc2"])
+    blob, t0, wtiles = [], 0, 0
+    for r in mats + vecs:
+        blob.append(struct.pack("<QQiiiiiiii", *r, t0))
+        t0 += (r[2] + trows - 1) // trows
+        if r[1]:
+            wtiles = t0
+    table = torch.frombuffer(bytearray(b"".join(blob)), dtype=torch.uint8).to(dev)
+    return {"table": table, "nrefs": len(blob), "tiles": t0, "wrefs": len(mats), "wtiles": wtiles, "w": copies, "L": len(layers),
+            "D": layers[0]["ln1_w"].numel(),
+            "stats": torch.zeros((len(layers), len(SPLIT16_STATS)), dtype=torch.int32, device=dev),
+            "plan": torch.zeros((len(layers), nplan), dtype=torch.float32, device=dev)}
+
+
+def split16_refresh(tab) -> None:
+    """Statistics, plan and weight split of a split16_table from the CURRENT weights: three launches, nothing read back."""
+    lib = _lib.load()
+    st = _stream()
+    _lib.check(lib.dclip_split16_stats(tab["table"].data_ptr(), tab["nrefs"], tab["tiles"], tab["stats"].data_ptr(), st),
+               "split16_stats")
+    _lib.check(lib.dclip_split16_plan(tab["stats"].data_ptr(), tab["plan"].data_ptr(), tab["L"], tab["D"], st), "split16_plan")
+    _lib.check(lib.dclip_split16_weights(tab["table"].data_ptr(), tab["wrefs"], tab["wtiles"], tab["plan"].data_ptr(), st),
+               "split16_weights")
+
+
 # ------------------------------------------------------------------------------------------- fp16 training path
 # The bf16 training wrappers above with fp16 tensors (include/dclip_hip.h, "fp16 TRAINING path"): same shapes and limits,
 # IEEE rounding — a value beyond +-65504 becomes +-inf (the frozen fp16 wrappers above saturate), so that the overflow of a

@@ -527,6 +527,41 @@ int dclip_gemm_f16_scaled_split(const void* A, const void* W, void* C, const flo
                                 int ldc, int epilogue, float alpha, float out_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The split-fp16 entries above for a tower whose weights CHANGE every step (the student's vision forward,
+ * DCLIP_VISION_SPLIT16): the scales live in DEVICE memory, are recomputed there from the weights, and are read
+ * through pointers, so that no host value goes stale in a captured graph and nothing is read back.
+ *   *_dev                the entry of the same name with `const float*` (device) where it takes a float; same kernels, every
+ *                        output bit-equal at equal scales.  layernorm_fwd_f16x3_dev may also write dclip_layernorm_fwd's fp32
+ *                        output y32 and row statistics (each may be NULL), bit for bit; gemm_f16_scaled_split_dev may also
+ *                        write the fp32 result g32 [M][N] and, with GELU, the fp32 pre-activation h32 [M][N] (each may be
+ *                        NULL), bit-equal to gemm_f16_scaled's output for that epilogue; with out_scale NULL there is no split
+ *                        and C is the fp32 result [M][ldc] itself (g32 NULL), h32 as before.
+ *   split16_stats        one launch over a table of `nrefs` records (split16_record_bytes each: src, dst, int rows, cols, layer,
+ *                        max_slot, l1_slot, l1_row0, scale_slot, tile0; tiles of split16_tile_rows rows, `tiles` in
+ *                        all): max|x| and the largest row L1 norm per record into stats, uint32 [layers][12] (bit patterns of
+ *                        non-negative floats; zero before the first call).  The same value in every run.
+ *   split16_plan         stats -> plan, float [layers][split16_plan_floats]: [0..3] activation scales 2^e (ln1, ctx, ln2, g),
+ *                        [4..7] weight scales 2^f (qkv, out, fc1, fc2), [8..11] alpha = 2^-(e+f), [12] flag bits (1: an e below
+ *                        -14, 2: a non-finite statistic, 4: a scale clamped to fp32's range), [16..27] the statistics; clears
+ *                        stats.  Exponents by the host rules (engine.split16_*), evaluated in double.
+ *   split16_weights      the [hi|hi|lo] split of src * (its plan scale) for every record with a dst, one launch. */
+int dclip_split_f32_f16x3_dev(const float* x, void* y, int rows, int cols, int ldx, int ldy, const float* scale, int order,
+                              void* stream);
+int dclip_layernorm_fwd_f16x3_dev(const float* x, const float* gamma, const float* beta, void* y, float* y32, float* mean,
+                                  float* rstd, int rows, int D, float eps, const float* scale, void* stream);
+int dclip_gemm_f16_scaled_dev(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
+                              int lda, int ldw, int ldc, int epilogue, int out_f16, const float* alpha, void* stream);
+int dclip_gemm_f16_scaled_split_dev(const void* A, const void* W, void* C, const float* bias, float* h32, float* g32, int M, int N,
+                                    int K, int lda, int ldw, int ldc, int epilogue, const float* alpha, const float* out_scale,
+                                    void* stream);
+int dclip_split16_record_bytes(void);
+int dclip_split16_plan_floats(void);
+int dclip_split16_tile_rows(void);
+int dclip_split16_stats(const void* refs, int nrefs, int tiles, void* stats, void* stream);
+int dclip_split16_plan(void* stats, float* plan, int nlayers, int D, void* stream);
+int dclip_split16_weights(const void* refs, int nrefs, int tiles, const float* plan, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * fp16 TRAINING path (opt-in student_precision="fp16" / get_image_features(precision="fp16-mixed")): fp16
  * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
  * a finite value beyond +-65504 becomes +-inf (it does NOT saturate as the frozen fp16 entries do), NaN stays NaN, so the
