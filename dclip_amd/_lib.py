@@ -131,6 +131,9 @@ SIGNATURES = {
     "dclip_split16_stats": (I, [P, I, I, P, P]),
     "dclip_split16_plan": (I, [P, P, I, I, P]),
     "dclip_split16_weights": (I, [P, I, I, P, P]),
+    "dclip_split_f32_f16x3_rows": (I, [P, P, P, I, I, I, P]),
+    "dclip_split16_weights_t": (I, [P, I, I, P, P, P]),
+    "dclip_gemm_f16_scaled_rows_dev": (I, [P, P, P, P, I, I, I, I, I, I, I, P, P, P]),
     "dclip_gemm_f16_ex": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "dclip_gemm_f16_wgrad_tokmajor_plan": (I, [I, I, I]),
     "dclip_gemm_f16_wgrad_tokmajor": (I, [P, P, P, I, I, I, I, I, I, I, P, Z, P]),

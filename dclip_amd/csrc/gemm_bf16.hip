@@ -48,7 +48,22 @@ struct GemmBf16Params {
   const float* out_scale_p = nullptr;  // non-null (out_scale != 0 marks the split output): out_scale = *out_scale_p
   float* h32 = nullptr;                // split output: also the fp32 pre-activation (GELU) [M][N], or nullptr
   float* g32 = nullptr;                // split output: also the fp32 result [M][N], or nullptr
+  // row-scaled form (dclip_gemm_f16_scaled_rows_dev, the split-fp16 dgrads of DESIGN.md §9e; the ROWS kernel instances only)
+  const float* row_alpha = nullptr;    // [M]: C[m][:] = epi(acc * alpha * row_alpha[m]), fp32 output
+  const float* aux32 = nullptr;        // fp32 [M][ldc]: the pre-activation h of DGELU (the 16-bit `aux` is not used)
 };
+
+// The ROWS epilogue of the register-staged and LDS-DMA kernels: v = acc * alpha for 4 columns of row `row`; x row_alpha, then
+// gemm_f32_kernel's EPI_DGELU statement on the fp32 h, one 16-byte store.
+__device__ __forceinline__ void store_rows4(const GemmBf16Params& p, f32x4 v, int row, size_t off) {
+  v = v * p.row_alpha[row];
+  if (p.epilogue & DCLIP_EPI_DGELU) {
+    const f32x4 h = *reinterpret_cast<const f32x4*>(p.aux32 + off);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(h[e]);
+  }
+  *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + off) = v;
+}
 
 __device__ __forceinline__ float dev_alpha(const GemmBf16Params& p) { return p.alpha_p ? *p.alpha_p : p.alpha; }
 __device__ __forceinline__ float dev_out_scale(const GemmBf16Params& p) { return p.out_scale_p ? *p.out_scale_p : p.out_scale; }
@@ -107,7 +122,7 @@ __device__ __forceinline__ int xcd_remap16(int bid, int nwg) {
   return base + i;
 }
 
-template <class T, int BM, int BN>
+template <class T, int BM, int BN, bool ROWS = false>
 __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
   typedef typename T::x8 V8;
   constexpr int WM = 2, WN = 2;
@@ -276,6 +291,10 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
       continue;
     }
     v = v * dev_alpha(p);
+    if (ROWS) {
+      store_rows4(p, v, row, (size_t)row * p.ldc + col);
+      continue;
+    }
     if (p.epilogue & DCLIP_EPI_BIAS) v += *reinterpret_cast<const f32x4*>(p.bias + col);
     const size_t off = (size_t)row * p.ldc + col;
     if (p.epilogue & DCLIP_EPI_GELU) {
@@ -326,7 +345,7 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, __bf16* lds_d
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
 }
 
-template <class T, int BM, int BN, int WM, int WN>
+template <class T, int BM, int BN, int WM, int WN, bool ROWS = false>
 __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Params p) {
   typedef typename T::x8 V8;
   constexpr int NW = WM * WN, NTHR = NW * 64;
@@ -463,6 +482,10 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Par
       const int row = m0 + hm * PROWS + lr, col = n0 + lc;
       if (row >= p.M || col >= p.N) continue;
       f32x4 v = *reinterpret_cast<const f32x4*>(ct + lr * BN + lc) * dev_alpha(p);
+      if (ROWS) {
+        store_rows4(p, v, row, (size_t)row * p.ldc + col);
+        continue;
+      }
       if (p.epilogue & DCLIP_EPI_BIAS) v += *reinterpret_cast<const f32x4*>(p.bias + col);
       const size_t off = (size_t)row * p.ldc + col;
       if (p.epilogue & DCLIP_EPI_GELU) {
@@ -500,7 +523,26 @@ template <class T, int BM, int BN, int WM, int WN>
 int launch_dma(GemmBf16Params p, hipStream_t st) {
   p.tiles_m = cdiv(p.M, BM);
   p.tiles_n = cdiv(p.N, BN);
+  if constexpr (std::is_same<T, F16T>::value) {   // the row-scaled entry exists for F16T only
+    if (p.row_alpha) {
+      hipLaunchKernelGGL((gemm_bf16_dma_kernel<T, BM, BN, WM, WN, true>), dim3(p.tiles_m * p.tiles_n), dim3(WM * WN * 64), 0, st, p);
+      return DCLIP_OK;
+    }
+  }
   hipLaunchKernelGGL((gemm_bf16_dma_kernel<T, BM, BN, WM, WN>), dim3(p.tiles_m * p.tiles_n), dim3(WM * WN * 64), 0, st, p);
+  return DCLIP_OK;
+}
+
+// the register-staged kernel on BM x BM tiles (p.tiles_m / tiles_n set by the caller), its ROWS instance for a row-scaled call
+template <class T, int BM>
+int launch_reg(const GemmBf16Params& p, size_t lds, hipStream_t st) {
+  if constexpr (std::is_same<T, F16T>::value) {   // the row-scaled entry exists for F16T only
+    if (p.row_alpha) {
+      hipLaunchKernelGGL((gemm_bf16_kernel<T, BM, BM, true>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
+      return DCLIP_OK;
+    }
+  }
+  hipLaunchKernelGGL((gemm_bf16_kernel<T, BM, BM>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
   return DCLIP_OK;
 }
 
@@ -521,7 +563,9 @@ int launch_dma(GemmBf16Params p, hipStream_t st) {
 // C[row 16 i + l15][column 16 j + 4 quad + r] — four consecutive columns per lane, one ds_write_b128 per block.
 // DEV (dclip_gemm_f16_scaled_dev / _split_dev): alpha and out_scale are read through p.alpha_p / p.out_scale_p and the fp32
 // side outputs h32 / g32 are written; a kernel instance of its own, so that the code of every other caller is what it was.
-template <class T, int KIND, bool OUT16, bool DEV = false>
+// ROWS (dclip_gemm_f16_scaled_rows_dev; KIND 0 or 2, fp32 output, DEV): the kernel has already multiplied the accumulators by
+// alpha and row_alpha (see there); KIND 2's side operand is the fp32 h (p.aux32) — gemm_f32_kernel's EPI_DGELU statement.
+template <class T, int KIND, bool OUT16, bool DEV = false, bool ROWS = false>
 __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4 (&acc)[8][4], float* ct, int m0, int n0,
                                             int tid, int wr, int wc, int quad, int l15) {
   constexpr int BN = 256;
@@ -534,14 +578,19 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
 #pragma unroll
   for (int hm = 0; hm < 2; ++hm) {
     const int rbase = m0 + hm * 128 + lr0;
-    f32x4 side[KIND == 3 ? 16 : 1];
-    u16x4 side16[KIND == 2 ? 16 : 1];
+    f32x4 side[KIND == 3 || (ROWS && KIND == 2) ? 16 : 1];
+    u16x4 side16[KIND == 2 && !ROWS ? 16 : 1];
+    if (ROWS && KIND == 2) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q)
+        side[q] = *reinterpret_cast<const f32x4*>(p.aux32 + (size_t)min(rbase + 8 * q, p.M - 1) * p.ldc + colc);
+    }
     if (KIND == 3) {
 #pragma unroll
       for (int q = 0; q < 16; ++q)
         side[q] = *reinterpret_cast<const f32x4*>(p.residual + (size_t)min(rbase + 8 * q, p.M - 1) * p.ldc + colc);
     }
-    if (KIND == 2) {
+    if (KIND == 2 && !ROWS) {
 #pragma unroll
       for (int q = 0; q < 16; ++q)
         side16[q] = *reinterpret_cast<const u16x4*>(p.aux + (size_t)min(rbase + 8 * q, p.M - 1) * p.ldc + colc);
@@ -558,9 +607,18 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const int row = rbase + 8 * q;
-      f32x4 v = *reinterpret_cast<const f32x4*>(ct + (lr0 + 8 * q) * BN + (((tid & 63) ^ ((lr0 + 8 * q) & 7)) << 2)) * (DEV ? alpha_d : p.alpha) + bias4;
+      f32x4 v = *reinterpret_cast<const f32x4*>(ct + (lr0 + 8 * q) * BN + (((tid & 63) ^ ((lr0 + 8 * q) & 7)) << 2));
+      if (!ROWS) v = v * (DEV ? alpha_d : p.alpha) + bias4;   // ROWS: the kernel has scaled the accumulators, and there is no bias
       const size_t off = (size_t)row * p.ldc + col;
       const bool ok = row < p.M && colok;
+      if (ROWS) {
+        if (KIND == 2) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(side[q][e]);
+        }
+        if (ok) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + off) = v;
+        continue;
+      }
       if (KIND == 1) {
         if (DEV && !OUT16 && p.h32 && ok) *reinterpret_cast<f32x4*>(p.h32 + (size_t)row * p.N + col) = v;
         if (p.aux) {
@@ -699,7 +757,7 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 // two lane groups of a half-wave (k-rows 8 apart) land on 32 different 8-byte bank pairs.  Same phases and barriers; the
 // DMA order is A1(kt+1) | - | A0(kt+2) | B0, B1(kt+2) (every half re-staged at least two phases after its last read, so
 // no lgkmcnt before a barrier is needed: phase 1 issues 24 reads, more than the 4-bit counter can express).
-template <class T, bool TOK, bool DEV = false>
+template <class T, bool TOK, bool DEV = false, bool ROWS = false>
 __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   typedef typename T::x8 V8;
   constexpr int BM = 256, BN = 256, ROW = BKH;
@@ -923,6 +981,21 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   // ---- epilogue (pp_epilogue above), one instance per epilogue kind and output type
   const int kind = (p.epilogue & DCLIP_EPI_RESIDUAL) ? 3 : (p.epilogue & DCLIP_EPI_DGELU) ? 2 : (p.epilogue & DCLIP_EPI_GELU) ? 1 : 0;
   float* ct = reinterpret_cast<float*>(lds_raw);
+  if (ROWS) {             // row-scaled dgrad: fp32 output, no epilogue or DGELU on the fp32 h
+    // both scales are applied to the accumulators HERE, in the order of the other kernels — (acc * alpha) * row_alpha — with
+    // the 8 row_alpha values of a lane fetched before any side operand: 16 more registers inside pp_epilogue would spill
+    const float alpha_r = *p.alpha_p;
+    float ra[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ra[i] = p.row_alpha[min(m0 + 128 * wr + 16 * i + l15, p.M - 1)];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = (acc[i][j] * alpha_r) * ra[i];
+    if (kind == 2) pp_epilogue<T, 2, false, true, true>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else pp_epilogue<T, 0, false, true, true>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    return;
+  }
   if (!DEV && p.slab) {   // split-K partial: raw accumulators into this split's [M][N] slab, the reduce kernel finishes
     GemmBf16Params ps = p;
     ps.C = p.slab + (size_t)blockIdx.y * p.M * p.N;
@@ -1306,6 +1379,10 @@ int launch_pp(GemmBf16Params p, hipStream_t st, int splits = 1) {
   p.tiles_m = cdiv(p.M, 256);
   p.tiles_n = cdiv(p.N, 256);
   if constexpr (std::is_same<T, F16T>::value && !TOK) {   // the device-scaled entries exist for F16T only
+    if (p.row_alpha) {
+      hipLaunchKernelGGL((gemm_bf16_pp_kernel<T, false, true, true>), dim3(p.tiles_m * p.tiles_n, splits), dim3(512), 0, st, p);
+      return DCLIP_OK;
+    }
     if (p.alpha_p) {
       hipLaunchKernelGGL((gemm_bf16_pp_kernel<T, false, true>), dim3(p.tiles_m * p.tiles_n, splits), dim3(512), 0, st, p);
       return DCLIP_OK;
@@ -1436,9 +1513,12 @@ struct DevScales {
   const float* out_scale_p;
   float* h32;
   float* g32;
+  const float* row_alpha = nullptr;   // dclip_gemm_f16_scaled_rows_dev
+  const float* aux32 = nullptr;
 };
 inline void set_dev(GemmBf16Params& p, const DevScales* d) {
-  if (d) p.alpha_p = d->alpha_p, p.out_scale_p = d->out_scale_p, p.h32 = d->h32, p.g32 = d->g32;
+  if (d) p.alpha_p = d->alpha_p, p.out_scale_p = d->out_scale_p, p.h32 = d->h32, p.g32 = d->g32, p.row_alpha = d->row_alpha,
+         p.aux32 = d->aux32;
 }
 
 // The forward dispatcher of both 16-bit types: same checks, same plan.  Every kernel it can pick — register-staged 128x128 /
@@ -1457,7 +1537,8 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
                 "%s: unsupported epilogue bits", name);
   DCLIP_REQUIRE(out_scale == 0.f || (!out_bf16 && !aux && !(epilogue & (DCLIP_EPI_RESIDUAL | DCLIP_EPI_DGELU)) && (long)ldc >= 3L * N),
                 "%s: a split output takes BIAS | GELU only and ldc >= 3 N", name);
-  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (aux && !(epilogue & DCLIP_EPI_GELU)), "%s: DGELU needs aux (and no GELU)", name);
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || ((aux || (dev && dev->aux32)) && !(epilogue & DCLIP_EPI_GELU)),
+                "%s: DGELU needs aux (and no GELU)", name);
   DCLIP_REQUIRE(!aux || (uintptr_t)aux % 8 == 0, "%s: aux must be 8-byte aligned", name);
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_BIAS) || bias, "%s: BIAS without bias", name);
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_RESIDUAL) || (residual && !out_bf16), "%s: RESIDUAL needs an fp32 output", name);
@@ -1517,8 +1598,8 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
                    cdiv(M, bm), cdiv(N, bn), (unsigned short*)aux, 0, nullptr, alpha, out_scale};
   set_dev(p, dev);
   const size_t lds = (size_t)2 * (bm + bn) * BKH * 2;
-  if (small) hipLaunchKernelGGL((gemm_bf16_kernel<T, 64, 64>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((gemm_bf16_kernel<T, 128, 128>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds, st, p);
+  if (small) launch_reg<T, 64>(p, lds, st);
+  else launch_reg<T, 128>(p, lds, st);
   DCLIP_CHECK_LAUNCH_V(name, small ? ".r64" : ".r128");
   return DCLIP_OK;
 }
@@ -1589,6 +1670,26 @@ DCLIP_API int dclip_gemm_f16_scaled_split_dev(const void* A, const void* W, void
   const DevScales dev{alpha, out_scale, h32, g32};
   return gemm16<F16T>("gemm_f16_scaled_split_dev", A, W, C, bias, nullptr, nullptr, M, N, K, lda, ldw, ldc, epilogue, 0, stream, 1.f,
                       out_scale ? 1.f : 0.f, &dev);
+}
+
+// dclip_gemm_f16_scaled_dev for the data-gradient GEMMs of the split-fp16 backward: A is the [hi|lo|hi] split of
+// dY with ONE power-of-two scale PER ROW (dclip_split_f32_f16x3_rows), so the accumulator of row m is scaled back by
+// row_alpha[m] as well:  C[m][n] = epi((acc * *alpha) * row_alpha[m]),  fp32.  epilogue 0, or DCLIP_EPI_DGELU with the fp32
+// pre-activation aux32 [M][ldc] (gemm_f32's statement: at equal accumulators the outputs are bit-equal).  With row_alpha == 1
+// everywhere the output is dclip_gemm_f16_scaled_dev's bit for bit.  Every kernel of the dispatcher except the persistent one.
+DCLIP_API int dclip_gemm_f16_scaled_rows_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K, int lda,
+                                             int ldw, int ldc, int epilogue, const float* alpha, const float* row_alpha,
+                                             void* stream) {
+  DCLIP_REQUIRE(alpha && row_alpha && ((uintptr_t)alpha | (uintptr_t)row_alpha) % 4 == 0,
+                "gemm_f16_scaled_rows_dev: alpha / row_alpha must be device pointers");
+  DCLIP_REQUIRE(epilogue == 0 || epilogue == DCLIP_EPI_DGELU, "gemm_f16_scaled_rows_dev: the epilogue is none or DGELU");
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (aux32 && (uintptr_t)aux32 % 16 == 0),
+                "gemm_f16_scaled_rows_dev: DGELU needs a 16-byte aligned fp32 aux32");
+  DevScales dev{alpha, nullptr, nullptr, nullptr};
+  dev.row_alpha = row_alpha;
+  dev.aux32 = (epilogue & DCLIP_EPI_DGELU) ? aux32 : nullptr;
+  return gemm16<F16T>("gemm_f16_scaled_rows_dev", A, W, C, nullptr, nullptr, nullptr, M, N, K, lda, ldw, ldc, epilogue, 0, stream, 1.f,
+                      0.f, &dev);
 }
 
 // fp16 TRAINING path: dclip_gemm_bf16_ex's arguments, epilogues and limits with fp16 A / W / aux / 16-bit C, IEEE rounding

@@ -53,6 +53,100 @@ __global__ void __launch_bounds__(256) split_f16x3_kernel(const float* __restric
   }
 }
 
+__device__ __forceinline__ float pow2f(int e) {      // 2^e, e clamped to the normal range
+  e = e < -126 ? -126 : (e > 127 ? 127 : e);
+  return __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
+}
+
+// Row-scaled split for the data-gradient GEMMs of the backward: dY has no bound derivable from the weights, so
+// every ROW m gets its own power of two, taken from the data in the same pass.  r = max|x[m,:]| = mu 2^x (mu in [0.5, 1)):
+// e_m = 14 - x clamped to [-100, 100] (r 2^e_m in [2^13, 2^14); 2^e_m, 2^-e_m and their products with a weight alpha stay
+// normal fp32), e_m = 0 when r is 0 or not finite.  y[m] = [hi|lo|hi] of x[m] 2^e_m, row_alpha[m] = 2^-e_m.  A non-finite row
+// yields non-finite pieces (and so a non-finite output row of the GEMM, as fp32 would); other rows are unaffected.
+// One wave per row.  NC > 0: the row (cols <= 512 NC) is held in registers between the maximum and the split, read from
+// memory ONCE; NC == 0 (any width): two loops over the row, the second read served by the cache.  The maximum is taken on the
+// bit patterns of |x| (NaN above inf), lane-local in column order, then the xor tree: the same in every run.
+__device__ __forceinline__ unsigned wave_umax_bits(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned w = (unsigned)__shfl_xor((int)v, o, 64);
+    v = v > w ? v : w;
+  }
+  return v;
+}
+
+__device__ __forceinline__ unsigned absmax8(unsigned m, const f32x4& a, const f32x4& b) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float fa = a[e], fb = b[e];   // a copy first: a bit cast of the vector ELEMENT itself reads element 0 whatever e is
+    const unsigned ua = __builtin_bit_cast(unsigned, fa) & 0x7fffffffu, ub = __builtin_bit_cast(unsigned, fb) & 0x7fffffffu;
+    m = m > ua ? m : ua;
+    m = m > ub ? m : ub;
+  }
+  return m;
+}
+
+// engine.split16_row_exp on the bit pattern of r = max|x| >= 0
+__device__ __forceinline__ int row_exp(unsigned rbits) {
+  if (rbits == 0u || rbits >= 0x7f800000u) return 0;
+  const int e = 14 - ((int)(rbits >> 23) - 126);        // a subnormal r (biased exponent 0) asks for more than the clamp
+  return e < -100 ? -100 : (e > 100 ? 100 : e);
+}
+
+__device__ __forceinline__ void split_store8(unsigned short* yr, int cols, const f32x4& a, const f32x4& b, float scale) {
+  u16x8 hi, lo;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    unsigned short h0, l0, h1, l1;
+    split1(a[e] * scale, h0, l0);
+    split1(b[e] * scale, h1, l1);
+    hi[e] = h0, lo[e] = l0, hi[4 + e] = h1, lo[4 + e] = l1;
+  }
+  *reinterpret_cast<u16x8*>(yr) = hi;
+  *reinterpret_cast<u16x8*>(yr + cols) = lo;
+  *reinterpret_cast<u16x8*>(yr + 2 * cols) = hi;
+}
+
+template <int NC>
+__global__ void __launch_bounds__(256) split_rows_f16x3_kernel(const float* __restrict__ x, unsigned short* __restrict__ y,
+                                                               float* __restrict__ row_alpha, int rows, int cols, int ldx) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int c8 = cols >> 3;
+  const float* xr = x + (size_t)row * ldx;
+  unsigned short* yr = y + (size_t)row * 3 * cols;
+  unsigned m = 0u;
+  if (NC > 0) {
+    f32x4 a[NC > 0 ? NC : 1], b[NC > 0 ? NC : 1];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = lane + 64 * c, ic = i < c8 ? i : 0;       // a chunk past the row re-reads chunk 0: same maximum
+      a[c] = *reinterpret_cast<const f32x4*>(xr + ic * 8);
+      b[c] = *reinterpret_cast<const f32x4*>(xr + ic * 8 + 4);
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) m = absmax8(m, a[c], b[c]);
+    const int e = row_exp(wave_umax_bits(m));
+    const float scale = pow2f(e);
+    if (lane == 0) row_alpha[row] = pow2f(-e);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = lane + 64 * c;
+      if (i < c8) split_store8(yr + i * 8, cols, a[c], b[c], scale);
+    }
+  } else {
+    for (int i = lane; i < c8; i += 64)
+      m = absmax8(m, *reinterpret_cast<const f32x4*>(xr + i * 8), *reinterpret_cast<const f32x4*>(xr + i * 8 + 4));
+    const int e = row_exp(wave_umax_bits(m));
+    const float scale = pow2f(e);
+    if (lane == 0) row_alpha[row] = pow2f(-e);
+    for (int i = lane; i < c8; i += 64)
+      split_store8(yr + i * 8, cols, *reinterpret_cast<const f32x4*>(xr + i * 8), *reinterpret_cast<const f32x4*>(xr + i * 8 + 4),
+                   scale);
+  }
+}
+
 // ln_fwd_kernel (layernorm.hip) with the split [hi | lo | hi] of scale * LN(x) as its output, y [rows][3 D] fp16.  Loads,
 // statistics and the normalisation are that kernel's, statement for statement; the fp32 result is pinned in a register before
 // it is scaled and split, so that it is the value ln_fwd_kernel would have stored (no fusion of the affine step into the
@@ -141,7 +235,8 @@ static_assert(sizeof(Split16Ref) == 48, "Split16Ref layout");
 
 constexpr int SPLIT16_TILE_ROWS = 32;
 constexpr int PLAN_FLOATS = 32;   // per layer: [0..3] activation scales ln1 ctx ln2 g | [4..7] weight scales qkv out fc1 fc2 |
-                                  // [8..11] alphas qkv out fc1 fc2 | [12] flags | [16..27] the twelve statistics
+                                  // [8..11] alphas qkv out fc1 fc2 | [12] flags | [16..27] the twelve statistics |
+                                  // [28..31] 2^-f qkv out fc1 fc2, the alphas of the backward's data-gradient GEMMs
 constexpr int NSTAT = 12;
 
 __device__ __forceinline__ const Split16Ref& find_ref(const Split16Ref* refs, int n, int tile) {
@@ -199,11 +294,6 @@ __global__ void __launch_bounds__(256) split16_stats_kernel(const Split16Ref* __
     atomicMax(stats + t.layer * NSTAT + t.max_slot, mx);
     if (t.l1_slot >= 0) atomicMax(stats + t.layer * NSTAT + t.l1_slot, l1);
   }
-}
-
-__device__ __forceinline__ float pow2f(int e) {      // 2^e, e clamped to the normal range
-  e = e < -126 ? -126 : (e > 127 ? 127 : e);
-  return __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
 }
 
 // engine.split16_weight_exp: f with max|W| 2^f in [2^13, 2^14); 0 for an all-zero (or, flagged, a non-finite) weight
@@ -267,7 +357,7 @@ __global__ void split16_plan_kernel(unsigned* __restrict__ stats, float* __restr
   }
   rec[12] = __builtin_bit_cast(float, flags);
   rec[13] = rec[14] = rec[15] = 0.f;
-  rec[28] = rec[29] = rec[30] = rec[31] = 0.f;
+  for (int i = 0; i < 4; ++i) rec[28 + i] = pow2f(-f[i]);   // the data-gradient GEMMs' alpha: the weight scale alone (§9e)
 }
 
 // [hi|hi|lo] of src * (the plan's scale for that weight) for every record with a destination: split_f16x3_kernel<1>'s
@@ -300,6 +390,59 @@ __global__ void __launch_bounds__(256) split16_weights_kernel(const Split16Ref* 
   }
 }
 
+// split16_weights_kernel that also writes the transposed copies (a kernel of its own: the one above stays what it was).  Same
+// arithmetic, 8 columns per thread, one tile of 32 rows per workgroup, 64 columns at a time.  dst_t (one entry per record,
+// null = none): the same pieces TRANSPOSED, [cols][3 rows] = [hi|hi|lo] of (src scale)^T — the weight operand of the
+// backward's data-gradient GEMMs — through an LDS transpose, 8 rows (16 bytes) per store; rows % 8 == 0 there.
+__global__ void __launch_bounds__(256) split16_weights_t_kernel(const Split16Ref* __restrict__ refs, int nrefs,
+                                                              const float* __restrict__ plan,
+                                                              unsigned short* const* __restrict__ dst_t) {
+  constexpr int TR = SPLIT16_TILE_ROWS, LDT = TR + 8;      // LDS row of a column: 32 values + 8 of padding (80 bytes)
+  static_assert(TR == 32, "256 threads = 32 rows x 8 column groups");
+  __shared__ __attribute__((aligned(16))) unsigned short th[64 * LDT], tl[64 * LDT];
+  const int ref = (int)(&find_ref(refs, nrefs, blockIdx.x) - refs);
+  const Split16Ref t = refs[ref];
+  if (!t.dst) return;                                  // uniform
+  unsigned short* dt = dst_t ? dst_t[ref] : nullptr;   // uniform
+  const float scale = plan[(size_t)t.layer * PLAN_FLOATS + t.scale_slot];
+  const int r0 = ((int)blockIdx.x - t.tile0) * TR;
+  const int lr = threadIdx.x >> 3, cg = threadIdx.x & 7;
+  const size_t r = (size_t)(r0 + lr);
+  const bool rok = r0 + lr < t.rows;
+  for (int c0 = 0; c0 < t.cols; c0 += 64) {
+    const int c = c0 + cg * 8;
+    u16x8 hi = {0, 0, 0, 0, 0, 0, 0, 0}, lo = hi;
+    if (rok && c < t.cols) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(t.src + r * t.cols + c);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(t.src + r * t.cols + c + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        unsigned short h0, l0, h1, l1;
+        split1(a[e] * scale, h0, l0);
+        split1(b[e] * scale, h1, l1);
+        hi[e] = h0, lo[e] = l0, hi[4 + e] = h1, lo[4 + e] = l1;
+      }
+      unsigned short* yr = t.dst + r * 3 * t.cols + c;
+      *reinterpret_cast<u16x8*>(yr) = hi;
+      *reinterpret_cast<u16x8*>(yr + t.cols) = hi;
+      *reinterpret_cast<u16x8*>(yr + 2 * t.cols) = lo;
+    }
+    if (!dt) continue;                                 // uniform (a record without a transposed copy)
+    __syncthreads();                                   // the previous chunk's reads of th / tl are done
+#pragma unroll
+    for (int e = 0; e < 8; ++e) th[(cg * 8 + e) * LDT + lr] = hi[e], tl[(cg * 8 + e) * LDT + lr] = lo[e];
+    __syncthreads();
+    const int tc = threadIdx.x >> 2, rg = (threadIdx.x & 3) * 8;   // column of the chunk, 8 rows of the tile
+    if (c0 + tc < t.cols && r0 + rg < t.rows) {        // rows % 8 == 0: a group of 8 rows is inside or outside as a whole
+      const u16x8 h = *reinterpret_cast<const u16x8*>(th + tc * LDT + rg), l = *reinterpret_cast<const u16x8*>(tl + tc * LDT + rg);
+      unsigned short* yc = dt + (size_t)(c0 + tc) * 3 * t.rows + r0 + rg;
+      *reinterpret_cast<u16x8*>(yc) = h;
+      *reinterpret_cast<u16x8*>(yc + t.rows) = h;
+      *reinterpret_cast<u16x8*>(yc + 2 * t.rows) = l;
+    }
+  }
+}
+
 int split_launch(const char* name, const float* x, void* y, int rows, int cols, int ldx, int ldy, float scale,
                  const float* scale_p, int order, void* stream) {
   const size_t work = (size_t)rows * (cols / 8);
@@ -311,6 +454,29 @@ int split_launch(const char* name, const float* x, void* y, int rows, int cols, 
   else
     hipLaunchKernelGGL(split_f16x3_kernel<1>, grid, dim3(256), 0, st, x, (unsigned short*)y, rows, cols, ldx, ldy, scale, scale_p);
   DCLIP_CHECK_LAUNCH_V(name, order == 0 ? ".act" : ".weight");
+  return DCLIP_OK;
+}
+
+int split_rows_launch(const float* x, void* y, float* row_alpha, int rows, int cols, int ldx, void* stream) {
+  dim3 grid(cdiv(rows, 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned short* yy = (unsigned short*)y;
+  const int nc = cdiv(cols / 8, 64);
+  const char* variant;
+#define SPLITROWS(NC)                                                                                               \
+  do {                                                                                                              \
+    hipLaunchKernelGGL((split_rows_f16x3_kernel<NC>), grid, block, 0, st, x, yy, row_alpha, rows, cols, ldx);      \
+    variant = (NC) ? ".regs.nc" #NC : ".cached";                                                                    \
+  } while (0)
+  if (nc <= 1) SPLITROWS(1);
+  else if (nc == 2) SPLITROWS(2);
+  else if (nc == 3) SPLITROWS(3);
+  else if (nc == 4) SPLITROWS(4);
+  else if (nc == 5) SPLITROWS(5);
+  else if (nc == 6) SPLITROWS(6);
+  else SPLITROWS(0);
+#undef SPLITROWS
+  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows", variant);
   return DCLIP_OK;
 }
 
@@ -366,6 +532,17 @@ DCLIP_API int dclip_split_f32_f16x3_dev(const float* x, void* y, int rows, int c
   return split_launch("split_f32_f16x3_dev", x, y, rows, cols, ldx, ldy, 1.f, scale, order, stream);
 }
 
+// x fp32 [rows][ldx >= cols] -> y fp16 [rows][3 cols] = [hi|lo|hi] of x[m] 2^e_m and row_alpha[m] = 2^-e_m, e_m from the row's
+// own maximum (split_rows_f16x3_kernel).  One read of x for cols <= 3072 (the row stays in registers); wider rows are read twice,
+// the second time from the cache.
+DCLIP_API int dclip_split_f32_f16x3_rows(const float* x, void* y, float* row_alpha, int rows, int cols, int ldx, void* stream) {
+  DCLIP_REQUIRE(x && y && row_alpha && rows > 0 && cols > 0, "split_f32_f16x3_rows: bad arguments");
+  DCLIP_REQUIRE(cols % 8 == 0, "split_f32_f16x3_rows: cols=%d must be a multiple of 8", cols);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "split_f32_f16x3_rows: ldx must be a multiple of 4 and >= cols");
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0 && (uintptr_t)row_alpha % 4 == 0, "split_f32_f16x3_rows: alignment");
+  return split_rows_launch(x, y, row_alpha, rows, cols, ldx, stream);
+}
+
 DCLIP_API int dclip_layernorm_fwd_f16x3(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,
                                         float eps, float scale, void* stream) {
   DCLIP_REQUIRE(x && gamma && beta && y, "layernorm_fwd_f16x3: null pointer");
@@ -416,5 +593,16 @@ DCLIP_API int dclip_split16_weights(const void* refs, int nrefs, int tiles, cons
   DCLIP_REQUIRE(refs && plan && nrefs > 0 && tiles > 0, "split16_weights: bad arguments");
   hipLaunchKernelGGL(split16_weights_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, (const Split16Ref*)refs, nrefs, plan);
   DCLIP_CHECK_LAUNCH("split16_weights");
+  return DCLIP_OK;
+}
+
+// dclip_split16_weights that also writes, in the same launch and from the same plan scale, the TRANSPOSED copies: dst_t is a
+// device array of nrefs pointers, entry i = fp16 [cols][3 rows] for record i ([hi|hi|lo] of (src scale)^T, bit-equal to
+// dclip_split_f32_f16x3 of the transposed weight) or null; records with one need rows % 8 == 0 (the caller's check).
+DCLIP_API int dclip_split16_weights_t(const void* refs, int nrefs, int tiles, const float* plan, const void* dst_t, void* stream) {
+  DCLIP_REQUIRE(refs && plan && dst_t && nrefs > 0 && tiles > 0, "split16_weights_t: bad arguments");
+  hipLaunchKernelGGL(split16_weights_t_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, (const Split16Ref*)refs, nrefs, plan,
+                     (unsigned short* const*)dst_t);
+  DCLIP_CHECK_LAUNCH_V("split16_weights", ".t");
   return DCLIP_OK;
 }

@@ -47,16 +47,19 @@ class Split16Layer:
     """One layer's view of a tower's device-side split-fp16 plan (_vision_split16_plan): the [hi|hi|lo] fp16
     copies of its four GEMM weights and the ADDRESSES of its scales in the plan record.  Handed to layer_fwd /
     last_layer_fwd_cls as `sp`: their full-size GEMMs then run on the fp16 MFMAs with split operands; None = plain fp32."""
-    __slots__ = ("w", "base")
+    __slots__ = ("w", "base", "wt")
 
-    def __init__(self, w: Dict[str, torch.Tensor], base: int):
-        self.w, self.base = w, base
+    def __init__(self, w: Dict[str, torch.Tensor], base: int, wt: Optional[Dict[str, torch.Tensor]] = None):
+        self.w, self.base, self.wt = w, base, wt      # wt: the transposed copies, for the backward's dgrads (§9e)
 
     def act(self, name: str) -> int:
         return self.base + 4 * ops.SPLIT16_PLAN_ACT[name]
 
     def alpha(self, name: str) -> int:
         return self.base + 4 * ops.SPLIT16_PLAN_ALPHA[name]
+
+    def walpha(self, name: str) -> int:
+        return self.base + 4 * ops.SPLIT16_PLAN_WALPHA[name]
 
 
 # The three steps of a layer schedule that differ between the plain fp32 path (sp None) and the split-fp16 one: each returns
@@ -140,22 +143,35 @@ def _ln_bwd(dy, x, gamma, mean, rstd, dresidual, want: bool, gr, wkey: str, bkey
     return dx
 
 
-def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, need: Dict[str, bool], alloc=None):
+def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None):
+    """dX = dy w (times quick_gelu'(aux) when given), the data gradient of a linear layer.  `sp` (a Split16Layer with
+    transposed copies): dy is split with one scale per row and meets the [hi|hi|lo] copy of w^T on the fp16 MFMAs (DESIGN.md
+    §9e); None = the plain fp32 GEMM.  dy itself stays fp32 for the weight and bias gradients."""
+    if sp is None:
+        if aux is None:
+            return ops.gemm(dy, w, ops.LAYOUT_NN)
+        return ops.gemm(dy, w, ops.LAYOUT_NN, aux=aux, epilogue=ops.EPI_DGELU)
+    dy3, row_alpha = ops.split_f16x3_rows(dy)
+    return ops.gemm_f16_rows_dev(dy3, sp.wt[name], sp.walpha(name), row_alpha, dgelu_h=aux)
+
+
+def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, need: Dict[str, bool], alloc=None,
+              sp: Optional[Split16Layer] = None):
     """Returns (dx, grads) with grads keyed like LayerParams.FIELDS (missing = not needed).  `alloc(field, shape)`:
-    see _galloc."""
+    see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad)."""
     x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved
     gr: Dict[str, torch.Tensor] = {}
     linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc)
-    dh = ops.gemm(dx2, p.fc2_w, ops.LAYOUT_NN, aux=h, epilogue=ops.EPI_DGELU)
+    dh = _dgrad(dx2, p.fc2_w, sp, "fc2", aux=h)
     linear_param_grads(dh, ln2, bool(need.get("fc1_w")), bool(need.get("fc1_b")), gr, "fc1_w", "fc1_b", alloc)
-    dln2 = ops.gemm(dh, p.fc1_w, ops.LAYOUT_NN)
+    dln2 = _dgrad(dh, p.fc1_w, sp, "fc1")
     del dh
     dx1 = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc)
     linear_param_grads(dx1, attn, bool(need.get("out_w")), bool(need.get("out_b")), gr, "out_w", "out_b", alloc)
-    dattn = ops.gemm(dx1, p.out_w, ops.LAYOUT_NN)
+    dattn = _dgrad(dx1, p.out_w, sp, "out")
     dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal)
     linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc)
-    dln1 = ops.gemm(dqkv, p.qkv_w, ops.LAYOUT_NN)
+    dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv")
     del dqkv
     dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dx1, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc)
     return dx, gr
@@ -186,8 +202,10 @@ def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, sa
     return x2, saved
 
 
-def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need: Dict[str, bool], alloc=None):
-    """dx2 [B, D] is the gradient w.r.t. the CLS rows of the final hidden state; returns (dx [B*S, D], grads)."""
+def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need: Dict[str, bool], alloc=None,
+                       sp: Optional[Split16Layer] = None):
+    """dx2 [B, D] is the gradient w.r.t. the CLS rows of the final hidden state; returns (dx [B*S, D], grads).  `sp`: the
+    full-size qkv data gradient takes the split-fp16 path (_dgrad); the M = B GEMMs stay on ops.gemm."""
     x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved
     D = x.shape[1]
     gr: Dict[str, torch.Tensor] = {}
@@ -200,7 +218,7 @@ def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need:
     dattn = ops.gemm(dx1, p.out_w, ops.LAYOUT_NN)
     dqkv = ops.attention_cls_bwd(qkv, attn, dattn, lse, B, S, H)          # [B*S, 3D]; d q only on the CLS rows
     linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc)
-    dln1 = ops.gemm(dqkv, p.qkv_w, ops.LAYOUT_NN)
+    dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv")
     del dqkv
     dres = ops.scatter_rows(dx1, None, B, S, D)                           # the skip connection carries dx1 on CLS rows only
     dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dres, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc)
@@ -269,11 +287,13 @@ def _grid_pos_grad(dpos_cols: torch.Tensor, p: VisionParams, v, grid, alloc, dev
 
 
 def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None, grid=None,
-               split16_cache: Optional[dict] = None):
+               split16_cache: Optional[dict] = None, split16_out: Optional[list] = None):
     """get_image_features: [B,3,H,W] -> [B,P]  (hf:modeling_clip.py:202-218, :641-651, :744-751).  `grid` = (gh, gw): run on
     that patch grid with the position table resampled to it (None: the configuration's image size, as ever).
     `split16_cache` (the model's, HipCLIPModel._vsplit16_cache): a forward that saves for the backward runs the encoder
-    layers' full-size GEMMs on split-fp16 operands (DCLIP_VISION_SPLIT16); a no-grad forward never does."""
+    layers' full-size GEMMs on split-fp16 operands (DCLIP_VISION_SPLIT16); a no-grad forward never does.
+    `split16_out` (a list): receives what vision_bwd needs to run its data-gradient GEMMs on the same plan (Split16Bwd, §9e)
+    when this forward took the split path and DCLIP_VISION_SPLIT16_BWD is on; nothing otherwise."""
     v = cfg
     B = pixel_values.shape[0]
     S, D, H = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads
@@ -291,6 +311,8 @@ def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hid
     saved_layers = []
     prune = hidden_out is None and len(p.layers) > 0          # full hidden states are only materialised on request
     plan = _vision_split16_plan(p.layers, v, split16_cache) if save and split16_cache is not None and _VSPLIT16 else None
+    if plan is not None and split16_out is not None and _VSPLIT16_BWD and plan[0].wt is not None:
+        split16_out.append(Split16Bwd(plan, split16_cache["__vsplit16__"], p.layers))
     for li, lp in enumerate(p.layers):
         sp = plan[li] if plan is not None else None
         if prune and li == len(p.layers) - 1:
@@ -309,8 +331,9 @@ def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hid
     return out, saved
 
 
-def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool], on_ready=None, alloc=None):
-    """Gradients for VisionParams.tensors() order (None where not needed).  `on_ready(dict name -> grad)` is called as
+def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool], on_ready=None, alloc=None, split16=None):
+    """Gradients for VisionParams.tensors() order (None where not needed).  `split16`: the forward's Split16Bwd — the
+    full-size data-gradient GEMMs then run on its split-fp16 weights, unless a watched parameter has changed since.  `on_ready(dict name -> grad)` is called as
     soon as a group of gradients is final (the tail, then each layer from the top down, then the head): the
     data-parallel all-reduce of that group starts while the layers below are still being back-propagated.
     `alloc(name, shape)` may name the tensor a parameter gradient is to be written into (see _galloc)."""
@@ -339,13 +362,15 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
     if lowest is None:
         return [grads[n] for n in names]
     dx = None if pruned else ops.scatter_rows(dcls, None, B, S, D)
+    plan = split16.layers if split16 is not None and _VSPLIT16_BWD and split16.fresh() else None
     for i in range(n_layers - 1, max(lowest, 0) - 1, -1):
         lneed = {f: needd[f"layers.{i}.{f}"] for f in LayerParams.FIELDS}
         lalloc = None if alloc is None else (lambda f, shape, i=i: alloc(f"layers.{i}.{f}", shape))
+        sp = plan[i] if plan is not None else None
         if pruned and i == n_layers - 1:
-            dx, gr = last_layer_bwd_cls(dcls, p.layers[i], saved_layers[i], B, S, H, lneed, lalloc)
+            dx, gr = last_layer_bwd_cls(dcls, p.layers[i], saved_layers[i], B, S, H, lneed, lalloc, sp)
         else:
-            dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, S, H, False, lneed, lalloc)
+            dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, S, H, False, lneed, lalloc, sp)
         saved_layers[i] = None
         for f, t in gr.items():
             grads[f"layers.{i}.{f}"] = t
@@ -1173,6 +1198,8 @@ def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: 
 _VSPLIT16 = os.environ.get("DCLIP_VISION_SPLIT16", "1") != "0"    # read once at import: no getenv on the launch path
 # fc1 leaves its GEMM as h, g AND the split of g (one launch, three outputs); 0 = h and g from the GEMM, then the split pass
 _VSPLIT16_FC1_EPI = os.environ.get("DCLIP_VISION_SPLIT16_FC1_EPI", "1") != "0"
+# the backward's full-size data-gradient GEMMs on the same plan, dY split per row; 0 = the plain fp32 dgrads
+_VSPLIT16_BWD = os.environ.get("DCLIP_VISION_SPLIT16_BWD", "1") != "0"
 
 
 def vision_split16_enabled() -> bool:
@@ -1216,6 +1243,52 @@ def split16_plan_host(st: Dict[str, float], D: int) -> Dict[str, object]:
     return {"e": e, "f": f, "a": a, "flags": flags}
 
 
+def split16_row_exp(r: float) -> int:
+    """e with r 2^e in [2^13, 2^14) for a row maximum r = max|dY[m,:]| (r = mu 2^x, mu in [0.5, 1): e = 14 - x), clamped to
+    [-100, 100] so that 2^e, 2^-e and their products with a weight alpha stay normal fp32; 0 for r = 0 or a non-finite r.
+    The rule of the row-scaled split (dclip_split_f32_f16x3_rows) and the reference of its tests."""
+    import math
+    if r == 0.0 or not math.isfinite(r):
+        return 0
+    return max(-100, min(100, _SPLIT16_TOP - math.frexp(abs(r))[1]))
+
+
+def split16_rows_host(x: torch.Tensor):
+    """What dclip_split_f32_f16x3_rows makes of a host fp32 matrix: (fp16 [rows, 3 cols] = [hi|lo|hi], fp32 row_alpha)."""
+    x = x.float()
+    e = torch.tensor([split16_row_exp(float(r)) for r in x.abs().amax(dim=1).double()], dtype=torch.float32)
+    v = x * torch.exp2(e)[:, None]
+    hi = v.half()
+    lo = (v - hi.float()).half()
+    return torch.cat([hi, lo, hi], dim=1), torch.exp2(-e)
+
+
+class Split16Bwd:
+    """What a backward needs to run its data-gradient GEMMs on the plan of ITS forward: the layers'
+    Split16Layer list and the versions / addresses of the watched parameters that the forward's refresh saw.  The split
+    copies are the model's and persistent, so a parameter written — or another forward's refresh issued — between this
+    forward and its backward would pair dY with other weights: fresh() is the host check (nothing read from the device)
+    that sends such a backward down the plain path."""
+    __slots__ = ("layers", "ent", "params", "ptrs", "versions", "epoch")
+
+    def __init__(self, layers, ent: dict, params: List[LayerParams]):
+        self.layers, self.ent, self.params = layers, ent, params
+        self.ptrs = tuple(getattr(lp, f).data_ptr() for lp in params for f in _SPLIT16_WATCHED)
+        self.versions = tuple(getattr(lp, f)._version for lp in params for f in _SPLIT16_WATCHED)
+        self.epoch = ent["epoch"]
+
+    def fresh(self) -> bool:
+        if torch.cuda.is_current_stream_capturing():
+            return True      # one capture holds the refresh, the forward and this backward: every replay re-splits first
+        ok = (self.epoch == self.ent["epoch"] and
+              self.ptrs == tuple(getattr(lp, f).data_ptr() for lp in self.params for f in _SPLIT16_WATCHED) and
+              self.versions == tuple(getattr(lp, f)._version for lp in self.params for f in _SPLIT16_WATCHED))
+        if not ok:
+            _split16_log_once("split-fp16 vision tower: a weight changed between a forward and its backward; that backward "
+                              "takes the plain fp32 data-gradient GEMMs")
+        return ok
+
+
 def _vision_split16_flags(ent: dict) -> None:
     """Look at the flags the LAST refresh left in pinned host memory (never waited for: a flag is seen a step late).  The
     copy of the current step may be in flight while this reads: a flag is one aligned 32-bit word, so what is read is
@@ -1256,10 +1329,11 @@ def _vision_split16_plan(layers: List[LayerParams], cfg, cache: dict):
             return None
         if any(not getattr(lp, f).is_contiguous() for lp in layers for f in _SPLIT16_WATCHED):
             return None
-        tab = ops.split16_table([{f: getattr(lp, f) for f in _SPLIT16_WATCHED} for lp in layers])
+        tab = ops.split16_table([{f: getattr(lp, f) for f in _SPLIT16_WATCHED} for lp in layers], transposed=_VSPLIT16_BWD)
         base, stride = tab["plan"].data_ptr(), 4 * tab["plan"].shape[1]
-        ent = {"ptrs": ptrs, "tab": tab, "versions": None, "host": None,
-               "layers": [Split16Layer(w, base + li * stride) for li, w in enumerate(tab["w"])]}
+        wt = tab.get("wt")
+        ent = {"ptrs": ptrs, "tab": tab, "versions": None, "host": None, "epoch": 0,
+               "layers": [Split16Layer(w, base + li * stride, wt[li] if wt else None) for li, w in enumerate(tab["w"])]}
         try:
             ent["host"] = torch.zeros(tuple(tab["plan"].shape), dtype=torch.float32).pin_memory()
         except RuntimeError:
@@ -1269,6 +1343,7 @@ def _vision_split16_plan(layers: List[LayerParams], cfg, cache: dict):
     if capturing or ent["versions"] != versions:
         _vision_split16_flags(ent)
         ops.split16_refresh(ent["tab"])
+        ent["epoch"] += 1                       # Split16Bwd.fresh: the copies a pending backward was planned on are gone
         if ent["host"] is not None:
             ent["host"].copy_(ent["tab"]["plan"], non_blocking=True)
         ent["versions"] = None if capturing else versions

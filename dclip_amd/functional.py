@@ -44,8 +44,11 @@ class VisionTowerFn(torch.autograd.Function):
         saves for the backward runs its full-size GEMMs with it (DCLIP_VISION_SPLIT16); None: the plain fp32 path."""
         p = engine.VisionParams.from_tensors([_c(t.detach()) for t in params], n_layers)
         save = any(ctx.needs_input_grad[5:])
-        out, saved = engine.vision_fwd(p, _c(pixel_values.detach()), cfg, save, grid=grid, split16_cache=split16_cache)
+        split16 = []                                       # the forward's split-fp16 plan, for the backward's dgrads (§9e)
+        out, saved = engine.vision_fwd(p, _c(pixel_values.detach()), cfg, save, grid=grid, split16_cache=split16_cache,
+                                       split16_out=split16)
         ctx.p, ctx.saved, ctx.cfg = p, saved, cfg
+        ctx.split16 = split16[0] if split16 else None
         ctx.param_refs = params if save else None          # the nn.Parameters, for the data-parallel hook
         return out
 
@@ -66,8 +69,9 @@ class VisionTowerFn(torch.autograd.Function):
         if _GRAD_ALLOC is not None:
             galloc = _GRAD_ALLOC
             alloc = lambda name, shape: galloc(by_name[name], shape)      # noqa: E731
-        grads = engine.vision_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[5:]), on_ready, alloc)
-        ctx.saved = None
+        grads = engine.vision_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[5:]), on_ready, alloc,
+                                  split16=ctx.split16)
+        ctx.saved = ctx.split16 = None
         if owned:           # handed to the data-parallel reducer: autograd neither accumulates nor clones them
             grads = [None if n in owned else g for n, g in zip(ctx.p.names(), grads)]
         return (None, None, None, None, None, *grads)

@@ -1257,18 +1257,21 @@ SPLIT16_PLAN_ACT = {"ln1": 0, "ctx": 1, "ln2": 2, "g": 3}          # floats of a
 SPLIT16_PLAN_W = {"qkv": 4, "out": 5, "fc1": 6, "fc2": 7}          # weight scales,
 SPLIT16_PLAN_ALPHA = {"qkv": 8, "out": 9, "fc1": 10, "fc2": 11}    # alphas; 12 = flags, 16..27 = the statistics
 SPLIT16_PLAN_FLAGS, SPLIT16_PLAN_STATS = 12, 16
+SPLIT16_PLAN_WALPHA = {"qkv": 28, "out": 29, "fc1": 30, "fc2": 31}  # 2^-f: the alphas of the data-gradient GEMMs (§9e)
 
 
-def split16_table(layers):
+def split16_table(layers, transposed: bool = False):
     """The device state of split16_refresh for encoder layers given as dicts of fp32 tensors ln1_w, ln1_b, qkv_w [3D, D],
     qkv_b, out_w, ln2_w, ln2_b, fc1_w, fc1_b, fc2_w (widths multiples of 8): the record table, the statistics accumulators,
-    the plan [L, 32] fp32, and per layer the [hi|hi|lo] fp16 copies {"qkv", "out", "fc1", "fc2"}.  One synchronous upload:
-    build it once, outside graph capture."""
+    the plan [L, 32] fp32, and per layer the [hi|hi|lo] fp16 copies {"qkv", "out", "fc1", "fc2"}.  `transposed`: also "wt",
+    per layer the [hi|hi|lo] copies of the TRANSPOSED scaled weights, [in, 3 out] — the operands of the backward's
+    data-gradient GEMMs (as much memory again as "w").  One synchronous upload: build it once, outside graph capture."""
     import struct
     lib = _lib.load()
     assert lib.dclip_split16_record_bytes() == 48
     nplan, trows = lib.dclip_split16_plan_floats(), lib.dclip_split16_tile_rows()
     slot = {n: i for i, n in enumerate(SPLIT16_STATS)}
+    tcopies = []
     mats, vecs, copies = [], [], []            # the matrices come first in the table: the weight-split launch covers only them
     dev = layers[0]["qkv_w"].device
 
@@ -1288,6 +1291,14 @@ def split16_table(layers):
             src = L[short + "_w"]
             w[short] = torch.empty((src.shape[0], 3 * src.shape[1]), dtype=torch.float16, device=dev)
         copies.append(w)
+        if transposed:
+            wt = {}
+            for short in ("qkv", "out", "fc1", "fc2"):
+                src = L[short + "_w"]
+                if src.shape[0] % 8:
+                    raise ValueError("split16_table: a transposed copy needs a multiple of 8 rows")
+                wt[short] = torch.empty((src.shape[1], 3 * src.shape[0]), dtype=torch.float16, device=dev)
+            tcopies.append(wt)
         vb = L["qkv_b"][2 * D:]                # an address inside qkv_b: the caller re-builds the table when a tensor moves
         for n in ("ln1_w", "ln1_b", "ln2_w", "ln2_b", "fc1_b"):
             rec(li, L[n], 1, L[n].numel(), slot[n])
@@ -1303,7 +1314,11 @@ def split16_table(layers):
         if r[1]:
             wtiles = t0
     table = torch.frombuffer(bytearray(b"".join(blob)), dtype=torch.uint8).to(dev)
-    return {"table": table, "nrefs": len(blob), "tiles": t0, "wrefs": len(mats), "wtiles": wtiles, "w": copies, "L": len(layers),
+    extra = {}
+    if transposed:         # one pointer per matrix record, in table order (a layer's qkv, out, fc1, fc2)
+        by_dst = {w[k].data_ptr(): wt[k].data_ptr() for w, wt in zip(copies, tcopies) for k in w}
+        extra = {"wt": tcopies, "dst_t": torch.tensor([by_dst[r[1]] for r in mats], dtype=torch.int64).to(dev)}
+    return {**extra, "table": table, "nrefs": len(blob), "tiles": t0, "wrefs": len(mats), "wtiles": wtiles, "w": copies, "L": len(layers),
             "D": layers[0]["ln1_w"].numel(),
             "stats": torch.zeros((len(layers), len(SPLIT16_STATS)), dtype=torch.int32, device=dev),
             "plan": torch.zeros((len(layers), nplan), dtype=torch.float32, device=dev)}
@@ -1316,8 +1331,46 @@ def split16_refresh(tab) -> None:
     _lib.check(lib.dclip_split16_stats(tab["table"].data_ptr(), tab["nrefs"], tab["tiles"], tab["stats"].data_ptr(), st),
                "split16_stats")
     _lib.check(lib.dclip_split16_plan(tab["stats"].data_ptr(), tab["plan"].data_ptr(), tab["L"], tab["D"], st), "split16_plan")
-    _lib.check(lib.dclip_split16_weights(tab["table"].data_ptr(), tab["wrefs"], tab["wtiles"], tab["plan"].data_ptr(), st),
-               "split16_weights")
+    if "dst_t" in tab:
+        _lib.check(lib.dclip_split16_weights_t(tab["table"].data_ptr(), tab["wrefs"], tab["wtiles"], tab["plan"].data_ptr(),
+                                               tab["dst_t"].data_ptr(), st), "split16_weights_t")
+    else:
+        _lib.check(lib.dclip_split16_weights(tab["table"].data_ptr(), tab["wrefs"], tab["wtiles"], tab["plan"].data_ptr(), st),
+                   "split16_weights")
+
+
+def split_f16x3_rows(x: torch.Tensor):
+    """[rows, cols] fp32 (row stride >= cols) -> (fp16 [rows, 3 cols], fp32 [rows]): the [hi|lo|hi] split of x[m] * 2^e_m with
+    one power of two PER ROW taken from the row's own maximum (engine.split16_row_exp), and row_alpha[m] = 2^-e_m."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("split_f16x3_rows: x must be a 2-D fp32 device tensor with unit column stride")
+    rows, cols = x.shape
+    y = torch.empty((rows, 3 * cols), dtype=torch.float16, device=x.device)
+    ra = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    _lib.check(lib.dclip_split_f32_f16x3_rows(x.data_ptr(), y.data_ptr(), ra.data_ptr(), rows, cols, x.stride(0) if rows > 1 else cols,
+                                              _stream()), "split_f32_f16x3_rows")
+    return y, ra
+
+
+def gemm_f16_rows_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, row_alpha: torch.Tensor,
+                      dgelu_h: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [M, N] = ((a w^T) * *alpha_ptr) * row_alpha[m], times quick_gelu'(dgelu_h) when given (fp32 [M, N]): gemm_f16_dev for
+    an `a` split by split_f16x3_rows."""
+    lib = _lib.load()
+    _f16(a, "a"), _f16(w, "w")
+    M, lda = a.shape
+    N, ldw = w.shape
+    K = min(lda, ldw)
+    if _f32(row_alpha, "row_alpha").numel() != M:
+        raise ValueError("gemm_f16_rows_dev: row_alpha size")
+    if dgelu_h is not None and tuple(_f32(dgelu_h, "dgelu_h").shape) != (M, N):
+        raise ValueError("gemm_f16_rows_dev: dgelu_h shape")
+    out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    _lib.check(lib.dclip_gemm_f16_scaled_rows_dev(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(dgelu_h), M, N, K, lda, ldw, N,
+                                                  EPI_DGELU if dgelu_h is not None else 0, alpha_ptr, row_alpha.data_ptr(),
+                                                  _stream()), "gemm_f16_scaled_rows_dev")
+    return out
 
 
 # ------------------------------------------------------------------------------------------- fp16 training path

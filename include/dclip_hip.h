@@ -562,6 +562,25 @@ int dclip_split16_plan(void* stats, float* plan, int nlayers, int D, void* strea
 int dclip_split16_weights(const void* refs, int nrefs, int tiles, const float* plan, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Split-fp16 DATA-GRADIENT GEMMs of the student's vision backward (DCLIP_VISION_SPLIT16_BWD): dX = dY W with dY
+ * split by ROW — it has no bound derivable from the weights, so its scale comes from the data, on the device.
+ *   split_f32_f16x3_rows     x fp32 [rows][ldx >= cols] -> y fp16 [rows][3 cols] = [hi|lo|hi] of x[m] 2^e_m, and
+ *                            row_alpha[m] = 2^-e_m.  r = max|x[m,:]| = mu 2^x (mu in [0.5, 1)): e_m = 14 - x clamped to
+ *                            [-100, 100]; e_m = 0 when r is 0 or not finite (such a row gives non-finite pieces).  One pass, the
+ *                            same result in every run.  cols % 8 == 0, ldx % 4 == 0, 16-byte aligned x / y.
+ *   split16_weights_t        split16_weights that also writes, in the same launch and from the same plan scale, the transposed
+ *                            copies: dst_t = device array of nrefs pointers, entry i = fp16 [cols][3 rows] of record i
+ *                            ([hi|hi|lo] of (src scale)^T, bit-equal to split_f32_f16x3(order 1) of the transposed weight) or
+ *                            NULL; such a record needs rows % 8 == 0.
+ *   gemm_f16_scaled_rows_dev C[m][n] = epi((acc * *alpha) * row_alpha[m]), fp32 [M][ldc]; epilogue 0 or DCLIP_EPI_DGELU with the
+ *                            fp32 pre-activation aux32 [M][ldc] (dclip_gemm_f32's DGELU statement).  row_alpha == 1 gives
+ *                            gemm_f16_scaled_dev's output bit for bit.  Any kernel of the dispatcher but the persistent one. */
+int dclip_split_f32_f16x3_rows(const float* x, void* y, float* row_alpha, int rows, int cols, int ldx, void* stream);
+int dclip_split16_weights_t(const void* refs, int nrefs, int tiles, const float* plan, const void* dst_t, void* stream);
+int dclip_gemm_f16_scaled_rows_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K, int lda, int ldw,
+                                   int ldc, int epilogue, const float* alpha, const float* row_alpha, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * fp16 TRAINING path (opt-in student_precision="fp16" / get_image_features(precision="fp16-mixed")): fp16
  * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
  * a finite value beyond +-65504 becomes +-inf (it does NOT saturate as the frozen fp16 entries do), NaN stays NaN, so the
