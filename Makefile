@@ -9,7 +9,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -fvisibility=hidden -Wal
 
 all: $(LIB)
 
-$(CSRC)/build/%.o: $(CSRC)/%.hip $(CSRC)/common.h include/dclip_hip.h
+$(CSRC)/build/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/attention_tiles.h include/dclip_hip.h
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import argparse
 import os
+from typing import Optional
 
 import torch
 
@@ -29,12 +30,23 @@ def main(args, clip_model=None, clip_preprocess=None, train_batches=None, val_ba
         clip_model = CLIPModel.from_pretrained(args.clip_path, local_files_only=True).to(device)
         clip_preprocess = CLIPProcessor.from_pretrained(args.clip_path, local_files_only=True)
     module_kwargs.setdefault("student_precision", getattr(args, "student_precision", "fp32"))
+    module_kwargs.setdefault("full_resolution_from_epoch", resolve_full_resolution_epoch(args))
     model = CLIPImageDistillation(args, clip_model, clip_preprocess, **module_kwargs).to(device)
     trainer = Trainer(max_epochs=args.phase1_epochs, accelerator="gpu", devices=devices, precision=32,
                       gradient_clip_val=0.5, accumulate_grad_batches=4, checkpoint_dir=args.checkpoint_dir,
                       save_top_k=10, max_steps=getattr(args, "max_steps", None))
     trainer.fit(model, train_batches, val_batches)
     return model, trainer
+
+
+def _epoch_or_half(value: str):
+    return "half" if value == "half" else int(value)
+
+
+def resolve_full_resolution_epoch(args) -> Optional[int]:
+    """--full_resolution_from_epoch as an epoch number: `half` is phase1_epochs // 2 (training/CLIP_image_distillation.py:723-729)."""
+    v = getattr(args, "full_resolution_from_epoch", None)
+    return args.phase1_epochs // 2 if v == "half" else v
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -47,6 +59,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--student_precision", choices=("fp32", "bf16", "fp16"), default="fp32",
                         help="GEMM inputs of the student's vision tower: fp32 (the reference), bf16, or fp16 with a dynamic "
                              "loss scale (Lightning's precision='16-mixed')")
+    parser.add_argument("--full_resolution_from_epoch", type=_epoch_or_half, default=None, metavar="N|half",
+                        help="from this epoch on the meta-teacher encodes region crops at their own size, in one packed tower "
+                             "pass; `half` = phase1_epochs // 2, the reference's rule (default: never)")
     return parser
 
 

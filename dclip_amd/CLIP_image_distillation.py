@@ -72,14 +72,21 @@ def _as_hip_model(clip_model) -> HipCLIPModel:
 
 class CLIPImageDistillation(LightningLikeModule):
     def __init__(self, hparams, clip_model, clip_preprocess=None, teacher=None, freeze_mode: str = "north_star",
-                 process_group=None, contrastive_teacher_path: Optional[str] = None, student_precision: str = "fp32"):
+                 process_group=None, contrastive_teacher_path: Optional[str] = None, student_precision: str = "fp32",
+                 full_resolution_from_epoch: Optional[int] = None):
         """`student_precision`: "fp32" (default: the reference's `precision=32`,
         training/CLIP_image_distill_training.py:40, and the benched config c2) or "bf16" — the student's VISION tower
         multiplies in bf16 (forward, dgrad, wgrad) with fp32 master weights, fp32 accumulation and fp32
         LayerNorm / softmax / losses: what BASELINE configs c3 / c5 quote ("bf16 MFMA"), or "fp16" — the same with fp16
         GEMM inputs (IEEE rounding) and a dynamic loss scale that Trainer.fit applies (amp.DynamicLossScaler; Lightning's
-        precision="16-mixed"), within the 1e-3 embedding bar."""
+        precision="16-mixed"), within the 1e-3 embedding bar.
+        `full_resolution_from_epoch` = N: from epoch N on the meta-teacher encodes every region crop at its own size, in one
+        packed tower pass (teacher.full_resolution = teacher.full_resolution_packed = current_epoch >= N, set before every
+        teacher call; training/CLIP_image_distillation.py:723-729 switches at half the epochs).  None leaves both flags alone."""
         super().__init__()
+        if full_resolution_from_epoch is not None and int(full_resolution_from_epoch) < 0:
+            raise ValueError(f"full_resolution_from_epoch {full_resolution_from_epoch!r}")
+        self.full_resolution_from_epoch = None if full_resolution_from_epoch is None else int(full_resolution_from_epoch)
         if student_precision not in ("fp32", "bf16", "fp16"):
             raise ValueError(f"student_precision {student_precision!r}")
         self.student_precision = student_precision
@@ -252,6 +259,9 @@ class CLIPImageDistillation(LightningLikeModule):
         early_student_image = None
         grad_on = torch.is_grad_enabled()            # (the teacher branches below run under no_grad)
         self.teacher.last_sentence_embedding = None
+        if self.full_resolution_from_epoch is not None:
+            self.teacher.full_resolution = self.teacher.full_resolution_packed = \
+                self.current_epoch >= self.full_resolution_from_epoch
         if isinstance(batch, dict) and "captions" in batch:
             # data.GpuCollate: decoded images already on the device, student preprocessing done there
             images = batch["pixel_values"].to(dev)

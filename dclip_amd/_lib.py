@@ -54,6 +54,10 @@ SIGNATURES = {
     "dclip_im2col_rect": (I, [P, P, I, I, I, I, I, P]),
     "dclip_im2col_rect_bf16": (I, [P, P, I, I, I, I, I, I, P]),
     "dclip_im2col_rect_f16": (I, [P, P, I, I, I, I, I, I, P]),
+    "dclip_patches_from_boxes_u8": (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    "dclip_vision_assemble_varlen": (I, [P, P, P, P, P, P, I, I, I, P]),
+    "dclip_attention_varlen_fwd": (I, [P, P, P, P, I, I, I, I, P]),
+    "dclip_gather_rows_at": (I, [P, P, P, I, I, I, P]),
     "dclip_normalize_rows_fwd": (I, [P, P, P, I, I, F, P]),
     "dclip_normalize_rows_bwd": (I, [P, P, P, P, I, I, F, I, P]),
     "dclip_contrastive_workspace": (Z, [I, I, I]),

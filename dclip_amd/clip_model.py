@@ -21,7 +21,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from . import engine, functional
+from . import engine, functional, ops
 from .config import ClipConfig, TextConfig, VisionConfig
 
 
@@ -135,6 +135,29 @@ class HipTextTransformer(nn.Module):
         self.final_layer_norm = _Affine((t.hidden_size,), ones=True)
 
 
+def packed_crop_tables(boxes: torch.Tensor, patch: int) -> dict:
+    """Host tables of the packed tower (engine.vision_fwd_packed) for the crops boxes [N,5] = (b, x1, y1, x2, y2), int32 on the
+    host: crop n has the grid gh = (y2 - y1) // patch, gw = (x2 - x1) // patch and 1 + gh*gw token rows.  Returns int32 host
+    tensors `grids` [N,2], `cu_seqlens` [N+1] (cumulative token rows), `patch_offsets` [N+1] (= cu_seqlens[n] - n), `cls_rows`
+    [N] (= cu_seqlens[:-1]) and the int `max_S`.  A crop with a side shorter than one patch is a ValueError."""
+    boxes = torch.as_tensor(boxes, dtype=torch.int32).reshape(-1, 5).cpu()
+    if patch < 1:
+        raise ValueError(f"patch {patch}")
+    gh = torch.div(boxes[:, 4] - boxes[:, 2], patch, rounding_mode="floor")
+    gw = torch.div(boxes[:, 3] - boxes[:, 1], patch, rounding_mode="floor")
+    if boxes.shape[0] and int(torch.minimum(gh, gw).min()) < 1:
+        n = int((torch.minimum(gh, gw) < 1).nonzero()[0])
+        raise ValueError(f"the crop of box {tuple(boxes[n, 1:].tolist())} is smaller than one patch ({patch}*{patch})")
+    seq = (1 + gh.long() * gw.long())
+    if int(seq.sum()) >= 2 ** 31:
+        raise ValueError("packed crops: more than 2^31 token rows")
+    cu = torch.zeros(boxes.shape[0] + 1, dtype=torch.int32)
+    cu[1:] = torch.cumsum(seq, 0).to(torch.int32)
+    po = cu - torch.arange(boxes.shape[0] + 1, dtype=torch.int32)
+    return {"grids": torch.stack([gh, gw], 1).to(torch.int32).contiguous(), "cu_seqlens": cu, "patch_offsets": po,
+            "cls_rows": cu[:-1].clone(), "max_S": int(seq.max()) if boxes.shape[0] else 0}
+
+
 class HipCLIPModel(nn.Module):
     def __init__(self, config: Optional[ClipConfig] = None):
         super().__init__()
@@ -221,6 +244,35 @@ class HipCLIPModel(nn.Module):
         train = torch.is_grad_enabled() and any(t.requires_grad for t in p.tensors())
         return functional.VisionTowerFn.apply(pixel_values.float(), v, v.num_hidden_layers, grid,
                                               self._vsplit16_cache() if train else None, *p.tensors())
+
+    @torch.no_grad()
+    def get_image_features_crops(self, images_u8: torch.Tensor, dims: torch.Tensor, boxes, precision: str = "fp32") -> torch.Tensor:
+        """Image features [N, P] of N crops of a padded uint8 batch, every crop at its OWN size, in one packed pass of the
+        frozen tower.  FORWARD ONLY: it runs under no_grad whatever the caller's mode and nothing is saved.
+        images_u8 [B,Hmax,Wmax,3] uint8 and dims [B,2] int32 (h, w) on the device (data.GpuCollate); boxes [N,5] =
+        (b, x1, y1, x2, y2) integers on the HOST (a tensor or a list).  Crop n is what PIL's crop((x1,y1,x2,y2)) + ToTensor()
+        give (values in [0,1], zero outside the image, no mean / std), cut on the device; its position table is the model's,
+        resampled to its patch grid as get_image_features(interpolate_pos_encoding=True) does.  A crop with a side shorter than
+        one patch is a ValueError.  precision: "fp32", "bf16" or "fp16" (16-bit GEMM inputs, fp32 attention core)."""
+        if precision not in ("fp32", "bf16", "fp16"):
+            raise ValueError(f"precision {precision!r}")
+        v = self.config.vision
+        flat = torch.as_tensor(boxes, dtype=torch.int32).reshape(-1, 5).cpu().contiguous()
+        N = flat.shape[0]
+        if N == 0:
+            return torch.zeros((0, self.config.projection_dim), dtype=torch.float32, device=images_u8.device)
+        if int(flat[:, 0].min()) < 0 or int(flat[:, 0].max()) >= images_u8.shape[0]:
+            raise ValueError(f"get_image_features_crops: a box names an image outside the batch of {images_u8.shape[0]}")
+        t = packed_crop_tables(flat, v.patch_size)
+        # one upload for the four tables
+        host = torch.cat([flat.reshape(-1), t["grids"].reshape(-1), t["cu_seqlens"], t["patch_offsets"]])
+        dev_t = host.to(images_u8.device, non_blocking=False)
+        bx, grids = dev_t[:5 * N].view(N, 5), dev_t[5 * N:7 * N].view(N, 2)
+        cu, po = dev_t[7 * N:8 * N + 1], dev_t[8 * N + 1:]
+        cols = ops.patches_from_boxes_u8(images_u8, dims, bx, po, int(t["patch_offsets"][-1]), v.patch_size)
+        pd = engine.VisionParams.from_tensors([x.detach() for x in self.vision_params().tensors()], v.num_hidden_layers)
+        cache = None if precision == "fp32" else (self._bf16_cache() if precision == "bf16" else self._f16_cache())
+        return engine.vision_fwd_packed(pd, cols, grids, cu, cu[:N], t["max_S"], v, precision, cache)
 
     def _bf16_cache(self) -> dict:
         """bf16 copies of the GEMM weights: persistent buffers, each refreshed in place when ITS parameter's version

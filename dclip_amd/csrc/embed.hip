@@ -138,6 +138,18 @@ __global__ void __launch_bounds__(256) scatter_rows_kernel(const float* __restri
   }
 }
 
+// out[n, :] = x[rows[n], :], rows anywhere in [0, T) in any order, repeats allowed (an index outside is clamped into the range,
+// as the token ids of text_embed_fwd are): the residual of the packed tower's last layer on its CLS rows.
+__global__ void __launch_bounds__(256) gather_rows_at_kernel(const float* __restrict__ x, const int32_t* __restrict__ rows,
+                                                             float* __restrict__ out, int T, int D4, size_t total4) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
+    const int d = (int)(i % D4);
+    int r = rows[i / D4];
+    r = r < 0 ? 0 : (r >= T ? T - 1 : r);
+    reinterpret_cast<f32x4*>(out)[i] = reinterpret_cast<const f32x4*>(x)[(size_t)r * D4 + d];
+  }
+}
+
 }  // namespace
 
 DCLIP_API int dclip_im2col(const float* pixels, float* cols, int B, int C, int Himg, int Wimg, int patch, void* stream) {
@@ -250,5 +262,17 @@ DCLIP_API int dclip_scatter_rows(const float* dout, const int32_t* idx, float* d
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, dout, idx, dx, S, D / 4,
                      total4);
   DCLIP_CHECK_LAUNCH("scatter_rows");
+  return DCLIP_OK;
+}
+
+DCLIP_API int dclip_gather_rows_at(const float* x, const int32_t* rows, float* out, int N, int T, int D, void* stream) {
+  DCLIP_REQUIRE(x && rows && out, "gather_rows_at: null pointer");
+  DCLIP_REQUIRE(N > 0 && T > 0 && D > 0 && D % 4 == 0, "gather_rows_at: bad shape N=%d T=%d D=%d", N, T, D);
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)out) % 16 == 0 && (uintptr_t)rows % 4 == 0,
+                "gather_rows_at: x / out must be 16-byte aligned, rows 4-byte aligned");
+  const size_t total4 = (size_t)N * (D / 4);
+  hipLaunchKernelGGL(gather_rows_at_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, x, rows, out, T, D / 4,
+                     total4);
+  DCLIP_CHECK_LAUNCH("gather_rows_at");
   return DCLIP_OK;
 }

@@ -1,6 +1,8 @@
 // The vision tower at another input size: the bicubic resample of the position table with its exact
 // transpose, and the patch gather on a gh x gw grid.  All HBM/L2-bound gathers like embed.hip's; the existing im2col
-// kernels there are left as they are, these are their twins with the grid extent g split into gh and gw.
+// kernels there are left as they are, these are their twins with the grid extent g split into gh and gw.  Below them the
+// packed front end of DESIGN.md §22: patch rows of many crops of different sizes cut from a uint8 batch, and the assemble step
+// that resamples the position table per crop.
 #include "common.h"
 
 namespace {
@@ -190,6 +192,93 @@ int im2col_rect16(const char* name, const float* pixels, void* cols, int B, int 
   return DCLIP_OK;
 }
 
+// ---- the packed (variable-length) front end of the tower ----
+// Patch rows of N crops cut from a padded uint8 batch, each crop at its own size: crop n = boxes[n] = (b, x1, y1, x2, y2) has
+// the grid gh = (y2-y1)/p, gw = (x2-x1)/p and owns rows po[n] .. po[n+1]-1 of cols; row gy*gw + gx, column c*p*p + py*p + px is
+// pixel (y1 + gy*p + py, x1 + gx*p + px) of image b, channel c, as float / 255 (an IEEE division: ToTensor()'s value).  A
+// position outside [0,h) x [0,w) of its image reads nothing and gives 0 (PIL's crop of a box past an edge); the batch's own
+// padding is never what supplies that zero.  Grid (N, chunks): a workgroup serves ONE crop, so no thread searches the offset
+// table.  VEC: four px per thread and a 16-byte store (p % 4 == 0).
+__device__ __forceinline__ float pixel_or_zero(const uint8_t* __restrict__ img, int y, int x, int c, int h, int w, int Wmax) {
+  return (y >= 0 && y < h && x >= 0 && x < w) ? (float)img[((size_t)y * Wmax + x) * 3 + c] / 255.0f : 0.0f;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) patches_from_boxes_kernel(const uint8_t* __restrict__ images, const int32_t* __restrict__ dims,
+                                                                 const int32_t* __restrict__ boxes, const int32_t* __restrict__ po,
+                                                                 float* __restrict__ cols, int B, int Hmax, int Wmax, int p) {
+  const int n = blockIdx.x;
+  const int b = boxes[5 * n], x1 = boxes[5 * n + 1], y1 = boxes[5 * n + 2], x2 = boxes[5 * n + 3], y2 = boxes[5 * n + 4];
+  if (b < 0 || b >= B || x2 - x1 < p || y2 - y1 < p) return;            // a crop the planner would not have listed
+  const int gw = (x2 - x1) / p, gh = (y2 - y1) / p;
+  const int row0 = po[n];
+  const long long nrows = min((long long)gh * gw, (long long)po[n + 1] - row0);    // never into the next crop's rows
+  if (row0 < 0 || nrows <= 0) return;
+  const int h = min(dims[2 * b], Hmax), w = min(dims[2 * b + 1], Wmax);
+  const uint8_t* img = images + (size_t)b * Hmax * Wmax * 3;
+  const int kdim = 3 * p * p, step = VEC ? 4 : 1, kper = kdim / step, pper = p / step;
+  const size_t total = (size_t)nrows * kper;
+  for (size_t i = (size_t)blockIdx.y * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.y * blockDim.x) {
+    const int k = (int)(i % kper);
+    const int j = (int)(i / kper);
+    const int gx = j % gw, gy = j / gw;
+    const int px = (k % pper) * step, py = (k / pper) % p, c = k / (pper * p);
+    const int y = y1 + gy * p + py, x = x1 + gx * p + px;
+    float* dst = cols + ((size_t)row0 + j) * kdim + (size_t)k * step;
+    if constexpr (VEC) {
+      f32x4 v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = pixel_or_zero(img, y, x + e, c, h, w, Wmax);
+      *reinterpret_cast<f32x4*>(dst) = v;
+    } else {
+      *dst = pixel_or_zero(img, y, x, c, h, w, Wmax);
+    }
+  }
+}
+
+// x rows of N crops: row cu[n] = cls + pos[0]; row cu[n] + 1 + j = patch[cu[n] - n + j] + R_n[1 + j], R_n the table resampled
+// to crop n's grid (gh, gw) = grids[n] by pos_interp_fwd_kernel's arithmetic (axis_taps, one 16-term fmaf chain, a outer, b
+// inner) and added by vision_assemble_fwd_kernel's statement: bit for bit what those two launches give crop by crop.
+// Grid (N, chunks), one crop per workgroup.
+__global__ void __launch_bounds__(256) vision_assemble_varlen_kernel(const float* __restrict__ patch, const float* __restrict__ cls,
+                                                                     const float* __restrict__ pos, const int32_t* __restrict__ grids,
+                                                                     const int32_t* __restrict__ cu, float* __restrict__ x, int g,
+                                                                     int D4) {
+  const int n = blockIdx.x;
+  const int gh = grids[2 * n], gw = grids[2 * n + 1];
+  const int row0 = cu[n];
+  if (gh < 1 || gw < 1 || row0 < n) return;
+  const long long S = min(1ll + (long long)gh * gw, (long long)cu[n + 1] - row0);  // never into the next crop's rows
+  if (S <= 0) return;
+  const size_t prow0 = (size_t)(row0 - n);                                         // patch_offsets[n]
+  const size_t total4 = (size_t)S * D4;
+  for (size_t i = (size_t)blockIdx.y * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.y * blockDim.x) {
+    const int d = (int)(i % D4);
+    const int s = (int)(i / D4);
+    f32x4 v, r;
+    if (s == 0) {
+      v = reinterpret_cast<const f32x4*>(cls)[d];
+      r = reinterpret_cast<const f32x4*>(pos)[d];
+    } else {
+      v = reinterpret_cast<const f32x4*>(patch)[(prow0 + (s - 1)) * D4 + d];
+      const int oy = (s - 1) / gw, ox = (s - 1) % gw;
+      const Taps ty = axis_taps(oy, g, gh), tx = axis_taps(ox, g, gw);
+      r = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb) {
+          const float wgt = ty.w[a] * tx.w[bb];
+          const f32x4 t = reinterpret_cast<const f32x4*>(pos)[(size_t)(1 + ty.idx[a] * g + tx.idx[bb]) * D4 + d];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) r[e] = fmaf(wgt, t[e], r[e]);
+        }
+      }
+    }
+    reinterpret_cast<f32x4*>(x)[((size_t)row0 + s) * D4 + d] = v + r;
+  }
+}
+
 }  // namespace
 
 DCLIP_API int dclip_pos_interp_fwd(const float* pos, float* out, int g, int gh, int gw, int D, void* stream) {
@@ -241,4 +330,39 @@ DCLIP_API int dclip_im2col_rect_bf16(const float* pixels, void* cols, int B, int
 DCLIP_API int dclip_im2col_rect_f16(const float* pixels, void* cols, int B, int C, int Himg, int Wimg, int patch, int ldc,
                                     void* stream) {
   return im2col_rect16<F16T>("im2col_rect_f16", pixels, cols, B, C, Himg, Wimg, patch, ldc, stream);
+}
+
+// The packed front end.  A fixed number of workgroups per crop: the kernels walk a crop's rows with a stride, so any crop
+// size is served and the host needs no per-crop figure.
+DCLIP_API int dclip_patches_from_boxes_u8(const uint8_t* images_u8, const int32_t* dims, const int32_t* boxes,
+                                          const int32_t* patch_offsets, float* cols, int B, int Hmax, int Wmax, int N, int patch,
+                                          void* stream) {
+  DCLIP_REQUIRE(images_u8 && dims && boxes && patch_offsets && cols, "patches_from_boxes_u8: null pointer");
+  DCLIP_REQUIRE(B > 0 && Hmax > 0 && Wmax > 0 && N > 0 && patch >= 1 && patch <= 1024,
+                "patches_from_boxes_u8: bad shape B=%d %dx%d N=%d patch=%d", B, Hmax, Wmax, N, patch);
+  DCLIP_REQUIRE(((uintptr_t)dims | (uintptr_t)boxes | (uintptr_t)patch_offsets) % 4 == 0 && (uintptr_t)cols % 16 == 0,
+                "patches_from_boxes_u8: dims / boxes / patch_offsets must be 4-byte aligned, cols 16-byte aligned");
+  const bool vec = patch % 4 == 0;
+  const dim3 grid(N, 16);
+  if (vec)
+    hipLaunchKernelGGL((patches_from_boxes_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, images_u8, dims, boxes,
+                       patch_offsets, cols, B, Hmax, Wmax, patch);
+  else
+    hipLaunchKernelGGL((patches_from_boxes_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, images_u8, dims, boxes,
+                       patch_offsets, cols, B, Hmax, Wmax, patch);
+  DCLIP_CHECK_LAUNCH("patches_from_boxes_u8");
+  return DCLIP_OK;
+}
+
+DCLIP_API int dclip_vision_assemble_varlen(const float* patch_emb, const float* cls, const float* pos, const int32_t* grids,
+                                           const int32_t* cu_seqlens, float* x, int g, int N, int D, void* stream) {
+  DCLIP_REQUIRE(patch_emb && cls && pos && grids && cu_seqlens && x, "vision_assemble_varlen: null pointer");
+  DCLIP_REQUIRE(g >= 1 && g <= 32768 && N > 0 && D > 0 && D % 4 == 0, "vision_assemble_varlen: bad shape g=%d N=%d D=%d", g, N, D);
+  DCLIP_REQUIRE(((uintptr_t)patch_emb | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)x) % 16 == 0 &&
+                    ((uintptr_t)grids | (uintptr_t)cu_seqlens) % 4 == 0,
+                "vision_assemble_varlen: float operands must be 16-byte aligned, grids / cu_seqlens 4-byte aligned");
+  hipLaunchKernelGGL(vision_assemble_varlen_kernel, dim3(N, 8), dim3(256), 0, (hipStream_t)stream, patch_emb, cls, pos, grids,
+                     cu_seqlens, x, g, D / 4);
+  DCLIP_CHECK_LAUNCH("vision_assemble_varlen");
+  return DCLIP_OK;
 }

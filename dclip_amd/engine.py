@@ -495,6 +495,58 @@ def vision_fwd_bf16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dic
     return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)          # [B,D] x [P,D]: tiny, kept in exact fp32
 
 
+# --------------------------------------------------------------------------------------------- packed frozen forward
+# The frozen tower over N crops of DIFFERENT sizes in one pass (the full-resolution teacher): the token rows of
+# all crops lie back to back (crop n in rows cu_seqlens[n] .. cu_seqlens[n+1]-1, T rows in all).  LayerNorm, the four GEMMs and
+# their epilogues are row-wise and run at M = T as they are; the assemble step, the attention core and the CLS gather have
+# ragged forms (ops.vision_assemble_varlen, ops.attention_varlen_fwd, ops.gather_rows_at).  Forward only.
+
+def vision_fwd_packed(p: VisionParams, cols: torch.Tensor, grids: torch.Tensor, cu_seqlens: torch.Tensor,
+                      cls_rows: torch.Tensor, max_S: int, cfg, precision: str = "fp32", cache: Optional[dict] = None) -> torch.Tensor:
+    """cols [T - N, 3 p p] fp32 (ops.patches_from_boxes_u8), grids [N,2], cu_seqlens [N+1], cls_rows [N] (= cu_seqlens[:-1]),
+    int32 on the device -> [N, P].  The schedule of vision_fwd without `save`: the last layer runs its out-projection and MLP on
+    the N CLS rows only.  "bf16" / "fp16": 16-bit GEMM inputs with the persistent weight copies of `cache` (the model's cache of
+    that type, as vision_fwd_bf16); the qkv projection writes fp32 for the fp32 packed attention core and the context is cast."""
+    v = cfg
+    D, H, eps = v.hidden_size, v.num_attention_heads, v.layer_norm_eps
+    if not p.layers:
+        raise ValueError("vision_fwd_packed: the tower has no encoder layer")
+    if precision == "fp32":
+        patch = ops.gemm(cols, p.patch_w.view(D, -1), ops.LAYOUT_NT)
+        emb = ops.vision_assemble_varlen(patch, p.class_embedding, p.pos, grids, cu_seqlens, v.grid)
+        del patch
+        x, _, _ = ops.layernorm_fwd(emb, p.pre_w, p.pre_b, eps, save_stats=False)
+        for li, lp in enumerate(p.layers):
+            last = li == len(p.layers) - 1
+            ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, eps, save_stats=False)
+            qkv = ops.gemm(ln1, lp.qkv_w, ops.LAYOUT_NT, bias=lp.qkv_b)
+            attn = ops.attention_varlen_fwd(qkv, cu_seqlens, max_S, H, cls_only=last)
+            x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows_at(x, cls_rows) if last else x)
+            ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
+            g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
+            x = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)        # the last layer: [N, D], the CLS rows
+    else:
+        if precision not in ("bf16", "fp16") or cache is None:
+            raise ValueError(f"vision_fwd_packed: precision {precision!r} (16-bit precisions need the model's weight cache)")
+        k = _OPS16[torch.bfloat16 if precision == "bf16" else torch.float16]
+        patch = k.gemm(k.cast(cols), _w16(cache, "patch", p.patch_w, k.cast), k=v.patch_dim)
+        emb = ops.vision_assemble_varlen(patch, p.class_embedding, p.pos, grids, cu_seqlens, v.grid)
+        del patch
+        x, _, _ = ops.layernorm_fwd(emb, p.pre_w, p.pre_b, eps, save_stats=False)
+        for li, lp in enumerate(p.layers):
+            last, pre = li == len(p.layers) - 1, f"v{li}."
+            ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, eps)
+            qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)                     # fp32 q | k | v
+            attn = k.cast(ops.attention_varlen_fwd(qkv, cu_seqlens, max_S, H, cls_only=last))
+            x1 = k.gemm(attn, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b,
+                        residual=ops.gather_rows_at(x, cls_rows) if last else x)
+            ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
+            g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+            x = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
+    pooled, _, _ = ops.layernorm_fwd(x, p.post_w, p.post_b, eps, save_stats=False)
+    return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+
+
 # --------------------------------------------------------------------------------------------- bf16 TRAINING (vision)
 # The student's vision tower with bf16 GEMM inputs in forward, dgrad AND wgrad (BASELINE configs c3 / c5 quote the step
 # in bf16; opt-in `precision="bf16"` with gradients enabled).  fp32 master weights (bf16 copies W and W^T are rebuilt

@@ -1622,6 +1622,86 @@ def clip_preprocess(images_u8: torch.Tensor, dims: torch.Tensor, size: int = 224
     return out
 
 
+# ------------------------------------------------------------------------------------------- packed (variable-length) tower
+
+def _i32(t: torch.Tensor, name: str, shape) -> torch.Tensor:
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name}: expected a contiguous int32 CUDA tensor {tuple(shape)}, got {t.dtype} {t.device} {tuple(t.shape)}")
+    return t
+
+
+def patches_from_boxes_u8(images_u8: torch.Tensor, dims: torch.Tensor, boxes: torch.Tensor, patch_offsets: torch.Tensor,
+                          total_patches: int, patch: int) -> torch.Tensor:
+    """Patch rows [total_patches, 3*patch*patch] in [0,1] of the crops boxes [N,5] = (b,x1,y1,x2,y2) of images_u8
+    [B,Hmax,Wmax,3] (dims [B,2] = (h,w)), crop n at rows patch_offsets[n] .. patch_offsets[n+1]-1 in the column order of im2col;
+    outside its image a crop reads 0.  `total_patches` is patch_offsets[N], which the caller has on the host."""
+    lib = _lib.load()
+    if not (images_u8.is_cuda and images_u8.dtype == torch.uint8 and images_u8.is_contiguous() and images_u8.dim() == 4
+            and images_u8.shape[3] == 3):
+        raise ValueError("patches_from_boxes_u8: images must be a contiguous uint8 CUDA tensor [B,H,W,3]")
+    B, Hmax, Wmax, _ = images_u8.shape
+    N = boxes.shape[0]
+    if N < 1 or total_patches < N or patch < 1:
+        raise ValueError(f"patches_from_boxes_u8: {N} boxes, {total_patches} patch rows, patch {patch}")
+    _i32(dims, "dims", (B, 2)), _i32(boxes, "boxes", (N, 5)), _i32(patch_offsets, "patch_offsets", (N + 1,))
+    cols = torch.empty((total_patches, 3 * patch * patch), dtype=torch.float32, device=images_u8.device)
+    _lib.check(lib.dclip_patches_from_boxes_u8(images_u8.data_ptr(), dims.data_ptr(), boxes.data_ptr(), patch_offsets.data_ptr(),
+                                               cols.data_ptr(), B, Hmax, Wmax, N, patch, _stream()), "patches_from_boxes_u8")
+    return cols
+
+
+def vision_assemble_varlen(patch_emb, cls, pos, grids: torch.Tensor, cu_seqlens: torch.Tensor, g: int) -> torch.Tensor:
+    """Token rows [T, D] of N crops: per crop the class row and its patch rows plus the position table resampled to the crop's
+    grid (grids [N,2] = (gh,gw)); bit-equal per crop to vision_assemble_fwd over pos_interp_fwd.  T = patch rows + N."""
+    lib = _lib.load()
+    _f32(patch_emb, "patch_emb"), _f32(cls, "class_embedding"), _f32(pos, "position_embedding")
+    N = grids.shape[0]
+    if patch_emb.dim() != 2 or N < 1 or patch_emb.shape[0] < N:
+        raise ValueError(f"vision_assemble_varlen: {N} crops, patch_emb {tuple(patch_emb.shape)}")
+    D = patch_emb.shape[1]
+    if D % 4 or cls.numel() != D or tuple(pos.shape) != (1 + g * g, D):
+        raise ValueError(f"vision_assemble_varlen: D {D} (% 4 == 0), class_embedding {cls.numel()}, position table "
+                         f"{tuple(pos.shape)} for g = {g}")
+    _i32(grids, "grids", (N, 2)), _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    x = torch.empty((patch_emb.shape[0] + N, D), dtype=torch.float32, device=patch_emb.device)
+    _lib.check(lib.dclip_vision_assemble_varlen(patch_emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), grids.data_ptr(),
+                                                cu_seqlens.data_ptr(), x.data_ptr(), g, N, D, _stream()), "vision_assemble_varlen")
+    return x
+
+
+def attention_varlen_fwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_S: int, H: int, cls_only: bool = False,
+                         want_lse: bool = False):
+    """Non-causal self-attention inside each of the N packed sequences of qkv [T, 3*H*64] (rows cu_seqlens[n] ..
+    cu_seqlens[n+1]-1; T = cu_seqlens[N]): out [T, H*64], or with `cls_only` row 0 of each sequence, [N, H*64].  `max_S` bounds
+    the lengths.  Returns out, or (out, lse [H, T] / [H, N]) with `want_lse`."""
+    lib = _lib.load()
+    _f32(qkv, "qkv")
+    N = cu_seqlens.numel() - 1
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or N < 1 or H < 1 or max_S < 1 or qkv.shape[0] < N:
+        raise ValueError(f"attention_varlen_fwd: qkv {tuple(qkv.shape)}, H {H}, {N} sequences, max_S {max_S}")
+    _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    rows = N if cls_only else qkv.shape[0]
+    out = torch.empty((rows, H * 64), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((H, rows), dtype=torch.float32, device=qkv.device) if want_lse else None
+    _lib.check(lib.dclip_attention_varlen_fwd(qkv.data_ptr(), cu_seqlens.data_ptr(), out.data_ptr(), _ptr(lse), N, max_S, H,
+                                              int(bool(cls_only)), _stream()), "attention_varlen_fwd")
+    return (out, lse) if want_lse else out
+
+
+def gather_rows_at(x: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """out[n] = x[rows[n]]: x [T, D], rows [N] int32 in [0, T), any order."""
+    lib = _lib.load()
+    _f32(x, "x")
+    N = rows.numel()
+    if x.dim() != 2 or x.shape[1] % 4 or N < 1 or x.shape[0] < 1:
+        raise ValueError(f"gather_rows_at: x {tuple(x.shape)} (D % 4 == 0), {N} rows")
+    _i32(rows, "rows", (N,))
+    out = torch.empty((N, x.shape[1]), dtype=torch.float32, device=x.device)
+    _lib.check(lib.dclip_gather_rows_at(x.data_ptr(), rows.data_ptr(), out.data_ptr(), N, x.shape[0], x.shape[1], _stream()),
+               "gather_rows_at")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- evaluation
 
 def rowdot_gather(a, b, idx=None):

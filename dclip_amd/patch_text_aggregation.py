@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .clip_model import HipCLIPModel, _Affine
+from .clip_model import HipCLIPModel, _Affine, packed_crop_tables
 
 
 # ------------------------------------------------------------------------------------------------ cross-modal block
@@ -259,22 +259,27 @@ class CLIPPatchTokenizer:
         arr = np.asarray(pil_patch.convert("RGB").resize((s, s), Image.BILINEAR), dtype=np.float32) / 255.0
         return torch.from_numpy(arr).permute(2, 0, 1).contiguous()
 
+    def _upload_u8(self, images: Sequence):
+        """PIL images (or HWC uint8 arrays) -> (images_u8 [B,Hmax,Wmax,3] zero padded, dims [B,2] = (h, w)) on the device, in one
+        upload: the layout data.GpuCollate hands over."""
+        import numpy as np
+        dev = self.device
+        arrs = [np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.uint8) for im in images]
+        hmax, wmax = max(a.shape[0] for a in arrs), max(a.shape[1] for a in arrs)
+        batch = np.zeros((len(arrs), hmax, wmax, 3), dtype=np.uint8)
+        for b, a in enumerate(arrs):
+            batch[b, :a.shape[0], :a.shape[1]] = a
+        return torch.from_numpy(batch).to(dev), torch.tensor([a.shape[:2] for a in arrs], dtype=torch.int32).to(dev)
+
     def crop_boxes_gpu(self, images: Sequence, boxes_per_image: Sequence[Sequence], images_u8: Optional[torch.Tensor] = None,
                        dims: Optional[torch.Tensor] = None) -> tuple:
         """PIL images (or HWC uint8 arrays) + per-image box lists -> (regions [B,Rmax,3,S,S] in [0,1], counts [B]).
         The crops are cut, resized and converted on the GPU, bit-exact with `patch_transform` (Pillow).
         `images_u8` [B,Hmax,Wmax,3] + `dims` [B,2] (already on the device, data.GpuCollate) replace `images`."""
-        import numpy as np
         dev = self.device
         s = self.clip_model.config.vision.image_size
         if images_u8 is None:
-            arrs = [np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.uint8) for im in images]
-            hmax, wmax = max(a.shape[0] for a in arrs), max(a.shape[1] for a in arrs)
-            batch = np.zeros((len(arrs), hmax, wmax, 3), dtype=np.uint8)
-            for b, a in enumerate(arrs):
-                batch[b, :a.shape[0], :a.shape[1]] = a
-            images_u8 = torch.from_numpy(batch).to(dev)
-            dims = torch.tensor([a.shape[:2] for a in arrs], dtype=torch.int32).to(dev)
+            images_u8, dims = self._upload_u8(images)
         B = images_u8.shape[0]
         if len(boxes_per_image) != B:
             raise ValueError("crop_boxes_gpu: one box list per image")
@@ -341,6 +346,50 @@ class CLIPPatchTokenizer:
                 embs[i] = out[j]
         return [(e, conf) for e, (_, conf) in zip(embs, weighted_boxes)]
 
+    @staticmethod
+    def plan_full_resolution(boxes_per_image: Sequence[Sequence], patch: int) -> dict:
+        """Host-only: the tables of ONE packed tower pass over every full-resolution crop of a batch.
+        Coordinates are truncated to integers as in crop_boxes_gpu.  An image with any box of zero or negative extent, or with
+        any crop that has a side shorter than one patch, keeps NO region (count 0: the per-crop path's ValueError -> zero-row
+        rule, PatchTextAggregation._global_embedding_full_resolution).  Returns int32 host tensors `boxes` [N,5] =
+        (b, x1, y1, x2, y2), `grids` [N,2], `cu_seqlens` [N+1], `patch_offsets` [N+1], `cls_rows` [N]; `max_S`; `counts`
+        (regions kept per image, a list) and `slots` [N] int64 = b*Rmax + r, the row of crop n in a [B*Rmax, E] result
+        (Rmax = max(counts), at least 1)."""
+        flat, counts = [], []
+        for b, boxes in enumerate(boxes_per_image):
+            ints = [(int(x1), int(y1), int(x2), int(y2)) for (x1, y1, x2, y2), _conf in boxes]
+            if any(x2 - x1 < patch or y2 - y1 < patch for x1, y1, x2, y2 in ints):
+                counts.append(0)
+                continue
+            counts.append(len(ints))
+            flat += [(b,) + bx for bx in ints]
+        plan = packed_crop_tables(torch.tensor(flat, dtype=torch.int32).reshape(-1, 5), patch)
+        rmax = max(max(counts, default=0), 1)
+        plan.update(boxes=torch.tensor(flat, dtype=torch.int32).reshape(-1, 5), counts=counts,
+                    slots=torch.tensor([b * rmax + r for b, n in enumerate(counts) for r in range(n)], dtype=torch.int64))
+        return plan
+
+    @torch.no_grad()
+    def encode_full_resolution_batch(self, images: Optional[Sequence], boxes_per_image: Sequence[Sequence],
+                                     images_u8: Optional[torch.Tensor] = None, dims: Optional[torch.Tensor] = None) -> tuple:
+        """Every box of every image encoded at its own size in ONE packed pass of the frozen tower
+        (HipCLIPModel.get_image_features_crops): (emb [B,Rmax,E] zero padded, counts [B]).  `images` (PIL or HWC uint8 arrays)
+        are padded and uploaded once, as crop_boxes_gpu does; with `images_u8` [B,Hmax,Wmax,3] + `dims` [B,2] already on the
+        device (data.GpuCollate) no pixel returns to the host and Pillow is not touched: the crops are cut on the device."""
+        model = self.clip_model
+        plan = self.plan_full_resolution(boxes_per_image, model.config.vision.patch_size)
+        B, rmax = len(boxes_per_image), max(max(plan["counts"], default=0), 1)
+        dev = self.device
+        emb = torch.zeros((B, rmax, model.config.projection_dim), dtype=torch.float32, device=dev)
+        if plan["boxes"].shape[0]:
+            if images_u8 is None:
+                images_u8, dims = self._upload_u8(images)
+            if images_u8.shape[0] != B:
+                raise ValueError("encode_full_resolution_batch: one box list per image")
+            out = model.get_image_features_crops(images_u8, dims, plan["boxes"], precision=self.precision)
+            emb.view(B * rmax, -1).index_copy_(0, plan["slots"].to(dev), out)
+        return emb, torch.tensor(plan["counts"], dtype=torch.int32)
+
 
 # ------------------------------------------------------------------------------------------------ the teacher
 
@@ -348,12 +397,15 @@ class PatchTextAggregation(nn.Module):
     def __init__(self, embed_dim=512, num_heads=8, similarity_threshold=0.85, projection_model_path=None,
                  faiss_index_path=None, embeddings_json_path=None, clip_model: Optional[HipCLIPModel] = None,
                  tokenizer=None, tower_precision: str = "fp32", owns_clip: bool = False,
-                 text_twin: Optional[HipCLIPModel] = None):
+                 text_twin: Optional[HipCLIPModel] = None, full_resolution_packed: bool = False):
         """`tower_precision` ("fp32" default = the reference's arithmetic; "bf16" / "fp16" opt-in) selects how the FROZEN
         region / text towers multiply; the trainable cross_modal_attention always runs in fp32.
         `owns_clip`: the towers are this teacher's private frozen copy (they follow `.to()` / `.cuda()` although they
         stay out of `state_dict()`).  `text_twin`: a model whose text tower held the SAME weights as `clip_model`'s
-        when this teacher was built (the student a snapshot was taken from) — see shares_text_tower_with."""
+        when this teacher was built (the student a snapshot was taken from) — see shares_text_tower_with.
+        `full_resolution_packed` (also an attribute): with `full_resolution` on, all crops of a batch go through the region
+        tower in ONE packed pass, cut on the device (CLIPPatchTokenizer.encode_full_resolution_batch), instead
+        of one forward per crop size; the targets differ from the per-crop path's in the last bits."""
         super().__init__()
         if tower_precision not in ("fp32", "bf16", "fp16"):
             raise ValueError(f"tower_precision {tower_precision!r}")
@@ -381,6 +433,7 @@ class PatchTextAggregation(nn.Module):
             self.advanced_tokenizer = TokenizerWithKNN(clip_model, projection_model_path, faiss_index_path,
                                                        embeddings_json_path, similarity_threshold)
         self.full_resolution = False
+        self.full_resolution_packed = bool(full_resolution_packed)
 
     @property
     def device(self):
@@ -501,6 +554,8 @@ class PatchTextAggregation(nn.Module):
             if knn:
                 raise NotImplementedError("full_resolution with the KNN / projection tokenizer: its queries are crops at the "
                                           "model's size (training/image_tokenizer.py:236-251)")
+            if self.full_resolution_packed:
+                return self._global_embedding_full_resolution_packed(image_paths, texts, boxes, images_u8, dims)
             return self._global_embedding_full_resolution(image_paths, texts, boxes, images_u8, dims)
         images = None
         if images_u8 is None or knn:
@@ -554,6 +609,27 @@ class PatchTextAggregation(nn.Module):
         for b, es in enumerate(per_image):
             if es:
                 emb[b, :len(es)] = torch.stack(es)
+        ids = self.text_tokenizer._ids(texts if isinstance(texts, torch.Tensor) else list(texts))
+        with torch.no_grad():
+            sent, tokens, eos = self.text_tokenizer.token_level_ids(ids)
+            self.last_sentence_embedding = sent
+            text = ops.pack_tokens(tokens.contiguous(), sent, eos, max(int(eos.max()) - 1, 1))
+        return self.global_embedding_from_tokens(text, emb)
+
+    def _global_embedding_full_resolution_packed(self, image_paths, texts, boxes, images_u8=None, dims=None):
+        """`full_resolution` with `full_resolution_packed`: the same targets as _global_embedding_full_resolution up to the last
+        bits (the tower's GEMMs see all crops' rows at once), from one packed tower pass.  Images are opened only when no
+        uploaded batch is handed over.  Runs on the caller's stream."""
+        images = None
+        if images_u8 is None:
+            from PIL import Image
+            images = []
+            for path in image_paths:
+                try:
+                    images.append(Image.open(path).convert("RGB"))
+                except Exception:
+                    images.append(Image.new("RGB", (224, 224)))        # the reference's fallback (:302)
+        emb, _counts = self.patch_tokenizer.encode_full_resolution_batch(images, boxes, images_u8, dims)
         ids = self.text_tokenizer._ids(texts if isinstance(texts, torch.Tensor) else list(texts))
         with torch.no_grad():
             sent, tokens, eos = self.text_tokenizer.token_level_ids(ids)

@@ -224,6 +224,40 @@ int dclip_im2col_rect_bf16(const float* pixels, void* cols, int B, int C, int Hi
 int dclip_im2col_rect_f16(const float* pixels, void* cols, int B, int C, int Himg, int Wimg, int patch, int ldc, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The frozen vision tower on a PACKED batch of crops of different sizes: the full-resolution teacher in one
+ * pass.  Forward only.  N crops; crop n has the patch grid gh_n = (y2-y1)/p, gw_n = (x2-x1)/p (floor, both >= 1) and
+ * S_n = 1 + gh_n gw_n token rows.  cu_seqlens [N+1] (int32) are the cumulative token rows, T = cu_seqlens[N];
+ * patch_offsets [N+1] the cumulative patch rows, patch_offsets[n] = cu_seqlens[n] - n.  Both tables live on the device and are
+ * built on the host from the box list.  The layers between these entries are row-wise over M = T and run unchanged.
+ * patches_from_boxes_u8: replaces the per-crop host path (PIL crop + ToTensor + upload + dclip_im2col_rect).  images_u8
+ *   [B][Hmax][Wmax][3], dims [B][2] = (h, w), boxes [N][5] = (b, x1, y1, x2, y2) as dclip_crop_resize_u8 takes them.  cols row
+ *   patch_offsets[n] + gy*gw_n + gx, column c*p*p + py*p + px (the column order of dclip_im2col*) = pixel (y1 + gy*p + py,
+ *   x1 + gx*p + px) of image b, channel c, DIVIDED by 255 (a correctly rounded fp32 division, ToTensor()'s value).  A
+ *   position outside [0,h) x [0,w) of its own image gives 0 without a read (PIL's crop past an edge); the bytes of the
+ *   batch's padding are never used.  Rows and columns of a crop beyond whole patches are not read.  Any patch in [1, 1024];
+ *   16-byte stores when patch % 4 == 0.  cols 16-byte aligned.
+ * vision_assemble_varlen: replaces dclip_pos_interp_fwd + dclip_vision_assemble_fwd per crop.  grids [N][2] = (gh, gw).  x row
+ *   cu[n] = cls + pos[0]; row cu[n] + 1 + j = patch_emb[cu[n] - n + j] + R_n[1 + j], R_n = pos [1 + g*g][D] resampled to crop n's
+ *   grid by the arithmetic of pos_interp_fwd (same taps, same 16-term fmaf chain) and added by vision_assemble_fwd's
+ *   statement: per crop bit-equal to those two calls.  D % 4 == 0, 16-byte aligned float operands.
+ * attention_varlen_fwd: replaces dclip_attention_fwd / dclip_attention_cls_fwd per crop.  qkv [T][3*H*64]; non-causal
+ *   self-attention inside each sequence cu[n] .. cu[n+1]-1 and nowhere else.  cls_only = 0: out [T][H*64], lse [H][T];
+ *   cls_only = 1: only row 0 of each sequence is a query, out [N][H*64], lse [H][N].  lse may be NULL.  max_S bounds the
+ *   sequence lengths (it sizes the grid: query rows at or beyond max_S of a sequence are not computed).  Any S_n >= 1.
+ *   A sequence's loads never leave its own rows.
+ * gather_rows_at: out[n] = x[rows[n]], x [T][D], rows [N] in [0, T) in any order, repeats allowed (an index outside is
+ *   clamped): replaces dclip_gather_rows (which needs equal strides) for the last layer's residual on the CLS rows.
+ * Each refuses N <= 0, a bad shape, a null or misaligned pointer with DCLIP_EINVAL before any launch. */
+int dclip_patches_from_boxes_u8(const uint8_t* images_u8, const int32_t* dims, const int32_t* boxes,
+                                const int32_t* patch_offsets, float* cols, int B, int Hmax, int Wmax, int N, int patch,
+                                void* stream);
+int dclip_vision_assemble_varlen(const float* patch_emb, const float* cls, const float* pos, const int32_t* grids,
+                                 const int32_t* cu_seqlens, float* x, int g, int N, int D, void* stream);
+int dclip_attention_varlen_fwd(const float* qkv, const int32_t* cu_seqlens, float* out, float* lse, int N, int max_S, int H,
+                               int cls_only, void* stream);
+int dclip_gather_rows_at(const float* x, const int32_t* rows, float* out, int N, int T, int D, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Losses.
  * normalize_rows: xhat = x / max(||x||, eps), inv[b] = 1/max(||x||,eps)   (F.normalize,
  *   training/CLIP_image_distillation.py:545-546,:569-570; eps = 1e-12).
