@@ -138,6 +138,10 @@ SIGNATURES = {
     "dclip_split_f32_f16x3_rows": (I, [P, P, P, I, I, I, P]),
     "dclip_split16_weights_t": (I, [P, I, I, P, P, P]),
     "dclip_gemm_f16_scaled_rows_dev": (I, [P, P, P, P, I, I, I, I, I, I, I, P, P, P]),
+    "dclip_split_f32_f16x3_rows_colstats_workspace": (Z, [I, I]),
+    "dclip_split_f32_f16x3_rows_colstats": (I, [P, P, P, P, P, P, P, I, I, I, P, Z, P]),
+    "dclip_gemm_f16_wgrad_tokmajor_seg3_plan": (I, [I, I, I]),
+    "dclip_gemm_f16_wgrad_tokmajor_seg3": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, Z, P]),
     "dclip_gemm_f16_ex": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "dclip_gemm_f16_wgrad_tokmajor_plan": (I, [I, I, I]),
     "dclip_gemm_f16_wgrad_tokmajor": (I, [P, P, P, I, I, I, I, I, I, I, P, Z, P]),

@@ -51,6 +51,11 @@ struct GemmBf16Params {
   // row-scaled form (dclip_gemm_f16_scaled_rows_dev, the split-fp16 dgrads of DESIGN.md §9e; the ROWS kernel instances only)
   const float* row_alpha = nullptr;    // [M]: C[m][:] = epi(acc * alpha * row_alpha[m]), fp32 output
   const float* aux32 = nullptr;        // fp32 [M][ldc]: the pre-activation h of DGELU (the 16-bit `aux` is not used)
+  // segmented token-major form (dclip_gemm_f16_wgrad_tokmajor_seg3; the SEG kernel instance only): gridDim.y =
+  // 3 seg_splits, work item y contracts its share of the K rows of segment y / seg_splits, whose operands start a_seg / w_seg
+  // COLUMNS into A / W
+  int seg_splits = 0;
+  int a_seg[3] = {0, 0, 0}, w_seg[3] = {0, 0, 0};
 };
 
 // The ROWS epilogue of the register-staged and LDS-DMA kernels: v = acc * alpha for 4 columns of row `row`; x row_alpha, then
@@ -757,8 +762,11 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 // two lane groups of a half-wave (k-rows 8 apart) land on 32 different 8-byte bank pairs.  Same phases and barriers; the
 // DMA order is A1(kt+1) | - | A0(kt+2) | B0, B1(kt+2) (every half re-staged at least two phases after its last read, so
 // no lgkmcnt before a barrier is needed: phase 1 issues 24 reads, more than the 4-bit counter can express).
-template <class T, bool TOK, bool DEV = false, bool ROWS = false>
+// SEG (token-major only): the contraction is three segments of K rows; the split index selects the segment, so a work item
+// stays inside one segment and the K loop, phases and barriers are what they were.  Always split-K (>= 3 slabs).
+template <class T, bool TOK, bool DEV = false, bool ROWS = false, bool SEG = false>
 __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
+  static_assert(!SEG || (TOK && !DEV && !ROWS), "the segmented form is token-major, split-K, fp32 slabs");
   typedef typename T::x8 V8;
   constexpr int BM = 256, BN = 256, ROW = BKH;
   constexpr int BUF = (BM + BN) * ROW;   // bf16 elements per K-tile buffer: 256 A rows then 256 B rows of 128 bytes
@@ -783,12 +791,19 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   const int tile_m = first_m + (swz % per_group) % gsize, tile_n = (swz % per_group) / gsize;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   // split-K (gridDim.y > 1): this work item contracts k in [kbeg, kbeg + kspan), both multiples of 64 (host check)
-  const int kbeg = p.k_per_split ? blockIdx.y * p.k_per_split : 0;
+  int ksplit = blockIdx.y, a_col0 = 0, w_col0 = 0;
+  if constexpr (SEG) {
+    const int seg = (int)blockIdx.y / p.seg_splits;
+    ksplit = (int)blockIdx.y - seg * p.seg_splits;
+    a_col0 = seg == 0 ? p.a_seg[0] : (seg == 1 ? p.a_seg[1] : p.a_seg[2]);
+    w_col0 = seg == 0 ? p.w_seg[0] : (seg == 1 ? p.w_seg[1] : p.w_seg[2]);
+  }
+  const int kbeg = p.k_per_split ? ksplit * p.k_per_split : 0;
   const int kspan = (p.k_per_split ? min(p.K, kbeg + p.k_per_split) : p.K) - kbeg;
   const int nk = kspan / BKH;
 
-  const __bf16* a_org = TOK ? p.A + (size_t)kbeg * p.lda + m0 : p.A + (size_t)m0 * p.lda + kbeg;
-  const __bf16* w_org = TOK ? p.W + (size_t)kbeg * p.ldw + n0 : p.W + (size_t)n0 * p.ldw + kbeg;
+  const __bf16* a_org = TOK ? p.A + (size_t)kbeg * p.lda + m0 + a_col0 : p.A + (size_t)m0 * p.lda + kbeg;
+  const __bf16* w_org = TOK ? p.W + (size_t)kbeg * p.ldw + n0 + w_col0 : p.W + (size_t)n0 * p.ldw + kbeg;
   const int a_rows = min(BM, p.M - m0), w_rows = min(BN, p.N - n0);
   const size_t a_bytes = TOK ? ((size_t)(p.K - kbeg - 1) * p.lda + a_rows) * 2 : ((size_t)(a_rows - 1) * p.lda + (p.K - kbeg)) * 2,
                w_bytes = TOK ? ((size_t)(p.K - kbeg - 1) * p.ldw + w_rows) * 2 : ((size_t)(w_rows - 1) * p.ldw + (p.K - kbeg)) * 2;
@@ -1481,6 +1496,23 @@ __global__ void __launch_bounds__(256) splitk_reduce_bf16_kernel(const float* __
   }
 }
 
+// splitk_reduce_bf16_kernel for the segmented weight gradient: C[m][:] = ((sum of slabs) (1 / *act_scale)) *
+// row_scale[m].  The scalar first, as in the row-scaled dgrads: the reciprocal of a power of two is exact, and sums of 2^41
+// times an activation scale's reciprocal stay far inside fp32 before a row scale of 2^+-100 meets them.
+__global__ void __launch_bounds__(256) splitk_reduce_scaled_bf16_kernel(const float* __restrict__ slab, float* __restrict__ C, int M,
+                                                                        int N, int ldc, int splits,
+                                                                        const float* __restrict__ row_scale,
+                                                                        const float* __restrict__ act_scale) {
+  const float inv = 1.f / *act_scale;
+  const size_t total4 = (size_t)M * N / 4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
+    f32x4 s = *reinterpret_cast<const f32x4*>(slab + i * 4);
+    for (int z = 1; z < splits; ++z) s += *reinterpret_cast<const f32x4*>(slab + (size_t)z * M * N + i * 4);
+    const size_t row = (i * 4) / N, col = (i * 4) % N;
+    *reinterpret_cast<f32x4*>(C + row * ldc + col) = (s * inv) * row_scale[row];
+  }
+}
+
 inline int grid_for(size_t work) {
   size_t b = (work + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -1765,6 +1797,61 @@ DCLIP_API int dclip_gemm_f16_wgrad_tokmajor(const void* dY, const void* X, float
                                             int ldc, int splits, void* workspace, size_t workspace_bytes, void* stream) {
   return wgrad_tokmajor16<F16IeeeT>("gemm_f16_wgrad_tokmajor", dY, X, C, M, N, K, lddy, ldx, ldc, splits, workspace,
                                     workspace_bytes, stream);
+}
+
+// The segmented form: dW[M][N] = ((sum over three segments s of dY_s^T X_s) / *act_scale) * col_alpha[m], with
+// dY_s = the M columns of dY from column a_seg[s] on and X_s = the N columns of X from w_seg[s] on, fp16 token-major
+// [tokens][lddy] / [tokens][ldx].  With dY = [hi|lo] (a_seg 0, M, 0) and X = [hi|lo|hi] (w_seg 0, 0, N) the segments are the
+// three products hi.hi + lo.hi + hi.lo of the split-fp16 weight gradient, out of the operands as the step already has them.
+// `splits` work items per tile and segment (3 splits slabs of fp32 partials in the workspace: dclip_gemm_f16_splitk_workspace(M,
+// N, 3 splits)), fixed-order reduce that also applies the two scales.  _plan: the split count, 0 = this form does not apply
+// (tokens % 64, M / N % 8) and the caller takes the fp32 GEMM.
+DCLIP_API int dclip_gemm_f16_wgrad_tokmajor_seg3_plan(int M, int N, int tokens) {
+  if (M <= 0 || N <= 0 || tokens <= 0 || tokens % BKH != 0 || M % 8 != 0 || N % 8 != 0) return 0;
+  const long items = 3L * cdiv(M, 256) * cdiv(N, 256);       // work items at one split per segment
+  int s = items >= 256 ? 1 : (int)(256 / items);             // one round of 256 CUs
+  const int kmax = tokens / 512 > 0 ? tokens / 512 : 1;      // at least 8 K-tiles per work item
+  s = s > kmax ? kmax : s;
+  return s > 21 ? 21 : s;                                    // 3 s <= 64 slabs
+}
+
+DCLIP_API int dclip_gemm_f16_wgrad_tokmajor_seg3(const void* dY, const void* X, float* C, int M, int N, int tokens, int lddy, int ldx,
+                                                 int ldc, int a_seg0, int a_seg1, int a_seg2, int w_seg0, int w_seg1, int w_seg2,
+                                                 const float* col_alpha, const float* act_scale, int splits, void* workspace,
+                                                 size_t workspace_bytes, void* stream) {
+  const char* name = "gemm_f16_wgrad_tokmajor_seg3";
+  const int a_seg[3] = {a_seg0, a_seg1, a_seg2}, w_seg[3] = {w_seg0, w_seg1, w_seg2};
+  DCLIP_REQUIRE(dY && X && C && col_alpha && act_scale, "%s: null operand", name);
+  DCLIP_REQUIRE(M > 0 && N > 0 && tokens > 0 && tokens % BKH == 0 && M % 8 == 0 && N % 8 == 0 && splits >= 1 && splits <= 21,
+                "%s: M=%d N=%d (multiples of 8) tokens=%d (multiple of 64) splits=%d (1..21)", name, M, N, tokens, splits);
+  DCLIP_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0 && ldc % 4 == 0 && ldc >= N, "%s: leading dimensions", name);
+  for (int s = 0; s < 3; ++s)
+    DCLIP_REQUIRE(a_seg[s] >= 0 && w_seg[s] >= 0 && a_seg[s] % 8 == 0 && w_seg[s] % 8 == 0 && (long)a_seg[s] + M <= lddy &&
+                      (long)w_seg[s] + N <= ldx,
+                  "%s: segment %d (offsets are multiples of 8, offset + width within the leading dimension)", name, s);
+  DCLIP_REQUIRE(((uintptr_t)dY | (uintptr_t)X | (uintptr_t)C | (uintptr_t)workspace) % 16 == 0 &&
+                    ((uintptr_t)col_alpha | (uintptr_t)act_scale) % 4 == 0, "%s: alignment", name);
+  const int kps = cdiv(cdiv(tokens, splits), BKH) * BKH;
+  const int s_eff = cdiv(tokens, kps);
+  const size_t need = (size_t)3 * s_eff * M * N * sizeof(float);
+  if (!workspace || workspace_bytes < need) {
+    dclip_set_error("%s: needs %zu workspace bytes, got %zu", name, need, workspace_bytes);
+    return DCLIP_EWORKSPACE;
+  }
+  GemmBf16Params pb{(const __bf16*)dY, (const __bf16*)X, C, nullptr, nullptr, M, N, tokens, lddy, ldx, ldc, 0, 0, 0, 0, nullptr, kps,
+                    (float*)workspace};
+  pb.seg_splits = s_eff;
+  for (int s = 0; s < 3; ++s) pb.a_seg[s] = a_seg[s], pb.w_seg[s] = w_seg[s];
+  pb.tiles_m = cdiv(M, 256);
+  pb.tiles_n = cdiv(N, 256);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16IeeeT, true, false, false, true>), dim3(pb.tiles_m * pb.tiles_n, 3 * s_eff), dim3(512), 0,
+                     st, pb);
+  DCLIP_CHECK_LAUNCH_V(name, ".pp_tok_seg");
+  hipLaunchKernelGGL(splitk_reduce_scaled_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, st, (const float*)workspace, C,
+                     M, N, ldc, 3 * s_eff, col_alpha, act_scale);
+  DCLIP_CHECK_LAUNCH_V(name, ".pp_tok_seg.splitk_reduce");
+  return DCLIP_OK;
 }
 
 namespace {

@@ -15,6 +15,8 @@ namespace {
 
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
+typedef int i32x4s __attribute__((ext_vector_type(4)));
 
 // hi = fp16(v), lo = fp16(v - hi).  v - float(hi) is exact in fp32 (hi is v to 11 bits), so each piece has ONE rounding
 // whether or not the compiler folds the subtraction into the conversion.
@@ -144,6 +146,180 @@ __global__ void __launch_bounds__(256) split_rows_f16x3_kernel(const float* __re
     for (int i = lane; i < c8; i += 64)
       split_store8(yr + i * 8, cols, *reinterpret_cast<const f32x4*>(xr + i * 8), *reinterpret_cast<const f32x4*>(xr + i * 8 + 4),
                    scale);
+  }
+}
+
+// ---- the weight gradients' operand: dW[n,k] = sum_m dY[m,n] X[m,k] contracts over the ROWS of dY, so the
+// scale that can be undone after the product is one power of two per COLUMN n.  Three launches:
+//   1. split_rows_colstats_f16x3_kernel: split_rows_f16x3_kernel's row split, statement for statement, by waves that walk
+//      several rows (wave w of W takes rows w, w + W, ...) and keep, for the columns a lane owns, the running maximum of the
+//      bit patterns of |x| and the fp32 sum in row order; each wave writes its two partial rows to the workspace
+//      [2][W][cols] (maxima, then sums).  No atomics, no zero fill: every word read later is written here first.
+//   2. colstats_finish_kernel: the partials in wave order -> col_exp[n] (row_exp on the column maximum), col_alpha[n] =
+//      2^-e_n and the bias gradient db[n] = sum_m dY[m,n].
+//   3. split_cols_f16x2_kernel: yc[m] = [hi | lo] of dY[m,n] 2^e_n, fp16 [rows][2 cols].
+constexpr int COLSTAT_MAX_WAVES = 1024, COLSTAT_ROWS_PER_WAVE = 8;
+
+inline int colstat_waves(int rows) {
+  const int w = cdiv(rows, COLSTAT_ROWS_PER_WAVE);
+  return cdiv(w < COLSTAT_MAX_WAVES ? w : COLSTAT_MAX_WAVES, 4) * 4;      // whole workgroups of 4 waves
+}
+
+__device__ __forceinline__ void colstat8(unsigned* mx, float* sm, const f32x4& a, const f32x4& b) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float fa = a[e], fb = b[e];
+    const unsigned ua = __builtin_bit_cast(unsigned, fa) & 0x7fffffffu, ub = __builtin_bit_cast(unsigned, fb) & 0x7fffffffu;
+    mx[e] = mx[e] > ua ? mx[e] : ua;
+    mx[4 + e] = mx[4 + e] > ub ? mx[4 + e] : ub;
+    sm[e] += fa;
+    sm[4 + e] += fb;
+  }
+}
+
+template <int NC>
+__global__ void __launch_bounds__(256) split_rows_colstats_f16x3_kernel(const float* __restrict__ x, unsigned short* __restrict__ y,
+                                                                        float* __restrict__ row_alpha, unsigned* __restrict__ pmax,
+                                                                        float* __restrict__ psum, int rows, int cols, int ldx) {
+  const int lane = threadIdx.x & 63;
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6), W = gridDim.x * 4;
+  if (w >= rows) return;                                 // a wave without a row writes no partial (the finish counts min(W, rows))
+  const int c8 = cols >> 3;
+  unsigned* pm = pmax + (size_t)w * cols;
+  float* ps = psum + (size_t)w * cols;
+  if (NC > 0) {
+    unsigned cm[NC > 0 ? NC : 1][8];
+    float cs[NC > 0 ? NC : 1][8];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) cm[c][e] = 0u, cs[c][e] = 0.f;
+    for (int row = w; row < rows; row += W) {
+      const float* xr = x + (size_t)row * ldx;
+      unsigned short* yr = y + (size_t)row * 3 * cols;
+      f32x4 a[NC > 0 ? NC : 1], b[NC > 0 ? NC : 1];
+      unsigned m = 0u;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int i = lane + 64 * c, ic = i < c8 ? i : 0;
+        a[c] = *reinterpret_cast<const f32x4*>(xr + ic * 8);
+        b[c] = *reinterpret_cast<const f32x4*>(xr + ic * 8 + 4);
+      }
+#pragma unroll
+      for (int c = 0; c < NC; ++c) m = absmax8(m, a[c], b[c]);
+      const int e = row_exp(wave_umax_bits(m));
+      const float scale = pow2f(e);
+      if (lane == 0) row_alpha[row] = pow2f(-e);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int i = lane + 64 * c;
+        if (i < c8) split_store8(yr + i * 8, cols, a[c], b[c], scale);
+        colstat8(cm[c], cs[c], a[c], b[c]);              // (a chunk past the row holds chunk 0 again: never stored below)
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = lane + 64 * c;
+      if (i < c8) {
+        *reinterpret_cast<u32x4s*>(pm + i * 8) = u32x4s{cm[c][0], cm[c][1], cm[c][2], cm[c][3]};
+        *reinterpret_cast<u32x4s*>(pm + i * 8 + 4) = u32x4s{cm[c][4], cm[c][5], cm[c][6], cm[c][7]};
+        *reinterpret_cast<f32x4*>(ps + i * 8) = f32x4{cs[c][0], cs[c][1], cs[c][2], cs[c][3]};
+        *reinterpret_cast<f32x4*>(ps + i * 8 + 4) = f32x4{cs[c][4], cs[c][5], cs[c][6], cs[c][7]};
+      }
+    }
+  } else {
+    // any width: the running values live in the wave's own partial rows (written by the first row, updated by the others;
+    // a lane meets the same columns in every row, so its own earlier stores are all it reads back)
+    bool first = true;
+    for (int row = w; row < rows; row += W, first = false) {
+      const float* xr = x + (size_t)row * ldx;
+      unsigned short* yr = y + (size_t)row * 3 * cols;
+      unsigned m = 0u;
+      for (int i = lane; i < c8; i += 64)
+        m = absmax8(m, *reinterpret_cast<const f32x4*>(xr + i * 8), *reinterpret_cast<const f32x4*>(xr + i * 8 + 4));
+      const int e = row_exp(wave_umax_bits(m));
+      const float scale = pow2f(e);
+      if (lane == 0) row_alpha[row] = pow2f(-e);
+      for (int i = lane; i < c8; i += 64) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(xr + i * 8), b = *reinterpret_cast<const f32x4*>(xr + i * 8 + 4);
+        split_store8(yr + i * 8, cols, a, b, scale);
+        unsigned cm[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (!first) {
+          const u32x4s m0 = *reinterpret_cast<const u32x4s*>(pm + i * 8), m1 = *reinterpret_cast<const u32x4s*>(pm + i * 8 + 4);
+          const f32x4 s0 = *reinterpret_cast<const f32x4*>(ps + i * 8), s1 = *reinterpret_cast<const f32x4*>(ps + i * 8 + 4);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) cm[k] = m0[k], cm[4 + k] = m1[k], cs[k] = s0[k], cs[4 + k] = s1[k];
+        }
+        colstat8(cm, cs, a, b);
+        *reinterpret_cast<u32x4s*>(pm + i * 8) = u32x4s{cm[0], cm[1], cm[2], cm[3]};
+        *reinterpret_cast<u32x4s*>(pm + i * 8 + 4) = u32x4s{cm[4], cm[5], cm[6], cm[7]};
+        *reinterpret_cast<f32x4*>(ps + i * 8) = f32x4{cs[0], cs[1], cs[2], cs[3]};
+        *reinterpret_cast<f32x4*>(ps + i * 8 + 4) = f32x4{cs[4], cs[5], cs[6], cs[7]};
+      }
+    }
+  }
+}
+
+// 8 columns x 32 groups of partials per workgroup (cols / 8 workgroups: enough of them to hide the latency of the strided
+// reads): group g folds partials g, g + 32, ... in order, then the threads of group 0 fold the 32 groups in order — one fixed
+// sequence per column, the same in every run.
+constexpr int FIN_COLS = 8, FIN_GROUPS = 32;
+__global__ void __launch_bounds__(256) colstats_finish_kernel(const unsigned* __restrict__ pmax, const float* __restrict__ psum,
+                                                              int* __restrict__ col_exp, float* __restrict__ col_alpha,
+                                                              float* __restrict__ db, int nw, int cols) {
+  static_assert(FIN_COLS * FIN_GROUPS == 256, "one thread per (column, group)");
+  __shared__ unsigned smax[FIN_GROUPS][FIN_COLS];
+  __shared__ float ssum[FIN_GROUPS][FIN_COLS];
+  const int cl = threadIdx.x % FIN_COLS, g = threadIdx.x / FIN_COLS;
+  const int col = blockIdx.x * FIN_COLS + cl;
+  unsigned m = 0u;
+  float s = 0.f;
+  if (col < cols) {
+#pragma unroll 4
+    for (int w = g; w < nw; w += FIN_GROUPS) {
+      const unsigned pm = pmax[(size_t)w * cols + col];
+      m = m > pm ? m : pm;
+      s += psum[(size_t)w * cols + col];
+    }
+  }
+  smax[g][cl] = m;
+  ssum[g][cl] = s;
+  __syncthreads();
+  if (g == 0 && col < cols) {
+    for (int k = 1; k < FIN_GROUPS; ++k) {
+      m = m > smax[k][cl] ? m : smax[k][cl];
+      s += ssum[k][cl];
+    }
+    const int e = row_exp(m);
+    col_exp[col] = e;
+    col_alpha[col] = pow2f(-e);
+    if (db) db[col] = s;
+  }
+}
+
+// yc[m] = [hi | lo] of x[m,n] 2^e_n, 8 columns per thread: two 16-byte loads of x (and of the exponents), two 16-byte stores
+__global__ void __launch_bounds__(256) split_cols_f16x2_kernel(const float* __restrict__ x, const int* __restrict__ col_exp,
+                                                               unsigned short* __restrict__ yc, int rows, int cols, int ldx) {
+  const int c8 = cols >> 3;
+  const size_t total = (size_t)rows * c8;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % c8) * 8;
+    const size_t r = i / c8;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(x + r * ldx + c);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(x + r * ldx + c + 4);
+    const i32x4s ea = *reinterpret_cast<const i32x4s*>(col_exp + c), eb = *reinterpret_cast<const i32x4s*>(col_exp + c + 4);
+    u16x8 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      unsigned short h0, l0, h1, l1;
+      split1(a[e] * pow2f(ea[e]), h0, l0);
+      split1(b[e] * pow2f(eb[e]), h1, l1);
+      hi[e] = h0, lo[e] = l0, hi[4 + e] = h1, lo[4 + e] = l1;
+    }
+    unsigned short* yr = yc + r * 2 * cols + c;
+    *reinterpret_cast<u16x8*>(yr) = hi;
+    *reinterpret_cast<u16x8*>(yr + cols) = lo;
   }
 }
 
@@ -480,6 +656,31 @@ int split_rows_launch(const float* x, void* y, float* row_alpha, int rows, int c
   return DCLIP_OK;
 }
 
+int split_rows_colstats_launch(const float* x, void* y, float* row_alpha, unsigned* pmax, float* psum, int rows, int cols, int ldx,
+                                void* stream) {
+  dim3 grid(colstat_waves(rows) / 4), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned short* yy = (unsigned short*)y;
+  const int nc = cdiv(cols / 8, 64);
+  const char* variant;
+#define SPLITROWSC(NC)                                                                                                        \
+  do {                                                                                                                        \
+    hipLaunchKernelGGL((split_rows_colstats_f16x3_kernel<NC>), grid, block, 0, st, x, yy, row_alpha, pmax, psum, rows, cols,  \
+                       ldx);                                                                                                  \
+    variant = (NC) ? ".regs.nc" #NC : ".cached";                                                                              \
+  } while (0)
+  if (nc <= 1) SPLITROWSC(1);
+  else if (nc == 2) SPLITROWSC(2);
+  else if (nc == 3) SPLITROWSC(3);
+  else if (nc == 4) SPLITROWSC(4);
+  else if (nc == 5) SPLITROWSC(5);
+  else if (nc == 6) SPLITROWSC(6);
+  else SPLITROWSC(0);
+#undef SPLITROWSC
+  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_colstats", variant);
+  return DCLIP_OK;
+}
+
 int ln_launch(const char* name, const float* x, const float* gamma, const float* beta, void* y, int rows, int D, float eps,
               float scale, const float* scale_p, float* y32, float* mean, float* rstd, void* stream) {
   dim3 grid(cdiv(rows, 4)), block(256);
@@ -541,6 +742,45 @@ DCLIP_API int dclip_split_f32_f16x3_rows(const float* x, void* y, float* row_alp
   DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "split_f32_f16x3_rows: ldx must be a multiple of 4 and >= cols");
   DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0 && (uintptr_t)row_alpha % 4 == 0, "split_f32_f16x3_rows: alignment");
   return split_rows_launch(x, y, row_alpha, rows, cols, ldx, stream);
+}
+
+// dclip_split_f32_f16x3_rows (y and row_alpha bit-equal to it) that in the same pass over x takes the column statistics, and
+// from them: col_exp[n] = the row rule applied to max|x[:,n]|, col_alpha[n] = 2^-col_exp[n], db[n] = sum_m x[m,n]
+// (may be null) and yc fp16 [rows][2 cols] = [hi|lo] of x[m,n] 2^col_exp[n], the token-major operand of the segmented weight-
+// gradient GEMM.  Three launches, no atomics, the same bits in every run.  workspace: dclip_split_f32_f16x3_rows_colstats_workspace.
+DCLIP_API size_t dclip_split_f32_f16x3_rows_colstats_workspace(int rows, int cols) {
+  if (rows <= 0 || cols <= 0) return 0;
+  return (size_t)2 * colstat_waves(rows) * cols * sizeof(float);
+}
+
+DCLIP_API int dclip_split_f32_f16x3_rows_colstats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
+                                                  float* db, int rows, int cols, int ldx, void* workspace, size_t workspace_bytes,
+                                                  void* stream) {
+  DCLIP_REQUIRE(x && y && row_alpha && yc && col_exp && col_alpha && rows > 0 && cols > 0, "split_f32_f16x3_rows_colstats: bad arguments");
+  DCLIP_REQUIRE(cols % 8 == 0, "split_f32_f16x3_rows_colstats: cols=%d must be a multiple of 8", cols);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "split_f32_f16x3_rows_colstats: ldx must be a multiple of 4 and >= cols");
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)yc | (uintptr_t)col_exp | (uintptr_t)workspace) % 16 == 0 &&
+                    ((uintptr_t)row_alpha | (uintptr_t)col_alpha | (uintptr_t)db) % 4 == 0,
+                "split_f32_f16x3_rows_colstats: alignment");
+  const size_t need = dclip_split_f32_f16x3_rows_colstats_workspace(rows, cols);
+  if (!workspace || workspace_bytes < need) {
+    dclip_set_error("split_f32_f16x3_rows_colstats: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+    return DCLIP_EWORKSPACE;
+  }
+  const int W = colstat_waves(rows);
+  unsigned* pmax = (unsigned*)workspace;
+  float* psum = (float*)workspace + (size_t)W * cols;
+  const int rc = split_rows_colstats_launch(x, y, row_alpha, pmax, psum, rows, cols, ldx, stream);
+  if (rc != DCLIP_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(colstats_finish_kernel, dim3(cdiv(cols, FIN_COLS)), dim3(256), 0, st, (const unsigned*)pmax, (const float*)psum, col_exp,
+                     col_alpha, db, W < rows ? W : rows, cols);
+  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_colstats", ".finish");
+  const size_t blocks = ((size_t)rows * (cols / 8) + 255) / 256;
+  hipLaunchKernelGGL(split_cols_f16x2_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, st, x, (const int*)col_exp,
+                     (unsigned short*)yc, rows, cols, ldx);
+  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_colstats", ".cols");
+  return DCLIP_OK;
 }
 
 DCLIP_API int dclip_layernorm_fwd_f16x3(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,

@@ -94,16 +94,21 @@ def _fc1_gelu(a, p: LayerParams, save: bool, sp: Optional[Split16Layer]):
     return ops.split_f16x3_dev(g, sp.act("g")), h, g
 
 
-def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: float, save: bool, sp: Optional[Split16Layer] = None):
-    a, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1")
-    qkv = _linear(a, p.qkv_w, sp, "qkv", p.qkv_b)
+def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: float, save: bool, sp: Optional[Split16Layer] = None,
+              keep_split: bool = False):
+    """`keep_split` (with `save` and `sp`): the four [hi|lo|hi] operands this forward produced anyway — of ln1, the attention
+    context, ln2 and g — are kept as a 14th entry of `saved`, the X operands of the split-fp16 weight gradients."""
+    a1, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1")
+    qkv = _linear(a1, p.qkv_w, sp, "qkv", p.qkv_b)
     attn, lse = ops.attention_fwd(qkv, B, S, H, causal)
-    a = attn if sp is None else ops.split_f16x3_dev(attn, sp.act("ctx"))
-    x1 = _linear(a, p.out_w, sp, "out", p.out_b, residual=x)
-    a, ln2, m2, r2 = _ln_operand(x1, p.ln2_w, p.ln2_b, eps, save, sp, "ln2")
-    a, h, g = _fc1_gelu(a, p, save, sp)
-    x2 = _linear(a, p.fc2_w, sp, "fc2", p.fc2_b, residual=x1)
+    ac = attn if sp is None else ops.split_f16x3_dev(attn, sp.act("ctx"))
+    x1 = _linear(ac, p.out_w, sp, "out", p.out_b, residual=x)
+    a2, ln2, m2, r2 = _ln_operand(x1, p.ln2_w, p.ln2_b, eps, save, sp, "ln2")
+    ag, h, g = _fc1_gelu(a2, p, save, sp)
+    x2 = _linear(ag, p.fc2_w, sp, "fc2", p.fc2_b, residual=x1)
     saved = (x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g) if save else None
+    if save and keep_split and sp is not None:
+        saved = saved + ({"ln1": a1, "ctx": ac, "ln2": a2, "g": ag},)
     return x2, saved
 
 
@@ -118,10 +123,24 @@ def _galloc(alloc, name: str, shape, device) -> torch.Tensor:
     return t if t is not None else _fresh(name, shape, device)
 
 
-def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Tensor], wkey: str, bkey: str, alloc=None):
+def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Tensor], wkey: str, bkey: str, alloc=None,
+                       sp: Optional[Split16Layer] = None, act: Optional[str] = None, x3: Optional[torch.Tensor] = None):
     """dW = dy^T x and db = colsum(dy) of one nn.Linear.  When both are wanted the bias gradient comes out of the
-    weight-gradient GEMM (DCLIP_EPI_A_ROWSUM): dy is streamed once, no separate column-sum launch."""
+    weight-gradient GEMM (DCLIP_EPI_A_ROWSUM): dy is streamed once, no separate column-sum launch.
+    `sp`, `act`, `x3` (the forward's [hi|lo|hi] split of x, made with the plan scale sp.act(act)): the split-fp16 weight
+    gradient when the plan takes the shape — ONE pass over dy gives its row split (for _dgrad), its column
+    statistics, db and its column-scaled [hi|lo] split; dW is the segmented token-major GEMM of that with x3.  Returns the row
+    pieces (dy3, row_alpha) for _dgrad then, None otherwise."""
     dev = dy.device
+    if (need_w and sp is not None and x3 is not None and _VSPLIT16_WGRAD and dy.dim() == 2 and dy.stride(1) == 1 and
+            ops.gemm_f16_wgrad_tokmajor_seg3_plan(dy.shape[1], x.shape[1], dy.shape[0]) > 0):
+        M, N = dy.shape[1], x.shape[1]
+        db = _galloc(alloc, bkey, (M,), dev) if need_b else None
+        dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=db)
+        if need_b:
+            gr[bkey] = db
+        gr[wkey] = ops.gemm_f16_wgrad_tokmajor_seg3(yc, x3, M, N, col_alpha, sp.act(act), out=_galloc(alloc, wkey, (M, N), dev))
+        return dy3, row_alpha
     if need_w and need_b:
         gr[bkey] = _galloc(alloc, bkey, (dy.shape[1],), dev)
         gr[wkey] = ops.gemm(dy, x, ops.LAYOUT_TN, out=_galloc(alloc, wkey, (dy.shape[1], x.shape[1]), dev), a_rowsum=gr[bkey])
@@ -129,6 +148,7 @@ def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Te
         gr[wkey] = ops.gemm(dy, x, ops.LAYOUT_TN, out=_galloc(alloc, wkey, (dy.shape[1], x.shape[1]), dev))
     elif need_b:
         gr[bkey] = ops.colsum(dy, out=_galloc(alloc, bkey, (dy.shape[1],), dev))
+    return None
 
 
 def _ln_bwd(dy, x, gamma, mean, rstd, dresidual, want: bool, gr, wkey: str, bkey: str, alloc):
@@ -143,15 +163,16 @@ def _ln_bwd(dy, x, gamma, mean, rstd, dresidual, want: bool, gr, wkey: str, bkey
     return dx
 
 
-def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None):
+def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None):
     """dX = dy w (times quick_gelu'(aux) when given), the data gradient of a linear layer.  `sp` (a Split16Layer with
     transposed copies): dy is split with one scale per row and meets the [hi|hi|lo] copy of w^T on the fp16 MFMAs (DESIGN.md
-    §9e); None = the plain fp32 GEMM.  dy itself stays fp32 for the weight and bias gradients."""
+    §9e); None = the plain fp32 GEMM.  dy itself stays fp32 for the weight and bias gradients.  `rows`: the row pieces
+    (dy3, row_alpha) when linear_param_grads has already made them in its fused pass (§9f)."""
     if sp is None:
         if aux is None:
             return ops.gemm(dy, w, ops.LAYOUT_NN)
         return ops.gemm(dy, w, ops.LAYOUT_NN, aux=aux, epilogue=ops.EPI_DGELU)
-    dy3, row_alpha = ops.split_f16x3_rows(dy)
+    dy3, row_alpha = rows if rows is not None else ops.split_f16x3_rows(dy)
     return ops.gemm_f16_rows_dev(dy3, sp.wt[name], sp.walpha(name), row_alpha, dgelu_h=aux)
 
 
@@ -159,20 +180,24 @@ def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, 
               sp: Optional[Split16Layer] = None):
     """Returns (dx, grads) with grads keyed like LayerParams.FIELDS (missing = not needed).  `alloc(field, shape)`:
     see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad)."""
-    x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved
+    x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved[:13]
+    s3 = saved[13] if len(saved) > 13 and sp is not None else {}      # the forward's split operands (layer_fwd, keep_split)
     gr: Dict[str, torch.Tensor] = {}
-    linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc)
-    dh = _dgrad(dx2, p.fc2_w, sp, "fc2", aux=h)
-    linear_param_grads(dh, ln2, bool(need.get("fc1_w")), bool(need.get("fc1_b")), gr, "fc1_w", "fc1_b", alloc)
-    dln2 = _dgrad(dh, p.fc1_w, sp, "fc1")
+    rows = linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc, sp, "g", s3.get("g"))
+    dh = _dgrad(dx2, p.fc2_w, sp, "fc2", aux=h, rows=rows)
+    rows = linear_param_grads(dh, ln2, bool(need.get("fc1_w")), bool(need.get("fc1_b")), gr, "fc1_w", "fc1_b", alloc, sp, "ln2",
+                              s3.get("ln2"))
+    dln2 = _dgrad(dh, p.fc1_w, sp, "fc1", rows=rows)
     del dh
     dx1 = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc)
-    linear_param_grads(dx1, attn, bool(need.get("out_w")), bool(need.get("out_b")), gr, "out_w", "out_b", alloc)
-    dattn = _dgrad(dx1, p.out_w, sp, "out")
+    rows = linear_param_grads(dx1, attn, bool(need.get("out_w")), bool(need.get("out_b")), gr, "out_w", "out_b", alloc, sp, "ctx",
+                              s3.get("ctx"))
+    dattn = _dgrad(dx1, p.out_w, sp, "out", rows=rows)
     dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal)
-    linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc)
-    dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv")
-    del dqkv
+    rows = linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc, sp, "ln1",
+                              s3.get("ln1"))
+    dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv", rows=rows)
+    del dqkv, rows
     dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dx1, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc)
     return dx, gr
 
@@ -186,8 +211,10 @@ def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, 
 # zero).  K and V, hence the qkv projection, LayerNorm1 and their gradients, stay full size.  Results are identical
 # to the unpruned schedule (tests/test_model_gpu.py); 9/12 of that layer's GEMM work disappears.
 
-def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, save: bool, sp: Optional[Split16Layer] = None):
-    """`sp`: the full-size qkv projection takes the split-fp16 path (layer_fwd); the M = B GEMMs stay on ops.gemm."""
+def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, save: bool, sp: Optional[Split16Layer] = None,
+                       keep_split: bool = False):
+    """`sp`: the full-size qkv projection takes the split-fp16 path (layer_fwd); the M = B GEMMs stay on ops.gemm.
+    `keep_split`: ln1's split is kept for the qkv weight gradient (layer_fwd)."""
     D = x.shape[1]
     a, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1")
     qkv = _linear(a, p.qkv_w, sp, "qkv", p.qkv_b)
@@ -199,6 +226,8 @@ def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, sa
     g = ops.gemm(ln2, p.fc1_w, ops.LAYOUT_NT, bias=p.fc1_b, aux=h, epilogue=ops.EPI_GELU)
     x2 = ops.gemm(g, p.fc2_w, ops.LAYOUT_NT, bias=p.fc2_b, residual=x1)   # [B, D] = final hidden state, CLS rows
     saved = (x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g) if save else None
+    if save and keep_split and sp is not None:
+        saved = saved + ({"ln1": a},)
     return x2, saved
 
 
@@ -206,7 +235,8 @@ def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need:
                        sp: Optional[Split16Layer] = None):
     """dx2 [B, D] is the gradient w.r.t. the CLS rows of the final hidden state; returns (dx [B*S, D], grads).  `sp`: the
     full-size qkv data gradient takes the split-fp16 path (_dgrad); the M = B GEMMs stay on ops.gemm."""
-    x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved
+    x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved[:13]
+    s3 = saved[13] if len(saved) > 13 and sp is not None else {}
     D = x.shape[1]
     gr: Dict[str, torch.Tensor] = {}
     linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc)
@@ -217,9 +247,10 @@ def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need:
     linear_param_grads(dx1, attn, bool(need.get("out_w")), bool(need.get("out_b")), gr, "out_w", "out_b", alloc)
     dattn = ops.gemm(dx1, p.out_w, ops.LAYOUT_NN)
     dqkv = ops.attention_cls_bwd(qkv, attn, dattn, lse, B, S, H)          # [B*S, 3D]; d q only on the CLS rows
-    linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc)
-    dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv")
-    del dqkv
+    rows = linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc, sp, "ln1",
+                              s3.get("ln1"))
+    dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv", rows=rows)
+    del dqkv, rows
     dres = ops.scatter_rows(dx1, None, B, S, D)                           # the skip connection carries dx1 on CLS rows only
     dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dres, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc)
     return dx, gr
@@ -311,15 +342,17 @@ def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hid
     saved_layers = []
     prune = hidden_out is None and len(p.layers) > 0          # full hidden states are only materialised on request
     plan = _vision_split16_plan(p.layers, v, split16_cache) if save and split16_cache is not None and _VSPLIT16 else None
+    keep = False
     if plan is not None and split16_out is not None and _VSPLIT16_BWD and plan[0].wt is not None:
         split16_out.append(Split16Bwd(plan, split16_cache["__vsplit16__"], p.layers))
+        keep = _VSPLIT16_WGRAD            # that backward's weight gradients take the forward's split operands (§9f)
     for li, lp in enumerate(p.layers):
         sp = plan[li] if plan is not None else None
         if prune and li == len(p.layers) - 1:
-            cls_tok, sv = last_layer_fwd_cls(x, lp, B, S, H, v.layer_norm_eps, save, sp)
+            cls_tok, sv = last_layer_fwd_cls(x, lp, B, S, H, v.layer_norm_eps, save, sp, keep)
             saved_layers.append(sv)
             break
-        x, sv = layer_fwd(x, lp, B, S, H, False, v.layer_norm_eps, save, sp)
+        x, sv = layer_fwd(x, lp, B, S, H, False, v.layer_norm_eps, save, sp, keep)
         saved_layers.append(sv)
         if hidden_out is not None:
             hidden_out.append(x)
@@ -1252,6 +1285,9 @@ _VSPLIT16 = os.environ.get("DCLIP_VISION_SPLIT16", "1") != "0"    # read once at
 _VSPLIT16_FC1_EPI = os.environ.get("DCLIP_VISION_SPLIT16_FC1_EPI", "1") != "0"
 # the backward's full-size data-gradient GEMMs on the same plan, dY split per row; 0 = the plain fp32 dgrads
 _VSPLIT16_BWD = os.environ.get("DCLIP_VISION_SPLIT16_BWD", "1") != "0"
+# that backward's full-size weight-gradient GEMMs too, dY split per column; 0 = the plain fp32 wgrads.  Needs
+# the two switches above: the X operands are the forward's splits, and the fused dY pass is the split backward's
+_VSPLIT16_WGRAD = os.environ.get("DCLIP_VISION_SPLIT16_WGRAD", "1") != "0"
 
 
 def vision_split16_enabled() -> bool:
@@ -1303,6 +1339,12 @@ def split16_row_exp(r: float) -> int:
     if r == 0.0 or not math.isfinite(r):
         return 0
     return max(-100, min(100, _SPLIT16_TOP - math.frexp(abs(r))[1]))
+
+
+def split16_col_exp(r: float) -> int:
+    """split16_row_exp applied to a COLUMN maximum r = max|dY[:,n]|: the exponent of the column-scaled split of the weight
+    gradients' dY operand (dclip_split_f32_f16x3_rows_colstats) and the reference of its tests."""
+    return split16_row_exp(r)
 
 
 def split16_rows_host(x: torch.Tensor):

@@ -1373,6 +1373,65 @@ def gemm_f16_rows_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, row_alph
     return out
 
 
+def split_f16x3_rows_colstats(x: torch.Tensor, db: Optional[torch.Tensor] = None):
+    """split_f16x3_rows that in the same pass takes the column statistics ->
+    (y3, row_alpha, yc, col_exp, col_alpha): y3 / row_alpha as split_f16x3_rows gives them (bit for bit); col_exp int32 [cols] =
+    engine.split16_col_exp of max|x[:, n]|, col_alpha = 2^-col_exp; yc fp16 [rows, 2 cols] = [hi|lo] of x[m, n] 2^col_exp[n];
+    `db` (fp32 [cols]) receives the column sums."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("split_f16x3_rows_colstats: x must be a 2-D fp32 device tensor with unit column stride")
+    rows, cols = x.shape
+    if db is not None and (_f32(db, "db").numel() != cols):
+        raise ValueError("split_f16x3_rows_colstats: db size")
+    dev = x.device
+    y = torch.empty((rows, 3 * cols), dtype=torch.float16, device=dev)
+    ra = torch.empty((rows,), dtype=torch.float32, device=dev)
+    yc = torch.empty((rows, 2 * cols), dtype=torch.float16, device=dev)
+    ce = torch.empty((cols,), dtype=torch.int32, device=dev)
+    ca = torch.empty((cols,), dtype=torch.float32, device=dev)
+    nbytes = lib.dclip_split_f32_f16x3_rows_colstats_workspace(rows, cols)
+    ws = _ws.get(nbytes, dev)
+    _lib.check(lib.dclip_split_f32_f16x3_rows_colstats(x.data_ptr(), y.data_ptr(), ra.data_ptr(), yc.data_ptr(), ce.data_ptr(),
+                                                       ca.data_ptr(), _ptr(db), rows, cols, x.stride(0) if rows > 1 else cols,
+                                                       _ptr(ws), nbytes, _stream()), "split_f32_f16x3_rows_colstats")
+    return y, ra, yc, ce, ca
+
+
+def gemm_f16_wgrad_tokmajor_seg3_plan(M: int, N: int, tokens: int) -> int:
+    """The split count gemm_f16_wgrad_tokmajor_seg3 would take, 0 when the form does not apply to the shape."""
+    return int(_lib.load().dclip_gemm_f16_wgrad_tokmajor_seg3_plan(M, N, tokens))
+
+
+def gemm_f16_wgrad_tokmajor_seg3(dy: torch.Tensor, x: torch.Tensor, M: int, N: int, col_alpha: torch.Tensor, act_scale_ptr: int,
+                                 a_seg=None, w_seg=None, splits: Optional[int] = None,
+                                 out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """dW [M, N] fp32 = ((sum of three segments dy_s^T x_s) / *act_scale_ptr) * col_alpha[m] from fp16 token-major operands
+    dy [tokens, >= a_seg + M], x [tokens, >= w_seg + N].  The default segments pair dy = [hi|lo] with x =
+    [hi|lo|hi]: hi.hi + lo.hi + hi.lo.  None when the form does not apply (and `splits` is left to the plan)."""
+    lib = _lib.load()
+    _f16(dy, "dy"), _f16(x, "x")
+    if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0]:
+        raise ValueError("gemm_f16_wgrad_tokmajor_seg3: dy / x are [tokens, ld] with the same token count")
+    tokens = dy.shape[0]
+    a_seg = (0, M, 0) if a_seg is None else tuple(int(v) for v in a_seg)
+    w_seg = (0, 0, N) if w_seg is None else tuple(int(v) for v in w_seg)
+    if splits is None:
+        splits = lib.dclip_gemm_f16_wgrad_tokmajor_seg3_plan(M, N, tokens)
+        if splits == 0:
+            return None
+    if _f32(col_alpha, "col_alpha").numel() != M:
+        raise ValueError("gemm_f16_wgrad_tokmajor_seg3: col_alpha size")
+    out = _out_f32(out, (M, N), dy.device, "gemm_f16_wgrad_tokmajor_seg3")
+    nbytes = lib.dclip_gemm_f16_splitk_workspace(M, N, 3 * splits)
+    ws = _ws.get(nbytes, dy.device)
+    _lib.check(lib.dclip_gemm_f16_wgrad_tokmajor_seg3(dy.data_ptr(), x.data_ptr(), out.data_ptr(), M, N, tokens, dy.shape[1], x.shape[1],
+                                                      N, a_seg[0], a_seg[1], a_seg[2], w_seg[0], w_seg[1], w_seg[2],
+                                                      col_alpha.data_ptr(), act_scale_ptr, splits, _ptr(ws), nbytes, _stream()),
+               "gemm_f16_wgrad_tokmajor_seg3")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- fp16 training path
 # The bf16 training wrappers above with fp16 tensors (include/dclip_hip.h, "fp16 TRAINING path"): same shapes and limits,
 # IEEE rounding — a value beyond +-65504 becomes +-inf (the frozen fp16 wrappers above saturate), so that the overflow of a

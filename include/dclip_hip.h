@@ -614,6 +614,26 @@ int dclip_split16_weights_t(const void* refs, int nrefs, int tiles, const float*
 int dclip_gemm_f16_scaled_rows_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K, int lda, int ldw,
                                    int ldc, int epilogue, const float* alpha, const float* row_alpha, void* stream);
 
+/* ---- the student's vision WEIGHT gradients on split-fp16 operands.  dW[n][k] = sum_m dY[m][n] X[m][k] contracts
+ * over the tokens, so dY gets one power of two per COLUMN n (per row of dW), taken from the column's own maximum by the rule of
+ * the row split and undone after the product.
+ *   split_f32_f16x3_rows_colstats   dclip_split_f32_f16x3_rows (y, row_alpha bit-equal to it) that in the same pass over x takes the
+ *                            column maxima and sums, then: col_exp[n] (int), col_alpha[n] = 2^-col_exp[n], db[n] = sum_m x[m][n]
+ *                            (NULL = not wanted) and yc fp16 [rows][2 cols] = [hi|lo] of x[m][n] 2^col_exp[n].  Three launches, no
+ *                            atomics, the same bits in every run.  workspace: ..._colstats_workspace(rows, cols) bytes.
+ *   gemm_f16_wgrad_tokmajor_seg3    C[M][ldc] fp32 = ((sum over segments s = 0..2 of dY_s^T X_s) / *act_scale) * col_alpha[m], dY_s =
+ *                            columns a_seg_s .. a_seg_s + M of dY fp16 [tokens][lddy], X_s = columns w_seg_s .. w_seg_s + N of X fp16
+ *                            [tokens][ldx]; offsets are multiples of 8.  `splits` work items per tile and segment, 3 splits fp32
+ *                            slabs in the workspace (dclip_gemm_f16_splitk_workspace(M, N, 3 splits)), fixed-order reduce.
+ *                            _plan = the split count, 0 when the form does not apply (tokens % 64, M or N % 8). */
+size_t dclip_split_f32_f16x3_rows_colstats_workspace(int rows, int cols);
+int dclip_split_f32_f16x3_rows_colstats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha, float* db,
+                                        int rows, int cols, int ldx, void* workspace, size_t workspace_bytes, void* stream);
+int dclip_gemm_f16_wgrad_tokmajor_seg3_plan(int M, int N, int tokens);
+int dclip_gemm_f16_wgrad_tokmajor_seg3(const void* dY, const void* X, float* C, int M, int N, int tokens, int lddy, int ldx, int ldc,
+                                       int a_seg0, int a_seg1, int a_seg2, int w_seg0, int w_seg1, int w_seg2, const float* col_alpha,
+                                       const float* act_scale, int splits, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * fp16 TRAINING path (opt-in student_precision="fp16" / get_image_features(precision="fp16-mixed")): fp16
  * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
