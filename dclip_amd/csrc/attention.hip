@@ -626,8 +626,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a, const flo
 }
 
 // ------------------------------------------------------------------------------------------- backward, one tile, lean
-// S <= 64 (ViT-B/32's 50 tokens), the five-product schedule of attn_bwd_fused_kernel with 48 KiB of LDS instead of
-// 80 KiB (three workgroups per CU instead of two: the fused kernel is latency bound at 1.8 waves per SIMD):
+// Self-attention with S <= 64 (ViT-B/32's 50 tokens): the whole (batch, head) problem is one tile, so S / P / dP / dS are
+// formed ONCE and dQ, dK, dV all come out of one workgroup — 5 MFMA products instead of the 7 of the two-kernel path, q / k /
+// v / dO read once.  48 KiB of LDS, three workgroups per CU (a first form kept P and dS in LDS tiles, 80 KiB and two
+// workgroups per CU, and was latency bound at 1.8 waves per SIMD):
 //   phase A  wave w owns KEYS 16w..16w+15.  K and V own rows come straight from global as B-operand fragments; the
 //            Q and dO tiles are in LDS.  S = Q K^T and dP = dO V^T land as [query 4qd+r][key l15], so P and dS are
 //            the B operands of dV^T = dO^T P and dK^T = Q^T dS without leaving registers; dS is also written to
@@ -1124,99 +1126,6 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_from_ds_kernel(AttnArgs a, co
   }
 }
 
-// ------------------------------------------------------------------------------------------- backward, one tile
-// Self-attention with S <= 64 (ViT-B/32: S = 50): the whole (batch, head) problem is one tile, so S/P/dP/dS are
-// formed ONCE and dQ, dK, dV all come out of one workgroup — 5 MFMA products instead of the 7 of the two-kernel
-// path, q/k/v/dO read once.  P and dS live in LDS as ordinary swizzled tiles: read by rows (ds_read_b128) they are
-// the A operand of dQ = dS K, read by columns (ds_read_b32) they are the A operand of dV = P^T dO and dK = dS^T Q.
-// LDS: Q, K, V, dO, P tiles + dS aliased onto V (dead after dP) = 5 x 16 KiB = 80 KiB -> two workgroups per CU.
-
-template <bool CAUSAL>
-__global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(AttnArgs a, const float* __restrict__ out,
-                                                                const float* __restrict__ dout, const float* __restrict__ lse,
-                                                                float* __restrict__ dq_out, float* __restrict__ dk_out,
-                                                                float* __restrict__ dv_out, int ldd) {
-  __shared__ __attribute__((aligned(16))) float lds[5 * TS * HD];
-  float* Qs = lds;
-  float* Ks = lds + TS * HD;
-  float* Vs = lds + 2 * TS * HD;
-  float* dOs = lds + 3 * TS * HD;
-  float* Ps = lds + 4 * TS * HD;
-  float* dSs = Vs;  // V is dead once dP = dO V^T has been formed
-  const int H = a.H, S = a.Sk;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int qd = lane >> 4, l15 = lane & 15;
-  const int bh = blockIdx.x, b = bh / H, h = bh % H;
-  const int D = H * HD;
-  const float* qbase = a.q + (size_t)b * S * a.ldq + h * HD;
-  const float* kbase = a.k + (size_t)b * S * a.ldkv + h * HD;
-  const float* vbase = a.v + (size_t)b * S * a.ldkv + h * HD;
-  const float* obase = out + (size_t)b * S * D + h * HD;
-  const float* dobase = dout + (size_t)b * S * D + h * HD;
-
-  stage_tiles2(Qs, qbase, (size_t)a.ldq, Ks, kbase, (size_t)a.ldkv, 0, S);
-  stage_tiles2(Vs, vbase, (size_t)a.ldkv, dOs, dobase, (size_t)D, 0, S);
-  // delta and lse for this lane's 4 query rows (rows 16*wave + 4*qd + r): 16 lanes share a row -> each sums 4 floats
-  float dl[4], lse_r[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = 16 * wave + 4 * qd + r;
-    float s = 0.f;
-    if (row < S) {
-      f32x4 o4 = *reinterpret_cast<const f32x4*>(obase + (size_t)row * D + l15 * 4);
-      f32x4 d4 = *reinterpret_cast<const f32x4*>(dobase + (size_t)row * D + l15 * 4);
-      s = (o4[0] * d4[0] + o4[1] * d4[1]) + (o4[2] * d4[2] + o4[3] * d4[3]);
-    }
-    dl[r] = quarter_sum(s);
-    lse_r[r] = (row < S) ? lse[(size_t)bh * S + row] : 0.f;
-  }
-  __syncthreads();
-  f32x4 qf[4], dof[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    qf[g] = frag_k(Qs, 16 * wave, g, lane);
-    dof[g] = frag_k(dOs, 16 * wave, g, lane);
-  }
-  f32x4 s[4], dp[4];
-  zero4(s);
-  zero4(dp);
-  mma_rows_x_tileT(s, qf, Ks, lane);
-  mma_rows_x_tileT(dp, dof, Vs, lane);
-  __syncthreads();  // every wave is done reading V before dS overwrites it
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    const int key = nt * 16 + l15;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int qrow = 16 * wave + 4 * qd + r;
-      const bool masked = key >= S || qrow >= S || (CAUSAL && key > qrow);
-      const float p = masked ? 0.f : __expf(s[nt][r] * kScale - lse_r[r]);
-      Ps[tile_off(qrow, key)] = p;
-      dSs[tile_off(qrow, key)] = p * (dp[nt][r] - dl[r]) * kScale;
-    }
-  }
-  __syncthreads();
-  f32x4 dq[4], dk[4], dv[4];
-  zero4(dq);
-  zero4(dk);
-  zero4(dv);
-  mma_tilerows_x_tile(dq, dSs, 16 * wave, Ks, lane);   // dQ[q rows of this wave]   = dS K
-  mma_tilecols_x_tile(dv, Ps, 16 * wave, dOs, lane);   // dV[key rows of this wave] = P^T dO
-  mma_tilecols_x_tile(dk, dSs, 16 * wave, Qs, lane);   // dK[key rows of this wave] = dS^T Q
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = 16 * wave + 4 * qd + r;
-    if (row < S)
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const size_t o = ((size_t)b * S + row) * ldd + h * HD + nt * 16 + l15;
-        dq_out[o] = dq[nt][r];
-        dk_out[o] = dk[nt][r];
-        dv_out[o] = dv[nt][r];
-      }
-  }
-}
-
 // ------------------------------------------------------------------------------------------- backward, whole rows
 // Short self-attention (S <= 16*KT): one workgroup per (batch, head), wave w owns rows 16w..16w+15 both as QUERIES
 // (phase 1 -> dQ) and as KEYS (phase 2 -> dK, dV).  Each phase forms the score / dP blocks it needs directly in the
@@ -1473,16 +1382,10 @@ int launch_bwd(const AttnArgs& a, const float* out, const float* dout, const flo
     DCLIP_CHECK_LAUNCH("attention_bwd.rows");
     return DCLIP_OK;
   }
-  if (a.Sq == a.Sk && a.Sq <= TS && lddq == lddkv && !getenv("DCLIP_ATTN_FUSED")) {   // one tile, 48 KiB LDS, P / dS in registers
+  if (a.Sq == a.Sk && a.Sq <= TS && lddq == lddkv) {   // one tile, 48 KiB LDS, P / dS in registers
     if (causal) hipLaunchKernelGGL((attn_bwd_lean_kernel<true>), dim3(B * a.H), block, 0, st, a, out, dout, lse, dq, dk, dv, lddq);
     else hipLaunchKernelGGL((attn_bwd_lean_kernel<false>), dim3(B * a.H), block, 0, st, a, out, dout, lse, dq, dk, dv, lddq);
     DCLIP_CHECK_LAUNCH("attention_bwd.lean");
-    return DCLIP_OK;
-  }
-  if (a.Sq == a.Sk && a.Sq <= TS && lddq == lddkv) {  // one-tile self-attention: fused dQ/dK/dV
-    if (causal) hipLaunchKernelGGL((attn_bwd_fused_kernel<true>), dim3(B * a.H), block, 0, st, a, out, dout, lse, dq, dk, dv, lddq);
-    else hipLaunchKernelGGL((attn_bwd_fused_kernel<false>), dim3(B * a.H), block, 0, st, a, out, dout, lse, dq, dk, dv, lddq);
-    DCLIP_CHECK_LAUNCH("attention_bwd.fused");
     return DCLIP_OK;
   }
   if (a.Sq == a.Sk && !a.q_rows && !causal && !getenv("DCLIP_ATTN_TILED")) {

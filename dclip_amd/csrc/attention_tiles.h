@@ -102,24 +102,6 @@ __device__ __forceinline__ void mma_tilerows_x_tile(f32x4 (&acc)[4], const float
   }
 }
 
-// acc[nt] += A[k][cbase + (lane&15)] * B[k][16nt + (lane&15)]   (A transposed on the fly: column reads)
-__device__ __forceinline__ void mma_tilecols_x_tile(f32x4 (&acc)[4], const float* atile, int cbase, const float* btile,
-                                                    int lane) {
-  const int qd = lane >> 4, l15 = lane & 15;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    float af[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) af[r] = atile[tile_off(16 * g + 4 * qd + r, cbase + l15)];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[r], btile[tile_off(16 * g + 4 * qd + r, 16 * nt + l15)], acc[nt], 0,
-                                                       0, 0);
-  }
-}
-
 __device__ __forceinline__ void zero4(f32x4 (&a)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) a[i] = f32x4{0.f, 0.f, 0.f, 0.f};

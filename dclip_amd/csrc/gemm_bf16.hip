@@ -1,20 +1,20 @@
-// bf16-input GEMM on v_mfma_f32_32x32x16_bf16 (fp32 accumulate) for the FROZEN towers of the step — the teacher's
-// region encoder (training/image_tokenizer.py:119-120, 8 crops per image) and, optionally, the frozen text tower —
-// in BASELINE configs c3 / c5 ("bf16 MFMA").  Forward only:  C[M,N] = epilogue( A[M,K] W[N,K]^T ).
+// 16-bit-input GEMM on the bf16 / fp16 MFMAs (fp32 accumulate):  C[M,N] = epilogue( A[M,K] W[N,K]^T ), the split-K form of it,
+// and the token-major weight gradient dW = dY^T X.  Callers: the frozen towers in bf16 / fp16 (BASELINE configs c3 / c5, DESIGN.md
+// §9 / §9b), the bf16 / fp16 student's forward and backward (§13 / §13b), and the split-fp16 GEMMs of the fp32 towers (§9c-§9f).
 //
-// Same skeleton as gemm_f32.hip (block tile 128x128 or 64x64, 4 waves of 2x2 / 1x1 MFMA tiles, buffer-load staging
-// with a scalar K walk, double-buffered XOR-swizzled LDS, LDS-transposed 16-byte epilogue), with K-tiles of 64 bf16
-// = the same 128-byte rows: a lane (row = lane&31, half = lane>>5) reads 16-byte slot 2s+half and holds
-// k = 16s + 8*half + {0..7}, exactly one MFMA operand per ds_read_b128.  At 16x the fp32 MFMA rate the kernel is
-// bounded by L2 -> LDS traffic (64 KB per 512 MFMA cycles per workgroup), not by the matrix pipes.
+// gemm_bf16_kernel — gemm_f32.hip's skeleton (block tile 128x128 or 64x64, 4 waves of 2x2 / 1x1 MFMA tiles,
+// buffer-load staging with a scalar K walk, double-buffered XOR-swizzled LDS, LDS-transposed 16-byte epilogue) with K-tiles of
+// 64 elements = the same 128-byte rows: a lane (row = lane&31, half = lane>>5) reads 16-byte slot 2s+half and holds
+// k = 16s + 8*half + {0..7}, exactly one MFMA operand per ds_read_b128.  At 16x the fp32 MFMA rate it is bounded by L2 -> LDS
+// traffic (64 KB per 512 MFMA cycles per workgroup), not by the matrix pipes.  gemm_bf16_pp_kernel — the 256x256 ping-pong
+// kernel on LDS-DMA, one workgroup per CU, for K % 64 == 0 and at least DCLIP_BF16_BIG_MIN (default 128) tiles; also the
+// token-major and segmented weight-gradient forms.  gemm_bf16_ppp_kernel is its persistent form, opt-in and measured slower
+// (DCLIP_BF16_PERSIST=1, _PERSIST_MIN).  Those and DCLIP_BF16_BIG_MIN are the switches this file reads, each per call.
 //
-// fp16: every kernel of the FORWARD plan is a template over the 16-bit type (common.h, Bf16T / F16T) and has an fp16
-// instance, reached through dclip_gemm_f16 / dclip_cast_f32_f16 / dclip_layernorm_fwd_f16.  Only the MFMA
-// (v_mfma_f32_{32x32x16,16x16x32}_f16) and the rounding differ.  The training forms (split-K, token-major weight gradient,
-// DGELU, saved pre-activation) have a second fp16 instance with IEEE rounding (common.h, F16IeeeT), reached
-// through dclip_gemm_f16_ex / _splitk / _wgrad_tokmajor / dclip_cast_f32_f16_ieee / dclip_layernorm_fwd_f16_stats: only the
-// kernels of the default plans (ping-pong, register-staged 128x128 / 64x64) are instantiated for it, so the A/B switches
-// DCLIP_BF16_PP / _MID_DMA / _PERSIST do not apply there.
+// Types: every kernel is a template over the 16-bit type (common.h: Bf16T, F16T, F16IeeeT); only the MFMA
+// (v_mfma_f32_{32x32x16,16x16x32}_{bf16,f16}) and the rounding differ.  F16T (saturating) serves the frozen towers and the
+// split-fp16 entries (dclip_gemm_f16 / _scaled* / dclip_cast_f32_f16 / dclip_layernorm_fwd_f16), F16IeeeT the fp16 training
+// path (dclip_gemm_f16_ex / _splitk / _wgrad_tokmajor* / dclip_cast_f32_f16_ieee / dclip_layernorm_fwd_f16_stats).
 #include "common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -58,7 +58,7 @@ struct GemmBf16Params {
   int a_seg[3] = {0, 0, 0}, w_seg[3] = {0, 0, 0};
 };
 
-// The ROWS epilogue of the register-staged and LDS-DMA kernels: v = acc * alpha for 4 columns of row `row`; x row_alpha, then
+// The ROWS epilogue of the register-staged kernel: v = acc * alpha for 4 columns of row `row`; x row_alpha, then
 // gemm_f32_kernel's EPI_DGELU statement on the fp32 h, one 16-byte store.
 __device__ __forceinline__ void store_rows4(const GemmBf16Params& p, f32x4 v, int row, size_t off) {
   v = v * p.row_alpha[row];
@@ -331,211 +331,15 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBf16Params p) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Large-problem variant (template; instantiated as 256x256x64, 8 waves = 2 x 4, wave tile 128x64 = 4x2 MFMA tiles,
-// one workgroup per CU).  At the bf16 MFMA rate the 128x128 kernel above is bound by its LDS traffic (registers -> ds_write_b128
-// moves 79 B/clk/CU: 32 KB per 512 MFMA cycles).  Here
-//   * global -> LDS goes by `buffer_load_dwordx4 ... lds` (LDS-DMA, gfx950): no staging registers, no ds_write; the
-//     XOR swizzle is applied on the GLOBAL side — lane i of a piece owns LDS granule i, and fetches the 16 bytes
-//     that belong there; rows past M / N are outside the buffer descriptor and arrive as zeros;
-//   * a wave tile of 128x64 needs 6 ds_read_b128 per 8 MFMAs (the 64x64 wave tile: 4 per 4), 37 % of the LDS read
-//     rate at full MFMA rate;
-//   * the next K-tile's 8 DMA pieces per wave are issued before the current tile's 32 MFMAs; one
-//     `s_waitcnt vmcnt(0)` + barrier per K-tile.
-// Requires K % 64 == 0 (a ragged row tail cannot be zeroed on the DMA path) — every projection of the towers.
+// LDS-DMA (`buffer_load_dwordx4 ... lds`, gfx950) of the ping-pong kernel below: no staging registers, no ds_write.  The XOR
+// swizzle is applied on the GLOBAL side — lane i of a piece owns LDS granule i, and fetches the 16 bytes that belong there; rows
+// past M / N are outside the buffer descriptor and arrive as zeros.  Requires K % 64 == 0 (a ragged row tail cannot be zeroed
+// on the DMA path) — every projection of the towers.
 // 16 bytes per lane, global -> LDS without passing through registers: lane i lands at lds_dst + 16 i.
 // (A __device__ function on purpose: with the builtin inside a lambda of the kernel template, hipcc 7.2 silently drops
 // the template's host stub.)
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, __bf16* lds_dst, int voff, int soff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-}
-
-template <class T, int BM, int BN, int WM, int WN, bool ROWS = false>
-__global__ void __launch_bounds__(WM * WN * 64) gemm_bf16_dma_kernel(GemmBf16Params p) {
-  typedef typename T::x8 V8;
-  constexpr int NW = WM * WN, NTHR = NW * 64;
-  constexpr int TM = BM / WM, TN = BN / WN, MT = TM / 32, NT = TN / 32;
-  constexpr int ROW = BKH;
-  constexpr int STAGE = (BM + BN) * ROW;  // bf16 elements per stage: A tile then B tile
-  constexpr int PA = BM / 8 / NW, PB = BN / 8 / NW;   // DMA pieces (8 rows x 128 B) per wave and K-tile
-  static_assert(PA * NW * 8 == BM && PB * NW * 8 == BN && MT % 2 == 0 && PA + PB == 8, "tile / wave shape");
-  // static LDS (128 KiB for the 256x256 tile): a static declaration may use the whole 160 KiB of a CU
-  __shared__ __attribute__((aligned(16))) unsigned char lds_raw[2 * STAGE * 2];
-  __bf16* lds = reinterpret_cast<__bf16*>(lds_raw);  // [2][A BMx64 | B BNx64]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-  const int l31 = lane & 31, half = lane >> 5;
-
-  constexpr int GROUP_M = 8;
-  const int nwg = p.tiles_m * p.tiles_n;
-  const int swz = xcd_remap16(blockIdx.x, nwg);
-  const int per_group = GROUP_M * p.tiles_n;
-  const int first_m = (swz / per_group) * GROUP_M;
-  const int gsize = min(GROUP_M, p.tiles_m - first_m);
-  const int tile_m = first_m + (swz % per_group) % gsize, tile_n = (swz % per_group) / gsize;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int nk = p.K / BKH;
-
-  const __bf16* a_org = p.A + (size_t)m0 * p.lda;
-  const __bf16* w_org = p.W + (size_t)n0 * p.ldw;
-  const int a_rows = min(BM, p.M - m0), w_rows = min(BN, p.N - n0);
-  const size_t a_bytes = ((size_t)(a_rows - 1) * p.lda + p.K) * 2, w_bytes = ((size_t)(w_rows - 1) * p.ldw + p.K) * 2;
-  const __amdgpu_buffer_rsrc_t a_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a_org), 0, (int)min(a_bytes, (size_t)0x7fffffff), 0x00020000);
-  const __amdgpu_buffer_rsrc_t w_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(w_org), 0, (int)min(w_bytes, (size_t)0x7fffffff), 0x00020000);
-  // piece pc = 8 rows x 8 granules; wave w owns pieces w, w+NW, ... of A and of B.
-  // lane -> (row, stored slot); it fetches logical granule slot ^ ((row>>1)&7) of that row.
-  int a_voff[PA], w_voff[PB];
-#pragma unroll
-  for (int q = 0; q < PA; ++q) {
-    const int row = (wave + NW * q) * 8 + (lane >> 3), g = (lane & 7) ^ ((row >> 1) & 7);
-    a_voff[q] = row < a_rows ? (row * p.lda + g * 8) * 2 : 0x7fffffff;   // out of range -> zeros in LDS
-  }
-#pragma unroll
-  for (int q = 0; q < PB; ++q) {
-    const int row = (wave + NW * q) * 8 + (lane >> 3), g = (lane & 7) ^ ((row >> 1) & 7);
-    w_voff[q] = row < w_rows ? (row * p.ldw + g * 8) * 2 : 0x7fffffff;
-  }
-  // one of this wave's 8 DMA pieces of a stage: x < PA A pieces, then B pieces
-  auto issue_piece = [&](int buf, int kt, int x) {
-    __bf16* sa = lds + buf * STAGE;
-    __bf16* sb = sa + BM * ROW;
-    if (x < PA) dma16(a_rsrc, sa + (wave + NW * x) * 8 * ROW, a_voff[x < PA ? x : 0], kt * (BKH * 2));
-    else dma16(w_rsrc, sb + (wave + NW * (x - PA)) * 8 * ROW, w_voff[x >= PA ? x - PA : 0], kt * (BKH * 2));
-  };
-
-  f32x16 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  auto read_frags = [&](const __bf16* a, const __bf16* b, int s, V8 (&fa)[MT], V8 (&fb)[NT]) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const int row = wm * TM + i * 32 + l31;
-      fa[i] = *reinterpret_cast<const V8*>(a + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
-    }
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int row = wn * TN + j * 32 + l31;
-      fb[j] = *reinterpret_cast<const V8*>(b + row * ROW + (((2 * s + half) ^ ((row >> 1) & 7)) << 3));
-    }
-  };
-
-#pragma unroll
-  for (int x = 0; x < 8; ++x) issue_piece(0, 0, x);
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    const bool more = kt + 1 < nk;
-    const __bf16* a = lds + buf * STAGE;
-    const __bf16* b = a + BM * ROW;
-    V8 fa[2][MT], fb[2][NT];
-    read_frags(a, b, 0, fa[0], fb[0]);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if (s + 1 < 4) read_frags(a, b, s + 1, fa[(s + 1) & 1], fb[(s + 1) & 1]);
-      // The waves sharing a SIMD run this code in step (one barrier per K-tile): DMA issues are spread two per k-step
-      // BETWEEN halves of the MFMA block, so that while one wave is held in a DMA issue its partner still has matrix
-      // work to feed the pipe with (all eight at the top of the tile would idle it for both).
-#pragma unroll
-      for (int i = 0; i < MT; ++i) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[i][j] = T::mfma32(fa[s & 1][i], fb[s & 1][j], acc[i][j]);
-        if (i == MT / 2 - 1 || i == MT - 1) {
-          __builtin_amdgcn_sched_barrier(0);
-          if (more) issue_piece(buf ^ 1, kt + 1, 2 * s + (i == MT - 1 ? 1 : 0));
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // the next stage has landed (this wave's pieces) ...
-    __syncthreads();                     // ... and everybody's; everyone is done reading `buf`
-  }
-
-  // ---- epilogue: PASSES slabs of rows through the (dead) staging LDS, 16-byte rows out
-  constexpr int LDS_BYTES = 2 * STAGE * 2;
-  constexpr int PASSES = BM * BN * 4 / LDS_BYTES;      // 256x256: 2 (one per wave row), 128x128: 1
-  constexpr int PROWS = BM / PASSES;
-  static_assert(PASSES == 1 || (PASSES == WM && PROWS == TM), "a pass must cover whole wave rows");
-  float* ct = reinterpret_cast<float*>(lds_raw);  // [PROWS][BN]
-#pragma unroll
-  for (int hm = 0; hm < PASSES; ++hm) {
-    if (PASSES == 1 || wm == hm) {
-      const int rbase = PASSES == 1 ? wm * TM : 0;
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r)
-            ct[(rbase + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * BN + wn * TN + j * 32 + l31] = acc[i][j][r];
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int q = 0; q < PROWS * BN / 4 / NTHR; ++q) {
-      const int id = tid + q * NTHR;
-      const int lr = id / (BN / 4), lc = (id % (BN / 4)) * 4;
-      const int row = m0 + hm * PROWS + lr, col = n0 + lc;
-      if (row >= p.M || col >= p.N) continue;
-      f32x4 v = *reinterpret_cast<const f32x4*>(ct + lr * BN + lc) * dev_alpha(p);
-      if (ROWS) {
-        store_rows4(p, v, row, (size_t)row * p.ldc + col);
-        continue;
-      }
-      if (p.epilogue & DCLIP_EPI_BIAS) v += *reinterpret_cast<const f32x4*>(p.bias + col);
-      const size_t off = (size_t)row * p.ldc + col;
-      if (p.epilogue & DCLIP_EPI_GELU) {
-        if (p.h32) *reinterpret_cast<f32x4*>(p.h32 + (size_t)row * p.N + col) = v;
-        if (p.aux) {
-          u16x4 h = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
-          *reinterpret_cast<u16x4*>(p.aux + off) = h;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = T::to_f32(h[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
-      }
-      if (p.epilogue & DCLIP_EPI_DGELU) {
-        const f32x4 h = load16x4<T>(p.aux + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(h[e]);
-      }
-      if (p.epilogue & DCLIP_EPI_RESIDUAL) v += *reinterpret_cast<const f32x4*>(p.residual + off);
-      if (p.out_scale != 0.f) {
-        if (p.g32) *reinterpret_cast<f32x4*>(p.g32 + (size_t)row * p.N + col) = v;
-        store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, dev_out_scale(p));
-      } else if (p.out_bf16) {
-        u16x4 o = {T::bits(v[0]), T::bits(v[1]), T::bits(v[2]), T::bits(v[3])};
-        *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned short*>(p.C) + off) = o;
-      } else {
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + off) = v;
-      }
-    }
-    if (hm + 1 < PASSES) __syncthreads();
-  }
-}
-
-template <class T, int BM, int BN, int WM, int WN>
-int launch_dma(GemmBf16Params p, hipStream_t st) {
-  p.tiles_m = cdiv(p.M, BM);
-  p.tiles_n = cdiv(p.N, BN);
-  if constexpr (std::is_same<T, F16T>::value) {   // the row-scaled entry exists for F16T only
-    if (p.row_alpha) {
-      hipLaunchKernelGGL((gemm_bf16_dma_kernel<T, BM, BN, WM, WN, true>), dim3(p.tiles_m * p.tiles_n), dim3(WM * WN * 64), 0, st, p);
-      return DCLIP_OK;
-    }
-  }
-  hipLaunchKernelGGL((gemm_bf16_dma_kernel<T, BM, BN, WM, WN>), dim3(p.tiles_m * p.tiles_n), dim3(WM * WN * 64), 0, st, p);
-  return DCLIP_OK;
 }
 
 // the register-staged kernel on BM x BM tiles (p.tiles_m / tiles_n set by the caller), its ROWS instance for a row-scaled call
@@ -736,9 +540,10 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 // ---------------------------------------------------------------------------------------------------------------
 // Ping-pong variant of the 256x256x64 tile (8 waves = 2 x 4, wave tile 128x64, v_mfma_f32_16x16x32_bf16): the two
 // waves of a SIMD belong to different wave rows (wr = wave >> 2) and run ONE BARRIER APART, so that while one issues
-// its LDS fragment reads and the next LDS-DMA pieces the other has the matrix pipe — the K loop of the kernel above
-// runs both waves of a SIMD in step (one barrier per K-tile) and measures ~4.2k cycles per K-tile against the 2,048
-// of the MFMAs alone.  Per K-tile four phases, one 64x32 quadrant of the wave tile each (16 MFMAs = 256 cycles):
+// its LDS fragment reads and the next LDS-DMA pieces the other has the matrix pipe — a K loop that runs both waves of
+// a SIMD in step (one barrier per K-tile: the lock-step kernel this one replaced) measured ~4.2k cycles
+// per K-tile against the 2,048 of the MFMAs alone.  Per K-tile four phases, one 64x32 quadrant of the wave tile each
+// (16 MFMAs = 256 cycles):
 //     phase 1  read B(qn 0) 4 + A(qm 0) 8 fragments | DMA A-half 1 of tile kt+1 | MFMA quadrant (0,0)
 //     phase 2  read B(qn 1) 4                         | DMA B-half 0 of tile kt+2 | MFMA (0,1)
 //     phase 3  read A(qm 1) 8                         | DMA A-half 0 of tile kt+2 | MFMA (1,1)
@@ -1407,12 +1212,6 @@ int launch_pp(GemmBf16Params p, hipStream_t st, int splits = 1) {
   return DCLIP_OK;
 }
 
-// A/B switch: DCLIP_BF16_PP=0 selects the lock-step 256x256 kernel (and the 128x128 split-K form) instead of the ping-pong one
-bool pingpong_enabled() {
-  static const bool on = !(getenv("DCLIP_BF16_PP") && atoi(getenv("DCLIP_BF16_PP")) == 0);
-  return on;
-}
-
 // y[i] = bf16(x[i]); rows of `cols` floats written with leading dimension ldy (>= cols, zero padded)
 template <class T>
 __global__ void __launch_bounds__(256) cast_bf16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, int rows,
@@ -1533,12 +1332,6 @@ DCLIP_API int dclip_gemm_bf16(const void* A, const void* W, void* C, const float
 }
 
 namespace {
-// fp16 of the training path (F16IeeeT): the ping-pong and register-staged kernels only, whatever the A/B switches say
-template <class T>
-constexpr bool kTrain16 = std::is_same<T, F16IeeeT>::value;
-template <class T>
-bool pp16() { return kTrain16<T> || pingpong_enabled(); }
-
 // the device-memory operands of the device-scaled entries (GemmBf16Params' last four members)
 struct DevScales {
   const float* alpha_p;
@@ -1553,9 +1346,13 @@ inline void set_dev(GemmBf16Params& p, const DevScales* d) {
          p.aux32 = d->aux32;
 }
 
-// The forward dispatcher of both 16-bit types: same checks, same plan.  Every kernel it can pick — register-staged 128x128 /
-// 64x64, LDS-DMA 128x128 (DCLIP_BF16_MID_DMA) and 256x256 (DCLIP_BF16_PP=0), ping-pong, persistent (DCLIP_BF16_PERSIST) — has
-// an instance per type, and the DCLIP_BF16_* switches select among them for fp16 exactly as for bf16.
+// fp16 of the training path (F16IeeeT): the ping-pong and register-staged kernels only (no persistent instance)
+template <class T>
+constexpr bool kTrain16 = std::is_same<T, F16IeeeT>::value;
+
+// The forward dispatcher of every 16-bit type: same checks, same plan.  Each kernel it can pick — ping-pong 256x256,
+// register-staged 128x128 / 64x64 — has an instance per type; the persistent form (DCLIP_BF16_PERSIST) for bf16 and the
+// saturating fp16.
 template <class T>
 int gemm16(const char* name, const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux, int M,
            int N, int K, int lda, int ldw, int ldc, int epilogue, int out_bf16, void* stream, float alpha = 1.f, float out_scale = 0.f,
@@ -1575,10 +1372,9 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_BIAS) || bias, "%s: BIAS without bias", name);
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_RESIDUAL) || (residual && !out_bf16), "%s: RESIDUAL needs an fp32 output", name);
   hipStream_t st = (hipStream_t)stream;
-  // LDS-DMA kernel (K % 64 == 0, at least 128 workgroups): measured faster than the register-staged 128x128
-  // kernel AND than a 128x128 LDS-DMA variant (two workgroups per CU) on every tower shape, short K included
-  // (tools/bf16_gemm_bench.py).  With fp32 outputs and K = 768 it is bound by writing C (944 MB for the qkv
-  // projection of 2048 crops): one workgroup per CU cannot overlap that with the next tile's MFMAs.
+  // Ping-pong kernel (K % 64 == 0, at least 128 workgroups): measured faster than the register-staged 128x128 kernel on
+  // every tower shape, short K included (tools/bf16_gemm_bench.py).  With fp32 outputs and K = 768 it is bound by writing C
+  // (944 MB for the qkv projection of 2048 crops): one workgroup per CU cannot overlap that with the next tile's MFMAs.
   const int big_min = getenv("DCLIP_BF16_BIG_MIN") ? atoi(getenv("DCLIP_BF16_BIG_MIN")) : 128;   // tuning aid (read per call)
   if (K % BKH == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= big_min) {
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
@@ -1588,41 +1384,19 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
     // overlaps the K loop of the next.  DGELU (an extra side operand in the epilogue) stays on the one-tile kernel, and so does
     // GELU with an fp32 C: the persistent kernel's fp32 store path applies bias and residual only (it returned the
     // pre-activation and left aux unwritten: tests/test_gemm16_paths_gpu.py).
-    const int persist_min = getenv("DCLIP_BF16_PERSIST_MIN") ? atoi(getenv("DCLIP_BF16_PERSIST_MIN")) : 512;
-    const bool gelu_f32 = (epilogue & DCLIP_EPI_GELU) && !out_bf16;
-    const bool persist = !kTrain16<T> && pingpong_enabled() && persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && !gelu_f32 &&
-                         out_scale == 0.f && !dev &&
-                         ldc % 8 == 0 && N % 8 == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min;
-    const char* variant = ".pp";
-    if constexpr (kTrain16<T>) {
-      (void)persist;
-      launch_pp<T>(pb, st);
-    } else {
-      if (persist) {
+    if constexpr (!kTrain16<T>) {
+      const int persist_min = getenv("DCLIP_BF16_PERSIST_MIN") ? atoi(getenv("DCLIP_BF16_PERSIST_MIN")) : 512;
+      const bool gelu_f32 = (epilogue & DCLIP_EPI_GELU) && !out_bf16;
+      if (persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && !gelu_f32 && out_scale == 0.f && !dev && ldc % 8 == 0 &&
+          N % 8 == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min) {
         launch_ppp<T>(pb, st);
-        variant = ".ppp";
-      } else if (pingpong_enabled()) {
-        launch_pp<T>(pb, st);
-      } else {
-        launch_dma<T, 256, 256, 2, 4>(pb, st);
-        variant = ".dma256";
+        DCLIP_CHECK_LAUNCH_V(name, ".ppp");
+        return DCLIP_OK;
       }
     }
-    DCLIP_CHECK_LAUNCH_V(name, variant);
+    launch_pp<T>(pb, st);
+    DCLIP_CHECK_LAUNCH_V(name, ".pp");
     return DCLIP_OK;
-  }
-  // A/B aid: DCLIP_BF16_MID_DMA=1 sends what falls below the big-tile threshold (K % 64 == 0) to the 128x128 LDS-DMA kernel,
-  // two workgroups per CU, instead of the register-staged 128x128 one
-  if constexpr (!kTrain16<T>) {
-    const bool mid_dma = getenv("DCLIP_BF16_MID_DMA") && atoi(getenv("DCLIP_BF16_MID_DMA")) != 0;
-    if (mid_dma && K % BKH == 0 && (long)cdiv(M, 128) * cdiv(N, 128) >= 256) {
-      GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
-                        (unsigned short*)aux, 0, nullptr, alpha, out_scale};
-      set_dev(pb, dev);
-      launch_dma<T, 128, 128, 2, 2>(pb, st);
-      DCLIP_CHECK_LAUNCH_V(name, ".dma128");
-      return DCLIP_OK;
-    }
   }
   const bool small = (long)cdiv(M, 128) * cdiv(N, 128) < 256;  // fewer tiles than CUs: use the finer tile
   const int bm = small ? 64 : 128, bn = bm;
@@ -1725,8 +1499,8 @@ DCLIP_API int dclip_gemm_f16_scaled_rows_dev(const void* A, const void* W, float
 }
 
 // fp16 TRAINING path: dclip_gemm_bf16_ex's arguments, epilogues and limits with fp16 A / W / aux / 16-bit C, IEEE rounding
-// (common.h, F16IeeeT: an overflow becomes +-inf).  The ping-pong / register-staged kernels only (DCLIP_BF16_PP, _MID_DMA and
-// _PERSIST do not apply).
+// (common.h, F16IeeeT: an overflow becomes +-inf).  The ping-pong / register-staged kernels only (DCLIP_BF16_PERSIST does
+// not apply).
 DCLIP_API int dclip_gemm_f16_ex(const void* A, const void* W, void* C, const float* bias, const float* residual, void* aux,
                                 int M, int N, int K, int lda, int ldw, int ldc, int epilogue, int out_f16, void* stream) {
   return gemm16<F16IeeeT>("gemm_f16_ex", A, W, C, bias, residual, aux, M, N, K, lda, ldw, ldc, epilogue, out_f16, stream);
@@ -1735,10 +1509,10 @@ DCLIP_API int dclip_gemm_f16_ex(const void* A, const void* W, void* C, const flo
 // dW[M = out][N = in] fp32 = dY^T X from the operands as the backward has them: dY [K = tokens][lddy >= M], X [K][ldx >= N],
 // bf16, token-major — no transposes.  Split-K over the tokens on the ping-pong kernel (token-major form), fixed-order reduce.
 // dclip_gemm_bf16_wgrad_tokmajor_plan = the split count to pass, 0 when this form does not apply (K % 64, M / N % 8, too few
-// work items for the chip, or DCLIP_BF16_PP=0): the caller then transposes and uses dclip_gemm_bf16_splitk.
+// work items for the chip): the caller then transposes and uses dclip_gemm_bf16_splitk.
 namespace {
-int tokmajor_plan(int M, int N, int K, bool pp) {
-  if (K % BKH != 0 || M % 8 != 0 || N % 8 != 0 || !pp) return 0;
+int tokmajor_plan(int M, int N, int K) {
+  if (K % BKH != 0 || M % 8 != 0 || N % 8 != 0) return 0;
   const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
   int s = t256 >= 256 ? 1 : (int)(256 / t256);
   const int kmax = K / 512 > 0 ? K / 512 : 1;                 // at least 8 K-tiles per work item
@@ -1755,7 +1529,6 @@ int wgrad_tokmajor16(const char* name, const void* dY, const void* X, float* C, 
                 "%s: M=%d N=%d (multiples of 8) K=%d (multiple of 64) splits=%d", name, M, N, K, splits);
   DCLIP_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0 && lddy >= M && ldx >= N && ldc % 4 == 0 && ldc >= N, "%s: leading dimensions", name);
   DCLIP_REQUIRE(((uintptr_t)dY | (uintptr_t)X | (uintptr_t)C) % 16 == 0, "%s: operands must be 16-byte aligned", name);
-  DCLIP_REQUIRE(pp16<T>(), "%s: needs the ping-pong kernel (DCLIP_BF16_PP=0 is set)", name);
   const int kps = cdiv(cdiv(K, splits), BKH) * BKH;
   const int s_eff = cdiv(K, kps);
   hipStream_t st = (hipStream_t)stream;
@@ -1782,7 +1555,7 @@ int wgrad_tokmajor16(const char* name, const void* dY, const void* X, float* C, 
 }
 }  // namespace
 
-DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor_plan(int M, int N, int K) { return tokmajor_plan(M, N, K, pingpong_enabled()); }
+DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor_plan(int M, int N, int K) { return tokmajor_plan(M, N, K); }
 
 DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor(const void* dY, const void* X, float* C, int M, int N, int K, int lddy, int ldx,
                                              int ldc, int splits, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1790,8 +1563,8 @@ DCLIP_API int dclip_gemm_bf16_wgrad_tokmajor(const void* dY, const void* X, floa
                                  workspace_bytes, stream);
 }
 
-// fp16 twins (training path, IEEE rounding is not involved: fp16 operands in, fp32 out); DCLIP_BF16_PP does not apply
-DCLIP_API int dclip_gemm_f16_wgrad_tokmajor_plan(int M, int N, int K) { return tokmajor_plan(M, N, K, true); }
+// fp16 twins (training path, IEEE rounding is not involved: fp16 operands in, fp32 out)
+DCLIP_API int dclip_gemm_f16_wgrad_tokmajor_plan(int M, int N, int K) { return dclip_gemm_bf16_wgrad_tokmajor_plan(M, N, K); }
 
 DCLIP_API int dclip_gemm_f16_wgrad_tokmajor(const void* dY, const void* X, float* C, int M, int N, int K, int lddy, int ldx,
                                             int ldc, int splits, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1931,8 +1704,8 @@ DCLIP_API int dclip_layernorm_fwd_f16_stats(const float* x, const float* gamma, 
 }
 
 namespace {
-int splitk_plan(int M, int N, int K, bool pp) {
-  if (K % BKH == 0 && pp) {                                  // 256x256 ping-pong kernel, one workgroup per CU
+int splitk_plan(int M, int N, int K) {
+  if (K % BKH == 0) {                                  // 256x256 ping-pong kernel, one workgroup per CU
     const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
     if (t256 >= 128 || K < 2048) return 1;
     int s = (int)(256 / t256);
@@ -1966,7 +1739,7 @@ int splitk16(const char* name, const void* A, const void* W, float* C, int M, in
     return DCLIP_EWORKSPACE;
   }
   DCLIP_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", name);
-  if (K % BKH == 0 && pp16<T>() && (long)cdiv(M, 256) * cdiv(N, 256) * s_eff >= 128) {
+  if (K % BKH == 0 && (long)cdiv(M, 256) * cdiv(N, 256) * s_eff >= 128) {
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, 0, nullptr, kps,
                       (float*)workspace};
     launch_pp<T>(pb, (hipStream_t)stream, s_eff);
@@ -1993,7 +1766,7 @@ int splitk16(const char* name, const void* A, const void* W, float* C, int M, in
 // path, dW[out,in] = (dY^T)[out,tok] (X^T)[in,tok]^T with tok = batch x sequence (12,800 .. 25,600): `splits` work items
 // per 128x128 tile write fp32 partials to the caller's workspace, a second kernel sums them in fixed order.  fp32 C, no
 // epilogue.  dclip_gemm_bf16_splitk_plan returns the split count this library would choose (1 = use dclip_gemm_bf16).
-DCLIP_API int dclip_gemm_bf16_splitk_plan(int M, int N, int K) { return splitk_plan(M, N, K, pingpong_enabled()); }
+DCLIP_API int dclip_gemm_bf16_splitk_plan(int M, int N, int K) { return splitk_plan(M, N, K); }
 
 DCLIP_API size_t dclip_gemm_bf16_splitk_workspace(int M, int N, int splits) {
   return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
@@ -2004,8 +1777,8 @@ DCLIP_API int dclip_gemm_bf16_splitk(const void* A, const void* W, float* C, int
   return splitk16<Bf16T>("gemm_bf16_splitk", A, W, C, M, N, K, lda, ldw, ldc, splits, workspace, workspace_bytes, stream);
 }
 
-// fp16 twins of the split-K form (training path; DCLIP_BF16_PP does not apply)
-DCLIP_API int dclip_gemm_f16_splitk_plan(int M, int N, int K) { return splitk_plan(M, N, K, true); }
+// fp16 twins of the split-K form (training path)
+DCLIP_API int dclip_gemm_f16_splitk_plan(int M, int N, int K) { return dclip_gemm_bf16_splitk_plan(M, N, K); }
 
 DCLIP_API size_t dclip_gemm_f16_splitk_workspace(int M, int N, int splits) {
   return dclip_gemm_bf16_splitk_workspace(M, N, splits);

@@ -811,7 +811,7 @@ const char* launch_cfg(const GemmParams& p_in, int layout, int splits, hipStream
     hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, true>), grid, dim3(WM * WN * 64), lds, st, p);
   else
     hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, false>), grid, dim3(WM * WN * 64), lds, st, p);
-  return WM * WN == 8 ? "gemm_f32.w8" : "gemm_f32";
+  return "gemm_f32";
 }
 
 constexpr int NUM_CU = 256;
@@ -943,14 +943,12 @@ DCLIP_API int dclip_gemm_f32(const float* A, const float* B, float* C, const flo
     p.rs_slab = p.slab + (size_t)pl.splits * M * N;
   }
   hipStream_t st = (hipStream_t)stream;
-  static const bool w8 = getenv("DCLIP_GEMM_W8") != nullptr;   // experiment: 8-wave 128x128 workgroups
   const char* site;
-  if (pl.bm == 128 && pl.bn == 128 && w8) site = launch_cfg<128, 128, 2, 4>(p, layout, pl.splits, st);
-  else if (pl.bm == 128 && pl.bn == 128) site = launch_cfg<128, 128, 2, 2>(p, layout, pl.splits, st);
+  if (pl.bm == 128 && pl.bn == 128) site = launch_cfg<128, 128, 2, 2>(p, layout, pl.splits, st);
   else if (pl.bm == 128 && pl.bn == 64) site = launch_cfg<128, 64, 2, 2>(p, layout, pl.splits, st);
   else if (pl.bm == 64 && pl.bn == 128) site = launch_cfg<64, 128, 2, 2>(p, layout, pl.splits, st);
   else site = launch_cfg<64, 64, 2, 2>(p, layout, pl.splits, st);
-  DCLIP_CHECK_LAUNCH(site);   // "gemm_f32", "gemm_f32.dma" (LDS-DMA staging) or "gemm_f32.w8" (8-wave workgroups)
+  DCLIP_CHECK_LAUNCH(site);   // "gemm_f32" or "gemm_f32.dma" (LDS-DMA staging)
   if (pl.splits > 1) {
     const size_t total4 = (size_t)M * N / 4;
     int blocks = (int)((total4 + 255) / 256);

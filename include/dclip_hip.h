@@ -43,12 +43,12 @@ int dclip_abi_version(void);
 const char* dclip_last_error(void);
 /* Name of the calling thread's most recent kernel launch site ("" before the first): lets a test that forces a kernel
  * path with an environment switch assert that the path was taken.  The fp32 GEMM reports "gemm_f32" (register staging),
- * "gemm_f32.dma" (LDS-DMA staging), "gemm_f32.w8" (8-wave workgroups) or, after a split-K, "gemm_f32.splitk_reduce"; the
- * attention "attention_fwd.rows" / ".stream" / "" (tiled) and "attention_bwd.rows" / ".lean" / ".fused" / ".stream_ds" /
- * ".stream" / ".one_key" / "" (tiled).  The 16-bit entries append the kernel variant to their own name: the GEMMs
- * (gemm_bf16, gemm_f16, gemm_f16_ex, gemm_*_splitk, gemm_*_wgrad_tokmajor) ".r64" / ".r128" (register-staged), ".dma128" /
- * ".dma256" (LDS-DMA), ".pp" (ping-pong), ".pp_tok" (its token-major form), ".ppp" (persistent) and, after a split-K,
- * that name + ".splitk_reduce"; attention_fwd_{bf16,f16}[_lse] ".head1" .. ".head9" (whole-head, NB = ceil(S / 32)),
+ * "gemm_f32.dma" (LDS-DMA staging) or, after a split-K, "gemm_f32.splitk_reduce"; the attention "attention_fwd.rows" /
+ * ".stream" / "" (tiled) and "attention_bwd.rows" / ".lean" / ".stream_ds" / ".stream" / ".one_key" / "" (tiled).  The
+ * 16-bit entries append the kernel variant to their own name: the GEMMs (gemm_bf16, gemm_f16, gemm_f16_ex, gemm_*_splitk,
+ * gemm_*_wgrad_tokmajor) ".r64" / ".r128" (register-staged), ".pp" (ping-pong), ".pp_tok" (its token-major form), ".ppp"
+ * (persistent) and, after a split-K, that name + ".splitk_reduce"; attention_fwd_{bf16,f16}[_lse] ".head1" .. ".head9"
+ * (whole-head, NB = ceil(S / 32)),
  * ".head_xq" (257 tokens, shared last query) or ".tiled"; attention_bwd_{bf16,f16} "" or ".one_key" (S = 1);
  * layernorm_fwd_* ".nc<N>" or ".nc<N>.exact".  The fp32 LayerNorm reports its template instance the same way:
  * "layernorm_fwd", "layernorm_bwd" (dclip_layernorm_bwd and _bwd_ex) and "layernorm_bwd_f16" + ".nc1" / ".nc2" / ".nc3" /
@@ -639,7 +639,7 @@ int dclip_gemm_f16_wgrad_tokmajor_seg3(const void* dY, const void* X, float* C, 
  * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
  * a finite value beyond +-65504 becomes +-inf (it does NOT saturate as the frozen fp16 entries do), NaN stays NaN, so the
  * overflow of a loss-scaled gradient reaches the gradient norm and the loss scaler skips the step.  Only the kernels of the
- * default plans have fp16 training instances: DCLIP_BF16_PP, _MID_DMA and _PERSIST do not apply to these entries.
+ * default plans have fp16 training instances: DCLIP_BF16_PERSIST does not apply to these entries.
  *   gemm_f16_ex                  dclip_gemm_bf16_ex (aux = the fp16 GELU pre-activation / dGELU input).
  *   gemm_f16_wgrad_tokmajor(_plan), gemm_f16_splitk(_plan, _workspace)   the weight-gradient forms.
  *   cast_f32_f16_ieee            dclip_cast_f32_f16 with IEEE rounding (fp32 gradients -> fp16).

@@ -1,6 +1,6 @@
 """TEST-ONLY runner: `python -m tests.gemm_paths_child` executes the integer GEMM matrix of tests/kernel_checks.py in THIS
-process and prints one JSON line.  DCLIP_GEMM_DMA, DCLIP_GEMM_GROUP_M and DCLIP_GEMM_W8 are read once into statics of the
-library, so tests/test_gemm_paths_gpu.py starts one fresh process per setting."""
+process and prints one JSON line.  DCLIP_GEMM_DMA and DCLIP_GEMM_GROUP_M are read once into statics of the library, so
+tests/test_gemm_paths_gpu.py starts one fresh process per setting."""
 import json
 import os
 import sys
@@ -17,7 +17,6 @@ def main() -> int:
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream().cuda_stream
     dma = os.environ.get("DCLIP_GEMM_DMA", "1") != "0"
-    w8 = "DCLIP_GEMM_W8" in os.environ
     failed, sites = [], {}
     cases = kc.integer_matrix()
     for c in cases:
@@ -27,7 +26,7 @@ def main() -> int:
             else:
                 os.environ[k] = v
         try:
-            fig = kc.run_gemm_on_device(lib, c, dev, stream, dma=dma, w8=w8)
+            fig = kc.run_gemm_on_device(lib, c, dev, stream, dma=dma)
             sites[fig["site"]] = sites.get(fig["site"], 0) + 1
         except AssertionError as e:          # a wrong result is reported; a GPU fault ends the process, as it should
             failed.append(f"{kc.case_id(c)}: {str(e)[:300]}")

@@ -306,16 +306,14 @@ def assert_gemm_plan(lib, c: GemmCase):
     return plan
 
 
-def expected_gemm_site(c: GemmCase, plan, dma: bool = True, w8: bool = False) -> str:
+def expected_gemm_site(c: GemmCase, plan, dma: bool = True) -> str:
     """The launch-site name dclip_last_launch must report after a case: which kernel variant launch_cfg chose."""
     if plan[2] > 1:
         return "gemm_f32.splitk_reduce"
-    if plan[:2] == [128, 128] and w8:
-        return "gemm_f32.w8"
     return "gemm_f32.dma" if dma and plan[0] == 128 and c.layout & A_KMAJOR else "gemm_f32"
 
 
-def run_gemm_on_device(lib, c: GemmCase, device, stream, dma: bool = True, w8: bool = False):
+def run_gemm_on_device(lib, c: GemmCase, device, stream, dma: bool = True):
     """Build, check the plan, launch through the C ABI, check the launch site, verify.  The caller has set gemm_env(c)."""
     s = build_gemm(c, device)
     plan = assert_gemm_plan(lib, c)
@@ -323,7 +321,7 @@ def run_gemm_on_device(lib, c: GemmCase, device, stream, dma: bool = True, w8: b
     assert rc == 0, f"{case_id(c)}: rc={rc}: {lib.dclip_last_error().decode(errors='replace')}"
     site = lib.dclip_last_launch().decode()
     torch.cuda.synchronize()
-    assert site == expected_gemm_site(c, plan, dma, w8), (case_id(c), site, plan)
+    assert site == expected_gemm_site(c, plan, dma), (case_id(c), site, plan)
     fig = verify_gemm(s)
     fig["site"], fig["plan"] = site, plan
     return fig
@@ -433,14 +431,13 @@ def verify_gemm(s, what: str = None):
 # ------------------------------------------------------------------------------------------------ attention cases
 
 HD = 64
-SelfCase = namedtuple("SelfCase", "B S H causal mode")         # mode: default | tiled | fused | no_ds
+SelfCase = namedtuple("SelfCase", "B S H causal mode")         # mode: default | tiled | no_ds
 CrossCase = namedtuple("CrossCase", "B Lq Lk H")
 ClsCase = namedtuple("ClsCase", "B S H")
 RowCase = namedtuple("RowCase", "B S H rows")
 
-ATTN_ENV = {"default": {}, "tiled": {"DCLIP_ATTN_TILED": "1"}, "fused": {"DCLIP_ATTN_FUSED": "1"},
-            "no_ds": {"DCLIP_ATTN_NO_DS": "1"}}
-ATTN_SWITCHES = ("DCLIP_ATTN_TILED", "DCLIP_ATTN_FUSED", "DCLIP_ATTN_NO_DS")
+ATTN_ENV = {"default": {}, "tiled": {"DCLIP_ATTN_TILED": "1"}, "no_ds": {"DCLIP_ATTN_NO_DS": "1"}}
+ATTN_SWITCHES = ("DCLIP_ATTN_TILED", "DCLIP_ATTN_NO_DS")
 
 _SELF_BASE = [(2, 50, 2, False), (3, 77, 2, True), (1, 197, 3, False), (2, 10, 1, True), (1, 257, 2, False), (2, 16, 2, True),
               (1, 64, 1, False), (1, 130, 1, True), (2, 65, 2, True), (2, 80, 1, False), (2, 77, 2, False), (1, 81, 1, True),
@@ -460,8 +457,6 @@ def self_cases():
     for B, S, H, causal in shapes:
         cases.append(SelfCase(B, S, H, causal, "default"))
         cases.append(SelfCase(B, S, H, causal, "tiled"))
-        if S <= 64:
-            cases.append(SelfCase(B, S, H, causal, "fused"))
         if S > 80 and not causal:
             cases.append(SelfCase(B, S, H, causal, "no_ds"))
     return tuple(cases)
@@ -486,7 +481,7 @@ def expected_launches(c):
         if c.S == 1:
             bwd = "attention_bwd.one_key"                       # a single key: the exact-zero form, whatever the switch
         elif c.S <= 64:
-            bwd = "attention_bwd.fused" if c.mode == "fused" else "attention_bwd.lean"
+            bwd = "attention_bwd.lean"
         elif tiled:
             bwd = "attention_bwd"
         elif c.S <= 80:
@@ -711,10 +706,9 @@ Gemm16Case = namedtuple("Gemm16Case", "entry ty M N K epi out16 save pads splits
 GEMM16_NAMES = {"gemm": {"bf16": "gemm_bf16", "f16": "gemm_f16", "f16ex": "gemm_f16_ex"},
                 "splitk": {"bf16": "gemm_bf16_splitk", "f16ex": "gemm_f16_splitk"},
                 "tok": {"bf16": "gemm_bf16_wgrad_tokmajor", "f16ex": "gemm_f16_wgrad_tokmajor"}}
-GEMM16_SWITCHES = ("DCLIP_BF16_BIG_MIN", "DCLIP_BF16_PERSIST", "DCLIP_BF16_PERSIST_MIN", "DCLIP_BF16_MID_DMA")   # read per call
+GEMM16_SWITCHES = ("DCLIP_BF16_BIG_MIN", "DCLIP_BF16_PERSIST", "DCLIP_BF16_PERSIST_MIN")   # read per call
 ENV_BIG = (("DCLIP_BF16_BIG_MIN", "1"),)
 ENV_PPP = (("DCLIP_BF16_BIG_MIN", "1"), ("DCLIP_BF16_PERSIST", "1"), ("DCLIP_BF16_PERSIST_MIN", "1"))
-ENV_MID = (("DCLIP_BF16_MID_DMA", "1"),)
 PADS16_K, PADS16_C = [0, 8, 40], [0, 4, 36]
 # (epilogue, 16-bit output, aux): every combination the dispatcher accepts
 EPI16 = [(0, 0, 0), (0, 1, 0), (EPI_BIAS, 0, 0), (EPI_BIAS, 1, 0), (EPI_BIAS | EPI_GELU, 0, 0), (EPI_BIAS | EPI_GELU, 1, 0),
@@ -725,7 +719,7 @@ EDGE_SHAPES16 = [(63, 60), (65, 68), (127, 124), (129, 132), (255, 252), (257, 2
 K16 = [64, 128, 192, 72, 85, 149, 4100]
 BIG_SHAPES16 = EDGE_SHAPES16 + [(1000, 520), (511, 508), (300, 1028)]
 K16_BIG = [64, 128, 192, 768]
-R128_SHAPE = (2047, 2044)               # 16 x 16 = 256 tiles of 128 (the r128 / dma128 threshold), 8 x 8 = 64 tiles of 256
+R128_SHAPE = (2047, 2044)               # 16 x 16 = 256 tiles of 128 (the r128 threshold), 8 x 8 = 64 tiles of 256
 BENCHED_FWD16 = (12800, 3072, 768)      # fc1 of the benched student step
 PPP_SHAPES16 = [(200, 256), (1789, 248), (600, 520), (4200, 4096)]          # 1, 7, 9 and 272 tiles of 256 x 256
 TOK_SHAPES16 = [(64, 64), (72, 136), (264, 248), (520, 1000)]
@@ -748,10 +742,11 @@ def s_eff16(K: int, splits: int) -> int:
 @functools.lru_cache(maxsize=None)
 def gemm16_matrix():
     """Every integer-data 16-bit GEMM case.  (a) r64: edge shapes x K with type, epilogue and padding cycling, then every type x
-    epilogue; (b) r128 and dma128 at 2047 x 2044; (c) pp (DCLIP_BF16_BIG_MIN=1; dma256 under DCLIP_BF16_PP=0) over shape x K and
-    over type x epilogue; (d) ppp at 1, 7, 9 and 272 tiles; (e) the benched forward shape; (f) split-K on r128 and pp with
-    splits 1, 2, 3, 7, 64 and more than K / 64; (g) the token-major weight gradient with s_eff == 1 and > 1; (h) values beyond
-    65504 for the two fp16 overflow rules."""
+    epilogue; (b) r128 at 2047 x 2044; (c) pp (DCLIP_BF16_BIG_MIN=1) over shape x K and over type x epilogue; (d) ppp at 1, 7,
+    9 and 272 tiles; (e) the benched forward shape; (f) split-K on r128 and pp with splits 1, 2, 3, 7, 64 and more than K / 64;
+    (g) the token-major weight gradient with s_eff == 1 and > 1; (h) values beyond 65504 for the two fp16 overflow rules.
+    The counter n that cycles type, epilogue and padding jumps once: (b) held four cases of a kernel that was removed
+    (DESIGN.md §17b), and every case after them keeps the operands it had."""
     types, cases, n = ["bf16", "f16", "f16ex"], [], 0
 
     def pick(ty, n):
@@ -771,9 +766,7 @@ def gemm16_matrix():
                      ("f16ex", 72, EPI16[3]), ("f16", 128, EPI16[4])]:      # (b)
         cases.append(_c16("gemm", ty, R128_SHAPE, K, e, n, want="r128"))
         n += 1
-    for ty, K, e in [("bf16", 64, EPI16[6]), ("f16", 192, EPI16[3]), ("bf16", 128, EPI16[9]), ("f16", 64, EPI16[10])]:
-        cases.append(_c16("gemm", ty, R128_SHAPE, K, e, n, env=ENV_MID, want="dma128"))
-        n += 1
+    n += 4                                                                   # (four cases of a removed kernel)
     for shape in BIG_SHAPES16:                                               # (c)
         for K in K16_BIG:
             ty = types[n % 3]
@@ -828,7 +821,6 @@ def gemm16_gaussian_matrix():
             n += 2
         if ty != "f16ex":
             cases.append(_c16("gemm", ty, (600, 520), 768, EPI16[5], n, env=ENV_PPP, want="ppp", data="gauss", cpads=PADS16_K))
-            cases.append(_c16("gemm", ty, R128_SHAPE, 192, EPI16[1], n, env=ENV_MID, want="dma128", data="gauss"))
         if ty != "f16":
             cases.append(_c16("gemm", ty, (300, 1028), 256, EPI16[9], n, env=ENV_BIG, want="pp", data="gauss"))
             cases.append(_c16("splitk", ty, (300, 256), 4100, EPI16[0], n, splits=7, want="r128", data="gauss"))
@@ -855,15 +847,9 @@ def gemm16_reduces(c: Gemm16Case) -> bool:
     return (c.entry == "splitk" and c.splits != 1) or (c.entry == "tok" and s_eff16(c.K, c.splits) > 1)
 
 
-def expected_gemm16_site(c: Gemm16Case, pp: bool = True) -> str:
-    """What dclip_last_launch must report; pp=False: under DCLIP_BF16_PP=0 (does not apply to the fp16 training type)."""
-    want = c.want
-    if not pp and c.ty != "f16ex":
-        if c.entry == "gemm" and want in ("pp", "ppp"):
-            want = "dma256"
-        elif c.entry == "splitk" and want == "pp":
-            want = "r128" if c.splits != 1 else "dma256"
-    return GEMM16_NAMES[c.entry][c.ty] + "." + want + (".splitk_reduce" if gemm16_reduces(c) else "")
+def expected_gemm16_site(c: Gemm16Case) -> str:
+    """What dclip_last_launch must report."""
+    return GEMM16_NAMES[c.entry][c.ty] + "." + c.want + (".splitk_reduce" if gemm16_reduces(c) else "")
 
 
 @functools.lru_cache(maxsize=8)
@@ -1032,17 +1018,14 @@ def verify_gemm16(s, what: str = None):
     return fig
 
 
-def run_gemm16_on_device(lib, c: Gemm16Case, device, stream, pp: bool = True):
+def run_gemm16_on_device(lib, c: Gemm16Case, device, stream):
     """Build, launch through the C ABI, check the variant the library reports, verify.  The caller has set gemm16_env(c)."""
     s = build_gemm16(c, device)
     rc = launch_gemm16(lib, s, stream)
-    if not pp and c.entry == "tok" and c.ty == "bf16":             # the token-major form needs the ping-pong kernel
-        assert rc == E_INVAL and b"ping-pong" in lib.dclip_last_error(), (case16_id(c), rc)
-        return {"site": "refused"}
     assert rc == 0, f"{case16_id(c)}: rc={rc}: {lib.dclip_last_error().decode(errors='replace')}"
     site = lib.dclip_last_launch().decode()
     torch.cuda.synchronize()
-    assert site == expected_gemm16_site(c, pp), (case16_id(c), site)
+    assert site == expected_gemm16_site(c), (case16_id(c), site)
     fig = verify_gemm16(s)
     fig["site"] = site
     if gemm16_reduces(c):

@@ -1,13 +1,12 @@
 """TEST-ONLY runner: `python -m tests.paths16_child gemm|attention` executes the 16-bit GEMM matrix / the 16-bit attention
-forward list of tests/kernel_checks.py in THIS process and prints one JSON line.  DCLIP_BF16_PP, DCLIP_ATTN16_TILED and
-DCLIP_ATTN16_NO_XQ are read once into statics of the library, so tests/test_gemm16_paths_gpu.py and
-tests/test_attention16_paths_gpu.py start one fresh process per setting."""
+forward list of tests/kernel_checks.py in THIS process and prints one JSON line.  DCLIP_ATTN16_TILED and DCLIP_ATTN16_NO_XQ
+are read once into statics of the library, so tests/test_attention16_paths_gpu.py starts one fresh process per setting."""
 import json
 import os
 import sys
 import time
 
-ONCE_READ = ("DCLIP_BF16_PP", "DCLIP_ATTN16_TILED", "DCLIP_ATTN16_NO_XQ")
+ONCE_READ = ("DCLIP_ATTN16_TILED", "DCLIP_ATTN16_NO_XQ")
 
 
 def main(what: str) -> int:
@@ -21,7 +20,6 @@ def main(what: str) -> int:
     stream = torch.cuda.current_stream().cuda_stream
     failed, sites, n = [], {}, 0
     if what == "gemm":
-        pp = os.environ.get("DCLIP_BF16_PP", "1") != "0"
         for c in kc.gemm16_matrix():
             for k, v in kc.gemm16_env(c).items():
                 if v is None:
@@ -30,7 +28,7 @@ def main(what: str) -> int:
                     os.environ[k] = v
             n += 1
             try:
-                fig = kc.run_gemm16_on_device(lib, c, dev, stream, pp=pp)
+                fig = kc.run_gemm16_on_device(lib, c, dev, stream)
                 sites[fig["site"]] = sites.get(fig["site"], 0) + 1
             except AssertionError as e:          # a wrong result is reported; a GPU fault ends the process, as it should
                 failed.append(f"{kc.case16_id(c)}: {str(e)[:300]}")

@@ -116,12 +116,9 @@ def test_meta_teacher_bf16_towers_close_to_fp32():
     assert float(cos.min()) > 0.999
 
 
-@pytest.mark.parametrize("pingpong", ["1", "0"])
-def test_gemm_bf16_big_tile_kernel_matches(pingpong):
-    """The 256x256 LDS-DMA kernels (ping-pong schedule, and the lock-step one behind DCLIP_BF16_PP=0), forced onto small
-    shapes (DCLIP_BF16_BIG_MIN=1 is read on every call; DCLIP_BF16_PP is read once per process, so this test runs the
-    comparison in a child process), against
-    the fp64 product of the rounded inputs.  K = 64 .. 3072 covers 1, 2, 3 (odd), 12 and 48 K-tiles."""
+def test_gemm_bf16_big_tile_kernel_matches():
+    """The 256x256 ping-pong kernel, forced onto small shapes (DCLIP_BF16_BIG_MIN=1, in a child process), against the fp64
+    product of the rounded inputs.  K = 64 .. 3072 covers 1, 2, 3 (odd), 12 and 48 K-tiles."""
     import subprocess, sys, os, textwrap
     code = textwrap.dedent("""
         import torch, sys
@@ -157,7 +154,7 @@ def test_gemm_bf16_big_tile_kernel_matches(pingpong):
                 assert float((d.double().cpu() - dref).abs().max() / dref.abs().max()) < tol, (M, N, K, o16)
         print("OK")
     """) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DCLIP_BF16_BIG_MIN="1", DCLIP_BF16_PP=pingpong)
+    env = dict(os.environ, DCLIP_BF16_BIG_MIN="1")
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0 and "OK" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
 

@@ -1,17 +1,11 @@
 """Opt-in fp16 path for frozen towers: kernels against fp64 on fp16-rounded operands, the conversion rule, and the towers'
 measured error against the fp32 towers (the 1e-3 bar that the bf16 path misses)."""
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
 from dclip_amd import config as dcfg, synth
 
 pytestmark = pytest.mark.gpu
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def rnd(shape, seed, scale=1.0):
@@ -65,9 +59,9 @@ def test_gemm_f16_matches_rounded_inputs(M, N, K):
 
 
 @pytest.mark.parametrize("M,N,K", [(1000, 520, 64), (2048, 1024, 128), (5000, 768, 768), (4096, 2304, 768)])
-def test_gemm_f16_persistent_and_mid_dma_kernels(M, N, K, monkeypatch):
-    """The env-selected variants have fp16 instances too: the persistent ping-pong kernel (DCLIP_BF16_PERSIST) against the
-    one-tile ping-pong kernel (bit-identical without a residual), and the 128x128 LDS-DMA kernel (DCLIP_BF16_MID_DMA)."""
+def test_gemm_f16_persistent_kernel(M, N, K, monkeypatch):
+    """The env-selected variant has fp16 instances too: the persistent ping-pong kernel (DCLIP_BF16_PERSIST) against the
+    one-tile ping-pong kernel (bit-identical without a residual)."""
     dev = torch.device("cuda:0")
     a16, w16 = rnd((M, K), 1).half().to(dev), rnd((N, K), 2, 0.1).half().to(dev)
     bias, res = rnd((N,), 3).to(dev), rnd((M, N), 4).to(dev)
@@ -79,26 +73,6 @@ def test_gemm_f16_persistent_and_mid_dma_kernels(M, N, K, monkeypatch):
     per = check_gemm(a16, w16, K, bias, res, "persistent")
     for i in (0, 2, 3):
         assert torch.equal(per[i], one[i]), i
-    monkeypatch.setenv("DCLIP_BF16_PERSIST", "0")
-    monkeypatch.setenv("DCLIP_BF16_BIG_MIN", "100000")
-    monkeypatch.setenv("DCLIP_BF16_MID_DMA", "1")
-    check_gemm(a16, w16, K, bias, res, "mid_dma")
-
-
-def test_gemm_f16_lockstep_big_tile_kernel():
-    """DCLIP_BF16_PP=0 (read once per process: a child process) selects the lock-step 256x256 LDS-DMA kernel."""
-    code = (
-        "import torch, sys\n"
-        "sys.path.insert(0, 'tests')\n"
-        "from test_fp16_gpu import rnd, check_gemm\n"
-        "dev = torch.device('cuda:0')\n"
-        "for M, N, K in ((5000, 768, 768), (300, 260, 192)):\n"
-        "    a16, w16 = rnd((M, K), 1).half().to(dev), rnd((N, K), 2, 0.1).half().to(dev)\n"
-        "    check_gemm(a16, w16, K, rnd((N,), 3).to(dev), rnd((M, N), 4).to(dev), 'dma256')\n"
-        "print('OK')\n")
-    env = dict(os.environ, DCLIP_BF16_PP="0", DCLIP_BF16_BIG_MIN="1")
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
-    assert p.returncode == 0 and "OK" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
 
 
 @pytest.mark.parametrize("M,N,K", [(64, 64, 64), (300, 512, 128), (12800, 1024, 64)])      # register-staged, ping-pong

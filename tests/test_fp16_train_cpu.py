@@ -99,7 +99,7 @@ def test_new_entries_reject_bad_arguments_without_a_gpu():
     assert lib.dclip_last_error() == b"attention_bwd_bf16: B=1 S=65 (<= 64) H=1"
     assert lib.dclip_attention_fwd_bf16_lse(16, 16, 16, 1, 289, 1, 0, None) == -1
     assert lib.dclip_last_error() == b"attention_fwd_bf16_lse: B=1 S=289 (<= 288, not 257) H=1"
-    # plans: the fp16 forms ignore DCLIP_BF16_PP and agree with bf16 under the default switches
+    # plans: the fp16 forms are the bf16 plans
     for m, n, k in ((768, 3072, 12800), (2304, 768, 400), (512, 768, 25600)):
         assert lib.dclip_gemm_f16_splitk_plan(m, n, k) == lib.dclip_gemm_bf16_splitk_plan(m, n, k)
         assert lib.dclip_gemm_f16_wgrad_tokmajor_plan(m, n, k) == lib.dclip_gemm_bf16_wgrad_tokmajor_plan(m, n, k)

@@ -1,9 +1,9 @@
-"""Every path of the 16-bit GEMM file (dclip_amd/csrc/gemm_bf16.hip) through the C ABI: the five kernel families x the three
+"""Every path of the 16-bit GEMM file (dclip_amd/csrc/gemm_bf16.hip) through the C ABI: the kernel variants x the three
 element types x every epilogue the dispatcher accepts x leading-dimension padding on integer data (bit-exact C and saved
 pre-activation, guarded outputs, NaN-poisoned operand padding), the two split-K entries and the token-major weight gradient
-with their workspace, a Gaussian subset under the derived bound, the once-read switch DCLIP_BF16_PP=0 in one fresh process,
-and the cast and LayerNorm-16 kernels that live in the same file.  Checkers and case lists: tests/kernel_checks.py;
-tests/test_kernel_checks16_cpu.py shows what they catch.  Every case asserts the kernel variant dclip_last_launch reports."""
+with their workspace, a Gaussian subset under the derived bound, and the cast and LayerNorm-16 kernels that live in the same
+file.  Checkers and case lists: tests/kernel_checks.py; tests/test_kernel_checks16_cpu.py shows what they catch.  Every case
+asserts the kernel variant dclip_last_launch reports."""
 import pytest
 import torch
 
@@ -41,20 +41,6 @@ def _nothing_starts_after_an_abnormal_child():
     kc.assert_no_child_ended_abnormally()
 
 
-# ---- the once-read switch: first in the module, while this process holds little device memory -----------------------------
-
-def test_integer_matrix_with_the_pingpong_kernels_switched_off():
-    """One fresh process (kc.run_child16: a child that ends by signal, abort, error or timeout fails the test, and neither a
-    further child nor an in-process case of the two 16-bit modules is started after it).  DCLIP_BF16_PP=0: the pp and ppp cases of bf16 and the saturating fp16 run the lock-step 256x256 LDS-DMA kernel, split-K
-    falls back to the 128x128 form, the token-major entry refuses; the fp16 training type is not affected."""
-    out = kc.run_child16("gemm", {"DCLIP_BF16_PP": "0"})
-    assert out["cases"] == len(kc.gemm16_matrix()) and not out["failed"], out["failed"][:5]
-    sites = out["sites"]
-    assert sites.get("gemm_bf16.dma256", 0) > 0 and sites.get("gemm_f16.dma256", 0) > 0 and sites.get("refused", 0) > 0
-    assert sites.get("gemm_f16_ex.pp", 0) > 0 and sites.get("gemm_f16_splitk.pp.splitk_reduce", 0) > 0
-    assert not any(k.startswith(("gemm_bf16.pp", "gemm_f16.pp", "gemm_bf16_splitk.pp")) for k in sites), sites
-
-
 # ---- the matrix in this process ---------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("case", kc.gemm16_matrix(), ids=kc.case16_id)
@@ -73,9 +59,9 @@ def test_gaussian_subset_under_the_derived_bound(dev, lib, monkeypatch, case):
 
 
 def test_every_variant_of_the_file_has_a_case():
-    sites = {kc.expected_gemm16_site(c, pp) for c in kc.gemm16_matrix() for pp in (True, False)}
+    sites = {kc.expected_gemm16_site(c) for c in kc.gemm16_matrix()}
     for ty in ("gemm_bf16", "gemm_f16"):
-        assert {f"{ty}.{v}" for v in ("r64", "r128", "dma128", "dma256", "pp", "ppp")} <= sites
+        assert {f"{ty}.{v}" for v in ("r64", "r128", "pp", "ppp")} <= sites
     assert {"gemm_f16_ex.r64", "gemm_f16_ex.r128", "gemm_f16_ex.pp"} <= sites
     for ty in ("bf16", "f16"):
         assert {f"gemm_{ty}_splitk.r64", f"gemm_{ty}_splitk.r128.splitk_reduce", f"gemm_{ty}_splitk.pp.splitk_reduce",

@@ -1,7 +1,7 @@
 """Every path of the fp32 GEMM (dclip_amd/csrc/gemm_f32.hip) through the C ABI: each tile forced with DCLIP_GEMM_TILE x each
 layout x split-K x epilogue x leading-dimension padding on integer data (exact equality, guarded outputs, NaN-poisoned
 operand padding), a Gaussian subset under the derived rounding bound, and the once-read switches (DCLIP_GEMM_DMA,
-DCLIP_GEMM_GROUP_M, DCLIP_GEMM_W8) in one fresh process each.  The checkers and the case lists live in
+DCLIP_GEMM_GROUP_M) in one fresh process each.  The checkers and the case lists live in
 tests/kernel_checks.py; tests/test_kernel_checks_cpu.py shows what they catch.  Every case asserts the tile, the split
 count (dclip_gemm_f32_plan) and the kernel variant (dclip_last_launch) it was written for."""
 import json
@@ -44,8 +44,7 @@ def set_env(monkeypatch, env):
 
 # ---- the once-read switches: first in the module, while this process holds little device memory ------------------------
 
-STATIC_SETTINGS = [{"DCLIP_GEMM_DMA": "0"}, {"DCLIP_GEMM_GROUP_M": "1"}, {"DCLIP_GEMM_GROUP_M": "3"}, {"DCLIP_GEMM_GROUP_M": "8"},
-                   {"DCLIP_GEMM_W8": "1"}]
+STATIC_SETTINGS = [{"DCLIP_GEMM_DMA": "0"}, {"DCLIP_GEMM_GROUP_M": "1"}, {"DCLIP_GEMM_GROUP_M": "3"}, {"DCLIP_GEMM_GROUP_M": "8"}]
 _child_ended_abnormally = []
 
 
@@ -69,15 +68,13 @@ def test_integer_matrix_under_a_once_read_switch(setting):
     print(out)
     assert out["switches"] == setting
     assert out["cases"] == len(kc.integer_matrix()) and not out["failed"], out["failed"][:5]
-    if "DCLIP_GEMM_W8" in setting:
-        assert out["sites"].get("gemm_f32.w8", 0) > 0
     if "DCLIP_GEMM_DMA" in setting:
         assert "gemm_f32.dma" not in out["sites"]
     else:
         assert out["sites"].get("gemm_f32.dma", 0) > 0
 
 
-# ---- the matrix in this process (default statics: LDS-DMA staging on, 4 tile-rows per group, 4-wave workgroups) --------
+# ---- the matrix in this process (default statics: LDS-DMA staging on, 4 tile-rows per group) ---------------------------
 
 @pytest.mark.parametrize("case", kc.integer_matrix(), ids=kc.case_id)
 def test_integer_matrix(dev, lib, monkeypatch, case):

@@ -102,7 +102,7 @@ def test_every_dispatch_branch_of_the_attention_has_a_case():
     for c in list(kc.self_cases()) + list(kc.cross_cases()) + list(kc.CLS_CASES) + list(kc.ROW_CASES):
         names.update(n for n in kc.expected_launches(c) if n)
     assert names == {"attention_fwd.rows", "attention_fwd.stream", "attention_fwd", "attention_bwd.rows", "attention_bwd.lean",
-                     "attention_bwd.fused", "attention_bwd.stream_ds", "attention_bwd.stream", "attention_bwd",
+                     "attention_bwd.stream_ds", "attention_bwd.stream", "attention_bwd",
                      "attention_bwd.one_key"}
     kt = {-(-c.S // 16) for c in kc.self_cases() if c.mode == "default" and c.S <= 80}
     assert kt == {1, 2, 3, 4, 5}                                         # every instance of the whole-row forward

@@ -4,7 +4,6 @@ against fp64, and the tower — against the switch-off path and the fp64 oracle,
 graph, run to run."""
 import argparse
 import os
-import subprocess
 import sys
 
 import pytest
@@ -18,7 +17,6 @@ from test_vision_split16_gpu import bits, norm_err, rnd, same, scalar      # noq
 
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WEIGHTS = ("qkv", "out", "fc1", "fc2")
 
 
@@ -138,28 +136,6 @@ def test_rows_gemm_never_takes_the_persistent_kernel(monkeypatch):
     monkeypatch.setenv("DCLIP_BF16_PERSIST", "1")
     check_rows_gemm(5900, 6144, 64)
     assert b".ppp" not in _lib.load().dclip_last_launch() and b".pp" in _lib.load().dclip_last_launch()
-
-
-def test_rows_gemm_mid_dma_kernel(monkeypatch):
-    from dclip_amd import _lib
-    monkeypatch.setenv("DCLIP_BF16_BIG_MIN", "100000")
-    monkeypatch.setenv("DCLIP_BF16_MID_DMA", "1")
-    check_rows_gemm(4096, 2304, 64)
-    assert b".dma128" in _lib.load().dclip_last_launch()
-
-
-def test_rows_gemm_lockstep_big_tile_kernel():
-    """DCLIP_BF16_PP=0 (read once per process: a child process) selects the lock-step 256x256 LDS-DMA kernel."""
-    code = ("import sys\n"
-            "sys.path.insert(0, 'tests')\n"
-            "from test_vision_split16_bwd_gpu import check_rows_gemm\n"
-            "from dclip_amd import _lib\n"
-            "check_rows_gemm(5000, 768, 768)\n"
-            "assert b'.dma256' in _lib.load().dclip_last_launch()\n"
-            "print('OK')\n")
-    env = dict(os.environ, DCLIP_BF16_PP="0", DCLIP_BF16_BIG_MIN="1")
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
-    assert p.returncode == 0 and "OK" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
 
 
 # ------------------------------------------------------------------------------------------------ 4. the dgrad end to end

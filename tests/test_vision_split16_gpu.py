@@ -4,9 +4,6 @@ fp32 path and the fp64 oracle — eager, with changing weights, under a HIP grap
 import argparse
 import logging
 import math
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -15,7 +12,6 @@ from dclip_amd import config as dcfg, synth
 
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WEIGHTS = ("qkv", "out", "fc1", "fc2")
 ACTS = ("ln1", "ctx", "ln2", "g")
 ACT_OF = {"qkv": "ln1", "out": "ctx", "fc1": "ln2", "fc2": "g"}
@@ -209,24 +205,6 @@ def test_gemm_dev_never_takes_the_persistent_kernel(monkeypatch):
     monkeypatch.setenv("DCLIP_BF16_PERSIST", "1")
     check_dev_gemm(5900, 6144, 64)
     assert b".ppp" not in _lib.load().dclip_last_launch()
-
-
-def test_gemm_dev_mid_dma_kernel(monkeypatch):
-    monkeypatch.setenv("DCLIP_BF16_BIG_MIN", "100000")
-    monkeypatch.setenv("DCLIP_BF16_MID_DMA", "1")
-    check_dev_gemm(4096, 2304, 64)
-
-
-def test_gemm_dev_lockstep_big_tile_kernel():
-    """DCLIP_BF16_PP=0 (read once per process: a child process) selects the lock-step 256x256 LDS-DMA kernel."""
-    code = ("import sys\n"
-            "sys.path.insert(0, 'tests')\n"
-            "from test_vision_split16_gpu import check_dev_gemm\n"
-            "check_dev_gemm(5000, 768, 768)\n"
-            "print('OK')\n")
-    env = dict(os.environ, DCLIP_BF16_PP="0", DCLIP_BF16_BIG_MIN="1")
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
-    assert p.returncode == 0 and "OK" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
 
 
 # ------------------------------------------------------------------------------------------------ 4. tower

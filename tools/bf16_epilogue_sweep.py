@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bf16 GEMM: time per epilogue kind on the tower shapes (bias / bias+residual fp32 / GELU bf16 / GELU+saved pre-activation /
-dGELU), to see what the epilogue costs beside the K loop.  DCLIP_BF16_PP=0 selects the lock-step 256x256 kernel."""
+dGELU), to see what the epilogue costs beside the K loop."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The bf16 GEMMs of the TRAINING student (M = 12,800 tokens: 256 images x 50) with the epilogues the step gives them, timed
-one by one: forward qkv / out / fc1 / fc2, data gradients fc2 / fc1 / out / qkv.  Kernel choice is read from the environment
-once per process (DCLIP_BF16_BIG_MIN, DCLIP_BF16_MID_DMA, DCLIP_BF16_PP): run once per setting."""
+one by one: forward qkv / out / fc1 / fc2, data gradients fc2 / fc1 / out / qkv.  DCLIP_BF16_BIG_MIN (the ping-pong
+kernel's tile threshold) is read from the environment: run once per setting."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -46,4 +46,4 @@ for name, n, k, kind in [("qkv fwd  (bias, bf16 out)", 3 * D, D, "b16"), ("out f
     tot += ms
     rows.append(f"{name:30s} {M}x{n}x{k}: {ms * 1e3:7.1f} us {2.0 * M * n * k / ms / 1e9:6.0f} TF/s  tiles256 {((M + 255) // 256) * ((n + 255) // 256)}")
 print("\n".join(rows))
-print(f"sum per layer {tot * 1e3:.1f} us  (env BIG_MIN={os.environ.get('DCLIP_BF16_BIG_MIN')} MID_DMA={os.environ.get('DCLIP_BF16_MID_DMA')})")
+print(f"sum per layer {tot * 1e3:.1f} us  (env BIG_MIN={os.environ.get('DCLIP_BF16_BIG_MIN')})")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bf16 weight-gradient GEMMs (split-K over the token axis): time per shape.  DCLIP_BF16_PP=0 -> the 128x128 split-K kernel."""
+"""bf16 weight-gradient GEMMs (split-K over the token axis): time per shape."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -2,9 +2,12 @@
 revision and of the working tree device-only (hipcc -O3 --offload-arch=gfx950, the Makefile's flags), disassembles both
 with llvm-objdump -d and compares them function by function, with the template arguments stripped from the demangled
 names: a kernel that gained a template parameter (the 16-bit type) keeps its name.  Every instruction stream of the base
-must appear, unchanged, under the same name in the working tree; functions the working tree adds are listed.
+must appear, unchanged, under the same name in the working tree; functions the working tree adds are listed.  A change that
+deletes kernels names them: with --removed NAME[=COUNT] up to COUNT (default: any number of) base functions of that stripped
+name may be missing from the working tree; they are listed as removed, not as changed.  Only a fall in the number of
+instances of a name counts as a removal: a surviving instance whose code differs is still reported as changed.
 
-    python tools/disasm_compare.py [--base HEAD] [--jobs 8]
+    python tools/disasm_compare.py [--base HEAD] [--jobs 8] [--removed NAME[=COUNT] ...]
 
 Exit status 0 when nothing existing changed.  Needs hipcc and git, no GPU."""
 from __future__ import annotations
@@ -39,6 +42,11 @@ def strip_templates(name: str) -> str:
         elif depth == 0:
             out.append(ch)
     return "".join(out)
+
+
+def bare(stripped: str) -> str:
+    """The function's own name: no namespaces, no parameter list (what --removed takes)."""
+    return stripped.replace("(anonymous namespace)::", "").split("(")[0].split("::")[-1]
 
 
 def functions(code_object: str):
@@ -87,7 +95,13 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--base", default="HEAD", help="git revision whose kernels must be unchanged (default HEAD)")
     ap.add_argument("--jobs", type=int, default=8)
+    ap.add_argument("--removed", nargs="*", default=[], metavar="NAME[=COUNT]",
+                    help="base functions of this stripped name may be missing from the tree, up to COUNT of them")
     a = ap.parse_args()
+    allowance = {}
+    for spec in a.removed:
+        n, _, c = spec.partition("=")
+        allowance[n] = int(c) if c else sys.maxsize
     with tempfile.TemporaryDirectory() as tmp:
         base_src = os.path.join(tmp, "base")
         os.makedirs(base_src)
@@ -98,16 +112,21 @@ def main() -> int:
         os.makedirs(os.path.join(tmp, "w"))
         base = compile_tree(base_src, os.path.join(tmp, "b"), a.jobs)
         work = compile_tree(REPO, os.path.join(tmp, "w"), a.jobs)
-        changed, same, added = [], 0, []
+        changed, same, added, removed = [], 0, [], collections.Counter()
         for f in sorted(set(base) | set(work)):
             fb = functions(base[f]) if f in base else {}
             fw = functions(work[f]) if f in work else {}
             for n, bodies in sorted(fb.items()):
                 have = collections.Counter(fw.get(n, []))
+                gone = len(bodies) - len(fw.get(n, []))      # a removal lowers the number of instances; what is missing beyond that changed
                 for b in bodies:
                     if have[b] > 0:
                         have[b] -= 1
                         same += 1
+                    elif gone > 0 and allowance.get(bare(n), 0) > 0:
+                        gone -= 1
+                        allowance[bare(n)] -= 1
+                        removed[f"{f}: {bare(n)}"] += 1
                     else:
                         changed.append(f"{f}: {n}")
             for n, bodies in sorted(fw.items()):
@@ -118,6 +137,10 @@ def main() -> int:
         print(f"added functions: {sum(int(x.rsplit('+', 1)[1][:-1]) for x in added)}")
         for x in added:
             print(f"  + {x}")
+        if a.removed:
+            print(f"removed functions: {sum(removed.values())}")
+            for x, c in sorted(removed.items()):
+                print(f"  - {x} (-{c})")
         print(f"changed functions: {len(changed)}")
         for x in changed:
             print(f"  ! {x}")

@@ -110,8 +110,7 @@ def main():
     xi = torch.randn((M, I), device=dev)
     one = torch.ones((1,), device=dev)
     a3, a3i = ops.split_f16x3(x, 1.0), ops.split_f16x3(xi, 1.0)
-    kernels = {"default": {}, "r128": dict(DCLIP_BF16_BIG_MIN="1000000"),
-               "dma128": dict(DCLIP_BF16_BIG_MIN="1000000", DCLIP_BF16_MID_DMA="1")}
+    kernels = {"default": {}, "r128": dict(DCLIP_BF16_BIG_MIN="1000000")}
     shapes = {"qkv": (a3, x, lp.qkv_w, lp.qkv_b, None), "out": (a3, x, lp.out_w, lp.out_b, x), "fc2": (a3i, xi, lp.fc2_w, lp.fc2_b, x)}
     for name, (a, a32, w, b, res) in shapes.items():
         fns = {"fp32": lambda: ops.gemm(a32, w, ops.LAYOUT_NT, bias=b, residual=res)}

@@ -84,8 +84,7 @@ def main():
     dys = {w: torch.randn((M, w), device=dev) for w in (D, 3 * D, I)}
     split = {w: ops.split_f16x3_rows(x) for w, x in dys.items()}
     h = torch.randn((M, I), device=dev)
-    kernels = {"default": {}, "r128": dict(DCLIP_BF16_BIG_MIN="1000000"),
-               "dma128": dict(DCLIP_BF16_BIG_MIN="1000000", DCLIP_BF16_MID_DMA="1")}
+    kernels = {"default": {}, "r128": dict(DCLIP_BF16_BIG_MIN="1000000")}
     shapes = {"dh (fc2)": ("fc2", D, lp.fc2_w, h), "dln2 (fc1)": ("fc1", I, lp.fc1_w, None), "dattn (out)": ("out", D, lp.out_w, None),
               "dln1 (qkv)": ("qkv", 3 * D, lp.qkv_w, None)}
     for label, (name, width, w, aux) in shapes.items():
