@@ -31,6 +31,7 @@ def main(args, clip_model=None, clip_preprocess=None, train_batches=None, val_ba
         clip_preprocess = CLIPProcessor.from_pretrained(args.clip_path, local_files_only=True)
     module_kwargs.setdefault("student_precision", getattr(args, "student_precision", "fp32"))
     module_kwargs.setdefault("full_resolution_from_epoch", resolve_full_resolution_epoch(args))
+    module_kwargs.setdefault("packed_text", bool(getattr(args, "packed_text", False)))
     model = CLIPImageDistillation(args, clip_model, clip_preprocess, **module_kwargs).to(device)
     trainer = Trainer(max_epochs=args.phase1_epochs, accelerator="gpu", devices=devices, precision=32,
                       gradient_clip_val=0.5, accumulate_grad_batches=4, checkpoint_dir=args.checkpoint_dir,
@@ -62,6 +63,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--full_resolution_from_epoch", type=_epoch_or_half, default=None, metavar="N|half",
                         help="from this epoch on the meta-teacher encodes region crops at their own size, in one packed tower "
                              "pass; `half` = phase1_epochs // 2, the reference's rule (default: never)")
+    parser.add_argument("--packed_text", action="store_true",
+                        help="run the frozen text towers on captions cut after their first EOS and laid back to back "
+                             "(lengths from the tokenizer's host output; default: the padded [B, T] rectangle)")
     return parser
 
 

@@ -73,7 +73,7 @@ def _as_hip_model(clip_model) -> HipCLIPModel:
 class CLIPImageDistillation(LightningLikeModule):
     def __init__(self, hparams, clip_model, clip_preprocess=None, teacher=None, freeze_mode: str = "north_star",
                  process_group=None, contrastive_teacher_path: Optional[str] = None, student_precision: str = "fp32",
-                 full_resolution_from_epoch: Optional[int] = None):
+                 full_resolution_from_epoch: Optional[int] = None, packed_text: bool = False):
         """`student_precision`: "fp32" (default: the reference's `precision=32`,
         training/CLIP_image_distill_training.py:40, and the benched config c2) or "bf16" — the student's VISION tower
         multiplies in bf16 (forward, dgrad, wgrad) with fp32 master weights, fp32 accumulation and fp32
@@ -82,8 +82,14 @@ class CLIPImageDistillation(LightningLikeModule):
         precision="16-mixed"), within the 1e-3 embedding bar.
         `full_resolution_from_epoch` = N: from epoch N on the meta-teacher encodes every region crop at its own size, in one
         packed tower pass (teacher.full_resolution = teacher.full_resolution_packed = current_epoch >= N, set before every
-        teacher call; training/CLIP_image_distillation.py:723-729 switches at half the epochs).  None leaves both flags alone."""
+        teacher call; training/CLIP_image_distillation.py:723-729 switches at half the epochs).  None leaves both flags alone.
+        `packed_text` (also an attribute; switches the teacher's `packed_text` on as well): where the text tower is frozen and
+        the captions' lengths are known on the HOST — tokenizer output, `batch["input_ids"]` on the CPU, or `batch["text_lens"]`
+        (first EOS index + 1 per caption, next to `max_tokens`) — every frozen text forward of the step runs on packed captions
+        (HipCLIPModel.get_text_features(packed_lens=...)).  Without host lengths, or with a trainable text
+        tower, the padded path runs as before."""
         super().__init__()
+        self.packed_text = bool(packed_text)
         if full_resolution_from_epoch is not None and int(full_resolution_from_epoch) < 0:
             raise ValueError(f"full_resolution_from_epoch {full_resolution_from_epoch!r}")
         self.full_resolution_from_epoch = None if full_resolution_from_epoch is None else int(full_resolution_from_epoch)
@@ -129,6 +135,8 @@ class CLIPImageDistillation(LightningLikeModule):
                                            owns_clip=True, text_twin=self.student)
             teacher.to(next(self.student.parameters()).device)
         self.teacher = teacher
+        if self.packed_text and hasattr(self.teacher, "packed_text"):
+            self.teacher.packed_text = True
         if contrastive_teacher_path:
             # weights_only: a checkpoint is data, nothing in it is executed (training/CLIP_image_distillation.py:458-462)
             sd = torch.load(contrastive_teacher_path, map_location="cpu", weights_only=True)
@@ -187,6 +195,20 @@ class CLIPImageDistillation(LightningLikeModule):
             raise RuntimeError("caption strings need clip_preprocess (an HF CLIPProcessor loaded from a local path)")
         return self.preprocess(text=captions, return_tensors="pt", padding=True, truncation=True)["input_ids"]
 
+    def _host_text_lens(self, host_ids=None, batch=None):
+        """Caption lengths (first EOS index + 1, int32 on the host) for the packed text paths, or None: `packed_text` off, or
+        no lengths without a device read — `batch["text_lens"]`, else token ids that are still on the host."""
+        if not self.packed_text:
+            return None
+        if isinstance(batch, dict) and batch.get("text_lens") is not None:
+            return batch["text_lens"]
+        if host_ids is None and isinstance(batch, dict):
+            host_ids = batch.get("input_ids")
+        if isinstance(host_ids, torch.Tensor) and host_ids.device.type == "cpu" and host_ids.dim() == 2:
+            from .clip_model import packed_text_tables
+            return packed_text_tables(host_ids, self.student.config.text.eos_token_id)["lens"]
+        return None
+
     @staticmethod
     def _batch_key(batch):
         r, t = batch["regions"], batch["input_ids"]
@@ -214,13 +236,15 @@ class CLIPImageDistillation(LightningLikeModule):
             return False
         from . import ops
         regions, tokens = batch["regions"].to(dev), batch["input_ids"].to(dev)
+        text_lens = self._host_text_lens(batch=batch)
+        lens_kw = {} if text_lens is None else {"text_lens": text_lens}      # (a teacher without that argument: called as before)
         main = torch.cuda.current_stream(dev)
         if self._teacher_stream is None:
             self._teacher_stream = torch.cuda.Stream(device=dev)
         self._teacher_stream.wait_stream(main)                       # fork behind what is queued now (the current forward)
         with torch.cuda.stream(self._teacher_stream), torch.no_grad(), ops.workspace_lane(3):
             target = self.teacher.compute_global_embedding_tensors(regions, tokens, batch.get("region_counts"),
-                                                                   batch.get("max_tokens")).float()
+                                                                   batch.get("max_tokens"), **lens_kw).float()
             sentence = self.teacher.last_sentence_embedding
         self._prefetched = (self._batch_key(batch), target, sentence, regions, tokens)
         return True
@@ -258,6 +282,7 @@ class CLIPImageDistillation(LightningLikeModule):
         ran_teacher = True
         early_student_image = None
         grad_on = torch.is_grad_enabled()            # (the teacher branches below run under no_grad)
+        text_lens = None                             # packed_text: the captions' lengths, known on the host
         self.teacher.last_sentence_embedding = None
         if self.full_resolution_from_epoch is not None:
             self.teacher.full_resolution = self.teacher.full_resolution_packed = \
@@ -267,6 +292,7 @@ class CLIPImageDistillation(LightningLikeModule):
             images = batch["pixel_values"].to(dev)
             host_tokens = self._tokenize(batch["captions"])
             tokens = host_tokens.to(dev)
+            text_lens = self._host_text_lens(host_tokens)
             with torch.no_grad():
                 teacher_image = self.teacher.compute_global_embedding_batch(
                     batch["image_paths"], host_tokens, batch["weighted_boxes"], batch.get("images_u8"),
@@ -275,6 +301,8 @@ class CLIPImageDistillation(LightningLikeModule):
         elif isinstance(batch, dict):
             images = batch["pixel_values"].to(dev)
             tokens = batch["input_ids"].to(dev)
+            text_lens = self._host_text_lens(batch=batch)
+            lens_kw = {} if text_lens is None else {"text_lens": text_lens}
             with torch.no_grad():
                 if "teacher_image_emb" in batch:
                     teacher_image = batch["teacher_image_emb"].to(dev).float()
@@ -307,20 +335,21 @@ class CLIPImageDistillation(LightningLikeModule):
                             pixel_values=images, precision=self._image_precision()).float()
                     with torch.cuda.stream(self._teacher_stream), ops.workspace_lane(3):
                         teacher_image = self.teacher.compute_global_embedding_tensors(
-                            regions, tokens, batch.get("region_counts"), batch.get("max_tokens")).float()
+                            regions, tokens, batch.get("region_counts"), batch.get("max_tokens"), **lens_kw).float()
                     main.wait_stream(self._teacher_stream)                       # join
                     teacher_image.record_stream(main)
                     if self.teacher.last_sentence_embedding is not None:
                         self.teacher.last_sentence_embedding.record_stream(main)
                 else:
                     teacher_image = self.teacher.compute_global_embedding_tensors(
-                        batch["regions"].to(dev), tokens, batch.get("region_counts"), batch.get("max_tokens")).float()
+                        batch["regions"].to(dev), tokens, batch.get("region_counts"), batch.get("max_tokens"), **lens_kw).float()
                 teacher_text = batch["teacher_text_emb"].to(dev).float() if "teacher_text_emb" in batch else None
         else:
             images, captions, image_paths, weighted_boxes_batch = batch
             images = images.to(dev, non_blocking=images.is_pinned())   # pinned by the DataLoader (pin_memory=True, :687)
             host_tokens = self._tokenize(captions)
             tokens = host_tokens.to(dev)
+            text_lens = self._host_text_lens(host_tokens)
             with torch.no_grad():
                 # the teacher gets the HOST ids: it sizes its token padding from them without a stream sync
                 teacher_image = self.teacher.compute_global_embedding_batch(
@@ -342,6 +371,8 @@ class CLIPImageDistillation(LightningLikeModule):
             and not self.student.text_projection.weight.requires_grad
         # a frozen text tower runs the frozen 16-bit forward of the student's type (bf16 or fp16); a trainable one stays fp32
         text_precision = self.student_precision if (self.student_precision in ("bf16", "fp16") and text_frozen) else "fp32"
+        # packed_text: the frozen tower on captions cut after their first EOS (never while a graph is being captured)
+        packed_kw = {"packed_lens": text_lens} if (text_lens is not None and text_frozen) else {}
         text_job = None
         text_beside = self.overlap_frozen_text
         if text_beside is None:
@@ -354,7 +385,7 @@ class CLIPImageDistillation(LightningLikeModule):
             self._text_stream.wait_stream(main)                      # fork: the token ids are ready
             from . import ops
             with torch.cuda.stream(self._text_stream), torch.no_grad(), ops.workspace_lane(1):     # own scratch: concurrent
-                text_job = self.student.get_text_features(input_ids=tokens, precision=text_precision).float()
+                text_job = self.student.get_text_features(input_ids=tokens, precision=text_precision, **packed_kw).float()
         student_image = early_student_image if early_student_image is not None else \
             self.student.get_image_features(pixel_values=images, precision=self._image_precision()).float()
         loss_image = self.cosine_distillation_loss(student_image, teacher_image)
@@ -367,7 +398,7 @@ class CLIPImageDistillation(LightningLikeModule):
             student_text = text_job
         elif text_frozen:
             with torch.no_grad():          # frozen text tower (of a bf16 student: bf16 GEMM inputs there as well)
-                student_text = self.student.get_text_features(input_ids=tokens, precision=text_precision).float()
+                student_text = self.student.get_text_features(input_ids=tokens, precision=text_precision, **packed_kw).float()
         else:
             student_text = self.student.get_text_features(input_ids=tokens).float()
         if teacher_text is None:

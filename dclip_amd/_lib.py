@@ -58,6 +58,9 @@ SIGNATURES = {
     "dclip_vision_assemble_varlen": (I, [P, P, P, P, P, P, I, I, I, P]),
     "dclip_attention_varlen_fwd": (I, [P, P, P, P, I, I, I, I, P]),
     "dclip_gather_rows_at": (I, [P, P, P, I, I, I, P]),
+    "dclip_text_embed_varlen": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "dclip_attention_varlen_causal_fwd": (I, [P, P, P, P, I, I, I, I, P]),
+    "dclip_pack_tokens_varlen": (I, [P, P, P, P, I, I, I, P]),
     "dclip_normalize_rows_fwd": (I, [P, P, P, I, I, F, P]),
     "dclip_normalize_rows_bwd": (I, [P, P, P, P, I, I, F, I, P]),
     "dclip_contrastive_workspace": (Z, [I, I, I]),

@@ -158,6 +158,50 @@ def packed_crop_tables(boxes: torch.Tensor, patch: int) -> dict:
             "cls_rows": cu[:-1].clone(), "max_S": int(seq.max()) if boxes.shape[0] else 0}
 
 
+def packed_text_tables(input_ids_host: torch.Tensor, eos_id: int, lens=None) -> dict:
+    """Host tables of the packed text tower (engine.text_fwd_frozen_packed) for the captions input_ids_host
+    [N,T]: caption n keeps its rows 0 .. first EOS, len_n = first EOS index + 1, or 1 for a row without EOS (ops.first_eos
+    gives 0 for it).  `lens` (a host int sequence or a CPU tensor [N]) hands the lengths over instead: every one must lie in
+    [1, T], and the ids are then used for their shape only (they may live anywhere).  Without `lens` the ids must be on the
+    host: nothing is read back from a device.  Returns int32 contiguous CPU tensors `lens` [N], `cu_seqlens` [N+1] (cumulative
+    lengths) and `last_rows` [N] (= cu_seqlens[1:] - 1, the packed rows of the first EOS), and the ints `max_S`, `Tp`
+    (= cu_seqlens[N]) and `max_tokens` (= max(max(lens) - 2, 1): the word-token padding of ops.pack_tokens_varlen)."""
+    if input_ids_host.dim() != 2 or input_ids_host.shape[0] < 1 or input_ids_host.shape[1] < 1:
+        raise ValueError(f"packed_text_tables: input_ids {tuple(input_ids_host.shape)}, expected [N, T]")
+    N, T = input_ids_host.shape
+    if lens is None:
+        if input_ids_host.device.type != "cpu":
+            raise ValueError("packed_text_tables: the caption lengths come from token ids on the HOST (or pass lens); ids on "
+                             f"{input_ids_host.device} are never read back")
+        hit = input_ids_host == int(eos_id)
+        first = hit.int().argmax(dim=1)                        # 0 for a row without EOS, as ops.first_eos
+        lens_t = (first + 1).to(torch.int32)
+    else:
+        if isinstance(lens, torch.Tensor):
+            if lens.device.type != "cpu":
+                raise ValueError(f"packed_text_tables: lens must be on the host, got {lens.device}")
+            if lens.dtype.is_floating_point or lens.dtype == torch.bool:
+                raise ValueError(f"packed_text_tables: lens must be integers, got {lens.dtype}")
+            lens_t = lens.reshape(-1).to(torch.int64)
+        else:
+            lens_t = torch.tensor([int(v) for v in lens], dtype=torch.int64)
+        if lens_t.numel() != N:
+            raise ValueError(f"packed_text_tables: {lens_t.numel()} lengths for {N} captions")
+        if int(lens_t.min()) < 1 or int(lens_t.max()) > T:
+            bad = int(((lens_t < 1) | (lens_t > T)).nonzero()[0])
+            raise ValueError(f"packed_text_tables: caption {bad} has length {int(lens_t[bad])}, outside [1, {T}]")
+        lens_t = lens_t.to(torch.int32)
+    lens_t = lens_t.contiguous()
+    total = int(lens_t.long().sum())
+    if total >= 2 ** 31:
+        raise ValueError("packed captions: more than 2^31 token rows")
+    cu = torch.zeros(N + 1, dtype=torch.int32)
+    cu[1:] = torch.cumsum(lens_t.long(), 0).to(torch.int32)
+    max_S = int(lens_t.max())
+    return {"lens": lens_t, "cu_seqlens": cu, "last_rows": (cu[1:] - 1).contiguous(), "max_S": max_S, "Tp": total,
+            "max_tokens": max(max_S - 2, 1)}
+
+
 class HipCLIPModel(nn.Module):
     def __init__(self, config: Optional[ClipConfig] = None):
         super().__init__()
@@ -328,17 +372,41 @@ class HipCLIPModel(nn.Module):
         return n
 
     def get_text_features(self, input_ids: torch.Tensor = None, attention_mask=None, precision: str = "fp32",
-                          **kwargs) -> torch.Tensor:
+                          packed_lens=None, **kwargs) -> torch.Tensor:
         """`attention_mask` is accepted and ignored: under the causal mask trailing pads cannot influence the
         first-EOS row that is pooled.  precision="bf16" / "fp16": frozen forward only (see
-        get_image_features)."""
+        get_image_features).  `packed_lens` (opt-in, frozen use only): the captions' lengths on the HOST
+        (first EOS index + 1; an int sequence or a CPU tensor [B]), or True when `input_ids` is a CPU tensor (the lengths
+        are then derived from it).  The tower then runs on the captions cut after their first EOS and laid back to back
+        — the rows behind a first EOS are read by no result — under no_grad semantics.  Lengths are never read back from
+        the device: True with ids that are not on the host is a ValueError.  While a stream is capturing the padded path
+        runs (a captured graph's shapes must not follow the batch)."""
         if input_ids is None:
             raise ValueError("You have to specify input_ids")
         t = self.config.text
         if input_ids.shape[-1] > t.max_position_embeddings:
             raise ValueError(f"Sequence length must be less than max_position_embeddings (got `sequence length`: "
                              f"{input_ids.shape[-1]} and max_position_embeddings: {t.max_position_embeddings}")
+        packed = packed_lens is not None and packed_lens is not False
+        if packed and packed_lens is True and input_ids.device.type != "cpu":
+            raise ValueError(f"packed_lens=True needs input_ids on the host (got {input_ids.device}): caption lengths are never "
+                             "read back from the device; pass the lengths")
+        if precision not in ("fp32", "bf16", "fp16"):
+            raise ValueError(f"precision {precision!r}")
         p = self.text_params()
+        if packed:
+            if torch.is_grad_enabled() and any(x.requires_grad for x in p.tensors()):
+                raise RuntimeError("packed_lens is a forward-only path for frozen towers: call it under torch.no_grad()")
+            dev = p.tok.device
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                packed = False
+            else:
+                with torch.no_grad():
+                    tables = self._packed_text_tables(input_ids, None if packed_lens is True else packed_lens, dev)
+                    cache = {"fp32": self._split16_cache, "bf16": self._bf16_cache, "fp16": self._f16_cache}[precision]()
+                    return engine.text_fwd_frozen_packed(self.text_params_detached(), input_ids.to(dev).long().contiguous(),
+                                                         tables, t, precision, cache)
+            input_ids = input_ids.to(dev)
         if precision == "bf16":
             if torch.is_grad_enabled() and any(x.requires_grad for x in p.tensors()):
                 raise RuntimeError("precision='bf16' is a forward-only path for frozen towers: call it under torch.no_grad()")
@@ -349,9 +417,33 @@ class HipCLIPModel(nn.Module):
                 raise RuntimeError("precision='fp16' is a forward-only path for frozen towers: call it under torch.no_grad()")
             return engine.text_fwd_frozen_bf16(self.text_params_detached(), input_ids.long().contiguous(), t,
                                                self._f16_cache(), torch.float16)
-        if precision != "fp32":
-            raise ValueError(f"precision {precision!r}")
         return functional.TextTowerFn.apply(input_ids.long(), t, t.num_hidden_layers, self._split16_cache(), *p.tensors())
+
+    def _packed_text_tables(self, input_ids: torch.Tensor, lens, dev) -> dict:
+        """packed_text_tables plus `cu_seqlens_dev` / `last_rows_dev`: ONE upload of a buffer allocated for this call (a
+        staging buffer shared between calls could be rewritten while a teacher that runs a step ahead still reads it)."""
+        tables = packed_text_tables(input_ids, self.config.text.eos_token_id, lens)
+        N = input_ids.shape[0]
+        both = torch.cat([tables["cu_seqlens"], tables["last_rows"]]).to(dev, non_blocking=False)
+        tables["cu_seqlens_dev"], tables["last_rows_dev"] = both[:N + 1], both[N + 1:]
+        return tables
+
+    @torch.no_grad()
+    def text_token_level_packed(self, input_ids: torch.Tensor, lens=None, precision: str = "fp32"):
+        """text_token_level on packed captions: (sentence [B,P], tokens_packed [Tp,P], cu_seqlens on the device
+        [B+1], tables).  Caption b's rows are tokens_packed[cu[b] : cu[b+1]] (BOS .. first EOS); `lens` as get_text_features'
+        `packed_lens` (None: derived from `input_ids` on the host).  tables: packed_text_tables' result (max_tokens, ...)."""
+        if precision not in ("fp32", "bf16", "fp16"):
+            raise ValueError(f"precision {precision!r}")
+        t = self.config.text
+        if input_ids.shape[-1] > t.max_position_embeddings:
+            raise ValueError(f"Sequence length must be less than max_position_embeddings (got {input_ids.shape[-1]})")
+        dev = self.text_projection.weight.device
+        tables = self._packed_text_tables(input_ids, lens, dev)
+        cache = None if precision == "fp32" else (self._bf16_cache() if precision == "bf16" else self._f16_cache())
+        sent, tokens = engine.text_token_level_packed(self.text_params_detached(), input_ids.to(dev).long().contiguous(), tables,
+                                                      t, precision, cache)
+        return sent, tokens, tables["cu_seqlens_dev"], tables
 
     @torch.no_grad()
     def text_token_level(self, input_ids: torch.Tensor, precision: str = "fp32"):

@@ -188,6 +188,26 @@ __global__ void __launch_bounds__(256) pack_tokens_kernel(const float* __restric
   }
 }
 
+// pack_tokens_kernel's rule on PACKED token rows: caption b holds len_b = cu[b+1] - cu[b] rows (BOS .. first
+// EOS), its word tokens are rows cu[b] + 1 .. cu[b] + len_b - 2.  The table is clamped as in attn_varlen_fwd_kernel.
+__global__ void __launch_bounds__(256) pack_tokens_varlen_kernel(const float* __restrict__ tokens, const float* __restrict__ sentence,
+                                                                 const int32_t* __restrict__ cu, float* __restrict__ out, int N,
+                                                                 int Tmax, int P4, size_t total4) {
+  const int Tp = cu[N];
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
+    const int d = (int)(i % P4);
+    const size_t bt = i / P4;
+    const int t = (int)(bt % Tmax);
+    const size_t b = bt / Tmax;
+    const int row0 = min(max(cu[b], 0), Tp);
+    const int n = max(min(max(cu[b + 1], row0), Tp) - row0 - 2, 0);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (t < n) v = reinterpret_cast<const f32x4*>(tokens)[((size_t)row0 + 1 + t) * P4 + d];
+    else if (n == 0 && t == 0) v = reinterpret_cast<const f32x4*>(sentence)[b * P4 + d];
+    reinterpret_cast<f32x4*>(out)[i] = v;
+  }
+}
+
 // x[b, r, :] = 0 for r >= count[b]
 __global__ void __launch_bounds__(256) mask_rows_kernel(float* __restrict__ x, const int32_t* __restrict__ count, int R, int E4,
                                                         size_t total4) {
@@ -261,6 +281,19 @@ DCLIP_API int dclip_pack_tokens(const float* tokens, const float* sentence, cons
   hipLaunchKernelGGL(pack_tokens_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, tokens, sentence, eos, out,
                      T, Tmax, P / 4, total4);
   DCLIP_CHECK_LAUNCH("pack_tokens");
+  return DCLIP_OK;
+}
+
+DCLIP_API int dclip_pack_tokens_varlen(const float* tokens, const float* sentence, const int32_t* cu_seqlens, float* out, int N,
+                                       int Tmax, int P, void* stream) {
+  DCLIP_REQUIRE(tokens && sentence && cu_seqlens && out, "pack_tokens_varlen: null pointer");
+  DCLIP_REQUIRE(N > 0 && Tmax > 0 && P > 0 && P % 4 == 0, "pack_tokens_varlen: bad shape N=%d Tmax=%d P=%d", N, Tmax, P);
+  DCLIP_REQUIRE(((uintptr_t)tokens | (uintptr_t)sentence | (uintptr_t)out) % 16 == 0 && (uintptr_t)cu_seqlens % 4 == 0,
+                "pack_tokens_varlen: tokens / sentence / out must be 16-byte aligned, cu_seqlens 4-byte aligned");
+  const size_t total4 = (size_t)N * Tmax * P / 4;
+  hipLaunchKernelGGL(pack_tokens_varlen_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, tokens, sentence,
+                     cu_seqlens, out, N, Tmax, P / 4, total4);
+  DCLIP_CHECK_LAUNCH("pack_tokens_varlen");
   return DCLIP_OK;
 }
 

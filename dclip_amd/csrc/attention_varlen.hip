@@ -1,5 +1,6 @@
 // Self-attention over a PACKED batch of sequences of different lengths: the frozen vision tower run on all
-// region crops of a batch at their own sizes in one pass.  Forward only, fp32, non-causal.
+// region crops of a batch at their own sizes in one pass.  Forward only, fp32, non-causal.  Below it the causal twin for the
+// frozen text tower on packed captions.
 //
 // qkv [T][3*H*64] holds N sequences back to back, sequence n in rows cu[n] .. cu[n+1]-1.  The kernel is the tiled forward of
 // attention.hip (attn_fwd_kernel: a 64-query tile per workgroup, 64-key tiles streamed with the online softmax, P in the
@@ -121,6 +122,121 @@ __global__ void __launch_bounds__(256) attn_varlen_fwd_kernel(const float* __res
   }
 }
 
+// The CAUSAL twin: the frozen text tower on packed captions, caption n in rows cu[n] .. cu[n+1]-1 (its first
+// EOS is the last of them).  attn_fwd_kernel<true> of attention.hip with b*S replaced by cu[n]: query row i sees keys 0..i of
+// its own sequence, key tiles beyond the query tile are not visited.  grid (N*H, query tiles).  LAST: the only query is the
+// LAST row of each sequence, which sees all of its keys (the ragged twin of the one-row kernel behind dclip_attention_row_fwd):
+// out [N][H*64], lse [H][N], grid (N*H, 1); otherwise out [T][H*64], lse [H][T].  The table is clamped as above.
+template <bool LAST>
+__global__ void __launch_bounds__(256) attn_varlen_causal_fwd_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ cu,
+                                                                     float* __restrict__ out, float* __restrict__ lse, int N,
+                                                                     int H) {
+  const int n = blockIdx.x / H, h = blockIdx.x % H;
+  const int T = cu[N];
+  const int s0 = min(max(cu[n], 0), T);
+  const int S = min(max(cu[n + 1], s0), T) - s0;
+  const int Sq = LAST ? min(S, 1) : S;                     // LAST: one query row, at sequence position S - 1
+  const int q0 = blockIdx.y * TS;
+  if (q0 >= Sq) return;                                    // uniform over the workgroup, before any barrier
+
+  __shared__ __attribute__((aligned(16))) float lds[3 * TS * HD];
+  float* Qs = lds;
+  float* Ks = lds + TS * HD;
+  float* Vs = lds + 2 * TS * HD;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int qd = lane >> 4, l15 = lane & 15;
+  const int D = H * HD;
+  const size_t ld = (size_t)3 * D;
+  const float* kbase = qkv + (size_t)s0 * ld + h * HD + D;
+  const float* vbase = kbase + D;
+  const float* qbase = kbase - D + (LAST ? (size_t)(S - 1) * ld : (size_t)0);
+
+  {
+    f32x4 vq[4], vk[4], vv[4];
+    tile_fetch(vq, qbase, q0, Sq, ld);
+    tile_fetch(vk, kbase, 0, S, ld);
+    tile_fetch(vv, vbase, 0, S, ld);
+    tile_commit(Qs, vq, q0, Sq);
+    tile_commit(Ks, vk, 0, S);
+    tile_commit(Vs, vv, 0, S);
+  }
+  __syncthreads();
+  f32x4 qf[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) qf[g] = frag_k(Qs, 16 * wave, g, lane);
+
+  float m[4], l[4];
+  f32x4 o[4];
+  zero4(o);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    m[r] = -INFINITY;
+    l[r] = 0.f;
+  }
+  int nkt = (S + TS - 1) / TS;
+  if (!LAST) nkt = min(nkt, (int)blockIdx.y + 1);          // key tiles beyond the query tile are fully masked
+  for (int kt = 0; kt < nkt; ++kt) {
+    if (kt > 0) {
+      __syncthreads();  // everyone is done with the previous K/V tile
+      stage_tiles2(Ks, kbase, ld, Vs, vbase, ld, kt * TS, S);
+      __syncthreads();
+    }
+    f32x4 s[4];
+    zero4(s);
+    mma_rows_x_tileT(s, qf, Ks, lane);
+    float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const int key = kt * TS + nt * 16 + l15;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int qrow = q0 + 16 * wave + 4 * qd + r;
+        float v = s[nt][r] * kScale;
+        if (key >= S || (!LAST && key > qrow)) v = -INFINITY;
+        s[nt][r] = v;
+        mx[r] = fmaxf(mx[r], v);
+      }
+    }
+    float alpha[4], rs[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float mn = fmaxf(m[r], quarter_max(mx[r]));
+      const float msafe = (mn == -INFINITY) ? 0.f : mn;
+      alpha[r] = __expf(m[r] - msafe);  // m = -inf -> 0
+      m[r] = mn;
+      rs[r] = 0.f;
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        float p = __expf(s[nt][r] - msafe);
+        s[nt][r] = p;
+        rs[r] += p;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      l[r] = l[r] * alpha[r] + quarter_sum(rs[r]);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        o[nt][r] *= alpha[r];
+        Qs[tile_off(16 * wave + 4 * qd + r, nt * 16 + l15)] = s[nt][r];   // this wave's private rows
+      }
+    }
+    mma_tilerows_x_tile(o, Qs, 16 * wave, Vs, lane);
+  }
+  const size_t orow0 = LAST ? (size_t)n : (size_t)s0;      // first output row of this sequence
+  const size_t lse_ld = LAST ? (size_t)N : (size_t)T;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = q0 + 16 * wave + 4 * qd + r;
+    if (row < Sq) {
+      const float inv = 1.0f / l[r];
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) out[(orow0 + row) * D + h * HD + nt * 16 + l15] = o[nt][r] * inv;
+      if (lse && l15 == 0) lse[(size_t)h * lse_ld + orow0 + row] = m[r] + __logf(l[r]);
+    }
+  }
+}
+
 }  // namespace
 
 DCLIP_API int dclip_attention_varlen_fwd(const float* qkv, const int32_t* cu_seqlens, float* out, float* lse, int N, int max_S,
@@ -137,5 +253,22 @@ DCLIP_API int dclip_attention_varlen_fwd(const float* qkv, const int32_t* cu_seq
     hipLaunchKernelGGL((attn_varlen_fwd_kernel<false>), dim3(N * H, cdiv(max_S, TS)), dim3(256), 0, st, qkv, cu_seqlens, out, lse,
                        N, H);
   DCLIP_CHECK_LAUNCH("attention_varlen_fwd");
+  return DCLIP_OK;
+}
+
+DCLIP_API int dclip_attention_varlen_causal_fwd(const float* qkv, const int32_t* cu_seqlens, float* out, float* lse, int N,
+                                                int max_S, int H, int last_only, void* stream) {
+  DCLIP_REQUIRE(qkv && cu_seqlens && out, "attention_varlen_causal_fwd: null pointer");
+  DCLIP_REQUIRE(N > 0 && max_S > 0 && H > 0 && (long long)N * H < (1ll << 31),
+                "attention_varlen_causal_fwd: bad shape N=%d max_S=%d H=%d", N, max_S, H);
+  DCLIP_REQUIRE(((uintptr_t)qkv | (uintptr_t)out) % 16 == 0 && ((uintptr_t)cu_seqlens | (uintptr_t)lse) % 4 == 0,
+                "attention_varlen_causal_fwd: qkv / out must be 16-byte aligned, cu_seqlens / lse 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (last_only)
+    hipLaunchKernelGGL((attn_varlen_causal_fwd_kernel<true>), dim3(N * H, 1), dim3(256), 0, st, qkv, cu_seqlens, out, lse, N, H);
+  else
+    hipLaunchKernelGGL((attn_varlen_causal_fwd_kernel<false>), dim3(N * H, cdiv(max_S, TS)), dim3(256), 0, st, qkv, cu_seqlens,
+                       out, lse, N, H);
+  DCLIP_CHECK_LAUNCH("attention_varlen_causal_fwd");
   return DCLIP_OK;
 }

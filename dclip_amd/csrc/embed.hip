@@ -150,6 +150,27 @@ __global__ void __launch_bounds__(256) gather_rows_at_kernel(const float* __rest
   }
 }
 
+// x[cu[n] + t, :] = tok[ids[n, t], :] + pos[t, :] for t < len_n = cu[n+1] - cu[n] (at most T): the token rows of N captions
+// back to back, each cut after its first EOS.  Grid (N, chunks): a workgroup serves ONE caption, so no thread
+// searches the offset table; ids[n, t >= len_n] are never read and nothing is written outside [cu[n], cu[n+1]).  The table
+// is clamped into [0, cu[N]] and made non-decreasing as in attn_varlen_fwd_kernel; the id clamp is text_embed_fwd_kernel's.
+__global__ void __launch_bounds__(256) text_embed_varlen_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ cu,
+                                                                const float* __restrict__ tok, const float* __restrict__ pos,
+                                                                float* __restrict__ x, int N, int T, int D4, int vocab) {
+  const int n = blockIdx.x;
+  const int Tp = cu[N];
+  const int row0 = min(max(cu[n], 0), Tp);
+  const int len = min(min(max(cu[n + 1], row0), Tp) - row0, T);
+  const int total4 = len * D4;
+  for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < total4; i += gridDim.y * blockDim.x) {
+    const int d = i % D4, t = i / D4;
+    int64_t id = ids[(size_t)n * T + t];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    reinterpret_cast<f32x4*>(x)[((size_t)row0 + t) * D4 + d] =
+        reinterpret_cast<const f32x4*>(tok)[(size_t)id * D4 + d] + reinterpret_cast<const f32x4*>(pos)[(size_t)t * D4 + d];
+  }
+}
+
 }  // namespace
 
 DCLIP_API int dclip_im2col(const float* pixels, float* cols, int B, int C, int Himg, int Wimg, int patch, void* stream) {
@@ -274,5 +295,19 @@ DCLIP_API int dclip_gather_rows_at(const float* x, const int32_t* rows, float* o
   hipLaunchKernelGGL(gather_rows_at_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, x, rows, out, T, D / 4,
                      total4);
   DCLIP_CHECK_LAUNCH("gather_rows_at");
+  return DCLIP_OK;
+}
+
+DCLIP_API int dclip_text_embed_varlen(const int64_t* ids, const int32_t* cu_seqlens, const float* tok, const float* pos, float* x,
+                                      int N, int T, int D, int vocab, void* stream) {
+  DCLIP_REQUIRE(ids && cu_seqlens && tok && pos && x, "text_embed_varlen: null pointer");
+  DCLIP_REQUIRE(N > 0 && T > 0 && D > 0 && D % 4 == 0 && vocab > 0 && (long long)T * (D / 4) < (1ll << 31),
+                "text_embed_varlen: bad shape N=%d T=%d D=%d vocab=%d", N, T, D, vocab);
+  DCLIP_REQUIRE(((uintptr_t)tok | (uintptr_t)pos | (uintptr_t)x) % 16 == 0 && (uintptr_t)ids % 8 == 0 &&
+                    (uintptr_t)cu_seqlens % 4 == 0,
+                "text_embed_varlen: tok / pos / x must be 16-byte aligned, ids 8-byte, cu_seqlens 4-byte aligned");
+  hipLaunchKernelGGL(text_embed_varlen_kernel, dim3(N, 4), dim3(256), 0, (hipStream_t)stream, ids, cu_seqlens, tok, pos, x, N, T,
+                     D / 4, vocab);
+  DCLIP_CHECK_LAUNCH("text_embed_varlen");
   return DCLIP_OK;
 }

@@ -1561,3 +1561,123 @@ def text_token_level(p: TextParams, input_ids: torch.Tensor, cfg):
     eos = ops.first_eos(input_ids, t.eos_token_id)
     sentence = ops.gather_rows(tokens, eos, B, T, tokens.shape[1])
     return sentence, tokens, eos
+
+
+# --------------------------------------------------------------------------------------------- packed frozen text forward
+# The frozen text tower on captions cut after their first EOS and laid back to back: caption n in rows
+# cu_seqlens[n] .. cu_seqlens[n+1]-1, Tp rows in all.  The tower is causal and pools at the first EOS, so no result reads a row
+# behind it.  As in vision_fwd_packed, LayerNorm, the GEMMs and their epilogues run at M = Tp as they are; the embedding, the
+# attention core and the first-EOS gather have ragged forms (ops.text_embed_varlen, ops.attention_varlen_causal_fwd,
+# ops.gather_rows_at at `last_rows`).  `tables`: HipCLIPModel._packed_text_tables (host ints max_S / Tp, the two device tables).
+# Forward only.
+
+def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str, plan=None, cache=None):
+    """`n_layers` full layers at M = Tp.  mode "fp32" (plan None) / "split16" (plan: _split16_plan's) / "bf16" / "fp16"
+    (cache: the model's weight cache of that type; fp32 q | k | v for the fp32 packed core, the context is cast)."""
+    H, eps = cfg.num_attention_heads, cfg.layer_norm_eps
+    for li, lp in enumerate(layers[:n_layers]):
+        if mode == "fp32":
+            ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, eps, save_stats=False)
+            qkv = ops.gemm(ln1, lp.qkv_w, ops.LAYOUT_NT, bias=lp.qkv_b)
+            attn = ops.attention_varlen_causal_fwd(qkv, cu, max_S, H)
+            x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=x)
+            ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
+            g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
+            x = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
+        elif mode == "split16":
+            ent = plan[li]
+            e = ent["e"]
+            ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** e["ln1"])
+            qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
+            attn = ops.attention_varlen_causal_fwd(qkv, cu, max_S, H)
+            x1 = _split16_gemm(ops.split_f16x3(attn, 2.0 ** e["ctx"]), ent, "out", "ctx", bias=lp.out_b, residual=x)
+            ln2 = ops.layernorm_fwd_f16x3(x1, lp.ln2_w, lp.ln2_b, eps, 2.0 ** e["ln2"])
+            if _SPLIT16_FC1_EPI:
+                g3 = _split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True, split_out_scale=2.0 ** e["g"])
+            else:
+                g3 = ops.split_f16x3(_split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True), 2.0 ** e["g"])
+            x = _split16_gemm(g3, ent, "fc2", "g", bias=lp.fc2_b, residual=x1)
+        else:
+            k, pre = _OPS16[torch.bfloat16 if mode == "bf16" else torch.float16], f"t{li}."
+            ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, eps)
+            qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)                     # fp32 q | k | v
+            attn = k.cast(ops.attention_varlen_causal_fwd(qkv, cu, max_S, H))
+            x1 = k.gemm(attn, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b, residual=x)
+            ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
+            g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+            x = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
+    return x
+
+
+def _packed_text_mode(p: TextParams, cfg, precision: str, cache: Optional[dict], what: str, split16: bool):
+    """(mode, plan): "fp32" takes the split-fp16 plan exactly when the padded frozen forward would (text_fwd_frozen_split16)."""
+    if precision == "fp32":
+        plan = None
+        if split16 and cache is not None and _SPLIT16 and len(p.layers) > 0 and cfg.hidden_size % 8 == 0 \
+                and cfg.intermediate_size % 8 == 0:
+            plan = _split16_plan(p, cache)
+        return ("split16" if plan is not None else "fp32"), plan
+    if precision not in ("bf16", "fp16") or cache is None:
+        raise ValueError(f"{what}: precision {precision!r} (16-bit precisions need the model's weight cache)")
+    return precision, None
+
+
+def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, precision: str = "fp32",
+                           cache: Optional[dict] = None) -> torch.Tensor:
+    """ids [N,T] on the device (the padded matrix: the pads are never read) -> [N,P], the schedule of text_fwd_frozen /
+    text_fwd_frozen_split16 / text_fwd_frozen_bf16 at M = Tp: the last layer's attention for the first-EOS row of each caption
+    only (keys 0..eos, ops.attention_varlen_causal_fwd(last_only)), everything after it on those N rows.  `cache`: "fp32" the
+    model's split-fp16 cache (None: the plain fp32 GEMMs), "bf16" / "fp16" the weight cache of that type."""
+    t = cfg
+    D, H, eps = t.hidden_size, t.num_attention_heads, t.layer_norm_eps
+    if not p.layers:
+        raise ValueError("text_fwd_frozen_packed: the tower has no encoder layer")
+    mode, plan = _packed_text_mode(p, t, precision, cache, "text_fwd_frozen_packed", True)
+    cu, last_rows, max_S = tables["cu_seqlens_dev"], tables["last_rows_dev"], tables["max_S"]
+    x = ops.text_embed_varlen(input_ids, cu, p.tok, p.pos, tables["Tp"])
+    x = _packed_text_layers(x, p.layers, len(p.layers) - 1, cu, max_S, t, mode, plan, cache)
+    lp, li = p.layers[-1], len(p.layers) - 1
+    if mode in ("fp32", "split16"):
+        if mode == "split16":
+            ent = plan[-1]
+            ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"])
+            qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
+        else:
+            ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, eps, save_stats=False)
+            qkv = ops.gemm(ln1, lp.qkv_w, ops.LAYOUT_NT, bias=lp.qkv_b)
+        attn = ops.attention_varlen_causal_fwd(qkv, cu, max_S, H, last_only=True)
+        x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows_at(x, last_rows))
+        ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
+        g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
+        rows = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
+    else:
+        k, pre = _OPS16[torch.bfloat16 if mode == "bf16" else torch.float16], f"t{li}."
+        ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, eps)
+        qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)                         # fp32 q | k | v
+        attn16 = k.cast(ops.attention_varlen_causal_fwd(qkv, cu, max_S, H, last_only=True))
+        x1 = k.gemm(attn16, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b, residual=ops.gather_rows_at(x, last_rows))
+        ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
+        g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+        rows = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
+    pooled, _, _ = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=False)
+    return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+
+
+def text_token_level_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, precision: str = "fp32",
+                            cache: Optional[dict] = None):
+    """text_token_level / text_token_level_bf16 on packed captions: (sentence [N,P], tokens [Tp,P]), every layer at M = Tp;
+    the word tokens of caption n are rows cu[n] + 1 .. cu[n+1] - 2, its sentence embedding is row cu[n+1] - 1.  "fp32" runs
+    the plain fp32 GEMMs, as text_token_level does."""
+    t = cfg
+    mode, plan = _packed_text_mode(p, t, precision, cache, "text_token_level_packed", False)
+    cu, last_rows, max_S = tables["cu_seqlens_dev"], tables["last_rows_dev"], tables["max_S"]
+    x = ops.text_embed_varlen(input_ids, cu, p.tok, p.pos, tables["Tp"])
+    x = _packed_text_layers(x, p.layers, len(p.layers), cu, max_S, t, mode, plan, cache)
+    if mode == "fp32":
+        ln, _, _ = ops.layernorm_fwd(x, p.final_w, p.final_b, t.layer_norm_eps, save_stats=False)
+        tokens = ops.gemm(ln, p.proj_w, ops.LAYOUT_NT)
+    else:
+        k = _OPS16[torch.bfloat16 if mode == "bf16" else torch.float16]
+        ln = k.layernorm(x, p.final_w, p.final_b, t.layer_norm_eps)
+        tokens = k.gemm(ln, _w16(cache, "tproj", p.proj_w, k.cast))
+    return ops.gather_rows_at(tokens, last_rows), tokens

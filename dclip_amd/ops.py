@@ -1761,6 +1761,64 @@ def gather_rows_at(x: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------------- packed captions (text tower)
+
+def text_embed_varlen(ids, cu_seqlens: torch.Tensor, tok, pos, total_rows: int) -> torch.Tensor:
+    """Token rows [Tp, D] of N captions cut after their first EOS and laid back to back: row cu_seqlens[n] + t =
+    tok[ids[n, t]] + pos[t] for t < cu_seqlens[n+1] - cu_seqlens[n].  ids [N, T] is the padded id matrix (the pads are never
+    read); `total_rows` is Tp = cu_seqlens[N], which the caller has on the host."""
+    lib = _lib.load()
+    _ids(ids), _f32(tok, "token_embedding"), _f32(pos, "position_embedding")
+    N, T = ids.shape
+    vocab, D = tok.shape
+    if pos.shape[0] < T or pos.shape[1] != D:
+        raise ValueError(f"text_embed_varlen: sequence {T} longer than position table {tuple(pos.shape)}")
+    if N < 1 or D % 4 or not (N <= total_rows <= N * T):
+        raise ValueError(f"text_embed_varlen: {N} captions of up to {T} ids, {total_rows} packed rows, D {D} (% 4 == 0)")
+    _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    x = torch.empty((total_rows, D), dtype=torch.float32, device=tok.device)
+    _lib.check(lib.dclip_text_embed_varlen(ids.data_ptr(), cu_seqlens.data_ptr(), tok.data_ptr(), pos.data_ptr(), x.data_ptr(),
+                                           N, T, D, vocab, _stream()), "text_embed_varlen")
+    return x
+
+
+def attention_varlen_causal_fwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_S: int, H: int, last_only: bool = False,
+                                want_lse: bool = False):
+    """Causal self-attention inside each of the N packed sequences of qkv [Tp, 3*H*64] (rows cu_seqlens[n] ..
+    cu_seqlens[n+1]-1; Tp = cu_seqlens[N]): out [Tp, H*64], or with `last_only` the LAST row of each sequence (which sees all
+    of it), [N, H*64].  `max_S` bounds the lengths.  Returns out, or (out, lse [H, Tp] / [H, N]) with `want_lse`."""
+    lib = _lib.load()
+    _f32(qkv, "qkv")
+    N = cu_seqlens.numel() - 1
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or N < 1 or H < 1 or max_S < 1 or qkv.shape[0] < N:
+        raise ValueError(f"attention_varlen_causal_fwd: qkv {tuple(qkv.shape)}, H {H}, {N} sequences, max_S {max_S}")
+    _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    rows = N if last_only else qkv.shape[0]
+    out = torch.empty((rows, H * 64), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((H, rows), dtype=torch.float32, device=qkv.device) if want_lse else None
+    _lib.check(lib.dclip_attention_varlen_causal_fwd(qkv.data_ptr(), cu_seqlens.data_ptr(), out.data_ptr(), _ptr(lse), N, max_S,
+                                                     H, int(bool(last_only)), _stream()), "attention_varlen_causal_fwd")
+    return (out, lse) if want_lse else out
+
+
+def pack_tokens_varlen(tokens, sentence, cu_seqlens: torch.Tensor, Tmax: int) -> torch.Tensor:
+    """pack_tokens on packed token rows: tokens [Tp, P], sentence [N, P] -> [N, Tmax, P]; caption b's word tokens are rows
+    cu_seqlens[b] + 1 .. cu_seqlens[b+1] - 2, zero beyond; a caption without word tokens gives its sentence row in slot 0."""
+    lib = _lib.load()
+    _f32(tokens, "tokens"), _f32(sentence, "sentence")
+    N = cu_seqlens.numel() - 1
+    if tokens.dim() != 2 or N < 1 or tuple(sentence.shape) != (N, tokens.shape[1]) or tokens.shape[1] % 4 or Tmax < 1 \
+            or tokens.shape[0] < N:
+        raise ValueError(f"pack_tokens_varlen: tokens {tuple(tokens.shape)}, sentence {tuple(sentence.shape)}, {N} captions, "
+                         f"Tmax {Tmax}")
+    _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    Pd = tokens.shape[1]
+    out = torch.empty((N, Tmax, Pd), dtype=torch.float32, device=tokens.device)
+    _lib.check(lib.dclip_pack_tokens_varlen(tokens.data_ptr(), sentence.data_ptr(), cu_seqlens.data_ptr(), out.data_ptr(), N, Tmax,
+                                            Pd, _stream()), "pack_tokens_varlen")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- evaluation
 
 def rowdot_gather(a, b, idx=None):

@@ -397,7 +397,8 @@ class PatchTextAggregation(nn.Module):
     def __init__(self, embed_dim=512, num_heads=8, similarity_threshold=0.85, projection_model_path=None,
                  faiss_index_path=None, embeddings_json_path=None, clip_model: Optional[HipCLIPModel] = None,
                  tokenizer=None, tower_precision: str = "fp32", owns_clip: bool = False,
-                 text_twin: Optional[HipCLIPModel] = None, full_resolution_packed: bool = False):
+                 text_twin: Optional[HipCLIPModel] = None, full_resolution_packed: bool = False,
+                 packed_text: bool = False):
         """`tower_precision` ("fp32" default = the reference's arithmetic; "bf16" / "fp16" opt-in) selects how the FROZEN
         region / text towers multiply; the trainable cross_modal_attention always runs in fp32.
         `owns_clip`: the towers are this teacher's private frozen copy (they follow `.to()` / `.cuda()` although they
@@ -405,7 +406,11 @@ class PatchTextAggregation(nn.Module):
         when this teacher was built (the student a snapshot was taken from) — see shares_text_tower_with.
         `full_resolution_packed` (also an attribute): with `full_resolution` on, all crops of a batch go through the region
         tower in ONE packed pass, cut on the device (CLIPPatchTokenizer.encode_full_resolution_batch), instead
-        of one forward per crop size; the targets differ from the per-crop path's in the last bits."""
+        of one forward per crop size; the targets differ from the per-crop path's in the last bits.
+        `packed_text` (also an attribute): whenever the captions' lengths are known on the HOST (token ids still on the host,
+        or a `text_lens` argument) the frozen text tower runs on the captions cut after their first EOS and laid back to back
+        (HipCLIPModel.text_token_level_packed + ops.pack_tokens_varlen); the token padding size then comes from
+        those lengths, not from the device.  Without host lengths the padded path runs as before."""
         super().__init__()
         if tower_precision not in ("fp32", "bf16", "fp16"):
             raise ValueError(f"tower_precision {tower_precision!r}")
@@ -434,6 +439,7 @@ class PatchTextAggregation(nn.Module):
                                                        embeddings_json_path, similarity_threshold)
         self.full_resolution = False
         self.full_resolution_packed = bool(full_resolution_packed)
+        self.packed_text = bool(packed_text)
 
     @property
     def device(self):
@@ -475,14 +481,35 @@ class PatchTextAggregation(nn.Module):
     def aggregation(self, attended_text, temperature=2.0):
         return AggregationFn.apply(attended_text, temperature)
 
+    def _packed_text_lens(self, input_ids: torch.Tensor, text_lens=None):
+        """What the packed text pass takes as its lengths, or None when it does not run: `packed_text` off, no lengths on the
+        host (ids on the device and no `text_lens`), or a stream that is capturing (a graph's shapes must not follow the
+        batch).  True stands for "derive them from the host ids"."""
+        if not self.packed_text:
+            return None
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            return None
+        if text_lens is not None:
+            return text_lens
+        return True if input_ids.device.type == "cpu" else None
+
+    @torch.no_grad()
+    def _text_block_packed(self, input_ids: torch.Tensor, lens, max_tokens: Optional[int] = None):
+        """(sentence [B,P], word-token block [B,Tmax,P]) from one packed pass; Tmax = `max_tokens`, or the tables' figure."""
+        sent, tokens, cu, tables = self._clip.text_token_level_packed(input_ids, None if lens is True else lens,
+                                                                      precision=self.text_tokenizer.precision)
+        return sent, ops.pack_tokens_varlen(tokens, sent, cu, tables["max_tokens"] if max_tokens is None else int(max_tokens))
+
     # ---- tensor-in variant (synthetic configs, and the body of the path-based method)
     def compute_global_embedding_tensors(self, regions: torch.Tensor, input_ids: torch.Tensor,
                                          region_counts: Optional[torch.Tensor] = None,
                                          max_tokens: Optional[int] = None,
-                                         region_positions: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                         region_positions: Optional[torch.Tensor] = None, text_lens=None) -> torch.Tensor:
         """regions [B,R,3,S,S] in [0,1] (rows >= region_counts[b] ignored), input_ids [B,T] -> [B,E].
         With the KNN / projection tokenizer on, every region embedding is replaced by `knn_or_projection`'s
         (`region_positions` [B,R,4] = (x1/w, y1/h, x2/w, y2/h), None = zeros).
+        `text_lens` (host ints or a CPU tensor [B]: first EOS index + 1 per caption) or `input_ids` on the host, with
+        `packed_text` on: the text tower runs on packed captions and the token padding size comes from the lengths.
         Gradients flow only into cross_modal_attention (the towers run frozen, as in the reference:
         training/image_tokenizer.py:119, training/text_tokenizer.py:185)."""
         dev = self.device
@@ -494,7 +521,8 @@ class PatchTextAggregation(nn.Module):
             # one stream).  Not inside a HIP-graph capture (the fork would have to be part of every caller's warm-up).
             import os
             side = None
-            if regions.is_cuda and input_ids.is_cuda and not torch.cuda.is_current_stream_capturing() \
+            lens = self._packed_text_lens(input_ids, text_lens)
+            if regions.is_cuda and (input_ids.is_cuda or lens is not None) and not torch.cuda.is_current_stream_capturing() \
                     and os.environ.get("DCLIP_TEACHER_TEXT_STREAM", "1") != "0":
                 if getattr(self, "_text_side_stream", None) is None:
                     object.__setattr__(self, "_text_side_stream", torch.cuda.Stream(device=dev))
@@ -502,7 +530,10 @@ class PatchTextAggregation(nn.Module):
                 here = torch.cuda.current_stream(dev)
                 side.wait_stream(here)
                 with torch.cuda.stream(side), ops.workspace_lane(4):
-                    sent, tokens, eos = self.text_tokenizer.token_level_ids(input_ids)
+                    if lens is not None:
+                        sent, text = self._text_block_packed(input_ids, lens, max_tokens)
+                    else:
+                        sent, tokens, eos = self.text_tokenizer.token_level_ids(input_ids)
             emb = self.patch_tokenizer.encode_regions(regions.reshape(B * R, *regions.shape[2:])).view(B, R, -1)
             if self.use_knn_projection and self.advanced_tokenizer is not None:
                 pos = None if region_positions is None else region_positions.to(dev).float().reshape(B * R, 4)
@@ -512,15 +543,19 @@ class PatchTextAggregation(nn.Module):
                 rmax = max(int(region_counts.max()), 1)        # an image without boxes keeps ONE zero row (:489-491)
                 emb = ops.mask_rows(emb.contiguous(), counts)[:, :rmax].contiguous()
             if side is None:
-                sent, tokens, eos = self.text_tokenizer.token_level_ids(input_ids)
+                if lens is not None:
+                    sent, text = self._text_block_packed(input_ids, lens, max_tokens)
+                else:
+                    sent, tokens, eos = self.text_tokenizer.token_level_ids(input_ids)
             else:
                 here.wait_stream(side)
-                for t_ in (sent, tokens, eos):
+                for t_ in ((sent, text) if lens is not None else (sent, tokens, eos)):
                     t_.record_stream(here)
             self.last_sentence_embedding = sent       # text_projection(final_LN(h)[first EOS]) of THIS call's captions
-            if max_tokens is None:
-                max_tokens = max(int(eos.max()) - 1, 1)       # host sync; pass max_tokens to avoid it
-            text = ops.pack_tokens(tokens.contiguous(), sent, eos, max_tokens)
+            if lens is None:
+                if max_tokens is None:
+                    max_tokens = max(int(eos.max()) - 1, 1)       # host sync; pass max_tokens (or run packed_text) to avoid it
+                text = ops.pack_tokens(tokens.contiguous(), sent, eos, max_tokens)
         return self.global_embedding_from_tokens(text, emb)
 
     def global_embedding_from_tokens(self, text: torch.Tensor, patches: torch.Tensor) -> torch.Tensor:
@@ -573,6 +608,9 @@ class PatchTextAggregation(nn.Module):
         ids = self.text_tokenizer._ids(texts if isinstance(texts, torch.Tensor) else list(texts), keep_host=True)
         max_tokens = None
         if not ids.is_cuda:
+            if self._packed_text_lens(ids) is not None:
+                # packed_text: the host ids go down as they are; lengths and token padding size are derived from them there
+                return self.compute_global_embedding_tensors(regions, ids, counts, None, positions)
             # token ids still on the host (tokenizer output): the longest caption's word-token count is known without
             # asking the GPU — no stream synchronisation in the middle of the step
             eos_id = self._clip.config.text.eos_token_id
@@ -580,6 +618,17 @@ class PatchTextAggregation(nn.Module):
             max_tokens = max(int(first_eos.max()) - 1, 1)
             ids = ids.to(self.device)
         return self.compute_global_embedding_tensors(regions, ids, counts, max_tokens, positions)
+
+    @torch.no_grad()
+    def _sentence_and_token_block(self, texts):
+        """(sentence [B,P], word-token block [B,Tmax,P]) of the full-resolution paths: packed when `packed_text` is on and the
+        ids are on the host, otherwise the padded pass with its one read of the longest caption's length."""
+        ids = self.text_tokenizer._ids(texts if isinstance(texts, torch.Tensor) else list(texts), keep_host=True)
+        lens = self._packed_text_lens(ids)
+        if lens is not None:
+            return self._text_block_packed(ids, lens)
+        sent, tokens, eos = self.text_tokenizer.token_level_ids(ids.to(self.device))
+        return sent, ops.pack_tokens(tokens.contiguous(), sent, eos, max(int(eos.max()) - 1, 1))
 
     def _global_embedding_full_resolution(self, image_paths, texts, boxes, images_u8=None, dims=None):
         """`self.full_resolution` (training/CLIP_image_distillation.py:723-729): every box is encoded at its own size, image by
@@ -609,11 +658,8 @@ class PatchTextAggregation(nn.Module):
         for b, es in enumerate(per_image):
             if es:
                 emb[b, :len(es)] = torch.stack(es)
-        ids = self.text_tokenizer._ids(texts if isinstance(texts, torch.Tensor) else list(texts))
-        with torch.no_grad():
-            sent, tokens, eos = self.text_tokenizer.token_level_ids(ids)
-            self.last_sentence_embedding = sent
-            text = ops.pack_tokens(tokens.contiguous(), sent, eos, max(int(eos.max()) - 1, 1))
+        sent, text = self._sentence_and_token_block(texts)
+        self.last_sentence_embedding = sent
         return self.global_embedding_from_tokens(text, emb)
 
     def _global_embedding_full_resolution_packed(self, image_paths, texts, boxes, images_u8=None, dims=None):
@@ -630,11 +676,8 @@ class PatchTextAggregation(nn.Module):
                 except Exception:
                     images.append(Image.new("RGB", (224, 224)))        # the reference's fallback (:302)
         emb, _counts = self.patch_tokenizer.encode_full_resolution_batch(images, boxes, images_u8, dims)
-        ids = self.text_tokenizer._ids(texts if isinstance(texts, torch.Tensor) else list(texts))
-        with torch.no_grad():
-            sent, tokens, eos = self.text_tokenizer.token_level_ids(ids)
-            self.last_sentence_embedding = sent
-            text = ops.pack_tokens(tokens.contiguous(), sent, eos, max(int(eos.max()) - 1, 1))
+        sent, text = self._sentence_and_token_block(texts)
+        self.last_sentence_embedding = sent
         return self.global_embedding_from_tokens(text, emb)
 
     def _knn_query_crops(self, images, boxes_per_image):

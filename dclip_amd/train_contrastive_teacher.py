@@ -91,10 +91,15 @@ class JsonPairDataset:
 def _embeddings(teacher: PatchTextAggregation, batch):
     if isinstance(batch, dict):
         dev = teacher.device
-        ids = batch["input_ids"].to(dev)
-        img = teacher.compute_global_embedding_tensors(batch["regions"].to(dev), ids, batch.get("region_counts"),
-                                                       batch.get("max_tokens"))
-        txt = teacher.text_tokenizer.aggregate_text_ids(ids)
+        host_ids = batch["input_ids"]
+        ids = host_ids.to(dev)
+        # packed_text: lengths from batch["text_lens"] or from ids that are still on the host (they then go down as they are)
+        lens = teacher._packed_text_lens(host_ids, batch.get("text_lens"))
+        img = teacher.compute_global_embedding_tensors(batch["regions"].to(dev), host_ids if lens is True else ids,
+                                                       batch.get("region_counts"), batch.get("max_tokens"),
+                                                       text_lens=batch.get("text_lens"))
+        # the packed pass has just encoded these captions: its first-EOS rows ARE the sentence embeddings
+        txt = teacher.last_sentence_embedding if lens is not None else teacher.text_tokenizer.aggregate_text_ids(ids)
     else:
         _, captions, image_paths, weighted_boxes_batch = batch
         img = teacher.compute_global_embedding_batch(image_paths, captions, weighted_boxes_batch)
@@ -117,7 +122,8 @@ def build_teacher(args, device) -> PatchTextAggregation:
     return PatchTextAggregation(embed_dim=clip.config.projection_dim, num_heads=clip.config.projection_dim // 64,
                                 similarity_threshold=0.85, projection_model_path="", faiss_index_path="",
                                 embeddings_json_path="", clip_model=clip, tokenizer=tok,
-                                tower_precision=getattr(args, "tower_precision", "fp32")).to(device)
+                                tower_precision=getattr(args, "tower_precision", "fp32"),
+                                packed_text=bool(getattr(args, "packed_text", False))).to(device)
 
 
 def main(args, teacher: Optional[PatchTextAggregation] = None, train_batches: Optional[Iterable] = None,
@@ -244,6 +250,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--tower_precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
                         help="arithmetic of the FROZEN CLIP towers (fp32: exact; bf16 / fp16: 16-bit GEMM inputs); "
                              "the cross-modal block always trains in fp32")
+    parser.add_argument("--packed_text", action="store_true",
+                        help="run the frozen text tower on captions cut after their first EOS and laid back to back "
+                             "(lengths from the tokenizer's host output; default: the padded [B, T] rectangle)")
     return parser
 
 

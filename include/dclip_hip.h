@@ -258,6 +258,30 @@ int dclip_attention_varlen_fwd(const float* qkv, const int32_t* cu_seqlens, floa
 int dclip_gather_rows_at(const float* x, const int32_t* rows, float* out, int N, int T, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The frozen text tower on PACKED captions: each caption is cut after its first EOS and the captions lie back
+ * to back.  Forward only.  N captions; len_n = first EOS index + 1 (1 for a caption without EOS, as dclip_first_eos returns 0
+ * for it); cu_seqlens [N+1] (int32, on the device, built on the host from the token ids) are the cumulative lengths,
+ * Tp = cu_seqlens[N].  Every entry is clamped into [0, Tp] and made non-decreasing on the device.  The layers between these
+ * entries are row-wise over M = Tp and run unchanged; dclip_gather_rows_at at rows cu[1:] - 1 gathers the first-EOS rows.
+ * text_embed_varlen: replaces dclip_text_embed_fwd.  ids [N][T] int64 (the padded matrix); x [Tp][D]:
+ *   x[cu[n] + t] = tok[clamp(ids[n][t])] + pos[t] for t < min(len_n, T), the id clamp of dclip_text_embed_fwd.  ids[n][t >= len_n]
+ *   are never read and nothing is written outside rows [cu[n], cu[n+1]).  D % 4 == 0; tok / pos / x 16-byte aligned.
+ * attention_varlen_causal_fwd: replaces dclip_attention_fwd(causal = 1) / dclip_attention_row_fwd.  qkv [Tp][3*H*64] fp32;
+ *   query row i of a sequence sees keys 0..i of that sequence and nothing else.  last_only = 0: out [Tp][H*64], lse [H][Tp];
+ *   last_only = 1: the only query is the LAST row of each sequence (the first EOS, which sees the whole sequence), out
+ *   [N][H*64], lse [H][N].  lse may be NULL.  max_S bounds the lengths (it sizes the grid, as in attention_varlen_fwd).
+ *   A sequence's loads never leave its own rows.
+ * pack_tokens_varlen: replaces dclip_pack_tokens.  tokens [Tp][P] packed, sentence [N][P], out [N][Tmax][P]; with
+ *   n_b = max(len_b - 2, 0): out[b][i] = tokens[cu[b] + 1 + i] for i < n_b, zero beyond; n_b == 0 puts sentence[b] in slot 0.
+ * Each refuses N <= 0, a bad shape, a null or misaligned pointer with DCLIP_EINVAL before any launch. */
+int dclip_text_embed_varlen(const int64_t* ids, const int32_t* cu_seqlens, const float* tok, const float* pos, float* x, int N,
+                            int T, int D, int vocab, void* stream);
+int dclip_attention_varlen_causal_fwd(const float* qkv, const int32_t* cu_seqlens, float* out, float* lse, int N, int max_S,
+                                      int H, int last_only, void* stream);
+int dclip_pack_tokens_varlen(const float* tokens, const float* sentence, const int32_t* cu_seqlens, float* out, int N, int Tmax,
+                             int P, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Losses.
  * normalize_rows: xhat = x / max(||x||, eps), inv[b] = 1/max(||x||,eps)   (F.normalize,
  *   training/CLIP_image_distillation.py:545-546,:569-570; eps = 1e-12).
