@@ -73,7 +73,8 @@ def _as_hip_model(clip_model) -> HipCLIPModel:
 class CLIPImageDistillation(LightningLikeModule):
     def __init__(self, hparams, clip_model, clip_preprocess=None, teacher=None, freeze_mode: str = "north_star",
                  process_group=None, contrastive_teacher_path: Optional[str] = None, student_precision: str = "fp32",
-                 full_resolution_from_epoch: Optional[int] = None, packed_text: bool = False):
+                 full_resolution_from_epoch: Optional[int] = None, packed_text: bool = False,
+                 packed_attention16: Optional[bool] = None):
         """`student_precision`: "fp32" (default: the reference's `precision=32`,
         training/CLIP_image_distill_training.py:40, and the benched config c2) or "bf16" — the student's VISION tower
         multiplies in bf16 (forward, dgrad, wgrad) with fp32 master weights, fp32 accumulation and fp32
@@ -87,9 +88,13 @@ class CLIPImageDistillation(LightningLikeModule):
         the captions' lengths are known on the HOST — tokenizer output, `batch["input_ids"]` on the CPU, or `batch["text_lens"]`
         (first EOS index + 1 per caption, next to `max_tokens`) — every frozen text forward of the step runs on packed captions
         (HipCLIPModel.get_text_features(packed_lens=...)).  Without host lengths, or with a trainable text
-        tower, the padded path runs as before."""
+        tower, the padded path runs as before.
+        `packed_attention16` (True / False; None leaves the models as they are): set as `packed_attention16` on the student and
+        on the teacher's towers — their packed frozen passes at "bf16" / "fp16" then run the 16-bit MFMA attention core
+        (DESIGN.md §24)."""
         super().__init__()
         self.packed_text = bool(packed_text)
+        self.packed_attention16 = None if packed_attention16 is None else bool(packed_attention16)
         if full_resolution_from_epoch is not None and int(full_resolution_from_epoch) < 0:
             raise ValueError(f"full_resolution_from_epoch {full_resolution_from_epoch!r}")
         self.full_resolution_from_epoch = None if full_resolution_from_epoch is None else int(full_resolution_from_epoch)
@@ -137,6 +142,10 @@ class CLIPImageDistillation(LightningLikeModule):
         self.teacher = teacher
         if self.packed_text and hasattr(self.teacher, "packed_text"):
             self.teacher.packed_text = True
+        if self.packed_attention16 is not None:
+            for m in (self.student, getattr(self.teacher, "_clip", None)):
+                if isinstance(m, HipCLIPModel):
+                    m.packed_attention16 = self.packed_attention16
         if contrastive_teacher_path:
             # weights_only: a checkpoint is data, nothing in it is executed (training/CLIP_image_distillation.py:458-462)
             sd = torch.load(contrastive_teacher_path, map_location="cpu", weights_only=True)

@@ -61,6 +61,10 @@ SIGNATURES = {
     "dclip_text_embed_varlen": (I, [P, P, P, P, P, I, I, I, I, P]),
     "dclip_attention_varlen_causal_fwd": (I, [P, P, P, P, I, I, I, I, P]),
     "dclip_pack_tokens_varlen": (I, [P, P, P, P, I, I, I, P]),
+    "dclip_attention_varlen_fwd_bf16": (I, [P, P, P, I, I, I, I, P]),
+    "dclip_attention_varlen_fwd_f16": (I, [P, P, P, I, I, I, I, P]),
+    "dclip_attention_varlen_row_fwd_bf16": (I, [P, P, P, I, I, I, I, P]),
+    "dclip_attention_varlen_row_fwd_f16": (I, [P, P, P, I, I, I, I, P]),
     "dclip_normalize_rows_fwd": (I, [P, P, P, I, I, F, P]),
     "dclip_normalize_rows_bwd": (I, [P, P, P, P, I, I, F, I, P]),
     "dclip_contrastive_workspace": (Z, [I, I, I]),

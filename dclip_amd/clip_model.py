@@ -203,6 +203,11 @@ def packed_text_tables(input_ids_host: torch.Tensor, eos_id: int, lens=None) -> 
 
 
 class HipCLIPModel(nn.Module):
+    # The 16-bit MFMA attention core of the packed frozen towers for get_image_features_crops,
+    # get_text_features(packed_lens=...) and text_token_level_packed at precision "bf16" / "fp16": True / False, or None for the
+    # process-wide DCLIP_PACKED_ATTN16 (off unless set).
+    packed_attention16: Optional[bool] = None
+
     def __init__(self, config: Optional[ClipConfig] = None):
         super().__init__()
         self.config = config or ClipConfig()
@@ -297,7 +302,8 @@ class HipCLIPModel(nn.Module):
         (b, x1, y1, x2, y2) integers on the HOST (a tensor or a list).  Crop n is what PIL's crop((x1,y1,x2,y2)) + ToTensor()
         give (values in [0,1], zero outside the image, no mean / std), cut on the device; its position table is the model's,
         resampled to its patch grid as get_image_features(interpolate_pos_encoding=True) does.  A crop with a side shorter than
-        one patch is a ValueError.  precision: "fp32", "bf16" or "fp16" (16-bit GEMM inputs, fp32 attention core)."""
+        one patch is a ValueError.  precision: "fp32", "bf16" or "fp16" (16-bit GEMM inputs; fp32 attention core, or the 16-bit
+        packed core with `packed_attention16`)."""
         if precision not in ("fp32", "bf16", "fp16"):
             raise ValueError(f"precision {precision!r}")
         v = self.config.vision
@@ -316,7 +322,7 @@ class HipCLIPModel(nn.Module):
         cols = ops.patches_from_boxes_u8(images_u8, dims, bx, po, int(t["patch_offsets"][-1]), v.patch_size)
         pd = engine.VisionParams.from_tensors([x.detach() for x in self.vision_params().tensors()], v.num_hidden_layers)
         cache = None if precision == "fp32" else (self._bf16_cache() if precision == "bf16" else self._f16_cache())
-        return engine.vision_fwd_packed(pd, cols, grids, cu, cu[:N], t["max_S"], v, precision, cache)
+        return engine.vision_fwd_packed(pd, cols, grids, cu, cu[:N], t["max_S"], v, precision, cache, self.packed_attention16)
 
     def _bf16_cache(self) -> dict:
         """bf16 copies of the GEMM weights: persistent buffers, each refreshed in place when ITS parameter's version
@@ -405,7 +411,7 @@ class HipCLIPModel(nn.Module):
                     tables = self._packed_text_tables(input_ids, None if packed_lens is True else packed_lens, dev)
                     cache = {"fp32": self._split16_cache, "bf16": self._bf16_cache, "fp16": self._f16_cache}[precision]()
                     return engine.text_fwd_frozen_packed(self.text_params_detached(), input_ids.to(dev).long().contiguous(),
-                                                         tables, t, precision, cache)
+                                                         tables, t, precision, cache, self.packed_attention16)
             input_ids = input_ids.to(dev)
         if precision == "bf16":
             if torch.is_grad_enabled() and any(x.requires_grad for x in p.tensors()):
@@ -442,7 +448,7 @@ class HipCLIPModel(nn.Module):
         tables = self._packed_text_tables(input_ids, lens, dev)
         cache = None if precision == "fp32" else (self._bf16_cache() if precision == "bf16" else self._f16_cache())
         sent, tokens = engine.text_token_level_packed(self.text_params_detached(), input_ids.to(dev).long().contiguous(), tables,
-                                                      t, precision, cache)
+                                                      t, precision, cache, self.packed_attention16)
         return sent, tokens, tables["cu_seqlens_dev"], tables
 
     @torch.no_grad()

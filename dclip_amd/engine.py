@@ -440,9 +440,11 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
 class _Ops16:
     """The forward kernels of one 16-bit type (ops.*_bf16 or ops.*_f16)."""
 
-    def __init__(self, dtype, gemm, layernorm, attention, attention_row, cast, im2col, im2col_rect):
+    def __init__(self, dtype, gemm, layernorm, attention, attention_row, cast, im2col, im2col_rect, attention_varlen,
+                 attention_varlen_row):
         self.dtype, self._gemm, self.layernorm, self.attention = dtype, gemm, layernorm, attention
         self.attention_row, self.cast, self.im2col, self.im2col_rect = attention_row, cast, im2col, im2col_rect
+        self.attention_varlen, self.attention_varlen_row = attention_varlen, attention_varlen_row    # packed towers, §24
 
     def gemm(self, a, w, out16: bool = False, **kw):
         """y = epilogue(a w^T), a 16-bit result with `out16`."""
@@ -453,10 +455,31 @@ class _Ops16:
 
 _OPS16 = {
     torch.bfloat16: _Ops16(torch.bfloat16, ops.gemm_bf16, ops.layernorm_fwd_bf16, ops.attention_fwd_bf16,
-                           ops.attention_row_fwd_bf16, ops.cast_bf16, ops.im2col_bf16, ops.im2col_rect_bf16),
+                           ops.attention_row_fwd_bf16, ops.cast_bf16, ops.im2col_bf16, ops.im2col_rect_bf16,
+                           ops.attention_varlen_fwd_bf16, ops.attention_varlen_row_fwd_bf16),
     torch.float16: _Ops16(torch.float16, ops.gemm_f16, ops.layernorm_fwd_f16, ops.attention_fwd_f16,
-                          ops.attention_row_fwd_f16, ops.cast_f16, ops.im2col_f16, ops.im2col_rect_f16),
+                          ops.attention_row_fwd_f16, ops.cast_f16, ops.im2col_f16, ops.im2col_rect_f16,
+                          ops.attention_varlen_fwd_f16, ops.attention_varlen_row_fwd_f16),
 }
+
+
+# 16-bit MFMA attention core for the packed frozen towers: opt-in, read once at import like _SPLIT16 below.
+_PACKED_ATTN16 = os.environ.get("DCLIP_PACKED_ATTN16", "0") != "0"
+_ROW16_MAX_S = 512                                               # the one-row kernel's limit (attention_varlen16.hip, ROW_MAXI)
+
+
+def packed_attn16_route(precision: str, max_S: int, one_row: bool, attn16: Optional[bool] = None) -> str:
+    """Which attention core a packed frozen layer takes: "f32" — fp32 q | k | v, ops.attention_varlen*_fwd, and for the 16-bit
+    precisions a cast of the context (the only route with the switch off, with precision "fp32" and with the split-fp16 plan);
+    "tiled16" — 16-bit q | k | v and k.attention_varlen; "row16" — 16-bit q | k | v and k.attention_varlen_row, the last layer
+    of a pooled forward (`one_row`) up to 512 tokens; above that the last layer keeps "f32", as vision_fwd_bf16 does.
+    `attn16` None: the module value (DCLIP_PACKED_ATTN16)."""
+    on = _PACKED_ATTN16 if attn16 is None else bool(attn16)
+    if not on or precision not in ("bf16", "fp16"):
+        return "f32"
+    if not one_row:
+        return "tiled16"
+    return "row16" if max_S <= _ROW16_MAX_S else "f32"
 
 
 def _w16(cache: dict, key: str, w: torch.Tensor, cast=ops.cast_bf16) -> torch.Tensor:
@@ -535,11 +558,13 @@ def vision_fwd_bf16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dic
 # ragged forms (ops.vision_assemble_varlen, ops.attention_varlen_fwd, ops.gather_rows_at).  Forward only.
 
 def vision_fwd_packed(p: VisionParams, cols: torch.Tensor, grids: torch.Tensor, cu_seqlens: torch.Tensor,
-                      cls_rows: torch.Tensor, max_S: int, cfg, precision: str = "fp32", cache: Optional[dict] = None) -> torch.Tensor:
+                      cls_rows: torch.Tensor, max_S: int, cfg, precision: str = "fp32", cache: Optional[dict] = None,
+                      attn16: Optional[bool] = None) -> torch.Tensor:
     """cols [T - N, 3 p p] fp32 (ops.patches_from_boxes_u8), grids [N,2], cu_seqlens [N+1], cls_rows [N] (= cu_seqlens[:-1]),
     int32 on the device -> [N, P].  The schedule of vision_fwd without `save`: the last layer runs its out-projection and MLP on
     the N CLS rows only.  "bf16" / "fp16": 16-bit GEMM inputs with the persistent weight copies of `cache` (the model's cache of
-    that type, as vision_fwd_bf16); the qkv projection writes fp32 for the fp32 packed attention core and the context is cast."""
+    that type, as vision_fwd_bf16); the qkv projection writes fp32 for the fp32 packed attention core and the context is cast,
+    or with `attn16` (packed_attn16_route) q | k | v and the context stay 16-bit around the packed MFMA core."""
     v = cfg
     D, H, eps = v.hidden_size, v.num_attention_heads, v.layer_norm_eps
     if not p.layers:
@@ -569,8 +594,14 @@ def vision_fwd_packed(p: VisionParams, cols: torch.Tensor, grids: torch.Tensor, 
         for li, lp in enumerate(p.layers):
             last, pre = li == len(p.layers) - 1, f"v{li}."
             ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, eps)
-            qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)                     # fp32 q | k | v
-            attn = k.cast(ops.attention_varlen_fwd(qkv, cu_seqlens, max_S, H, cls_only=last))
+            route = packed_attn16_route(precision, max_S, last, attn16)
+            if route == "f32":
+                qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)                 # fp32 q | k | v
+                attn = k.cast(ops.attention_varlen_fwd(qkv, cu_seqlens, max_S, H, cls_only=last))
+            else:
+                qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b, out16=True)
+                attn = (k.attention_varlen_row(qkv, cu_seqlens, max_S, H, last=False) if route == "row16"
+                        else k.attention_varlen(qkv, cu_seqlens, max_S, H, False))
             x1 = k.gemm(attn, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b,
                         residual=ops.gather_rows_at(x, cls_rows) if last else x)
             ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
@@ -1571,9 +1602,11 @@ def text_token_level(p: TextParams, input_ids: torch.Tensor, cfg):
 # ops.gather_rows_at at `last_rows`).  `tables`: HipCLIPModel._packed_text_tables (host ints max_S / Tp, the two device tables).
 # Forward only.
 
-def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str, plan=None, cache=None):
+def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str, plan=None, cache=None,
+                        attn16: Optional[bool] = None):
     """`n_layers` full layers at M = Tp.  mode "fp32" (plan None) / "split16" (plan: _split16_plan's) / "bf16" / "fp16"
-    (cache: the model's weight cache of that type; fp32 q | k | v for the fp32 packed core, the context is cast)."""
+    (cache: the model's weight cache of that type; fp32 q | k | v for the fp32 packed core, the context is cast — or, with
+    `attn16`, 16-bit q | k | v and context around the packed MFMA core, packed_attn16_route)."""
     H, eps = cfg.num_attention_heads, cfg.layer_norm_eps
     for li, lp in enumerate(layers[:n_layers]):
         if mode == "fp32":
@@ -1600,8 +1633,12 @@ def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str
         else:
             k, pre = _OPS16[torch.bfloat16 if mode == "bf16" else torch.float16], f"t{li}."
             ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, eps)
-            qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)                     # fp32 q | k | v
-            attn = k.cast(ops.attention_varlen_causal_fwd(qkv, cu, max_S, H))
+            if packed_attn16_route(mode, max_S, False, attn16) == "tiled16":
+                qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b, out16=True)
+                attn = k.attention_varlen(qkv, cu, max_S, H, True)
+            else:
+                qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)                 # fp32 q | k | v
+                attn = k.cast(ops.attention_varlen_causal_fwd(qkv, cu, max_S, H))
             x1 = k.gemm(attn, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b, residual=x)
             ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
             g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
@@ -1623,11 +1660,12 @@ def _packed_text_mode(p: TextParams, cfg, precision: str, cache: Optional[dict],
 
 
 def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, precision: str = "fp32",
-                           cache: Optional[dict] = None) -> torch.Tensor:
+                           cache: Optional[dict] = None, attn16: Optional[bool] = None) -> torch.Tensor:
     """ids [N,T] on the device (the padded matrix: the pads are never read) -> [N,P], the schedule of text_fwd_frozen /
     text_fwd_frozen_split16 / text_fwd_frozen_bf16 at M = Tp: the last layer's attention for the first-EOS row of each caption
     only (keys 0..eos, ops.attention_varlen_causal_fwd(last_only)), everything after it on those N rows.  `cache`: "fp32" the
-    model's split-fp16 cache (None: the plain fp32 GEMMs), "bf16" / "fp16" the weight cache of that type."""
+    model's split-fp16 cache (None: the plain fp32 GEMMs), "bf16" / "fp16" the weight cache of that type.  `attn16`: the 16-bit
+    packed attention core for those two (packed_attn16_route; the last layer takes the one-row kernel up to 512 tokens)."""
     t = cfg
     D, H, eps = t.hidden_size, t.num_attention_heads, t.layer_norm_eps
     if not p.layers:
@@ -1635,7 +1673,7 @@ def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict,
     mode, plan = _packed_text_mode(p, t, precision, cache, "text_fwd_frozen_packed", True)
     cu, last_rows, max_S = tables["cu_seqlens_dev"], tables["last_rows_dev"], tables["max_S"]
     x = ops.text_embed_varlen(input_ids, cu, p.tok, p.pos, tables["Tp"])
-    x = _packed_text_layers(x, p.layers, len(p.layers) - 1, cu, max_S, t, mode, plan, cache)
+    x = _packed_text_layers(x, p.layers, len(p.layers) - 1, cu, max_S, t, mode, plan, cache, attn16)
     lp, li = p.layers[-1], len(p.layers) - 1
     if mode in ("fp32", "split16"):
         if mode == "split16":
@@ -1653,9 +1691,13 @@ def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict,
     else:
         k, pre = _OPS16[torch.bfloat16 if mode == "bf16" else torch.float16], f"t{li}."
         ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, eps)
-        qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)                         # fp32 q | k | v
-        attn16 = k.cast(ops.attention_varlen_causal_fwd(qkv, cu, max_S, H, last_only=True))
-        x1 = k.gemm(attn16, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b, residual=ops.gather_rows_at(x, last_rows))
+        if packed_attn16_route(mode, max_S, True, attn16) == "row16":
+            qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b, out16=True)
+            ctx16 = k.attention_varlen_row(qkv, cu, max_S, H, last=True)
+        else:
+            qkv = k.gemm(ln1, _w16(cache, pre + "qkv", lp.qkv_w, k.cast), bias=lp.qkv_b)                     # fp32 q | k | v
+            ctx16 = k.cast(ops.attention_varlen_causal_fwd(qkv, cu, max_S, H, last_only=True))
+        x1 = k.gemm(ctx16, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b, residual=ops.gather_rows_at(x, last_rows))
         ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
         g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
         rows = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
@@ -1664,15 +1706,15 @@ def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict,
 
 
 def text_token_level_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, precision: str = "fp32",
-                            cache: Optional[dict] = None):
+                            cache: Optional[dict] = None, attn16: Optional[bool] = None):
     """text_token_level / text_token_level_bf16 on packed captions: (sentence [N,P], tokens [Tp,P]), every layer at M = Tp;
     the word tokens of caption n are rows cu[n] + 1 .. cu[n+1] - 2, its sentence embedding is row cu[n+1] - 1.  "fp32" runs
-    the plain fp32 GEMMs, as text_token_level does."""
+    the plain fp32 GEMMs, as text_token_level does.  `attn16`: as in text_fwd_frozen_packed (every layer is a full layer)."""
     t = cfg
     mode, plan = _packed_text_mode(p, t, precision, cache, "text_token_level_packed", False)
     cu, last_rows, max_S = tables["cu_seqlens_dev"], tables["last_rows_dev"], tables["max_S"]
     x = ops.text_embed_varlen(input_ids, cu, p.tok, p.pos, tables["Tp"])
-    x = _packed_text_layers(x, p.layers, len(p.layers), cu, max_S, t, mode, plan, cache)
+    x = _packed_text_layers(x, p.layers, len(p.layers), cu, max_S, t, mode, plan, cache, attn16)
     if mode == "fp32":
         ln, _, _ = ops.layernorm_fwd(x, p.final_w, p.final_b, t.layer_norm_eps, save_stats=False)
         tokens = ops.gemm(ln, p.proj_w, ops.LAYOUT_NT)

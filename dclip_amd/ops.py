@@ -1819,6 +1819,46 @@ def pack_tokens_varlen(tokens, sentence, cu_seqlens: torch.Tensor, Tmax: int) ->
     return out
 
 
+# ------------------------------------------------------------------------------------------- 16-bit packed attention core
+
+def _attention_varlen16(name: str, dtype, check, qkv, cu_seqlens, max_S: int, H: int, flag: bool, one_row: bool) -> torch.Tensor:
+    lib = _lib.load()
+    check(qkv, "qkv")
+    N = cu_seqlens.numel() - 1
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or N < 1 or H < 1 or max_S < 1 or qkv.shape[0] < N:
+        raise ValueError(f"{name}: qkv {tuple(qkv.shape)}, H {H}, {N} sequences, max_S {max_S}")
+    if one_row and max_S > 512:
+        raise ValueError(f"{name}: max_S {max_S} > 512")
+    _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    out = torch.empty((N if one_row else qkv.shape[0], H * 64), dtype=dtype, device=qkv.device)
+    _lib.check(getattr(lib, "dclip_" + name)(qkv.data_ptr(), cu_seqlens.data_ptr(), out.data_ptr(), N, max_S, H, int(bool(flag)),
+                                             _stream()), name)
+    return out
+
+
+def attention_varlen_fwd_bf16(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_S: int, H: int, causal: bool = False) -> torch.Tensor:
+    """Self-attention inside each of the N packed sequences of a bf16 qkv [T, 3*H*64] (rows cu_seqlens[n] .. cu_seqlens[n+1]-1;
+    T = cu_seqlens[N]) on the bf16 MFMAs: context [T, H*64] bf16.  `causal`: query i sees keys 0..i of its sequence.  `max_S`
+    bounds the lengths."""
+    return _attention_varlen16("attention_varlen_fwd_bf16", torch.bfloat16, _bf16, qkv, cu_seqlens, max_S, H, causal, False)
+
+
+def attention_varlen_fwd_f16(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_S: int, H: int, causal: bool = False) -> torch.Tensor:
+    """attention_varlen_fwd_bf16 on an fp16 qkv: [T, H*64] fp16."""
+    return _attention_varlen16("attention_varlen_fwd_f16", torch.float16, _f16, qkv, cu_seqlens, max_S, H, causal, False)
+
+
+def attention_varlen_row_fwd_bf16(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_S: int, H: int, last: bool = False) -> torch.Tensor:
+    """One attention output row per packed sequence from a bf16 qkv [T, 3*H*64]: row 0 of each sequence (the CLS row), or with
+    `last` its last row (the first EOS of a packed caption), against all keys of that sequence.  [N, H*64] bf16; max_S <= 512."""
+    return _attention_varlen16("attention_varlen_row_fwd_bf16", torch.bfloat16, _bf16, qkv, cu_seqlens, max_S, H, last, True)
+
+
+def attention_varlen_row_fwd_f16(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_S: int, H: int, last: bool = False) -> torch.Tensor:
+    """attention_varlen_row_fwd_bf16 on an fp16 qkv: [N, H*64] fp16."""
+    return _attention_varlen16("attention_varlen_row_fwd_f16", torch.float16, _f16, qkv, cu_seqlens, max_S, H, last, True)
+
+
 # ------------------------------------------------------------------------------------------- evaluation
 
 def rowdot_gather(a, b, idx=None):

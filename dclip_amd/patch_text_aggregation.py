@@ -398,7 +398,7 @@ class PatchTextAggregation(nn.Module):
                  faiss_index_path=None, embeddings_json_path=None, clip_model: Optional[HipCLIPModel] = None,
                  tokenizer=None, tower_precision: str = "fp32", owns_clip: bool = False,
                  text_twin: Optional[HipCLIPModel] = None, full_resolution_packed: bool = False,
-                 packed_text: bool = False):
+                 packed_text: bool = False, packed_attention16: Optional[bool] = None):
         """`tower_precision` ("fp32" default = the reference's arithmetic; "bf16" / "fp16" opt-in) selects how the FROZEN
         region / text towers multiply; the trainable cross_modal_attention always runs in fp32.
         `owns_clip`: the towers are this teacher's private frozen copy (they follow `.to()` / `.cuda()` although they
@@ -410,10 +410,14 @@ class PatchTextAggregation(nn.Module):
         `packed_text` (also an attribute): whenever the captions' lengths are known on the HOST (token ids still on the host,
         or a `text_lens` argument) the frozen text tower runs on the captions cut after their first EOS and laid back to back
         (HipCLIPModel.text_token_level_packed + ops.pack_tokens_varlen); the token padding size then comes from
-        those lengths, not from the device.  Without host lengths the padded path runs as before."""
+        those lengths, not from the device.  Without host lengths the padded path runs as before.
+        `packed_attention16` (True / False; None leaves the model as it is): set as `clip_model.packed_attention16` — the two
+        packed passes above then run the 16-bit MFMA attention core at `tower_precision` "bf16" / "fp16" (DESIGN.md §24)."""
         super().__init__()
         if tower_precision not in ("fp32", "bf16", "fp16"):
             raise ValueError(f"tower_precision {tower_precision!r}")
+        if packed_attention16 is not None and clip_model is not None:
+            clip_model.packed_attention16 = bool(packed_attention16)
         if clip_model is None:
             raise ValueError("pass clip_model (a HipCLIPModel holding the teacher's CLIP towers); nothing is "
                              "downloaded by name here")

@@ -123,7 +123,8 @@ def build_teacher(args, device) -> PatchTextAggregation:
                                 similarity_threshold=0.85, projection_model_path="", faiss_index_path="",
                                 embeddings_json_path="", clip_model=clip, tokenizer=tok,
                                 tower_precision=getattr(args, "tower_precision", "fp32"),
-                                packed_text=bool(getattr(args, "packed_text", False))).to(device)
+                                packed_text=bool(getattr(args, "packed_text", False)),
+                                packed_attention16=True if getattr(args, "packed_attention16", False) else None).to(device)
 
 
 def main(args, teacher: Optional[PatchTextAggregation] = None, train_batches: Optional[Iterable] = None,
@@ -253,6 +254,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--packed_text", action="store_true",
                         help="run the frozen text tower on captions cut after their first EOS and laid back to back "
                              "(lengths from the tokenizer's host output; default: the padded [B, T] rectangle)")
+    parser.add_argument("--packed_attention16", action="store_true",
+                        help="with --tower_precision bf16 / fp16: the packed frozen towers keep q, k, v and the context in 16 "
+                             "bits and run the packed MFMA attention core (default: the fp32 packed core and a cast)")
     return parser
 
 

@@ -282,6 +282,30 @@ int dclip_pack_tokens_varlen(const float* tokens, const float* sentence, const i
                              int P, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 16-bit MFMA attention core for the two packed frozen towers above.  Forward only, head dim 64, no lse.
+ * qkv [T][3*H*64] bf16 / fp16 (the qkv projection writes it), N sequences back to back, sequence n in rows cu[n] .. cu[n+1]-1,
+ * T = cu_seqlens[N]; every table entry is clamped into [0, T] and made non-decreasing on the device.  Scores and softmax are
+ * fp32; a sequence's loads never leave its own rows; an empty sequence writes nothing.
+ * attention_varlen_fwd_*: the padded tiled kernel of dclip_attention_fwd_bf16 / _f16 (P rounded to the type for P V) with b*S
+ *   replaced by cu[n]: bit-equal to it on equal lengths above 288.  causal = 0: every query sees all keys of its sequence (packed
+ *   vision crops); causal = 1: query i sees keys 0..i (packed captions).  out [T][H*64] of the type.  max_S bounds the lengths (it
+ *   sizes the grid: query rows at or beyond max_S of a sequence are not computed).
+ * attention_varlen_row_fwd_*: one query row per sequence, P kept in fp32 (dclip_attention_row_fwd_bf16 / _f16 with the same
+ *   substitution).  last = 0: row 0 of each sequence (CLS); last = 1: its last row (the first EOS).  Either way the query sees
+ *   all keys of its own sequence.  out [N][H*64] of the type; the row of an empty sequence is left untouched.  max_S <= 512;
+ *   lengths are clamped to max_S.
+ * Each refuses N <= 0, H <= 0, max_S <= 0 (row: max_S > 512), N*H >= 2^31, a null pointer, qkv / out not 16-byte aligned or
+ * cu_seqlens not 4-byte aligned with DCLIP_EINVAL before any launch. */
+int dclip_attention_varlen_fwd_bf16(const void* qkv, const int32_t* cu_seqlens, void* out, int N, int max_S, int H, int causal,
+                                    void* stream);
+int dclip_attention_varlen_fwd_f16(const void* qkv, const int32_t* cu_seqlens, void* out, int N, int max_S, int H, int causal,
+                                   void* stream);
+int dclip_attention_varlen_row_fwd_bf16(const void* qkv, const int32_t* cu_seqlens, void* out, int N, int max_S, int H, int last,
+                                        void* stream);
+int dclip_attention_varlen_row_fwd_f16(const void* qkv, const int32_t* cu_seqlens, void* out, int N, int max_S, int H, int last,
+                                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Losses.
  * normalize_rows: xhat = x / max(||x||, eps), inv[b] = 1/max(||x||,eps)   (F.normalize,
  *   training/CLIP_image_distillation.py:545-546,:569-570; eps = 1e-12).

@@ -5,9 +5,11 @@ A seeded batch of synthetic photos (about 480 x 640) with boxes whose sides are 
 (random weights) in fp32 and in bf16.  Both paths get the batch as data.GpuCollate hands it over (images_u8 / dims on the
 device).  After one warm-up call of each, the two paths alternate; every timed window is one teacher call and ends in a
 device synchronise.  Prints ms per teacher call (each pair, then median and spread), the launches of one call of each path
-and the largest relative difference of the two targets.
+and the largest relative difference of the two targets.  --attn16 adds, for bf16 and fp16, the leg "packed + 16-bit core" (the
+packed pass with HipCLIPModel.packed_attention16 on), which alternates with the other two under the same protocol.
 
-usage: python tools/fullres_teacher_bench.py [--images 64] [--boxes 8] [--pairs 3] [--precisions fp32 bf16] [--json out.json]
+usage: python tools/fullres_teacher_bench.py [--images 64] [--boxes 8] [--pairs 3] [--precisions fp32 bf16] [--attn16]
+       [--json out.json]
 """
 import argparse
 import json
@@ -66,6 +68,8 @@ def main(argv=None):
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precisions", nargs="+", default=["fp32", "bf16"], choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--attn16", action="store_true",
+                    help="bf16 / fp16: add the leg `packed + 16-bit core` (HipCLIPModel.packed_attention16), alternating with the others")
     ap.add_argument("--json", default=None)
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "a measurement needs the GPU"
@@ -85,8 +89,9 @@ def main(argv=None):
         print(f"[{prec}] {args.images} images, {sum(plan['counts'])} crops kept, {int(plan['cu_seqlens'][-1])} packed token rows, "
               f"longest sequence {plan['max_S']}, {len(set(map(tuple, plan['grids'].tolist())))} distinct grids")
 
-        def call(packed: bool):
+        def call(packed: bool, attn16: bool = False):
             teacher.full_resolution_packed = packed
+            clip.packed_attention16 = attn16
             with torch.no_grad():
                 out = teacher.compute_global_embedding_batch(paths, ids, boxes, images_u8=u8, dims=dims)
             torch.cuda.synchronize()
@@ -100,15 +105,29 @@ def main(argv=None):
         print(f"[{prec}] launches per teacher call: per-crop {n_crop}, packed {n_pack}")
         print(f"[{prec}] packed-only launch sites: {[s for s in sites_pack if s not in sites_crop]}")
         print(f"[{prec}] largest relative difference of the two targets {diff:.3e}, smallest cosine {cos:.8f}")
-        ms = {"per_crop": [], "packed": []}
+        # --attn16 (16-bit precisions): a third leg, the packed pass with the 16-bit packed attention core
+        legs = [("per_crop", False, False), ("packed", True, False)]
+        if args.attn16 and prec != "fp32":
+            legs.append(("packed16", True, True))
+            got16, n_pack16, _ = count_launches(lambda: call(True, True))              # its warm-up
+            d16 = float((got16 - got).abs().max() / got.abs().max())
+            c16 = float(torch.nn.functional.cosine_similarity(got16.double(), got.double(), dim=1).min())
+            print(f"[{prec}] packed + 16-bit core: {n_pack16} launches per teacher call; against the packed target: largest relative "
+                  f"difference {d16:.3e}, smallest cosine {c16:.8f}")
+        ms = {name: [] for name, _, _ in legs}
         for pair in range(args.pairs):
-            for name, packed in (("per_crop", False), ("packed", True)):
+            for name, packed, a16 in legs:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                call(packed)
+                call(packed, a16)
                 ms[name].append(1e3 * (time.perf_counter() - t0))
-            print(f"[{prec}] pair {pair}: per-crop {ms['per_crop'][-1]:.1f} ms, packed {ms['packed'][-1]:.1f} ms")
+            print(f"[{prec}] pair {pair}: " + ", ".join(f"{name} {ms[name][-1]:.1f} ms" for name in ms))
         med = {k: statistics.median(v) for k, v in ms.items()}
+        if "packed16" in ms:
+            print(f"[{prec}] packed + 16-bit core {med['packed16']:.2f} ms (min {min(ms['packed16']):.2f}, max {max(ms['packed16']):.2f}) "
+                  f"against packed {med['packed']:.2f} (min {min(ms['packed']):.2f}, max {max(ms['packed']):.2f}); packed / packed16 "
+                  f"{med['packed'] / med['packed16']:.2f}")
+        clip.packed_attention16 = None
         print(f"[{prec}] ms per teacher call, median of {args.pairs}: per-crop {med['per_crop']:.1f} "
               f"(min {min(ms['per_crop']):.1f}, max {max(ms['per_crop']):.1f}), packed {med['packed']:.1f} "
               f"(min {min(ms['packed']):.1f}, max {max(ms['packed']):.1f}); ratio {med['per_crop'] / med['packed']:.2f}")

@@ -7,9 +7,11 @@ has been measured for this project; (2) every caption 77 tokens long, the worst 
 synthetic ids are.  For fp32 (the split-fp16 plan, the default), bf16 and fp16: after one warm-up call of each path the two
 alternate for --pairs pairs; a timed window is --calls get_text_features calls and ends in a device synchronise.  Prints the
 realised mean and maximum length, Tp / (B * Tmax), ms per call (each pair, then the median and the spread) and the largest
-relative difference of the two outputs.
+relative difference of the two outputs.  --attn16 adds, for bf16 and fp16, the leg "packed + 16-bit core" (the packed tower with
+HipCLIPModel.packed_attention16 on), which alternates with the other two under the same protocol.
 
-usage: python tools/packed_text_bench.py [--batch 256] [--mean 20] [--sd 8] [--max 77] [--pairs 3] [--calls 10] [--json out.json]
+usage: python tools/packed_text_bench.py [--batch 256] [--mean 20] [--sd 8] [--max 77] [--pairs 3] [--calls 10] [--attn16]
+       [--json out.json]
 """
 import argparse
 import json
@@ -49,6 +51,8 @@ def main(argv=None):
     ap.add_argument("--calls", type=int, default=10, help="get_text_features calls per timed window")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precisions", nargs="+", default=["fp32", "bf16", "fp16"], choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--attn16", action="store_true",
+                    help="bf16 / fp16: add the leg `packed + 16-bit core` (HipCLIPModel.packed_attention16), alternating with the others")
     ap.add_argument("--json", default=None)
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "a measurement needs the GPU"
@@ -70,28 +74,41 @@ def main(argv=None):
         result[name] = {"Tmax": ids.shape[1], "mean_len": float(lens.float().mean()), "max_len": t["max_S"], "Tp": t["Tp"],
                         "fill": fill}
         for prec in args.precisions:
-            def call(packed: bool, n: int = 1):
+            def call(packed: bool, n: int = 1, attn16: bool = False):
+                clip.packed_attention16 = attn16
                 with torch.no_grad():
                     for _ in range(n):
                         out = clip.get_text_features(input_ids=idd, precision=prec, packed_lens=lens if packed else None)
                 torch.cuda.synchronize()
                 return out
 
-            want, got = call(False), call(True)                          # warm-up of both (weight copies, plan, code objects)
+            # --attn16 (16-bit precisions): a third leg, the packed tower with the 16-bit packed attention core
+            legs = [("padded", False, False), ("packed", True, False)]
+            if args.attn16 and prec != "fp32":
+                legs.append(("packed16", True, True))
+            outs = {which: call(packed, 1, a16) for which, packed, a16 in legs}     # warm-up of each (weight copies, plan, code objects)
+            want, got = outs["padded"], outs["packed"]
             diff = float((got - want).abs().max() / want.abs().max())
-            ms = {"padded": [], "packed": []}
+            ms = {which: [] for which, _, _ in legs}
             for pair in range(args.pairs):
-                for which, packed in (("padded", False), ("packed", True)):
+                for which, packed, a16 in legs:
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    call(packed, args.calls)
+                    call(packed, args.calls, a16)
                     ms[which].append(1e3 * (time.perf_counter() - t0) / args.calls)
-                print(f"[{name} {prec}] pair {pair}: padded {ms['padded'][-1]:.3f} ms, packed {ms['packed'][-1]:.3f} ms")
+                print(f"[{name} {prec}] pair {pair}: " + ", ".join(f"{which} {ms[which][-1]:.3f} ms" for which in ms))
             med = {k: statistics.median(v) for k, v in ms.items()}
             print(f"[{name} {prec}] ms per call, median of {args.pairs}: padded {med['padded']:.3f} (min {min(ms['padded']):.3f}, max "
                   f"{max(ms['padded']):.3f}), packed {med['packed']:.3f} (min {min(ms['packed']):.3f}, max {max(ms['packed']):.3f}); "
                   f"padded / packed {med['padded'] / med['packed']:.2f}; largest relative difference of the outputs {diff:.3e}")
             result[name][prec] = {"ms": ms, "median_ms": med, "max_rel_diff": diff}
+            if "packed16" in ms:
+                d16 = float((outs["packed16"] - want).abs().max() / want.abs().max())
+                print(f"[{name} {prec}] packed + 16-bit core {med['packed16']:.3f} (min {min(ms['packed16']):.3f}, max "
+                      f"{max(ms['packed16']):.3f}); packed / packed16 {med['packed'] / med['packed16']:.2f}, padded / packed16 "
+                      f"{med['padded'] / med['packed16']:.2f}; largest relative difference to the padded output {d16:.3e}")
+                result[name][prec]["max_rel_diff_packed16"] = d16
+            clip.packed_attention16 = None
     print(json.dumps(result))
     if args.json:
         with open(args.json, "w") as f:
