@@ -23,6 +23,7 @@ SIGNATURES = {
     "dclip_abi_version": (I, []),
     "dclip_last_error": (C.c_char_p, []),
     "dclip_last_launch": (C.c_char_p, []),
+    "dclip_first_launch": (C.c_char_p, []),
     "dclip_gemm_f32_workspace": (Z, [I, I, I, I, I]),
     "dclip_gemm_f32_plan": (I, [I, I, I, I, I, C.POINTER(C.c_int)]),
     "dclip_gemm_f32": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, I, P, Z, P]),

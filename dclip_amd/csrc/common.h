@@ -16,6 +16,9 @@ void dclip_set_error(const char* fmt, ...);
 void dclip_note_launch(const char* name);   // what dclip_last_launch() returns; `name` is a string literal
 // a kernel-variant suffix (string literal, ".r64", ".head3", ...) appended to the name the last dclip_note_launch recorded
 void dclip_note_variant(const char* variant);
+// an entry of several launches whose FIRST launch has instances of its own records that one here (two string literals):
+// dclip_first_launch() returns it after the later launches have overwritten dclip_last_launch()
+void dclip_note_first_launch(const char* name, const char* variant);
 
 #define DCLIP_REQUIRE(cond, ...)                         \
   do {                                                   \

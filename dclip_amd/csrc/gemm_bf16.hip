@@ -83,6 +83,7 @@ __device__ __forceinline__ void store_split4(unsigned short* c, int N, f32x4 v, 
     float x = v[e];
     asm volatile("" : "+v"(x));
     x *= s;
+    asm volatile("" : "+v"(x));   // and the product: converted twice (once as fp16(fma(x, s, +0))), a result of -0 gave lo = -0 (split16.hip, split1)
     const _Float16 h = (_Float16)x;
     const _Float16 l = (_Float16)(x - (float)h);
     hi[e] = __builtin_bit_cast(unsigned short, h);

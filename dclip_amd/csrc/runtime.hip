@@ -5,6 +5,9 @@ static thread_local char g_err[512] = "";
 static thread_local const char* g_last_launch = "";
 static thread_local const char* g_last_variant = "";
 static thread_local char g_last_launch_full[96] = "";
+static thread_local const char* g_first_launch = "";
+static thread_local const char* g_first_variant = "";
+static thread_local char g_first_launch_full[96] = "";
 
 void dclip_set_error(const char* fmt, ...) {
   va_list ap;
@@ -26,6 +29,15 @@ DCLIP_API const char* dclip_last_launch(void) {
   if (!g_last_variant[0]) return g_last_launch;
   snprintf(g_last_launch_full, sizeof(g_last_launch_full), "%s%s", g_last_launch, g_last_variant);
   return g_last_launch_full;
+}
+
+void dclip_note_first_launch(const char* name, const char* variant) {
+  g_first_launch = name;
+  g_first_variant = variant;
+}
+DCLIP_API const char* dclip_first_launch(void) {
+  snprintf(g_first_launch_full, sizeof(g_first_launch_full), "%s%s", g_first_launch, g_first_variant);
+  return g_first_launch_full;
 }
 
 namespace {

@@ -20,7 +20,11 @@ typedef int i32x4s __attribute__((ext_vector_type(4)));
 
 // hi = fp16(v), lo = fp16(v - hi).  v - float(hi) is exact in fp32 (hi is v to 11 bits), so each piece has ONE rounding
 // whether or not the compiler folds the subtraction into the conversion.
+// v (the caller's x * scale) is pinned in a register first.  Left to itself the compiler converts the product twice: the hi it
+// stores from the product, the hi it subtracts as fp16(fma(x, scale, +0)) — which is +0 for a product of -0 — and lo came out
+// as -0 - (+0) = -0 where IEEE (and every other instance of this function) gives -0 - (-0) = +0.
 __device__ __forceinline__ void split1(float v, unsigned short& hi, unsigned short& lo) {
+  asm volatile("" : "+v"(v));
   const _Float16 h = (_Float16)v;
   const _Float16 l = (_Float16)(v - (float)h);
   hi = __builtin_bit_cast(unsigned short, h);
@@ -678,6 +682,7 @@ int split_rows_colstats_launch(const float* x, void* y, float* row_alpha, unsign
   else SPLITROWSC(0);
 #undef SPLITROWSC
   DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_colstats", variant);
+  dclip_note_first_launch("split_f32_f16x3_rows_colstats", variant);   // .finish and .cols overwrite the name above
   return DCLIP_OK;
 }
 
@@ -756,6 +761,7 @@ DCLIP_API size_t dclip_split_f32_f16x3_rows_colstats_workspace(int rows, int col
 DCLIP_API int dclip_split_f32_f16x3_rows_colstats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
                                                   float* db, int rows, int cols, int ldx, void* workspace, size_t workspace_bytes,
                                                   void* stream) {
+  dclip_note_first_launch("", "");                     // a refused call leaves no earlier call's instance standing
   DCLIP_REQUIRE(x && y && row_alpha && yc && col_exp && col_alpha && rows > 0 && cols > 0, "split_f32_f16x3_rows_colstats: bad arguments");
   DCLIP_REQUIRE(cols % 8 == 0, "split_f32_f16x3_rows_colstats: cols=%d must be a multiple of 8", cols);
   DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "split_f32_f16x3_rows_colstats: ldx must be a multiple of 4 and >= cols");

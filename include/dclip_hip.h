@@ -56,6 +56,11 @@ const char* dclip_last_error(void);
  * 1024); the partial-sum reduce that follows a backward keeps that name.  "im2col" + ".vec" (patch % 4 == 0 and both
  * pointers 16-byte aligned) or ".scalar".  The pointer stays valid until the thread's next call of this function. */
 const char* dclip_last_launch(void);
+/* The FIRST launch of the calling thread's most recent entry that makes several launches and whose first one has template
+ * instances of its own: dclip_split_f32_f16x3_rows_colstats leaves "split_f32_f16x3_rows_colstats" + ".regs.nc1" .. ".regs.nc6"
+ * / ".cached" here, while dclip_last_launch() reports its ".cols".  "" before the first such call and after a refused one (the
+ * entry clears it first); same lifetime. */
+const char* dclip_first_launch(void);
 
 /* ------------------------------------------------------------------------------------------
  * GEMM  C[M,N] = epilogue( sum_k A(m,k) * B(k,n) )           (fp32 MFMA, LDS-tiled)

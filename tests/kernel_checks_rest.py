@@ -261,24 +261,32 @@ def emulate_ln_fwd(s, fault=None):
         s.rstd.payload.copy_(rs[None])
 
 
-def verify_ln_fwd(s, what=None):
-    """y: |g| rstd (e_mu + |d| (rho_rs + 3u)) + u |want|, with L = ceil(D / 256) + 8 the depth of a row sum,
+def ln_fwd_bounds(x, g, b, D: int):
+    """fp64 LayerNorm of x (want, mean, rstd) and the per-element bounds of an fp32 evaluation by one wave per row:
+    y: |g| rstd (e_mu + |d| (rho_rs + 3u)) + u |want|, with L = ceil(D / 256) + 8 the depth of a row sum,
     e_mu = gamma(L + 1) mean|x| the error of the mean, rho_v = gamma(L + 5) + e_mu^2 / var the relative error of the variance
     (a shift e of the mean changes sum (d - e)^2 only by D e^2, because sum d = 0) and rho_rs = rho_v / 2 + 2 ulp that of rsqrtf."""
-    c = s.case
-    rep = Report(what or f"layernorm_fwd {c}")
-    rep.guards(y=s.y, mean=s.mean, rstd=s.rstd)
-    x, g, b = s.x.double(), s.g.double(), s.b.double()
+    x, g, b = x.double(), g.double(), b.double()
     mu = x.mean(1)
     d = x - mu[:, None]
     var = (d * d).mean(1)
     rstd = 1.0 / torch.sqrt(var + LN_EPS)
     want = d * rstd[:, None] * g + b
-    L = -(-c.D // 256) + 8
+    L = -(-D // 256) + 8
     e_mu = gamma(L + 1) * x.abs().mean(1)
     rho_v = gamma(L + 5) + e_mu ** 2 / (var + LN_EPS)
     rho_rs = 0.5 * rho_v / (1.0 - rho_v) + 2 * ULP
     bnd = g.abs() * rstd[:, None] * (e_mu[:, None] + d.abs() * (rho_rs[:, None] + 3 * U)) + U * want.abs() + F32_TINY
+    return SimpleNamespace(want=want, bnd=bnd, mu=mu, rstd=rstd, e_mu=e_mu, rho_rs=rho_rs)
+
+
+def verify_ln_fwd(s, what=None):
+    """y, mean and rstd under the bounds of ln_fwd_bounds."""
+    c = s.case
+    rep = Report(what or f"layernorm_fwd {c}")
+    rep.guards(y=s.y, mean=s.mean, rstd=s.rstd)
+    r = ln_fwd_bounds(s.x, s.g, s.b, c.D)
+    want, bnd, mu, rstd, e_mu, rho_rs = r.want, r.bnd, r.mu, r.rstd, r.e_mu, r.rho_rs
     rep.bound("y", s.y.get(), want, bnd)
     if c.stats:
         rep.bound("mean", s.mean.get()[0], mu, e_mu + U * mu.abs() + F32_TINY)
