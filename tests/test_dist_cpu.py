@@ -12,6 +12,16 @@ import torch.multiprocessing as mp
 from oracle import dclip_oracle as O
 
 
+@pytest.fixture(autouse=True)
+def _real_ops_back():
+    """The tests below put tests/cpu_ops_shim.py into functional.ops; a GPU test that follows in the same process must find
+    the kernels there again (the shim's host index tensors are refused inside a HIP-graph capture)."""
+    from dclip_amd import functional
+    saved = functional.ops
+    yield
+    functional.ops = saved
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

@@ -140,6 +140,16 @@ def _worker(rank, world, port, ckpt_dir, out):
 import pytest
 
 
+@pytest.fixture(autouse=True)
+def _real_ops_back():
+    """The tests below put tests/cpu_ops_shim.py into functional.ops; a GPU test that follows in the same process must find
+    the kernels there again (the shim's host index tensors are refused inside a HIP-graph capture)."""
+    from dclip_amd import functional
+    saved = functional.ops
+    yield
+    functional.ops = saved
+
+
 @pytest.mark.parametrize("world", [2, 3])
 def test_n_rank_fit_equals_single_process_fit_on_concatenated_batches(tmp_path, world):
     from dclip_amd.lightning_lite import Trainer
