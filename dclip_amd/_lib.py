@@ -148,6 +148,13 @@ SIGNATURES = {
     "dclip_gemm_f16_scaled_rows_dev": (I, [P, P, P, P, I, I, I, I, I, I, I, P, P, P]),
     "dclip_split_f32_f16x3_rows_colstats_workspace": (Z, [I, I]),
     "dclip_split_f32_f16x3_rows_colstats": (I, [P, P, P, P, P, P, P, I, I, I, P, Z, P]),
+    "dclip_split_f32_f16x3_rows_cols_stats": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "dclip_gemm_f16_scaled_rows_stats_plan": (I, [I, I, I]),
+    "dclip_gemm_f16_scaled_rows_stats_dev": (I, [P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),
+    "dclip_attention_bwd_stats_plan": (I, [I, I, I]),
+    "dclip_attention_bwd_stats": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
+    "dclip_layernorm_bwd_stats_plan": (I, [I, I]),
+    "dclip_layernorm_bwd_stats": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, Z, P]),
     "dclip_gemm_f16_wgrad_tokmajor_seg3_plan": (I, [I, I, I]),
     "dclip_gemm_f16_wgrad_tokmajor_seg3": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, Z, P]),
     "dclip_gemm_f16_ex": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),

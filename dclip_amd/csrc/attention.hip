@@ -637,11 +637,17 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnArgs a, const flo
 //   phase B  the K tile is staged over the (now dead) Q tile; wave w owns QUERIES 16w..16w+15 and forms
 //            dQ^T = K^T dS^T with dS^T read as 16-byte runs of its own rows of the dS tile.
 // IO16: q / k / v, `out`, `dout` and dq / dk / dv are bf16 (see the bf16 I/O note above); lse fp32.
-template <bool CAUSAL, bool IO16 = false>
-__global__ void __launch_bounds__(256, 3) attn_bwd_lean_kernel(AttnArgs a, const float* __restrict__ out,
-                                                               const float* __restrict__ dout, const float* __restrict__ lse,
-                                                               float* __restrict__ dq_out, float* __restrict__ dk_out,
-                                                               float* __restrict__ dv_out, int ldd) {
+// STATS (attn_bwd_lean_stats_kernel, fp32, packed dqkv with ldd = 3 D): dqkv is the dY of the qkv projection, so the
+// workgroup also leaves the column statistics of the 192 columns it stored — dq, dk, dv of its head — in partial row b of
+// pmax / psum [B][3 D] (colstats_finish_kernel's layout).  After phase B all three LDS tiles are dead: the stored values are
+// staged there as [matrix][token][64] (16-byte granule g of token t at g ^ (t & 15)), and thread c < 192 folds column c over
+// tokens 0 .. S-1 in order — maximum of the bit patterns of |x|, fp32 sum; the same bits in every run.
+template <bool CAUSAL, bool IO16, bool STATS>
+__device__ __forceinline__ void attn_bwd_lean_body(const AttnArgs& a, const float* __restrict__ out, const float* __restrict__ dout,
+                                                   const float* __restrict__ lse, float* __restrict__ dq_out,
+                                                   float* __restrict__ dk_out, float* __restrict__ dv_out, int ldd,
+                                                   unsigned* __restrict__ pmax, float* __restrict__ psum) {
+  static_assert(!STATS || !IO16, "the statistics form is fp32");
   __shared__ __attribute__((aligned(16))) float lds[3 * TS * HD + 2 * TS];
   float* Qs = lds;                 // phase B: the K tile
   float* dOs = lds + TS * HD;
@@ -723,6 +729,7 @@ __global__ void __launch_bounds__(256, 3) attn_bwd_lean_kernel(AttnArgs a, const
   }
   __syncthreads();
   const int kts = (S + 15) / 16;
+  f32x4 sk[STATS ? 4 : 1], sv[STATS ? 4 : 1];          // STATS: the stored dK / dV rows, kept until the tiles are dead
   // ---- phase A: own keys, every query tile -> dK, dV, and the dS tile
   {
     f32x4 dk[4], dv[4];
@@ -777,6 +784,10 @@ __global__ void __launch_bounds__(256, 3) attn_bwd_lean_kernel(AttnArgs a, const
         }
       }
     }
+    if constexpr (STATS) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) sk[dt] = dk[dt], sv[dt] = dv[dt];
+    }
   }
   __syncthreads();                                   // Q tile dead, dS tile complete
   if constexpr (IO16) tile_commit16(Qs, tk16, S);    // K over Q
@@ -812,7 +823,53 @@ __global__ void __launch_bounds__(256, 3) attn_bwd_lean_kernel(AttnArgs a, const
         for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(o + 16 * dt) = dq[dt];
       }
     }
+    if constexpr (STATS) {
+      __syncthreads();                                 // phase B's reads of the K and dS tiles are done
+      if (own < S) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const int o = tile_off(own, 16 * dt + 4 * qd);
+          *reinterpret_cast<f32x4*>(lds + o) = dq[dt];
+          *reinterpret_cast<f32x4*>(lds + TS * HD + o) = sk[dt];
+          *reinterpret_cast<f32x4*>(lds + 2 * TS * HD + o) = sv[dt];
+        }
+      }
+      __syncthreads();
+      const int c = threadIdx.x;
+      if (c < 3 * HD) {                                // (matrix, head column): tokens 0 .. S-1 in order; rows >= S were not staged
+        const int mt = c >> 6, cc = c & 63;
+        const float* t = lds + mt * TS * HD;
+        unsigned m = 0u;
+        float s = 0.f;
+        for (int r = 0; r < S; ++r) {
+          const float v = t[tile_off(r, cc)];
+          const unsigned u = __builtin_bit_cast(unsigned, v) & 0x7fffffffu;
+          m = m > u ? m : u;
+          s += v;
+        }
+        const size_t o = (size_t)b * 3 * D + (size_t)mt * D + h * HD + cc;
+        pmax[o] = m;
+        psum[o] = s;
+      }
+    }
   }
+}
+
+template <bool CAUSAL, bool IO16 = false>
+__global__ void __launch_bounds__(256, 3) attn_bwd_lean_kernel(AttnArgs a, const float* __restrict__ out,
+                                                               const float* __restrict__ dout, const float* __restrict__ lse,
+                                                               float* __restrict__ dq_out, float* __restrict__ dk_out,
+                                                               float* __restrict__ dv_out, int ldd) {
+  attn_bwd_lean_body<CAUSAL, IO16, false>(a, out, dout, lse, dq_out, dk_out, dv_out, ldd, nullptr, nullptr);
+}
+
+template <bool CAUSAL>
+__global__ void __launch_bounds__(256, 3) attn_bwd_lean_stats_kernel(AttnArgs a, const float* __restrict__ out,
+                                                                     const float* __restrict__ dout, const float* __restrict__ lse,
+                                                                     float* __restrict__ dq_out, float* __restrict__ dk_out,
+                                                                     float* __restrict__ dv_out, int ldd,
+                                                                     unsigned* __restrict__ pmax, float* __restrict__ psum) {
+  attn_bwd_lean_body<CAUSAL, false, true>(a, out, dout, lse, dq_out, dk_out, dv_out, ldd, pmax, psum);
 }
 
 // ------------------------------------------------------------------------------------------- backward, streamed
@@ -1442,6 +1499,30 @@ DCLIP_API int dclip_attention_bwd(const float* qkv, const float* out, const floa
   const int D = H * HD;
   AttnArgs a{qkv, qkv + D, qkv + 2 * D, 3 * D, 3 * D, S, S, H, nullptr};
   return launch_bwd(a, out, dout, lse, dqkv, 3 * D, dqkv + D, dqkv + 2 * D, 3 * D, delta, B, causal, (hipStream_t)stream);
+}
+
+// dclip_attention_bwd that also leaves the column statistics of the dqkv it stores, for the single-pass split of
+// dqkv as the qkv projection's dY: pmax / psum [P][3 D], P = dclip_attention_bwd_stats_plan(B, S, H) = B partial rows (one per
+// image), every word written; dqkv is bit-equal to dclip_attention_bwd's.  The one-tile kernel only: _plan returns 0 for S == 1
+// and S > 64, and the caller then takes dclip_attention_bwd.
+DCLIP_API int dclip_attention_bwd_stats_plan(int B, int S, int H) { return B > 0 && H > 0 && S > 1 && S <= TS ? B : 0; }
+
+DCLIP_API int dclip_attention_bwd_stats(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                                        void* pmax, float* psum, int B, int S, int H, int causal, void* stream) {
+  DCLIP_REQUIRE(qkv && out && dout && lse && dqkv && pmax && psum, "attention_bwd_stats: null pointer");
+  DCLIP_REQUIRE(dclip_attention_bwd_stats_plan(B, S, H) > 0, "attention_bwd_stats: no such form for B=%d S=%d H=%d", B, S, H);
+  DCLIP_REQUIRE(((uintptr_t)pmax | (uintptr_t)psum) % 4 == 0, "attention_bwd_stats: alignment");
+  const int D = H * HD;
+  AttnArgs a{qkv, qkv + D, qkv + 2 * D, 3 * D, 3 * D, S, S, H, nullptr};
+  hipStream_t st = (hipStream_t)stream;
+  if (causal)
+    hipLaunchKernelGGL((attn_bwd_lean_stats_kernel<true>), dim3(B * H), dim3(256), 0, st, a, out, dout, lse, dqkv, dqkv + D,
+                       dqkv + 2 * D, 3 * D, (unsigned*)pmax, psum);
+  else
+    hipLaunchKernelGGL((attn_bwd_lean_stats_kernel<false>), dim3(B * H), dim3(256), 0, st, a, out, dout, lse, dqkv, dqkv + D,
+                       dqkv + 2 * D, 3 * D, (unsigned*)pmax, psum);
+  DCLIP_CHECK_LAUNCH("attention_bwd.lean.stats");
+  return DCLIP_OK;
 }
 
 // Workspace form: `workspace` holds delta [B*H*S] and, for long non-causal sequences (S > 80: ViT-B/16's 197 tokens,

@@ -56,6 +56,10 @@ struct GemmBf16Params {
   // COLUMNS into A / W
   int seg_splits = 0;
   int a_seg[3] = {0, 0, 0}, w_seg[3] = {0, 0, 0};
+  // statistics form of the row-scaled GEMM (dclip_gemm_f16_scaled_rows_stats_dev; the STATS kernel instance only):
+  // partial row tile_m of pmax / psum [tiles_m][N] receives the column statistics of the C values the tile stored
+  unsigned* pmax = nullptr;
+  float* psum = nullptr;
 };
 
 // The ROWS epilogue of the register-staged kernel: v = acc * alpha for 4 columns of row `row`; x row_alpha, then
@@ -375,7 +379,11 @@ int launch_reg(const GemmBf16Params& p, size_t lds, hipStream_t st) {
 // side outputs h32 / g32 are written; a kernel instance of its own, so that the code of every other caller is what it was.
 // ROWS (dclip_gemm_f16_scaled_rows_dev; KIND 0 or 2, fp32 output, DEV): the kernel has already multiplied the accumulators by
 // alpha and row_alpha (see there); KIND 2's side operand is the fp32 h (p.aux32) — gemm_f32_kernel's EPI_DGELU statement.
-template <class T, int KIND, bool OUT16, bool DEV = false, bool ROWS = false>
+// STATS (ROWS only): C is the dY of a weight gradient, so the tile also leaves the column statistics of what it
+// stored.  A thread owns 4 columns and walks 32 rows of the tile: 4 maxima of the bit patterns of |v| and 4 fp32 sums in row
+// order; after the last pass the 8 waves put them into the dead LDS and threads 0..255 fold them in wave order into partial
+// row m0 / 256 of p.pmax / p.psum.  Rows >= M and columns >= N contribute nothing and write nothing.
+template <class T, int KIND, bool OUT16, bool DEV = false, bool ROWS = false, bool STATS = false>
 __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4 (&acc)[8][4], float* ct, int m0, int n0,
                                             int tid, int wr, int wc, int quad, int l15) {
   constexpr int BN = 256;
@@ -385,6 +393,13 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
   f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
   if (p.epilogue & DCLIP_EPI_BIAS) bias4 = *reinterpret_cast<const f32x4*>(p.bias + colc);
   const float alpha_d = DEV ? *p.alpha_p : 0.f;        // the DEV instance is launched only with alpha_p set
+  static_assert(!STATS || ROWS, "the statistics form is the row-scaled one");
+  unsigned smx[STATS ? 4 : 1];
+  float ssm[STATS ? 4 : 1];
+  if constexpr (STATS) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) smx[e] = 0u, ssm[e] = 0.f;
+  }
 #pragma unroll
   for (int hm = 0; hm < 2; ++hm) {
     const int rbase = m0 + hm * 128 + lr0;
@@ -427,6 +442,15 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
           for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(side[q][e]);
         }
         if (ok) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + off) = v;
+        if constexpr (STATS) if (ok) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float ve = v[e];
+            const unsigned u = __builtin_bit_cast(unsigned, ve) & 0x7fffffffu;
+            smx[e] = smx[e] > u ? smx[e] : u;
+            ssm[e] += ve;
+          }
+        }
         continue;
       }
       if (KIND == 1) {
@@ -465,6 +489,29 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
     }
   }
   PP_STAMP(8);                 // second pass: stores issued
+  if constexpr (STATS) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // pass 1's LDS reads are done before the tile is overwritten
+    PP_BARRIER();
+    unsigned* cu = reinterpret_cast<unsigned*>(ct);         // [8 waves][256] maxima, then [8][256] sums
+    float* cs = ct + 8 * BN;
+    *reinterpret_cast<u32x4*>(cu + lr0 * BN + lc) = u32x4{smx[0], smx[1], smx[2], smx[3]};
+    *reinterpret_cast<f32x4*>(cs + lr0 * BN + lc) = f32x4{ssm[0], ssm[1], ssm[2], ssm[3]};
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    PP_BARRIER();
+    if (tid < BN && n0 + tid < p.N) {
+      unsigned m = cu[tid];
+      float sm = cs[tid];
+#pragma unroll
+      for (int w = 1; w < 8; ++w) {
+        const unsigned mw = cu[w * BN + tid];
+        m = m > mw ? m : mw;
+        sm += cs[w * BN + tid];
+      }
+      const size_t o = (size_t)(m0 / 256) * p.N + n0 + tid;
+      p.pmax[o] = m;
+      p.psum[o] = sm;
+    }
+  }
 #ifdef DCLIP_GEMM_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -570,9 +617,11 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 // no lgkmcnt before a barrier is needed: phase 1 issues 24 reads, more than the 4-bit counter can express).
 // SEG (token-major only): the contraction is three segments of K rows; the split index selects the segment, so a work item
 // stays inside one segment and the K loop, phases and barriers are what they were.  Always split-K (>= 3 slabs).
-template <class T, bool TOK, bool DEV = false, bool ROWS = false, bool SEG = false>
+// STATS (ROWS only): pp_epilogue's statistics form; nothing else differs.
+template <class T, bool TOK, bool DEV = false, bool ROWS = false, bool SEG = false, bool STATS = false>
 __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   static_assert(!SEG || (TOK && !DEV && !ROWS), "the segmented form is token-major, split-K, fp32 slabs");
+  static_assert(!STATS || (ROWS && !TOK), "the statistics form is the row-scaled dgrad");
   typedef typename T::x8 V8;
   constexpr int BM = 256, BN = 256, ROW = BKH;
   constexpr int BUF = (BM + BN) * ROW;   // bf16 elements per K-tile buffer: 256 A rows then 256 B rows of 128 bytes
@@ -813,8 +862,8 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = (acc[i][j] * alpha_r) * ra[i];
-    if (kind == 2) pp_epilogue<T, 2, false, true, true>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
-    else pp_epilogue<T, 0, false, true, true>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    if (kind == 2) pp_epilogue<T, 2, false, true, true, STATS>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else pp_epilogue<T, 0, false, true, true, STATS>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
     return;
   }
   if (!DEV && p.slab) {   // split-K partial: raw accumulators into this split's [M][N] slab, the reduce kernel finishes
@@ -1200,6 +1249,11 @@ int launch_pp(GemmBf16Params p, hipStream_t st, int splits = 1) {
   p.tiles_m = cdiv(p.M, 256);
   p.tiles_n = cdiv(p.N, 256);
   if constexpr (std::is_same<T, F16T>::value && !TOK) {   // the device-scaled entries exist for F16T only
+    if (p.row_alpha && p.pmax) {
+      hipLaunchKernelGGL((gemm_bf16_pp_kernel<T, false, true, true, false, true>), dim3(p.tiles_m * p.tiles_n, splits), dim3(512), 0,
+                         st, p);
+      return DCLIP_OK;
+    }
     if (p.row_alpha) {
       hipLaunchKernelGGL((gemm_bf16_pp_kernel<T, false, true, true>), dim3(p.tiles_m * p.tiles_n, splits), dim3(512), 0, st, p);
       return DCLIP_OK;
@@ -1341,11 +1395,17 @@ struct DevScales {
   float* g32;
   const float* row_alpha = nullptr;   // dclip_gemm_f16_scaled_rows_dev
   const float* aux32 = nullptr;
+  unsigned* pmax = nullptr;           // dclip_gemm_f16_scaled_rows_stats_dev
+  float* psum = nullptr;
 };
 inline void set_dev(GemmBf16Params& p, const DevScales* d) {
   if (d) p.alpha_p = d->alpha_p, p.out_scale_p = d->out_scale_p, p.h32 = d->h32, p.g32 = d->g32, p.row_alpha = d->row_alpha,
-         p.aux32 = d->aux32;
+         p.aux32 = d->aux32, p.pmax = d->pmax, p.psum = d->psum;
 }
+
+// the dispatcher's test for the ping-pong kernel (gemm16 below)
+inline int pp_big_min() { return getenv("DCLIP_BF16_BIG_MIN") ? atoi(getenv("DCLIP_BF16_BIG_MIN")) : 128; }
+inline bool takes_pp(int M, int N, int K) { return K % BKH == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= pp_big_min(); }
 
 // fp16 of the training path (F16IeeeT): the ping-pong and register-staged kernels only (no persistent instance)
 template <class T>
@@ -1376,8 +1436,7 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
   // Ping-pong kernel (K % 64 == 0, at least 128 workgroups): measured faster than the register-staged 128x128 kernel on
   // every tower shape, short K included (tools/bf16_gemm_bench.py).  With fp32 outputs and K = 768 it is bound by writing C
   // (944 MB for the qkv projection of 2048 crops): one workgroup per CU cannot overlap that with the next tile's MFMAs.
-  const int big_min = getenv("DCLIP_BF16_BIG_MIN") ? atoi(getenv("DCLIP_BF16_BIG_MIN")) : 128;   // tuning aid (read per call)
-  if (K % BKH == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= big_min) {
+  if (takes_pp(M, N, K)) {   // (DCLIP_BF16_BIG_MIN, default 128: a tuning aid, read per call)
     GemmBf16Params pb{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_bf16, 0, 0,
                       (unsigned short*)aux, 0, nullptr, alpha, out_scale};
     set_dev(pb, dev);
@@ -1497,6 +1556,34 @@ DCLIP_API int dclip_gemm_f16_scaled_rows_dev(const void* A, const void* W, float
   dev.aux32 = (epilogue & DCLIP_EPI_DGELU) ? aux32 : nullptr;
   return gemm16<F16T>("gemm_f16_scaled_rows_dev", A, W, C, nullptr, nullptr, nullptr, M, N, K, lda, ldw, ldc, epilogue, 0, stream, 1.f,
                       0.f, &dev);
+}
+
+// dclip_gemm_f16_scaled_rows_dev that also leaves the column statistics of the C it stores, for the single-pass
+// split of C as the next weight gradient's dY: pmax / psum [P][N], P = dclip_gemm_f16_scaled_rows_stats_plan(M, N, K) = ceil(M /
+// 256) partial rows (one per tile row), every word written; C is bit-equal to dclip_gemm_f16_scaled_rows_dev's.  The ping-pong
+// kernel only: _plan returns 0 where the dispatcher takes a register-staged kernel, and the caller then takes the plain entry.
+DCLIP_API int dclip_gemm_f16_scaled_rows_stats_plan(int M, int N, int K) {
+  return M > 0 && N > 0 && K > 0 && takes_pp(M, N, K) ? cdiv(M, 256) : 0;
+}
+
+DCLIP_API int dclip_gemm_f16_scaled_rows_stats_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K,
+                                                   int lda, int ldw, int ldc, int epilogue, const float* alpha, const float* row_alpha,
+                                                   void* pmax, float* psum, void* stream) {
+  DCLIP_REQUIRE(alpha && row_alpha && ((uintptr_t)alpha | (uintptr_t)row_alpha) % 4 == 0,
+                "gemm_f16_scaled_rows_stats_dev: alpha / row_alpha must be device pointers");
+  DCLIP_REQUIRE(pmax && psum && ((uintptr_t)pmax | (uintptr_t)psum) % 4 == 0, "gemm_f16_scaled_rows_stats_dev: pmax / psum");
+  DCLIP_REQUIRE(epilogue == 0 || epilogue == DCLIP_EPI_DGELU, "gemm_f16_scaled_rows_stats_dev: the epilogue is none or DGELU");
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (aux32 && (uintptr_t)aux32 % 16 == 0),
+                "gemm_f16_scaled_rows_stats_dev: DGELU needs a 16-byte aligned fp32 aux32");
+  DCLIP_REQUIRE(dclip_gemm_f16_scaled_rows_stats_plan(M, N, K) > 0,
+                "gemm_f16_scaled_rows_stats_dev: M=%d N=%d K=%d takes a register-staged kernel, which has no statistics form", M, N, K);
+  DevScales dev{alpha, nullptr, nullptr, nullptr};
+  dev.row_alpha = row_alpha;
+  dev.aux32 = (epilogue & DCLIP_EPI_DGELU) ? aux32 : nullptr;
+  dev.pmax = (unsigned*)pmax;
+  dev.psum = psum;
+  return gemm16<F16T>("gemm_f16_scaled_rows_dev.stats", A, W, C, nullptr, nullptr, nullptr, M, N, K, lda, ldw, ldc, epilogue, 0, stream,
+                      1.f, 0.f, &dev);
 }
 
 // fp16 TRAINING path: dclip_gemm_bf16_ex's arguments, epilogues and limits with fp16 A / W / aux / 16-bit C, IEEE rounding

@@ -58,6 +58,138 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
   }
 }
 
+// ln_bwd_kernel's body (below) again for ln_bwd_stats_kernel — a copy, so that ln_bwd_kernel's instances compile to what they
+// were; STATS is always true here.  DESIGN.md §9g: dx is the dY of the Linear before this LayerNorm, so the block also leaves the
+// column statistics of the dx it stored — pmax[blockIdx][D], the maximum of the bit patterns of |dx|, and psum[blockIdx][D],
+// the column sums (what NS == 3 carries) — in the layout colstats_finish_kernel reads.  LDS is [4][4][D] then; `partial`
+// (may be null: no parameter gradients wanted) keeps the NS == 2 layout.  dx, dgamma and dbeta are what they are without.
+template <class T, int NC, bool EXACT, bool STATS>
+__device__ __forceinline__ void ln_bwd_body(const float* __restrict__ dy, const float* __restrict__ x,
+                                            const float* __restrict__ gamma, const float* __restrict__ mean,
+                                            const float* __restrict__ rstd, const float* __restrict__ dres,
+                                            float* __restrict__ dx, float* __restrict__ partial, int rows, int D,
+                                            unsigned short* __restrict__ dx16, int NS, unsigned* __restrict__ pmax,
+                                            float* __restrict__ psum) {
+  extern __shared__ __attribute__((aligned(16))) float red[];  // [4][NS][D]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int d4 = D >> 2;
+  f32x4 g[NC], dg[NC], db[NC], dsum[NC];
+  unsigned dmx[STATS ? NC : 1][4];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    int i = lane + 64 * c;
+    g[c] = (EXACT || i < d4) ? reinterpret_cast<const f32x4*>(gamma)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    dg[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    db[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    dsum[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (STATS) dmx[c][0] = dmx[c][1] = dmx[c][2] = dmx[c][3] = 0u;
+  }
+  const float invD = 1.0f / (float)D;
+  const bool has_res = dres != nullptr;                       // wave-uniform
+  for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
+    const f32x4* xr = reinterpret_cast<const f32x4*>(x + (size_t)row * D);
+    const f32x4* dyr = reinterpret_cast<const f32x4*>(dy + (size_t)row * D);
+    const f32x4* rr = reinterpret_cast<const f32x4*>((has_res ? dres : dy) + (size_t)row * D);   // (a valid address either way)
+    const float mu = mean[row], rs = rstd[row];
+    f32x4 xh[NC], dyh[NC], rv[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = lane + 64 * c, ic = (EXACT || i < d4) ? i : 0;
+      dyh[c] = dyr[ic];
+      xh[c] = xr[ic];
+      rv[c] = rr[ic];
+    }
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      if (EXACT || lane + 64 * c < d4) {
+        const f32x4 dyv = dyh[c];
+        xh[c] = (xh[c] - mu) * rs;
+        dg[c] += dyv * xh[c];
+        db[c] += dyv;
+        dyh[c] = dyv * g[c];
+        f32x4 t = dyh[c] * xh[c];
+        s1 += (t[0] + t[1]) + (t[2] + t[3]);
+        s2 += (dyh[c][0] + dyh[c][1]) + (dyh[c][2] + dyh[c][3]);
+      } else {
+        xh[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        dyh[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    const float c1 = wave_sum(s1) * invD, c2 = wave_sum(s2) * invD;
+    f32x4* dxr = reinterpret_cast<f32x4*>(dx + (size_t)row * D);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = lane + 64 * c;
+      if (EXACT || i < d4) {
+        f32x4 o = (dyh[c] - c2 - xh[c] * c1) * rs;
+        if (has_res) o += rv[c];
+        dxr[i] = o;
+        if (NS == 3) dsum[c] += o;
+        if constexpr (STATS) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float oe = o[e];
+            const unsigned u = __builtin_bit_cast(unsigned, oe) & 0x7fffffffu;
+            dmx[c][e] = dmx[c][e] > u ? dmx[c][e] : u;
+          }
+        }
+        if (dx16) {
+          typedef unsigned short u16x4_t __attribute__((ext_vector_type(4)));
+          u16x4_t b;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) b[e] = T::bits(o[e]);
+          *reinterpret_cast<u16x4_t*>(dx16 + (size_t)row * D + i * 4) = b;
+        }
+      }
+    }
+  }
+  if constexpr (STATS) {
+    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      int i = lane + 64 * c;
+      if (EXACT || i < d4) {
+        reinterpret_cast<f32x4*>(red + (wave * 4 + 0) * D)[i] = dg[c];
+        reinterpret_cast<f32x4*>(red + (wave * 4 + 1) * D)[i] = db[c];
+        reinterpret_cast<f32x4*>(red + (wave * 4 + 2) * D)[i] = dsum[c];
+        reinterpret_cast<u32x4_t*>(red + (wave * 4 + 3) * D)[i] = u32x4_t{dmx[c][0], dmx[c][1], dmx[c][2], dmx[c][3]};
+      }
+    }
+    __syncthreads();
+    const int W = 4 * D;
+    for (int i = threadIdx.x; i < W; i += 256) {
+      if (i < 3 * D) {                                   // the association of the plain kernel's fold
+        float s = red[i] + red[W + i] + red[2 * W + i] + red[3 * W + i];
+        if (i >= 2 * D) psum[(size_t)blockIdx.x * D + (i - 2 * D)] = s;
+        else if (partial) partial[(size_t)blockIdx.x * 2 * D + i] = s;
+      } else {
+        const unsigned* ru = reinterpret_cast<const unsigned*>(red);
+        const unsigned m01 = ru[i] > ru[W + i] ? ru[i] : ru[W + i], m23 = ru[2 * W + i] > ru[3 * W + i] ? ru[2 * W + i] : ru[3 * W + i];
+        pmax[(size_t)blockIdx.x * D + (i - 3 * D)] = m01 > m23 ? m01 : m23;
+      }
+    }
+    return;
+  }
+  if (partial) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      int i = lane + 64 * c;
+      if (EXACT || i < d4) {
+        reinterpret_cast<f32x4*>(red + (wave * NS + 0) * D)[i] = dg[c];
+        reinterpret_cast<f32x4*>(red + (wave * NS + 1) * D)[i] = db[c];
+        if (NS == 3) reinterpret_cast<f32x4*>(red + (wave * NS + 2) * D)[i] = dsum[c];
+      }
+    }
+    __syncthreads();
+    const int W = NS * D;
+    for (int i = threadIdx.x; i < W; i += 256) {
+      float s = red[i] + red[W + i] + red[2 * W + i] + red[3 * W + i];
+      partial[(size_t)blockIdx.x * W + i] = s;
+    }
+  }
+}
+
 // Each wave walks rows with a grid stride; per-column dgamma/dbeta partials stay in registers, are summed
 // over the block's 4 waves through LDS and written to partial[blockIdx][NS][D].
 // bf16 training path (NS == 3 / dx16): the same pass also leaves what the NEXT two launches of the backward would
@@ -151,6 +283,15 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ d
       partial[(size_t)blockIdx.x * W + i] = s;
     }
   }
+}
+
+template <class T, int NC, bool EXACT>
+__global__ void __launch_bounds__(256) ln_bwd_stats_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                           const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                           const float* __restrict__ rstd, const float* __restrict__ dres,
+                                                           float* __restrict__ dx, float* __restrict__ partial, int rows, int D,
+                                                           unsigned* __restrict__ pmax, float* __restrict__ psum) {
+  ln_bwd_body<T, NC, EXACT, true>(dy, x, gamma, mean, rstd, dres, dx, partial, rows, D, nullptr, 3, pmax, psum);
 }
 
 // out[n] (+)= sum_p partial[p][n]   (fixed order -> deterministic).  Block = 16 columns x 64 row groups: N/16
@@ -377,6 +518,57 @@ DCLIP_API int dclip_layernorm_bwd_ex_f16(const float* dy, const float* x, const 
                                          void* workspace, size_t workspace_bytes, void* stream) {
   return layernorm_bwd16<F16IeeeT>("layernorm_bwd_f16", dy, x, gamma, mean, rstd, dresidual, dx, dx_f16, dgamma, dbeta, dx_colsum,
                                    rows, D, accumulate_param_grads, workspace, workspace_bytes, stream);
+}
+
+// dclip_layernorm_bwd that also leaves the column statistics of the dx it stores, for the single-pass split of
+// dx as the next Linear's dY (dclip_split_f32_f16x3_rows_cols_stats): pmax / psum [P][D], P = dclip_layernorm_bwd_stats_plan(rows,
+// D) partial rows, every word written.  dx, dgamma and dbeta (both may be null) are bit-equal to dclip_layernorm_bwd's; psum's rows
+// are the partials its dx_colsum is folded from.  _plan returns 0 where the form does not exist (D > 1024: four chunks per lane
+// at most, 4 x 4 x D floats of LDS); the caller then takes dclip_layernorm_bwd.
+DCLIP_API int dclip_layernorm_bwd_stats_plan(int rows, int D) {
+  if (rows <= 0 || D <= 0 || D % 4 || D > 1024) return 0;
+  return ln_bwd_blocks(rows);
+}
+
+DCLIP_API int dclip_layernorm_bwd_stats(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                        const float* dresidual, float* dx, float* dgamma, float* dbeta, void* pmax, float* psum,
+                                        int rows, int D, int accumulate_param_grads, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+  DCLIP_REQUIRE(dy && x && gamma && mean && rstd && dx && pmax && psum, "layernorm_bwd_stats: null pointer");
+  DCLIP_REQUIRE(dclip_layernorm_bwd_stats_plan(rows, D) > 0, "layernorm_bwd_stats: no such form for rows=%d D=%d", rows, D);
+  DCLIP_REQUIRE(((uintptr_t)pmax | (uintptr_t)psum) % 4 == 0, "layernorm_bwd_stats: alignment");
+  const bool want_params = dgamma || dbeta;
+  const int blocks = ln_bwd_blocks(rows);
+  if (want_params && (!workspace || workspace_bytes < dclip_layernorm_bwd_workspace(rows, D))) {
+    dclip_set_error("layernorm_bwd_stats: workspace too small (%zu < %zu)", workspace_bytes, dclip_layernorm_bwd_workspace(rows, D));
+    return DCLIP_EWORKSPACE;
+  }
+  float* partial = want_params ? (float*)workspace : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = (size_t)4 * 4 * D * sizeof(float);      // <= 64 KiB at D <= 1024
+  const int nc = cdiv(D / 4, 64);
+  const char* variant;
+#define LN_BWDS(NC, EX)                                                                                                          \
+  do {                                                                                                                           \
+    hipLaunchKernelGGL((ln_bwd_stats_kernel<Bf16T, NC, EX>), dim3(blocks), dim3(256), lds, st, dy, x, gamma, mean, rstd, dresidual, \
+                       dx, partial, rows, D, (unsigned*)pmax, psum);                                                             \
+    variant = (EX) ? ".nc" #NC ".exact" : ".nc" #NC;                                                                             \
+  } while (0)
+  if (D == 512) LN_BWDS(2, true);
+  else if (D == 768) LN_BWDS(3, true);
+  else if (D == 1024) LN_BWDS(4, true);
+  else if (nc <= 1) LN_BWDS(1, false);
+  else if (nc == 2) LN_BWDS(2, false);
+  else if (nc == 3) LN_BWDS(3, false);
+  else LN_BWDS(4, false);
+#undef LN_BWDS
+  DCLIP_CHECK_LAUNCH_V("layernorm_bwd_stats", variant);
+  if (want_params) {
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(cdiv(2 * D, RP_COLS)), dim3(1024), 0, st, partial, dgamma, dbeta, blocks, D, D,
+                       accumulate_param_grads, (float*)nullptr, 0);
+    DCLIP_CHECK_LAUNCH_V("layernorm_bwd_stats", variant);
+  }
+  return DCLIP_OK;
 }
 
 DCLIP_API size_t dclip_colsum_f32_workspace(int M, int N) { return (size_t)colsum_splits(M) * N * sizeof(float); }

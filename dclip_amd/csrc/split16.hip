@@ -327,6 +327,87 @@ __global__ void __launch_bounds__(256) split_cols_f16x2_kernel(const float* __re
   }
 }
 
+// ---- the single pass: when the kernel that PRODUCED x left the column partials, the finish runs first and the
+// column exponents are known before x is read; one wave per row then writes both splits from the same registers —
+// split_rows_f16x3_kernel's row split, statement for statement, and split_cols_f16x2_kernel's statement for the same 8 columns.
+__device__ __forceinline__ void split_cols_store8(unsigned short* yr, int cols, const f32x4& a, const f32x4& b,
+                                                  const int* __restrict__ ce) {
+  const i32x4s ea = *reinterpret_cast<const i32x4s*>(ce), eb = *reinterpret_cast<const i32x4s*>(ce + 4);
+  u16x8 hi, lo;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    unsigned short h0, l0, h1, l1;
+    split1(a[e] * pow2f(ea[e]), h0, l0);
+    split1(b[e] * pow2f(eb[e]), h1, l1);
+    hi[e] = h0, lo[e] = l0, hi[4 + e] = h1, lo[4 + e] = l1;
+  }
+  *reinterpret_cast<u16x8*>(yr) = hi;
+  *reinterpret_cast<u16x8*>(yr + cols) = lo;
+}
+
+// split_store8 with non-temporal stores: the row split is read only by the data-gradient GEMM, which runs AFTER the weight
+// gradient has read yc, so it should not push yc out of the cache on its way to memory
+__device__ __forceinline__ void split_store8_nt(unsigned short* yr, int cols, const f32x4& a, const f32x4& b, float scale) {
+  u16x8 hi, lo;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    unsigned short h0, l0, h1, l1;
+    split1(a[e] * scale, h0, l0);
+    split1(b[e] * scale, h1, l1);
+    hi[e] = h0, lo[e] = l0, hi[4 + e] = h1, lo[4 + e] = l1;
+  }
+  __builtin_nontemporal_store(hi, reinterpret_cast<u16x8*>(yr));
+  __builtin_nontemporal_store(lo, reinterpret_cast<u16x8*>(yr + cols));
+  __builtin_nontemporal_store(hi, reinterpret_cast<u16x8*>(yr + 2 * cols));
+}
+
+template <int NC>
+__global__ void __launch_bounds__(256) split_rows_cols_f16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y,
+                                                                  float* __restrict__ row_alpha, const int* __restrict__ col_exp,
+                                                                  unsigned short* __restrict__ yc, int rows, int cols, int ldx) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int c8 = cols >> 3;
+  const float* xr = x + (size_t)row * ldx;
+  unsigned short* yr = y + (size_t)row * 3 * cols;
+  unsigned short* ycr = yc + (size_t)row * 2 * cols;
+  unsigned m = 0u;
+  if (NC > 0) {
+    f32x4 a[NC > 0 ? NC : 1], b[NC > 0 ? NC : 1];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = lane + 64 * c, ic = i < c8 ? i : 0;       // a chunk past the row re-reads chunk 0: same maximum
+      a[c] = *reinterpret_cast<const f32x4*>(xr + ic * 8);
+      b[c] = *reinterpret_cast<const f32x4*>(xr + ic * 8 + 4);
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) m = absmax8(m, a[c], b[c]);
+    const int e = row_exp(wave_umax_bits(m));
+    const float scale = pow2f(e);
+    if (lane == 0) row_alpha[row] = pow2f(-e);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = lane + 64 * c;
+      if (i < c8) {
+        split_store8_nt(yr + i * 8, cols, a[c], b[c], scale);
+        split_cols_store8(ycr + i * 8, cols, a[c], b[c], col_exp + i * 8);
+      }
+    }
+  } else {
+    for (int i = lane; i < c8; i += 64)
+      m = absmax8(m, *reinterpret_cast<const f32x4*>(xr + i * 8), *reinterpret_cast<const f32x4*>(xr + i * 8 + 4));
+    const int e = row_exp(wave_umax_bits(m));
+    const float scale = pow2f(e);
+    if (lane == 0) row_alpha[row] = pow2f(-e);
+    for (int i = lane; i < c8; i += 64) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(xr + i * 8), b = *reinterpret_cast<const f32x4*>(xr + i * 8 + 4);
+      split_store8_nt(yr + i * 8, cols, a, b, scale);
+      split_cols_store8(ycr + i * 8, cols, a, b, col_exp + i * 8);
+    }
+  }
+}
+
 // ln_fwd_kernel (layernorm.hip) with the split [hi | lo | hi] of scale * LN(x) as its output, y [rows][3 D] fp16.  Loads,
 // statistics and the normalisation are that kernel's, statement for statement; the fp32 result is pinned in a register before
 // it is scaled and split, so that it is the value ln_fwd_kernel would have stored (no fusion of the affine step into the
@@ -686,6 +767,30 @@ int split_rows_colstats_launch(const float* x, void* y, float* row_alpha, unsign
   return DCLIP_OK;
 }
 
+int split_rows_cols_launch(const float* x, void* y, float* row_alpha, const int* col_exp, void* yc, int rows, int cols, int ldx,
+                           void* stream) {
+  dim3 grid(cdiv(rows, 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned short *yy = (unsigned short*)y, *yyc = (unsigned short*)yc;
+  const int nc = cdiv(cols / 8, 64);
+  const char* variant;
+#define SPLITROWSCOLS(NC)                                                                                                          \
+  do {                                                                                                                             \
+    hipLaunchKernelGGL((split_rows_cols_f16_kernel<NC>), grid, block, 0, st, x, yy, row_alpha, col_exp, yyc, rows, cols, ldx);     \
+    variant = (NC) ? ".regs.nc" #NC : ".cached";                                                                                   \
+  } while (0)
+  if (nc <= 1) SPLITROWSCOLS(1);
+  else if (nc == 2) SPLITROWSCOLS(2);
+  else if (nc == 3) SPLITROWSCOLS(3);
+  else if (nc == 4) SPLITROWSCOLS(4);
+  else if (nc == 5) SPLITROWSCOLS(5);
+  else if (nc == 6) SPLITROWSCOLS(6);
+  else SPLITROWSCOLS(0);
+#undef SPLITROWSCOLS
+  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_cols_stats", variant);
+  return DCLIP_OK;
+}
+
 int ln_launch(const char* name, const float* x, const float* gamma, const float* beta, void* y, int rows, int D, float eps,
               float scale, const float* scale_p, float* y32, float* mean, float* rstd, void* stream) {
   dim3 grid(cdiv(rows, 4)), block(256);
@@ -787,6 +892,29 @@ DCLIP_API int dclip_split_f32_f16x3_rows_colstats(const float* x, void* y, float
                      (unsigned short*)yc, rows, cols, ldx);
   DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_colstats", ".cols");
   return DCLIP_OK;
+}
+
+// dclip_split_f32_f16x3_rows_colstats when the kernel that produced x has left the column partials: pmax [P][cols]
+// (bit patterns of |x| maxima) and psum [P][cols] (fp32 sums), every word written.  Two launches: the finish over the P partial
+// rows, then ONE pass over x that writes both splits.  y, row_alpha, col_exp, col_alpha and yc are bit-equal to the three-launch
+// entry's on the same x (a maximum does not depend on how the rows were grouped); db is another association of the same sum.
+DCLIP_API int dclip_split_f32_f16x3_rows_cols_stats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
+                                                    float* db, const void* pmax, const float* psum, int P, int rows, int cols, int ldx,
+                                                    void* stream) {
+  dclip_note_first_launch("", "");
+  DCLIP_REQUIRE(x && y && row_alpha && yc && col_exp && col_alpha && pmax && psum && P > 0 && rows > 0 && cols > 0,
+                "split_f32_f16x3_rows_cols_stats: bad arguments");
+  DCLIP_REQUIRE(cols % 8 == 0, "split_f32_f16x3_rows_cols_stats: cols=%d must be a multiple of 8", cols);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "split_f32_f16x3_rows_cols_stats: ldx must be a multiple of 4 and >= cols");
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)yc | (uintptr_t)col_exp) % 16 == 0 &&
+                    ((uintptr_t)row_alpha | (uintptr_t)col_alpha | (uintptr_t)db | (uintptr_t)pmax | (uintptr_t)psum) % 4 == 0,
+                "split_f32_f16x3_rows_cols_stats: alignment");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(colstats_finish_kernel, dim3(cdiv(cols, FIN_COLS)), dim3(256), 0, st, (const unsigned*)pmax, psum, col_exp, col_alpha,
+                     db, P, cols);
+  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_cols_stats", ".finish");
+  dclip_note_first_launch("split_f32_f16x3_rows_cols_stats", ".finish");
+  return split_rows_cols_launch(x, y, row_alpha, (const int*)col_exp, yc, rows, cols, ldx, stream);
 }
 
 DCLIP_API int dclip_layernorm_fwd_f16x3(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,

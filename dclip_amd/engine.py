@@ -130,13 +130,17 @@ def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Te
     `sp`, `act`, `x3` (the forward's [hi|lo|hi] split of x, made with the plan scale sp.act(act)): the split-fp16 weight
     gradient when the plan takes the shape — ONE pass over dy gives its row split (for _dgrad), its column
     statistics, db and its column-scaled [hi|lo] split; dW is the segmented token-major GEMM of that with x3.  Returns the row
-    pieces (dy3, row_alpha) for _dgrad then, None otherwise."""
+    pieces (dy3, row_alpha) for _dgrad then, None otherwise.  A dy that carries the column partials its producer left
+    (`dy.dystats`, _with_stats) is read ONCE: the finish over the partials, then one pass that writes both splits (§9g)."""
     dev = dy.device
-    if (need_w and sp is not None and x3 is not None and _VSPLIT16_WGRAD and dy.dim() == 2 and dy.stride(1) == 1 and
-            ops.gemm_f16_wgrad_tokmajor_seg3_plan(dy.shape[1], x.shape[1], dy.shape[0]) > 0):
+    if dy.dim() == 2 and dy.stride(1) == 1 and _split_wgrad_taken(need_w, sp, x3, dy.shape[1], x.shape[1], dy.shape[0]):
         M, N = dy.shape[1], x.shape[1]
         db = _galloc(alloc, bkey, (M,), dev) if need_b else None
-        dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=db)
+        st = getattr(dy, "dystats", None) if _VSPLIT16_DYSTATS else None
+        if st is not None:
+            dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_cols_stats(dy, st, db=db)
+        else:
+            dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=db)
         if need_b:
             gr[bkey] = db
         gr[wkey] = ops.gemm_f16_wgrad_tokmajor_seg3(yc, x3, M, N, col_alpha, sp.act(act), out=_galloc(alloc, wkey, (M, N), dev))
@@ -151,54 +155,96 @@ def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Te
     return None
 
 
-def _ln_bwd(dy, x, gamma, mean, rstd, dresidual, want: bool, gr, wkey: str, bkey: str, alloc):
-    """LayerNorm backward; dγ / dβ land where `alloc` says."""
+def _split_wgrad_taken(need_w: bool, sp: Optional[Split16Layer], x3, out_f: int, in_f: int, tokens: int) -> bool:
+    """Whether linear_param_grads takes the split-fp16 weight gradient for a dY [tokens, out_f] and an x [tokens, in_f]."""
+    return bool(need_w and sp is not None and x3 is not None and _VSPLIT16_WGRAD and
+                ops.gemm_f16_wgrad_tokmajor_seg3_plan(out_f, in_f, tokens) > 0)
+
+
+def _dystats_regime(tokens: int, D: int, I: int) -> bool:
+    """Whether a tower's backward asks its producers of dY for column partials at all: the switch is on and the
+    step is large enough for its data-gradient GEMMs to run on the ping-pong kernel (fc2's, [tokens, 3 D] x [I, 3 D], stands for
+    the four).  That is where the single pass was measured and where it can pay: below it a dY fits the cache, its second read
+    costs no memory traffic, the step is launch-bound, and the schedule stays §9f's, launch for launch."""
+    return bool(_VSPLIT16_DYSTATS and ops.gemm_f16_rows_stats_plan(tokens, I, 3 * D) > 0)
+
+
+def _with_stats(want: bool, P: int, cols: int, dev):
+    """The ColStats a producer of dY is handed: only when the weight gradient that follows will take the split path
+    (`want`, _split_wgrad_taken), the switch is on and the producer's plan P says yes; None = the three-launch pass as before."""
+    return ops.ColStats(P, cols, dev) if want and _VSPLIT16_DYSTATS and P > 0 else None
+
+
+def _ln_bwd(dy, x, gamma, mean, rstd, dresidual, want: bool, gr, wkey: str, bkey: str, alloc, dx_stats: bool = False):
+    """LayerNorm backward; dγ / dβ land where `alloc` says.  `dx_stats`: dx is the dY of a split weight gradient and leaves with
+    its column partials (`dx.dystats`) when the kernel has that form."""
+    D = x.shape[-1]
+    st = _with_stats(dx_stats, ops.layernorm_bwd_stats_plan(x.numel() // D, D) if dx_stats else 0, D, dy.device)
     if want:
         dg = _galloc(alloc, wkey, tuple(gamma.shape), dy.device)
         db = _galloc(alloc, bkey, tuple(gamma.shape), dy.device)
-        dx, dg, db = ops.layernorm_bwd(dy, x, gamma, mean, rstd, dresidual=dresidual, dgamma=dg, dbeta=db, accumulate=False)
+        dx, dg, db = ops.layernorm_bwd(dy, x, gamma, mean, rstd, dresidual=dresidual, dgamma=dg, dbeta=db, accumulate=False, stats=st)
         gr[wkey], gr[bkey] = dg, db
-        return dx
-    dx, _, _ = ops.layernorm_bwd(dy, x, gamma, mean, rstd, dresidual=dresidual, need_param_grads=False)
+    else:
+        dx, _, _ = ops.layernorm_bwd(dy, x, gamma, mean, rstd, dresidual=dresidual, need_param_grads=False, stats=st)
+    if st is not None:
+        dx.dystats = st
     return dx
 
 
-def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None):
+def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None, out_stats: bool = False):
     """dX = dy w (times quick_gelu'(aux) when given), the data gradient of a linear layer.  `sp` (a Split16Layer with
     transposed copies): dy is split with one scale per row and meets the [hi|hi|lo] copy of w^T on the fp16 MFMAs (DESIGN.md
     §9e); None = the plain fp32 GEMM.  dy itself stays fp32 for the weight and bias gradients.  `rows`: the row pieces
-    (dy3, row_alpha) when linear_param_grads has already made them in its fused pass (§9f)."""
+    (dy3, row_alpha) when linear_param_grads has already made them in its fused pass (§9f).  `out_stats`: dX is itself the dY of
+    a split weight gradient and leaves with its column partials (`.dystats`, §9g) when the GEMM's plan has that form."""
     if sp is None:
         if aux is None:
             return ops.gemm(dy, w, ops.LAYOUT_NN)
         return ops.gemm(dy, w, ops.LAYOUT_NN, aux=aux, epilogue=ops.EPI_DGELU)
     dy3, row_alpha = rows if rows is not None else ops.split_f16x3_rows(dy)
-    return ops.gemm_f16_rows_dev(dy3, sp.wt[name], sp.walpha(name), row_alpha, dgelu_h=aux)
+    wt = sp.wt[name]
+    st = _with_stats(out_stats, ops.gemm_f16_rows_stats_plan(dy3.shape[0], wt.shape[0], min(dy3.shape[1], wt.shape[1]))
+                     if out_stats else 0, wt.shape[0], dy3.device)
+    dx = ops.gemm_f16_rows_dev(dy3, wt, sp.walpha(name), row_alpha, dgelu_h=aux, stats=st)
+    if st is not None:
+        dx.dystats = st
+    return dx
 
 
 def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, need: Dict[str, bool], alloc=None,
-              sp: Optional[Split16Layer] = None):
+              sp: Optional[Split16Layer] = None, dx_stats: bool = False, dystats: bool = False):
     """Returns (dx, grads) with grads keyed like LayerParams.FIELDS (missing = not needed).  `alloc(field, shape)`:
-    see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad)."""
+    see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad).  `dystats` (the caller's decision for
+    the whole tower, _dystats_regime): each kernel that produces the dY of a weight gradient that will take the split path is
+    asked for its column partials (§9g); `dx_stats`: the caller says so for the returned dx (the layer below's fc2)."""
     x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved[:13]
     s3 = saved[13] if len(saved) > 13 and sp is not None else {}      # the forward's split operands (layer_fwd, keep_split)
     gr: Dict[str, torch.Tensor] = {}
+    T, D, I = x.shape[0], x.shape[1], p.fc1_w.shape[0]
     rows = linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc, sp, "g", s3.get("g"))
-    dh = _dgrad(dx2, p.fc2_w, sp, "fc2", aux=h, rows=rows)
+    dh = _dgrad(dx2, p.fc2_w, sp, "fc2", aux=h, rows=rows,
+                out_stats=dystats and _split_wgrad_taken(bool(need.get("fc1_w")), sp, s3.get("ln2"), I, D, T))
     rows = linear_param_grads(dh, ln2, bool(need.get("fc1_w")), bool(need.get("fc1_b")), gr, "fc1_w", "fc1_b", alloc, sp, "ln2",
                               s3.get("ln2"))
     dln2 = _dgrad(dh, p.fc1_w, sp, "fc1", rows=rows)
     del dh
-    dx1 = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc)
+    dx1 = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc,
+                  dx_stats=dystats and _split_wgrad_taken(bool(need.get("out_w")), sp, s3.get("ctx"), D, D, T))
     rows = linear_param_grads(dx1, attn, bool(need.get("out_w")), bool(need.get("out_b")), gr, "out_w", "out_b", alloc, sp, "ctx",
                               s3.get("ctx"))
     dattn = _dgrad(dx1, p.out_w, sp, "out", rows=rows)
-    dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal)
+    qkv_stats = dystats and _split_wgrad_taken(bool(need.get("qkv_w")), sp, s3.get("ln1"), 3 * D, D, T)
+    st = _with_stats(qkv_stats, ops.attention_bwd_stats_plan(B, S, H) if qkv_stats else 0, 3 * D, dattn.device)
+    dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal, stats=st)
+    if st is not None:
+        dqkv.dystats = st
     rows = linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc, sp, "ln1",
                               s3.get("ln1"))
     dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv", rows=rows)
     del dqkv, rows
-    dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dx1, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc)
+    dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dx1, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc,
+                 dx_stats=dx_stats)
     return dx, gr
 
 
@@ -232,7 +278,7 @@ def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, sa
 
 
 def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need: Dict[str, bool], alloc=None,
-                       sp: Optional[Split16Layer] = None):
+                       sp: Optional[Split16Layer] = None, dx_stats: bool = False):
     """dx2 [B, D] is the gradient w.r.t. the CLS rows of the final hidden state; returns (dx [B*S, D], grads).  `sp`: the
     full-size qkv data gradient takes the split-fp16 path (_dgrad); the M = B GEMMs stay on ops.gemm."""
     x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved[:13]
@@ -252,7 +298,8 @@ def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need:
     dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv", rows=rows)
     del dqkv, rows
     dres = ops.scatter_rows(dx1, None, B, S, D)                           # the skip connection carries dx1 on CLS rows only
-    dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dres, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc)
+    dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dres, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc,
+                 dx_stats=dx_stats)       # (dqkv comes from attention_cls_bwd, which has no statistics form: three launches)
     return dx, gr
 
 
@@ -396,14 +443,20 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
         return [grads[n] for n in names]
     dx = None if pruned else ops.scatter_rows(dcls, None, B, S, D)
     plan = split16.layers if split16 is not None and _VSPLIT16_BWD and split16.fresh() else None
+    dystats = plan is not None and _dystats_regime(B * S, D, p.layers[0].fc1_w.shape[0])
     for i in range(n_layers - 1, max(lowest, 0) - 1, -1):
         lneed = {f: needd[f"layers.{i}.{f}"] for f in LayerParams.FIELDS}
         lalloc = None if alloc is None else (lambda f, shape, i=i: alloc(f"layers.{i}.{f}", shape))
         sp = plan[i] if plan is not None else None
+        # dx is the dY of the layer below's fc2: its producer is asked for the column partials when that weight gradient will
+        # take the split path (§9g)
+        below = dystats and i - 1 >= max(lowest, 0) and len(saved_layers[i - 1]) > 13
+        dxs = below and _split_wgrad_taken(bool(needd[f"layers.{i - 1}.fc2_w"]), plan[i - 1], saved_layers[i - 1][13].get("g"),
+                                           D, p.layers[i - 1].fc1_w.shape[0], B * S)
         if pruned and i == n_layers - 1:
-            dx, gr = last_layer_bwd_cls(dcls, p.layers[i], saved_layers[i], B, S, H, lneed, lalloc, sp)
+            dx, gr = last_layer_bwd_cls(dcls, p.layers[i], saved_layers[i], B, S, H, lneed, lalloc, sp, dxs)
         else:
-            dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, S, H, False, lneed, lalloc, sp)
+            dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, S, H, False, lneed, lalloc, sp, dxs, dystats)
         saved_layers[i] = None
         for f, t in gr.items():
             grads[f"layers.{i}.{f}"] = t
@@ -1319,6 +1372,9 @@ _VSPLIT16_BWD = os.environ.get("DCLIP_VISION_SPLIT16_BWD", "1") != "0"
 # that backward's full-size weight-gradient GEMMs too, dY split per column; 0 = the plain fp32 wgrads.  Needs
 # the two switches above: the X operands are the forward's splits, and the fused dY pass is the split backward's
 _VSPLIT16_WGRAD = os.environ.get("DCLIP_VISION_SPLIT16_WGRAD", "1") != "0"
+# ... and the kernels that produce those dY leave the column partials, so that dY is read once; 0 = the
+# three-launch pass of §9f for every dY, the parent's launch list and outputs bit for bit
+_VSPLIT16_DYSTATS = os.environ.get("DCLIP_VISION_SPLIT16_DYSTATS", "1") != "0"
 
 
 def vision_split16_enabled() -> bool:

@@ -86,6 +86,33 @@ class workspace_lane:
         return False
 
 
+class ColStats:
+    """Column partials of an fp32 dY left by the kernel that produced it: pmax int32 [P, cols] (bit patterns of
+    the maxima of |x|), psum fp32 [P, cols].  Views into a persistent buffer of the current workspace lane that lives beside the
+    lane's scratch: ONE set per lane, valid from the producer's launch to the split_f16x3_rows_cols_stats that consumes it —
+    the next launch sequence of the backward, so nothing else asks for a set in between."""
+    __slots__ = ("pmax", "psum", "P", "cols")
+
+    def __init__(self, P: int, cols: int, device):
+        ws = _stats_lanes.setdefault(id(_ws), _Workspace()).get(2 * P * cols * 4, device)
+        self.pmax = ws[:P * cols * 4].view(torch.int32).view(P, cols)
+        self.psum = ws[P * cols * 4:2 * P * cols * 4].view(torch.float32).view(P, cols)
+        self.P, self.cols = P, cols
+
+    @classmethod
+    def of(cls, pmax: torch.Tensor, psum: torch.Tensor) -> "ColStats":
+        """Partials in the caller's own contiguous tensors (int32 / fp32 [P, cols])."""
+        if pmax.dtype != torch.int32 or psum.dtype != torch.float32 or pmax.shape != psum.shape or pmax.dim() != 2 or \
+                not (pmax.is_contiguous() and psum.is_contiguous() and pmax.is_cuda and psum.is_cuda):
+            raise ValueError("ColStats.of: pmax int32 / psum fp32, contiguous device tensors of one shape [P, cols]")
+        st = cls.__new__(cls)
+        st.pmax, st.psum, (st.P, st.cols) = pmax, psum, pmax.shape
+        return st
+
+
+_stats_lanes = {}
+
+
 # ------------------------------------------------------------------------------------------- GEMM
 
 def gemm(a: torch.Tensor, b: torch.Tensor, layout: int, *, out: Optional[torch.Tensor] = None,
@@ -172,8 +199,10 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, *, dresidual=None, dgamma=None, dbeta=None, accumulate=False,
                   need_param_grads=True, want_bf16: bool = False, dx_colsum: Optional[torch.Tensor] = None,
-                  dtype16: torch.dtype = torch.bfloat16):
+                  dtype16: torch.dtype = torch.bfloat16, stats: Optional[ColStats] = None):
     """Returns (dx, dgamma, dbeta); dgamma/dbeta are written (or accumulated into) if requested.
+    `stats` (a ColStats of layernorm_bwd_stats_plan(rows, D) partial rows, > 0): the kernel also leaves the column partials of
+    dx there; dx, dgamma, dbeta are bit-equal to the call without.
     16-bit training path: `want_bf16` -> returns (dx, dgamma, dbeta, dx16) with the 16-bit copy of dx (`dtype16`: bf16, or
     fp16 with IEEE rounding) from the same pass; `dx_colsum` [D] receives the column sums of dx (the bias gradient of the
     Linear that produced LayerNorm's input)."""
@@ -200,6 +229,14 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, *, dresidual=None, dgamma=None, dbet
         raise ValueError("layernorm_bwd: dx_colsum size")
     nbytes = lib.dclip_layernorm_bwd_workspace(rows, D) if (need_param_grads or dx_colsum is not None) else 0
     ws = _ws.get(nbytes, x.device)
+    if stats is not None:
+        if want_bf16 or dx_colsum is not None or (stats.P, stats.cols) != (layernorm_bwd_stats_plan(rows, D), D) or stats.P == 0:
+            raise ValueError("layernorm_bwd: stats go with the plain fp32 call and layernorm_bwd_stats_plan's row count")
+        _lib.check(lib.dclip_layernorm_bwd_stats(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                 _ptr(dresidual), dx.data_ptr(), _ptr(dgamma), _ptr(dbeta), stats.pmax.data_ptr(),
+                                                 stats.psum.data_ptr(), rows, D, int(accumulate), _ptr(ws), nbytes, _stream()),
+                   "layernorm_bwd_stats")
+        return dx, dgamma, dbeta
     if not want_bf16 and dx_colsum is None:
         _lib.check(lib.dclip_layernorm_bwd(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
                                            rstd.data_ptr(), _ptr(dresidual), dx.data_ptr(), _ptr(dgamma), _ptr(dbeta),
@@ -216,6 +253,11 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, *, dresidual=None, dgamma=None, dbet
     return (dx, dgamma, dbeta, dx16) if want_bf16 else (dx, dgamma, dbeta)
 
 
+def layernorm_bwd_stats_plan(rows: int, D: int) -> int:
+    """Partial rows layernorm_bwd leaves with `stats`, 0 where that form does not exist (D > 1024)."""
+    return int(_lib.load().dclip_layernorm_bwd_stats_plan(rows, D))
+
+
 # ------------------------------------------------------------------------------------------- attention
 
 def attention_fwd(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool):
@@ -230,13 +272,27 @@ def attention_fwd(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool):
     return out, lse
 
 
-def attention_bwd(qkv, out, dout, lse, B: int, S: int, H: int, causal: bool):
+def attention_bwd_stats_plan(B: int, S: int, H: int) -> int:
+    """Partial rows attention_bwd leaves with `stats` (B), 0 where that form does not exist (S == 1, S > 64)."""
+    return int(_lib.load().dclip_attention_bwd_stats_plan(B, S, H))
+
+
+def attention_bwd(qkv, out, dout, lse, B: int, S: int, H: int, causal: bool, stats: Optional[ColStats] = None):
+    """`stats` (a ColStats of attention_bwd_stats_plan(B, S, H) partial rows, > 0, 3 H 64 columns): the kernel also leaves the
+    column partials of dqkv there; dqkv is bit-equal to the call without."""
     lib = _lib.load()
     _f32(qkv, "qkv"), _f32(out, "out"), _f32(dout, "dout"), _f32(lse, "lse")
     if qkv.numel() != B * S * 3 * H * 64 or out.numel() != B * S * H * 64 or dout.numel() != out.numel() \
             or lse.numel() != B * H * S:
         raise ValueError("attention_bwd: shape mismatch")
     dqkv = torch.empty_like(qkv)
+    if stats is not None:
+        if (stats.P, stats.cols) != (attention_bwd_stats_plan(B, S, H), 3 * H * 64) or stats.P == 0:
+            raise ValueError("attention_bwd: stats must have attention_bwd_stats_plan's row count and 3 H 64 columns")
+        _lib.check(lib.dclip_attention_bwd_stats(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(),
+                                                 stats.pmax.data_ptr(), stats.psum.data_ptr(), B, S, H, int(causal), _stream()),
+                   "attention_bwd_stats")
+        return dqkv
     # delta, and for long non-causal sequences the dS blocks the dK/dV kernel hands to the dQ kernel (include/dclip_hip.h)
     nbytes = int(lib.dclip_attention_bwd_workspace(B, S, H, int(causal)))
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=qkv.device)
@@ -1353,10 +1409,17 @@ def split_f16x3_rows(x: torch.Tensor):
     return y, ra
 
 
+def gemm_f16_rows_stats_plan(M: int, N: int, K: int) -> int:
+    """Partial rows gemm_f16_rows_dev leaves with `stats` (ceil(M / 256)), 0 where the dispatcher takes a register-staged kernel,
+    which has no such form."""
+    return int(_lib.load().dclip_gemm_f16_scaled_rows_stats_plan(M, N, K))
+
+
 def gemm_f16_rows_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, row_alpha: torch.Tensor,
-                      dgelu_h: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      dgelu_h: Optional[torch.Tensor] = None, stats: Optional[ColStats] = None) -> torch.Tensor:
     """fp32 [M, N] = ((a w^T) * *alpha_ptr) * row_alpha[m], times quick_gelu'(dgelu_h) when given (fp32 [M, N]): gemm_f16_dev for
-    an `a` split by split_f16x3_rows."""
+    an `a` split by split_f16x3_rows.  `stats` (a ColStats of gemm_f16_rows_stats_plan(M, N, K) partial rows, > 0): the kernel
+    also leaves the column partials of the result there; the result is bit-equal to the call without."""
     lib = _lib.load()
     _f16(a, "a"), _f16(w, "w")
     M, lda = a.shape
@@ -1367,6 +1430,14 @@ def gemm_f16_rows_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, row_alph
     if dgelu_h is not None and tuple(_f32(dgelu_h, "dgelu_h").shape) != (M, N):
         raise ValueError("gemm_f16_rows_dev: dgelu_h shape")
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    if stats is not None:
+        if (stats.P, stats.cols) != (gemm_f16_rows_stats_plan(M, N, K), N) or stats.P == 0:
+            raise ValueError("gemm_f16_rows_dev: stats must have gemm_f16_rows_stats_plan's row count and N columns")
+        _lib.check(lib.dclip_gemm_f16_scaled_rows_stats_dev(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(dgelu_h), M, N, K, lda, ldw,
+                                                            N, EPI_DGELU if dgelu_h is not None else 0, alpha_ptr,
+                                                            row_alpha.data_ptr(), stats.pmax.data_ptr(), stats.psum.data_ptr(),
+                                                            _stream()), "gemm_f16_scaled_rows_stats_dev")
+        return out
     _lib.check(lib.dclip_gemm_f16_scaled_rows_dev(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(dgelu_h), M, N, K, lda, ldw, N,
                                                   EPI_DGELU if dgelu_h is not None else 0, alpha_ptr, row_alpha.data_ptr(),
                                                   _stream()), "gemm_f16_scaled_rows_dev")
@@ -1395,6 +1466,30 @@ def split_f16x3_rows_colstats(x: torch.Tensor, db: Optional[torch.Tensor] = None
     _lib.check(lib.dclip_split_f32_f16x3_rows_colstats(x.data_ptr(), y.data_ptr(), ra.data_ptr(), yc.data_ptr(), ce.data_ptr(),
                                                        ca.data_ptr(), _ptr(db), rows, cols, x.stride(0) if rows > 1 else cols,
                                                        _ptr(ws), nbytes, _stream()), "split_f32_f16x3_rows_colstats")
+    return y, ra, yc, ce, ca
+
+
+def split_f16x3_rows_cols_stats(x: torch.Tensor, stats: ColStats, db: Optional[torch.Tensor] = None):
+    """split_f16x3_rows_colstats for an x whose producer left its column partials in `stats`: the finish over
+    the partial rows, then ONE pass over x.  The same five outputs, bit for bit; `db` is another association of the same sums."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("split_f16x3_rows_cols_stats: x must be a 2-D fp32 device tensor with unit column stride")
+    rows, cols = x.shape
+    if stats.cols != cols or stats.P <= 0:
+        raise ValueError("split_f16x3_rows_cols_stats: stats columns")
+    if db is not None and (_f32(db, "db").numel() != cols):
+        raise ValueError("split_f16x3_rows_cols_stats: db size")
+    dev = x.device
+    y = torch.empty((rows, 3 * cols), dtype=torch.float16, device=dev)
+    ra = torch.empty((rows,), dtype=torch.float32, device=dev)
+    yc = torch.empty((rows, 2 * cols), dtype=torch.float16, device=dev)
+    ce = torch.empty((cols,), dtype=torch.int32, device=dev)
+    ca = torch.empty((cols,), dtype=torch.float32, device=dev)
+    _lib.check(lib.dclip_split_f32_f16x3_rows_cols_stats(x.data_ptr(), y.data_ptr(), ra.data_ptr(), yc.data_ptr(), ce.data_ptr(),
+                                                         ca.data_ptr(), _ptr(db), stats.pmax.data_ptr(), stats.psum.data_ptr(), stats.P,
+                                                         rows, cols, x.stride(0) if rows > 1 else cols, _stream()),
+               "split_f32_f16x3_rows_cols_stats")
     return y, ra, yc, ce, ca
 
 

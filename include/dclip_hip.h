@@ -687,6 +687,33 @@ int dclip_gemm_f16_wgrad_tokmajor_seg3(const void* dY, const void* X, float* C, 
                                        int a_seg0, int a_seg1, int a_seg2, int w_seg0, int w_seg1, int w_seg2, const float* col_alpha,
                                        const float* act_scale, int splits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- dY read once: the kernels that PRODUCE a dY leave its column partials, pmax [P][cols] (bit patterns of the
+ * maxima of |x|, unsigned) and psum [P][cols] (fp32 sums), partial row p from the producer's p-th row block, every word written,
+ * no atomics, the same bits in every run; statistics are of the values stored.  Each producer entry is the plain entry plus the
+ * two pointers, its other outputs bit-equal to the plain entry's; its _plan returns P, or 0 where the form does not exist (the
+ * caller then takes the plain entry and the three-launch split).
+ *   split_f32_f16x3_rows_cols_stats  the finish over the P partial rows, then ONE pass over x that writes both splits: y, row_alpha,
+ *                            col_exp, col_alpha, yc bit-equal to split_f32_f16x3_rows_colstats on the same x; db (NULL = not
+ *                            wanted) is another association of the same sum.
+ *   gemm_f16_scaled_rows_stats_dev   gemm_f16_scaled_rows_dev on the ping-pong kernel, P = ceil(M / 256); _plan is 0 where the
+ *                            dispatcher takes a register-staged kernel.
+ *   attention_bwd_stats      attention_bwd for 1 < S <= 64, cols = 3 D, P = B.
+ *   layernorm_bwd_stats      layernorm_bwd for D <= 1024, cols = D, P = the kernel's block count; psum's rows are the partials
+ *                            dx_colsum is folded from.  workspace as layernorm_bwd (needed with dgamma / dbeta only). */
+int dclip_split_f32_f16x3_rows_cols_stats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha, float* db,
+                                          const void* pmax, const float* psum, int P, int rows, int cols, int ldx, void* stream);
+int dclip_gemm_f16_scaled_rows_stats_plan(int M, int N, int K);
+int dclip_gemm_f16_scaled_rows_stats_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K, int lda,
+                                         int ldw, int ldc, int epilogue, const float* alpha, const float* row_alpha, void* pmax,
+                                         float* psum, void* stream);
+int dclip_attention_bwd_stats_plan(int B, int S, int H);
+int dclip_attention_bwd_stats(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, void* pmax,
+                              float* psum, int B, int S, int H, int causal, void* stream);
+int dclip_layernorm_bwd_stats_plan(int rows, int D);
+int dclip_layernorm_bwd_stats(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                              const float* dresidual, float* dx, float* dgamma, float* dbeta, void* pmax, float* psum, int rows, int D,
+                              int accumulate_param_grads, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * fp16 TRAINING path (opt-in student_precision="fp16" / get_image_features(precision="fp16-mixed")): fp16
  * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
