@@ -155,6 +155,17 @@ SIGNATURES = {
     "dclip_attention_bwd_stats": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     "dclip_layernorm_bwd_stats_plan": (I, [I, I]),
     "dclip_layernorm_bwd_stats": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, Z, P]),
+    "dclip_gemm_f16x3_plan": (I, [I, I, I]),
+    "dclip_gemm_f16x3_scaled": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, P]),
+    "dclip_gemm_f16x3_scaled_split": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, F, P]),
+    "dclip_gemm_f16x3_scaled_dev": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P]),
+    "dclip_gemm_f16x3_scaled_split_dev": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P, P]),
+    "dclip_gemm_f16x3_scaled_rows_dev": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P, P]),
+    "dclip_gemm_f16x3_scaled_rows_stats_plan": (I, [I, I, I]),
+    "dclip_gemm_f16x3_scaled_rows_stats_dev": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P, P, P, P]),
+    "dclip_gemm_f16x3_wgrad_tokmajor_plan": (I, [I, I, I]),
+    "dclip_gemm_f16x3_wgrad_tokmajor_workspace": (Z, [I, I, I]),
+    "dclip_gemm_f16x3_wgrad_tokmajor": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, P, P, I, P, Z, P]),
     "dclip_gemm_f16_wgrad_tokmajor_seg3_plan": (I, [I, I, I]),
     "dclip_gemm_f16_wgrad_tokmajor_seg3": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, Z, P]),
     "dclip_gemm_f16_ex": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),

@@ -9,7 +9,8 @@
 // traffic (64 KB per 512 MFMA cycles per workgroup), not by the matrix pipes.  gemm_bf16_pp_kernel — the 256x256 ping-pong
 // kernel on LDS-DMA, one workgroup per CU, for K % 64 == 0 and at least DCLIP_BF16_BIG_MIN (default 128) tiles; also the
 // token-major and segmented weight-gradient forms.  gemm_bf16_ppp_kernel is its persistent form, opt-in and measured slower
-// (DCLIP_BF16_PERSIST=1, _PERSIST_MIN).  Those and DCLIP_BF16_BIG_MIN are the switches this file reads, each per call.
+// (DCLIP_BF16_PERSIST=1, _PERSIST_MIN).  Those, DCLIP_BF16_BIG_MIN and the two plan thresholds of the fused split-fp16 entries
+// (DCLIP_F16X3_MIN, DCLIP_F16X3_TOK_MIN) are the switches this file reads, each per call.
 //
 // Types: every kernel is a template over the 16-bit type (common.h: Bf16T, F16T, F16IeeeT); only the MFMA
 // (v_mfma_f32_{32x32x16,16x16x32}_{bf16,f16}) and the rounding differ.  F16T (saturating) serves the frozen towers and the
@@ -618,9 +619,16 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 // SEG (token-major only): the contraction is three segments of K rows; the split index selects the segment, so a work item
 // stays inside one segment and the K loop, phases and barriers are what they were.  Always split-K (>= 3 slabs).
 // STATS (ROWS only): pp_epilogue's statistics form; nothing else differs.
-template <class T, bool TOK, bool DEV = false, bool ROWS = false, bool SEG = false, bool STATS = false>
+// FUSED (the dclip_gemm_f16x3_* entries): the split-fp16 sum A_hi W_hi + A_lo W_hi + A_hi W_lo out of ONE staging of
+// the four distinct pieces.  A K-tile is 32 logical k: k-step 0 (granules 0-3 / k-rows 0-31) holds their hi pieces, k-step 1
+// (granules 4-7 / k-rows 32-63) their lo pieces, fetched from the column offsets a_seg / w_seg [0] (hi) and [1] (lo), and a
+// phase issues three products per accumulator (24 MFMAs) on the same 12 fragment reads and 2 DMA pieces.  p.K is the logical K
+// (a multiple of 32; the token-major form contracts whole 64-token units per split).  Same phases, barriers and counted waits.
+template <class T, bool TOK, bool DEV = false, bool ROWS = false, bool SEG = false, bool STATS = false, bool FUSED = false>
 __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   static_assert(!SEG || (TOK && !DEV && !ROWS), "the segmented form is token-major, split-K, fp32 slabs");
+  static_assert(!FUSED || !SEG, "the fused form does all three products in one work item");
+  constexpr int KT = FUSED ? BKH / 2 : BKH;   // logical k per K-tile
   static_assert(!STATS || (ROWS && !TOK), "the statistics form is the row-scaled dgrad");
   typedef typename T::x8 V8;
   constexpr int BM = 256, BN = 256, ROW = BKH;
@@ -655,30 +663,49 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   }
   const int kbeg = p.k_per_split ? ksplit * p.k_per_split : 0;
   const int kspan = (p.k_per_split ? min(p.K, kbeg + p.k_per_split) : p.K) - kbeg;
-  const int nk = kspan / BKH;
+  const int nk = kspan / KT;
 
   const __bf16* a_org = TOK ? p.A + (size_t)kbeg * p.lda + m0 + a_col0 : p.A + (size_t)m0 * p.lda + kbeg;
   const __bf16* w_org = TOK ? p.W + (size_t)kbeg * p.ldw + n0 + w_col0 : p.W + (size_t)n0 * p.ldw + kbeg;
   const int a_rows = min(BM, p.M - m0), w_rows = min(BN, p.N - n0);
-  const size_t a_bytes = TOK ? ((size_t)(p.K - kbeg - 1) * p.lda + a_rows) * 2 : ((size_t)(a_rows - 1) * p.lda + (p.K - kbeg)) * 2,
-               w_bytes = TOK ? ((size_t)(p.K - kbeg - 1) * p.ldw + w_rows) * 2 : ((size_t)(w_rows - 1) * p.ldw + (p.K - kbeg)) * 2;
+  size_t a_bytes = TOK ? ((size_t)(p.K - kbeg - 1) * p.lda + a_rows) * 2 : ((size_t)(a_rows - 1) * p.lda + (p.K - kbeg)) * 2,
+         w_bytes = TOK ? ((size_t)(p.K - kbeg - 1) * p.ldw + w_rows) * 2 : ((size_t)(w_rows - 1) * p.ldw + (p.K - kbeg)) * 2;
+  if constexpr (FUSED) {   // the hi / lo column offsets are part of the lanes' offsets: the range ends behind the farther segment
+    a_bytes += (size_t)max(p.a_seg[0], p.a_seg[1]) * 2;
+    w_bytes += (size_t)max(p.w_seg[0], p.w_seg[1]) * 2;
+  }
   const __amdgpu_buffer_rsrc_t a_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a_org), 0, (int)min(a_bytes, (size_t)0x7fffffff), 0x00020000);
   const __amdgpu_buffer_rsrc_t w_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(w_org), 0, (int)min(w_bytes, (size_t)0x7fffffff), 0x00020000);
   // scalar byte advance per K-tile
-  const int a_kstep = TOK ? BKH * p.lda * 2 : BKH * 2, w_kstep = TOK ? BKH * p.ldw * 2 : BKH * 2;
+  const int a_kstep = TOK ? KT * p.lda * 2 : KT * 2, w_kstep = TOK ? KT * p.ldw * 2 : KT * 2;
   // DMA pieces.  K-major: 8 rows x 128 B, lane i -> row i >> 3, stored slot i & 7 = logical granule slot ^ ((row >> 1) & 7);
   // A-half h: piece x of this wave covers rows 128 x + 64 h + 8 wave; B-half h: rows 64 (2 x + (wave >> 2)) + 32 h + 8 (wave & 3).
   // Token-major: 4 k-rows x 256 B of a half image, piece x of this wave = k-rows 4 (wave + 8 x) ..; lane i -> k-row i >> 4,
   // stored granule i & 15 = logical granule ^ swizzle(k-row); logical granule g of an A half-row holds columns 128 (g >> 3) +
   // 64 h + 8 (g & 7) .., of a B half-row columns 64 (g >> 2) + 32 h + 8 (g & 3) ...
+  // FUSED.  K-major: logical granule g < 4 is k 8 g .. of the hi segment, g >= 4 is k 8 (g - 4) .. of the lo segment.  Token-major:
+  // piece 0 (k-rows 0-31) is tokens 4 wave + (lane >> 4) of the hi columns, piece 1 (k-rows 32-63) the same tokens of the lo columns.
   int a_voff[2][2], w_voff[2][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
-      if (TOK) {
+      if constexpr (FUSED) {
+        if (TOK) {
+          const int k = 4 * (wave + 8 * x) + (lane >> 4), tok = k & 31;
+          const int lg = (lane & 15) ^ (((k & 3) << 2) | (((k >> 3) & 1) << 1));
+          const int ma = 128 * (lg >> 3) + 64 * h + 8 * (lg & 7), nb = 64 * (lg >> 2) + 32 * h + 8 * (lg & 3);
+          a_voff[h][x] = ma < a_rows ? (tok * p.lda + p.a_seg[x] + ma) * 2 : 0x7fffffff;
+          w_voff[h][x] = nb < w_rows ? (tok * p.ldw + p.w_seg[x] + nb) * 2 : 0x7fffffff;
+        } else {
+          const int ra = 128 * x + 64 * h + 8 * wave + (lane >> 3), ga = (lane & 7) ^ ((ra >> 1) & 7);
+          a_voff[h][x] = ra < a_rows ? (ra * p.lda + (ga < 4 ? p.a_seg[0] : p.a_seg[1]) + (ga & 3) * 8) * 2 : 0x7fffffff;
+          const int rb = 64 * (2 * x + (wave >> 2)) + 32 * h + 8 * (wave & 3) + (lane >> 3), gb = (lane & 7) ^ ((rb >> 1) & 7);
+          w_voff[h][x] = rb < w_rows ? (rb * p.ldw + (gb < 4 ? p.w_seg[0] : p.w_seg[1]) + (gb & 3) * 8) * 2 : 0x7fffffff;
+        }
+      } else if (TOK) {
         const int k = 4 * (wave + 8 * x) + (lane >> 4);
         const int lg = (lane & 15) ^ (((k & 3) << 2) | (((k >> 3) & 1) << 1));
         const int ma = 128 * (lg >> 3) + 64 * h + 8 * (lg & 7), nb = 64 * (lg >> 2) + 32 * h + 8 * (lg & 3);
@@ -767,14 +794,15 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
       fb[j][1] = *reinterpret_cast<const V8*>(pb1 + (off) + (32 * (qn) + 16 * j) * ROW);        \
     }                                                                                               \
   }
+  // (FUSED: product s = 0 W_hi A_hi, 1 W_hi A_lo, 2 W_lo A_hi; the product index outermost keeps two MFMAs on one accumulator 8 apart)
 #define PP_MFMA(qm, qn, fb)                                                                                         \
   do {                                                                                                              \
     __builtin_amdgcn_s_setprio(1);                                                                                  \
-    _Pragma("unroll") for (int s = 0; s < 2; ++s)                                                                   \
+    _Pragma("unroll") for (int s = 0; s < (FUSED ? 3 : 2); ++s)                                                     \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                   \
       acc[4 * (qm) + i][2 * (qn) + j] =                                                                             \
-          T::mfma16(fb[j][s], fa[i][s], acc[4 * (qm) + i][2 * (qn) + j]);    \
+          T::mfma16(fb[j][FUSED ? s >> 1 : s], fa[i][FUSED ? s & 1 : s], acc[4 * (qm) + i][2 * (qn) + j]);          \
     __builtin_amdgcn_s_setprio(0);                                                                                  \
   } while (0)
 
@@ -1586,6 +1614,150 @@ DCLIP_API int dclip_gemm_f16_scaled_rows_stats_dev(const void* A, const void* W,
                       1.f, 0.f, &dev);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Fused split-fp16 GEMMs: C = epilogue(alpha (A_hi W_hi^T + A_lo W_hi^T + A_hi W_lo^T)) with A_hi / A_lo the K
+// columns of A from column a_hi / a_lo on and W_hi / W_lo those of W from w_hi / w_lo on — the operands of the scaled entries
+// above as they lie (A = [hi|lo|hi]: 0, K; W = [hi|hi|lo]: 0, 2K), each piece staged once (the FUSED kernel instances).  K is
+// the LOGICAL contraction length, a multiple of 32; the ping-pong kernel only, at any M and N.  Epilogues, scales and outputs
+// are those of the entry each twins; the accumulation order differs, so the values agree to fp32 rounding, not bit for bit.
+namespace {
+struct Segs { int a_hi, a_lo, w_hi, w_lo; };
+
+int gemm16x3(const char* name, const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
+             int lda, int ldw, int ldc, Segs sg, int epilogue, int out_f16, void* stream, float alpha, float out_scale,
+             const DevScales* dev) {
+  DCLIP_REQUIRE(A && W && C, "%s: null operand", name);
+  DCLIP_REQUIRE(M > 0 && N > 0 && K > 0 && K % 32 == 0, "%s: bad shape M=%d N=%d K=%d (K: the logical length, a multiple of 32)", name,
+                M, N, K);
+  DCLIP_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda > 0 && ldw > 0, "%s: lda/ldw must be multiples of 8", name);
+  DCLIP_REQUIRE(sg.a_hi >= 0 && sg.a_lo >= 0 && sg.w_hi >= 0 && sg.w_lo >= 0 && (sg.a_hi | sg.a_lo | sg.w_hi | sg.w_lo) % 8 == 0,
+                "%s: segment offsets must be non-negative multiples of 8", name);
+  DCLIP_REQUIRE((long)sg.a_hi + K <= lda && (long)sg.a_lo + K <= lda && (long)sg.w_hi + K <= ldw && (long)sg.w_lo + K <= ldw,
+                "%s: a segment (offset + K) must lie within the leading dimension", name);
+  DCLIP_REQUIRE(N % 4 == 0 && ldc % 4 == 0 && ldc >= N, "%s: N / ldc must be multiples of 4", name);
+  DCLIP_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 == 0, "%s: operands must be 16-byte aligned", name);
+  DCLIP_REQUIRE(!(epilogue & ~(DCLIP_EPI_BIAS | DCLIP_EPI_GELU | DCLIP_EPI_DGELU | DCLIP_EPI_RESIDUAL)),
+                "%s: unsupported epilogue bits", name);
+  DCLIP_REQUIRE(out_scale == 0.f || (!out_f16 && !(epilogue & (DCLIP_EPI_RESIDUAL | DCLIP_EPI_DGELU)) && (long)ldc >= 3L * N),
+                "%s: a split output takes BIAS | GELU only and ldc >= 3 N", name);
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (dev && dev->aux32 && !(epilogue & DCLIP_EPI_GELU)), "%s: DGELU needs aux32", name);
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_BIAS) || bias, "%s: BIAS without bias", name);
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_RESIDUAL) || (residual && !out_f16), "%s: RESIDUAL needs an fp32 output", name);
+  // 32-bit byte offsets inside a 256-row tile (the kernel's buffer loads)
+  DCLIP_REQUIRE(256L * lda * 2 < 0x7fffffffL && 256L * ldw * 2 < 0x7fffffffL, "%s: leading dimension too large", name);
+  GemmBf16Params p{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_f16, cdiv(M, 256),
+                   cdiv(N, 256), nullptr, 0, nullptr, alpha, out_scale};
+  set_dev(p, dev);
+  p.a_seg[0] = sg.a_hi, p.a_seg[1] = sg.a_lo, p.w_seg[0] = sg.w_hi, p.w_seg[1] = sg.w_lo;
+  const dim3 grid(p.tiles_m * p.tiles_n), block(512);
+  hipStream_t st = (hipStream_t)stream;
+  if (p.row_alpha && p.pmax)
+    hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, true, true, false, true, true>), grid, block, 0, st, p);
+  else if (p.row_alpha)
+    hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, true, true, false, false, true>), grid, block, 0, st, p);
+  else if (p.alpha_p)
+    hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, true, false, false, false, true>), grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, false, false, false, false, true>), grid, block, 0, st, p);
+  DCLIP_CHECK_LAUNCH_V(name, ".pp3");
+  return DCLIP_OK;
+}
+}  // namespace
+
+// Where the step should take a fused entry: exactly where the unfused entry (contraction length 3 K) takes the ping-pong kernel.
+// DCLIP_F16X3_MIN (default 128 tiles, the dispatcher's own default; a tuning aid read per call) is a threshold of its own, so that
+// lowering DCLIP_BF16_BIG_MIN alone moves the unfused entries onto the ping-pong kernel and nothing else.
+DCLIP_API int dclip_gemm_f16x3_plan(int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0 || !takes_pp(M, N, 3 * K)) return 0;
+  const int tiles_min = getenv("DCLIP_F16X3_MIN") ? atoi(getenv("DCLIP_F16X3_MIN")) : 128;
+  return (long)cdiv(M, 256) * cdiv(N, 256) >= tiles_min ? 1 : 0;
+}
+
+DCLIP_API int dclip_gemm_f16x3_scaled(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N,
+                                      int K, int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue,
+                                      int out_f16, float alpha, void* stream) {
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU), "gemm_f16x3_scaled: DGELU is a training epilogue");
+  DCLIP_REQUIRE(alpha == alpha && alpha - alpha == 0.f, "gemm_f16x3_scaled: alpha must be finite");
+  return gemm16x3("gemm_f16x3_scaled", A, W, C, bias, residual, M, N, K, lda, ldw, ldc, Segs{a_hi, a_lo, w_hi, w_lo}, epilogue, out_f16,
+                  stream, alpha, 0.f, nullptr);
+}
+
+DCLIP_API int dclip_gemm_f16x3_scaled_split(const void* A, const void* W, void* C, const float* bias, int M, int N, int K, int lda,
+                                            int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue, float alpha,
+                                            float out_scale, void* stream) {
+  DCLIP_REQUIRE(alpha == alpha && alpha - alpha == 0.f, "gemm_f16x3_scaled_split: alpha must be finite");
+  DCLIP_REQUIRE(out_scale > 0.f && out_scale - out_scale == 0.f && (__builtin_bit_cast(unsigned int, out_scale) & 0x007fffffu) == 0,
+                "gemm_f16x3_scaled_split: out_scale must be a power of two");
+  DCLIP_REQUIRE(ldc % 8 == 0, "gemm_f16x3_scaled_split: ldc must be a multiple of 8");
+  return gemm16x3("gemm_f16x3_scaled_split", A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, Segs{a_hi, a_lo, w_hi, w_lo}, epilogue, 0,
+                  stream, alpha, out_scale, nullptr);
+}
+
+DCLIP_API int dclip_gemm_f16x3_scaled_dev(const void* A, const void* W, void* C, const float* bias, const float* residual, int M,
+                                          int N, int K, int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue,
+                                          int out_f16, const float* alpha, void* stream) {
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU), "gemm_f16x3_scaled_dev: DGELU is a training epilogue");
+  DCLIP_REQUIRE(alpha && (uintptr_t)alpha % 4 == 0, "gemm_f16x3_scaled_dev: alpha must be a device pointer");
+  const DevScales dev{alpha, nullptr, nullptr, nullptr};
+  return gemm16x3("gemm_f16x3_scaled_dev", A, W, C, bias, residual, M, N, K, lda, ldw, ldc, Segs{a_hi, a_lo, w_hi, w_lo}, epilogue,
+                  out_f16, stream, 1.f, 0.f, &dev);
+}
+
+DCLIP_API int dclip_gemm_f16x3_scaled_split_dev(const void* A, const void* W, void* C, const float* bias, float* h32, float* g32,
+                                                int M, int N, int K, int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo,
+                                                int epilogue, const float* alpha, const float* out_scale, void* stream) {
+  DCLIP_REQUIRE(alpha && ((uintptr_t)alpha | (uintptr_t)out_scale) % 4 == 0,
+                "gemm_f16x3_scaled_split_dev: alpha / out_scale must be device pointers");
+  DCLIP_REQUIRE(ldc % 8 == 0, "gemm_f16x3_scaled_split_dev: ldc must be a multiple of 8");
+  DCLIP_REQUIRE(((uintptr_t)h32 | (uintptr_t)g32) % 16 == 0, "gemm_f16x3_scaled_split_dev: h32 / g32 must be 16-byte aligned");
+  DCLIP_REQUIRE(!h32 || (epilogue & DCLIP_EPI_GELU), "gemm_f16x3_scaled_split_dev: h32 is the pre-activation of a GELU epilogue");
+  DCLIP_REQUIRE(!(epilogue & ~(DCLIP_EPI_BIAS | DCLIP_EPI_GELU)), "gemm_f16x3_scaled_split_dev: the epilogue is BIAS | GELU");
+  DCLIP_REQUIRE(out_scale || !g32, "gemm_f16x3_scaled_split_dev: without out_scale C is the fp32 result (g32 must be NULL)");
+  const DevScales dev{alpha, out_scale, h32, g32};
+  return gemm16x3("gemm_f16x3_scaled_split_dev", A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, Segs{a_hi, a_lo, w_hi, w_lo}, epilogue,
+                  0, stream, 1.f, out_scale ? 1.f : 0.f, &dev);
+}
+
+DCLIP_API int dclip_gemm_f16x3_scaled_rows_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K, int lda,
+                                               int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue,
+                                               const float* alpha, const float* row_alpha, void* stream) {
+  DCLIP_REQUIRE(alpha && row_alpha && ((uintptr_t)alpha | (uintptr_t)row_alpha) % 4 == 0,
+                "gemm_f16x3_scaled_rows_dev: alpha / row_alpha must be device pointers");
+  DCLIP_REQUIRE(epilogue == 0 || epilogue == DCLIP_EPI_DGELU, "gemm_f16x3_scaled_rows_dev: the epilogue is none or DGELU");
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (aux32 && (uintptr_t)aux32 % 16 == 0),
+                "gemm_f16x3_scaled_rows_dev: DGELU needs a 16-byte aligned fp32 aux32");
+  DevScales dev{alpha, nullptr, nullptr, nullptr};
+  dev.row_alpha = row_alpha;
+  dev.aux32 = (epilogue & DCLIP_EPI_DGELU) ? aux32 : nullptr;
+  return gemm16x3("gemm_f16x3_scaled_rows_dev", A, W, C, nullptr, nullptr, M, N, K, lda, ldw, ldc, Segs{a_hi, a_lo, w_hi, w_lo},
+                  epilogue, 0, stream, 1.f, 0.f, &dev);
+}
+
+// Partial rows of the statistics twin: ceil(M / 256) where dclip_gemm_f16x3_plan holds, else 0.
+DCLIP_API int dclip_gemm_f16x3_scaled_rows_stats_plan(int M, int N, int K) {
+  return dclip_gemm_f16x3_plan(M, N, K) ? cdiv(M, 256) : 0;
+}
+
+// pmax / psum [ceil(M / 256)][N], every word written (the entry itself runs at any M, N: it has the ping-pong kernel only).
+DCLIP_API int dclip_gemm_f16x3_scaled_rows_stats_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K,
+                                                     int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue,
+                                                     const float* alpha, const float* row_alpha, void* pmax, float* psum,
+                                                     void* stream) {
+  DCLIP_REQUIRE(alpha && row_alpha && ((uintptr_t)alpha | (uintptr_t)row_alpha) % 4 == 0,
+                "gemm_f16x3_scaled_rows_stats_dev: alpha / row_alpha must be device pointers");
+  DCLIP_REQUIRE(pmax && psum && ((uintptr_t)pmax | (uintptr_t)psum) % 4 == 0, "gemm_f16x3_scaled_rows_stats_dev: pmax / psum");
+  DCLIP_REQUIRE(epilogue == 0 || epilogue == DCLIP_EPI_DGELU, "gemm_f16x3_scaled_rows_stats_dev: the epilogue is none or DGELU");
+  DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (aux32 && (uintptr_t)aux32 % 16 == 0),
+                "gemm_f16x3_scaled_rows_stats_dev: DGELU needs a 16-byte aligned fp32 aux32");
+  DevScales dev{alpha, nullptr, nullptr, nullptr};
+  dev.row_alpha = row_alpha;
+  dev.aux32 = (epilogue & DCLIP_EPI_DGELU) ? aux32 : nullptr;
+  dev.pmax = (unsigned*)pmax;
+  dev.psum = psum;
+  return gemm16x3("gemm_f16x3_scaled_rows_dev.stats", A, W, C, nullptr, nullptr, M, N, K, lda, ldw, ldc, Segs{a_hi, a_lo, w_hi, w_lo},
+                  epilogue, 0, stream, 1.f, 0.f, &dev);
+}
+
 // fp16 TRAINING path: dclip_gemm_bf16_ex's arguments, epilogues and limits with fp16 A / W / aux / 16-bit C, IEEE rounding
 // (common.h, F16IeeeT: an overflow becomes +-inf).  The ping-pong / register-staged kernels only (DCLIP_BF16_PERSIST does
 // not apply).
@@ -1712,6 +1884,70 @@ DCLIP_API int dclip_gemm_f16_wgrad_tokmajor_seg3(const void* dY, const void* X, 
   hipLaunchKernelGGL(splitk_reduce_scaled_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, st, (const float*)workspace, C,
                      M, N, ldc, 3 * s_eff, col_alpha, act_scale);
   DCLIP_CHECK_LAUNCH_V(name, ".pp_tok_seg.splitk_reduce");
+  return DCLIP_OK;
+}
+
+// The fused form of the segmented weight gradient: dW[M][N] = ((dY_hi^T X_hi + dY_lo^T X_hi + dY_hi^T X_lo) /
+// *act_scale) * col_alpha[m], dY_hi / dY_lo the M columns of dY from dy_hi / dy_lo on, X_hi / X_lo the N columns of X from x_hi /
+// x_lo on (the step: 0, M, 0, N).  A work item owns a token range — whole 64-token units — and does all three products for it
+// out of one staging of the four pieces (the FUSED token-major kernel instance): `splits` fp32 slabs in the workspace
+// (dclip_gemm_f16x3_wgrad_tokmajor_workspace(M, N, splits)), then dclip_gemm_f16_wgrad_tokmajor_seg3's fixed-order scaled reduce.
+// _plan: the split count — one round of 256 work items, at least 192 tokens each (about the segmented plan's work-item count;
+// swept at the step's shapes) — or 0 where the segmented form does not apply or this one would start fewer than
+// DCLIP_F16X3_TOK_MIN (default 128, a tuning aid read per call) work items.
+DCLIP_API int dclip_gemm_f16x3_wgrad_tokmajor_plan(int M, int N, int tokens) {
+  if (dclip_gemm_f16_wgrad_tokmajor_seg3_plan(M, N, tokens) == 0) return 0;
+  const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
+  int s = t256 >= 256 ? 1 : (int)(256 / t256);               // one round of 256 CUs (the sweep of tools/split16_fused_bench.py)
+  const int kmax = tokens / 192 > 0 ? tokens / 192 : 1;      // at least 6 K-tiles of 32 tokens per work item
+  s = s > kmax ? kmax : s;
+  s = s > 64 ? 64 : s;
+  const int kps = cdiv(cdiv(tokens, s), BKH) * BKH;
+  s = cdiv(tokens, kps);                                       // the slabs the entry will use
+  const int items_min = getenv("DCLIP_F16X3_TOK_MIN") ? atoi(getenv("DCLIP_F16X3_TOK_MIN")) : 128;
+  return (long)cdiv(M, 256) * cdiv(N, 256) * s >= items_min ? s : 0;
+}
+
+// `splits` slabs of M N floats, one split included (the scaled reduce always runs)
+DCLIP_API size_t dclip_gemm_f16x3_wgrad_tokmajor_workspace(int M, int N, int splits) {
+  return M > 0 && N > 0 && splits > 0 ? (size_t)splits * M * N * sizeof(float) : 0;
+}
+
+DCLIP_API int dclip_gemm_f16x3_wgrad_tokmajor(const void* dY, const void* X, float* C, int M, int N, int tokens, int lddy, int ldx,
+                                              int ldc, int dy_hi, int dy_lo, int x_hi, int x_lo, const float* col_alpha,
+                                              const float* act_scale, int splits, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  const char* name = "gemm_f16x3_wgrad_tokmajor";
+  DCLIP_REQUIRE(dY && X && C && col_alpha && act_scale, "%s: null operand", name);
+  DCLIP_REQUIRE(M > 0 && N > 0 && tokens > 0 && tokens % BKH == 0 && M % 8 == 0 && N % 8 == 0 && splits >= 1 && splits <= 64,
+                "%s: M=%d N=%d (multiples of 8) tokens=%d (multiple of 64) splits=%d (1..64)", name, M, N, tokens, splits);
+  DCLIP_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0 && ldc % 4 == 0 && ldc >= N, "%s: leading dimensions", name);
+  DCLIP_REQUIRE(dy_hi >= 0 && dy_lo >= 0 && x_hi >= 0 && x_lo >= 0 && (dy_hi | dy_lo | x_hi | x_lo) % 8 == 0 &&
+                    (long)dy_hi + M <= lddy && (long)dy_lo + M <= lddy && (long)x_hi + N <= ldx && (long)x_lo + N <= ldx,
+                "%s: segments (offsets are multiples of 8, offset + width within the leading dimension)", name);
+  DCLIP_REQUIRE(((uintptr_t)dY | (uintptr_t)X | (uintptr_t)C | (uintptr_t)workspace) % 16 == 0 &&
+                    ((uintptr_t)col_alpha | (uintptr_t)act_scale) % 4 == 0, "%s: alignment", name);
+  // 32-bit byte offsets inside a work item's token range (the kernel's buffer loads)
+  DCLIP_REQUIRE((long)tokens * lddy * 2 < 0x7fffffffL && (long)tokens * ldx * 2 < 0x7fffffffL, "%s: operand too large", name);
+  const int kps = cdiv(cdiv(tokens, splits), BKH) * BKH;
+  const int s_eff = cdiv(tokens, kps);
+  const size_t need = (size_t)s_eff * M * N * sizeof(float);
+  if (!workspace || workspace_bytes < need) {
+    dclip_set_error("%s: needs %zu workspace bytes, got %zu", name, need, workspace_bytes);
+    return DCLIP_EWORKSPACE;
+  }
+  GemmBf16Params pb{(const __bf16*)dY, (const __bf16*)X, C, nullptr, nullptr, M, N, tokens, lddy, ldx, ldc, 0, 0, 0, 0, nullptr, kps,
+                    (float*)workspace};
+  pb.a_seg[0] = dy_hi, pb.a_seg[1] = dy_lo, pb.w_seg[0] = x_hi, pb.w_seg[1] = x_lo;
+  pb.tiles_m = cdiv(M, 256);
+  pb.tiles_n = cdiv(N, 256);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16IeeeT, true, false, false, false, false, true>), dim3(pb.tiles_m * pb.tiles_n, s_eff),
+                     dim3(512), 0, st, pb);
+  DCLIP_CHECK_LAUNCH_V(name, ".pp3_tok");
+  hipLaunchKernelGGL(splitk_reduce_scaled_bf16_kernel, dim3(grid_for((size_t)M * N / 4)), dim3(256), 0, st, (const float*)workspace, C,
+                     M, N, ldc, s_eff, col_alpha, act_scale);
+  DCLIP_CHECK_LAUNCH_V(name, ".pp3_tok.splitk_reduce");
   return DCLIP_OK;
 }
 

@@ -72,10 +72,21 @@ def _ln_operand(x, w, b, eps: float, save: bool, sp: Optional[Split16Layer], nam
     return ops.layernorm_fwd_f16x3_dev(x, w, b, eps, sp.act(name), save=save)
 
 
+def _fused_k(a3, w3) -> bool:
+    """Whether a split GEMM of a3 [M, 3K] with w3 [N, 3K] takes its fused twin: the switch is on and the plan says
+    so — exactly where the 3 K form takes the ping-pong kernel; elsewhere the call is what it was."""
+    k3 = min(a3.shape[1], w3.shape[1])
+    return bool(_SPLIT16_FUSED_K and k3 % 3 == 0 and ops.gemm_f16x3_plan(a3.shape[0], w3.shape[0], k3 // 3) > 0)
+
+
+def _gemm_f16_dev(a3, w3, alpha_ptr: int, **kw):
+    return (ops.gemm_f16x3_dev if _fused_k(a3, w3) else ops.gemm_f16_dev)(a3, w3, alpha_ptr, **kw)
+
+
 def _linear(a, w, sp: Optional[Split16Layer], name: str, bias, residual=None):
     if sp is None:
         return ops.gemm(a, w, ops.LAYOUT_NT, bias=bias, residual=residual)
-    return ops.gemm_f16_dev(a, sp.w[name], sp.alpha(name), bias=bias, residual=residual)
+    return _gemm_f16_dev(a, sp.w[name], sp.alpha(name), bias=bias, residual=residual)
 
 
 def _fc1_gelu(a, p: LayerParams, save: bool, sp: Optional[Split16Layer]):
@@ -87,10 +98,10 @@ def _fc1_gelu(a, p: LayerParams, save: bool, sp: Optional[Split16Layer]):
         return g, h, g
     g = torch.empty((M, I), dtype=torch.float32, device=a.device) if save else None
     if _VSPLIT16_FC1_EPI:
-        g3 = ops.gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), bias=p.fc1_b, gelu=True, split_out_scale_ptr=sp.act("g"), h32=h, g32=g)
+        g3 = _gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), bias=p.fc1_b, gelu=True, split_out_scale_ptr=sp.act("g"), h32=h, g32=g)
         return g3, h, g
     # two-launch form (bit-identical results; kept for the A/B of DESIGN.md §9d): h and g leave the GEMM, g is split after it
-    g = ops.gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), bias=p.fc1_b, gelu=True, h32=h)
+    g = _gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), bias=p.fc1_b, gelu=True, h32=h)
     return ops.split_f16x3_dev(g, sp.act("g")), h, g
 
 
@@ -143,7 +154,11 @@ def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Te
             dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=db)
         if need_b:
             gr[bkey] = db
-        gr[wkey] = ops.gemm_f16_wgrad_tokmajor_seg3(yc, x3, M, N, col_alpha, sp.act(act), out=_galloc(alloc, wkey, (M, N), dev))
+        out = _galloc(alloc, wkey, (M, N), dev)
+        if _SPLIT16_FUSED_TOK and ops.gemm_f16x3_wgrad_tokmajor_plan(M, N, dy.shape[0]) > 0:      # the fused twin (§9h)
+            gr[wkey] = ops.gemm_f16x3_wgrad_tokmajor(yc, x3, M, N, col_alpha, sp.act(act), out=out)
+        else:
+            gr[wkey] = ops.gemm_f16_wgrad_tokmajor_seg3(yc, x3, M, N, col_alpha, sp.act(act), out=out)
         return dy3, row_alpha
     if need_w and need_b:
         gr[bkey] = _galloc(alloc, bkey, (dy.shape[1],), dev)
@@ -204,9 +219,15 @@ def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None, ou
         return ops.gemm(dy, w, ops.LAYOUT_NN, aux=aux, epilogue=ops.EPI_DGELU)
     dy3, row_alpha = rows if rows is not None else ops.split_f16x3_rows(dy)
     wt = sp.wt[name]
-    st = _with_stats(out_stats, ops.gemm_f16_rows_stats_plan(dy3.shape[0], wt.shape[0], min(dy3.shape[1], wt.shape[1]))
-                     if out_stats else 0, wt.shape[0], dy3.device)
-    dx = ops.gemm_f16_rows_dev(dy3, wt, sp.walpha(name), row_alpha, dgelu_h=aux, stats=st)
+    k3 = min(dy3.shape[1], wt.shape[1])
+    if _fused_k(dy3, wt):      # the fused twin (§9h); its statistics plan is the unfused one's wherever it is taken
+        st = _with_stats(out_stats, ops.gemm_f16x3_rows_stats_plan(dy3.shape[0], wt.shape[0], k3 // 3) if out_stats else 0, wt.shape[0],
+                         dy3.device)
+        dx = ops.gemm_f16x3_rows_dev(dy3, wt, sp.walpha(name), row_alpha, dgelu_h=aux, stats=st)
+    else:
+        st = _with_stats(out_stats, ops.gemm_f16_rows_stats_plan(dy3.shape[0], wt.shape[0], k3) if out_stats else 0, wt.shape[0],
+                         dy3.device)
+        dx = ops.gemm_f16_rows_dev(dy3, wt, sp.walpha(name), row_alpha, dgelu_h=aux, stats=st)
     if st is not None:
         dx.dystats = st
     return dx
@@ -1315,7 +1336,10 @@ def _split16_plan(p: TextParams, cache: dict):
 
 def _split16_gemm(a3, ent, short: str, akey: str, **kw):
     """epilogue(A W^T) from the split operands; alpha undoes the operand scales."""
-    return ops.gemm_f16(a3, ent["w"][short], alpha=2.0 ** -(ent["e"][akey] + ent["f"][short]), **kw)
+    alpha = 2.0 ** -(ent["e"][akey] + ent["f"][short])
+    if _fused_k(a3, ent["w"][short]):      # the fused twin (§9h)
+        return ops.gemm_f16x3(a3, ent["w"][short], alpha=alpha, **kw)
+    return ops.gemm_f16(a3, ent["w"][short], alpha=alpha, **kw)
 
 
 def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict):
@@ -1375,6 +1399,12 @@ _VSPLIT16_WGRAD = os.environ.get("DCLIP_VISION_SPLIT16_WGRAD", "1") != "0"
 # ... and the kernels that produce those dY leave the column partials, so that dY is read once; 0 = the
 # three-launch pass of §9f for every dY, the parent's launch list and outputs bit for bit
 _VSPLIT16_DYSTATS = os.environ.get("DCLIP_VISION_SPLIT16_DYSTATS", "1") != "0"
+# Every split GEMM above — both towers' forwards, the data and the weight gradients — on its fused twin, which stages the hi
+# pieces once, wherever that twin's plan takes the shape; 0 = the 3 K / three-segment entries everywhere, the
+# parent's launch list and outputs bit for bit.  "kmajor" / "tokmajor": one form alone (the A/B of §9h).
+_SPLIT16_FUSED = os.environ.get("DCLIP_SPLIT16_FUSED", "1")
+_SPLIT16_FUSED_K = _SPLIT16_FUSED not in ("0", "tokmajor")
+_SPLIT16_FUSED_TOK = _SPLIT16_FUSED not in ("0", "kmajor")
 
 
 def vision_split16_enabled() -> bool:

@@ -1527,6 +1527,168 @@ def gemm_f16_wgrad_tokmajor_seg3(dy: torch.Tensor, x: torch.Tensor, M: int, N: i
     return out
 
 
+# ------------------------------------------------------------------------------------------- fused split-fp16 GEMMs
+# The split GEMMs above with each of the four distinct pieces staged once (include/dclip_hip.h, "fused split-fp16 GEMMs"): the same
+# operands as they lie — a = [hi|lo|hi], w = [hi|hi|lo], dy = [hi|lo], x = [hi|lo|hi] — the same epilogues and outputs; the
+# duplicate third is not read.  The plans say where the step takes them.
+
+def gemm_f16x3_plan(M: int, N: int, K: int) -> int:
+    """1 where the step takes a fused K-major entry for logical K (where the 3 K form takes the ping-pong kernel), else 0."""
+    return int(_lib.load().dclip_gemm_f16x3_plan(M, N, K))
+
+
+def _x3_k(a: torch.Tensor, w: torch.Tensor, name: str):
+    _f16(a, "a"), _f16(w, "w")
+    M, lda = a.shape
+    N, ldw = w.shape
+    if min(lda, ldw) % 3:
+        raise ValueError(f"{name}: a / w are [rows, 3 K] splits")
+    K = min(lda, ldw) // 3
+    return M, N, K, lda, ldw
+
+
+def gemm_f16x3(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+               gelu: bool = False, out_f16: bool = False, alpha: float = 1.0, split_out_scale: Optional[float] = None,
+               segs=None) -> torch.Tensor:
+    """gemm_f16(alpha=..., split_out_scale=...) of a = [hi|lo|hi] [M, 3K] and w = [hi|hi|lo] [N, 3K] on the fused kernel.
+    `segs` = (a_hi, a_lo, w_hi, w_lo) column offsets, default (0, K, 0, 2K)."""
+    lib = _lib.load()
+    M, N, K, lda, ldw = _x3_k(a, w, "gemm_f16x3")
+    sg = (0, K, 0, 2 * K) if segs is None else tuple(int(v) for v in segs)
+    epi = 0
+    if bias is not None:
+        epi |= EPI_BIAS
+        if _f32(bias, "bias").numel() != N:
+            raise ValueError("gemm_f16x3: bias size")
+    if gelu:
+        epi |= EPI_GELU
+    if residual is not None:
+        epi |= EPI_RESIDUAL
+        if tuple(_f32(residual, "residual").shape) != (M, N):
+            raise ValueError("gemm_f16x3: residual shape")
+    if split_out_scale is not None:
+        if residual is not None or out_f16:
+            raise ValueError("gemm_f16x3: a split output takes bias / gelu only")
+        y3 = torch.empty((M, 3 * N), dtype=torch.float16, device=a.device)
+        _lib.check(lib.dclip_gemm_f16x3_scaled_split(a.data_ptr(), w.data_ptr(), y3.data_ptr(), _ptr(bias), M, N, K, lda, ldw, 3 * N,
+                                                     *sg, epi, float(alpha), float(split_out_scale), _stream()),
+                   "gemm_f16x3_scaled_split")
+        return y3
+    out = torch.empty((M, N), dtype=torch.float16 if out_f16 else torch.float32, device=a.device)
+    _lib.check(lib.dclip_gemm_f16x3_scaled(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual), M, N, K, lda, ldw,
+                                           N, *sg, epi, int(out_f16), float(alpha), _stream()), "gemm_f16x3_scaled")
+    return out
+
+
+def gemm_f16x3_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, *, bias: Optional[torch.Tensor] = None,
+                   residual: Optional[torch.Tensor] = None, gelu: bool = False, out_f16: bool = False,
+                   split_out_scale_ptr: Optional[int] = None, h32: Optional[torch.Tensor] = None,
+                   g32: Optional[torch.Tensor] = None, segs=None) -> torch.Tensor:
+    """gemm_f16_dev on the fused kernel: the same arguments and outputs."""
+    lib = _lib.load()
+    M, N, K, lda, ldw = _x3_k(a, w, "gemm_f16x3_dev")
+    sg = (0, K, 0, 2 * K) if segs is None else tuple(int(v) for v in segs)
+    epi = 0
+    if bias is not None:
+        epi |= EPI_BIAS
+        if _f32(bias, "bias").numel() != N:
+            raise ValueError("gemm_f16x3_dev: bias size")
+    if gelu:
+        epi |= EPI_GELU
+    if residual is not None:
+        epi |= EPI_RESIDUAL
+        if tuple(_f32(residual, "residual").shape) != (M, N):
+            raise ValueError("gemm_f16x3_dev: residual shape")
+    if split_out_scale_ptr is not None:
+        if residual is not None or out_f16:
+            raise ValueError("gemm_f16x3_dev: a split output takes bias / gelu only")
+        for t, nm in ((h32, "h32"), (g32, "g32")):
+            if t is not None and tuple(_f32(t, nm).shape) != (M, N):
+                raise ValueError(f"gemm_f16x3_dev: {nm} shape")
+        if h32 is not None and not gelu:
+            raise ValueError("gemm_f16x3_dev: h32 is the pre-activation of a gelu epilogue")
+        y3 = torch.empty((M, 3 * N), dtype=torch.float16, device=a.device)
+        _lib.check(lib.dclip_gemm_f16x3_scaled_split_dev(a.data_ptr(), w.data_ptr(), y3.data_ptr(), _ptr(bias), _ptr(h32), _ptr(g32), M,
+                                                         N, K, lda, ldw, 3 * N, *sg, epi, alpha_ptr, split_out_scale_ptr, _stream()),
+                   "gemm_f16x3_scaled_split_dev")
+        return y3
+    if g32 is not None:
+        raise ValueError("gemm_f16x3_dev: g32 goes with a split output")
+    out = torch.empty((M, N), dtype=torch.float16 if out_f16 else torch.float32, device=a.device)
+    if h32 is not None:      # fp32 result and fp32 pre-activation, no split
+        if not gelu or residual is not None or out_f16 or tuple(_f32(h32, "h32").shape) != (M, N) or N % 8:
+            raise ValueError("gemm_f16x3_dev: h32 [M, N] is the pre-activation of a bias / gelu epilogue with an fp32 result")
+        _lib.check(lib.dclip_gemm_f16x3_scaled_split_dev(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), h32.data_ptr(), None,
+                                                         M, N, K, lda, ldw, N, *sg, epi, alpha_ptr, None, _stream()),
+                   "gemm_f16x3_scaled_split_dev")
+        return out
+    _lib.check(lib.dclip_gemm_f16x3_scaled_dev(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual), M, N, K, lda,
+                                               ldw, N, *sg, epi, int(out_f16), alpha_ptr, _stream()), "gemm_f16x3_scaled_dev")
+    return out
+
+
+def gemm_f16x3_rows_stats_plan(M: int, N: int, K: int) -> int:
+    """Partial rows gemm_f16x3_rows_dev leaves with `stats` (ceil(M / 256)) where gemm_f16x3_plan holds for logical K, else 0."""
+    return int(_lib.load().dclip_gemm_f16x3_scaled_rows_stats_plan(M, N, K))
+
+
+def gemm_f16x3_rows_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, row_alpha: torch.Tensor,
+                        dgelu_h: Optional[torch.Tensor] = None, stats: Optional[ColStats] = None, segs=None) -> torch.Tensor:
+    """gemm_f16_rows_dev on the fused kernel; `stats` has ceil(M / 256) partial rows and N columns."""
+    lib = _lib.load()
+    M, N, K, lda, ldw = _x3_k(a, w, "gemm_f16x3_rows_dev")
+    sg = (0, K, 0, 2 * K) if segs is None else tuple(int(v) for v in segs)
+    if _f32(row_alpha, "row_alpha").numel() != M:
+        raise ValueError("gemm_f16x3_rows_dev: row_alpha size")
+    if dgelu_h is not None and tuple(_f32(dgelu_h, "dgelu_h").shape) != (M, N):
+        raise ValueError("gemm_f16x3_rows_dev: dgelu_h shape")
+    out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    epi = EPI_DGELU if dgelu_h is not None else 0
+    if stats is not None:
+        if (stats.P, stats.cols) != ((M + 255) // 256, N):
+            raise ValueError("gemm_f16x3_rows_dev: stats must have ceil(M / 256) rows and N columns")
+        _lib.check(lib.dclip_gemm_f16x3_scaled_rows_stats_dev(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(dgelu_h), M, N, K, lda,
+                                                              ldw, N, *sg, epi, alpha_ptr, row_alpha.data_ptr(),
+                                                              stats.pmax.data_ptr(), stats.psum.data_ptr(), _stream()),
+                   "gemm_f16x3_scaled_rows_stats_dev")
+        return out
+    _lib.check(lib.dclip_gemm_f16x3_scaled_rows_dev(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(dgelu_h), M, N, K, lda, ldw, N,
+                                                    *sg, epi, alpha_ptr, row_alpha.data_ptr(), _stream()),
+               "gemm_f16x3_scaled_rows_dev")
+    return out
+
+
+def gemm_f16x3_wgrad_tokmajor_plan(M: int, N: int, tokens: int) -> int:
+    """The split count gemm_f16x3_wgrad_tokmajor would take, 0 where the step keeps gemm_f16_wgrad_tokmajor_seg3 (or neither applies)."""
+    return int(_lib.load().dclip_gemm_f16x3_wgrad_tokmajor_plan(M, N, tokens))
+
+
+def gemm_f16x3_wgrad_tokmajor(dy: torch.Tensor, x: torch.Tensor, M: int, N: int, col_alpha: torch.Tensor, act_scale_ptr: int,
+                              segs=None, splits: Optional[int] = None,
+                              out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """gemm_f16_wgrad_tokmajor_seg3's dW on the fused kernel: hi.hi + lo.hi + hi.lo of dy = [hi|lo] and x = [hi|lo|..], `segs` =
+    (dy_hi, dy_lo, x_hi, x_lo) column offsets, default (0, M, 0, N).  None when the plan is 0 (and `splits` is left to it)."""
+    lib = _lib.load()
+    _f16(dy, "dy"), _f16(x, "x")
+    if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0]:
+        raise ValueError("gemm_f16x3_wgrad_tokmajor: dy / x are [tokens, ld] with the same token count")
+    tokens = dy.shape[0]
+    sg = (0, M, 0, N) if segs is None else tuple(int(v) for v in segs)
+    if splits is None:
+        splits = lib.dclip_gemm_f16x3_wgrad_tokmajor_plan(M, N, tokens)
+        if splits == 0:
+            return None
+    if _f32(col_alpha, "col_alpha").numel() != M:
+        raise ValueError("gemm_f16x3_wgrad_tokmajor: col_alpha size")
+    out = _out_f32(out, (M, N), dy.device, "gemm_f16x3_wgrad_tokmajor")
+    nbytes = lib.dclip_gemm_f16x3_wgrad_tokmajor_workspace(M, N, splits)
+    ws = _ws.get(nbytes, dy.device)
+    _lib.check(lib.dclip_gemm_f16x3_wgrad_tokmajor(dy.data_ptr(), x.data_ptr(), out.data_ptr(), M, N, tokens, dy.shape[1], x.shape[1],
+                                                   N, *sg, col_alpha.data_ptr(), act_scale_ptr, splits, _ptr(ws), nbytes, _stream()),
+               "gemm_f16x3_wgrad_tokmajor")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- fp16 training path
 # The bf16 training wrappers above with fp16 tensors (include/dclip_hip.h, "fp16 TRAINING path"): same shapes and limits,
 # IEEE rounding — a value beyond +-65504 becomes +-inf (the frozen fp16 wrappers above saturate), so that the overflow of a

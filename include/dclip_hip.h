@@ -714,6 +714,47 @@ int dclip_layernorm_bwd_stats(const float* dy, const float* x, const float* gamm
                               const float* dresidual, float* dx, float* dgamma, float* dbeta, void* pmax, float* psum, int rows, int D,
                               int accumulate_param_grads, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fused split-fp16 GEMMs: the three products A_hi W_hi + A_lo W_hi + A_hi W_lo of a split GEMM out of ONE
+ * staging of the four distinct pieces, where the entries above contract K' = 3 K columns (or three token-major segments) and
+ * stage the hi pieces twice.  Each K-major entry is the twin of the entry named after "f16x3_": the same epilogues, scales and
+ * outputs, with K the LOGICAL contraction length (a multiple of 32) and four column offsets, multiples of 8 with offset + K within
+ * the leading dimension: A_hi / A_lo = columns a_hi.. / a_lo.. of A, W_hi / W_lo = columns w_hi.. / w_lo.. of W ([hi|lo|hi] with
+ * [hi|hi|lo]: 0, K, 0, 2 K).  No other column is read.  The ping-pong kernel only, at any M and N; the sum is accumulated in
+ * another order than the 3 K form's, so the two agree to fp32 rounding and are not bit-equal.
+ *   gemm_f16x3_plan          1 exactly where the 3 K form takes the ping-pong kernel (the step then takes the twin), else 0;
+ *                            also 0 below DCLIP_F16X3_MIN tiles of 256 x 256 (default 128, the dispatcher's default; read per call).
+ *   gemm_f16x3_scaled_rows_stats_plan   the partial rows, ceil(M / 256), where gemm_f16x3_plan is 1, else 0.
+ *   gemm_f16x3_wgrad_tokmajor   gemm_f16_wgrad_tokmajor_seg3 with the segments dY_hi^T X_hi + dY_lo^T X_hi + dY_hi^T X_lo: a work
+ *                            item owns a token range (whole 64-token units) and does all three; `splits` fp32 slabs
+ *                            (_workspace(M, N, splits) bytes, one split included), the same fixed-order scaled reduce.  _plan = the split
+ *                            count, 0 where the form does not apply or would start fewer than 128 work items
+ *                            (DCLIP_F16X3_TOK_MIN, read per call). */
+int dclip_gemm_f16x3_plan(int M, int N, int K);
+int dclip_gemm_f16x3_scaled(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
+                            int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue, int out_f16, float alpha,
+                            void* stream);
+int dclip_gemm_f16x3_scaled_split(const void* A, const void* W, void* C, const float* bias, int M, int N, int K, int lda, int ldw,
+                                  int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue, float alpha, float out_scale,
+                                  void* stream);
+int dclip_gemm_f16x3_scaled_dev(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
+                                int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue, int out_f16,
+                                const float* alpha, void* stream);
+int dclip_gemm_f16x3_scaled_split_dev(const void* A, const void* W, void* C, const float* bias, float* h32, float* g32, int M, int N,
+                                      int K, int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue,
+                                      const float* alpha, const float* out_scale, void* stream);
+int dclip_gemm_f16x3_scaled_rows_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K, int lda, int ldw,
+                                     int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue, const float* alpha,
+                                     const float* row_alpha, void* stream);
+int dclip_gemm_f16x3_scaled_rows_stats_plan(int M, int N, int K);
+int dclip_gemm_f16x3_scaled_rows_stats_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K, int lda,
+                                           int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue, const float* alpha,
+                                           const float* row_alpha, void* pmax, float* psum, void* stream);
+int dclip_gemm_f16x3_wgrad_tokmajor_plan(int M, int N, int tokens);
+size_t dclip_gemm_f16x3_wgrad_tokmajor_workspace(int M, int N, int splits);
+int dclip_gemm_f16x3_wgrad_tokmajor(const void* dY, const void* X, float* C, int M, int N, int tokens, int lddy, int ldx, int ldc,
+                                    int dy_hi, int dy_lo, int x_hi, int x_lo, const float* col_alpha, const float* act_scale,
+                                    int splits, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * fp16 TRAINING path (opt-in student_precision="fp16" / get_image_features(precision="fp16-mixed")): fp16
  * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
