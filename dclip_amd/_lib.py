@@ -156,6 +156,7 @@ SIGNATURES = {
     "dclip_layernorm_bwd_stats_plan": (I, [I, I]),
     "dclip_layernorm_bwd_stats": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, Z, P]),
     "dclip_gemm_f16x3_plan": (I, [I, I, I]),
+    "dclip_gemm_f16x3_tile_rows": (I, [I, I, I, I, I]),
     "dclip_gemm_f16x3_scaled": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, P]),
     "dclip_gemm_f16x3_scaled_split": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, F, P]),
     "dclip_gemm_f16x3_scaled_dev": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P]),

@@ -384,10 +384,13 @@ int launch_reg(const GemmBf16Params& p, size_t lds, hipStream_t st) {
 // stored.  A thread owns 4 columns and walks 32 rows of the tile: 4 maxima of the bit patterns of |v| and 4 fp32 sums in row
 // order; after the last pass the 8 waves put them into the dead LDS and threads 0..255 fold them in wave order into partial
 // row m0 / 256 of p.pmax / p.psum.  Rows >= M and columns >= N contribute nothing and write nothing.
-template <class T, int KIND, bool OUT16, bool DEV = false, bool ROWS = false, bool STATS = false>
-__device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4 (&acc)[8][4], float* ct, int m0, int n0,
+// BM (256 or 192): the tile height.  A pass is one wave row of WM = BM / 2 rows, a thread walks WM / 8 of them and
+// the wave row stages its BM / 32 accumulator row blocks; every statement applied to a value is the same at both heights.
+template <class T, int KIND, bool OUT16, bool DEV = false, bool ROWS = false, bool STATS = false, int BM = 256>
+__device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4 (&acc)[BM / 32][4], float* ct, int m0, int n0,
                                             int tid, int wr, int wc, int quad, int l15) {
-  constexpr int BN = 256;
+  constexpr int BN = 256, WM = BM / 2, NQ = WM / 8;
+  static_assert(BM == 256 || (BM == 192 && !OUT16 && !STATS), "the 192-row tile has fp32 outputs and no statistics form");
   const int lc = (tid & 63) * 4, col = n0 + lc, lr0 = tid >> 6;
   const bool colok = col < p.N;                     // N % 4 == 0: a column group is inside or outside as a whole
   const int colc = colok ? col : 0;
@@ -403,27 +406,27 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
   }
 #pragma unroll
   for (int hm = 0; hm < 2; ++hm) {
-    const int rbase = m0 + hm * 128 + lr0;
-    f32x4 side[KIND == 3 || (ROWS && KIND == 2) ? 16 : 1];
-    u16x4 side16[KIND == 2 && !ROWS ? 16 : 1];
+    const int rbase = m0 + hm * WM + lr0;
+    f32x4 side[KIND == 3 || (ROWS && KIND == 2) ? NQ : 1];
+    u16x4 side16[KIND == 2 && !ROWS ? NQ : 1];
     if (ROWS && KIND == 2) {
 #pragma unroll
-      for (int q = 0; q < 16; ++q)
+      for (int q = 0; q < NQ; ++q)
         side[q] = *reinterpret_cast<const f32x4*>(p.aux32 + (size_t)min(rbase + 8 * q, p.M - 1) * p.ldc + colc);
     }
     if (KIND == 3) {
 #pragma unroll
-      for (int q = 0; q < 16; ++q)
+      for (int q = 0; q < NQ; ++q)
         side[q] = *reinterpret_cast<const f32x4*>(p.residual + (size_t)min(rbase + 8 * q, p.M - 1) * p.ldc + colc);
     }
     if (KIND == 2 && !ROWS) {
 #pragma unroll
-      for (int q = 0; q < 16; ++q)
+      for (int q = 0; q < NQ; ++q)
         side16[q] = *reinterpret_cast<const u16x4*>(p.aux + (size_t)min(rbase + 8 * q, p.M - 1) * p.ldc + colc);
     }
     if (wr == hm) {      // 16-byte granule g of row r is stored at g ^ (r & 7): the 8 rows of a ds_write_b128 lane group spread over 32 banks
 #pragma unroll
-      for (int i = 0; i < 8; ++i)
+      for (int i = 0; i < BM / 32; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           *reinterpret_cast<f32x4*>(ct + (16 * i + l15) * BN + (((16 * wc + 4 * j + quad) ^ (l15 & 7)) << 2)) = acc[i][j];
@@ -431,7 +434,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     PP_BARRIER();
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {
+    for (int q = 0; q < NQ; ++q) {
       const int row = rbase + 8 * q;
       f32x4 v = *reinterpret_cast<const f32x4*>(ct + (lr0 + 8 * q) * BN + (((tid & 63) ^ ((lr0 + 8 * q) & 7)) << 2));
       if (!ROWS) v = v * (DEV ? alpha_d : p.alpha) + bias4;   // ROWS: the kernel has scaled the accumulators, and there is no bias
@@ -471,7 +474,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
       }
       if (KIND == 3) v += side[q];
       if (!ok) continue;
-      if ((KIND == 0 || KIND == 1) && !OUT16 && p.out_scale != 0.f) {
+      if (BM == 256 && (KIND == 0 || KIND == 1) && !OUT16 && p.out_scale != 0.f) {   // (no split output at 192 rows)
         if (DEV && p.g32) *reinterpret_cast<f32x4*>(p.g32 + (size_t)row * p.N + col) = v;
         store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, DEV ? *p.out_scale_p : p.out_scale);
         continue;
@@ -624,16 +627,37 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 // (granules 4-7 / k-rows 32-63) their lo pieces, fetched from the column offsets a_seg / w_seg [0] (hi) and [1] (lo), and a
 // phase issues three products per accumulator (24 MFMAs) on the same 12 fragment reads and 2 DMA pieces.  p.K is the logical K
 // (a multiple of 32; the token-major form contracts whole 64-token units per split).  Same phases, barriers and counted waits.
-template <class T, bool TOK, bool DEV = false, bool ROWS = false, bool SEG = false, bool STATS = false, bool FUSED = false>
+// BM = 192 (K-major, FUSED, fp32 output): a 192 x 256 tile for the shapes whose 256-row tiles fill the chip only
+// to 0.6 — a third more workgroups in the same single round, each with three quarters of the MFMAs, A reads and A pieces.  The
+// wave tile is WM = 96 rows, a quadrant QM = 48 rows = IB = 3 row blocks (18 MFMAs per product and phase); the phases, the eight
+// barriers per K-tile and the stagger are those above.  The A rows lie at their natural index and the B rows from row BM on; all
+// fragment and piece row offsets stay multiples of 16 / 8, so both sides of the XOR swizzle hold as written.
+//   A pieces  A-half h is rows WM w + QM h + r, w in {0, 1}, r < 48: 12 pieces of 8 rows where the 256 form has 16.  Piece
+//        q = wave + 8 x covers w = q / 6, r = 8 (q % 6) .. for q < 12.  The choice taken for the remaining four: waves 4-7 still
+//        ISSUE their second piece, with every lane outside the buffer range (no memory request, zeros), into a 1-KiB-per-wave dump
+//        region behind the two buffers, inside the one LDS array and read by nobody.  So every wave issues two pieces per half,
+//        and the counted waits (vmcnt(6), the prologue's) mean what they mean above — no per-wave wait counts.
+//   RAW  unchanged: a wave's vmcnt(6) in phase 4 retires all of ITS pieces of tile kt+1 (dump pieces retire in order like any
+//        other), the barrier behind it publishes them, and the first read of kt+1 comes a phase later.
+//   WAR  unchanged in phases: A0 (96 rows: both wave rows' quadrant 0) is read in phase 1 and re-staged in phase 3, A1 read in 3
+//        and re-staged in phase 1 of the next tile, B1 2 -> 4, and B0 one phase after its read.  That last one is retired before
+//        phase 1's first barrier by counting the A reads issued BEHIND the four B reads: lgkmcnt(2 IB) — 6 here, 8 at 256 rows.
+//        The dump region has no reader, and its writers all write zeros.
+// No TOK / SEG / STATS / 16-bit or split output / persistent form at 192 rows: the host keeps those calls on 256.
+template <class T, bool TOK, bool DEV = false, bool ROWS = false, bool SEG = false, bool STATS = false, bool FUSED = false,
+          int BM = 256>
 __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   static_assert(!SEG || (TOK && !DEV && !ROWS), "the segmented form is token-major, split-K, fp32 slabs");
   static_assert(!FUSED || !SEG, "the fused form does all three products in one work item");
   constexpr int KT = FUSED ? BKH / 2 : BKH;   // logical k per K-tile
   static_assert(!STATS || (ROWS && !TOK), "the statistics form is the row-scaled dgrad");
+  static_assert(BM == 256 || (BM == 192 && FUSED && !TOK && !SEG && !STATS), "the 192-row tile is K-major, fused, no statistics");
   typedef typename T::x8 V8;
-  constexpr int BM = 256, BN = 256, ROW = BKH;
-  constexpr int BUF = (BM + BN) * ROW;   // bf16 elements per K-tile buffer: 256 A rows then 256 B rows of 128 bytes
-  __shared__ __attribute__((aligned(16))) unsigned char lds_raw[2 * BUF * 2];   // 128 KiB: the ONLY LDS object
+  constexpr int BN = 256, ROW = BKH;
+  constexpr int WM = BM / 2, QM = WM / 2, IB = QM / 16;   // wave tile rows, quadrant rows, 16-row blocks per quadrant
+  constexpr int BUF = (BM + BN) * ROW;   // bf16 elements per K-tile buffer: BM A rows then 256 B rows of 128 bytes
+  constexpr int DUMP = BM == 256 ? 0 : 8 * 1024;   // bytes behind the buffers for the pieces that fetch nothing (192 rows only)
+  __shared__ __attribute__((aligned(16))) unsigned char lds_raw[2 * BUF * 2 + DUMP];   // 128 KiB (120 KiB): the ONLY LDS object
   __bf16* lds = reinterpret_cast<__bf16*>(lds_raw);
 
   PP_STAMP(0);
@@ -700,7 +724,10 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
           a_voff[h][x] = ma < a_rows ? (tok * p.lda + p.a_seg[x] + ma) * 2 : 0x7fffffff;
           w_voff[h][x] = nb < w_rows ? (tok * p.ldw + p.w_seg[x] + nb) * 2 : 0x7fffffff;
         } else {
-          const int ra = 128 * x + 64 * h + 8 * wave + (lane >> 3), ga = (lane & 7) ^ ((ra >> 1) & 7);
+          // (192 rows: piece q = wave + 8 x is rows 96 (q / 6) + 48 h + 8 (q % 6) ..; q >= 12 fetches nothing, row 192 is past a_rows)
+          const int qa = wave + 8 * x;
+          const int ra = (BM == 256 ? 128 * x + 64 * h + 8 * wave : qa < 12 ? WM * (qa / 6) + QM * h + 8 * (qa % 6) : BM) + (lane >> 3);
+          const int ga = (lane & 7) ^ ((ra >> 1) & 7);
           a_voff[h][x] = ra < a_rows ? (ra * p.lda + (ga < 4 ? p.a_seg[0] : p.a_seg[1]) + (ga & 3) * 8) * 2 : 0x7fffffff;
           const int rb = 64 * (2 * x + (wave >> 2)) + 32 * h + 8 * (wave & 3) + (lane >> 3), gb = (lane & 7) ^ ((rb >> 1) & 7);
           w_voff[h][x] = rb < w_rows ? (rb * p.ldw + (gb < 4 ? p.w_seg[0] : p.w_seg[1]) + (gb & 3) * 8) * 2 : 0x7fffffff;
@@ -719,11 +746,19 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
       }
     }
   constexpr int HALF = 64 * 128;   // bf16 elements of a token-major half image (16 KiB): A0 | A1 | B0 | B1 per buffer
+  // 192 rows: LDS element offsets of this wave's two A pieces inside a half (scalars).  The second piece of waves 4-7 goes to the
+  // dump region whatever the buffer and the half: a192_in selects which.
+  const int a192_e0 = (WM * (wave / 6) + 8 * (wave % 6)) * ROW;
+  const bool a192_in = wave < 4;
+  const int a192_e1 = a192_in ? (WM + 8 * (wave + 2)) * ROW : 2 * BUF + wave * 512;
 #define PP_ISSUE_A(h, buf, kt)                                                                                          \
   do {                                                                                                                  \
     if (TOK) {                                                                                                          \
       dma16(a_rsrc, lds + (buf) * BUF + (h) * HALF + wave * 512, a_voff[h][0], (kt) * a_kstep);                         \
       dma16(a_rsrc, lds + (buf) * BUF + (h) * HALF + (wave + 8) * 512, a_voff[h][1], (kt) * a_kstep);                   \
+    } else if (BM == 192) {                                                                                             \
+      dma16(a_rsrc, lds + (buf) * BUF + QM * (h) * ROW + a192_e0, a_voff[h][0], (kt) * a_kstep);                        \
+      dma16(a_rsrc, lds + (a192_in ? (buf) * BUF + QM * (h) * ROW : 0) + a192_e1, a_voff[h][1], (kt) * a_kstep);        \
     } else {                                                                                                            \
       dma16(a_rsrc, lds + (buf) * BUF + (64 * (h) + 8 * wave) * ROW, a_voff[h][0], (kt) * a_kstep);                     \
       dma16(a_rsrc, lds + (buf) * BUF + (128 + 64 * (h) + 8 * wave) * ROW, a_voff[h][1], (kt) * a_kstep);               \
@@ -744,8 +779,8 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
 
   // fragment addresses.  K-major: row 16 blk + l15, k-step s: logical granule 4 s + quad, stored at granule ^ (l15 >> 1).
   const int sw = l15 >> 1;
-  const __bf16* pa0 = lds + (128 * wr + l15) * ROW + (((0 + quad) ^ sw) << 3);
-  const __bf16* pa1 = lds + (128 * wr + l15) * ROW + (((4 + quad) ^ sw) << 3);
+  const __bf16* pa0 = lds + (WM * wr + l15) * ROW + (((0 + quad) ^ sw) << 3);
+  const __bf16* pa1 = lds + (WM * wr + l15) * ROW + (((4 + quad) ^ sw) << 3);
   const __bf16* pb0 = lds + (BM + 64 * wc + l15) * ROW + (((0 + quad) ^ sw) << 3);
   const __bf16* pb1 = lds + (BM + 64 * wc + l15) * ROW + (((4 + quad) ^ sw) << 3);
   // Token-major: a lane of a 16-lane group addresses k-row 8 quad + (l15 >> 2) (+ 32 s + 4 u) at columns 4 (l15 & 3) .. of the
@@ -767,21 +802,21 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
     return __builtin_bit_cast(V8, s16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
   };
 
-  f32x4 acc[8][4];
+  f32x4 acc[2 * IB][4];
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
+  for (int i = 0; i < 2 * IB; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  V8 fa[4][2], fb0[2][2], fb1[2][2];
+  V8 fa[IB][2], fb0[2][2], fb1[2][2];
 
 #define PP_READ_A(qm, off)                                                                          \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                   \
+  _Pragma("unroll") for (int i = 0; i < IB; ++i) {                                                  \
     if (TOK) {                                                                                      \
       fa[i][0] = tr8((off) * 2 + (qm) * (HALF * 2) + ta[i]);                                        \
       fa[i][1] = tr8((off) * 2 + (qm) * (HALF * 2) + ta[i] + 32 * 256);                             \
     } else {                                                                                        \
-      fa[i][0] = *reinterpret_cast<const V8*>(pa0 + (off) + (64 * (qm) + 16 * i) * ROW);        \
-      fa[i][1] = *reinterpret_cast<const V8*>(pa1 + (off) + (64 * (qm) + 16 * i) * ROW);        \
+      fa[i][0] = *reinterpret_cast<const V8*>(pa0 + (off) + (QM * (qm) + 16 * i) * ROW);        \
+      fa[i][1] = *reinterpret_cast<const V8*>(pa1 + (off) + (QM * (qm) + 16 * i) * ROW);        \
     }                                                                                               \
   }
 #define PP_READ_B(fb, qn, off)                                                                      \
@@ -799,10 +834,10 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   do {                                                                                                              \
     __builtin_amdgcn_s_setprio(1);                                                                                  \
     _Pragma("unroll") for (int s = 0; s < (FUSED ? 3 : 2); ++s)                                                     \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
+    _Pragma("unroll") for (int i = 0; i < IB; ++i)                                                                  \
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                   \
-      acc[4 * (qm) + i][2 * (qn) + j] =                                                                             \
-          T::mfma16(fb[j][FUSED ? s >> 1 : s], fa[i][FUSED ? s & 1 : s], acc[4 * (qm) + i][2 * (qn) + j]);          \
+      acc[IB * (qm) + i][2 * (qn) + j] =                                                                            \
+          T::mfma16(fb[j][FUSED ? s >> 1 : s], fa[i][FUSED ? s & 1 : s], acc[IB * (qm) + i][2 * (qn) + j]);         \
     __builtin_amdgcn_s_setprio(0);                                                                                  \
   } while (0)
 
@@ -832,7 +867,9 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
     PP_READ_A(0, off);
     __builtin_amdgcn_sched_barrier(0);
     if (n1) PP_ISSUE_A(1, cur ^ 1, kt + 1);
-    if (!TOK) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");   // the B reads are done: their rows may be re-staged next phase
+    // the B reads are done (the 2 IB A reads behind them may be outstanding): their rows may be re-staged next phase
+    if (!TOK && BM == 256) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+    if (!TOK && BM == 192) asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
     PP_BARRIER();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
@@ -881,17 +918,17 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   float* ct = reinterpret_cast<float*>(lds_raw);
   if (ROWS) {             // row-scaled dgrad: fp32 output, no epilogue or DGELU on the fp32 h
     // both scales are applied to the accumulators HERE, in the order of the other kernels — (acc * alpha) * row_alpha — with
-    // the 8 row_alpha values of a lane fetched before any side operand: 16 more registers inside pp_epilogue would spill
+    // the 8 (6) row_alpha values of a lane fetched before any side operand: 16 more registers inside pp_epilogue would spill
     const float alpha_r = *p.alpha_p;
-    float ra[8];
+    float ra[2 * IB];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) ra[i] = p.row_alpha[min(m0 + 128 * wr + 16 * i + l15, p.M - 1)];
+    for (int i = 0; i < 2 * IB; ++i) ra[i] = p.row_alpha[min(m0 + WM * wr + 16 * i + l15, p.M - 1)];
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 2 * IB; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = (acc[i][j] * alpha_r) * ra[i];
-    if (kind == 2) pp_epilogue<T, 2, false, true, true, STATS>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
-    else pp_epilogue<T, 0, false, true, true, STATS>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    if (kind == 2) pp_epilogue<T, 2, false, true, true, STATS, BM>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else pp_epilogue<T, 0, false, true, true, STATS, BM>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
     return;
   }
   if (!DEV && p.slab) {   // split-K partial: raw accumulators into this split's [M][N] slab, the reduce kernel finishes
@@ -901,10 +938,15 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
     ps.epilogue = 0;
     ps.alpha = 1.f;
     ps.out_scale = 0.f;
-    pp_epilogue<T, 0, false, false>(ps, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    pp_epilogue<T, 0, false, false, false, false, BM>(ps, acc, ct, m0, n0, tid, wr, wc, quad, l15);
     return;
   }
-  if (p.out_bf16) {
+  if constexpr (BM == 192) {   // fp32 outputs only (host check)
+    if (kind == 0) pp_epilogue<T, 0, false, DEV, false, false, BM>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 1) pp_epilogue<T, 1, false, DEV, false, false, BM>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else if (kind == 2) pp_epilogue<T, 2, false, DEV, false, false, BM>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else pp_epilogue<T, 3, false, DEV, false, false, BM>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+  } else if (p.out_bf16) {
     unsigned short* ct16 = reinterpret_cast<unsigned short*>(lds_raw);
     if (kind == 0) pp_epilogue_b16<T, false, false, DEV>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
     else if (kind == 1 && p.aux) pp_epilogue_b16<T, true, true, DEV>(p, acc, ct16, m0, n0, tid, wr, wc, quad, l15);
@@ -1623,6 +1665,27 @@ DCLIP_API int dclip_gemm_f16_scaled_rows_stats_dev(const void* A, const void* W,
 namespace {
 struct Segs { int a_hi, a_lo, w_hi, w_lo; };
 
+// Tile height of a fused call: 192 rows where the 256-row tiles leave CUs idle and a third more, cheaper tiles still
+// fit the same number of rounds.  has192: the call's form has a 192-row instance (K-major fp32 output, no split output, no
+// statistics).  DCLIP_F16X3_BM192 (read per call): 0 never, 1 by the rule below (default), 2 wherever the instance exists (tests,
+// A/Bs).  The rule: at least DCLIP_F16X3_BM192_MIN 256-row tiles (default 128, a threshold of its own, read per call) and
+//     ceil(tiles192 / CUs) * r < ceil(tiles256 / CUs),   CUs = 256,
+// r = the cost of a 192-row tile relative to a 256-row one: kBm192CostPct / 100, the largest ratio measured on the flagship
+// step's seven single-round shapes rounded up — 0.84-0.85 at K >= 2048, 0.86-0.90 at K = 512 / 768, largest 0.903 (DESIGN.md §9i
+// has the table; the model said 0.80).  With it a round more never pays (3 r >= 2, 4 r >= 3), so the rule needs no K term.
+// The outputs are bit-equal at both heights.
+constexpr int kBm192CostPct = 91;
+int f16x3_tile_rows(int M, int N, bool has192) {
+  const int mode = getenv("DCLIP_F16X3_BM192") ? atoi(getenv("DCLIP_F16X3_BM192")) : 1;
+  if (!has192 || mode <= 0) return 256;
+  if (mode >= 2) return 192;
+  const int tiles_min = getenv("DCLIP_F16X3_BM192_MIN") ? atoi(getenv("DCLIP_F16X3_BM192_MIN")) : 128;
+  const long t256 = (long)cdiv(M, 256) * cdiv(N, 256), t192 = (long)cdiv(M, 192) * cdiv(N, 256);
+  if (t256 < tiles_min) return 256;
+  const long r256 = (t256 + 255) / 256, r192 = (t192 + 255) / 256;
+  return r192 * kBm192CostPct < r256 * 100 ? 192 : 256;
+}
+
 int gemm16x3(const char* name, const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
              int lda, int ldw, int ldc, Segs sg, int epilogue, int out_f16, void* stream, float alpha, float out_scale,
              const DevScales* dev) {
@@ -1645,12 +1708,24 @@ int gemm16x3(const char* name, const void* A, const void* W, void* C, const floa
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_RESIDUAL) || (residual && !out_f16), "%s: RESIDUAL needs an fp32 output", name);
   // 32-bit byte offsets inside a 256-row tile (the kernel's buffer loads)
   DCLIP_REQUIRE(256L * lda * 2 < 0x7fffffffL && 256L * ldw * 2 < 0x7fffffffL, "%s: leading dimension too large", name);
-  GemmBf16Params p{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_f16, cdiv(M, 256),
+  const bool has192 = !out_f16 && out_scale == 0.f && !(dev && dev->pmax);
+  const int bm = f16x3_tile_rows(M, N, has192);
+  GemmBf16Params p{(const __bf16*)A, (const __bf16*)W, C, bias, residual, M, N, K, lda, ldw, ldc, epilogue, out_f16, cdiv(M, bm),
                    cdiv(N, 256), nullptr, 0, nullptr, alpha, out_scale};
   set_dev(p, dev);
   p.a_seg[0] = sg.a_hi, p.a_seg[1] = sg.a_lo, p.w_seg[0] = sg.w_hi, p.w_seg[1] = sg.w_lo;
   const dim3 grid(p.tiles_m * p.tiles_n), block(512);
   hipStream_t st = (hipStream_t)stream;
+  if (bm == 192) {
+    if (p.row_alpha)
+      hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, true, true, false, false, true, 192>), grid, block, 0, st, p);
+    else if (p.alpha_p)
+      hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, true, false, false, false, true, 192>), grid, block, 0, st, p);
+    else
+      hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, false, false, false, false, true, 192>), grid, block, 0, st, p);
+    DCLIP_CHECK_LAUNCH_V(name, ".pp3_192");
+    return DCLIP_OK;
+  }
   if (p.row_alpha && p.pmax)
     hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, true, true, false, true, true>), grid, block, 0, st, p);
   else if (p.row_alpha)
@@ -1671,6 +1746,14 @@ DCLIP_API int dclip_gemm_f16x3_plan(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0 || !takes_pp(M, N, 3 * K)) return 0;
   const int tiles_min = getenv("DCLIP_F16X3_MIN") ? atoi(getenv("DCLIP_F16X3_MIN")) : 128;
   return (long)cdiv(M, 256) * cdiv(N, 256) >= tiles_min ? 1 : 0;
+}
+
+// The tile height a fused fp32-output call of this shape takes now (192 or 256): rows_form = the row-scaled entry, stats_form = its
+// statistics twin (always 256).  Split-output and 16-bit-output calls always take 256.
+DCLIP_API int dclip_gemm_f16x3_tile_rows(int M, int N, int K, int rows_form, int stats_form) {
+  (void)K, (void)rows_form;   // every fp32-output form has the 192-row instance; the rule has no K term
+  if (M <= 0 || N <= 0) return 256;
+  return f16x3_tile_rows(M, N, !stats_form);
 }
 
 DCLIP_API int dclip_gemm_f16x3_scaled(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N,

@@ -1537,6 +1537,11 @@ def gemm_f16x3_plan(M: int, N: int, K: int) -> int:
     return int(_lib.load().dclip_gemm_f16x3_plan(M, N, K))
 
 
+def gemm_f16x3_tile_rows(M: int, N: int, K: int, rows_form: bool = False, stats_form: bool = False) -> int:
+    """Tile height (192 or 256) a fused K-major fp32-output call of this shape takes now."""
+    return int(_lib.load().dclip_gemm_f16x3_tile_rows(M, N, K, int(rows_form), int(stats_form)))
+
+
 def _x3_k(a: torch.Tensor, w: torch.Tensor, name: str):
     _f16(a, "a"), _f16(w, "w")
     M, lda = a.shape

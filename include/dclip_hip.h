@@ -728,8 +728,15 @@ int dclip_layernorm_bwd_stats(const float* dy, const float* x, const float* gamm
  *                            item owns a token range (whole 64-token units) and does all three; `splits` fp32 slabs
  *                            (_workspace(M, N, splits) bytes, one split included), the same fixed-order scaled reduce.  _plan = the split
  *                            count, 0 where the form does not apply or would start fewer than 128 work items
- *                            (DCLIP_F16X3_TOK_MIN, read per call). */
+ *                            (DCLIP_F16X3_TOK_MIN, read per call).
+ *   gemm_f16x3_tile_rows     the tile height (192 or 256 rows x 256 columns) a K-major fp32-output call of this shape takes now
+ *                            (DESIGN.md §9i): 192 where the 256-row tiles leave CUs idle and the 192-row tiles fit the same number
+ *                            of rounds.  rows_form: the row-scaled entry; stats_form: its statistics twin, which has the 256-row
+ *                            tile only, as the split-output and 16-bit-output calls have.  DCLIP_F16X3_BM192 = 0 never / 1 by the
+ *                            rule (default) / 2 wherever the form has the tile; DCLIP_F16X3_BM192_MIN (default 128 tiles of 256 x
+ *                            256), both read per call.  The outputs are bit-equal at both heights. */
 int dclip_gemm_f16x3_plan(int M, int N, int K);
+int dclip_gemm_f16x3_tile_rows(int M, int N, int K, int rows_form, int stats_form);
 int dclip_gemm_f16x3_scaled(const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
                             int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue, int out_f16, float alpha,
                             void* stream);
