@@ -167,6 +167,14 @@ SIGNATURES = {
     "dclip_gemm_f16x3_wgrad_tokmajor_plan": (I, [I, I, I]),
     "dclip_gemm_f16x3_wgrad_tokmajor_workspace": (Z, [I, I, I]),
     "dclip_gemm_f16x3_wgrad_tokmajor": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, P, P, I, P, Z, P]),
+    "dclip_split_f32_f16x2": (I, [P, P, I, I, I, I, F, P, P]),
+    "dclip_quick_gelu_f32": (I, [P, P, Z, P]),
+    "dclip_layernorm_fwd_f16x2": (I, [P, P, P, P, P, P, P, I, I, F, F, P, P]),
+    "dclip_split_f32_f16x2_rows": (I, [P, P, P, I, I, I, P]),
+    "dclip_split_f32_f16x2_rows_colstats": (I, [P, P, P, P, P, P, P, I, I, I, P, Z, P]),
+    "dclip_split_f32_f16x2_rows_cols_stats": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "dclip_gemm_f16x3_scaled_split2": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, F, P]),
+    "dclip_gemm_f16x3_scaled_split2_dev": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P, P]),
     "dclip_gemm_f16_wgrad_tokmajor_seg3_plan": (I, [I, I, I]),
     "dclip_gemm_f16_wgrad_tokmajor_seg3": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, Z, P]),
     "dclip_gemm_f16_ex": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),

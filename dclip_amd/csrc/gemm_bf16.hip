@@ -81,6 +81,8 @@ __device__ __forceinline__ float dev_out_scale(const GemmBf16Params& p) { return
 // Split-output store (split16.hip has the stand-alone kernel): v = the final fp32 results of 4 consecutive columns, c = their
 // place in the first third of the row; hi = fp16(v s), lo = fp16(v s - hi), written as [hi | lo | hi], N columns apart.  v is
 // pinned in registers first: it is the value the fp32 epilogue would have stored, rounded to fp32 BEFORE the conversion.
+// P = 2: the two-piece form [hi | lo], the duplicate third not stored.
+template <int P = 3>
 __device__ __forceinline__ void store_split4(unsigned short* c, int N, f32x4 v, float s) {
   u16x4 hi, lo;
 #pragma unroll
@@ -96,7 +98,7 @@ __device__ __forceinline__ void store_split4(unsigned short* c, int N, f32x4 v, 
   }
   *reinterpret_cast<u16x4*>(c) = hi;
   *reinterpret_cast<u16x4*>(c + N) = lo;
-  *reinterpret_cast<u16x4*>(c + 2 * N) = hi;
+  if (P == 3) *reinterpret_cast<u16x4*>(c + 2 * N) = hi;
 }
 
 // 4 consecutive 16-bit values at p (8-byte aligned) -> 4 floats
@@ -386,7 +388,7 @@ int launch_reg(const GemmBf16Params& p, size_t lds, hipStream_t st) {
 // row m0 / 256 of p.pmax / p.psum.  Rows >= M and columns >= N contribute nothing and write nothing.
 // BM (256 or 192): the tile height.  A pass is one wave row of WM = BM / 2 rows, a thread walks WM / 8 of them and
 // the wave row stages its BM / 32 accumulator row blocks; every statement applied to a value is the same at both heights.
-template <class T, int KIND, bool OUT16, bool DEV = false, bool ROWS = false, bool STATS = false, int BM = 256>
+template <class T, int KIND, bool OUT16, bool DEV = false, bool ROWS = false, bool STATS = false, int BM = 256, int PIECES = 3>
 __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4 (&acc)[BM / 32][4], float* ct, int m0, int n0,
                                             int tid, int wr, int wc, int quad, int l15) {
   constexpr int BN = 256, WM = BM / 2, NQ = WM / 8;
@@ -476,7 +478,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmBf16Params& p, const f32x4
       if (!ok) continue;
       if (BM == 256 && (KIND == 0 || KIND == 1) && !OUT16 && p.out_scale != 0.f) {   // (no split output at 192 rows)
         if (DEV && p.g32) *reinterpret_cast<f32x4*>(p.g32 + (size_t)row * p.N + col) = v;
-        store_split4(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, DEV ? *p.out_scale_p : p.out_scale);
+        store_split4<PIECES>(reinterpret_cast<unsigned short*>(p.C) + off, p.N, v, DEV ? *p.out_scale_p : p.out_scale);
         continue;
       }
       if (OUT16) {
@@ -644,9 +646,12 @@ __device__ __forceinline__ void pp_epilogue_b16(const GemmBf16Params& p, const f
 //        phase 1's first barrier by counting the A reads issued BEHIND the four B reads: lgkmcnt(2 IB) — 6 here, 8 at 256 rows.
 //        The dump region has no reader, and its writers all write zeros.
 // No TOK / SEG / STATS / 16-bit or split output / persistent form at 192 rows: the host keeps those calls on 256.
+// PIECES = 2: the fused K-major split-output call whose C is [hi | lo], ldc >= 2 N — the epilogue's third store left
+// out, nothing else; an instance of its own (BIAS / BIAS | GELU only), so that the three-piece instances stay what they were.
 template <class T, bool TOK, bool DEV = false, bool ROWS = false, bool SEG = false, bool STATS = false, bool FUSED = false,
-          int BM = 256>
+          int BM = 256, int PIECES = 3>
 __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
+  static_assert(PIECES == 3 || (PIECES == 2 && FUSED && !TOK && !ROWS && BM == 256), "two pieces: the fused split-output call");
   static_assert(!SEG || (TOK && !DEV && !ROWS), "the segmented form is token-major, split-K, fp32 slabs");
   static_assert(!FUSED || !SEG, "the fused form does all three products in one work item");
   constexpr int KT = FUSED ? BKH / 2 : BKH;   // logical k per K-tile
@@ -916,6 +921,11 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(GemmBf16Params p) {
   // ---- epilogue (pp_epilogue above), one instance per epilogue kind and output type
   const int kind = (p.epilogue & DCLIP_EPI_RESIDUAL) ? 3 : (p.epilogue & DCLIP_EPI_DGELU) ? 2 : (p.epilogue & DCLIP_EPI_GELU) ? 1 : 0;
   float* ct = reinterpret_cast<float*>(lds_raw);
+  if constexpr (PIECES == 2) {   // split output only (host check): BIAS or BIAS | GELU
+    if (kind == 1) pp_epilogue<T, 1, false, DEV, false, false, BM, 2>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    else pp_epilogue<T, 0, false, DEV, false, false, BM, 2>(p, acc, ct, m0, n0, tid, wr, wc, quad, l15);
+    return;
+  }
   if (ROWS) {             // row-scaled dgrad: fp32 output, no epilogue or DGELU on the fp32 h
     // both scales are applied to the accumulators HERE, in the order of the other kernels — (acc * alpha) * row_alpha — with
     // the 8 (6) row_alpha values of a lane fetched before any side operand: 16 more registers inside pp_epilogue would spill
@@ -1688,7 +1698,7 @@ int f16x3_tile_rows(int M, int N, bool has192) {
 
 int gemm16x3(const char* name, const void* A, const void* W, void* C, const float* bias, const float* residual, int M, int N, int K,
              int lda, int ldw, int ldc, Segs sg, int epilogue, int out_f16, void* stream, float alpha, float out_scale,
-             const DevScales* dev) {
+             const DevScales* dev, int pieces = 3) {
   DCLIP_REQUIRE(A && W && C, "%s: null operand", name);
   DCLIP_REQUIRE(M > 0 && N > 0 && K > 0 && K % 32 == 0, "%s: bad shape M=%d N=%d K=%d (K: the logical length, a multiple of 32)", name,
                 M, N, K);
@@ -1701,8 +1711,9 @@ int gemm16x3(const char* name, const void* A, const void* W, void* C, const floa
   DCLIP_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 == 0, "%s: operands must be 16-byte aligned", name);
   DCLIP_REQUIRE(!(epilogue & ~(DCLIP_EPI_BIAS | DCLIP_EPI_GELU | DCLIP_EPI_DGELU | DCLIP_EPI_RESIDUAL)),
                 "%s: unsupported epilogue bits", name);
-  DCLIP_REQUIRE(out_scale == 0.f || (!out_f16 && !(epilogue & (DCLIP_EPI_RESIDUAL | DCLIP_EPI_DGELU)) && (long)ldc >= 3L * N),
-                "%s: a split output takes BIAS | GELU only and ldc >= 3 N", name);
+  DCLIP_REQUIRE(out_scale == 0.f || (!out_f16 && !(epilogue & (DCLIP_EPI_RESIDUAL | DCLIP_EPI_DGELU)) && (long)ldc >= (long)pieces * N),
+                "%s: a split output takes BIAS | GELU only and ldc >= %d N", name, pieces);
+  DCLIP_REQUIRE(pieces == 3 || (pieces == 2 && out_scale != 0.f), "%s: two pieces go with a split output", name);
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_DGELU) || (dev && dev->aux32 && !(epilogue & DCLIP_EPI_GELU)), "%s: DGELU needs aux32", name);
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_BIAS) || bias, "%s: BIAS without bias", name);
   DCLIP_REQUIRE(!(epilogue & DCLIP_EPI_RESIDUAL) || (residual && !out_f16), "%s: RESIDUAL needs an fp32 output", name);
@@ -1724,6 +1735,14 @@ int gemm16x3(const char* name, const void* A, const void* W, void* C, const floa
     else
       hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, false, false, false, false, true, 192>), grid, block, 0, st, p);
     DCLIP_CHECK_LAUNCH_V(name, ".pp3_192");
+    return DCLIP_OK;
+  }
+  if (pieces == 2) {
+    if (p.alpha_p)
+      hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, true, false, false, false, true, 256, 2>), grid, block, 0, st, p);
+    else
+      hipLaunchKernelGGL((gemm_bf16_pp_kernel<F16T, false, false, false, false, false, true, 256, 2>), grid, block, 0, st, p);
+    DCLIP_CHECK_LAUNCH_V(name, ".pp3");
     return DCLIP_OK;
   }
   if (p.row_alpha && p.pmax)
@@ -1799,6 +1818,35 @@ DCLIP_API int dclip_gemm_f16x3_scaled_split_dev(const void* A, const void* W, vo
   const DevScales dev{alpha, out_scale, h32, g32};
   return gemm16x3("gemm_f16x3_scaled_split_dev", A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, Segs{a_hi, a_lo, w_hi, w_lo}, epilogue,
                   0, stream, 1.f, out_scale ? 1.f : 0.f, &dev);
+}
+
+// The two-piece forms of the two split-output entries above: C fp16 [M][ldc >= 2 N] = [hi | lo], bit-equal to the
+// first two pieces of theirs; nothing past column 2 N of a row is written; h32 / g32 as there.  out_scale is required.  The launch
+// is recorded under the three-piece twin's name (the same call site of the step).
+DCLIP_API int dclip_gemm_f16x3_scaled_split2(const void* A, const void* W, void* C, const float* bias, int M, int N, int K, int lda,
+                                             int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue, float alpha,
+                                             float out_scale, void* stream) {
+  DCLIP_REQUIRE(alpha == alpha && alpha - alpha == 0.f, "gemm_f16x3_scaled_split2: alpha must be finite");
+  DCLIP_REQUIRE(out_scale > 0.f && out_scale - out_scale == 0.f && (__builtin_bit_cast(unsigned int, out_scale) & 0x007fffffu) == 0,
+                "gemm_f16x3_scaled_split2: out_scale must be a power of two");
+  DCLIP_REQUIRE(ldc % 8 == 0, "gemm_f16x3_scaled_split2: ldc must be a multiple of 8");
+  DCLIP_REQUIRE(!(epilogue & ~(DCLIP_EPI_BIAS | DCLIP_EPI_GELU)), "gemm_f16x3_scaled_split2: the epilogue is BIAS | GELU");
+  return gemm16x3("gemm_f16x3_scaled_split", A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, Segs{a_hi, a_lo, w_hi, w_lo}, epilogue, 0,
+                  stream, alpha, out_scale, nullptr, 2);
+}
+
+DCLIP_API int dclip_gemm_f16x3_scaled_split2_dev(const void* A, const void* W, void* C, const float* bias, float* h32, float* g32,
+                                                 int M, int N, int K, int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo,
+                                                 int epilogue, const float* alpha, const float* out_scale, void* stream) {
+  DCLIP_REQUIRE(alpha && out_scale && ((uintptr_t)alpha | (uintptr_t)out_scale) % 4 == 0,
+                "gemm_f16x3_scaled_split2_dev: alpha / out_scale must be device pointers");
+  DCLIP_REQUIRE(ldc % 8 == 0, "gemm_f16x3_scaled_split2_dev: ldc must be a multiple of 8");
+  DCLIP_REQUIRE(((uintptr_t)h32 | (uintptr_t)g32) % 16 == 0, "gemm_f16x3_scaled_split2_dev: h32 / g32 must be 16-byte aligned");
+  DCLIP_REQUIRE(!h32 || (epilogue & DCLIP_EPI_GELU), "gemm_f16x3_scaled_split2_dev: h32 is the pre-activation of a GELU epilogue");
+  DCLIP_REQUIRE(!(epilogue & ~(DCLIP_EPI_BIAS | DCLIP_EPI_GELU)), "gemm_f16x3_scaled_split2_dev: the epilogue is BIAS | GELU");
+  const DevScales dev{alpha, out_scale, h32, g32};
+  return gemm16x3("gemm_f16x3_scaled_split_dev", A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, Segs{a_hi, a_lo, w_hi, w_lo}, epilogue,
+                  0, stream, 1.f, 1.f, &dev, 2);
 }
 
 DCLIP_API int dclip_gemm_f16x3_scaled_rows_dev(const void* A, const void* W, float* C, const float* aux32, int M, int N, int K, int lda,

@@ -31,7 +31,8 @@ __device__ __forceinline__ void split1(float v, unsigned short& hi, unsigned sho
   lo = __builtin_bit_cast(unsigned short, l);
 }
 
-// 8 columns per thread: two 16-byte loads, three 16-byte stores
+// 8 columns per thread: two 16-byte loads, three 16-byte stores.  ORDER 2: the two-piece form [hi | lo], the third
+// store — the duplicate hi no fused GEMM reads — left out; ldy >= 2 cols there.
 template <int ORDER>
 __global__ void __launch_bounds__(256) split_f16x3_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, int rows,
                                                           int cols, int ldx, int ldy, float scale_v,
@@ -54,8 +55,8 @@ __global__ void __launch_bounds__(256) split_f16x3_kernel(const float* __restric
     }
     unsigned short* yr = y + r * ldy + c;
     *reinterpret_cast<u16x8*>(yr) = hi;
-    *reinterpret_cast<u16x8*>(yr + cols) = ORDER == 0 ? lo : hi;
-    *reinterpret_cast<u16x8*>(yr + 2 * cols) = ORDER == 0 ? hi : lo;
+    *reinterpret_cast<u16x8*>(yr + cols) = ORDER == 1 ? hi : lo;
+    if (ORDER != 2) *reinterpret_cast<u16x8*>(yr + 2 * cols) = ORDER == 0 ? hi : lo;
   }
 }
 
@@ -99,6 +100,8 @@ __device__ __forceinline__ int row_exp(unsigned rbits) {
   return e < -100 ? -100 : (e > 100 ? 100 : e);
 }
 
+// P = pieces per row: 3 = [hi|lo|hi], 2 = [hi|lo] (the same two pieces, the duplicate third not stored)
+template <int P = 3>
 __device__ __forceinline__ void split_store8(unsigned short* yr, int cols, const f32x4& a, const f32x4& b, float scale) {
   u16x8 hi, lo;
 #pragma unroll
@@ -110,10 +113,10 @@ __device__ __forceinline__ void split_store8(unsigned short* yr, int cols, const
   }
   *reinterpret_cast<u16x8*>(yr) = hi;
   *reinterpret_cast<u16x8*>(yr + cols) = lo;
-  *reinterpret_cast<u16x8*>(yr + 2 * cols) = hi;
+  if (P == 3) *reinterpret_cast<u16x8*>(yr + 2 * cols) = hi;
 }
 
-template <int NC>
+template <int NC, int P = 3>
 __global__ void __launch_bounds__(256) split_rows_f16x3_kernel(const float* __restrict__ x, unsigned short* __restrict__ y,
                                                                float* __restrict__ row_alpha, int rows, int cols, int ldx) {
   const int lane = threadIdx.x & 63;
@@ -121,7 +124,7 @@ __global__ void __launch_bounds__(256) split_rows_f16x3_kernel(const float* __re
   if (row >= rows) return;
   const int c8 = cols >> 3;
   const float* xr = x + (size_t)row * ldx;
-  unsigned short* yr = y + (size_t)row * 3 * cols;
+  unsigned short* yr = y + (size_t)row * P * cols;
   unsigned m = 0u;
   if (NC > 0) {
     f32x4 a[NC > 0 ? NC : 1], b[NC > 0 ? NC : 1];
@@ -139,7 +142,7 @@ __global__ void __launch_bounds__(256) split_rows_f16x3_kernel(const float* __re
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const int i = lane + 64 * c;
-      if (i < c8) split_store8(yr + i * 8, cols, a[c], b[c], scale);
+      if (i < c8) split_store8<P>(yr + i * 8, cols, a[c], b[c], scale);
     }
   } else {
     for (int i = lane; i < c8; i += 64)
@@ -148,7 +151,7 @@ __global__ void __launch_bounds__(256) split_rows_f16x3_kernel(const float* __re
     const float scale = pow2f(e);
     if (lane == 0) row_alpha[row] = pow2f(-e);
     for (int i = lane; i < c8; i += 64)
-      split_store8(yr + i * 8, cols, *reinterpret_cast<const f32x4*>(xr + i * 8), *reinterpret_cast<const f32x4*>(xr + i * 8 + 4),
+      split_store8<P>(yr + i * 8, cols, *reinterpret_cast<const f32x4*>(xr + i * 8), *reinterpret_cast<const f32x4*>(xr + i * 8 + 4),
                    scale);
   }
 }
@@ -181,7 +184,7 @@ __device__ __forceinline__ void colstat8(unsigned* mx, float* sm, const f32x4& a
   }
 }
 
-template <int NC>
+template <int NC, int P = 3>
 __global__ void __launch_bounds__(256) split_rows_colstats_f16x3_kernel(const float* __restrict__ x, unsigned short* __restrict__ y,
                                                                         float* __restrict__ row_alpha, unsigned* __restrict__ pmax,
                                                                         float* __restrict__ psum, int rows, int cols, int ldx) {
@@ -200,7 +203,7 @@ __global__ void __launch_bounds__(256) split_rows_colstats_f16x3_kernel(const fl
       for (int e = 0; e < 8; ++e) cm[c][e] = 0u, cs[c][e] = 0.f;
     for (int row = w; row < rows; row += W) {
       const float* xr = x + (size_t)row * ldx;
-      unsigned short* yr = y + (size_t)row * 3 * cols;
+      unsigned short* yr = y + (size_t)row * P * cols;
       f32x4 a[NC > 0 ? NC : 1], b[NC > 0 ? NC : 1];
       unsigned m = 0u;
 #pragma unroll
@@ -217,7 +220,7 @@ __global__ void __launch_bounds__(256) split_rows_colstats_f16x3_kernel(const fl
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
         const int i = lane + 64 * c;
-        if (i < c8) split_store8(yr + i * 8, cols, a[c], b[c], scale);
+        if (i < c8) split_store8<P>(yr + i * 8, cols, a[c], b[c], scale);
         colstat8(cm[c], cs[c], a[c], b[c]);              // (a chunk past the row holds chunk 0 again: never stored below)
       }
     }
@@ -237,7 +240,7 @@ __global__ void __launch_bounds__(256) split_rows_colstats_f16x3_kernel(const fl
     bool first = true;
     for (int row = w; row < rows; row += W, first = false) {
       const float* xr = x + (size_t)row * ldx;
-      unsigned short* yr = y + (size_t)row * 3 * cols;
+      unsigned short* yr = y + (size_t)row * P * cols;
       unsigned m = 0u;
       for (int i = lane; i < c8; i += 64)
         m = absmax8(m, *reinterpret_cast<const f32x4*>(xr + i * 8), *reinterpret_cast<const f32x4*>(xr + i * 8 + 4));
@@ -246,7 +249,7 @@ __global__ void __launch_bounds__(256) split_rows_colstats_f16x3_kernel(const fl
       if (lane == 0) row_alpha[row] = pow2f(-e);
       for (int i = lane; i < c8; i += 64) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(xr + i * 8), b = *reinterpret_cast<const f32x4*>(xr + i * 8 + 4);
-        split_store8(yr + i * 8, cols, a, b, scale);
+        split_store8<P>(yr + i * 8, cols, a, b, scale);
         unsigned cm[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
         float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (!first) {
@@ -347,6 +350,7 @@ __device__ __forceinline__ void split_cols_store8(unsigned short* yr, int cols, 
 
 // split_store8 with non-temporal stores: the row split is read only by the data-gradient GEMM, which runs AFTER the weight
 // gradient has read yc, so it should not push yc out of the cache on its way to memory
+template <int P = 3>
 __device__ __forceinline__ void split_store8_nt(unsigned short* yr, int cols, const f32x4& a, const f32x4& b, float scale) {
   u16x8 hi, lo;
 #pragma unroll
@@ -358,10 +362,10 @@ __device__ __forceinline__ void split_store8_nt(unsigned short* yr, int cols, co
   }
   __builtin_nontemporal_store(hi, reinterpret_cast<u16x8*>(yr));
   __builtin_nontemporal_store(lo, reinterpret_cast<u16x8*>(yr + cols));
-  __builtin_nontemporal_store(hi, reinterpret_cast<u16x8*>(yr + 2 * cols));
+  if (P == 3) __builtin_nontemporal_store(hi, reinterpret_cast<u16x8*>(yr + 2 * cols));
 }
 
-template <int NC>
+template <int NC, int P = 3>
 __global__ void __launch_bounds__(256) split_rows_cols_f16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y,
                                                                   float* __restrict__ row_alpha, const int* __restrict__ col_exp,
                                                                   unsigned short* __restrict__ yc, int rows, int cols, int ldx) {
@@ -370,7 +374,7 @@ __global__ void __launch_bounds__(256) split_rows_cols_f16_kernel(const float* _
   if (row >= rows) return;
   const int c8 = cols >> 3;
   const float* xr = x + (size_t)row * ldx;
-  unsigned short* yr = y + (size_t)row * 3 * cols;
+  unsigned short* yr = y + (size_t)row * P * cols;
   unsigned short* ycr = yc + (size_t)row * 2 * cols;
   unsigned m = 0u;
   if (NC > 0) {
@@ -390,7 +394,7 @@ __global__ void __launch_bounds__(256) split_rows_cols_f16_kernel(const float* _
     for (int c = 0; c < NC; ++c) {
       const int i = lane + 64 * c;
       if (i < c8) {
-        split_store8_nt(yr + i * 8, cols, a[c], b[c], scale);
+        split_store8_nt<P>(yr + i * 8, cols, a[c], b[c], scale);
         split_cols_store8(ycr + i * 8, cols, a[c], b[c], col_exp + i * 8);
       }
     }
@@ -402,7 +406,7 @@ __global__ void __launch_bounds__(256) split_rows_cols_f16_kernel(const float* _
     if (lane == 0) row_alpha[row] = pow2f(-e);
     for (int i = lane; i < c8; i += 64) {
       const f32x4 a = *reinterpret_cast<const f32x4*>(xr + i * 8), b = *reinterpret_cast<const f32x4*>(xr + i * 8 + 4);
-      split_store8_nt(yr + i * 8, cols, a, b, scale);
+      split_store8_nt<P>(yr + i * 8, cols, a, b, scale);
       split_cols_store8(ycr + i * 8, cols, a, b, col_exp + i * 8);
     }
   }
@@ -412,7 +416,7 @@ __global__ void __launch_bounds__(256) split_rows_cols_f16_kernel(const float* _
 // statistics and the normalisation are that kernel's, statement for statement; the fp32 result is pinned in a register before
 // it is scaled and split, so that it is the value ln_fwd_kernel would have stored (no fusion of the affine step into the
 // conversion, which would round once instead of twice).
-template <int NC, bool EXACT>
+template <int NC, bool EXACT, int P = 3>
 __global__ void __launch_bounds__(256) ln_fwd_f16x3_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, unsigned short* __restrict__ y,
                                                            int rows, int D, float eps, float scale_v,
@@ -452,7 +456,7 @@ __global__ void __launch_bounds__(256) ln_fwd_f16x3_kernel(const float* __restri
     if (mean) mean[row] = mu;
     if (rstd) rstd[row] = rs;
   }
-  unsigned short* yr = y + (size_t)row * 3 * D;
+  unsigned short* yr = y + (size_t)row * P * D;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const int i = lane + 64 * c;
@@ -470,8 +474,19 @@ __global__ void __launch_bounds__(256) ln_fwd_f16x3_kernel(const float* __restri
       }
       *reinterpret_cast<u16x4*>(yr + i * 4) = hi;
       *reinterpret_cast<u16x4*>(yr + D + i * 4) = lo;
-      *reinterpret_cast<u16x4*>(yr + 2 * D + i * 4) = hi;
+      if (P == 3) *reinterpret_cast<u16x4*>(yr + 2 * D + i * 4) = hi;
     }
+  }
+}
+
+// g = quick_gelu(h), the statement of the GEMM epilogues (quick_gelu_f on the fp32 pre-activation they store as h32): the
+// rematerialisation of an fp32 g the forward did not keep.  4 values per thread.
+__global__ void __launch_bounds__(256) quick_gelu_kernel(const float* __restrict__ h, float* __restrict__ g, size_t n4) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    f32x4 v = reinterpret_cast<const f32x4*>(h)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
+    reinterpret_cast<f32x4*>(g)[i] = v;
   }
 }
 
@@ -712,13 +727,16 @@ int split_launch(const char* name, const float* x, void* y, int rows, int cols, 
   hipStream_t st = (hipStream_t)stream;
   if (order == 0)
     hipLaunchKernelGGL(split_f16x3_kernel<0>, grid, dim3(256), 0, st, x, (unsigned short*)y, rows, cols, ldx, ldy, scale, scale_p);
-  else
+  else if (order == 1)
     hipLaunchKernelGGL(split_f16x3_kernel<1>, grid, dim3(256), 0, st, x, (unsigned short*)y, rows, cols, ldx, ldy, scale, scale_p);
-  DCLIP_CHECK_LAUNCH_V(name, order == 0 ? ".act" : ".weight");
+  else
+    hipLaunchKernelGGL(split_f16x3_kernel<2>, grid, dim3(256), 0, st, x, (unsigned short*)y, rows, cols, ldx, ldy, scale, scale_p);
+  DCLIP_CHECK_LAUNCH_V(name, order == 1 ? ".weight" : ".act");
   return DCLIP_OK;
 }
 
-int split_rows_launch(const float* x, void* y, float* row_alpha, int rows, int cols, int ldx, void* stream) {
+int split_rows_launch(const char* name, const float* x, void* y, float* row_alpha, int rows, int cols, int ldx, int pieces,
+                      void* stream) {
   dim3 grid(cdiv(rows, 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
   unsigned short* yy = (unsigned short*)y;
@@ -726,7 +744,10 @@ int split_rows_launch(const float* x, void* y, float* row_alpha, int rows, int c
   const char* variant;
 #define SPLITROWS(NC)                                                                                               \
   do {                                                                                                              \
-    hipLaunchKernelGGL((split_rows_f16x3_kernel<NC>), grid, block, 0, st, x, yy, row_alpha, rows, cols, ldx);      \
+    if (pieces == 2)                                                                                                \
+      hipLaunchKernelGGL((split_rows_f16x3_kernel<NC, 2>), grid, block, 0, st, x, yy, row_alpha, rows, cols, ldx); \
+    else                                                                                                            \
+      hipLaunchKernelGGL((split_rows_f16x3_kernel<NC>), grid, block, 0, st, x, yy, row_alpha, rows, cols, ldx);    \
     variant = (NC) ? ".regs.nc" #NC : ".cached";                                                                    \
   } while (0)
   if (nc <= 1) SPLITROWS(1);
@@ -737,12 +758,12 @@ int split_rows_launch(const float* x, void* y, float* row_alpha, int rows, int c
   else if (nc == 6) SPLITROWS(6);
   else SPLITROWS(0);
 #undef SPLITROWS
-  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows", variant);
+  DCLIP_CHECK_LAUNCH_V(name, variant);
   return DCLIP_OK;
 }
 
-int split_rows_colstats_launch(const float* x, void* y, float* row_alpha, unsigned* pmax, float* psum, int rows, int cols, int ldx,
-                                void* stream) {
+int split_rows_colstats_launch(const char* name, const float* x, void* y, float* row_alpha, unsigned* pmax, float* psum, int rows,
+                               int cols, int ldx, int pieces, void* stream) {
   dim3 grid(colstat_waves(rows) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
   unsigned short* yy = (unsigned short*)y;
@@ -750,8 +771,12 @@ int split_rows_colstats_launch(const float* x, void* y, float* row_alpha, unsign
   const char* variant;
 #define SPLITROWSC(NC)                                                                                                        \
   do {                                                                                                                        \
-    hipLaunchKernelGGL((split_rows_colstats_f16x3_kernel<NC>), grid, block, 0, st, x, yy, row_alpha, pmax, psum, rows, cols,  \
-                       ldx);                                                                                                  \
+    if (pieces == 2)                                                                                                          \
+      hipLaunchKernelGGL((split_rows_colstats_f16x3_kernel<NC, 2>), grid, block, 0, st, x, yy, row_alpha, pmax, psum, rows,   \
+                         cols, ldx);                                                                                          \
+    else                                                                                                                      \
+      hipLaunchKernelGGL((split_rows_colstats_f16x3_kernel<NC>), grid, block, 0, st, x, yy, row_alpha, pmax, psum, rows,      \
+                         cols, ldx);                                                                                          \
     variant = (NC) ? ".regs.nc" #NC : ".cached";                                                                              \
   } while (0)
   if (nc <= 1) SPLITROWSC(1);
@@ -762,13 +787,13 @@ int split_rows_colstats_launch(const float* x, void* y, float* row_alpha, unsign
   else if (nc == 6) SPLITROWSC(6);
   else SPLITROWSC(0);
 #undef SPLITROWSC
-  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_colstats", variant);
-  dclip_note_first_launch("split_f32_f16x3_rows_colstats", variant);   // .finish and .cols overwrite the name above
+  DCLIP_CHECK_LAUNCH_V(name, variant);
+  dclip_note_first_launch(name, variant);   // .finish and .cols overwrite the name above
   return DCLIP_OK;
 }
 
-int split_rows_cols_launch(const float* x, void* y, float* row_alpha, const int* col_exp, void* yc, int rows, int cols, int ldx,
-                           void* stream) {
+int split_rows_cols_launch(const char* name, const float* x, void* y, float* row_alpha, const int* col_exp, void* yc, int rows,
+                           int cols, int ldx, int pieces, void* stream) {
   dim3 grid(cdiv(rows, 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
   unsigned short *yy = (unsigned short*)y, *yyc = (unsigned short*)yc;
@@ -776,7 +801,10 @@ int split_rows_cols_launch(const float* x, void* y, float* row_alpha, const int*
   const char* variant;
 #define SPLITROWSCOLS(NC)                                                                                                          \
   do {                                                                                                                             \
-    hipLaunchKernelGGL((split_rows_cols_f16_kernel<NC>), grid, block, 0, st, x, yy, row_alpha, col_exp, yyc, rows, cols, ldx);     \
+    if (pieces == 2)                                                                                                               \
+      hipLaunchKernelGGL((split_rows_cols_f16_kernel<NC, 2>), grid, block, 0, st, x, yy, row_alpha, col_exp, yyc, rows, cols, ldx); \
+    else                                                                                                                           \
+      hipLaunchKernelGGL((split_rows_cols_f16_kernel<NC>), grid, block, 0, st, x, yy, row_alpha, col_exp, yyc, rows, cols, ldx);   \
     variant = (NC) ? ".regs.nc" #NC : ".cached";                                                                                   \
   } while (0)
   if (nc <= 1) SPLITROWSCOLS(1);
@@ -787,12 +815,12 @@ int split_rows_cols_launch(const float* x, void* y, float* row_alpha, const int*
   else if (nc == 6) SPLITROWSCOLS(6);
   else SPLITROWSCOLS(0);
 #undef SPLITROWSCOLS
-  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_cols_stats", variant);
+  DCLIP_CHECK_LAUNCH_V(name, variant);
   return DCLIP_OK;
 }
 
 int ln_launch(const char* name, const float* x, const float* gamma, const float* beta, void* y, int rows, int D, float eps,
-              float scale, const float* scale_p, float* y32, float* mean, float* rstd, void* stream) {
+              float scale, const float* scale_p, float* y32, float* mean, float* rstd, void* stream, int pieces = 3) {
   dim3 grid(cdiv(rows, 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
   const int nc = cdiv(D / 4, 64);
@@ -800,8 +828,12 @@ int ln_launch(const char* name, const float* x, const float* gamma, const float*
   const char* variant;
 #define LN16X3(NC, EX)                                                                                                      \
   do {                                                                                                                      \
-    hipLaunchKernelGGL((ln_fwd_f16x3_kernel<NC, EX>), grid, block, 0, st, x, gamma, beta, yy, rows, D, eps, scale, scale_p, \
-                       y32, mean, rstd);                                                                                    \
+    if (pieces == 2)                                                                                                        \
+      hipLaunchKernelGGL((ln_fwd_f16x3_kernel<NC, EX, 2>), grid, block, 0, st, x, gamma, beta, yy, rows, D, eps, scale,     \
+                         scale_p, y32, mean, rstd);                                                                         \
+    else                                                                                                                    \
+      hipLaunchKernelGGL((ln_fwd_f16x3_kernel<NC, EX>), grid, block, 0, st, x, gamma, beta, yy, rows, D, eps, scale,        \
+                         scale_p, y32, mean, rstd);                                                                         \
     variant = (EX) ? ".nc" #NC ".exact" : ".nc" #NC;                                                                        \
   } while (0)
   if (D == 512) LN16X3(2, true);
@@ -843,15 +875,44 @@ DCLIP_API int dclip_split_f32_f16x3_dev(const float* x, void* y, int rows, int c
   return split_launch("split_f32_f16x3_dev", x, y, rows, cols, ldx, ldy, 1.f, scale, order, stream);
 }
 
+// The two-piece form of the order-0 split: y [rows][ldy >= 2 cols] = [hi|lo], bit-equal to the first two pieces of
+// dclip_split_f32_f16x3(order 0) / _dev; nothing past column 2 cols of a row is written.  scale_dev (device, may be null) takes
+// the place of `scale` when given.
+DCLIP_API int dclip_split_f32_f16x2(const float* x, void* y, int rows, int cols, int ldx, int ldy, float scale, const float* scale_dev,
+                                    void* stream) {
+  DCLIP_REQUIRE(x && y && rows > 0 && cols > 0, "split_f32_f16x2: bad arguments");
+  DCLIP_REQUIRE(cols % 8 == 0, "split_f32_f16x2: cols=%d must be a multiple of 8", cols);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0 && ldy % 8 == 0 && (long)ldy >= 2L * cols,
+                "split_f32_f16x2: ldx (multiple of 4, >= cols) / ldy (multiple of 8, >= 2 cols)");
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0 && (uintptr_t)scale_dev % 4 == 0, "split_f32_f16x2: alignment");
+  DCLIP_REQUIRE(scale_dev || pow2(scale), "split_f32_f16x2: scale must be a power of two");
+  // (the launch is recorded under the three-piece twin's name: the same call site of the step, the same kernel but for a store)
+  return split_launch(scale_dev ? "split_f32_f16x3_dev" : "split_f32_f16x3", x, y, rows, cols, ldx, ldy, scale_dev ? 1.f : scale, scale_dev, 2,
+                      stream);
+}
+
 // x fp32 [rows][ldx >= cols] -> y fp16 [rows][3 cols] = [hi|lo|hi] of x[m] 2^e_m and row_alpha[m] = 2^-e_m, e_m from the row's
 // own maximum (split_rows_f16x3_kernel).  One read of x for cols <= 3072 (the row stays in registers); wider rows are read twice,
 // the second time from the cache.
+namespace {
+int split_rows_entry(const char* name, const float* x, void* y, float* row_alpha, int rows, int cols, int ldx, int pieces,
+                     void* stream) {
+  DCLIP_REQUIRE(x && y && row_alpha && rows > 0 && cols > 0, "%s: bad arguments", name);
+  DCLIP_REQUIRE(cols % 8 == 0, "%s: cols=%d must be a multiple of 8", name, cols);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "%s: ldx must be a multiple of 4 and >= cols", name);
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0 && (uintptr_t)row_alpha % 4 == 0, "%s: alignment", name);
+  return split_rows_launch(name, x, y, row_alpha, rows, cols, ldx, pieces, stream);
+}
+}  // namespace
+
 DCLIP_API int dclip_split_f32_f16x3_rows(const float* x, void* y, float* row_alpha, int rows, int cols, int ldx, void* stream) {
-  DCLIP_REQUIRE(x && y && row_alpha && rows > 0 && cols > 0, "split_f32_f16x3_rows: bad arguments");
-  DCLIP_REQUIRE(cols % 8 == 0, "split_f32_f16x3_rows: cols=%d must be a multiple of 8", cols);
-  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "split_f32_f16x3_rows: ldx must be a multiple of 4 and >= cols");
-  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0 && (uintptr_t)row_alpha % 4 == 0, "split_f32_f16x3_rows: alignment");
-  return split_rows_launch(x, y, row_alpha, rows, cols, ldx, stream);
+  return split_rows_entry("split_f32_f16x3_rows", x, y, row_alpha, rows, cols, ldx, 3, stream);
+}
+
+// The two-piece form: y fp16 [rows][2 cols] = [hi|lo], bit-equal to the first two pieces of the entry above;
+// row_alpha as there.  Its launches are recorded under that entry's name, as are those of the other two-piece forms below.
+DCLIP_API int dclip_split_f32_f16x2_rows(const float* x, void* y, float* row_alpha, int rows, int cols, int ldx, void* stream) {
+  return split_rows_entry("split_f32_f16x3_rows", x, y, row_alpha, rows, cols, ldx, 2, stream);
 }
 
 // dclip_split_f32_f16x3_rows (y and row_alpha bit-equal to it) that in the same pass over x takes the column statistics, and
@@ -863,58 +924,94 @@ DCLIP_API size_t dclip_split_f32_f16x3_rows_colstats_workspace(int rows, int col
   return (size_t)2 * colstat_waves(rows) * cols * sizeof(float);
 }
 
-DCLIP_API int dclip_split_f32_f16x3_rows_colstats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
-                                                  float* db, int rows, int cols, int ldx, void* workspace, size_t workspace_bytes,
-                                                  void* stream) {
+namespace {
+int split_rows_colstats_entry(const char* name, const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
+                              float* db, int rows, int cols, int ldx, void* workspace, size_t workspace_bytes, int pieces,
+                              void* stream) {
   dclip_note_first_launch("", "");                     // a refused call leaves no earlier call's instance standing
-  DCLIP_REQUIRE(x && y && row_alpha && yc && col_exp && col_alpha && rows > 0 && cols > 0, "split_f32_f16x3_rows_colstats: bad arguments");
-  DCLIP_REQUIRE(cols % 8 == 0, "split_f32_f16x3_rows_colstats: cols=%d must be a multiple of 8", cols);
-  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "split_f32_f16x3_rows_colstats: ldx must be a multiple of 4 and >= cols");
+  DCLIP_REQUIRE(x && y && row_alpha && yc && col_exp && col_alpha && rows > 0 && cols > 0, "%s: bad arguments", name);
+  DCLIP_REQUIRE(cols % 8 == 0, "%s: cols=%d must be a multiple of 8", name, cols);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "%s: ldx must be a multiple of 4 and >= cols", name);
   DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)yc | (uintptr_t)col_exp | (uintptr_t)workspace) % 16 == 0 &&
                     ((uintptr_t)row_alpha | (uintptr_t)col_alpha | (uintptr_t)db) % 4 == 0,
-                "split_f32_f16x3_rows_colstats: alignment");
+                "%s: alignment", name);
   const size_t need = dclip_split_f32_f16x3_rows_colstats_workspace(rows, cols);
   if (!workspace || workspace_bytes < need) {
-    dclip_set_error("split_f32_f16x3_rows_colstats: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+    dclip_set_error("%s: needs %zu workspace bytes, got %zu", name, need, workspace_bytes);
     return DCLIP_EWORKSPACE;
   }
   const int W = colstat_waves(rows);
   unsigned* pmax = (unsigned*)workspace;
   float* psum = (float*)workspace + (size_t)W * cols;
-  const int rc = split_rows_colstats_launch(x, y, row_alpha, pmax, psum, rows, cols, ldx, stream);
+  const int rc = split_rows_colstats_launch(name, x, y, row_alpha, pmax, psum, rows, cols, ldx, pieces, stream);
   if (rc != DCLIP_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(colstats_finish_kernel, dim3(cdiv(cols, FIN_COLS)), dim3(256), 0, st, (const unsigned*)pmax, (const float*)psum, col_exp,
                      col_alpha, db, W < rows ? W : rows, cols);
-  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_colstats", ".finish");
+  DCLIP_CHECK_LAUNCH_V(name, ".finish");
   const size_t blocks = ((size_t)rows * (cols / 8) + 255) / 256;
   hipLaunchKernelGGL(split_cols_f16x2_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, st, x, (const int*)col_exp,
                      (unsigned short*)yc, rows, cols, ldx);
-  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_colstats", ".cols");
+  DCLIP_CHECK_LAUNCH_V(name, ".cols");
   return DCLIP_OK;
+}
+}  // namespace
+
+DCLIP_API int dclip_split_f32_f16x3_rows_colstats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
+                                                  float* db, int rows, int cols, int ldx, void* workspace, size_t workspace_bytes,
+                                                  void* stream) {
+  return split_rows_colstats_entry("split_f32_f16x3_rows_colstats", x, y, row_alpha, yc, col_exp, col_alpha, db, rows, cols, ldx,
+                                   workspace, workspace_bytes, 3, stream);
+}
+
+// The two-piece form: y fp16 [rows][2 cols] = [hi|lo], bit-equal to the first two pieces of the entry above; every
+// other output and the workspace as there.
+DCLIP_API int dclip_split_f32_f16x2_rows_colstats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
+                                                  float* db, int rows, int cols, int ldx, void* workspace, size_t workspace_bytes,
+                                                  void* stream) {
+  return split_rows_colstats_entry("split_f32_f16x3_rows_colstats", x, y, row_alpha, yc, col_exp, col_alpha, db, rows, cols, ldx,
+                                   workspace, workspace_bytes, 2, stream);
 }
 
 // dclip_split_f32_f16x3_rows_colstats when the kernel that produced x has left the column partials: pmax [P][cols]
 // (bit patterns of |x| maxima) and psum [P][cols] (fp32 sums), every word written.  Two launches: the finish over the P partial
 // rows, then ONE pass over x that writes both splits.  y, row_alpha, col_exp, col_alpha and yc are bit-equal to the three-launch
 // entry's on the same x (a maximum does not depend on how the rows were grouped); db is another association of the same sum.
-DCLIP_API int dclip_split_f32_f16x3_rows_cols_stats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
-                                                    float* db, const void* pmax, const float* psum, int P, int rows, int cols, int ldx,
-                                                    void* stream) {
+namespace {
+int split_rows_cols_stats_entry(const char* name, const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
+                                float* db, const void* pmax, const float* psum, int P, int rows, int cols, int ldx, int pieces,
+                                void* stream) {
   dclip_note_first_launch("", "");
   DCLIP_REQUIRE(x && y && row_alpha && yc && col_exp && col_alpha && pmax && psum && P > 0 && rows > 0 && cols > 0,
-                "split_f32_f16x3_rows_cols_stats: bad arguments");
-  DCLIP_REQUIRE(cols % 8 == 0, "split_f32_f16x3_rows_cols_stats: cols=%d must be a multiple of 8", cols);
-  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "split_f32_f16x3_rows_cols_stats: ldx must be a multiple of 4 and >= cols");
+                "%s: bad arguments", name);
+  DCLIP_REQUIRE(cols % 8 == 0, "%s: cols=%d must be a multiple of 8", name, cols);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "%s: ldx must be a multiple of 4 and >= cols", name);
   DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)yc | (uintptr_t)col_exp) % 16 == 0 &&
                     ((uintptr_t)row_alpha | (uintptr_t)col_alpha | (uintptr_t)db | (uintptr_t)pmax | (uintptr_t)psum) % 4 == 0,
-                "split_f32_f16x3_rows_cols_stats: alignment");
+                "%s: alignment", name);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(colstats_finish_kernel, dim3(cdiv(cols, FIN_COLS)), dim3(256), 0, st, (const unsigned*)pmax, psum, col_exp, col_alpha,
                      db, P, cols);
-  DCLIP_CHECK_LAUNCH_V("split_f32_f16x3_rows_cols_stats", ".finish");
-  dclip_note_first_launch("split_f32_f16x3_rows_cols_stats", ".finish");
-  return split_rows_cols_launch(x, y, row_alpha, (const int*)col_exp, yc, rows, cols, ldx, stream);
+  DCLIP_CHECK_LAUNCH_V(name, ".finish");
+  dclip_note_first_launch(name, ".finish");
+  return split_rows_cols_launch(name, x, y, row_alpha, (const int*)col_exp, yc, rows, cols, ldx, pieces, stream);
+}
+}  // namespace
+
+DCLIP_API int dclip_split_f32_f16x3_rows_cols_stats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
+                                                    float* db, const void* pmax, const float* psum, int P, int rows, int cols, int ldx,
+                                                    void* stream) {
+  return split_rows_cols_stats_entry("split_f32_f16x3_rows_cols_stats", x, y, row_alpha, yc, col_exp, col_alpha, db, pmax, psum, P, rows,
+                                     cols, ldx, 3, stream);
+}
+
+// The two-piece form: y fp16 [rows][2 cols] = [hi|lo] (non-temporal stores, as above), bit-equal to the first two
+// pieces of the entry above; every other output as there.
+DCLIP_API int dclip_split_f32_f16x2_rows_cols_stats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha,
+                                                    float* db, const void* pmax, const float* psum, int P, int rows, int cols, int ldx,
+                                                    void* stream) {
+  return split_rows_cols_stats_entry("split_f32_f16x3_rows_cols_stats", x, y, row_alpha, yc, col_exp, col_alpha, db, pmax, psum, P, rows,
+                                     cols, ldx, 2, stream);
 }
 
 DCLIP_API int dclip_layernorm_fwd_f16x3(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,
@@ -937,6 +1034,32 @@ DCLIP_API int dclip_layernorm_fwd_f16x3_dev(const float* x, const float* gamma, 
                     (uintptr_t)scale % 4 == 0,
                 "layernorm_fwd_f16x3_dev: alignment");
   return ln_launch("layernorm_fwd_f16x3_dev", x, gamma, beta, y, rows, D, eps, 1.f, scale, y32, mean, rstd, stream);
+}
+
+// The two-piece form: y fp16 [rows][2 D] = [hi|lo], bit-equal to the first two pieces of the entries above; y32 /
+// mean / rstd (each may be null) as dclip_layernorm_fwd_f16x3_dev writes them.  scale_dev (device, may be null) takes the place of
+// `scale` when given.
+DCLIP_API int dclip_layernorm_fwd_f16x2(const float* x, const float* gamma, const float* beta, void* y, float* y32, float* mean,
+                                        float* rstd, int rows, int D, float eps, float scale, const float* scale_dev, void* stream) {
+  DCLIP_REQUIRE(x && gamma && beta && y, "layernorm_fwd_f16x2: null pointer");
+  DCLIP_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 2048, "layernorm_fwd_f16x2: bad D=%d", D);
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y32) % 16 == 0 && (uintptr_t)y % 8 == 0 &&
+                    (uintptr_t)scale_dev % 4 == 0,
+                "layernorm_fwd_f16x2: alignment");
+  DCLIP_REQUIRE(scale_dev || pow2(scale), "layernorm_fwd_f16x2: scale must be a power of two");
+  return ln_launch(scale_dev ? "layernorm_fwd_f16x3_dev" : "layernorm_fwd_f16x3", x, gamma, beta, y, rows, D, eps, scale_dev ? 1.f : scale,
+                   scale_dev, y32, mean, rstd, stream, 2);
+}
+
+// g[i] = quick_gelu(h[i]) for n fp32 values (n % 4 == 0, 16-byte aligned): bit-equal to the g32 the GELU epilogue of
+// dclip_gemm_f16_scaled_split_dev / dclip_gemm_f16x3_scaled_split_dev stores beside the h32 it is given here.
+DCLIP_API int dclip_quick_gelu_f32(const float* h, float* g, size_t n, void* stream) {
+  DCLIP_REQUIRE(h && g && n > 0 && n % 4 == 0, "quick_gelu_f32: bad arguments (n a positive multiple of 4)");
+  DCLIP_REQUIRE(((uintptr_t)h | (uintptr_t)g) % 16 == 0, "quick_gelu_f32: operands must be 16-byte aligned");
+  const size_t blocks = cdivz(n / 4, 256);
+  hipLaunchKernelGGL(quick_gelu_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, (hipStream_t)stream, h, g, n / 4);
+  DCLIP_CHECK_LAUNCH("quick_gelu_f32");
+  return DCLIP_OK;
 }
 
 // ---- device plan (see Split16Ref): record size, and the three launches over a table of `nrefs` records / `tiles` tiles

@@ -65,22 +65,67 @@ class Split16Layer:
 # The three steps of a layer schedule that differ between the plain fp32 path (sp None) and the split-fp16 one: each returns
 # the GEMM operand first (the fp32 tensor itself / its [hi|lo|hi] split) and the fp32 tensors the backward keeps.
 
-def _ln_operand(x, w, b, eps: float, save: bool, sp: Optional[Split16Layer], name: str):
+def split16_pieces(consumers, plan=None, on: Optional[bool] = None, fused_k: Optional[bool] = None) -> int:
+    """How many pieces the producer of a split activation / gradient operand writes: 2, [hi|lo], exactly when
+    EVERY K-major GEMM that will read it — `consumers`, one (M, N, K logical) each, known at the producer's call — takes a fused
+    entry, which never reads the third piece: the test _fused_k makes at the consumer (the switch DCLIP_SPLIT16_FUSED and
+    ops.gemm_f16x3_plan).  3, [hi|lo|hi], everywhere else — tiny towers, shapes below DCLIP_F16X3_MIN, DCLIP_SPLIT16_FUSED=0 —
+    and with DCLIP_SPLIT16_PIECES2=0.  The weight-gradient consumers address either layout and do not count.  A pure function of
+    the shapes and the switches (`plan`, `on`, `fused_k`: stand-ins for ops.gemm_f16x3_plan and the two switches)."""
+    on = _SPLIT16_PIECES2 if on is None else on
+    fused_k = _SPLIT16_FUSED_K if fused_k is None else fused_k
+    plan = ops.gemm_f16x3_plan if plan is None else plan
+    consumers = list(consumers)
+    return 2 if on and fused_k and consumers and all(plan(M, N, K) > 0 for M, N, K in consumers) else 3
+
+
+def _ln_operand(x, w, b, eps: float, save: bool, sp: Optional[Split16Layer], name: str, pieces: int = 3, save32: bool = True):
     if sp is None:
         ln, m, r = ops.layernorm_fwd(x, w, b, eps, save_stats=save)
         return ln, ln, m, r
-    return ops.layernorm_fwd_f16x3_dev(x, w, b, eps, sp.act(name), save=save)
+    return ops.layernorm_fwd_f16x3_dev(x, w, b, eps, sp.act(name), save=save, pieces=pieces, save32=save32)
+
+
+class _Remat:
+    """An fp32 operand of a weight gradient that the forward did not store: its shape, and how to make it again —
+    bit for bit — on the rare path that reads it (linear_param_grads' fp32 GEMM)."""
+    __slots__ = ("shape", "make")
+
+    def __init__(self, shape, make):
+        self.shape, self.make = tuple(shape), make
+
+
+def _drops32(keep_split: bool, save: bool, sp: Optional[Split16Layer], out_f: int, in_f: int, tokens: int) -> bool:
+    """Whether a forward that keeps its split operands leaves out the fp32 copy of the operand of the weight gradient dW [out_f,
+    in_f]: that gradient has a split plan, so only the fp32 fall-back would read the copy — and it makes it again."""
+    return bool(_VSPLIT16_DROP32 and save and keep_split and sp is not None and
+                ops.gemm_f16_wgrad_tokmajor_seg3_plan(out_f, in_f, tokens) > 0)
+
+
+def _a_pieces(a3, w3) -> int:
+    """2 for an operand a3 = [hi|lo] [M, 2K], 3 for [hi|lo|hi]; its weight w3 is [hi|hi|lo] [N, 3K] either way."""
+    return 2 if 2 * w3.shape[1] == 3 * a3.shape[1] else 3
 
 
 def _fused_k(a3, w3) -> bool:
     """Whether a split GEMM of a3 [M, 3K] with w3 [N, 3K] takes its fused twin: the switch is on and the plan says
-    so — exactly where the 3 K form takes the ping-pong kernel; elsewhere the call is what it was."""
+    so — exactly where the 3 K form takes the ping-pong kernel; elsewhere the call is what it was.  A two-piece a3 (§9j) is made
+    only where this holds: the 3 K form cannot read it, and there is no other path."""
+    if _a_pieces(a3, w3) == 2:
+        K = w3.shape[1] // 3
+        if not (_SPLIT16_FUSED_K and ops.gemm_f16x3_plan(a3.shape[0], w3.shape[0], K) > 0):
+            raise RuntimeError(f"a two-piece split operand {tuple(a3.shape)} met a GEMM (N = {w3.shape[0]}, K = {K}) without a fused entry")
+        return True
     k3 = min(a3.shape[1], w3.shape[1])
     return bool(_SPLIT16_FUSED_K and k3 % 3 == 0 and ops.gemm_f16x3_plan(a3.shape[0], w3.shape[0], k3 // 3) > 0)
 
 
-def _gemm_f16_dev(a3, w3, alpha_ptr: int, **kw):
-    return (ops.gemm_f16x3_dev if _fused_k(a3, w3) else ops.gemm_f16_dev)(a3, w3, alpha_ptr, **kw)
+def _gemm_f16_dev(a3, w3, alpha_ptr: int, out_pieces: int = 3, **kw):
+    if _fused_k(a3, w3):
+        return ops.gemm_f16x3_dev(a3, w3, alpha_ptr, pieces=_a_pieces(a3, w3), out_pieces=out_pieces, **kw)
+    if out_pieces != 3:
+        raise RuntimeError("a two-piece split output needs the fused entry")
+    return ops.gemm_f16_dev(a3, w3, alpha_ptr, **kw)
 
 
 def _linear(a, w, sp: Optional[Split16Layer], name: str, bias, residual=None):
@@ -89,33 +134,51 @@ def _linear(a, w, sp: Optional[Split16Layer], name: str, bias, residual=None):
     return _gemm_f16_dev(a, sp.w[name], sp.alpha(name), bias=bias, residual=residual)
 
 
-def _fc1_gelu(a, p: LayerParams, save: bool, sp: Optional[Split16Layer]):
-    """(operand of fc2, h, g): g = quick_gelu(h), h = a fc1_w^T + b kept only with `save`."""
+def _fc1_gelu(a, p: LayerParams, save: bool, sp: Optional[Split16Layer], pieces: int = 3, save_g32: bool = True):
+    """(operand of fc2, h, g): g = quick_gelu(h), h = a fc1_w^T + b kept only with `save`.  `pieces`: of the split operand;
+    `save_g32` False (`sp` only): the fp32 g is not kept (None)."""
     M, I = a.shape[0], p.fc1_w.shape[0]
     h = torch.empty((M, I), dtype=torch.float32, device=a.device) if save else None
     if sp is None:
         g = ops.gemm(a, p.fc1_w, ops.LAYOUT_NT, bias=p.fc1_b, aux=h, epilogue=ops.EPI_GELU)
         return g, h, g
-    g = torch.empty((M, I), dtype=torch.float32, device=a.device) if save else None
+    g = torch.empty((M, I), dtype=torch.float32, device=a.device) if save and save_g32 else None
     if _VSPLIT16_FC1_EPI:
-        g3 = _gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), bias=p.fc1_b, gelu=True, split_out_scale_ptr=sp.act("g"), h32=h, g32=g)
+        g3 = _gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), out_pieces=pieces, bias=p.fc1_b, gelu=True,
+                           split_out_scale_ptr=sp.act("g"), h32=h, g32=g)
         return g3, h, g
     # two-launch form (bit-identical results; kept for the A/B of DESIGN.md §9d): h and g leave the GEMM, g is split after it
     g = _gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), bias=p.fc1_b, gelu=True, h32=h)
-    return ops.split_f16x3_dev(g, sp.act("g")), h, g
+    return ops.split_f16x3_dev(g, sp.act("g"), pieces=pieces), h, (g if save and save_g32 else None)
+
+
+def _layer_pieces(T: int, D: int, I: int, fc1_epi: bool) -> Dict[str, int]:
+    """Pieces of the four split operands of an encoder layer's forward at T rows (split16_pieces): ln1 feeds qkv, the context out,
+    ln2 fc1 and g fc2.  Where g leaves fc1's epilogue (`fc1_epi`) it has its two-piece form on the fused entry only."""
+    pc = {"ln1": split16_pieces([(T, 3 * D, D)]), "ctx": split16_pieces([(T, D, D)]), "ln2": split16_pieces([(T, I, D)]),
+          "g": split16_pieces([(T, D, I)])}
+    if fc1_epi and pc["ln2"] == 3 and not (_SPLIT16_FUSED_K and ops.gemm_f16x3_plan(T, I, D) > 0):
+        pc["g"] = 3
+    return pc
 
 
 def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: float, save: bool, sp: Optional[Split16Layer] = None,
               keep_split: bool = False):
-    """`keep_split` (with `save` and `sp`): the four [hi|lo|hi] operands this forward produced anyway — of ln1, the attention
-    context, ln2 and g — are kept as a 14th entry of `saved`, the X operands of the split-fp16 weight gradients."""
-    a1, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1")
+    """`keep_split` (with `save` and `sp`): the four [hi|lo|hi] (or [hi|lo], §9j) operands this forward produced anyway — of ln1,
+    the attention context, ln2 and g — are kept as a 14th entry of `saved`, the X operands of the split-fp16 weight gradients
+    (DESIGN.md §9f).  The fp32 ln1, ln2 and g are then None in `saved` wherever that weight gradient has a split plan (_drops32,
+    §9j): layer_bwd makes them again if it lands on the fp32 weight gradient after all."""
+    T, D, I = x.shape[0], x.shape[1], p.fc1_w.shape[0]
+    pc = _layer_pieces(T, D, I, _VSPLIT16_FC1_EPI) if sp is not None else {}
+    a1, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1", pc.get("ln1", 3),
+                                  not _drops32(keep_split, save, sp, 3 * D, D, T))
     qkv = _linear(a1, p.qkv_w, sp, "qkv", p.qkv_b)
     attn, lse = ops.attention_fwd(qkv, B, S, H, causal)
-    ac = attn if sp is None else ops.split_f16x3_dev(attn, sp.act("ctx"))
+    ac = attn if sp is None else ops.split_f16x3_dev(attn, sp.act("ctx"), pieces=pc["ctx"])
     x1 = _linear(ac, p.out_w, sp, "out", p.out_b, residual=x)
-    a2, ln2, m2, r2 = _ln_operand(x1, p.ln2_w, p.ln2_b, eps, save, sp, "ln2")
-    ag, h, g = _fc1_gelu(a2, p, save, sp)
+    a2, ln2, m2, r2 = _ln_operand(x1, p.ln2_w, p.ln2_b, eps, save, sp, "ln2", pc.get("ln2", 3),
+                                  not _drops32(keep_split, save, sp, I, D, T))
+    ag, h, g = _fc1_gelu(a2, p, save, sp, pc.get("g", 3), not _drops32(keep_split, save, sp, D, I, T))
     x2 = _linear(ag, p.fc2_w, sp, "fc2", p.fc2_b, residual=x1)
     saved = (x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g) if save else None
     if save and keep_split and sp is not None:
@@ -140,7 +203,8 @@ def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Te
     weight-gradient GEMM (DCLIP_EPI_A_ROWSUM): dy is streamed once, no separate column-sum launch.
     `sp`, `act`, `x3` (the forward's [hi|lo|hi] split of x, made with the plan scale sp.act(act)): the split-fp16 weight
     gradient when the plan takes the shape — ONE pass over dy gives its row split (for _dgrad), its column
-    statistics, db and its column-scaled [hi|lo] split; dW is the segmented token-major GEMM of that with x3.  Returns the row
+    statistics, db and its column-scaled [hi|lo] split; dW is the segmented token-major GEMM of that with x3 (x itself, which may
+    be a _Remat, gives its shape only).  Returns the row
     pieces (dy3, row_alpha) for _dgrad then, None otherwise.  A dy that carries the column partials its producer left
     (`dy.dystats`, _with_stats) is read ONCE: the finish over the partials, then one pass that writes both splits (§9g)."""
     dev = dy.device
@@ -148,10 +212,11 @@ def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Te
         M, N = dy.shape[1], x.shape[1]
         db = _galloc(alloc, bkey, (M,), dev) if need_b else None
         st = getattr(dy, "dystats", None) if _VSPLIT16_DYSTATS else None
+        pc = split16_pieces([(dy.shape[0], N, M)])      # the row pieces' one reader: _dgrad's dX [tokens, in_f] = dy3 wt^T along out_f
         if st is not None:
-            dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_cols_stats(dy, st, db=db)
+            dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_cols_stats(dy, st, db=db, pieces=pc)
         else:
-            dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=db)
+            dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=db, pieces=pc)
         if need_b:
             gr[bkey] = db
         out = _galloc(alloc, wkey, (M, N), dev)
@@ -160,6 +225,8 @@ def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Te
         else:
             gr[wkey] = ops.gemm_f16_wgrad_tokmajor_seg3(yc, x3, M, N, col_alpha, sp.act(act), out=out)
         return dy3, row_alpha
+    if need_w and isinstance(x, _Remat):      # the forward did not store it (§9j): made again, bit for bit
+        x = x.make()
     if need_w and need_b:
         gr[bkey] = _galloc(alloc, bkey, (dy.shape[1],), dev)
         gr[wkey] = ops.gemm(dy, x, ops.LAYOUT_TN, out=_galloc(alloc, wkey, (dy.shape[1], x.shape[1]), dev), a_rowsum=gr[bkey])
@@ -217,13 +284,15 @@ def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None, ou
         if aux is None:
             return ops.gemm(dy, w, ops.LAYOUT_NN)
         return ops.gemm(dy, w, ops.LAYOUT_NN, aux=aux, epilogue=ops.EPI_DGELU)
-    dy3, row_alpha = rows if rows is not None else ops.split_f16x3_rows(dy)
     wt = sp.wt[name]
+    dy3, row_alpha = rows if rows is not None else ops.split_f16x3_rows(
+        dy, pieces=split16_pieces([(dy.shape[0], wt.shape[0], wt.shape[1] // 3)]))
     k3 = min(dy3.shape[1], wt.shape[1])
     if _fused_k(dy3, wt):      # the fused twin (§9h); its statistics plan is the unfused one's wherever it is taken
-        st = _with_stats(out_stats, ops.gemm_f16x3_rows_stats_plan(dy3.shape[0], wt.shape[0], k3 // 3) if out_stats else 0, wt.shape[0],
+        K = wt.shape[1] // 3 if _a_pieces(dy3, wt) == 2 else k3 // 3
+        st = _with_stats(out_stats, ops.gemm_f16x3_rows_stats_plan(dy3.shape[0], wt.shape[0], K) if out_stats else 0, wt.shape[0],
                          dy3.device)
-        dx = ops.gemm_f16x3_rows_dev(dy3, wt, sp.walpha(name), row_alpha, dgelu_h=aux, stats=st)
+        dx = ops.gemm_f16x3_rows_dev(dy3, wt, sp.walpha(name), row_alpha, dgelu_h=aux, stats=st, pieces=_a_pieces(dy3, wt))
     else:
         st = _with_stats(out_stats, ops.gemm_f16_rows_stats_plan(dy3.shape[0], wt.shape[0], k3) if out_stats else 0, wt.shape[0],
                          dy3.device)
@@ -233,16 +302,29 @@ def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None, ou
     return dx
 
 
+def _remat_ln(ln, x, w, b, eps: Optional[float]):
+    """The saved fp32 LayerNorm output, or — where the forward left it out (§9j) — how to make it again from the saved input."""
+    if ln is not None:
+        return ln
+    if eps is None:
+        raise ValueError("the forward did not keep an fp32 LayerNorm output: the backward needs the layer's eps")
+    return _Remat(x.shape, lambda: ops.layernorm_fwd(x, w, b, eps, save_stats=False)[0])
+
+
 def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, need: Dict[str, bool], alloc=None,
-              sp: Optional[Split16Layer] = None, dx_stats: bool = False, dystats: bool = False):
+              sp: Optional[Split16Layer] = None, dx_stats: bool = False, dystats: bool = False, eps: Optional[float] = None):
     """Returns (dx, grads) with grads keyed like LayerParams.FIELDS (missing = not needed).  `alloc(field, shape)`:
-    see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad).  `dystats` (the caller's decision for
+    see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad).  `eps`: the layer's, for an fp32 LayerNorm
+    output the forward did not keep (_remat_ln, §9j).  `dystats` (the caller's decision for
     the whole tower, _dystats_regime): each kernel that produces the dY of a weight gradient that will take the split path is
     asked for its column partials (§9g); `dx_stats`: the caller says so for the returned dx (the layer below's fc2)."""
     x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved[:13]
     s3 = saved[13] if len(saved) > 13 and sp is not None else {}      # the forward's split operands (layer_fwd, keep_split)
     gr: Dict[str, torch.Tensor] = {}
     T, D, I = x.shape[0], x.shape[1], p.fc1_w.shape[0]
+    ln1, ln2 = _remat_ln(ln1, x, p.ln1_w, p.ln1_b, eps), _remat_ln(ln2, x1, p.ln2_w, p.ln2_b, eps)
+    if g is None:
+        g = _Remat(h.shape, lambda: ops.quick_gelu(h))
     rows = linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc, sp, "g", s3.get("g"))
     dh = _dgrad(dx2, p.fc2_w, sp, "fc2", aux=h, rows=rows,
                 out_stats=dystats and _split_wgrad_taken(bool(need.get("fc1_w")), sp, s3.get("ln2"), I, D, T))
@@ -283,7 +365,9 @@ def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, sa
     """`sp`: the full-size qkv projection takes the split-fp16 path (layer_fwd); the M = B GEMMs stay on ops.gemm.
     `keep_split`: ln1's split is kept for the qkv weight gradient (layer_fwd)."""
     D = x.shape[1]
-    a, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1")
+    a, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1",
+                                 3 if sp is None else split16_pieces([(x.shape[0], 3 * D, D)]),
+                                 not _drops32(keep_split, save, sp, 3 * D, D, x.shape[0]))
     qkv = _linear(a, p.qkv_w, sp, "qkv", p.qkv_b)
     attn, lse = ops.attention_cls_fwd(qkv, B, S, H)                       # [B, D]
     x_cls = ops.gather_rows(x, None, B, S, D)
@@ -299,12 +383,13 @@ def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, sa
 
 
 def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need: Dict[str, bool], alloc=None,
-                       sp: Optional[Split16Layer] = None, dx_stats: bool = False):
+                       sp: Optional[Split16Layer] = None, dx_stats: bool = False, eps: Optional[float] = None):
     """dx2 [B, D] is the gradient w.r.t. the CLS rows of the final hidden state; returns (dx [B*S, D], grads).  `sp`: the
     full-size qkv data gradient takes the split-fp16 path (_dgrad); the M = B GEMMs stay on ops.gemm."""
     x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved[:13]
     s3 = saved[13] if len(saved) > 13 and sp is not None else {}
     D = x.shape[1]
+    ln1 = _remat_ln(ln1, x, p.ln1_w, p.ln1_b, eps)
     gr: Dict[str, torch.Tensor] = {}
     linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc)
     dh = ops.gemm(dx2, p.fc2_w, ops.LAYOUT_NN, aux=h, epilogue=ops.EPI_DGELU)
@@ -475,9 +560,10 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
         dxs = below and _split_wgrad_taken(bool(needd[f"layers.{i - 1}.fc2_w"]), plan[i - 1], saved_layers[i - 1][13].get("g"),
                                            D, p.layers[i - 1].fc1_w.shape[0], B * S)
         if pruned and i == n_layers - 1:
-            dx, gr = last_layer_bwd_cls(dcls, p.layers[i], saved_layers[i], B, S, H, lneed, lalloc, sp, dxs)
+            dx, gr = last_layer_bwd_cls(dcls, p.layers[i], saved_layers[i], B, S, H, lneed, lalloc, sp, dxs, eps=v.layer_norm_eps)
         else:
-            dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, S, H, False, lneed, lalloc, sp, dxs, dystats)
+            dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, S, H, False, lneed, lalloc, sp, dxs, dystats,
+                               eps=v.layer_norm_eps)
         saved_layers[i] = None
         for f, t in gr.items():
             grads[f"layers.{i}.{f}"] = t
@@ -1337,8 +1423,11 @@ def _split16_plan(p: TextParams, cache: dict):
 def _split16_gemm(a3, ent, short: str, akey: str, **kw):
     """epilogue(A W^T) from the split operands; alpha undoes the operand scales."""
     alpha = 2.0 ** -(ent["e"][akey] + ent["f"][short])
+    out_pieces = kw.pop("out_pieces", 3)
     if _fused_k(a3, ent["w"][short]):      # the fused twin (§9h)
-        return ops.gemm_f16x3(a3, ent["w"][short], alpha=alpha, **kw)
+        return ops.gemm_f16x3(a3, ent["w"][short], alpha=alpha, pieces=_a_pieces(a3, ent["w"][short]), out_pieces=out_pieces, **kw)
+    if out_pieces != 3:
+        raise RuntimeError("a two-piece split output needs the fused entry")
     return ops.gemm_f16(a3, ent["w"][short], alpha=alpha, **kw)
 
 
@@ -1355,20 +1444,21 @@ def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: 
     H, eps = t.num_attention_heads, t.layer_norm_eps
     eos = ops.first_eos(input_ids, t.eos_token_id)
     x = ops.text_embed_fwd(input_ids, p.tok, p.pos)
+    pc = _layer_pieces(x.shape[0], D, t.intermediate_size, _SPLIT16_FC1_EPI)
     for lp, ent in zip(p.layers[:-1], plan[:-1]):
         e = ent["e"]
-        ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** e["ln1"])
+        ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** e["ln1"], pieces=pc["ln1"])
         qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
         attn, _ = ops.attention_fwd(qkv, B, T, H, True)
-        x1 = _split16_gemm(ops.split_f16x3(attn, 2.0 ** e["ctx"]), ent, "out", "ctx", bias=lp.out_b, residual=x)
-        ln2 = ops.layernorm_fwd_f16x3(x1, lp.ln2_w, lp.ln2_b, eps, 2.0 ** e["ln2"])
+        x1 = _split16_gemm(ops.split_f16x3(attn, 2.0 ** e["ctx"], pieces=pc["ctx"]), ent, "out", "ctx", bias=lp.out_b, residual=x)
+        ln2 = ops.layernorm_fwd_f16x3(x1, lp.ln2_w, lp.ln2_b, eps, 2.0 ** e["ln2"], pieces=pc["ln2"])
         if _SPLIT16_FC1_EPI:
-            g3 = _split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True, split_out_scale=2.0 ** e["g"])
+            g3 = _split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True, split_out_scale=2.0 ** e["g"], out_pieces=pc["g"])
         else:
-            g3 = ops.split_f16x3(_split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True), 2.0 ** e["g"])
+            g3 = ops.split_f16x3(_split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True), 2.0 ** e["g"], pieces=pc["g"])
         x = _split16_gemm(g3, ent, "fc2", "g", bias=lp.fc2_b, residual=x1)
     lp, ent = p.layers[-1], plan[-1]
-    ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"])
+    ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"], pieces=pc["ln1"])
     qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
     attn = ops.attention_row_fwd(qkv, eos, B, T, H)
     x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows(x, eos, B, T, D))
@@ -1405,6 +1495,15 @@ _VSPLIT16_DYSTATS = os.environ.get("DCLIP_VISION_SPLIT16_DYSTATS", "1") != "0"
 _SPLIT16_FUSED = os.environ.get("DCLIP_SPLIT16_FUSED", "1")
 _SPLIT16_FUSED_K = _SPLIT16_FUSED not in ("0", "tokmajor")
 _SPLIT16_FUSED_TOK = _SPLIT16_FUSED not in ("0", "kmajor")
+# The split activation / gradient operands of both towers as two pieces [hi|lo] wherever every K-major GEMM that reads one takes
+# its fused twin (split16_pieces): the duplicate third of [hi|lo|hi], which no fused entry reads, is not written;
+# 0 = three pieces everywhere, the parent's launches, allocations and outputs bit for bit
+_SPLIT16_PIECES2 = os.environ.get("DCLIP_SPLIT16_PIECES2", "1") != "0"
+# A vision forward that keeps its split operands for the weight gradients (§9f) does not also store the fp32 ln1 / ln2 / g where
+# that weight gradient has a split plan (_drops32): only the fp32 fall-back reads them, and it makes them again
+# (layernorm_fwd on the saved input; quick_gelu of the saved h), bit for bit.  Opt-in (1): alone against the parent it gained
+# 1.0-1.6 % and missed the project's bar in one of three pairs (§9j); the default, 0, stores them as before
+_VSPLIT16_DROP32 = os.environ.get("DCLIP_VISION_SPLIT16_DROP32", "0") == "1"
 
 
 def vision_split16_enabled() -> bool:
@@ -1694,6 +1793,7 @@ def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str
     (cache: the model's weight cache of that type; fp32 q | k | v for the fp32 packed core, the context is cast — or, with
     `attn16`, 16-bit q | k | v and context around the packed MFMA core, packed_attn16_route)."""
     H, eps = cfg.num_attention_heads, cfg.layer_norm_eps
+    pc = _layer_pieces(x.shape[0], cfg.hidden_size, cfg.intermediate_size, _SPLIT16_FC1_EPI) if mode == "split16" else None
     for li, lp in enumerate(layers[:n_layers]):
         if mode == "fp32":
             ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, eps, save_stats=False)
@@ -1706,15 +1806,16 @@ def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str
         elif mode == "split16":
             ent = plan[li]
             e = ent["e"]
-            ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** e["ln1"])
+            ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** e["ln1"], pieces=pc["ln1"])
             qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
             attn = ops.attention_varlen_causal_fwd(qkv, cu, max_S, H)
-            x1 = _split16_gemm(ops.split_f16x3(attn, 2.0 ** e["ctx"]), ent, "out", "ctx", bias=lp.out_b, residual=x)
-            ln2 = ops.layernorm_fwd_f16x3(x1, lp.ln2_w, lp.ln2_b, eps, 2.0 ** e["ln2"])
+            x1 = _split16_gemm(ops.split_f16x3(attn, 2.0 ** e["ctx"], pieces=pc["ctx"]), ent, "out", "ctx", bias=lp.out_b, residual=x)
+            ln2 = ops.layernorm_fwd_f16x3(x1, lp.ln2_w, lp.ln2_b, eps, 2.0 ** e["ln2"], pieces=pc["ln2"])
             if _SPLIT16_FC1_EPI:
-                g3 = _split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True, split_out_scale=2.0 ** e["g"])
+                g3 = _split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True, split_out_scale=2.0 ** e["g"],
+                                   out_pieces=pc["g"])
             else:
-                g3 = ops.split_f16x3(_split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True), 2.0 ** e["g"])
+                g3 = ops.split_f16x3(_split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True), 2.0 ** e["g"], pieces=pc["g"])
             x = _split16_gemm(g3, ent, "fc2", "g", bias=lp.fc2_b, residual=x1)
         else:
             k, pre = _OPS16[torch.bfloat16 if mode == "bf16" else torch.float16], f"t{li}."
@@ -1764,7 +1865,8 @@ def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict,
     if mode in ("fp32", "split16"):
         if mode == "split16":
             ent = plan[-1]
-            ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"])
+            ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"],
+                                          pieces=split16_pieces([(x.shape[0], 3 * D, D)]))
             qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
         else:
             ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, eps, save_stats=False)

@@ -1187,14 +1187,23 @@ def gemm_f16(a: torch.Tensor, w: torch.Tensor, *, n: Optional[int] = None, k: Op
 # ------------------------------------------------------------------------------------------- split-fp16 (frozen fp32 text tower)
 # fp32 x = hi + lo in two fp16 pieces (include/dclip_hip.h, "Split-fp16"; DESIGN.md §9c): the operands of gemm_f16(alpha=...).
 
-def split_f16x3(x: torch.Tensor, scale: float = 1.0, order: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def split_f16x3(x: torch.Tensor, scale: float = 1.0, order: int = 0, out: Optional[torch.Tensor] = None,
+                pieces: int = 3) -> torch.Tensor:
     """[rows, cols] fp32 -> fp16 [rows, 3 cols] of x * scale (a power of two): order 0 [hi|lo|hi] (activations), 1 [hi|hi|lo]
-    (weights); cols % 8 == 0.  `out`: refresh an existing split in place."""
+    (weights); cols % 8 == 0.  `out`: refresh an existing split in place.  `pieces` = 2 (order 0): fp16 [rows, 2 cols] = [hi|lo],
+    the operand of the fused GEMMs without its unread third."""
     lib = _lib.load()
     _f32(x, "x")
     if x.dim() != 2:
         raise ValueError("split_f16x3: x must be 2-D")
     rows, cols = x.shape
+    if pieces == 2:
+        if order != 0 or out is not None:
+            raise ValueError("split_f16x3: two pieces are the order-0 split into a fresh tensor")
+        y = torch.empty((rows, 2 * cols), dtype=torch.float16, device=x.device)
+        _lib.check(lib.dclip_split_f32_f16x2(x.data_ptr(), y.data_ptr(), rows, cols, cols, 2 * cols, float(scale), None, _stream()),
+                   "split_f32_f16x2")
+        return y
     if out is not None:
         if tuple(_f16(out, "out").shape) != (rows, 3 * cols):
             raise ValueError(f"split_f16x3: out shape {tuple(out.shape)} != {(rows, 3 * cols)}")
@@ -1206,12 +1215,18 @@ def split_f16x3(x: torch.Tensor, scale: float = 1.0, order: int = 0, out: Option
     return y
 
 
-def layernorm_fwd_f16x3(x, gamma, beta, eps: float, scale: float = 1.0) -> torch.Tensor:
-    """nn.LayerNorm (fp32 statistics and arithmetic) written as the [hi|lo|hi] split of scale * LN(x): [rows, 3 D] fp16."""
+def layernorm_fwd_f16x3(x, gamma, beta, eps: float, scale: float = 1.0, pieces: int = 3) -> torch.Tensor:
+    """nn.LayerNorm (fp32 statistics and arithmetic) written as the [hi|lo|hi] split of scale * LN(x): [rows, 3 D] fp16; `pieces`
+    = 2: [hi|lo], [rows, 2 D]."""
     lib = _lib.load()
     _f32(x, "x"), _f32(gamma, "gamma"), _f32(beta, "beta")
     D = x.shape[-1]
     rows = x.numel() // D
+    if pieces == 2:
+        y = torch.empty((rows, 2 * D), dtype=torch.float16, device=x.device)
+        _lib.check(lib.dclip_layernorm_fwd_f16x2(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), None, None, None, rows,
+                                                 D, float(eps), float(scale), None, _stream()), "layernorm_fwd_f16x2")
+        return y
     y = torch.empty((rows, 3 * D), dtype=torch.float16, device=x.device)
     _lib.check(lib.dclip_layernorm_fwd_f16x3(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), rows, D, float(eps),
                                              float(scale), _stream()), "layernorm_fwd_f16x3")
@@ -1222,13 +1237,21 @@ def layernorm_fwd_f16x3(x, gamma, beta, eps: float, scale: float = 1.0) -> torch
 # The wrappers above for a tower whose weights change every step (the student's vision forward): every scale
 # is the ADDRESS of a float of the device plan record (split16_refresh computes it on the device), passed as an int.
 
-def split_f16x3_dev(x: torch.Tensor, scale_ptr: int, order: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def split_f16x3_dev(x: torch.Tensor, scale_ptr: int, order: int = 0, out: Optional[torch.Tensor] = None,
+                    pieces: int = 3) -> torch.Tensor:
     """split_f16x3 with the scale read from device memory."""
     lib = _lib.load()
     _f32(x, "x")
     if x.dim() != 2:
         raise ValueError("split_f16x3_dev: x must be 2-D")
     rows, cols = x.shape
+    if pieces == 2:
+        if order != 0 or out is not None:
+            raise ValueError("split_f16x3_dev: two pieces are the order-0 split into a fresh tensor")
+        y = torch.empty((rows, 2 * cols), dtype=torch.float16, device=x.device)
+        _lib.check(lib.dclip_split_f32_f16x2(x.data_ptr(), y.data_ptr(), rows, cols, cols, 2 * cols, 1.0, scale_ptr, _stream()),
+                   "split_f32_f16x2")
+        return y
     if out is not None:
         if tuple(_f16(out, "out").shape) != (rows, 3 * cols):
             raise ValueError(f"split_f16x3_dev: out shape {tuple(out.shape)} != {(rows, 3 * cols)}")
@@ -1240,22 +1263,36 @@ def split_f16x3_dev(x: torch.Tensor, scale_ptr: int, order: int = 0, out: Option
     return y
 
 
-def layernorm_fwd_f16x3_dev(x, gamma, beta, eps: float, scale_ptr: int, save: bool = False):
+def layernorm_fwd_f16x3_dev(x, gamma, beta, eps: float, scale_ptr: int, save: bool = False, pieces: int = 3, save32: bool = True):
     """layernorm_fwd_f16x3 with the scale read from device memory -> (y3, y, mean, rstd); with `save`, y / mean / rstd are what
-    layernorm_fwd returns (bit for bit), otherwise None."""
+    layernorm_fwd returns (bit for bit), otherwise None.  `pieces` = 2: y3 is [hi|lo], [rows, 2 D].  `save32` False: the fp32 y is
+    not stored (None) even with `save`."""
     lib = _lib.load()
     _f32(x, "x"), _f32(gamma, "gamma"), _f32(beta, "beta")
     D = x.shape[-1]
     rows = x.numel() // D
     if gamma.numel() != D or beta.numel() != D:
         raise ValueError("layernorm_fwd_f16x3_dev: gamma/beta size")
-    y3 = torch.empty((rows, 3 * D), dtype=torch.float16, device=x.device)
-    y = torch.empty_like(x) if save else None
+    y3 = torch.empty((rows, pieces * D), dtype=torch.float16, device=x.device)
+    y = torch.empty_like(x) if save and save32 else None
     mean = torch.empty((rows,), dtype=torch.float32, device=x.device) if save else None
     rstd = torch.empty((rows,), dtype=torch.float32, device=x.device) if save else None
+    if pieces == 2:
+        _lib.check(lib.dclip_layernorm_fwd_f16x2(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y3.data_ptr(), _ptr(y), _ptr(mean),
+                                                 _ptr(rstd), rows, D, float(eps), 1.0, scale_ptr, _stream()), "layernorm_fwd_f16x2")
+        return y3, y, mean, rstd
     _lib.check(lib.dclip_layernorm_fwd_f16x3_dev(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y3.data_ptr(), _ptr(y), _ptr(mean),
                                                  _ptr(rstd), rows, D, float(eps), scale_ptr, _stream()), "layernorm_fwd_f16x3_dev")
     return y3, y, mean, rstd
+
+
+def quick_gelu(h: torch.Tensor) -> torch.Tensor:
+    """quick_gelu(h) of a contiguous fp32 tensor (numel % 4 == 0), bit-equal to the g32 the split-output GEMMs' GELU epilogue stores
+    beside that h32 (the fp32 g a backward makes again)."""
+    lib = _lib.load()
+    g = torch.empty_like(_f32(h, "h"))
+    _lib.check(lib.dclip_quick_gelu_f32(h.data_ptr(), g.data_ptr(), h.numel(), _stream()), "quick_gelu_f32")
+    return g
 
 
 def gemm_f16_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, *, bias: Optional[torch.Tensor] = None,
@@ -1395,16 +1432,17 @@ def split16_refresh(tab) -> None:
                    "split16_weights")
 
 
-def split_f16x3_rows(x: torch.Tensor):
+def split_f16x3_rows(x: torch.Tensor, pieces: int = 3):
     """[rows, cols] fp32 (row stride >= cols) -> (fp16 [rows, 3 cols], fp32 [rows]): the [hi|lo|hi] split of x[m] * 2^e_m with
-    one power of two PER ROW taken from the row's own maximum (engine.split16_row_exp), and row_alpha[m] = 2^-e_m."""
+    one power of two PER ROW taken from the row's own maximum (engine.split16_row_exp), and row_alpha[m] = 2^-e_m.  `pieces` = 2:
+    [hi|lo], fp16 [rows, 2 cols]."""
     lib = _lib.load()
     if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
         raise ValueError("split_f16x3_rows: x must be a 2-D fp32 device tensor with unit column stride")
     rows, cols = x.shape
-    y = torch.empty((rows, 3 * cols), dtype=torch.float16, device=x.device)
+    y = torch.empty((rows, pieces * cols), dtype=torch.float16, device=x.device)
     ra = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    _lib.check(lib.dclip_split_f32_f16x3_rows(x.data_ptr(), y.data_ptr(), ra.data_ptr(), rows, cols, x.stride(0) if rows > 1 else cols,
+    _lib.check((lib.dclip_split_f32_f16x2_rows if pieces == 2 else lib.dclip_split_f32_f16x3_rows)(x.data_ptr(), y.data_ptr(), ra.data_ptr(), rows, cols, x.stride(0) if rows > 1 else cols,
                                               _stream()), "split_f32_f16x3_rows")
     return y, ra
 
@@ -1444,11 +1482,11 @@ def gemm_f16_rows_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, row_alph
     return out
 
 
-def split_f16x3_rows_colstats(x: torch.Tensor, db: Optional[torch.Tensor] = None):
+def split_f16x3_rows_colstats(x: torch.Tensor, db: Optional[torch.Tensor] = None, pieces: int = 3):
     """split_f16x3_rows that in the same pass takes the column statistics ->
     (y3, row_alpha, yc, col_exp, col_alpha): y3 / row_alpha as split_f16x3_rows gives them (bit for bit); col_exp int32 [cols] =
     engine.split16_col_exp of max|x[:, n]|, col_alpha = 2^-col_exp; yc fp16 [rows, 2 cols] = [hi|lo] of x[m, n] 2^col_exp[n];
-    `db` (fp32 [cols]) receives the column sums."""
+    `db` (fp32 [cols]) receives the column sums.  `pieces` = 2: y3 is [hi|lo], fp16 [rows, 2 cols]."""
     lib = _lib.load()
     if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
         raise ValueError("split_f16x3_rows_colstats: x must be a 2-D fp32 device tensor with unit column stride")
@@ -1456,22 +1494,23 @@ def split_f16x3_rows_colstats(x: torch.Tensor, db: Optional[torch.Tensor] = None
     if db is not None and (_f32(db, "db").numel() != cols):
         raise ValueError("split_f16x3_rows_colstats: db size")
     dev = x.device
-    y = torch.empty((rows, 3 * cols), dtype=torch.float16, device=dev)
+    y = torch.empty((rows, pieces * cols), dtype=torch.float16, device=dev)
     ra = torch.empty((rows,), dtype=torch.float32, device=dev)
     yc = torch.empty((rows, 2 * cols), dtype=torch.float16, device=dev)
     ce = torch.empty((cols,), dtype=torch.int32, device=dev)
     ca = torch.empty((cols,), dtype=torch.float32, device=dev)
     nbytes = lib.dclip_split_f32_f16x3_rows_colstats_workspace(rows, cols)
     ws = _ws.get(nbytes, dev)
-    _lib.check(lib.dclip_split_f32_f16x3_rows_colstats(x.data_ptr(), y.data_ptr(), ra.data_ptr(), yc.data_ptr(), ce.data_ptr(),
+    _lib.check((lib.dclip_split_f32_f16x2_rows_colstats if pieces == 2 else lib.dclip_split_f32_f16x3_rows_colstats)(x.data_ptr(), y.data_ptr(), ra.data_ptr(), yc.data_ptr(), ce.data_ptr(),
                                                        ca.data_ptr(), _ptr(db), rows, cols, x.stride(0) if rows > 1 else cols,
                                                        _ptr(ws), nbytes, _stream()), "split_f32_f16x3_rows_colstats")
     return y, ra, yc, ce, ca
 
 
-def split_f16x3_rows_cols_stats(x: torch.Tensor, stats: ColStats, db: Optional[torch.Tensor] = None):
+def split_f16x3_rows_cols_stats(x: torch.Tensor, stats: ColStats, db: Optional[torch.Tensor] = None, pieces: int = 3):
     """split_f16x3_rows_colstats for an x whose producer left its column partials in `stats`: the finish over
-    the partial rows, then ONE pass over x.  The same five outputs, bit for bit; `db` is another association of the same sums."""
+    the partial rows, then ONE pass over x.  The same five outputs, bit for bit; `db` is another association of the same sums.
+    `pieces` as there."""
     lib = _lib.load()
     if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
         raise ValueError("split_f16x3_rows_cols_stats: x must be a 2-D fp32 device tensor with unit column stride")
@@ -1481,12 +1520,12 @@ def split_f16x3_rows_cols_stats(x: torch.Tensor, stats: ColStats, db: Optional[t
     if db is not None and (_f32(db, "db").numel() != cols):
         raise ValueError("split_f16x3_rows_cols_stats: db size")
     dev = x.device
-    y = torch.empty((rows, 3 * cols), dtype=torch.float16, device=dev)
+    y = torch.empty((rows, pieces * cols), dtype=torch.float16, device=dev)
     ra = torch.empty((rows,), dtype=torch.float32, device=dev)
     yc = torch.empty((rows, 2 * cols), dtype=torch.float16, device=dev)
     ce = torch.empty((cols,), dtype=torch.int32, device=dev)
     ca = torch.empty((cols,), dtype=torch.float32, device=dev)
-    _lib.check(lib.dclip_split_f32_f16x3_rows_cols_stats(x.data_ptr(), y.data_ptr(), ra.data_ptr(), yc.data_ptr(), ce.data_ptr(),
+    _lib.check((lib.dclip_split_f32_f16x2_rows_cols_stats if pieces == 2 else lib.dclip_split_f32_f16x3_rows_cols_stats)(x.data_ptr(), y.data_ptr(), ra.data_ptr(), yc.data_ptr(), ce.data_ptr(),
                                                          ca.data_ptr(), _ptr(db), stats.pmax.data_ptr(), stats.psum.data_ptr(), stats.P,
                                                          rows, cols, x.stride(0) if rows > 1 else cols, _stream()),
                "split_f32_f16x3_rows_cols_stats")
@@ -1542,10 +1581,18 @@ def gemm_f16x3_tile_rows(M: int, N: int, K: int, rows_form: bool = False, stats_
     return int(_lib.load().dclip_gemm_f16x3_tile_rows(M, N, K, int(rows_form), int(stats_form)))
 
 
-def _x3_k(a: torch.Tensor, w: torch.Tensor, name: str):
+def _x3_k(a: torch.Tensor, w: torch.Tensor, name: str, pieces: int = 3):
+    """(M, N, K, lda, ldw) of a fused call.  `pieces` = 2: a is [hi|lo] [M, 2 K] — K cannot be read off a 2 K
+    and a 3 K width together, so the caller says which; w is [hi|hi|lo] [N, 3 K] either way."""
     _f16(a, "a"), _f16(w, "w")
     M, lda = a.shape
     N, ldw = w.shape
+    if pieces == 2:
+        if lda % 2 or ldw < 3 * (lda // 2):
+            raise ValueError(f"{name}: a is a [rows, 2 K] split and w a [rows, 3 K] one")
+        return M, N, lda // 2, lda, ldw
+    if pieces != 3:
+        raise ValueError(f"{name}: pieces is 2 or 3")
     if min(lda, ldw) % 3:
         raise ValueError(f"{name}: a / w are [rows, 3 K] splits")
     K = min(lda, ldw) // 3
@@ -1554,11 +1601,12 @@ def _x3_k(a: torch.Tensor, w: torch.Tensor, name: str):
 
 def gemm_f16x3(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
                gelu: bool = False, out_f16: bool = False, alpha: float = 1.0, split_out_scale: Optional[float] = None,
-               segs=None) -> torch.Tensor:
+               segs=None, pieces: int = 3, out_pieces: int = 3) -> torch.Tensor:
     """gemm_f16(alpha=..., split_out_scale=...) of a = [hi|lo|hi] [M, 3K] and w = [hi|hi|lo] [N, 3K] on the fused kernel.
-    `segs` = (a_hi, a_lo, w_hi, w_lo) column offsets, default (0, K, 0, 2K)."""
+    `segs` = (a_hi, a_lo, w_hi, w_lo) column offsets, default (0, K, 0, 2K).  `pieces` = 2: a is [hi|lo] [M, 2K]; `out_pieces` = 2:
+    a split output is [hi|lo] [M, 2N]."""
     lib = _lib.load()
-    M, N, K, lda, ldw = _x3_k(a, w, "gemm_f16x3")
+    M, N, K, lda, ldw = _x3_k(a, w, "gemm_f16x3", pieces)
     sg = (0, K, 0, 2 * K) if segs is None else tuple(int(v) for v in segs)
     epi = 0
     if bias is not None:
@@ -1574,10 +1622,10 @@ def gemm_f16x3(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor]
     if split_out_scale is not None:
         if residual is not None or out_f16:
             raise ValueError("gemm_f16x3: a split output takes bias / gelu only")
-        y3 = torch.empty((M, 3 * N), dtype=torch.float16, device=a.device)
-        _lib.check(lib.dclip_gemm_f16x3_scaled_split(a.data_ptr(), w.data_ptr(), y3.data_ptr(), _ptr(bias), M, N, K, lda, ldw, 3 * N,
-                                                     *sg, epi, float(alpha), float(split_out_scale), _stream()),
-                   "gemm_f16x3_scaled_split")
+        y3 = torch.empty((M, out_pieces * N), dtype=torch.float16, device=a.device)
+        fn = lib.dclip_gemm_f16x3_scaled_split2 if out_pieces == 2 else lib.dclip_gemm_f16x3_scaled_split
+        _lib.check(fn(a.data_ptr(), w.data_ptr(), y3.data_ptr(), _ptr(bias), M, N, K, lda, ldw, out_pieces * N, *sg, epi, float(alpha),
+                      float(split_out_scale), _stream()), "gemm_f16x3_scaled_split")
         return y3
     out = torch.empty((M, N), dtype=torch.float16 if out_f16 else torch.float32, device=a.device)
     _lib.check(lib.dclip_gemm_f16x3_scaled(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual), M, N, K, lda, ldw,
@@ -1588,10 +1636,10 @@ def gemm_f16x3(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor]
 def gemm_f16x3_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, *, bias: Optional[torch.Tensor] = None,
                    residual: Optional[torch.Tensor] = None, gelu: bool = False, out_f16: bool = False,
                    split_out_scale_ptr: Optional[int] = None, h32: Optional[torch.Tensor] = None,
-                   g32: Optional[torch.Tensor] = None, segs=None) -> torch.Tensor:
-    """gemm_f16_dev on the fused kernel: the same arguments and outputs."""
+                   g32: Optional[torch.Tensor] = None, segs=None, pieces: int = 3, out_pieces: int = 3) -> torch.Tensor:
+    """gemm_f16_dev on the fused kernel: the same arguments and outputs; `pieces` / `out_pieces` as gemm_f16x3's."""
     lib = _lib.load()
-    M, N, K, lda, ldw = _x3_k(a, w, "gemm_f16x3_dev")
+    M, N, K, lda, ldw = _x3_k(a, w, "gemm_f16x3_dev", pieces)
     sg = (0, K, 0, 2 * K) if segs is None else tuple(int(v) for v in segs)
     epi = 0
     if bias is not None:
@@ -1612,10 +1660,10 @@ def gemm_f16x3_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, *, bias: Op
                 raise ValueError(f"gemm_f16x3_dev: {nm} shape")
         if h32 is not None and not gelu:
             raise ValueError("gemm_f16x3_dev: h32 is the pre-activation of a gelu epilogue")
-        y3 = torch.empty((M, 3 * N), dtype=torch.float16, device=a.device)
-        _lib.check(lib.dclip_gemm_f16x3_scaled_split_dev(a.data_ptr(), w.data_ptr(), y3.data_ptr(), _ptr(bias), _ptr(h32), _ptr(g32), M,
-                                                         N, K, lda, ldw, 3 * N, *sg, epi, alpha_ptr, split_out_scale_ptr, _stream()),
-                   "gemm_f16x3_scaled_split_dev")
+        y3 = torch.empty((M, out_pieces * N), dtype=torch.float16, device=a.device)
+        fn = lib.dclip_gemm_f16x3_scaled_split2_dev if out_pieces == 2 else lib.dclip_gemm_f16x3_scaled_split_dev
+        _lib.check(fn(a.data_ptr(), w.data_ptr(), y3.data_ptr(), _ptr(bias), _ptr(h32), _ptr(g32), M, N, K, lda, ldw, out_pieces * N,
+                      *sg, epi, alpha_ptr, split_out_scale_ptr, _stream()), "gemm_f16x3_scaled_split_dev")
         return y3
     if g32 is not None:
         raise ValueError("gemm_f16x3_dev: g32 goes with a split output")
@@ -1638,10 +1686,11 @@ def gemm_f16x3_rows_stats_plan(M: int, N: int, K: int) -> int:
 
 
 def gemm_f16x3_rows_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, row_alpha: torch.Tensor,
-                        dgelu_h: Optional[torch.Tensor] = None, stats: Optional[ColStats] = None, segs=None) -> torch.Tensor:
-    """gemm_f16_rows_dev on the fused kernel; `stats` has ceil(M / 256) partial rows and N columns."""
+                        dgelu_h: Optional[torch.Tensor] = None, stats: Optional[ColStats] = None, segs=None,
+                        pieces: int = 3) -> torch.Tensor:
+    """gemm_f16_rows_dev on the fused kernel; `stats` has ceil(M / 256) partial rows and N columns; `pieces` as gemm_f16x3's."""
     lib = _lib.load()
-    M, N, K, lda, ldw = _x3_k(a, w, "gemm_f16x3_rows_dev")
+    M, N, K, lda, ldw = _x3_k(a, w, "gemm_f16x3_rows_dev", pieces)
     sg = (0, K, 0, 2 * K) if segs is None else tuple(int(v) for v in segs)
     if _f32(row_alpha, "row_alpha").numel() != M:
         raise ValueError("gemm_f16x3_rows_dev: row_alpha size")
@@ -1671,8 +1720,9 @@ def gemm_f16x3_wgrad_tokmajor_plan(M: int, N: int, tokens: int) -> int:
 def gemm_f16x3_wgrad_tokmajor(dy: torch.Tensor, x: torch.Tensor, M: int, N: int, col_alpha: torch.Tensor, act_scale_ptr: int,
                               segs=None, splits: Optional[int] = None,
                               out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
-    """gemm_f16_wgrad_tokmajor_seg3's dW on the fused kernel: hi.hi + lo.hi + hi.lo of dy = [hi|lo] and x = [hi|lo|..], `segs` =
-    (dy_hi, dy_lo, x_hi, x_lo) column offsets, default (0, M, 0, N).  None when the plan is 0 (and `splits` is left to it)."""
+    """gemm_f16_wgrad_tokmajor_seg3's dW on the fused kernel: hi.hi + lo.hi + hi.lo of dy = [hi|lo] and x = [hi|lo|..] (three
+    pieces or two: the third is not read), `segs` = (dy_hi, dy_lo, x_hi, x_lo) column offsets, default (0, M, 0, N).  None when
+    the plan is 0 (and `splits` is left to it)."""
     lib = _lib.load()
     _f16(dy, "dy"), _f16(x, "x")
     if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0]:

@@ -762,6 +762,38 @@ int dclip_gemm_f16x3_wgrad_tokmajor(const void* dY, const void* X, float* C, int
                                     int dy_hi, int dy_lo, int x_hi, int x_lo, const float* col_alpha, const float* act_scale,
                                     int splits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- two-piece operands: no fused entry reads the duplicate third of an [hi|lo|hi] operand, so each producer of
+ * one has a twin that writes fp16 [rows][2 cols] = [hi|lo] and nothing else — hi and lo bit-equal to the first two pieces of the
+ * entry named after "f16x2" / before "split2", every other output (row_alpha, yc, col_exp, col_alpha, db, y32, mean, rstd, h32, g32)
+ * bit-equal to that entry's, the same limits.  The consumers are the fused entries above as they are: K-major with lda = 2 K and
+ * offsets (0, K, 0, 2 K) — the weights stay [hi|hi|lo] — token-major with ldx = 2 N and (x_hi, x_lo) = (0, N); the segmented
+ * gemm_f16_wgrad_tokmajor_seg3 reads it with w_seg = (0, 0, N).  The 3 K entries (gemm_f16_scaled*) cannot read it.
+ *   split_f32_f16x2, layernorm_fwd_f16x2   order-0 split / LayerNorm; `scale` (a power of two) or, when not NULL, the device
+ *                            float scale_dev; ldy >= 2 cols.  layernorm's y32 / mean / rstd may be NULL.
+ *   split_f32_f16x2_rows, _rows_colstats, _rows_cols_stats   the row-scaled splits (the last keeps its non-temporal stores).
+ *   gemm_f16x3_scaled_split2(_dev)   C fp16 [M][ldc >= 2 N, a multiple of 8]; out_scale is required (BIAS | GELU).
+ * dclip_last_launch / dclip_first_launch report a two-piece entry under its three-piece twin's name and variant: the call site of
+ * the step is the same, and which layout it wrote shows in the tensor's width. */
+int dclip_split_f32_f16x2(const float* x, void* y, int rows, int cols, int ldx, int ldy, float scale, const float* scale_dev,
+                          void* stream);
+/*   quick_gelu_f32           g[i] = quick_gelu(h[i]), n fp32 values (n % 4 == 0, 16-byte aligned): bit-equal to the g32 a GELU epilogue of
+ *                            the split-output entries stores beside that h32 — what a backward makes again where the forward did
+ *                            not keep the fp32 g. */
+int dclip_quick_gelu_f32(const float* h, float* g, size_t n, void* stream);
+int dclip_layernorm_fwd_f16x2(const float* x, const float* gamma, const float* beta, void* y, float* y32, float* mean, float* rstd,
+                              int rows, int D, float eps, float scale, const float* scale_dev, void* stream);
+int dclip_split_f32_f16x2_rows(const float* x, void* y, float* row_alpha, int rows, int cols, int ldx, void* stream);
+int dclip_split_f32_f16x2_rows_colstats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha, float* db,
+                                        int rows, int cols, int ldx, void* workspace, size_t workspace_bytes, void* stream);
+int dclip_split_f32_f16x2_rows_cols_stats(const float* x, void* y, float* row_alpha, void* yc, int* col_exp, float* col_alpha, float* db,
+                                          const void* pmax, const float* psum, int P, int rows, int cols, int ldx, void* stream);
+int dclip_gemm_f16x3_scaled_split2(const void* A, const void* W, void* C, const float* bias, int M, int N, int K, int lda, int ldw,
+                                   int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue, float alpha, float out_scale,
+                                   void* stream);
+int dclip_gemm_f16x3_scaled_split2_dev(const void* A, const void* W, void* C, const float* bias, float* h32, float* g32, int M, int N,
+                                       int K, int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue,
+                                       const float* alpha, const float* out_scale, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * fp16 TRAINING path (opt-in student_precision="fp16" / get_image_features(precision="fp16-mixed")): fp16
  * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
