@@ -168,6 +168,8 @@ SIGNATURES = {
     "dclip_gemm_f16x3_wgrad_tokmajor_workspace": (Z, [I, I, I]),
     "dclip_gemm_f16x3_wgrad_tokmajor": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, P, P, I, P, Z, P]),
     "dclip_split_f32_f16x2": (I, [P, P, I, I, I, I, F, P, P]),
+    "dclip_attention_fwd_f16x2": (I, [P, P, I, I, I, I, F, I, I, P]),
+    "dclip_attention_varlen_fwd_f16x2": (I, [P, P, P, I, I, I, I, F, I, I, P]),
     "dclip_quick_gelu_f32": (I, [P, P, Z, P]),
     "dclip_layernorm_fwd_f16x2": (I, [P, P, P, P, P, P, P, I, I, F, F, P, P]),
     "dclip_split_f32_f16x2_rows": (I, [P, P, P, I, I, I, P]),

@@ -262,7 +262,11 @@ class HipCLIPModel(nn.Module):
         the caller scales the loss, amp.DynamicLossScaler) when grad is enabled and a parameter is trainable, otherwise the
         frozen "fp16" forward.  interpolate_pos_encoding=True (as on HF's CLIPModel): any H x W of at least one patch a side;
         the position table is resampled bicubically to the image's patch grid, rows and columns beyond the
-        last whole patch are ignored.  Without the flag nothing changes, the size check included."""
+        last whole patch are ignored.  Without the flag nothing changes, the size check included.
+        precision="fp32-split16" (opt-in, frozen use only): the fp32 forward with the encoder layers' full-size
+        GEMMs on the fp16 MFMAs from hi/lo split operands — fp32-grade features (the error of "fp32" itself against fp64, not
+        that of "fp16") at 16-bit-pipe speed; with grad enabled and a trainable vision parameter it is a RuntimeError (training
+        has its own split path under "fp32").  `packed_attention16` has no effect at this precision."""
         if pixel_values is None:
             raise ValueError("You have to specify pixel_values")
         v = self.config.vision
@@ -286,6 +290,13 @@ class HipCLIPModel(nn.Module):
             pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)
             return engine.vision_fwd_bf16(pd, pixel_values.float().contiguous(), v, self._f16_cache(), torch.float16,
                                           grid=grid)
+        if precision == "fp32-split16":
+            if torch.is_grad_enabled() and any(t.requires_grad for t in p.tensors()):
+                raise RuntimeError("precision='fp32-split16' is a forward-only path for frozen towers: call it under "
+                                   "torch.no_grad() (training: precision='fp32' takes its own split path)")
+            pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)
+            return engine.vision_fwd_frozen_split16(pd, pixel_values.float().contiguous(), v, self._vsplit16_frozen_cache(),
+                                                    grid=grid)
         if precision != "fp32":
             raise ValueError(f"precision {precision!r}")
         # the split-fp16 forward (engine.vision_fwd, DCLIP_VISION_SPLIT16) is the TRAINING forward only: a no-grad call
@@ -303,8 +314,9 @@ class HipCLIPModel(nn.Module):
         give (values in [0,1], zero outside the image, no mean / std), cut on the device; its position table is the model's,
         resampled to its patch grid as get_image_features(interpolate_pos_encoding=True) does.  A crop with a side shorter than
         one patch is a ValueError.  precision: "fp32", "bf16" or "fp16" (16-bit GEMM inputs; fp32 attention core, or the 16-bit
-        packed core with `packed_attention16`)."""
-        if precision not in ("fp32", "bf16", "fp16"):
+        packed core with `packed_attention16`), or "fp32-split16" (the fp32 pass with its full-size GEMMs on split-fp16 operands,
+        get_image_features; `packed_attention16` has no effect there)."""
+        if precision not in ("fp32", "bf16", "fp16", "fp32-split16"):
             raise ValueError(f"precision {precision!r}")
         v = self.config.vision
         flat = torch.as_tensor(boxes, dtype=torch.int32).reshape(-1, 5).cpu().contiguous()
@@ -321,7 +333,8 @@ class HipCLIPModel(nn.Module):
         cu, po = dev_t[7 * N:8 * N + 1], dev_t[8 * N + 1:]
         cols = ops.patches_from_boxes_u8(images_u8, dims, bx, po, int(t["patch_offsets"][-1]), v.patch_size)
         pd = engine.VisionParams.from_tensors([x.detach() for x in self.vision_params().tensors()], v.num_hidden_layers)
-        cache = None if precision == "fp32" else (self._bf16_cache() if precision == "bf16" else self._f16_cache())
+        cache = {"fp32": lambda: None, "bf16": self._bf16_cache, "fp16": self._f16_cache,
+                 "fp32-split16": self._vsplit16_frozen_cache}[precision]()
         return engine.vision_fwd_packed(pd, cols, grids, cu, cu[:N], t["max_S"], v, precision, cache, self.packed_attention16)
 
     def _bf16_cache(self) -> dict:
@@ -358,6 +371,16 @@ class HipCLIPModel(nn.Module):
         if c is None:
             c = {}
             object.__setattr__(self, "_vsplit16_w", c)
+        return c
+
+    def _vsplit16_frozen_cache(self) -> dict:
+        """The FROZEN vision tower's host split-fp16 plan (precision "fp32-split16", engine.vision_fwd_frozen_split16): the
+        [hi|hi|lo] weight copies and host-float scales, built at the first such forward (one device-to-host read) and rebuilt when
+        a weight changes.  Never the training plan of _vsplit16_cache: that one's buffers are rewritten on the training stream."""
+        c = getattr(self, "_vsplit16_frozen_w", None)
+        if c is None:
+            c = {}
+            object.__setattr__(self, "_vsplit16_frozen_w", c)
         return c
 
     def invalidate_bf16_of_trainable(self) -> int:
@@ -438,22 +461,26 @@ class HipCLIPModel(nn.Module):
     def text_token_level_packed(self, input_ids: torch.Tensor, lens=None, precision: str = "fp32"):
         """text_token_level on packed captions: (sentence [B,P], tokens_packed [Tp,P], cu_seqlens on the device
         [B+1], tables).  Caption b's rows are tokens_packed[cu[b] : cu[b+1]] (BOS .. first EOS); `lens` as get_text_features'
-        `packed_lens` (None: derived from `input_ids` on the host).  tables: packed_text_tables' result (max_tokens, ...)."""
-        if precision not in ("fp32", "bf16", "fp16"):
+        `packed_lens` (None: derived from `input_ids` on the host).  tables: packed_text_tables' result (max_tokens, ...).
+        precision: as text_token_level; `packed_attention16` has no effect at "fp32" and "fp32-split16"."""
+        if precision not in ("fp32", "bf16", "fp16", "fp32-split16"):
             raise ValueError(f"precision {precision!r}")
         t = self.config.text
         if input_ids.shape[-1] > t.max_position_embeddings:
             raise ValueError(f"Sequence length must be less than max_position_embeddings (got {input_ids.shape[-1]})")
         dev = self.text_projection.weight.device
         tables = self._packed_text_tables(input_ids, lens, dev)
-        cache = None if precision == "fp32" else (self._bf16_cache() if precision == "bf16" else self._f16_cache())
+        cache = {"fp32": lambda: None, "bf16": self._bf16_cache, "fp16": self._f16_cache,
+                 "fp32-split16": self._split16_cache}[precision]()
         sent, tokens = engine.text_token_level_packed(self.text_params_detached(), input_ids.to(dev).long().contiguous(), tables,
                                                       t, precision, cache, self.packed_attention16)
         return sent, tokens, tables["cu_seqlens_dev"], tables
 
     @torch.no_grad()
     def text_token_level(self, input_ids: torch.Tensor, precision: str = "fp32"):
-        """Frozen pass used by the meta-teacher: (sentence [B,P], tokens [B,T,P], first-EOS index [B])."""
+        """Frozen pass used by the meta-teacher: (sentence [B,P], tokens [B,T,P], first-EOS index [B]).  precision "bf16" / "fp16":
+        16-bit GEMM inputs; "fp32-split16": the fp32 pass with every layer's GEMMs on split-fp16 operands (the text tower's
+        _split16_cache plan); "fp32": the plain fp32 GEMMs."""
         t = self.config.text
         ids = input_ids.long().contiguous()
         if precision == "bf16":
@@ -463,6 +490,8 @@ class HipCLIPModel(nn.Module):
                                                              torch.float16)
         elif precision == "fp32":
             sent, tokens, eos = engine.text_token_level(self.text_params_detached(), ids, t)
+        elif precision == "fp32-split16":      # every layer's GEMMs on the text tower's split-fp16 plan
+            sent, tokens, eos = engine.text_token_level_split16(self.text_params_detached(), ids, t, self._split16_cache())
         else:
             raise ValueError(f"precision {precision!r}")
         return sent, tokens.view(input_ids.shape[0], input_ids.shape[1], -1), eos

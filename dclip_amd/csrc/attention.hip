@@ -190,9 +190,14 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a, float* __rest
 //     dimensions per lane: 16-byte stores.
 //   * 16-row granularity: a causal wave w touches key tiles 0..w only (77 tokens: 15 of the 25 16x16 tiles).
 // IO16: a.q / a.k / a.v and `out` are bf16 (see the bf16 I/O note above); lse stays fp32.
-template <int KT, bool CAUSAL, bool IO16 = false>
+// SPLIT (2 / 3, fp32 input): `out` is the fp16 split of so.scale * context and lse is not written (SplitOut, attention_tiles.h):
+// a lane's 16-byte fp32 store becomes one 8-byte store per piece.
+template <int KT, bool CAUSAL, bool IO16 = false, int SPLIT = 0, typename... SO>
 __global__ void __launch_bounds__(KT * 64) attn_fwd_rows_kernel(AttnArgs a, float* __restrict__ out,
-                                                                float* __restrict__ lse) {
+                                                                float* __restrict__ lse, SO... so_) {
+  static_assert(!SPLIT || !IO16, "the split output is of the fp32 instance");
+  static_assert(sizeof...(SO) == (SPLIT ? 1 : 0), "a SplitOut argument exactly for the SPLIT instances");
+  const SplitOut so = split_out(so_...);
   constexpr int R = KT * 16;
   extern __shared__ __attribute__((aligned(16))) float lds_rows[];
   float* Ks = lds_rows;
@@ -312,12 +317,17 @@ __global__ void __launch_bounds__(KT * 64) attn_fwd_rows_kernel(AttnArgs a, floa
       unsigned short* orow = reinterpret_cast<unsigned short*>(out) + ((size_t)b * S + query) * D + h * HD + 4 * qd;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<u16x4a*>(orow + 16 * dt) = f32_to_bf4(o[dt] * inv);
+    } else if constexpr (SPLIT != 0) {
+      unsigned short* yrow = reinterpret_cast<unsigned short*>(out) + ((size_t)b * S + query) * so.ldy + h * HD + 4 * qd;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) split_store4<SPLIT>(yrow + 16 * dt, D, o[dt] * inv, so.scale);
     } else {
       float* orow = out + ((size_t)b * S + query) * D + h * HD + 4 * qd;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(orow + 16 * dt) = o[dt] * inv;
     }
-    if (qd == 0) lse[(size_t)bh * S + query] = mx + __logf(sum);
+    if constexpr (SPLIT == 0)
+      if (qd == 0) lse[(size_t)bh * S + query] = mx + __logf(sum);
   }
 }
 
@@ -328,8 +338,16 @@ __global__ void __launch_bounds__(KT * 64) attn_fwd_rows_kernel(AttnArgs a, floa
 // keys {(r&3) + 8(r>>2) + 4 half} of a 32-key block in registers r = 0..15 — which is exactly the pair of keys one
 // 32x32x2 MFMA step r of O^T = V^T P^T contracts (k-slot = half).  P never leaves registers; the running max / sum
 // and the accumulator rescale are per-lane scalars; O^T leaves as 16-byte stores.
-template <bool CAUSAL>
-__global__ void __launch_bounds__(256) attn_fwd_stream_kernel(AttnArgs a, float* __restrict__ out, float* __restrict__ lse) {
+// SPLIT: as in attn_fwd_rows_kernel — the lane's 4 consecutive head dimensions leave as one 8-byte store per piece.  The
+// non-causal SPLIT instances (the vision tower's) ask for two waves per SIMD: left alone the allocator takes 229 VGPRs beside 32
+// AGPRs, five more than the fp32 instance and one wave less; asked, it keeps the accumulators in VGPRs (229 + 0), no scratch.
+// Every other instance carries the default (1), and its code is what it was without the attribute.
+template <bool CAUSAL, int SPLIT = 0, typename... SO>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SPLIT != 0 && !CAUSAL) ? 2 : 1)))
+attn_fwd_stream_kernel(AttnArgs a, float* __restrict__ out, float* __restrict__ lse,
+                                                              SO... so_) {
+  static_assert(sizeof...(SO) == (SPLIT ? 1 : 0), "a SplitOut argument exactly for the SPLIT instances");
+  const SplitOut so = split_out(so_...);
   // (a double-buffered LDS-DMA staging of the K / V tiles was measured SLOWER here: 272 vs 255 us at B/16 — the
   // second stage halves the workgroups per CU's LDS headroom and the DMA issue competes with the MFMA stream)
   __shared__ __attribute__((aligned(16))) float lds[2 * TS * HD];
@@ -439,6 +457,16 @@ __global__ void __launch_bounds__(256) attn_fwd_stream_kernel(AttnArgs a, float*
   }
   if (query < S) {
     const float inv = 1.0f / l;
+    if constexpr (SPLIT != 0) {
+      unsigned short* yrow = reinterpret_cast<unsigned short*>(out) + ((size_t)b * S + query) * so.ldy + h * HD + 4 * half;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const f32x4 v = {o[dt][4 * j] * inv, o[dt][4 * j + 1] * inv, o[dt][4 * j + 2] * inv, o[dt][4 * j + 3] * inv};
+          split_store4<SPLIT>(yrow + 32 * dt + 8 * j, D, v, so.scale);
+        }
+    } else {
     float* orow = out + ((size_t)b * S + query) * D + h * HD + 4 * half;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
@@ -448,6 +476,7 @@ __global__ void __launch_bounds__(256) attn_fwd_stream_kernel(AttnArgs a, float*
         *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * j) = v;
       }
     if (half == 0) lse[(size_t)bh * S + query] = m + __logf(l);
+    }
   }
 }
 
@@ -1490,6 +1519,58 @@ DCLIP_API int dclip_attention_fwd(const float* qkv, float* out, float* lse, int 
   const int D = H * HD;
   AttnArgs a{qkv, qkv + D, qkv + 2 * D, 3 * D, 3 * D, S, S, H, nullptr};
   return launch_fwd(a, out, lse, B, causal, (hipStream_t)stream);
+}
+
+// dclip_attention_fwd that writes the context ALREADY SPLIT: y fp16 [B*S][ldy >= pieces D] = [hi|lo] (pieces 2) or
+// [hi|lo|hi] (3) of scale * context, bit-equal to dclip_attention_fwd followed by dclip_split_f32_f16x2 / _f16x3(order 0); columns
+// past pieces D of a row are not written, and there is no lse (a frozen forward).  The whole-row kernel up to 80 tokens, the
+// streamed one above; DCLIP_ATTN_TILED is not read (there is no tiled form).
+namespace {
+template <int KT, int P>
+void launch_fwd_rows_split(const AttnArgs& a, void* y, SplitOut so, int B, int causal, hipStream_t st) {
+  const size_t lds = (size_t)2 * KT * 16 * HD * sizeof(float);
+  float* out = reinterpret_cast<float*>(y);                       // re-typed inside the kernel
+  if (causal)
+    hipLaunchKernelGGL((attn_fwd_rows_kernel<KT, true, false, P, SplitOut>), dim3(B * a.H), dim3(KT * 64), lds, st, a, out, (float*)nullptr, so);
+  else
+    hipLaunchKernelGGL((attn_fwd_rows_kernel<KT, false, false, P, SplitOut>), dim3(B * a.H), dim3(KT * 64), lds, st, a, out, (float*)nullptr, so);
+}
+
+template <int P>
+void launch_fwd_split(const AttnArgs& a, void* y, SplitOut so, int B, int causal, hipStream_t st) {
+  if (a.Sk <= 80) {
+    switch (cdiv(a.Sk, 16)) {
+      case 1: launch_fwd_rows_split<1, P>(a, y, so, B, causal, st); break;
+      case 2: launch_fwd_rows_split<2, P>(a, y, so, B, causal, st); break;
+      case 3: launch_fwd_rows_split<3, P>(a, y, so, B, causal, st); break;
+      case 4: launch_fwd_rows_split<4, P>(a, y, so, B, causal, st); break;
+      default: launch_fwd_rows_split<5, P>(a, y, so, B, causal, st); break;
+    }
+    return;
+  }
+  dim3 g2(B * a.H, cdiv(a.Sq, 128));
+  float* out = reinterpret_cast<float*>(y);
+  if (causal) hipLaunchKernelGGL((attn_fwd_stream_kernel<true, P, SplitOut>), g2, dim3(256), 0, st, a, out, (float*)nullptr, so);
+  else hipLaunchKernelGGL((attn_fwd_stream_kernel<false, P, SplitOut>), g2, dim3(256), 0, st, a, out, (float*)nullptr, so);
+}
+}  // namespace
+
+DCLIP_API int dclip_attention_fwd_f16x2(const float* qkv, void* y, int B, int S, int H, int causal, float scale, int pieces,
+                                        int ldy, void* stream) {
+  DCLIP_REQUIRE(qkv && y, "attention_fwd_f16x2: null pointer");
+  DCLIP_REQUIRE(B > 0 && S > 0 && H > 0, "attention_fwd_f16x2: bad shape B=%d S=%d H=%d", B, S, H);
+  DCLIP_REQUIRE(pieces == 2 || pieces == 3, "attention_fwd_f16x2: pieces is 2 ([hi|lo]) or 3 ([hi|lo|hi])");
+  DCLIP_REQUIRE(ldy % 4 == 0 && (long)ldy >= (long)pieces * H * HD, "attention_fwd_f16x2: ldy (multiple of 4, >= pieces H 64)");
+  DCLIP_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)y % 8 == 0, "attention_fwd_f16x2: qkv 16-byte, y 8-byte aligned");
+  DCLIP_REQUIRE(scale > 0.f && scale - scale == 0.f && (__builtin_bit_cast(unsigned int, scale) & 0x007fffffu) == 0,
+                "attention_fwd_f16x2: scale must be a power of two");
+  const int D = H * HD;
+  AttnArgs a{qkv, qkv + D, qkv + 2 * D, 3 * D, 3 * D, S, S, H, nullptr};
+  const SplitOut so{scale, ldy};
+  if (pieces == 2) launch_fwd_split<2>(a, y, so, B, causal, (hipStream_t)stream);
+  else launch_fwd_split<3>(a, y, so, B, causal, (hipStream_t)stream);
+  DCLIP_CHECK_LAUNCH_V("attention_fwd_f16x2", S <= 80 ? ".rows" : ".stream");
+  return DCLIP_OK;
 }
 
 DCLIP_API int dclip_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse,

@@ -102,6 +102,45 @@ __device__ __forceinline__ void mma_tilerows_x_tile(f32x4 (&acc)[4], const float
   }
 }
 
+// The forward instances that write their context ALREADY SPLIT (template parameter SPLIT = pieces): `out` is
+// then fp16 [rows][ldy >= SPLIT D] = [hi|lo] (2) or [hi|lo|hi] (3) of scale * context — split1 on the fp32 value the SPLIT = 0
+// instance would have stored, so the result is bit-equal to that instance followed by the stand-alone split pass — and no lse
+// is written.  The argument is a trailing parameter pack of the kernel, empty for SPLIT = 0: those instances keep their
+// signature, and their code is what it was without the parameter.
+struct SplitOut {
+  float scale;
+  int ldy;
+};
+__device__ __forceinline__ SplitOut split_out() { return SplitOut{1.f, 0}; }
+__device__ __forceinline__ SplitOut split_out(SplitOut so) { return so; }
+
+typedef unsigned short u16x4s __attribute__((ext_vector_type(4)));
+
+// four consecutive columns of a row: one 8-byte store per piece.  yr = the hi piece's address, D = columns per piece.
+template <int SPLIT>
+__device__ __forceinline__ void split_store4(unsigned short* yr, int D, const f32x4& c, float scale) {
+  u16x4s hi, lo;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    unsigned short h, l;
+    split1(c[e] * scale, h, l);
+    hi[e] = h, lo[e] = l;
+  }
+  *reinterpret_cast<u16x4s*>(yr) = hi;
+  *reinterpret_cast<u16x4s*>(yr + D) = lo;
+  if (SPLIT == 3) *reinterpret_cast<u16x4s*>(yr + 2 * D) = hi;
+}
+
+// one column (the tiled kernels, whose lanes own a column of 16): 2-byte stores
+template <int SPLIT>
+__device__ __forceinline__ void split_store1(unsigned short* yr, int D, float c, float scale) {
+  unsigned short h, l;
+  split1(c * scale, h, l);
+  yr[0] = h;
+  yr[D] = l;
+  if (SPLIT == 3) yr[2 * D] = h;
+}
+
 __device__ __forceinline__ void zero4(f32x4 (&a)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) a[i] = f32x4{0.f, 0.f, 0.f, 0.f};

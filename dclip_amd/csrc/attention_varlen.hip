@@ -15,9 +15,15 @@ namespace {
 // grid (N*H, query tiles).  CLS: only row 0 of each sequence is a query (the last layer's pruned schedule): out [N][H*64],
 // lse [H][N]; otherwise out [T][H*64], lse [H][T].  T = cu[N]; every cu entry is clamped into [0, T] and made non-decreasing
 // here, so a malformed table cannot send a load or a store past the T rows the caller allocated.
-template <bool CLS>
+// SPLIT (2 / 3, every row a query): `out` is the fp16 split of so.scale * context, [T][so.ldy], and lse is not written
+// (SplitOut, attention_tiles.h).
+template <bool CLS, int SPLIT = 0, typename... SO>
 __global__ void __launch_bounds__(256) attn_varlen_fwd_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ cu,
-                                                              float* __restrict__ out, float* __restrict__ lse, int N, int H) {
+                                                              float* __restrict__ out, float* __restrict__ lse, int N, int H,
+                                                              SO... so_) {
+  static_assert(!SPLIT || !CLS, "the one-row form stays fp32");
+  static_assert(sizeof...(SO) == (SPLIT ? 1 : 0), "a SplitOut argument exactly for the SPLIT instances");
+  const SplitOut so = split_out(so_...);
   const int n = blockIdx.x / H, h = blockIdx.x % H;
   const int T = cu[N];
   const int s0 = min(max(cu[n], 0), T);
@@ -115,9 +121,15 @@ __global__ void __launch_bounds__(256) attn_varlen_fwd_kernel(const float* __res
     const int row = q0 + 16 * wave + 4 * qd + r;
     if (row < Sq) {
       const float inv = 1.0f / l[r];
+      if constexpr (SPLIT != 0) {
+        unsigned short* yrow = reinterpret_cast<unsigned short*>(out) + (orow0 + row) * so.ldy + h * HD + l15;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) split_store1<SPLIT>(yrow + nt * 16, D, o[nt][r] * inv, so.scale);
+      } else {
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) out[(orow0 + row) * D + h * HD + nt * 16 + l15] = o[nt][r] * inv;
       if (lse && l15 == 0) lse[(size_t)h * lse_ld + orow0 + row] = m[r] + __logf(l[r]);
+      }
     }
   }
 }
@@ -127,10 +139,14 @@ __global__ void __launch_bounds__(256) attn_varlen_fwd_kernel(const float* __res
 // its own sequence, key tiles beyond the query tile are not visited.  grid (N*H, query tiles).  LAST: the only query is the
 // LAST row of each sequence, which sees all of its keys (the ragged twin of the one-row kernel behind dclip_attention_row_fwd):
 // out [N][H*64], lse [H][N], grid (N*H, 1); otherwise out [T][H*64], lse [H][T].  The table is clamped as above.
-template <bool LAST>
+// SPLIT: as in attn_varlen_fwd_kernel.
+template <bool LAST, int SPLIT = 0, typename... SO>
 __global__ void __launch_bounds__(256) attn_varlen_causal_fwd_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                                      float* __restrict__ out, float* __restrict__ lse, int N,
-                                                                     int H) {
+                                                                     int H, SO... so_) {
+  static_assert(!SPLIT || !LAST, "the one-row form stays fp32");
+  static_assert(sizeof...(SO) == (SPLIT ? 1 : 0), "a SplitOut argument exactly for the SPLIT instances");
+  const SplitOut so = split_out(so_...);
   const int n = blockIdx.x / H, h = blockIdx.x % H;
   const int T = cu[N];
   const int s0 = min(max(cu[n], 0), T);
@@ -230,9 +246,15 @@ __global__ void __launch_bounds__(256) attn_varlen_causal_fwd_kernel(const float
     const int row = q0 + 16 * wave + 4 * qd + r;
     if (row < Sq) {
       const float inv = 1.0f / l[r];
+      if constexpr (SPLIT != 0) {
+        unsigned short* yrow = reinterpret_cast<unsigned short*>(out) + (orow0 + row) * so.ldy + h * HD + l15;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) split_store1<SPLIT>(yrow + nt * 16, D, o[nt][r] * inv, so.scale);
+      } else {
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) out[(orow0 + row) * D + h * HD + nt * 16 + l15] = o[nt][r] * inv;
       if (lse && l15 == 0) lse[(size_t)h * lse_ld + orow0 + row] = m[r] + __logf(l[r]);
+      }
     }
   }
 }
@@ -270,5 +292,37 @@ DCLIP_API int dclip_attention_varlen_causal_fwd(const float* qkv, const int32_t*
     hipLaunchKernelGGL((attn_varlen_causal_fwd_kernel<false>), dim3(N * H, cdiv(max_S, TS)), dim3(256), 0, st, qkv, cu_seqlens,
                        out, lse, N, H);
   DCLIP_CHECK_LAUNCH("attention_varlen_causal_fwd");
+  return DCLIP_OK;
+}
+
+// The two entries above (every row a query) writing the context ALREADY SPLIT: y fp16 [T][ldy >= pieces H 64] =
+// [hi|lo] (pieces 2) or [hi|lo|hi] (3) of scale * context, bit-equal to the fp32 entry followed by dclip_split_f32_f16x2 /
+// _f16x3(order 0); columns past pieces H 64 of a row are not written; no lse.
+DCLIP_API int dclip_attention_varlen_fwd_f16x2(const float* qkv, const int32_t* cu_seqlens, void* y, int N, int max_S, int H,
+                                               int causal, float scale, int pieces, int ldy, void* stream) {
+  DCLIP_REQUIRE(qkv && cu_seqlens && y, "attention_varlen_fwd_f16x2: null pointer");
+  DCLIP_REQUIRE(N > 0 && max_S > 0 && H > 0 && (long long)N * H < (1ll << 31),
+                "attention_varlen_fwd_f16x2: bad shape N=%d max_S=%d H=%d", N, max_S, H);
+  DCLIP_REQUIRE(pieces == 2 || pieces == 3, "attention_varlen_fwd_f16x2: pieces is 2 ([hi|lo]) or 3 ([hi|lo|hi])");
+  DCLIP_REQUIRE(ldy > 0 && (long)ldy >= (long)pieces * H * HD, "attention_varlen_fwd_f16x2: ldy >= pieces H 64");
+  DCLIP_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)cu_seqlens % 4 == 0 && (uintptr_t)y % 2 == 0,
+                "attention_varlen_fwd_f16x2: qkv must be 16-byte, cu_seqlens 4-byte, y 2-byte aligned");
+  DCLIP_REQUIRE(scale > 0.f && scale - scale == 0.f && (__builtin_bit_cast(unsigned int, scale) & 0x007fffffu) == 0,
+                "attention_varlen_fwd_f16x2: scale must be a power of two");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(N * H, cdiv(max_S, TS));
+  float* out = reinterpret_cast<float*>(y);                       // re-typed inside the kernel
+  const SplitOut so{scale, ldy};
+#define VARLEN_SPLIT(KERNEL, P) \
+  hipLaunchKernelGGL((KERNEL<false, P, SplitOut>), grid, dim3(256), 0, st, qkv, cu_seqlens, out, (float*)nullptr, N, H, so)
+  if (causal) {
+    if (pieces == 2) VARLEN_SPLIT(attn_varlen_causal_fwd_kernel, 2);
+    else VARLEN_SPLIT(attn_varlen_causal_fwd_kernel, 3);
+  } else {
+    if (pieces == 2) VARLEN_SPLIT(attn_varlen_fwd_kernel, 2);
+    else VARLEN_SPLIT(attn_varlen_fwd_kernel, 3);
+  }
+#undef VARLEN_SPLIT
+  DCLIP_CHECK_LAUNCH_V("attention_varlen_fwd_f16x2", causal ? ".causal" : ".full");
   return DCLIP_OK;
 }

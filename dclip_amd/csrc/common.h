@@ -93,6 +93,20 @@ __device__ __forceinline__ float quick_gelu_grad_f(float x) {
   return s * (1.0f + 1.702f * x * (1.0f - s));
 }
 
+// ---- the split-fp16 pieces of one value (split16.hip, and the attention forwards that write their context split)
+// hi = fp16(v), lo = fp16(v - hi).  v - float(hi) is exact in fp32 (hi is v to 11 bits), so each piece has ONE rounding
+// whether or not the compiler folds the subtraction into the conversion.
+// v (the caller's x * scale) is pinned in a register first.  Left to itself the compiler converts the product twice: the hi it
+// stores from the product, the hi it subtracts as fp16(fma(x, scale, +0)) — which is +0 for a product of -0 — and lo came out
+// as -0 - (+0) = -0 where IEEE (and every other instance of this function) gives -0 - (-0) = +0.
+static __device__ __forceinline__ void split1(float v, unsigned short& hi, unsigned short& lo) {
+  asm volatile("" : "+v"(v));
+  const _Float16 h = (_Float16)v;
+  const _Float16 l = (_Float16)(v - (float)h);
+  hi = __builtin_bit_cast(unsigned short, h);
+  lo = __builtin_bit_cast(unsigned short, l);
+}
+
 // ---- 16-bit element types of the frozen-tower forward.  The 16-bit kernels are templates over one of these traits; loads,
 // LDS layouts, the transposing LDS read and the MFMA C/D layouts do not depend on the type, only the MFMA instruction and
 // the fp32 -> 16-bit rounding do.

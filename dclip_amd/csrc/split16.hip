@@ -18,19 +18,6 @@ typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
 typedef int i32x4s __attribute__((ext_vector_type(4)));
 
-// hi = fp16(v), lo = fp16(v - hi).  v - float(hi) is exact in fp32 (hi is v to 11 bits), so each piece has ONE rounding
-// whether or not the compiler folds the subtraction into the conversion.
-// v (the caller's x * scale) is pinned in a register first.  Left to itself the compiler converts the product twice: the hi it
-// stores from the product, the hi it subtracts as fp16(fma(x, scale, +0)) — which is +0 for a product of -0 — and lo came out
-// as -0 - (+0) = -0 where IEEE (and every other instance of this function) gives -0 - (-0) = +0.
-__device__ __forceinline__ void split1(float v, unsigned short& hi, unsigned short& lo) {
-  asm volatile("" : "+v"(v));
-  const _Float16 h = (_Float16)v;
-  const _Float16 l = (_Float16)(v - (float)h);
-  hi = __builtin_bit_cast(unsigned short, h);
-  lo = __builtin_bit_cast(unsigned short, l);
-}
-
 // 8 columns per thread: two 16-byte loads, three 16-byte stores.  ORDER 2: the two-piece form [hi | lo], the third
 // store — the duplicate hi no fused GEMM reads — left out; ldy >= 2 cols there.
 template <int ORDER>

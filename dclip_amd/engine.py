@@ -724,25 +724,40 @@ def vision_fwd_packed(p: VisionParams, cols: torch.Tensor, grids: torch.Tensor, 
     int32 on the device -> [N, P].  The schedule of vision_fwd without `save`: the last layer runs its out-projection and MLP on
     the N CLS rows only.  "bf16" / "fp16": 16-bit GEMM inputs with the persistent weight copies of `cache` (the model's cache of
     that type, as vision_fwd_bf16); the qkv projection writes fp32 for the fp32 packed attention core and the context is cast,
-    or with `attn16` (packed_attn16_route) q | k | v and the context stay 16-bit around the packed MFMA core."""
+    or with `attn16` (packed_attn16_route) q | k | v and the context stay 16-bit around the packed MFMA core.
+    "fp32-split16" (`cache`: the model's frozen split cache): the schedule of vision_fwd_frozen_split16 — layers
+    0 .. L-2 on split-fp16 operands with the context written split by the packed attention entry, the last layer's full-size qkv
+    projection too, its CLS-row steps in fp32; the "fp32" schedule, bit for bit, when the guard trips.  `attn16` has no effect."""
     v = cfg
     D, H, eps = v.hidden_size, v.num_attention_heads, v.layer_norm_eps
     if not p.layers:
         raise ValueError("vision_fwd_packed: the tower has no encoder layer")
-    if precision == "fp32":
+    if precision in ("fp32", "fp32-split16"):
+        if precision == "fp32-split16" and cache is None:
+            raise ValueError("vision_fwd_packed: precision 'fp32-split16' needs the model's frozen split cache")
+        plan = _vision_frozen_split16_plan(p.layers, v, cache) if precision == "fp32-split16" else None
         patch = ops.gemm(cols, p.patch_w.view(D, -1), ops.LAYOUT_NT)
         emb = ops.vision_assemble_varlen(patch, p.class_embedding, p.pos, grids, cu_seqlens, v.grid)
         del patch
         x, _, _ = ops.layernorm_fwd(emb, p.pre_w, p.pre_b, eps, save_stats=False)
-        for li, lp in enumerate(p.layers):
-            last = li == len(p.layers) - 1
-            ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, eps, save_stats=False)
-            qkv = ops.gemm(ln1, lp.qkv_w, ops.LAYOUT_NT, bias=lp.qkv_b)
-            attn = ops.attention_varlen_fwd(qkv, cu_seqlens, max_S, H, cls_only=last)
-            x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows_at(x, cls_rows) if last else x)
-            ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
-            g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
-            x = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)        # the last layer: [N, D], the CLS rows
+        if plan is not None:
+            pc = _layer_pieces(x.shape[0], D, v.intermediate_size, _SPLIT16_FC1_EPI)
+            ctx3 = _packed_ctx3(cu_seqlens, max_S, H, False, True)
+            for lp, ent in zip(p.layers[:-1], plan[:-1]):
+                x = _frozen_split16_layer(x, lp, ent, pc, eps, ctx3)
+            x = _frozen_split16_last_cls(x, p.layers[-1], plan[-1], eps,
+                                         lambda qkv: ops.attention_varlen_fwd(qkv, cu_seqlens, max_S, H, cls_only=True),
+                                         lambda xx: ops.gather_rows_at(xx, cls_rows))
+        else:
+            for li, lp in enumerate(p.layers):
+                last = li == len(p.layers) - 1
+                ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, eps, save_stats=False)
+                qkv = ops.gemm(ln1, lp.qkv_w, ops.LAYOUT_NT, bias=lp.qkv_b)
+                attn = ops.attention_varlen_fwd(qkv, cu_seqlens, max_S, H, cls_only=last)
+                x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows_at(x, cls_rows) if last else x)
+                ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
+                g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
+                x = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)    # the last layer: [N, D], the CLS rows
     else:
         if precision not in ("bf16", "fp16") or cache is None:
             raise ValueError(f"vision_fwd_packed: precision {precision!r} (16-bit precisions need the model's weight cache)")
@@ -1368,26 +1383,29 @@ def _split16_stamp(layers: List[LayerParams]) -> tuple:
     return tuple((t._version, t.data_ptr()) for lp in layers for t in (getattr(lp, f) for f in _SPLIT16_WATCHED))
 
 
-def _split16_plan(p: TextParams, cache: dict):
+def _split16_plan(layers_p: List[LayerParams], cache: dict, what: str = "split-fp16 text tower",
+                  off: str = "set DCLIP_TEXT_SPLIT16=0"):
     """Per weight version: the [hi|hi|lo] fp16 copies of W 2^f and the power-of-two activation scales of every layer, or
     None when the guard sends the tower to the plain fp32 path.  ONE device -> host read of the weight statistics, at
-    cache-build time (warm-up, before any graph capture); the copies are refreshed in place when a weight changes."""
-    stamp = _split16_stamp(p.layers)
+    cache-build time (warm-up, before any graph capture); the copies are refreshed in place when a weight changes.
+    `layers_p`: the frozen tower's encoder layers (the text tower's, or the vision tower's at precision "fp32-split16",
+    DESIGN.md §28); `what` heads the log records, `off` is their advice for a tower whose weights do move."""
+    stamp = _split16_stamp(layers_p)
     plan = cache.get("__split16__")
     if plan is not None and plan["stamp"] == stamp:
         return plan["layers"]
     if torch.cuda.is_current_stream_capturing():
-        _split16_log_once("split-fp16 text tower: weights changed while a graph is being captured; this capture takes the "
+        _split16_log_once(f"{what}: weights changed while a graph is being captured; this capture takes the "
                           "plain fp32 path (run one eager step first)")
         return None
     if plan is not None:
         # frozen weights do not move: a rebuild after the first costs a host read, and one on every call (a parameter that is
         # written each step, or a non-contiguous one whose contiguous copy has a new address each call) would do so every step
-        _split16_log_once("split-fp16 text tower: a weight's version or storage changed; the split copies and scales are rebuilt "
-                          "(one device-to-host read).  If a weight changes every step, set DCLIP_TEXT_SPLIT16=0")
-    D = p.layers[0].ln1_w.shape[0]
+        _split16_log_once(f"{what}: a weight's version or storage changed; the split copies and scales are rebuilt "
+                          f"(one device-to-host read).  If a weight changes every step, {off}")
+    D = layers_p[0].ln1_w.shape[0]
     rows = []
-    for lp in p.layers:
+    for lp in layers_p:
         wv, bv = lp.qkv_w[2 * D:], lp.qkv_b[2 * D:]
         rows.append(torch.stack([lp.ln1_w.abs().max(), lp.ln1_b.abs().max(), wv.abs().sum(1).max(), bv.abs().max(),
                                  lp.ln2_w.abs().max(), lp.ln2_b.abs().max(), lp.fc1_w.abs().sum(1).max(), lp.fc1_b.abs().max(),
@@ -1396,16 +1414,16 @@ def _split16_plan(p: TextParams, cache: dict):
     import math
     layers = []
     old = plan["layers"] if plan is not None and plan["layers"] is not None else None
-    for li, (lp, row) in enumerate(zip(p.layers, stats)):
+    for li, (lp, row) in enumerate(zip(layers_p, stats)):
         st = dict(zip(_SPLIT16_STATS, row))
         if not all(math.isfinite(v) for v in row):
             layers = None
-            _split16_log_once(f"split-fp16 text tower: non-finite weight in layer {li}; taking the plain fp32 path")
+            _split16_log_once(f"{what}: non-finite weight in layer {li}; taking the plain fp32 path")
             break
         exps = {k: split16_act_exp(b) for k, b in split16_layer_bounds(st, D).items()}
         if any(e is None for e in exps.values()):
             layers = None
-            _split16_log_once(f"split-fp16 text tower: an activation bound of layer {li} does not fit fp16 at any scale >= 2^-14; "
+            _split16_log_once(f"{what}: an activation bound of layer {li} does not fit fp16 at any scale >= 2^-14; "
                               "taking the plain fp32 path")
             break
         ent = {"e": exps, "f": {}, "w": {}}
@@ -1431,13 +1449,50 @@ def _split16_gemm(a3, ent, short: str, akey: str, **kw):
     return ops.gemm_f16(a3, ent["w"][short], alpha=alpha, **kw)
 
 
+# The attention context of a frozen split layer leaves the attention kernel already split (ops.attention_fwd_f16x2 /
+# ops.attention_varlen_fwd_f16x2) at precision "fp32-split16"; 0 = attention_fwd + the stand-alone split pass there
+# too (bit-identical results; the A/B of §28).  The paths that existed before that precision keep the two launches.
+_SPLIT16_ATTN_EPI = os.environ.get("DCLIP_SPLIT16_ATTN_EPI", "1") != "0"
+
+
+def _dense_ctx3(B: int, S: int, H: int, causal: bool, fused: bool):
+    """(qkv, scale, pieces) -> the split attention context of B sequences of S tokens: one launch (`fused` and the switch
+    above), or the fp32 context and the split pass."""
+    if fused and _SPLIT16_ATTN_EPI:
+        return lambda qkv, scale, pieces: ops.attention_fwd_f16x2(qkv, B, S, H, causal, scale, pieces)
+    return lambda qkv, scale, pieces: ops.split_f16x3(ops.attention_fwd(qkv, B, S, H, causal)[0], scale, pieces=pieces)
+
+
+def _packed_ctx3(cu, max_S: int, H: int, causal: bool, fused: bool):
+    """_dense_ctx3 for packed sequences (rows cu[n] .. cu[n+1]-1)."""
+    if fused and _SPLIT16_ATTN_EPI:
+        return lambda qkv, scale, pieces: ops.attention_varlen_fwd_f16x2(qkv, cu, max_S, H, causal, scale, pieces)
+    attn = ops.attention_varlen_causal_fwd if causal else ops.attention_varlen_fwd
+    return lambda qkv, scale, pieces: ops.split_f16x3(attn(qkv, cu, max_S, H), scale, pieces=pieces)
+
+
+def _frozen_split16_layer(x, lp: LayerParams, ent, pc: Dict[str, int], eps: float, ctx3):
+    """One full encoder layer of a frozen tower on the host plan's entry `ent` (_split16_plan): the four GEMMs on split-fp16
+    operands, everything else the fp32 kernels.  `pc`: _layer_pieces at these rows; `ctx3`: _dense_ctx3 / _packed_ctx3."""
+    e = ent["e"]
+    ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** e["ln1"], pieces=pc["ln1"])
+    qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
+    x1 = _split16_gemm(ctx3(qkv, 2.0 ** e["ctx"], pc["ctx"]), ent, "out", "ctx", bias=lp.out_b, residual=x)
+    ln2 = ops.layernorm_fwd_f16x3(x1, lp.ln2_w, lp.ln2_b, eps, 2.0 ** e["ln2"], pieces=pc["ln2"])
+    if _SPLIT16_FC1_EPI:
+        g3 = _split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True, split_out_scale=2.0 ** e["g"], out_pieces=pc["g"])
+    else:
+        g3 = ops.split_f16x3(_split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True), 2.0 ** e["g"], pieces=pc["g"])
+    return _split16_gemm(g3, ent, "fc2", "g", bias=lp.fc2_b, residual=x1)
+
+
 def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict):
     """text_fwd_frozen with every full-size GEMM evaluated on split-fp16 operands (see above); the last layer's EOS-row
     GEMMs (M = B), the final LayerNorm and the projection stay on ops.gemm.  `cache`: the split weights and scales, kept
     between calls.  Falls back to text_fwd_frozen when the switch is off or the guard trips."""
     t = cfg
     D = t.hidden_size
-    plan = _split16_plan(p, cache) if _SPLIT16 and len(p.layers) > 0 and D % 8 == 0 and t.intermediate_size % 8 == 0 else None
+    plan = _split16_plan(p.layers, cache) if _SPLIT16 and len(p.layers) > 0 and D % 8 == 0 and t.intermediate_size % 8 == 0 else None
     if plan is None:
         return text_fwd_frozen(p, input_ids, cfg)
     B, T = input_ids.shape
@@ -1445,18 +1500,9 @@ def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: 
     eos = ops.first_eos(input_ids, t.eos_token_id)
     x = ops.text_embed_fwd(input_ids, p.tok, p.pos)
     pc = _layer_pieces(x.shape[0], D, t.intermediate_size, _SPLIT16_FC1_EPI)
+    ctx3 = _dense_ctx3(B, T, H, True, False)
     for lp, ent in zip(p.layers[:-1], plan[:-1]):
-        e = ent["e"]
-        ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** e["ln1"], pieces=pc["ln1"])
-        qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
-        attn, _ = ops.attention_fwd(qkv, B, T, H, True)
-        x1 = _split16_gemm(ops.split_f16x3(attn, 2.0 ** e["ctx"], pieces=pc["ctx"]), ent, "out", "ctx", bias=lp.out_b, residual=x)
-        ln2 = ops.layernorm_fwd_f16x3(x1, lp.ln2_w, lp.ln2_b, eps, 2.0 ** e["ln2"], pieces=pc["ln2"])
-        if _SPLIT16_FC1_EPI:
-            g3 = _split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True, split_out_scale=2.0 ** e["g"], out_pieces=pc["g"])
-        else:
-            g3 = ops.split_f16x3(_split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True), 2.0 ** e["g"], pieces=pc["g"])
-        x = _split16_gemm(g3, ent, "fc2", "g", bias=lp.fc2_b, residual=x1)
+        x = _frozen_split16_layer(x, lp, ent, pc, eps, ctx3)
     lp, ent = p.layers[-1], plan[-1]
     ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"], pieces=pc["ln1"])
     qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
@@ -1466,6 +1512,65 @@ def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: 
     g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
     rows = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
     pooled, _, _ = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=False)
+    return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+
+
+# --------------------------------------------------------------------------------------------- frozen fp32 vision tower, split fp16
+# The frozen vision tower at precision "fp32-split16" (opt-in): the host plan above on the vision tower's layers,
+# in a cache of its own on the model (HipCLIPModel._vsplit16_frozen_cache) — never the student's device plan, whose buffers the
+# training stream rewrites.  The patch embedding, the pre / post LayerNorm and the projection stay fp32 (pixel magnitudes have no
+# bound derivable from the weights); precision "fp32" is untouched.
+
+_VFROZEN_WHAT = "split-fp16 frozen vision tower"
+
+
+def _vision_frozen_split16_plan(layers: List[LayerParams], cfg, cache: Optional[dict]):
+    """The frozen vision tower's host plan (_split16_plan's layers), or None: the plain fp32 path."""
+    if cache is None or not layers or cfg.hidden_size % 8 or cfg.intermediate_size % 8:
+        return None
+    return _split16_plan(layers, cache, _VFROZEN_WHAT, 'use precision="fp32"')
+
+
+def _frozen_split16_last_cls(x, lp: LayerParams, ent, eps: float, ctx_rows, x_rows):
+    """The pruned last layer of a frozen vision schedule on the host plan: LayerNorm1 and the qkv projection at full size on
+    split operands, then last_layer_fwd_cls's steps on the CLS rows — `ctx_rows(qkv)` their fp32 attention context, `x_rows(x)`
+    their residual rows — on ops.gemm (M = images).  Returns the final hidden state of the CLS rows."""
+    D = x.shape[1]
+    ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"], pieces=split16_pieces([(x.shape[0], 3 * D, D)]))
+    qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
+    x1 = ops.gemm(ctx_rows(qkv), lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=x_rows(x))
+    ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
+    g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
+    return ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
+
+
+def vision_fwd_frozen_split16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict, grid=None,
+                              hidden_out: Optional[list] = None) -> torch.Tensor:
+    """vision_fwd(save=False) with the full-size GEMMs of the encoder layers on split-fp16 operands: [B,3,H,W] -> [B,P].  `grid`
+    as in vision_fwd.  `cache`: the model's frozen split cache (copies and scales, kept between calls).  The plain fp32 forward,
+    bit for bit, when the guard trips (_split16_plan) and whenever hidden states are asked for."""
+    v = cfg
+    plan = _vision_frozen_split16_plan(p.layers, v, cache) if hidden_out is None else None
+    if plan is None:
+        return vision_fwd(p, pixel_values, cfg, False, hidden_out, grid=grid)[0]
+    B = pixel_values.shape[0]
+    S, D, H, eps = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads, v.layer_norm_eps
+    if grid is None:
+        cols, pos = ops.im2col(pixel_values, v.patch_size), p.pos
+    else:
+        pos = _grid_front(p, pixel_values, v, grid)
+        cols = ops.im2col_rect(pixel_values, v.patch_size)
+    patch = ops.gemm(cols, p.patch_w.view(D, -1), ops.LAYOUT_NT)
+    emb = ops.vision_assemble_fwd(patch, p.class_embedding, pos, B, S, D)
+    del patch, cols
+    x, _, _ = ops.layernorm_fwd(emb, p.pre_w, p.pre_b, eps, save_stats=False)
+    pc = _layer_pieces(x.shape[0], D, v.intermediate_size, _SPLIT16_FC1_EPI)
+    ctx3 = _dense_ctx3(B, S, H, False, True)
+    for lp, ent in zip(p.layers[:-1], plan[:-1]):
+        x = _frozen_split16_layer(x, lp, ent, pc, eps, ctx3)
+    cls_tok = _frozen_split16_last_cls(x, p.layers[-1], plan[-1], eps, lambda qkv: ops.attention_cls_fwd(qkv, B, S, H)[0],
+                                       lambda xx: ops.gather_rows(xx, None, B, S, D))
+    pooled, _, _ = ops.layernorm_fwd(cls_tok, p.post_w, p.post_b, eps, save_stats=False)
     return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
 
 
@@ -1779,6 +1884,28 @@ def text_token_level(p: TextParams, input_ids: torch.Tensor, cfg):
     return sentence, tokens, eos
 
 
+def text_token_level_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict):
+    """text_token_level at precision "fp32-split16" (DESIGN.md §28): EVERY layer is a full layer (every row is an output), its
+    four GEMMs on the split-fp16 operands of the text tower's plan (`cache`: the model's _split16_cache, the plan
+    text_fwd_frozen_split16 uses), the context written split by the causal attention entry; the final LayerNorm and the
+    projection stay fp32.  The plain fp32 pass, bit for bit, when the guard trips."""
+    t = cfg
+    D = t.hidden_size
+    plan = _split16_plan(p.layers, cache) if _SPLIT16 and len(p.layers) > 0 and D % 8 == 0 and t.intermediate_size % 8 == 0 else None
+    if plan is None:
+        return text_token_level(p, input_ids, cfg)
+    B, T = input_ids.shape
+    x = ops.text_embed_fwd(input_ids, p.tok, p.pos)
+    pc = _layer_pieces(x.shape[0], D, t.intermediate_size, _SPLIT16_FC1_EPI)
+    ctx3 = _dense_ctx3(B, T, t.num_attention_heads, True, True)
+    for lp, ent in zip(p.layers, plan):
+        x = _frozen_split16_layer(x, lp, ent, pc, t.layer_norm_eps, ctx3)
+    ln, _, _ = ops.layernorm_fwd(x, p.final_w, p.final_b, t.layer_norm_eps, save_stats=False)
+    tokens = ops.gemm(ln, p.proj_w, ops.LAYOUT_NT)
+    eos = ops.first_eos(input_ids, t.eos_token_id)
+    return ops.gather_rows(tokens, eos, B, T, tokens.shape[1]), tokens, eos
+
+
 # --------------------------------------------------------------------------------------------- packed frozen text forward
 # The frozen text tower on captions cut after their first EOS and laid back to back (DESIGN.md §23): caption n in rows
 # cu_seqlens[n] .. cu_seqlens[n+1]-1, Tp rows in all.  The tower is causal and pools at the first EOS, so no result reads a row
@@ -1788,10 +1915,11 @@ def text_token_level(p: TextParams, input_ids: torch.Tensor, cfg):
 # Forward only.
 
 def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str, plan=None, cache=None,
-                        attn16: Optional[bool] = None):
-    """`n_layers` full layers at M = Tp.  mode "fp32" (plan None) / "split16" (plan: _split16_plan's) / "bf16" / "fp16"
-    (cache: the model's weight cache of that type; fp32 q | k | v for the fp32 packed core, the context is cast — or, with
-    `attn16`, 16-bit q | k | v and context around the packed MFMA core, packed_attn16_route)."""
+                        attn16: Optional[bool] = None, ctx_fused: bool = False):
+    """`n_layers` full layers at M = Tp.  mode "fp32" (plan None) / "split16" (plan: _split16_plan's; `ctx_fused`: the context
+    leaves the attention kernel split, _packed_ctx3) / "bf16" / "fp16" (cache: the model's weight cache of that type; fp32
+    q | k | v for the fp32 packed core, the context is cast — or, with `attn16`, 16-bit q | k | v and context around the packed
+    MFMA core, packed_attn16_route)."""
     H, eps = cfg.num_attention_heads, cfg.layer_norm_eps
     pc = _layer_pieces(x.shape[0], cfg.hidden_size, cfg.intermediate_size, _SPLIT16_FC1_EPI) if mode == "split16" else None
     for li, lp in enumerate(layers[:n_layers]):
@@ -1804,19 +1932,7 @@ def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str
             g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
             x = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
         elif mode == "split16":
-            ent = plan[li]
-            e = ent["e"]
-            ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** e["ln1"], pieces=pc["ln1"])
-            qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
-            attn = ops.attention_varlen_causal_fwd(qkv, cu, max_S, H)
-            x1 = _split16_gemm(ops.split_f16x3(attn, 2.0 ** e["ctx"], pieces=pc["ctx"]), ent, "out", "ctx", bias=lp.out_b, residual=x)
-            ln2 = ops.layernorm_fwd_f16x3(x1, lp.ln2_w, lp.ln2_b, eps, 2.0 ** e["ln2"], pieces=pc["ln2"])
-            if _SPLIT16_FC1_EPI:
-                g3 = _split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True, split_out_scale=2.0 ** e["g"],
-                                   out_pieces=pc["g"])
-            else:
-                g3 = ops.split_f16x3(_split16_gemm(ln2, ent, "fc1", "ln2", bias=lp.fc1_b, gelu=True), 2.0 ** e["g"], pieces=pc["g"])
-            x = _split16_gemm(g3, ent, "fc2", "g", bias=lp.fc2_b, residual=x1)
+            x = _frozen_split16_layer(x, lp, plan[li], pc, eps, _packed_ctx3(cu, max_S, H, True, ctx_fused))
         else:
             k, pre = _OPS16[torch.bfloat16 if mode == "bf16" else torch.float16], f"t{li}."
             ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, eps)
@@ -1834,12 +1950,13 @@ def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str
 
 
 def _packed_text_mode(p: TextParams, cfg, precision: str, cache: Optional[dict], what: str, split16: bool):
-    """(mode, plan): "fp32" takes the split-fp16 plan exactly when the padded frozen forward would (text_fwd_frozen_split16)."""
-    if precision == "fp32":
+    """(mode, plan): "fp32" takes the split-fp16 plan exactly when the padded frozen forward would (text_fwd_frozen_split16);
+    "fp32-split16" (the token-level pass) whenever the guard lets it, whatever `split16` says."""
+    if precision in ("fp32", "fp32-split16"):
         plan = None
-        if split16 and cache is not None and _SPLIT16 and len(p.layers) > 0 and cfg.hidden_size % 8 == 0 \
+        if (split16 or precision == "fp32-split16") and cache is not None and _SPLIT16 and len(p.layers) > 0 and cfg.hidden_size % 8 == 0 \
                 and cfg.intermediate_size % 8 == 0:
-            plan = _split16_plan(p, cache)
+            plan = _split16_plan(p.layers, cache)
         return ("split16" if plan is not None else "fp32"), plan
     if precision not in ("bf16", "fp16") or cache is None:
         raise ValueError(f"{what}: precision {precision!r} (16-bit precisions need the model's weight cache)")
@@ -1897,13 +2014,15 @@ def text_token_level_packed(p: TextParams, input_ids: torch.Tensor, tables: dict
                             cache: Optional[dict] = None, attn16: Optional[bool] = None):
     """text_token_level / text_token_level_bf16 on packed captions: (sentence [N,P], tokens [Tp,P]), every layer at M = Tp;
     the word tokens of caption n are rows cu[n] + 1 .. cu[n+1] - 2, its sentence embedding is row cu[n+1] - 1.  "fp32" runs
-    the plain fp32 GEMMs, as text_token_level does.  `attn16`: as in text_fwd_frozen_packed (every layer is a full layer)."""
+    the plain fp32 GEMMs, as text_token_level does; "fp32-split16" (`cache`: the model's split-fp16 text cache) every layer's
+    GEMMs on split-fp16 operands with the causal attention-split entry, the final LayerNorm and the projection in fp32
+    (text_token_level_split16).  `attn16`: as in text_fwd_frozen_packed (every layer is a full layer)."""
     t = cfg
     mode, plan = _packed_text_mode(p, t, precision, cache, "text_token_level_packed", False)
     cu, last_rows, max_S = tables["cu_seqlens_dev"], tables["last_rows_dev"], tables["max_S"]
     x = ops.text_embed_varlen(input_ids, cu, p.tok, p.pos, tables["Tp"])
-    x = _packed_text_layers(x, p.layers, len(p.layers), cu, max_S, t, mode, plan, cache, attn16)
-    if mode == "fp32":
+    x = _packed_text_layers(x, p.layers, len(p.layers), cu, max_S, t, mode, plan, cache, attn16, ctx_fused=True)
+    if mode in ("fp32", "split16"):
         ln, _, _ = ops.layernorm_fwd(x, p.final_w, p.final_b, t.layer_norm_eps, save_stats=False)
         tokens = ops.gemm(ln, p.proj_w, ops.LAYOUT_NT)
     else:

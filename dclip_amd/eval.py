@@ -73,22 +73,32 @@ def zero_shot_topk(image_features: torch.Tensor, class_text_features: torch.Tens
     return retrieve_topk(image_features, class_text_features, k)
 
 
+PRECISIONS = ("fp32", "bf16", "fp16", "fp32-split16")      # of the frozen encoders' forward (--precision of the launchers)
+
+
+def text_precision(precision: str) -> str:
+    """What get_text_features is called with beside an image side at `precision`: "fp32-split16"  is a precision
+    of the IMAGE tower; the sentence-level text tower at "fp32" already runs its GEMMs on split-fp16 operands (§9c)."""
+    return "fp32" if precision == "fp32-split16" else precision
+
+
 def encoders(model, precision: str = "fp32", interpolate_pos_encoding: bool = False):
     """(image encoder, text encoder) of a CLIPImageDistillation (forward(image=)/forward(text=)) or a HipCLIPModel.
     `precision` "bf16" / "fp16": the frozen 16-bit forward of the towers (HipCLIPModel.get_*_features; the student's
-    towers for a CLIPImageDistillation) — evaluation never needs gradients.  `interpolate_pos_encoding`: the image encoder
+    towers for a CLIPImageDistillation) — evaluation never needs gradients.  "fp32-split16": the frozen fp32 image forward on
+    split-fp16 operands, the text side at "fp32" (text_precision).  `interpolate_pos_encoding`: the image encoder
     takes images of any size (the towers' get_image_features with that flag)."""
     if precision == "fp32" and not interpolate_pos_encoding:
         enc_i = (lambda x: model(image=x)) if hasattr(model, "student") else (lambda x: model.get_image_features(pixel_values=x))
         enc_t = (lambda x: model(text=x)) if hasattr(model, "student") else (lambda x: model.get_text_features(input_ids=x))
         return enc_i, enc_t
-    if precision not in ("fp32", "bf16", "fp16"):
+    if precision not in PRECISIONS:
         raise ValueError(f"precision {precision!r}")
     clip = model.student if hasattr(model, "student") else model
     dev = next(clip.parameters()).device
     kw = {"interpolate_pos_encoding": True} if interpolate_pos_encoding else {}
     return (lambda x: clip.get_image_features(pixel_values=x.to(dev), precision=precision, **kw),
-            lambda x: clip.get_text_features(input_ids=x.to(dev), precision=precision))
+            lambda x: clip.get_text_features(input_ids=x.to(dev), precision=text_precision(precision)))
 
 
 @torch.no_grad()
@@ -112,9 +122,9 @@ def zero_shot_ranks(image_features: torch.Tensor, class_text_features: torch.Ten
 def evaluate_zero_shot(clip_model, image_batches, label_batches, class_input_ids, normalize_images: bool = True,
                        precision: str = "fp32"):
     """top-1 / top-5 accuracy; images in [0,1] are normalised with CLIP mean/std as the reference does (:69-71).
-    `precision`: that of the frozen towers' forward ("fp32", "bf16" or "fp16")."""
+    `precision`: that of the frozen towers' forward ("fp32", "bf16", "fp16" or "fp32-split16": see encoders)."""
     dev = next(clip_model.parameters()).device
-    text = clip_model.get_text_features(input_ids=class_input_ids.to(dev), precision=precision)
+    text = clip_model.get_text_features(input_ids=class_input_ids.to(dev), precision=text_precision(precision))
     mean = torch.tensor(CLIP_MEAN, device=dev).view(1, 3, 1, 1)
     std = torch.tensor(CLIP_STD, device=dev).view(1, 3, 1, 1)
     top1 = top5 = total = 0

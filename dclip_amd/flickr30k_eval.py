@@ -81,7 +81,7 @@ def evaluate_model(model_name: str, device, max_images: int = 1000, dataset_json
     else:
         model = base
     eval_size = int(image_size) if image_size else size
-    # precision: the frozen encoders' forward (fp32 / bf16 / fp16)
+    # precision: the frozen encoders' forward (fp32 / bf16 / fp16 / fp32-split16)
     enc_i, enc_t = E.encoders(model, precision, interpolate_pos_encoding=eval_size != size)
     model.eval()
 
@@ -138,8 +138,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--checkpoint", type=str, default=None, help="Path to custom model checkpoint")
     parser.add_argument("--dataset_json", type=str, required=True, help="flickr30k_test_karpathy.json (local path)")
     parser.add_argument("--clip_path", type=str, required=True, help="local directory with HF CLIP weights + tokenizer")
-    parser.add_argument("--precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
-                        help="arithmetic of the frozen encoders' forward (fp32: exact; bf16 / fp16: 16-bit GEMM inputs)")
+    parser.add_argument("--precision", type=str, default="fp32", choices=list(E.PRECISIONS),
+                        help="arithmetic of the frozen encoders' forward (fp32: exact; bf16 / fp16: 16-bit GEMM inputs; fp32-split16: "
+                             "the image tower's fp32 forward on hi/lo split fp16 operands, fp32-grade error)")
     parser.add_argument("--image_size", type=int, default=None,
                         help="evaluate at N x N pixels (default: the model's size; another N resamples the position table)")
     return parser

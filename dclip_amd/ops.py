@@ -272,6 +272,34 @@ def attention_fwd(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool):
     return out, lse
 
 
+def _split_ctx_out(what: str, rows: int, D: int, pieces: int, out: Optional[torch.Tensor], device) -> torch.Tensor:
+    """The fp16 destination of an attention forward that writes its context split: fresh [rows, pieces D], or the caller's
+    contiguous `out` [rows, ldy >= pieces D] (the columns past pieces D are left as they are)."""
+    if pieces not in (2, 3):
+        raise ValueError(f"{what}: pieces {pieces} (2 = [hi|lo], 3 = [hi|lo|hi])")
+    if out is None:
+        return torch.empty((rows, pieces * D), dtype=torch.float16, device=device)
+    _f16(out, "out")
+    if out.dim() != 2 or out.shape[0] != rows or out.shape[1] < pieces * D:
+        raise ValueError(f"{what}: out {tuple(out.shape)}, expected [{rows}, >= {pieces * D}]")
+    return out
+
+
+def attention_fwd_f16x2(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool, scale: float = 1.0, pieces: int = 2,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attention_fwd whose context leaves the kernel as the split operand of the next GEMM: fp16
+    [B*S, pieces*H*64] = [hi|lo] (pieces 2) or [hi|lo|hi] (3) of scale * context (scale a power of two), bit-equal to
+    split_f16x3(attention_fwd(qkv)[0], scale, pieces=pieces).  No lse: forward only.  `out`: see _split_ctx_out."""
+    lib = _lib.load()
+    _f32(qkv, "qkv")
+    if qkv.numel() != B * S * 3 * H * 64:
+        raise ValueError(f"attention_fwd_f16x2: qkv has {qkv.numel()} elements, expected B*S*3*H*64 = {B * S * 3 * H * 64}")
+    y = _split_ctx_out("attention_fwd_f16x2", B * S, H * 64, pieces, out, qkv.device)
+    _lib.check(lib.dclip_attention_fwd_f16x2(qkv.data_ptr(), y.data_ptr(), B, S, H, int(bool(causal)), float(scale), int(pieces),
+                                             y.shape[1], _stream()), "attention_fwd_f16x2")
+    return y
+
+
 def attention_bwd_stats_plan(B: int, S: int, H: int) -> int:
     """Partial rows attention_bwd leaves with `stats` (B), 0 where that form does not exist (S == 1, S > 64)."""
     return int(_lib.load().dclip_attention_bwd_stats_plan(B, S, H))
@@ -2111,6 +2139,24 @@ def attention_varlen_causal_fwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max
     _lib.check(lib.dclip_attention_varlen_causal_fwd(qkv.data_ptr(), cu_seqlens.data_ptr(), out.data_ptr(), _ptr(lse), N, max_S,
                                                      H, int(bool(last_only)), _stream()), "attention_varlen_causal_fwd")
     return (out, lse) if want_lse else out
+
+
+def attention_varlen_fwd_f16x2(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_S: int, H: int, causal: bool = False,
+                               scale: float = 1.0, pieces: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attention_varlen_fwd (`causal` False) / attention_varlen_causal_fwd (True) over every row, with the context written as
+    the split operand of the next GEMM: fp16 [T, pieces*H*64] of scale * context, bit-equal to the fp32 entry
+    followed by split_f16x3(.., scale, pieces=pieces).  `out`: see _split_ctx_out."""
+    lib = _lib.load()
+    _f32(qkv, "qkv")
+    N = cu_seqlens.numel() - 1
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or N < 1 or H < 1 or max_S < 1 or qkv.shape[0] < N:
+        raise ValueError(f"attention_varlen_fwd_f16x2: qkv {tuple(qkv.shape)}, H {H}, {N} sequences, max_S {max_S}")
+    _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    y = _split_ctx_out("attention_varlen_fwd_f16x2", qkv.shape[0], H * 64, pieces, out, qkv.device)
+    _lib.check(lib.dclip_attention_varlen_fwd_f16x2(qkv.data_ptr(), cu_seqlens.data_ptr(), y.data_ptr(), N, max_S, H,
+                                                    int(bool(causal)), float(scale), int(pieces), y.shape[1], _stream()),
+               "attention_varlen_fwd_f16x2")
+    return y
 
 
 def pack_tokens_varlen(tokens, sentence, cu_seqlens: torch.Tensor, Tmax: int) -> torch.Tensor:

@@ -184,16 +184,23 @@ class AggregationFn(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------------------------ tokenizers
 
+TOWER_PRECISIONS = ("fp32", "bf16", "fp16", "fp32-split16")      # of the teacher's frozen towers (`tower_precision`)
+
+
 class CLIPTextTokenizer:
     """Frozen teacher text side (training/text_tokenizer.py).  `model` is a HipCLIPModel; `tokenizer` an HF
     CLIPTokenizer loaded from a LOCAL path, or None when callers pass token ids (synthetic configs).
     The BERT / GloVe word-complexity machinery of the reference (:26-143) is never called on this path."""
 
     def __init__(self, model: HipCLIPModel, tokenizer=None, max_chunk_size: int = 77, precision: str = "fp32"):
+        if precision not in TOWER_PRECISIONS:
+            raise ValueError(f"precision {precision!r}")
         self.model = model
         self.tokenizer = tokenizer
         self.max_chunk_size = max_chunk_size
-        self.precision = precision          # "bf16" / "fp16": opt-in 16-bit GEMM inputs for this frozen tower (DESIGN.md §9, §9b)
+        # "bf16" / "fp16": opt-in 16-bit GEMM inputs for this frozen tower (DESIGN.md §9, §9b); "fp32-split16": the fp32 pass with
+        # every layer's GEMMs on split-fp16 operands (§28).  Passed through to HipCLIPModel.text_token_level(_packed)
+        self.precision = precision
 
     @property
     def device(self):
@@ -238,8 +245,10 @@ class CLIPPatchTokenizer:
     """Frozen teacher region side (training/image_tokenizer.py:19-124) without the detector: boxes are inputs."""
 
     def __init__(self, clip_model: HipCLIPModel, precision: str = "fp32"):
+        if precision not in TOWER_PRECISIONS:
+            raise ValueError(f"precision {precision!r}")
         self.clip_model = clip_model
-        self.precision = precision
+        self.precision = precision       # of HipCLIPModel.get_image_features / get_image_features_crops
 
     @property
     def device(self):
@@ -399,7 +408,8 @@ class PatchTextAggregation(nn.Module):
                  tokenizer=None, tower_precision: str = "fp32", owns_clip: bool = False,
                  text_twin: Optional[HipCLIPModel] = None, full_resolution_packed: bool = False,
                  packed_text: bool = False, packed_attention16: Optional[bool] = None):
-        """`tower_precision` ("fp32" default = the reference's arithmetic; "bf16" / "fp16" opt-in) selects how the FROZEN
+        """`tower_precision` ("fp32" default = the reference's arithmetic; "bf16" / "fp16" opt-in; "fp32-split16" opt-in: fp32
+        with the towers' full-size GEMMs on hi/lo split fp16 operands, fp32-grade error) selects how the FROZEN
         region / text towers multiply; the trainable cross_modal_attention always runs in fp32.
         `owns_clip`: the towers are this teacher's private frozen copy (they follow `.to()` / `.cuda()` although they
         stay out of `state_dict()`).  `text_twin`: a model whose text tower held the SAME weights as `clip_model`'s
@@ -412,9 +422,10 @@ class PatchTextAggregation(nn.Module):
         (HipCLIPModel.text_token_level_packed + ops.pack_tokens_varlen); the token padding size then comes from
         those lengths, not from the device.  Without host lengths the padded path runs as before.
         `packed_attention16` (True / False; None leaves the model as it is): set as `clip_model.packed_attention16` — the two
-        packed passes above then run the 16-bit MFMA attention core at `tower_precision` "bf16" / "fp16" (DESIGN.md §24)."""
+        packed passes above then run the 16-bit MFMA attention core at `tower_precision` "bf16" / "fp16" (DESIGN.md §24); it has
+        no effect at "fp32" and "fp32-split16"."""
         super().__init__()
-        if tower_precision not in ("fp32", "bf16", "fp16"):
+        if tower_precision not in TOWER_PRECISIONS:
             raise ValueError(f"tower_precision {tower_precision!r}")
         if packed_attention16 is not None and clip_model is not None:
             clip_model.packed_attention16 = bool(packed_attention16)

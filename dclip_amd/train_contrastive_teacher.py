@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from . import functional
-from .patch_text_aggregation import PatchTextAggregation
+from .patch_text_aggregation import TOWER_PRECISIONS, PatchTextAggregation
 
 
 def seed_everything(seed: int = 42):
@@ -248,14 +248,15 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Path to save the trained teacher model")
     parser.add_argument("--clip_path", type=str, default=None, help="LOCAL directory with HF CLIP weights + tokenizer")
     parser.add_argument("--devices", type=int, default=1, help="GPUs of this node (one process per GPU, RCCL)")
-    parser.add_argument("--tower_precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
-                        help="arithmetic of the FROZEN CLIP towers (fp32: exact; bf16 / fp16: 16-bit GEMM inputs); "
+    parser.add_argument("--tower_precision", type=str, default="fp32", choices=list(TOWER_PRECISIONS),
+                        help="arithmetic of the FROZEN CLIP towers (fp32: exact; bf16 / fp16: 16-bit GEMM inputs; fp32-split16: "
+                             "fp32 with the full-size GEMMs on hi/lo split fp16 operands, fp32-grade error); "
                              "the cross-modal block always trains in fp32")
     parser.add_argument("--packed_text", action="store_true",
                         help="run the frozen text tower on captions cut after their first EOS and laid back to back "
                              "(lengths from the tokenizer's host output; default: the padded [B, T] rectangle)")
     parser.add_argument("--packed_attention16", action="store_true",
-                        help="with --tower_precision bf16 / fp16: the packed frozen towers keep q, k, v and the context in 16 "
+                        help="with --tower_precision bf16 / fp16 (no effect at fp32 / fp32-split16): the packed frozen towers keep q, k, v and the context in 16 "
                              "bits and run the packed MFMA attention core (default: the fp32 packed core and a cast)")
     return parser
 

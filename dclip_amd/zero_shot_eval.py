@@ -92,14 +92,15 @@ def make_prompts(classnames: Sequence[str], dataset_name: Optional[str] = None) 
 def evaluate_zero_shot(model_name: str, model, processor: Callable, dataloader, classnames: Sequence[str],
                        dataset_name: Optional[str] = None, precision: str = "fp32"):
     """Evaluate a single model for zero-shot classification (reference signature; see the module docstring).
-    `precision`: the frozen towers' forward ("fp32" default, "bf16" or "fp16": HipCLIPModel.get_*_features).  Images of
+    `precision`: the frozen towers' forward ("fp32" default, "bf16", "fp16", or "fp32-split16": the image tower's fp32 forward on
+    split-fp16 operands, the text side at "fp32"; HipCLIPModel.get_*_features).  Images of
     another size than the model's (--image_size) are encoded with interpolate_pos_encoding."""
     print(f"\nEvaluating {model_name}" + (f" on {dataset_name}" if dataset_name else "") + "...")
     clip = model if model_name == "base" or not hasattr(model, "student") else model.student
     dev = next(clip.parameters()).device
     tok = processor(text=make_prompts(classnames, dataset_name), return_tensors="pt", padding=True)
     ids = tok["input_ids"] if isinstance(tok, dict) or hasattr(tok, "keys") else tok
-    text_features = clip.get_text_features(input_ids=ids.to(dev), precision=precision)
+    text_features = clip.get_text_features(input_ids=ids.to(dev), precision=E.text_precision(precision))
     mean = torch.tensor(E.CLIP_MEAN, device=dev).view(1, 3, 1, 1)
     std = torch.tensor(E.CLIP_STD, device=dev).view(1, 3, 1, 1)
     correct_top1 = correct_top5 = total = 0
@@ -127,8 +128,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--max_images", type=int, default=0)
     ap.add_argument("--results", default=None, help="results text file (default <dataset>_zero_shot_results.txt)")
-    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "fp16"],
-                    help="arithmetic of the frozen encoders' forward (fp32: exact; bf16 / fp16: 16-bit GEMM inputs)")
+    ap.add_argument("--precision", default="fp32", choices=list(E.PRECISIONS),
+                    help="arithmetic of the frozen encoders' forward (fp32: exact; bf16 / fp16: 16-bit GEMM inputs; fp32-split16: "
+                         "the image tower's fp32 forward on hi/lo split fp16 operands, fp32-grade error)")
     ap.add_argument("--image_size", type=int, default=None,
                     help="evaluate at N x N pixels (default: the model's size; another N resamples the position table)")
     return ap

@@ -794,6 +794,24 @@ int dclip_gemm_f16x3_scaled_split2_dev(const void* A, const void* W, void* C, co
                                        int K, int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue,
                                        const float* alpha, const float* out_scale, void* stream);
 
+/* ---- attention forward that writes its context ALREADY SPLIT (the frozen towers at precision "fp32-split16"):
+ * the context of a frozen split-fp16 layer is read by one consumer, the split out-projection, so the fp32 [T][D] round trip
+ * through dclip_split_f32_f16x2 / _f16x3 is folded into the attention kernel's store.
+ *   y fp16 [rows][ldy >= pieces H 64] = [hi|lo] (pieces 2) or [hi|lo|hi] (pieces 3) of scale * context, scale a power of two:
+ *   hi = fp16(v), lo = fp16(v - hi), v = context * scale with the fp32 context dclip_attention_fwd / dclip_attention_varlen_fwd /
+ *   dclip_attention_varlen_causal_fwd stores — bit-equal to that entry followed by the stand-alone split (order 0), NaN for NaN.
+ *   Columns past pieces H 64 of a row are not written.  No lse: forward only.
+ *   attention_fwd_f16x2          qkv [B*S][3 H 64]; the whole-row kernel for S <= 80, the streamed kernel above (DCLIP_ATTN_TILED is
+ *                                not read: there is no tiled form); ldy % 4 == 0, qkv 16-byte and y 8-byte aligned.
+ *   attention_varlen_fwd_f16x2   packed sequences, every row a query; causal = 0: attention_varlen_fwd, 1: _causal_fwd; the table
+ *                                is clamped as there; qkv 16-byte aligned.
+ * Each refuses a null pointer, a non-positive dimension, pieces outside {2, 3}, a short ldy and a scale that is not a power of
+ * two with DCLIP_EINVAL before any launch. */
+int dclip_attention_fwd_f16x2(const float* qkv, void* y, int B, int S, int H, int causal, float scale, int pieces, int ldy,
+                              void* stream);
+int dclip_attention_varlen_fwd_f16x2(const float* qkv, const int32_t* cu_seqlens, void* y, int N, int max_S, int H, int causal,
+                                     float scale, int pieces, int ldy, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * fp16 TRAINING path (opt-in student_precision="fp16" / get_image_features(precision="fp16-mixed")): fp16
  * twins of the bf16 training entries above — same arguments, limits and kernels — with plain IEEE round-to-nearest-even:
