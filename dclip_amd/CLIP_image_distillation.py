@@ -70,11 +70,18 @@ def _as_hip_model(clip_model) -> HipCLIPModel:
     raise TypeError("clip_model must be a dclip_amd HipCLIPModel or a transformers CLIPModel")
 
 
+def packed_text_train_route(flag: bool, text_trainable: bool, have_host_lens: bool, capturing: bool) -> bool:
+    """Whether a step's student text features come from the packed TRAINABLE tower: the switch is on, the text
+    tower trains, the captions' lengths are known on the host and no graph is being captured (a captured graph's shapes must
+    not follow the batch).  Everything else is the padded path."""
+    return bool(flag and text_trainable and have_host_lens and not capturing)
+
+
 class CLIPImageDistillation(LightningLikeModule):
     def __init__(self, hparams, clip_model, clip_preprocess=None, teacher=None, freeze_mode: str = "north_star",
                  process_group=None, contrastive_teacher_path: Optional[str] = None, student_precision: str = "fp32",
                  full_resolution_from_epoch: Optional[int] = None, packed_text: bool = False,
-                 packed_attention16: Optional[bool] = None):
+                 packed_attention16: Optional[bool] = None, packed_text_train: bool = False):
         """`student_precision`: "fp32" (default: the reference's `precision=32`,
         training/CLIP_image_distill_training.py:40, and the benched config c2) or "bf16" — the student's VISION tower
         multiplies in bf16 (forward, dgrad, wgrad) with fp32 master weights, fp32 accumulation and fp32
@@ -91,9 +98,15 @@ class CLIPImageDistillation(LightningLikeModule):
         tower, the padded path runs as before.
         `packed_attention16` (True / False; None leaves the models as they are): set as `packed_attention16` on the student and
         on the teacher's towers — their packed frozen passes at "bf16" / "fp16" then run the 16-bit MFMA attention core
-        (DESIGN.md §24)."""
+        (DESIGN.md §24).
+        `packed_text_train` (also an attribute): where the student's text tower TRAINS (freeze_mode
+        "as_written"), the captions' lengths are known on the host (as for `packed_text`) and no graph is being captured, the
+        student's text features come from the packed trainable tower, forward and backward
+        (HipCLIPModel.get_text_features(packed_lens=..., packed_train=True)); otherwise the step runs as without it.  It
+        implies nothing about `packed_text`: the teacher's frozen passes follow that flag alone."""
         super().__init__()
         self.packed_text = bool(packed_text)
+        self.packed_text_train = bool(packed_text_train)
         self.packed_attention16 = None if packed_attention16 is None else bool(packed_attention16)
         if full_resolution_from_epoch is not None and int(full_resolution_from_epoch) < 0:
             raise ValueError(f"full_resolution_from_epoch {full_resolution_from_epoch!r}")
@@ -204,10 +217,11 @@ class CLIPImageDistillation(LightningLikeModule):
             raise RuntimeError("caption strings need clip_preprocess (an HF CLIPProcessor loaded from a local path)")
         return self.preprocess(text=captions, return_tensors="pt", padding=True, truncation=True)["input_ids"]
 
-    def _host_text_lens(self, host_ids=None, batch=None):
-        """Caption lengths (first EOS index + 1, int32 on the host) for the packed text paths, or None: `packed_text` off, or
-        no lengths without a device read — `batch["text_lens"]`, else token ids that are still on the host."""
-        if not self.packed_text:
+    def _host_text_lens(self, host_ids=None, batch=None, train: bool = False):
+        """Caption lengths (first EOS index + 1, int32 on the host) for the packed text paths, or None: `packed_text` off
+        (`train`: `packed_text_train` off), or no lengths without a device read — `batch["text_lens"]`, else token ids that are
+        still on the host."""
+        if not (self.packed_text_train if train else self.packed_text):
             return None
         if isinstance(batch, dict) and batch.get("text_lens") is not None:
             return batch["text_lens"]
@@ -302,6 +316,7 @@ class CLIPImageDistillation(LightningLikeModule):
             host_tokens = self._tokenize(batch["captions"])
             tokens = host_tokens.to(dev)
             text_lens = self._host_text_lens(host_tokens)
+            lens_src = {"host_ids": host_tokens}
             with torch.no_grad():
                 teacher_image = self.teacher.compute_global_embedding_batch(
                     batch["image_paths"], host_tokens, batch["weighted_boxes"], batch.get("images_u8"),
@@ -311,6 +326,7 @@ class CLIPImageDistillation(LightningLikeModule):
             images = batch["pixel_values"].to(dev)
             tokens = batch["input_ids"].to(dev)
             text_lens = self._host_text_lens(batch=batch)
+            lens_src = {"batch": batch}
             lens_kw = {} if text_lens is None else {"text_lens": text_lens}
             with torch.no_grad():
                 if "teacher_image_emb" in batch:
@@ -359,6 +375,7 @@ class CLIPImageDistillation(LightningLikeModule):
             host_tokens = self._tokenize(captions)
             tokens = host_tokens.to(dev)
             text_lens = self._host_text_lens(host_tokens)
+            lens_src = {"host_ids": host_tokens}
             with torch.no_grad():
                 # the teacher gets the HOST ids: it sizes its token padding from them without a stream sync
                 teacher_image = self.teacher.compute_global_embedding_batch(
@@ -409,7 +426,13 @@ class CLIPImageDistillation(LightningLikeModule):
             with torch.no_grad():          # frozen text tower (of a bf16 student: bf16 GEMM inputs there as well)
                 student_text = self.student.get_text_features(input_ids=tokens, precision=text_precision, **packed_kw).float()
         else:
-            student_text = self.student.get_text_features(input_ids=tokens).float()
+            # packed_text_train: the trainable tower on packed captions, forward and backward
+            train_lens = self._host_text_lens(train=True, **lens_src) if self.packed_text_train else None
+            capturing = tokens.is_cuda and torch.cuda.is_current_stream_capturing()
+            if packed_text_train_route(self.packed_text_train, not text_frozen, train_lens is not None, capturing):
+                student_text = self.student.get_text_features(input_ids=tokens, packed_lens=train_lens, packed_train=True).float()
+            else:
+                student_text = self.student.get_text_features(input_ids=tokens).float()
         if teacher_text is None:
             with torch.no_grad():
                 if self.teacher.shares_text_tower_with(self.student):

@@ -62,6 +62,9 @@ SIGNATURES = {
     "dclip_text_embed_varlen": (I, [P, P, P, P, P, I, I, I, I, P]),
     "dclip_attention_varlen_causal_fwd": (I, [P, P, P, P, I, I, I, I, P]),
     "dclip_pack_tokens_varlen": (I, [P, P, P, P, I, I, I, P]),
+    "dclip_attention_varlen_causal_bwd": (I, [P, P, P, P, P, P, P, I, I, I, P]),
+    "dclip_text_embed_varlen_bwd": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "dclip_scatter_last_rows": (I, [P, P, P, I, I, P]),
     "dclip_attention_varlen_fwd_bf16": (I, [P, P, P, I, I, I, I, P]),
     "dclip_attention_varlen_fwd_f16": (I, [P, P, P, I, I, I, I, P]),
     "dclip_attention_varlen_row_fwd_bf16": (I, [P, P, P, I, I, I, I, P]),

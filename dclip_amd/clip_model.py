@@ -401,7 +401,7 @@ class HipCLIPModel(nn.Module):
         return n
 
     def get_text_features(self, input_ids: torch.Tensor = None, attention_mask=None, precision: str = "fp32",
-                          packed_lens=None, **kwargs) -> torch.Tensor:
+                          packed_lens=None, packed_train: bool = False, **kwargs) -> torch.Tensor:
         """`attention_mask` is accepted and ignored: under the causal mask trailing pads cannot influence the
         first-EOS row that is pooled.  precision="bf16" / "fp16": frozen forward only (see
         get_image_features).  `packed_lens` (opt-in, frozen use only): the captions' lengths on the HOST
@@ -409,7 +409,12 @@ class HipCLIPModel(nn.Module):
         are then derived from it).  The tower then runs on the captions cut after their first EOS and laid back to back
         — the rows behind a first EOS are read by no result — under no_grad semantics.  Lengths are never read back from
         the device: True with ids that are not on the host is a ValueError.  While a stream is capturing the padded path
-        runs (a captured graph's shapes must not follow the batch)."""
+        runs (a captured graph's shapes must not follow the batch).
+        `packed_train` (opt-in, with `packed_lens`): with grad enabled, a trainable text parameter and
+        precision "fp32", the TRAINABLE tower runs on the packed captions, forward and backward (engine.text_fwd_packed) —
+        the padded tower's gradients from Tp rows instead of B T.  Without it that call is refused as before; under no_grad it
+        changes nothing; a 16-bit precision keeps the forward-only error; while a stream is capturing the padded trainable
+        path runs."""
         if input_ids is None:
             raise ValueError("You have to specify input_ids")
         t = self.config.text
@@ -424,11 +429,16 @@ class HipCLIPModel(nn.Module):
             raise ValueError(f"precision {precision!r}")
         p = self.text_params()
         if packed:
-            if torch.is_grad_enabled() and any(x.requires_grad for x in p.tensors()):
+            train = torch.is_grad_enabled() and any(x.requires_grad for x in p.tensors())
+            if train and not (packed_train and precision == "fp32"):
                 raise RuntimeError("packed_lens is a forward-only path for frozen towers: call it under torch.no_grad()")
             dev = p.tok.device
             if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
                 packed = False
+            elif train:
+                tables = self._packed_text_tables(input_ids, None if packed_lens is True else packed_lens, dev)
+                return functional.TextTowerPackedFn.apply(input_ids.to(dev).long().contiguous(), t, t.num_hidden_layers, tables,
+                                                          *p.tensors())
             else:
                 with torch.no_grad():
                     tables = self._packed_text_tables(input_ids, None if packed_lens is True else packed_lens, dev)

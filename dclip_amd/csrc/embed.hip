@@ -171,6 +171,59 @@ __global__ void __launch_bounds__(256) text_embed_varlen_kernel(const int64_t* _
   }
 }
 
+// The backward of text_embed_varlen_kernel, token half: dtok[clamp(ids[n, t]), :] += dx[cu[n] + t, :] for
+// t < len_n.  Same grid, table clamp and id clamp as the forward, the float atomics of text_embed_bwd_kernel (ids repeat);
+// ids[n, t >= len_n] are never read.
+__global__ void __launch_bounds__(256) text_embed_varlen_bwd_tok_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ cu,
+                                                                        const float* __restrict__ dx, float* __restrict__ dtok, int N,
+                                                                        int T, int D, int vocab) {
+  const int n = blockIdx.x;
+  const int Tp = cu[N];
+  const int row0 = min(max(cu[n], 0), Tp);
+  const int len = min(min(max(cu[n + 1], row0), Tp) - row0, T);
+  const int total = len * D;
+  for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < total; i += gridDim.y * blockDim.x) {
+    const int d = i % D, t = i / D;
+    int64_t id = ids[(size_t)n * T + t];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    atomicAdd(dtok + (size_t)id * D + d, dx[((size_t)row0 + t) * D + d]);
+  }
+}
+
+// Position half: dpos[t, :] = sum over the captions with len_n > t of dx[cu[n] + t, :], for every t < T (zeros where no
+// caption reaches).  One thread per 16-byte group of dpos adds in ascending n — no atomics, the same bits in every run.
+__global__ void __launch_bounds__(256) text_embed_varlen_bwd_pos_kernel(const int32_t* __restrict__ cu, const float* __restrict__ dx,
+                                                                        float* __restrict__ dpos, int N, int T, int D4) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= T * D4) return;
+  const int d = i % D4, t = i / D4;
+  const int Tp = cu[N];
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  for (int n = 0; n < N; ++n) {
+    const int row0 = min(max(cu[n], 0), Tp);
+    const int len = min(min(max(cu[n + 1], row0), Tp) - row0, T);
+    if (t < len) s = s + reinterpret_cast<const f32x4*>(dx)[((size_t)row0 + t) * D4 + d];
+  }
+  reinterpret_cast<f32x4*>(dpos)[i] = s;
+}
+
+// dx[cu[n+1] - 1, :] = dout[n, :], every other row of [cu[n], cu[n+1]) zero: the ragged twin of scatter_rows_kernel.  Grid
+// (N, chunks), a workgroup serves ONE caption as in text_embed_varlen_kernel; the table is clamped as there.
+__global__ void __launch_bounds__(256) scatter_last_rows_kernel(const float* __restrict__ dout, const int32_t* __restrict__ cu,
+                                                                float* __restrict__ dx, int N, int D4) {
+  const int n = blockIdx.x;
+  const int Tp = cu[N];
+  const int row0 = min(max(cu[n], 0), Tp);
+  const int len = min(max(cu[n + 1], row0), Tp) - row0;
+  const size_t total4 = (size_t)len * D4;
+  for (size_t i = (size_t)blockIdx.y * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.y * blockDim.x) {
+    const int d = (int)(i % D4), t = (int)(i / D4);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (t == len - 1) v = reinterpret_cast<const f32x4*>(dout)[(size_t)n * D4 + d];
+    reinterpret_cast<f32x4*>(dx)[((size_t)row0 + t) * D4 + d] = v;
+  }
+}
+
 }  // namespace
 
 DCLIP_API int dclip_im2col(const float* pixels, float* cols, int B, int C, int Himg, int Wimg, int patch, void* stream) {
@@ -309,5 +362,33 @@ DCLIP_API int dclip_text_embed_varlen(const int64_t* ids, const int32_t* cu_seql
   hipLaunchKernelGGL(text_embed_varlen_kernel, dim3(N, 4), dim3(256), 0, (hipStream_t)stream, ids, cu_seqlens, tok, pos, x, N, T,
                      D / 4, vocab);
   DCLIP_CHECK_LAUNCH("text_embed_varlen");
+  return DCLIP_OK;
+}
+
+DCLIP_API int dclip_text_embed_varlen_bwd(const int64_t* ids, const int32_t* cu_seqlens, const float* dx, float* dtok, float* dpos,
+                                          int N, int T, int D, int vocab, void* stream) {
+  DCLIP_REQUIRE(ids && cu_seqlens && dx && (dtok || dpos), "text_embed_varlen_bwd: null pointer");
+  DCLIP_REQUIRE(N > 0 && T > 0 && D > 0 && D % 4 == 0 && vocab > 0 && (long long)T * D < (1ll << 31),
+                "text_embed_varlen_bwd: bad shape N=%d T=%d D=%d vocab=%d", N, T, D, vocab);
+  DCLIP_REQUIRE(((uintptr_t)dx | (uintptr_t)dpos) % 16 == 0 && (uintptr_t)ids % 8 == 0 &&
+                    ((uintptr_t)cu_seqlens | (uintptr_t)dtok) % 4 == 0,
+                "text_embed_varlen_bwd: dx / dpos must be 16-byte aligned, ids 8-byte, cu_seqlens / dtok 4-byte aligned");
+  if (dtok)
+    hipLaunchKernelGGL(text_embed_varlen_bwd_tok_kernel, dim3(N, 4), dim3(256), 0, (hipStream_t)stream, ids, cu_seqlens, dx, dtok,
+                       N, T, D, vocab);
+  if (dpos)
+    hipLaunchKernelGGL(text_embed_varlen_bwd_pos_kernel, dim3(cdiv(T * (D / 4), 256)), dim3(256), 0, (hipStream_t)stream,
+                       cu_seqlens, dx, dpos, N, T, D / 4);
+  DCLIP_CHECK_LAUNCH("text_embed_varlen_bwd");
+  return DCLIP_OK;
+}
+
+DCLIP_API int dclip_scatter_last_rows(const float* dout, const int32_t* cu_seqlens, float* dx, int N, int D, void* stream) {
+  DCLIP_REQUIRE(dout && cu_seqlens && dx, "scatter_last_rows: null pointer");
+  DCLIP_REQUIRE(N > 0 && D > 0 && D % 4 == 0, "scatter_last_rows: bad shape N=%d D=%d", N, D);
+  DCLIP_REQUIRE(((uintptr_t)dout | (uintptr_t)dx) % 16 == 0 && (uintptr_t)cu_seqlens % 4 == 0,
+                "scatter_last_rows: dout / dx must be 16-byte aligned, cu_seqlens 4-byte aligned");
+  hipLaunchKernelGGL(scatter_last_rows_kernel, dim3(N, 4), dim3(256), 0, (hipStream_t)stream, dout, cu_seqlens, dx, N, D / 4);
+  DCLIP_CHECK_LAUNCH("scatter_last_rows");
   return DCLIP_OK;
 }

@@ -163,17 +163,24 @@ def _layer_pieces(T: int, D: int, I: int, fc1_epi: bool) -> Dict[str, int]:
 
 
 def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: float, save: bool, sp: Optional[Split16Layer] = None,
-              keep_split: bool = False):
+              keep_split: bool = False, varlen=None):
     """`keep_split` (with `save` and `sp`): the four [hi|lo|hi] (or [hi|lo], §9j) operands this forward produced anyway — of ln1,
     the attention context, ln2 and g — are kept as a 14th entry of `saved`, the X operands of the split-fp16 weight gradients
     (DESIGN.md §9f).  The fp32 ln1, ln2 and g are then None in `saved` wherever that weight gradient has a split plan (_drops32,
-    §9j): layer_bwd makes them again if it lands on the fp32 weight gradient after all."""
+    §9j): layer_bwd makes them again if it lands on the fp32 weight gradient after all.
+    `varlen` = (cu_seqlens, max_S): x holds packed captions (DESIGN.md §29) and the attention core is the ragged causal one;
+    B and S are not read then.  Plain fp32 only (`sp` None, `causal` True)."""
     T, D, I = x.shape[0], x.shape[1], p.fc1_w.shape[0]
     pc = _layer_pieces(T, D, I, _VSPLIT16_FC1_EPI) if sp is not None else {}
     a1, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1", pc.get("ln1", 3),
                                   not _drops32(keep_split, save, sp, 3 * D, D, T))
     qkv = _linear(a1, p.qkv_w, sp, "qkv", p.qkv_b)
-    attn, lse = ops.attention_fwd(qkv, B, S, H, causal)
+    if varlen is None:
+        attn, lse = ops.attention_fwd(qkv, B, S, H, causal)
+    else:
+        if sp is not None or not causal:
+            raise ValueError("layer_fwd: the packed layer is causal and runs the plain fp32 GEMMs")
+        attn, lse = ops.attention_varlen_causal_fwd(qkv, varlen[0], varlen[1], H, want_lse=True)
     ac = attn if sp is None else ops.split_f16x3_dev(attn, sp.act("ctx"), pieces=pc["ctx"])
     x1 = _linear(ac, p.out_w, sp, "out", p.out_b, residual=x)
     a2, ln2, m2, r2 = _ln_operand(x1, p.ln2_w, p.ln2_b, eps, save, sp, "ln2", pc.get("ln2", 3),
@@ -312,8 +319,9 @@ def _remat_ln(ln, x, w, b, eps: Optional[float]):
 
 
 def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, need: Dict[str, bool], alloc=None,
-              sp: Optional[Split16Layer] = None, dx_stats: bool = False, dystats: bool = False, eps: Optional[float] = None):
-    """Returns (dx, grads) with grads keyed like LayerParams.FIELDS (missing = not needed).  `alloc(field, shape)`:
+              sp: Optional[Split16Layer] = None, dx_stats: bool = False, dystats: bool = False, eps: Optional[float] = None,
+              varlen=None):
+    """Returns (dx, grads) with grads keyed like LayerParams.FIELDS (missing = not needed).  `varlen`: as in layer_fwd.  `alloc(field, shape)`:
     see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad).  `eps`: the layer's, for an fp32 LayerNorm
     output the forward did not keep (_remat_ln, §9j).  `dystats` (the caller's decision for
     the whole tower, _dystats_regime): each kernel that produces the dY of a weight gradient that will take the split path is
@@ -339,7 +347,12 @@ def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, 
     dattn = _dgrad(dx1, p.out_w, sp, "out", rows=rows)
     qkv_stats = dystats and _split_wgrad_taken(bool(need.get("qkv_w")), sp, s3.get("ln1"), 3 * D, D, T)
     st = _with_stats(qkv_stats, ops.attention_bwd_stats_plan(B, S, H) if qkv_stats else 0, 3 * D, dattn.device)
-    dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal, stats=st)
+    if varlen is None:
+        dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal, stats=st)
+    else:
+        if sp is not None or not causal:
+            raise ValueError("layer_bwd: the packed layer is causal and runs the plain fp32 GEMMs")
+        dqkv = ops.attention_varlen_causal_bwd(qkv, varlen[0], attn, dattn, lse, varlen[1], H)
     if st is not None:
         dqkv.dystats = st
     rows = linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc, sp, "ln1",
@@ -1912,7 +1925,8 @@ def text_token_level_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache:
 # behind it.  As in vision_fwd_packed, LayerNorm, the GEMMs and their epilogues run at M = Tp as they are; the embedding, the
 # attention core and the first-EOS gather have ragged forms (ops.text_embed_varlen, ops.attention_varlen_causal_fwd,
 # ops.gather_rows_at at `last_rows`).  `tables`: HipCLIPModel._packed_text_tables (host ints max_S / Tp, the two device tables).
-# Forward only.
+# These are forward only; the trainable tower on packed captions (text_fwd_packed / text_bwd_packed) is at the
+# end of this file.
 
 def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str, plan=None, cache=None,
                         attn16: Optional[bool] = None, ctx_fused: bool = False):
@@ -2030,3 +2044,63 @@ def text_token_level_packed(p: TextParams, input_ids: torch.Tensor, tables: dict
         ln = k.layernorm(x, p.final_w, p.final_b, t.layer_norm_eps)
         tokens = k.gemm(ln, _w16(cache, "tproj", p.proj_w, k.cast))
     return ops.gather_rows_at(tokens, last_rows), tokens
+
+
+# --------------------------------------------------------------------------------------------- trainable text tower, packed
+# text_fwd / text_bwd at M = Tp.  d x of the padded tower is exactly zero on every row behind a first EOS, so
+# every parameter gradient of the padded rectangle is the sum over the cut captions: the same gradients from Tp rows instead of
+# B T.  The layer schedule is layer_fwd / layer_bwd themselves (`varlen`), plain fp32 GEMMs as the padded trainable tower runs.
+
+def text_fwd_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, save: bool):
+    """ids [N,T] on the device (the padded matrix: the pads are never read), `tables` as in text_fwd_frozen_packed -> (out [N,P],
+    saved for text_bwd_packed)."""
+    t = cfg
+    H, eps = t.num_attention_heads, t.layer_norm_eps
+    cu, last_rows, max_S = tables["cu_seqlens_dev"], tables["last_rows_dev"], tables["max_S"]
+    x = ops.text_embed_varlen(input_ids, cu, p.tok, p.pos, tables["Tp"])
+    saved_layers = []
+    for lp in p.layers:
+        x, sv = layer_fwd(x, lp, input_ids.shape[0], max_S, H, True, eps, save, varlen=(cu, max_S))
+        saved_layers.append(sv)
+    rows = ops.gather_rows_at(x, last_rows)
+    pooled, mp, rp = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=save)
+    out = ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+    saved = (input_ids, saved_layers, cu, max_S, tables["Tp"], rows, mp, rp, pooled) if save else None
+    return out, saved
+
+
+def text_bwd_packed(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool]):
+    """text_bwd on what text_fwd_packed saved: the same `need` masks and the same cut-off below the lowest layer asked for."""
+    t = cfg
+    input_ids, saved_layers, cu, max_S, Tp, rows, mp, rp, pooled = saved
+    N = input_ids.shape[0]
+    H = t.num_attention_heads
+    names = p.names()
+    needd = dict(zip(names, need))
+    grads: Dict[str, Optional[torch.Tensor]] = {n: None for n in names}
+    if needd["proj_w"]:
+        grads["proj_w"] = ops.gemm(d_out, pooled, ops.LAYOUT_TN)
+    dpooled = ops.gemm(d_out, p.proj_w, ops.LAYOUT_NN)
+    want = needd["final_w"] or needd["final_b"]
+    drows, dg, db = ops.layernorm_bwd(dpooled, rows, p.final_w, mp, rp, need_param_grads=want)
+    if want:
+        grads["final_w"], grads["final_b"] = dg, db
+    lowest = None
+    for n in names:
+        if needd[n] and n not in TextParams.TAIL:
+            li = -1 if n in TextParams.HEAD else int(n.split(".")[1])
+            lowest = li if lowest is None else min(lowest, li)
+    if lowest is None:
+        return [grads[n] for n in names]
+    dx = ops.scatter_last_rows(drows, cu, Tp)
+    for i in range(len(p.layers) - 1, max(lowest, 0) - 1, -1):
+        lneed = {f: needd[f"layers.{i}.{f}"] for f in LayerParams.FIELDS}
+        dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], N, max_S, H, True, lneed, varlen=(cu, max_S))
+        saved_layers[i] = None
+        for f, tn in gr.items():
+            grads[f"layers.{i}.{f}"] = tn
+    if lowest < 0:
+        dpos = torch.zeros_like(p.pos) if needd["pos"] else None
+        dtok = torch.zeros_like(p.tok) if needd["tok"] else None
+        grads["tok"], grads["pos"] = ops.text_embed_varlen_bwd(input_ids, cu, dx, dtok, dpos)
+    return [grads[n] for n in names]

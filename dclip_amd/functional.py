@@ -140,6 +140,27 @@ class TextTowerFn(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
+class TextTowerPackedFn(torch.autograd.Function):
+    """TextTowerFn for a TRAINABLE tower on packed captions (engine.text_fwd_packed / text_bwd_packed): `tables`
+    is HipCLIPModel._packed_text_tables' result.  Plain fp32 GEMMs, as the padded trainable tower runs."""
+
+    @staticmethod
+    def forward(ctx, input_ids, cfg, n_layers, tables, *params):
+        p = engine.TextParams.from_tensors([_c(t.detach()) for t in params], n_layers)
+        save = any(ctx.needs_input_grad[4:])
+        out, saved = engine.text_fwd_packed(p, _c(input_ids), tables, cfg, save)
+        ctx.p, ctx.saved, ctx.cfg = p, saved, cfg
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        if ctx.saved is None:
+            raise RuntimeError("TextTowerPackedFn.backward called twice, or forward ran without grad")
+        grads = engine.text_bwd_packed(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[4:]))
+        ctx.saved = None
+        return (None, None, None, None, *grads)
+
+
 class CosineDistillationLossFn(torch.autograd.Function):
     """mean_b (1 - cos(student_b, teacher_b)) — training/CLIP_image_distillation.py:564-576.
     No gradient flows to the teacher (it is computed under no_grad in the reference step, :597-600)."""

@@ -2141,6 +2141,73 @@ def attention_varlen_causal_fwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max
     return (out, lse) if want_lse else out
 
 
+def attention_varlen_causal_bwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, out: torch.Tensor, dout: torch.Tensor,
+                                lse: torch.Tensor, max_S: int, H: int) -> torch.Tensor:
+    """Backward of attention_varlen_causal_fwd over every row: qkv [Tp, 3*H*64], out / dout [Tp, H*64], lse
+    [H, Tp] as that call returned it with `want_lse`; returns dqkv [Tp, 3*H*64], every word written.  `max_S` bounds the
+    lengths.  The delta scratch [H, Tp] comes from the current workspace lane."""
+    lib = _lib.load()
+    _f32(qkv, "qkv"), _f32(out, "out"), _f32(dout, "dout"), _f32(lse, "lse")
+    N = cu_seqlens.numel() - 1
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or N < 1 or H < 1 or max_S < 1 or qkv.shape[0] < N:
+        raise ValueError(f"attention_varlen_causal_bwd: qkv {tuple(qkv.shape)}, H {H}, {N} sequences, max_S {max_S}")
+    Tp = qkv.shape[0]
+    if tuple(out.shape) != (Tp, H * 64) or tuple(dout.shape) != (Tp, H * 64) or tuple(lse.shape) != (H, Tp):
+        raise ValueError(f"attention_varlen_causal_bwd: out {tuple(out.shape)} / dout {tuple(dout.shape)} must be "
+                         f"{(Tp, H * 64)}, lse {tuple(lse.shape)} must be {(H, Tp)}")
+    _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    dqkv = torch.empty_like(qkv)
+    delta = _ws.get(H * Tp * 4, qkv.device)
+    _lib.check(lib.dclip_attention_varlen_causal_bwd(qkv.data_ptr(), cu_seqlens.data_ptr(), out.data_ptr(), dout.data_ptr(),
+                                                     lse.data_ptr(), dqkv.data_ptr(), delta.data_ptr(), N, max_S, H, _stream()),
+               "attention_varlen_causal_bwd")
+    return dqkv
+
+
+def text_embed_varlen_bwd(ids, cu_seqlens: torch.Tensor, dx: torch.Tensor, dtok: Optional[torch.Tensor] = None,
+                          dpos: Optional[torch.Tensor] = None):
+    """Backward of text_embed_varlen: dx [Tp, D] packed as there.  dtok [vocab, D] is ACCUMULATED into (float
+    atomics; the caller zeroes it); dpos [P >= T, D] gets rows 0 .. T-1 WRITTEN (a sum in ascending caption order, zeros where
+    no caption reaches), rows beyond T untouched.  Either may be None, not both.  Returns (dtok, dpos)."""
+    lib = _lib.load()
+    _ids(ids), _f32(dx, "dx")
+    N, T = ids.shape
+    if dtok is None and dpos is None:
+        raise ValueError("text_embed_varlen_bwd: neither dtok nor dpos asked for")
+    if dx.dim() != 2 or dx.shape[1] % 4 or N < 1 or not (N <= dx.shape[0] <= N * T):
+        raise ValueError(f"text_embed_varlen_bwd: {N} captions of up to {T} ids, dx {tuple(dx.shape)} (D % 4 == 0)")
+    D = dx.shape[1]
+    vocab = 1
+    if dtok is not None:
+        _f32(dtok, "dtok")
+        if dtok.dim() != 2 or dtok.shape[1] != D:
+            raise ValueError(f"text_embed_varlen_bwd: dtok {tuple(dtok.shape)} for D {D}")
+        vocab = dtok.shape[0]
+    if dpos is not None:
+        _f32(dpos, "dpos")
+        if dpos.dim() != 2 or dpos.shape[1] != D or dpos.shape[0] < T:
+            raise ValueError(f"text_embed_varlen_bwd: dpos {tuple(dpos.shape)} for {T} positions, D {D}")
+    _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    _lib.check(lib.dclip_text_embed_varlen_bwd(ids.data_ptr(), cu_seqlens.data_ptr(), dx.data_ptr(), _ptr(dtok), _ptr(dpos), N, T,
+                                               D, vocab, _stream()), "text_embed_varlen_bwd")
+    return dtok, dpos
+
+
+def scatter_last_rows(dout: torch.Tensor, cu_seqlens: torch.Tensor, total_rows: int) -> torch.Tensor:
+    """The transpose of gather_rows_at(x, cu_seqlens[1:] - 1): dx [Tp, D] with row cu_seqlens[n+1] - 1 = dout[n] and zeros
+    elsewhere, the whole tensor written.  `total_rows` is Tp = cu_seqlens[N], which the caller has on the host."""
+    lib = _lib.load()
+    _f32(dout, "dout")
+    if dout.dim() != 2 or dout.shape[1] % 4 or dout.shape[0] < 1 or total_rows < dout.shape[0]:
+        raise ValueError(f"scatter_last_rows: dout {tuple(dout.shape)} (D % 4 == 0), {total_rows} packed rows")
+    N, D = dout.shape
+    _i32(cu_seqlens, "cu_seqlens", (N + 1,))
+    dx = torch.empty((total_rows, D), dtype=torch.float32, device=dout.device)
+    _lib.check(lib.dclip_scatter_last_rows(dout.data_ptr(), cu_seqlens.data_ptr(), dx.data_ptr(), N, D, _stream()),
+               "scatter_last_rows")
+    return dx
+
+
 def attention_varlen_fwd_f16x2(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_S: int, H: int, causal: bool = False,
                                scale: float = 1.0, pieces: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """attention_varlen_fwd (`causal` False) / attention_varlen_causal_fwd (True) over every row, with the context written as

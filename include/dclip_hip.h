@@ -264,7 +264,7 @@ int dclip_gather_rows_at(const float* x, const int32_t* rows, float* out, int N,
 
 /* ------------------------------------------------------------------------------------------
  * The frozen text tower on PACKED captions: each caption is cut after its first EOS and the captions lie back
- * to back.  Forward only.  N captions; len_n = first EOS index + 1 (1 for a caption without EOS, as dclip_first_eos returns 0
+ * to back.  Forward (the backward is the next section).  N captions; len_n = first EOS index + 1 (1 for a caption without EOS, as dclip_first_eos returns 0
  * for it); cu_seqlens [N+1] (int32, on the device, built on the host from the token ids) are the cumulative lengths,
  * Tp = cu_seqlens[N].  Every entry is clamped into [0, Tp] and made non-decreasing on the device.  The layers between these
  * entries are row-wise over M = Tp and run unchanged; dclip_gather_rows_at at rows cu[1:] - 1 gathers the first-EOS rows.
@@ -285,6 +285,32 @@ int dclip_attention_varlen_causal_fwd(const float* qkv, const int32_t* cu_seqlen
                                       int H, int last_only, void* stream);
 int dclip_pack_tokens_varlen(const float* tokens, const float* sentence, const int32_t* cu_seqlens, float* out, int N, int Tmax,
                              int P, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The TRAINABLE text tower on packed captions: the backward of the three ragged entries above, fp32.  Layout,
+ * table and its on-device clamp as there (Tp = cu_seqlens[N]).  The gradients are the padded tower's: d x is exactly zero on
+ * every row behind a first EOS, so every parameter gradient of the padded rectangle is the sum over the cut captions.
+ * attention_varlen_causal_bwd: the backward of dclip_attention_varlen_causal_fwd(last_only = 0).  qkv [Tp][3*H*64], out / dout
+ *   [Tp][H*64], lse [H][Tp] exactly what that entry wrote, dqkv [Tp][3*H*64] = [dq|dk|dv], delta [H][Tp] caller-provided scratch
+ *   (written, then read; no meaning afterwards).  Two tiled kernels, grid (N*H, cdiv(max_S, 64)): dQ visits key tiles 0 .. its
+ *   own, dK / dV query tiles from its own on.  max_S bounds the lengths (rows at or beyond max_S of a sequence are not computed).
+ *   Every word of the dqkv rows of sequences of length 1 .. max_S is written and nothing else; a sequence of length 1 gets exact
+ *   zeros in dq and dk and dv = dout; a sequence of length 0 writes nothing.  No atomics: bit-equal from run to run.  A
+ *   sequence's loads never leave its own rows.  qkv / out / dout / dqkv 16-byte aligned.
+ * text_embed_varlen_bwd: the backward of dclip_text_embed_varlen.  ids [N][T], dx [Tp][D].  dtok [vocab][D]:
+ *   dtok[clamp(ids[n][t])] += dx[cu[n] + t] for t < min(len_n, T) — float atomics into the caller's buffer (zeroed or accumulating),
+ *   the id clamp of dclip_text_embed_bwd; ids[n][t >= len_n] are never read.  dpos [>= T][D]: dpos[t] = sum over the captions with
+ *   len_n > t of dx[cu[n] + t], added in ascending n (deterministic), WRITTEN for every t < T (zeros where no caption reaches);
+ *   rows >= T are untouched.  dtok or dpos may be NULL, not both.  D % 4 == 0, T * D < 2^31; dx / dpos 16-byte aligned.
+ * scatter_last_rows: the ragged twin of dclip_scatter_rows and the transpose of dclip_gather_rows_at at rows cu[1:] - 1.  dout
+ *   [N][D]; the whole dx [Tp][D] is written: row cu[n+1] - 1 gets dout[n], every other row of [cu[n], cu[n+1]) zero.  D % 4 == 0,
+ *   dout / dx 16-byte aligned.
+ * Each refuses N <= 0, a bad shape, a null or misaligned pointer with DCLIP_EINVAL before any launch. */
+int dclip_attention_varlen_causal_bwd(const float* qkv, const int32_t* cu_seqlens, const float* out, const float* dout,
+                                      const float* lse, float* dqkv, float* delta, int N, int max_S, int H, void* stream);
+int dclip_text_embed_varlen_bwd(const int64_t* ids, const int32_t* cu_seqlens, const float* dx, float* dtok, float* dpos, int N,
+                                int T, int D, int vocab, void* stream);
+int dclip_scatter_last_rows(const float* dout, const int32_t* cu_seqlens, float* dx, int N, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * 16-bit MFMA attention core for the two packed frozen towers above.  Forward only, head dim 64, no lse.
