@@ -34,6 +34,7 @@ def main(args, clip_model=None, clip_preprocess=None, train_batches=None, val_ba
     module_kwargs.setdefault("packed_text", bool(getattr(args, "packed_text", False)))
     module_kwargs.setdefault("packed_attention16", True if getattr(args, "packed_attention16", False) else None)
     module_kwargs.setdefault("packed_text_train", bool(getattr(args, "packed_text_train", False)))
+    module_kwargs.setdefault("text_train_split16", bool(getattr(args, "text_train_split16", False)))
     model = CLIPImageDistillation(args, clip_model, clip_preprocess, **module_kwargs).to(device)
     trainer = Trainer(max_epochs=args.phase1_epochs, accelerator="gpu", devices=devices, precision=32,
                       gradient_clip_val=0.5, accumulate_grad_batches=4, checkpoint_dir=args.checkpoint_dir,
@@ -72,6 +73,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="where the student's text tower trains, run it on captions cut after their first EOS and laid "
                              "back to back, forward and backward (lengths from the tokenizer's host output; default: the "
                              "padded [B, T] rectangle)")
+    parser.add_argument("--text_train_split16", action="store_true",
+                        help="where the student's text tower trains, run its layers' full-size fp32 GEMMs (forward, data and "
+                             "weight gradients) on the fp16 MFMAs from hi/lo split operands at fp32-grade error (default: the "
+                             "plain fp32 GEMMs)")
     parser.add_argument("--packed_attention16", action="store_true",
                         help="16-bit packed frozen towers keep q, k, v and the context in 16 bits and run the packed MFMA "
                              "attention core (default: fp32 q | k | v, the fp32 packed core and a cast)")

@@ -21,6 +21,9 @@ import torch
 
 from . import functional
 from .clip_model import HipCLIPModel, from_hf_state_dict
+# packed_text_train_route's twin for `text_train_split16` (§30).  The MODEL asks it (HipCLIPModel._text_train_split16_cache: it is
+# the model that knows whether a text parameter trains and a stream captures); it is named here beside its twin for the reader
+from .clip_model import text_train_split16_route      # noqa: F401
 from .config import from_hf
 from .lightning_lite import LightningLikeModule
 
@@ -81,7 +84,8 @@ class CLIPImageDistillation(LightningLikeModule):
     def __init__(self, hparams, clip_model, clip_preprocess=None, teacher=None, freeze_mode: str = "north_star",
                  process_group=None, contrastive_teacher_path: Optional[str] = None, student_precision: str = "fp32",
                  full_resolution_from_epoch: Optional[int] = None, packed_text: bool = False,
-                 packed_attention16: Optional[bool] = None, packed_text_train: bool = False):
+                 packed_attention16: Optional[bool] = None, packed_text_train: bool = False,
+                 text_train_split16: bool = False):
         """`student_precision`: "fp32" (default: the reference's `precision=32`,
         training/CLIP_image_distill_training.py:40, and the benched config c2) or "bf16" — the student's VISION tower
         multiplies in bf16 (forward, dgrad, wgrad) with fp32 master weights, fp32 accumulation and fp32
@@ -103,8 +107,13 @@ class CLIPImageDistillation(LightningLikeModule):
         "as_written"), the captions' lengths are known on the host (as for `packed_text`) and no graph is being captured, the
         student's text features come from the packed trainable tower, forward and backward
         (HipCLIPModel.get_text_features(packed_lens=..., packed_train=True)); otherwise the step runs as without it.  It
-        implies nothing about `packed_text`: the teacher's frozen passes follow that flag alone."""
+        implies nothing about `packed_text`: the teacher's frozen passes follow that flag alone.
+        `text_train_split16` (also an attribute; set as `text_train_split16` on the student at every step): where
+        the student's text tower TRAINS, its layers' full-size GEMMs — forward, data and weight gradients — run on the fp16 MFMAs
+        from hi/lo split operands at fp32-grade error, padded or (with `packed_text_train`) packed; under a graph capture, with a
+        frozen tower or with widths that are not multiples of 8 the step runs as without it."""
         super().__init__()
+        self.text_train_split16 = bool(text_train_split16)
         self.packed_text = bool(packed_text)
         self.packed_text_train = bool(packed_text_train)
         self.packed_attention16 = None if packed_attention16 is None else bool(packed_attention16)
@@ -426,7 +435,9 @@ class CLIPImageDistillation(LightningLikeModule):
             with torch.no_grad():          # frozen text tower (of a bf16 student: bf16 GEMM inputs there as well)
                 student_text = self.student.get_text_features(input_ids=tokens, precision=text_precision, **packed_kw).float()
         else:
-            # packed_text_train: the trainable tower on packed captions, forward and backward
+            # packed_text_train: the trainable tower on packed captions, forward and backward; text_train_split16:
+            # either form on the split-fp16 plan (§30; the model routes: text_train_split16_route)
+            self.student.text_train_split16 = bool(self.text_train_split16)
             train_lens = self._host_text_lens(train=True, **lens_src) if self.packed_text_train else None
             capturing = tokens.is_cuda and torch.cuda.is_current_stream_capturing()
             if packed_text_train_route(self.packed_text_train, not text_frozen, train_lens is not None, capturing):

@@ -156,6 +156,10 @@ SIGNATURES = {
     "dclip_gemm_f16_scaled_rows_stats_dev": (I, [P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),
     "dclip_attention_bwd_stats_plan": (I, [I, I, I]),
     "dclip_attention_bwd_stats": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
+    "dclip_colsum_segments_f32_workspace": (Z, [I, I]),
+    "dclip_colsum_segments_f32": (I, [P, P, I, I, I, I, P, Z, P]),
+    "dclip_attention_bwd_rows_stats_plan": (I, [I, I, I]),
+    "dclip_attention_bwd_rows_stats": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     "dclip_layernorm_bwd_stats_plan": (I, [I, I]),
     "dclip_layernorm_bwd_stats": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, Z, P]),
     "dclip_gemm_f16x3_plan": (I, [I, I, I]),

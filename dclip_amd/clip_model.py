@@ -202,11 +202,22 @@ def packed_text_tables(input_ids_host: torch.Tensor, eos_id: int, lens=None) -> 
             "max_tokens": max(max_S - 2, 1)}
 
 
+def text_train_split16_route(flag: bool, text_trainable: bool, capturing: bool, widths_ok: bool) -> bool:
+    """Whether a gradient-enabled text forward takes the trainable tower's split-fp16 plan: the switch is on, a
+    text parameter trains (gradients are needed), no stream is capturing and the widths are multiples of 8 (the plan's
+    condition).  Everything else is the plain fp32 path, the tower as it runs without the switch."""
+    return bool(flag and text_trainable and not capturing and widths_ok)
+
+
 class HipCLIPModel(nn.Module):
     # The 16-bit MFMA attention core of the packed frozen towers (DESIGN.md §24) for get_image_features_crops,
     # get_text_features(packed_lens=...) and text_token_level_packed at precision "bf16" / "fp16": True / False, or None for the
     # process-wide DCLIP_PACKED_ATTN16 (off unless set).
     packed_attention16: Optional[bool] = None
+    # The TRAINABLE fp32 text tower — get_text_features with grad enabled and a trainable text parameter, padded or with
+    # `packed_train` — with its layers' full-size GEMMs (forward, data and weight gradients) on the fp16 MFMAs from hi/lo split
+    # operands (DESIGN.md §30).  Off: the plain fp32 GEMMs, launch for launch what the tower ran before the switch existed.
+    text_train_split16: bool = False
 
     def __init__(self, config: Optional[ClipConfig] = None):
         super().__init__()
@@ -373,6 +384,30 @@ class HipCLIPModel(nn.Module):
             object.__setattr__(self, "_vsplit16_w", c)
         return c
 
+    def _tsplit16_train_cache(self) -> dict:
+        """The TRAINABLE text tower's device-side split-fp16 plan (`text_train_split16`): its own cache — apart
+        from the frozen host plan of _split16_cache and from the vision tower's _vsplit16_cache, so a refresh of one tower never
+        invalidates the other's pending backward."""
+        c = getattr(self, "_tsplit16_train_w", None)
+        if c is None:
+            c = {}
+            object.__setattr__(self, "_tsplit16_train_w", c)
+        return c
+
+    def _text_train_split16_cache(self, p) -> Optional[dict]:
+        """_tsplit16_train_cache() where text_train_split16_route takes the plan for this call, else None (logged once)."""
+        t = self.config.text
+        flag = bool(self.text_train_split16)
+        trainable = torch.is_grad_enabled() and any(x.requires_grad for x in p.tensors())
+        capturing = p.tok.is_cuda and torch.cuda.is_current_stream_capturing()
+        widths_ok = t.hidden_size % 8 == 0 and t.intermediate_size % 8 == 0 and t.num_hidden_layers > 0
+        if text_train_split16_route(flag, trainable, capturing, widths_ok):
+            return self._tsplit16_train_cache()
+        if flag and trainable:
+            engine._split16_log_once("split-fp16 trainable text tower: " + ("a stream is capturing" if capturing else
+                                     "the widths are not multiples of 8") + "; the tower takes the plain fp32 path")
+        return None
+
     def _vsplit16_frozen_cache(self) -> dict:
         """The FROZEN vision tower's host split-fp16 plan (precision "fp32-split16", engine.vision_fwd_frozen_split16): the
         [hi|hi|lo] weight copies and host-float scales, built at the first such forward (one device-to-host read) and rebuilt when
@@ -414,7 +449,9 @@ class HipCLIPModel(nn.Module):
         precision "fp32", the TRAINABLE tower runs on the packed captions, forward and backward (engine.text_fwd_packed) —
         the padded tower's gradients from Tp rows instead of B T.  Without it that call is refused as before; under no_grad it
         changes nothing; a 16-bit precision keeps the forward-only error; while a stream is capturing the padded trainable
-        path runs."""
+        path runs.
+        `text_train_split16` (the model's attribute): the trainable fp32 tower, padded or packed, on the
+        split-fp16 plan; under no_grad, with a frozen tower or while a stream is capturing it changes nothing."""
         if input_ids is None:
             raise ValueError("You have to specify input_ids")
         t = self.config.text
@@ -438,7 +475,7 @@ class HipCLIPModel(nn.Module):
             elif train:
                 tables = self._packed_text_tables(input_ids, None if packed_lens is True else packed_lens, dev)
                 return functional.TextTowerPackedFn.apply(input_ids.to(dev).long().contiguous(), t, t.num_hidden_layers, tables,
-                                                          *p.tensors())
+                                                          self._text_train_split16_cache(p), *p.tensors())
             else:
                 with torch.no_grad():
                     tables = self._packed_text_tables(input_ids, None if packed_lens is True else packed_lens, dev)
@@ -456,7 +493,8 @@ class HipCLIPModel(nn.Module):
                 raise RuntimeError("precision='fp16' is a forward-only path for frozen towers: call it under torch.no_grad()")
             return engine.text_fwd_frozen_bf16(self.text_params_detached(), input_ids.long().contiguous(), t,
                                                self._f16_cache(), torch.float16)
-        return functional.TextTowerFn.apply(input_ids.long(), t, t.num_hidden_layers, self._split16_cache(), *p.tensors())
+        return functional.TextTowerFn.apply(input_ids.long(), t, t.num_hidden_layers, self._split16_cache(),
+                                            self._text_train_split16_cache(p), *p.tensors())
 
     def _packed_text_tables(self, input_ids: torch.Tensor, lens, dev) -> dict:
         """packed_text_tables plus `cu_seqlens_dev` / `last_rows_dev`: ONE upload of a buffer allocated for this call (a

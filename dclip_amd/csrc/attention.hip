@@ -1218,12 +1218,25 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_from_ds_kernel(AttnArgs a, co
 // register layout its products consume (see attn_fwd_rows_kernel: the contraction order is free), so P and dS never
 // touch LDS, there is no barrier after the staging one, and dQ / dK / dV leave as 16-byte stores.  The price is
 // forming S and dP twice (7 MFMA products instead of 5); the LDS operand traffic drops by a third.
-template <int KT, bool CAUSAL>
+// STATS (a trailing RowStats argument, fp32, packed dqkv with ldd = 3 D): the statistics twin, as
+// attn_bwd_lean_stats_kernel is of the one-tile kernel.  After phase 2 all four LDS tiles are dead behind a barrier: the stored
+// dq, dk, dv of the head are staged there as [matrix][token][64] (16-byte granule g of token t at g ^ (t & 15)), and thread
+// c < 192 folds column c over tokens 0 .. S-1 in order — maximum of the bit patterns of |x|, fp32 sum — into partial row b of
+// pmax / psum [B][3 D] (colstats_finish_kernel's layout); the same bits in every run.  The argument is a trailing parameter pack,
+// empty without STATS: those instances keep their parameter list and their code.
+struct RowStats {
+  unsigned* pmax;
+  float* psum;
+};
+
+template <int KT, bool CAUSAL, typename... ST>
 __global__ void __launch_bounds__(KT * 64) attn_bwd_rows_kernel(AttnArgs a, const float* __restrict__ out,
                                                                 const float* __restrict__ dout,
                                                                 const float* __restrict__ lse, float* __restrict__ dq_out,
                                                                 float* __restrict__ dk_out, float* __restrict__ dv_out,
-                                                                int ldd) {
+                                                                int ldd, ST... st_) {
+  static_assert(sizeof...(ST) <= 1, "at most one RowStats argument");
+  constexpr bool STATS = sizeof...(ST) == 1;
   constexpr int R = KT * 16;
   __shared__ __attribute__((aligned(16))) float lds[4 * R * HD + 2 * R];
   float* Qs = lds;
@@ -1281,6 +1294,7 @@ __global__ void __launch_bounds__(KT * 64) attn_bwd_rows_kernel(AttnArgs a, cons
   }
   __syncthreads();
   const int kts = (S + 15) / 16;  // 16-row tiles that hold data
+  f32x4 sq[STATS ? 4 : 1];        // STATS: the stored dQ rows, kept until the tiles are dead
 
   // ---- phase 1: own queries (lane column l15), every key tile -> dQ
   {
@@ -1327,6 +1341,10 @@ __global__ void __launch_bounds__(KT * 64) attn_bwd_rows_kernel(AttnArgs a, cons
       float* o = dq_out + ((size_t)b * S + own) * ldd + h * HD + 4 * qd;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(o + 16 * dt) = dq[dt];
+    }
+    if constexpr (STATS) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) sq[dt] = dq[dt];
     }
   }
 
@@ -1379,6 +1397,36 @@ __global__ void __launch_bounds__(KT * 64) attn_bwd_rows_kernel(AttnArgs a, cons
       for (int dt = 0; dt < 4; ++dt) {
         *reinterpret_cast<f32x4*>(dk_out + o + 16 * dt) = dk[dt];
         *reinterpret_cast<f32x4*>(dv_out + o + 16 * dt) = dv[dt];
+      }
+    }
+    if constexpr (STATS) {
+      const RowStats rs = [](RowStats r) { return r; }(st_...);
+      __syncthreads();                                 // every wave's reads of the four tiles are done
+      if (own < S) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const int o = tile_off(own, 16 * dt + 4 * qd);
+          *reinterpret_cast<f32x4*>(lds + o) = sq[dt];
+          *reinterpret_cast<f32x4*>(lds + R * HD + o) = dk[dt];
+          *reinterpret_cast<f32x4*>(lds + 2 * R * HD + o) = dv[dt];
+        }
+      }
+      __syncthreads();
+      const int c = threadIdx.x;
+      if (c < 3 * HD) {                                // (matrix, head column): tokens 0 .. S-1 in order; rows >= S were not staged
+        const int mt = c >> 6, cc = c & 63;
+        const float* t = lds + mt * R * HD;
+        unsigned m = 0u;
+        float s = 0.f;
+        for (int r = 0; r < S; ++r) {
+          const float v = t[tile_off(r, cc)];
+          const unsigned u = __builtin_bit_cast(unsigned, v) & 0x7fffffffu;
+          m = m > u ? m : u;
+          s += v;
+        }
+        const size_t o = (size_t)b * 3 * D + (size_t)mt * D + h * HD + cc;
+        rs.pmax[o] = m;
+        rs.psum[o] = s;
       }
     }
   }
@@ -1603,6 +1651,29 @@ DCLIP_API int dclip_attention_bwd_stats(const float* qkv, const float* out, cons
     hipLaunchKernelGGL((attn_bwd_lean_stats_kernel<false>), dim3(B * H), dim3(256), 0, st, a, out, dout, lse, dqkv, dqkv + D,
                        dqkv + 2 * D, 3 * D, (unsigned*)pmax, psum);
   DCLIP_CHECK_LAUNCH("attention_bwd.lean.stats");
+  return DCLIP_OK;
+}
+
+// The same for 65 .. 80 rows (the 77-token text tower when it trains): the statistics twin of the whole-row kernel.
+// _plan returns B there and 0 elsewhere; dclip_attention_bwd_stats_plan keeps its own range, so the two never overlap.
+DCLIP_API int dclip_attention_bwd_rows_stats_plan(int B, int S, int H) { return B > 0 && H > 0 && S > TS && S <= 80 ? B : 0; }
+
+DCLIP_API int dclip_attention_bwd_rows_stats(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                                             void* pmax, float* psum, int B, int S, int H, int causal, void* stream) {
+  DCLIP_REQUIRE(qkv && out && dout && lse && dqkv && pmax && psum, "attention_bwd_rows_stats: null pointer");
+  DCLIP_REQUIRE(dclip_attention_bwd_rows_stats_plan(B, S, H) > 0, "attention_bwd_rows_stats: no such form for B=%d S=%d H=%d", B, S, H);
+  DCLIP_REQUIRE(((uintptr_t)pmax | (uintptr_t)psum) % 4 == 0, "attention_bwd_rows_stats: alignment");
+  const int D = H * HD;
+  AttnArgs a{qkv, qkv + D, qkv + 2 * D, 3 * D, 3 * D, S, S, H, nullptr};
+  hipStream_t st = (hipStream_t)stream;
+  const RowStats rs{(unsigned*)pmax, psum};
+  if (causal)
+    hipLaunchKernelGGL((attn_bwd_rows_kernel<5, true, RowStats>), dim3(B * H), dim3(320), 0, st, a, out, dout, lse, dqkv, dqkv + D,
+                       dqkv + 2 * D, 3 * D, rs);
+  else
+    hipLaunchKernelGGL((attn_bwd_rows_kernel<5, false, RowStats>), dim3(B * H), dim3(320), 0, st, a, out, dout, lse, dqkv, dqkv + D,
+                       dqkv + 2 * D, 3 * D, rs);
+  DCLIP_CHECK_LAUNCH("attention_bwd.rows.stats");
   return DCLIP_OK;
 }
 

@@ -1001,6 +1001,59 @@ DCLIP_API int dclip_split_f32_f16x2_rows_cols_stats(const float* x, void* y, flo
                                      cols, ldx, 2, stream);
 }
 
+// Column sums of x [B*S][cols] in the association of a producer that leaves one partial row per segment of S rows and of the
+// finish over them: psum[b][c] = the fp32 sum of rows b S .. b S + S - 1 in order, then colstats_finish_kernel's
+// fold over the B partial rows — bit-equal to the db that dclip_split_f32_f16x3_rows_cols_stats folds from the partials of
+// dclip_attention_bwd_rows_stats / dclip_attention_bwd_stats on the same x.  For the form of a backward that runs WITHOUT the
+// producer's statistics and must still return the same bias gradient.  workspace: (2 B + 2) cols 4-byte words.
+// The finish is the shared kernel, launched as the single pass launches it, so that the fold is that one by construction: the
+// column maxima this kernel writes and the col_exp / col_alpha the finish derives from them land in the workspace and are read
+// by nobody.  That is B cols words of extra stores in a form that is switched off by default, against a second finish kernel.
+namespace {
+__global__ void __launch_bounds__(256) colstats_segments_kernel(const float* __restrict__ x, unsigned* __restrict__ pmax,
+                                                                float* __restrict__ psum, int S, int cols, int ldx) {
+  const int c = blockIdx.y * 256 + threadIdx.x, b = blockIdx.x;
+  if (c >= cols) return;
+  const float* p = x + (size_t)b * S * ldx + c;
+  unsigned m = 0u;
+  float s = 0.f;
+  for (int r = 0; r < S; ++r) {
+    const float v = p[(size_t)r * ldx];
+    const unsigned u = __builtin_bit_cast(unsigned, v) & 0x7fffffffu;
+    m = m > u ? m : u;
+    s += v;
+  }
+  pmax[(size_t)b * cols + c] = m;
+  psum[(size_t)b * cols + c] = s;
+}
+}  // namespace
+
+DCLIP_API size_t dclip_colsum_segments_f32_workspace(int B, int cols) {
+  return B > 0 && cols > 0 ? ((size_t)2 * B + 2) * cols * sizeof(float) : 0;
+}
+
+DCLIP_API int dclip_colsum_segments_f32(const float* x, float* db, int B, int S, int cols, int ldx, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  DCLIP_REQUIRE(x && db && B > 0 && S > 0 && cols > 0 && ldx >= cols, "colsum_segments_f32: bad arguments");
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)db | (uintptr_t)workspace) % 4 == 0, "colsum_segments_f32: alignment");
+  const size_t need = dclip_colsum_segments_f32_workspace(B, cols);
+  if (!workspace || workspace_bytes < need) {
+    dclip_set_error("colsum_segments_f32: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+    return DCLIP_EWORKSPACE;
+  }
+  unsigned* pmax = (unsigned*)workspace;
+  float* psum = (float*)workspace + (size_t)B * cols;
+  int* col_exp = (int*)workspace + (size_t)2 * B * cols;
+  float* col_alpha = (float*)workspace + (size_t)2 * B * cols + cols;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(colstats_segments_kernel, dim3(B, cdiv(cols, 256)), dim3(256), 0, st, x, pmax, psum, S, cols, ldx);
+  DCLIP_CHECK_LAUNCH("colsum_segments_f32");
+  hipLaunchKernelGGL(colstats_finish_kernel, dim3(cdiv(cols, FIN_COLS)), dim3(256), 0, st, (const unsigned*)pmax, (const float*)psum, col_exp,
+                     col_alpha, db, B, cols);
+  DCLIP_CHECK_LAUNCH_V("colsum_segments_f32", ".finish");
+  return DCLIP_OK;
+}
+
 DCLIP_API int dclip_layernorm_fwd_f16x3(const float* x, const float* gamma, const float* beta, void* y, int rows, int D,
                                         float eps, float scale, void* stream) {
   DCLIP_REQUIRE(x && gamma && beta && y, "layernorm_fwd_f16x3: null pointer");

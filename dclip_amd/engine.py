@@ -169,7 +169,8 @@ def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: floa
     (DESIGN.md §9f).  The fp32 ln1, ln2 and g are then None in `saved` wherever that weight gradient has a split plan (_drops32,
     §9j): layer_bwd makes them again if it lands on the fp32 weight gradient after all.
     `varlen` = (cu_seqlens, max_S): x holds packed captions (DESIGN.md §29) and the attention core is the ragged causal one;
-    B and S are not read then.  Plain fp32 only (`sp` None, `causal` True)."""
+    B and S are not read then.  Causal only; with `sp` the ragged attention is followed by the split pass of its context
+    (DESIGN.md §30)."""
     T, D, I = x.shape[0], x.shape[1], p.fc1_w.shape[0]
     pc = _layer_pieces(T, D, I, _VSPLIT16_FC1_EPI) if sp is not None else {}
     a1, ln1, m1, r1 = _ln_operand(x, p.ln1_w, p.ln1_b, eps, save, sp, "ln1", pc.get("ln1", 3),
@@ -178,8 +179,8 @@ def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: floa
     if varlen is None:
         attn, lse = ops.attention_fwd(qkv, B, S, H, causal)
     else:
-        if sp is not None or not causal:
-            raise ValueError("layer_fwd: the packed layer is causal and runs the plain fp32 GEMMs")
+        if not causal:
+            raise ValueError("layer_fwd: the packed layer is causal")
         attn, lse = ops.attention_varlen_causal_fwd(qkv, varlen[0], varlen[1], H, want_lse=True)
     ac = attn if sp is None else ops.split_f16x3_dev(attn, sp.act("ctx"), pieces=pc["ctx"])
     x1 = _linear(ac, p.out_w, sp, "out", p.out_b, residual=x)
@@ -222,6 +223,9 @@ def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Te
         pc = split16_pieces([(dy.shape[0], N, M)])      # the row pieces' one reader: _dgrad's dX [tokens, in_f] = dy3 wt^T along out_f
         if st is not None:
             dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_cols_stats(dy, st, db=db, pieces=pc)
+        elif need_b and getattr(dy, "db_segments", None) is not None:      # §30: the bias gradient in the statistics form's order
+            dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=None, pieces=pc)
+            ops.colsum_segments(dy, *dy.db_segments, out=db)
         else:
             dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=db, pieces=pc)
         if need_b:
@@ -262,6 +266,22 @@ def _with_stats(want: bool, P: int, cols: int, dev):
     """The ColStats a producer of dY is handed: only when the weight gradient that follows will take the split path
     (`want`, _split_wgrad_taken), the switch is on and the producer's plan P says yes; None = the three-launch pass as before."""
     return ops.ColStats(P, cols, dev) if want and _VSPLIT16_DYSTATS and P > 0 else None
+
+
+def _attention_bwd_stats_form(B: int, S: int, H: int, causal: bool):
+    """(ops.attention_bwd's keyword, partial rows) of the statistics form of the dense attention backward at S tokens: the one-tile
+    kernel's up to 64 (§9g), and for the CAUSAL tower — the text tower; a vision tower of 65 .. 80 tokens keeps the schedule it
+    had — the whole-row kernel's twin for 65 .. 80.  (None, 0) where there is none: dqkv then takes the
+    three-launch split.  ("segments", 0): the twin exists but DCLIP_TEXT_SPLIT16_ROWS_STATS=0 switched it off — the three-launch
+    split, with the bias gradient summed per caption as the twin's partials are (ops.colsum_segments), so that the switch
+    changes no training result."""
+    P = ops.attention_bwd_stats_plan(B, S, H)
+    if P > 0:
+        return "stats", P
+    P = ops.attention_bwd_rows_stats_plan(B, S, H) if causal else 0
+    if P > 0 and not _TSPLIT16_ROWS_STATS:
+        return "segments", 0
+    return ("rows_stats", P) if P > 0 else (None, 0)
 
 
 def _ln_bwd(dy, x, gamma, mean, rstd, dresidual, want: bool, gr, wkey: str, bkey: str, alloc, dx_stats: bool = False):
@@ -346,12 +366,16 @@ def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, 
                               s3.get("ctx"))
     dattn = _dgrad(dx1, p.out_w, sp, "out", rows=rows)
     qkv_stats = dystats and _split_wgrad_taken(bool(need.get("qkv_w")), sp, s3.get("ln1"), 3 * D, D, T)
-    st = _with_stats(qkv_stats, ops.attention_bwd_stats_plan(B, S, H) if qkv_stats else 0, 3 * D, dattn.device)
     if varlen is None:
-        dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal, stats=st)
+        form, P = _attention_bwd_stats_form(B, S, H, causal) if qkv_stats else (None, 0)
+        st = _with_stats(qkv_stats, P, 3 * D, dattn.device)
+        dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal, **({form: st} if st is not None else {}))
+        if form == "segments" and _VSPLIT16_DYSTATS:
+            dqkv.db_segments = (B, S)
     else:
-        if sp is not None or not causal:
-            raise ValueError("layer_bwd: the packed layer is causal and runs the plain fp32 GEMMs")
+        if not causal:
+            raise ValueError("layer_bwd: the packed layer is causal")
+        st = None      # the tiled ragged kernels have no statistics form: dqkv takes the three-launch split (§30)
         dqkv = ops.attention_varlen_causal_bwd(qkv, varlen[0], attn, dattn, lse, varlen[1], H)
     if st is not None:
         dqkv.dystats = st
@@ -1285,8 +1309,11 @@ class TextParams:
         return out + list(self.TAIL)
 
 
-def text_encoder_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None):
-    """Embeddings + causal stack; returns the PRE-final-LN hidden states [B*T, D]."""
+def text_encoder_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None,
+                     split16_cache: Optional[dict] = None, split16_out: Optional[list] = None):
+    """Embeddings + causal stack; returns the PRE-final-LN hidden states [B*T, D].  `split16_cache`, `split16_out`: as
+    vision_fwd's — a forward that saves for the backward runs the layers' full-size GEMMs on the trainable text tower's own
+    device plan (HipCLIPModel._tsplit16_train_cache)."""
     t = cfg
     B, T = input_ids.shape
     D, H = t.hidden_size, t.num_attention_heads
@@ -1294,8 +1321,9 @@ def text_encoder_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hi
     if hidden_out is not None:
         hidden_out.append(x)
     saved_layers = []
-    for lp in p.layers:
-        x, sv = layer_fwd(x, lp, B, T, H, True, t.layer_norm_eps, save)
+    plan, keep = _text_train_split16(p, cfg, save, split16_cache, split16_out)
+    for li, lp in enumerate(p.layers):
+        x, sv = layer_fwd(x, lp, B, T, H, True, t.layer_norm_eps, save, plan[li] if plan is not None else None, keep)
         saved_layers.append(sv)
         if hidden_out is not None:
             hidden_out.append(x)
@@ -1622,6 +1650,12 @@ _SPLIT16_PIECES2 = os.environ.get("DCLIP_SPLIT16_PIECES2", "1") != "0"
 # (layernorm_fwd on the saved input; quick_gelu of the saved h), bit for bit.  Opt-in (1): alone against the parent it gained
 # 1.0-1.6 % and missed the project's bar in one of three pairs (§9j); the default, 0, stores them as before
 _VSPLIT16_DROP32 = os.environ.get("DCLIP_VISION_SPLIT16_DROP32", "0") == "1"
+# The TRAINABLE text tower on the same machinery (HipCLIPModel.text_train_split16) has no switches of its own for
+# the sub-features: _VSPLIT16_BWD, _WGRAD, _DYSTATS, _FC1_EPI, _DROP32, _SPLIT16_FUSED* and _PIECES2 are read inside the shared
+# layer functions and act on the text path exactly as on the vision path.  Its one own switch: the statistics twin of the
+# 65 .. 80-row attention backward; 0 = dqkv takes the three-launch split of §9f and qkv_b one more pass over dqkv (ops.colsum_segments), every gradient bit for bit the statistics form's
+_TSPLIT16_ROWS_STATS = os.environ.get("DCLIP_TEXT_SPLIT16_ROWS_STATS", "1") != "0"
+_TSPLIT16_KEY, _TSPLIT16_WHAT = "__tsplit16__", "split-fp16 trainable text tower"
 
 
 def vision_split16_enabled() -> bool:
@@ -1712,8 +1746,8 @@ class Split16Bwd:
               self.ptrs == tuple(getattr(lp, f).data_ptr() for lp in self.params for f in _SPLIT16_WATCHED) and
               self.versions == tuple(getattr(lp, f)._version for lp in self.params for f in _SPLIT16_WATCHED))
         if not ok:
-            _split16_log_once("split-fp16 vision tower: a weight changed between a forward and its backward; that backward "
-                              "takes the plain fp32 data-gradient GEMMs")
+            _split16_log_once(self.ent.get("what", "split-fp16 vision tower") + ": a weight changed between a forward and its "
+                              "backward; that backward takes the plain fp32 data-gradient GEMMs")
         return ok
 
 
@@ -1726,10 +1760,11 @@ def _vision_split16_flags(ent: dict) -> None:
         return
     flags = host[:, ops.SPLIT16_PLAN_FLAGS].view(torch.int32)
     if bool(flags.any()):
-        _split16_log_once("split-fp16 vision tower: a weight statistic is non-finite or an activation bound needs a scale below "
-                          "2^-14 (layer flags " + ", ".join(f"{i}:{int(f)}" for i, f in enumerate(flags.tolist()) if f) +
-                          "); the forward stays on the split path with that scale and may lose accuracy "
-                          "(DCLIP_VISION_SPLIT16=0 selects the plain fp32 path)")
+        _split16_log_once(ent.get("what", "split-fp16 vision tower") + ": a weight statistic is non-finite or an activation bound "
+                          "needs a scale below 2^-14 (layer flags " +
+                          ", ".join(f"{i}:{int(f)}" for i, f in enumerate(flags.tolist()) if f) +
+                          "); the forward stays on the split path with that scale and may lose accuracy (" +
+                          ent.get("off", "DCLIP_VISION_SPLIT16=0") + " selects the plain fp32 path)")
 
 
 def vision_split16_check_flags(cache: Optional[dict]) -> None:
@@ -1740,19 +1775,22 @@ def vision_split16_check_flags(cache: Optional[dict]) -> None:
         _vision_split16_flags(ent)
 
 
-def _vision_split16_plan(layers: List[LayerParams], cfg, cache: dict):
-    """Per layer a Split16Layer over the model's device plan, refreshed (three launches, no host read) when a watched
+def _vision_split16_plan(layers: List[LayerParams], cfg, cache: dict, key: str = "__vsplit16__",
+                         what: str = "split-fp16 vision tower", off: str = "DCLIP_VISION_SPLIT16=0"):
+    """`key`, `what`, `off`: the cache entry, the log label and the way back to the plain path that a message names — the
+    trainable text tower keeps its own plan under its own key.
+    Per layer a Split16Layer over the model's device plan, refreshed (three launches, no host read) when a watched
     parameter changed; None = the plain path (widths not multiples of 8, or the very first call arrives inside a graph
     capture).  While a stream is capturing the refresh is always issued, so that it is part of the graph and every replay
     plans and splits the weights of that moment."""
     if len(layers) == 0 or cfg.hidden_size % 8 or cfg.intermediate_size % 8:
         return None
     capturing = torch.cuda.is_current_stream_capturing()
-    ent = cache.get("__vsplit16__")
+    ent = cache.get(key)
     ptrs = tuple(getattr(lp, f).data_ptr() for lp in layers for f in _SPLIT16_WATCHED)
     if ent is None or ent["ptrs"] != ptrs:
         if capturing:
-            _split16_log_once("split-fp16 vision tower: first use inside a graph capture; this capture takes the plain fp32 path "
+            _split16_log_once(what + ": first use inside a graph capture; this capture takes the plain fp32 path "
                               "(run one eager step first)")
             return None
         if any(not getattr(lp, f).is_contiguous() for lp in layers for f in _SPLIT16_WATCHED):
@@ -1760,13 +1798,13 @@ def _vision_split16_plan(layers: List[LayerParams], cfg, cache: dict):
         tab = ops.split16_table([{f: getattr(lp, f) for f in _SPLIT16_WATCHED} for lp in layers], transposed=_VSPLIT16_BWD)
         base, stride = tab["plan"].data_ptr(), 4 * tab["plan"].shape[1]
         wt = tab.get("wt")
-        ent = {"ptrs": ptrs, "tab": tab, "versions": None, "host": None, "epoch": 0,
+        ent = {"ptrs": ptrs, "tab": tab, "versions": None, "host": None, "epoch": 0, "what": what, "off": off,
                "layers": [Split16Layer(w, base + li * stride, wt[li] if wt else None) for li, w in enumerate(tab["w"])]}
         try:
             ent["host"] = torch.zeros(tuple(tab["plan"].shape), dtype=torch.float32).pin_memory()
         except RuntimeError:
             ent["host"] = None
-        cache["__vsplit16__"] = ent
+        cache[key] = ent
     versions = tuple(getattr(lp, f)._version for lp in layers for f in _SPLIT16_WATCHED)
     if capturing or ent["versions"] != versions:
         _vision_split16_flags(ent)
@@ -1778,13 +1816,35 @@ def _vision_split16_plan(layers: List[LayerParams], cfg, cache: dict):
     return ent["layers"]
 
 
-def text_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None):
+def _text_train_split16(p: TextParams, cfg, save: bool, split16_cache: Optional[dict], split16_out: Optional[list]):
+    """(plan, keep_split) of a trainable text forward: the tower's own device plan — _vision_split16_plan under
+    the text key, so neither tower's refresh touches the other's pending backward — when the forward saves for a backward and
+    the caller handed the model's cache; (None, False) = the plain fp32 schedule, the parent's launch for launch.  The forward's
+    Split16Bwd goes to `split16_out` as in vision_fwd."""
+    if not (save and split16_cache is not None):
+        return None, False
+    plan = _vision_split16_plan(p.layers, cfg, split16_cache, _TSPLIT16_KEY, _TSPLIT16_WHAT, "text_train_split16 = False")
+    if plan is None:
+        _split16_log_once(_TSPLIT16_WHAT + ": the plan declined (widths not multiples of 8, or first use inside a graph capture); "
+                          "the tower takes the plain fp32 path")
+        return None, False
+    keep = False
+    if split16_out is not None and _VSPLIT16_BWD and plan[0].wt is not None:
+        split16_out.append(Split16Bwd(plan, split16_cache[_TSPLIT16_KEY], p.layers))
+        keep = _VSPLIT16_WGRAD
+    return plan, keep
+
+
+def text_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None,
+             split16_cache: Optional[dict] = None, split16_out: Optional[list] = None):
     """get_text_features: ids [B,T] -> [B,P]  (hf:modeling_clip.py:541-586, :705-713).  LayerNorm is row-wise, so
-    the first-EOS rows are gathered BEFORE final_layer_norm: only B rows are normalised and projected."""
+    the first-EOS rows are gathered BEFORE final_layer_norm: only B rows are normalised and projected.
+    `split16_cache`, `split16_out`: text_encoder_fwd's; the embedding, the gathered EOS rows, final_layer_norm and the projection
+    (M = B) stay on ops.gemm."""
     t = cfg
     B, T = input_ids.shape
     D = t.hidden_size
-    x, saved_layers = text_encoder_fwd(p, input_ids, cfg, save, hidden_out)
+    x, saved_layers = text_encoder_fwd(p, input_ids, cfg, save, hidden_out, split16_cache, split16_out)
     eos = ops.first_eos(input_ids, t.eos_token_id)
     rows = ops.gather_rows(x, eos, B, T, D)
     pooled, mp, rp = ops.layernorm_fwd(rows, p.final_w, p.final_b, t.layer_norm_eps, save_stats=save)
@@ -1793,7 +1853,8 @@ def text_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hidden_out
     return out, saved
 
 
-def text_bwd(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool]):
+def text_bwd(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool], split16=None):
+    """`split16`: the forward's Split16Bwd (text_fwd's `split16_out`); None = the plain fp32 backward."""
     t = cfg
     input_ids, saved_layers, eos, rows, mp, rp, pooled = saved
     B, T = input_ids.shape
@@ -1816,9 +1877,18 @@ def text_bwd(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool]):
     if lowest is None:
         return [grads[n] for n in names]
     dx = ops.scatter_rows(drows, eos, B, T, D)
+    # sp, the dY-statistics regime and the per-layer dx_stats decision as vision_bwd derives them.  The top
+    # layer's incoming dx is zero in all but one row per caption: a row-scaled split of an all-zero row gives zero pieces and
+    # alpha = 1 (split16_row_exp(0) = 0)
+    plan = split16.layers if split16 is not None and _VSPLIT16_BWD and split16.fresh() else None
+    dystats = plan is not None and _dystats_regime(B * T, D, p.layers[0].fc1_w.shape[0])
     for i in range(len(p.layers) - 1, max(lowest, 0) - 1, -1):
         lneed = {f: needd[f"layers.{i}.{f}"] for f in LayerParams.FIELDS}
-        dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, T, H, True, lneed)
+        sp = plan[i] if plan is not None else None      # None: the plain fp32 GEMMs (eps: what a forward on the plan left out, §9j)
+        below = dystats and i - 1 >= max(lowest, 0) and len(saved_layers[i - 1]) > 13
+        dxs = below and _split_wgrad_taken(bool(needd[f"layers.{i - 1}.fc2_w"]), plan[i - 1], saved_layers[i - 1][13].get("g"),
+                                           D, p.layers[i - 1].fc1_w.shape[0], B * T)
+        dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, T, H, True, lneed, None, sp, dxs, dystats, eps=t.layer_norm_eps)
         saved_layers[i] = None
         for f, tn in gr.items():
             grads[f"layers.{i}.{f}"] = tn
@@ -2051,16 +2121,19 @@ def text_token_level_packed(p: TextParams, input_ids: torch.Tensor, tables: dict
 # every parameter gradient of the padded rectangle is the sum over the cut captions: the same gradients from Tp rows instead of
 # B T.  The layer schedule is layer_fwd / layer_bwd themselves (`varlen`), plain fp32 GEMMs as the padded trainable tower runs.
 
-def text_fwd_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, save: bool):
+def text_fwd_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, save: bool, split16_cache: Optional[dict] = None,
+                    split16_out: Optional[list] = None):
     """ids [N,T] on the device (the padded matrix: the pads are never read), `tables` as in text_fwd_frozen_packed -> (out [N,P],
-    saved for text_bwd_packed)."""
+    saved for text_bwd_packed).  `split16_cache`, `split16_out`: as text_fwd's."""
     t = cfg
     H, eps = t.num_attention_heads, t.layer_norm_eps
     cu, last_rows, max_S = tables["cu_seqlens_dev"], tables["last_rows_dev"], tables["max_S"]
     x = ops.text_embed_varlen(input_ids, cu, p.tok, p.pos, tables["Tp"])
     saved_layers = []
-    for lp in p.layers:
-        x, sv = layer_fwd(x, lp, input_ids.shape[0], max_S, H, True, eps, save, varlen=(cu, max_S))
+    plan, keep = _text_train_split16(p, cfg, save, split16_cache, split16_out)
+    for li, lp in enumerate(p.layers):
+        x, sv = layer_fwd(x, lp, input_ids.shape[0], max_S, H, True, eps, save, plan[li] if plan is not None else None, keep,
+                          varlen=(cu, max_S))
         saved_layers.append(sv)
     rows = ops.gather_rows_at(x, last_rows)
     pooled, mp, rp = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=save)
@@ -2069,12 +2142,13 @@ def text_fwd_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, s
     return out, saved
 
 
-def text_bwd_packed(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool]):
-    """text_bwd on what text_fwd_packed saved: the same `need` masks and the same cut-off below the lowest layer asked for."""
+def text_bwd_packed(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool], split16=None):
+    """text_bwd on what text_fwd_packed saved: the same `need` masks and the same cut-off below the lowest layer asked for.
+    `split16`: as text_bwd's; the ragged attention backward has no statistics form, so dqkv takes the three-launch split."""
     t = cfg
     input_ids, saved_layers, cu, max_S, Tp, rows, mp, rp, pooled = saved
     N = input_ids.shape[0]
-    H = t.num_attention_heads
+    D, H = t.hidden_size, t.num_attention_heads
     names = p.names()
     needd = dict(zip(names, need))
     grads: Dict[str, Optional[torch.Tensor]] = {n: None for n in names}
@@ -2093,9 +2167,19 @@ def text_bwd_packed(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[b
     if lowest is None:
         return [grads[n] for n in names]
     dx = ops.scatter_last_rows(drows, cu, Tp)
+    # sp, the dY-statistics regime and the per-layer dx_stats decision as vision_bwd derives them.  The top
+    # layer's incoming dx is zero in all but one row per caption: a row-scaled split of an all-zero row gives zero pieces and
+    # alpha = 1 (split16_row_exp(0) = 0)
+    plan = split16.layers if split16 is not None and _VSPLIT16_BWD and split16.fresh() else None
+    dystats = plan is not None and _dystats_regime(Tp, D, p.layers[0].fc1_w.shape[0])
     for i in range(len(p.layers) - 1, max(lowest, 0) - 1, -1):
         lneed = {f: needd[f"layers.{i}.{f}"] for f in LayerParams.FIELDS}
-        dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], N, max_S, H, True, lneed, varlen=(cu, max_S))
+        sp = plan[i] if plan is not None else None      # None: the plain fp32 GEMMs (eps: what a forward on the plan left out, §9j)
+        below = dystats and i - 1 >= max(lowest, 0) and len(saved_layers[i - 1]) > 13
+        dxs = below and _split_wgrad_taken(bool(needd[f"layers.{i - 1}.fc2_w"]), plan[i - 1], saved_layers[i - 1][13].get("g"),
+                                           D, p.layers[i - 1].fc1_w.shape[0], Tp)
+        dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], N, max_S, H, True, lneed, None, sp, dxs, dystats, eps=t.layer_norm_eps,
+                           varlen=(cu, max_S))
         saved_layers[i] = None
         for f, tn in gr.items():
             grads[f"layers.{i}.{f}"] = tn

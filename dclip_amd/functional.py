@@ -117,48 +117,56 @@ class VisionTowerBf16Fn(torch.autograd.Function):
 
 class TextTowerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, input_ids, cfg, n_layers, split16_cache, *params):
+    def forward(ctx, input_ids, cfg, n_layers, split16_cache, train_split16_cache, *params):
         """`split16_cache`: the model's cache of split-fp16 weights (HipCLIPModel._split16_cache) — the frozen forward takes
-        the split-fp16 path with it (engine.text_fwd_frozen_split16, DCLIP_TEXT_SPLIT16); None: the plain fp32 path."""
+        the split-fp16 path with it (engine.text_fwd_frozen_split16, DCLIP_TEXT_SPLIT16); None: the plain fp32 path.
+        `train_split16_cache`: the TRAINABLE tower's own device plan (HipCLIPModel._tsplit16_train_cache) — a
+        forward that saves for the backward runs its full-size GEMMs with it, and the backward follows; None: plain fp32."""
         p = engine.TextParams.from_tensors([_c(t.detach()) for t in params], n_layers)
-        save = any(ctx.needs_input_grad[4:])
+        save = any(ctx.needs_input_grad[5:])
         if not save and len(p.layers) > 0:
             ctx.saved = None
             if split16_cache is not None and engine.text_split16_enabled():
                 return engine.text_fwd_frozen_split16(p, _c(input_ids), cfg, split16_cache)
             return engine.text_fwd_frozen(p, _c(input_ids), cfg)
-        out, saved = engine.text_fwd(p, _c(input_ids), cfg, save)
+        split16 = []                                       # the forward's split-fp16 plan, for the backward (§30)
+        out, saved = engine.text_fwd(p, _c(input_ids), cfg, save, split16_cache=train_split16_cache, split16_out=split16)
         ctx.p, ctx.saved, ctx.cfg = p, saved, cfg
+        ctx.split16 = split16[0] if split16 else None
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         if ctx.saved is None:
             raise RuntimeError("TextTowerFn.backward called twice, or forward ran without grad")
-        grads = engine.text_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[4:]))
-        ctx.saved = None
-        return (None, None, None, None, *grads)
+        grads = engine.text_bwd(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[5:]), split16=ctx.split16)
+        ctx.saved = ctx.split16 = None
+        return (None, None, None, None, None, *grads)
 
 
 class TextTowerPackedFn(torch.autograd.Function):
     """TextTowerFn for a TRAINABLE tower on packed captions (engine.text_fwd_packed / text_bwd_packed): `tables`
-    is HipCLIPModel._packed_text_tables' result.  Plain fp32 GEMMs, as the padded trainable tower runs."""
+    is HipCLIPModel._packed_text_tables' result.  Plain fp32 GEMMs, as the padded trainable tower runs, or — with
+    `train_split16_cache`, as TextTowerFn's — the split-fp16 plan."""
 
     @staticmethod
-    def forward(ctx, input_ids, cfg, n_layers, tables, *params):
+    def forward(ctx, input_ids, cfg, n_layers, tables, train_split16_cache, *params):
         p = engine.TextParams.from_tensors([_c(t.detach()) for t in params], n_layers)
-        save = any(ctx.needs_input_grad[4:])
-        out, saved = engine.text_fwd_packed(p, _c(input_ids), tables, cfg, save)
+        save = any(ctx.needs_input_grad[5:])
+        split16 = []
+        out, saved = engine.text_fwd_packed(p, _c(input_ids), tables, cfg, save, split16_cache=train_split16_cache,
+                                            split16_out=split16)
         ctx.p, ctx.saved, ctx.cfg = p, saved, cfg
+        ctx.split16 = split16[0] if split16 else None
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         if ctx.saved is None:
             raise RuntimeError("TextTowerPackedFn.backward called twice, or forward ran without grad")
-        grads = engine.text_bwd_packed(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[4:]))
-        ctx.saved = None
-        return (None, None, None, None, *grads)
+        grads = engine.text_bwd_packed(ctx.p, ctx.saved, _c(d_out), ctx.cfg, list(ctx.needs_input_grad[5:]), split16=ctx.split16)
+        ctx.saved = ctx.split16 = None
+        return (None, None, None, None, None, *grads)
 
 
 class CosineDistillationLossFn(torch.autograd.Function):

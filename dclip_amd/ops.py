@@ -180,6 +180,25 @@ def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool
     return out
 
 
+def colsum_segments(x: torch.Tensor, B: int, S: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Column sums of x [B*S, cols] summed per segment of S rows in order and folded over the B segments as the finish of
+    split_f16x3_rows_cols_stats folds a producer's partials: the db of that entry for the partials attention_bwd leaves with
+    `stats` / `rows_stats` on the same x, bit for bit."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1 or x.shape[0] != B * S:
+        raise ValueError("colsum_segments: x must be a 2-D fp32 device tensor [B*S, cols] with unit column stride")
+    N = x.shape[1]
+    if out is None:
+        out = torch.empty((N,), dtype=torch.float32, device=x.device)
+    if _f32(out, "out").numel() != N:
+        raise ValueError("colsum_segments: out size")
+    nbytes = lib.dclip_colsum_segments_f32_workspace(B, N)
+    ws = _ws.get(nbytes, x.device)
+    _lib.check(lib.dclip_colsum_segments_f32(x.data_ptr(), out.data_ptr(), B, S, N, x.stride(0), _ptr(ws), nbytes, _stream()),
+               "colsum_segments")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- LayerNorm
 
 def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, save_stats: bool = True):
@@ -305,15 +324,33 @@ def attention_bwd_stats_plan(B: int, S: int, H: int) -> int:
     return int(_lib.load().dclip_attention_bwd_stats_plan(B, S, H))
 
 
-def attention_bwd(qkv, out, dout, lse, B: int, S: int, H: int, causal: bool, stats: Optional[ColStats] = None):
+def attention_bwd_rows_stats_plan(B: int, S: int, H: int) -> int:
+    """Partial rows attention_bwd leaves with `rows_stats` (B) — the whole-row kernel's statistics twin, 65 <= S <= 80
+     — and 0 everywhere else."""
+    return int(_lib.load().dclip_attention_bwd_rows_stats_plan(B, S, H))
+
+
+def attention_bwd(qkv, out, dout, lse, B: int, S: int, H: int, causal: bool, stats: Optional[ColStats] = None,
+                  rows_stats: Optional[ColStats] = None):
     """`stats` (a ColStats of attention_bwd_stats_plan(B, S, H) partial rows, > 0, 3 H 64 columns): the kernel also leaves the
-    column partials of dqkv there; dqkv is bit-equal to the call without."""
+    column partials of dqkv there; dqkv is bit-equal to the call without.  `rows_stats`: the same for the
+    65 .. 80-row form (attention_bwd_rows_stats_plan); one of the two at most."""
     lib = _lib.load()
     _f32(qkv, "qkv"), _f32(out, "out"), _f32(dout, "dout"), _f32(lse, "lse")
     if qkv.numel() != B * S * 3 * H * 64 or out.numel() != B * S * H * 64 or dout.numel() != out.numel() \
             or lse.numel() != B * H * S:
         raise ValueError("attention_bwd: shape mismatch")
     dqkv = torch.empty_like(qkv)
+    if rows_stats is not None:
+        if stats is not None:
+            raise ValueError("attention_bwd: stats or rows_stats, not both")
+        st = rows_stats
+        if (st.P, st.cols) != (attention_bwd_rows_stats_plan(B, S, H), 3 * H * 64) or st.P == 0:
+            raise ValueError("attention_bwd: rows_stats must have attention_bwd_rows_stats_plan's row count and 3 H 64 columns")
+        _lib.check(lib.dclip_attention_bwd_rows_stats(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                                                      dqkv.data_ptr(), st.pmax.data_ptr(), st.psum.data_ptr(), B, S, H, int(causal),
+                                                      _stream()), "attention_bwd_rows_stats")
+        return dqkv
     if stats is not None:
         if (stats.P, stats.cols) != (attention_bwd_stats_plan(B, S, H), 3 * H * 64) or stats.P == 0:
             raise ValueError("attention_bwd: stats must have attention_bwd_stats_plan's row count and 3 H 64 columns")

@@ -735,6 +735,17 @@ int dclip_gemm_f16_scaled_rows_stats_dev(const void* A, const void* W, float* C,
 int dclip_attention_bwd_stats_plan(int B, int S, int H);
 int dclip_attention_bwd_stats(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, void* pmax,
                               float* psum, int B, int S, int H, int causal, void* stream);
+/* attention_bwd_rows_stats: the same for 65 <= S <= 80 (the whole-row kernel's statistics twin), cols = 3 D, P = B;
+ * _plan is 0 everywhere else, and attention_bwd_stats_plan stays 0 above 64. */
+int dclip_attention_bwd_rows_stats_plan(int B, int S, int H);
+int dclip_attention_bwd_rows_stats(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, void* pmax,
+                                   float* psum, int B, int S, int H, int causal, void* stream);
+/* colsum_segments_f32: db[c] = sum of x [B*S][cols] over the rows, summed per segment of S rows in order and folded over the B
+ * segments as the finish of split_f32_f16x3_rows_cols_stats folds a producer's partials: bit-equal to that entry's db for the
+ * partials of attention_bwd_stats / attention_bwd_rows_stats on the same x. */
+size_t dclip_colsum_segments_f32_workspace(int B, int cols);
+int dclip_colsum_segments_f32(const float* x, float* db, int B, int S, int cols, int ldx, void* workspace, size_t workspace_bytes,
+                              void* stream);
 int dclip_layernorm_bwd_stats_plan(int rows, int D);
 int dclip_layernorm_bwd_stats(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                               const float* dresidual, float* dx, float* dgamma, float* dbeta, void* pmax, float* psum, int rows, int D,
