@@ -206,26 +206,29 @@ def _galloc(alloc, name: str, shape, device) -> torch.Tensor:
 
 
 def linear_param_grads(dy, x, need_w: bool, need_b: bool, gr: Dict[str, torch.Tensor], wkey: str, bkey: str, alloc=None,
-                       sp: Optional[Split16Layer] = None, act: Optional[str] = None, x3: Optional[torch.Tensor] = None):
+                       sp: Optional[Split16Layer] = None, act: Optional[str] = None, x3: Optional[torch.Tensor] = None,
+                       stats=None, db_segments=None):
     """dW = dy^T x and db = colsum(dy) of one nn.Linear.  When both are wanted the bias gradient comes out of the
     weight-gradient GEMM (DCLIP_EPI_A_ROWSUM): dy is streamed once, no separate column-sum launch.
     `sp`, `act`, `x3` (the forward's [hi|lo|hi] split of x, made with the plan scale sp.act(act)): the split-fp16 weight
     gradient when the plan takes the shape — ONE pass over dy gives its row split (for _dgrad), its column
     statistics, db and its column-scaled [hi|lo] split; dW is the segmented token-major GEMM of that with x3 (x itself, which may
     be a _Remat, gives its shape only).  Returns the row
-    pieces (dy3, row_alpha) for _dgrad then, None otherwise.  A dy that carries the column partials its producer left
-    (`dy.dystats`, _with_stats) is read ONCE: the finish over the partials, then one pass that writes both splits (§9g)."""
+    pieces (dy3, row_alpha) for _dgrad then, None otherwise.  `stats`: the column partials (a ColStats, _with_stats) that the
+    producer of dy left — dy is then read ONCE: the finish over the partials, then one pass that writes both splits (§9g).
+    `db_segments` = (B, S), for a dy without partials: the bias gradient is summed per caption in the statistics form's order
+    (ops.colsum_segments, §30)."""
     dev = dy.device
     if dy.dim() == 2 and dy.stride(1) == 1 and _split_wgrad_taken(need_w, sp, x3, dy.shape[1], x.shape[1], dy.shape[0]):
         M, N = dy.shape[1], x.shape[1]
         db = _galloc(alloc, bkey, (M,), dev) if need_b else None
-        st = getattr(dy, "dystats", None) if _VSPLIT16_DYSTATS else None
+        st = stats if _VSPLIT16_DYSTATS else None
         pc = split16_pieces([(dy.shape[0], N, M)])      # the row pieces' one reader: _dgrad's dX [tokens, in_f] = dy3 wt^T along out_f
         if st is not None:
             dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_cols_stats(dy, st, db=db, pieces=pc)
-        elif need_b and getattr(dy, "db_segments", None) is not None:      # §30: the bias gradient in the statistics form's order
+        elif need_b and db_segments is not None:      # §30: the bias gradient in the statistics form's order
             dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=None, pieces=pc)
-            ops.colsum_segments(dy, *dy.db_segments, out=db)
+            ops.colsum_segments(dy, *db_segments, out=db)
         else:
             dy3, row_alpha, yc, _, col_alpha = ops.split_f16x3_rows_colstats(dy, db=db, pieces=pc)
         if need_b:
@@ -285,8 +288,8 @@ def _attention_bwd_stats_form(B: int, S: int, H: int, causal: bool):
 
 
 def _ln_bwd(dy, x, gamma, mean, rstd, dresidual, want: bool, gr, wkey: str, bkey: str, alloc, dx_stats: bool = False):
-    """LayerNorm backward; dγ / dβ land where `alloc` says.  `dx_stats`: dx is the dY of a split weight gradient and leaves with
-    its column partials (`dx.dystats`) when the kernel has that form."""
+    """LayerNorm backward -> (dx, stats); dγ / dβ land where `alloc` says.  `dx_stats`: dx is the dY of a split weight gradient
+    and its column partials are asked for; `stats` is that ColStats when the kernel has the form, None otherwise."""
     D = x.shape[-1]
     st = _with_stats(dx_stats, ops.layernorm_bwd_stats_plan(x.numel() // D, D) if dx_stats else 0, D, dy.device)
     if want:
@@ -296,21 +299,20 @@ def _ln_bwd(dy, x, gamma, mean, rstd, dresidual, want: bool, gr, wkey: str, bkey
         gr[wkey], gr[bkey] = dg, db
     else:
         dx, _, _ = ops.layernorm_bwd(dy, x, gamma, mean, rstd, dresidual=dresidual, need_param_grads=False, stats=st)
-    if st is not None:
-        dx.dystats = st
-    return dx
+    return dx, st
 
 
 def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None, out_stats: bool = False):
-    """dX = dy w (times quick_gelu'(aux) when given), the data gradient of a linear layer.  `sp` (a Split16Layer with
+    """(dX, stats): dX = dy w (times quick_gelu'(aux) when given), the data gradient of a linear layer.  `sp` (a Split16Layer with
     transposed copies): dy is split with one scale per row and meets the [hi|hi|lo] copy of w^T on the fp16 MFMAs (DESIGN.md
     §9e); None = the plain fp32 GEMM.  dy itself stays fp32 for the weight and bias gradients.  `rows`: the row pieces
     (dy3, row_alpha) when linear_param_grads has already made them in its fused pass (§9f).  `out_stats`: dX is itself the dY of
-    a split weight gradient and leaves with its column partials (`.dystats`, §9g) when the GEMM's plan has that form."""
+    a split weight gradient and its column partials are asked for (§9g); `stats` is that ColStats when the GEMM's plan has the
+    form, None otherwise."""
     if sp is None:
         if aux is None:
-            return ops.gemm(dy, w, ops.LAYOUT_NN)
-        return ops.gemm(dy, w, ops.LAYOUT_NN, aux=aux, epilogue=ops.EPI_DGELU)
+            return ops.gemm(dy, w, ops.LAYOUT_NN), None
+        return ops.gemm(dy, w, ops.LAYOUT_NN, aux=aux, epilogue=ops.EPI_DGELU), None
     wt = sp.wt[name]
     dy3, row_alpha = rows if rows is not None else ops.split_f16x3_rows(
         dy, pieces=split16_pieces([(dy.shape[0], wt.shape[0], wt.shape[1] // 3)]))
@@ -324,9 +326,7 @@ def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None, ou
         st = _with_stats(out_stats, ops.gemm_f16_rows_stats_plan(dy3.shape[0], wt.shape[0], k3) if out_stats else 0, wt.shape[0],
                          dy3.device)
         dx = ops.gemm_f16_rows_dev(dy3, wt, sp.walpha(name), row_alpha, dgelu_h=aux, stats=st)
-    if st is not None:
-        dx.dystats = st
-    return dx
+    return dx, st
 
 
 def _remat_ln(ln, x, w, b, eps: Optional[float]):
@@ -340,12 +340,14 @@ def _remat_ln(ln, x, w, b, eps: Optional[float]):
 
 def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, need: Dict[str, bool], alloc=None,
               sp: Optional[Split16Layer] = None, dx_stats: bool = False, dystats: bool = False, eps: Optional[float] = None,
-              varlen=None):
-    """Returns (dx, grads) with grads keyed like LayerParams.FIELDS (missing = not needed).  `varlen`: as in layer_fwd.  `alloc(field, shape)`:
-    see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad).  `eps`: the layer's, for an fp32 LayerNorm
-    output the forward did not keep (_remat_ln, §9j).  `dystats` (the caller's decision for
-    the whole tower, _dystats_regime): each kernel that produces the dY of a weight gradient that will take the split path is
-    asked for its column partials (§9g); `dx_stats`: the caller says so for the returned dx (the layer below's fc2)."""
+              varlen=None, dx2_stats=None):
+    """Returns (dx, grads, stats) with grads keyed like LayerParams.FIELDS (missing = not needed).  `varlen`: as in layer_fwd.
+    `alloc(field, shape)`: see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad).  `eps`: the layer's,
+    for an fp32 LayerNorm output the forward did not keep (_remat_ln, §9j).  `dystats` (the caller's decision for the whole
+    tower, _dystats_regime): each kernel that produces the dY of a weight gradient that will take the split path is asked for
+    its column partials (§9g), and they go to that weight gradient as a value.  `dx_stats`: the caller says so for the returned
+    dx (the layer below's fc2) — `stats` is then its ColStats, or None where the kernel has no such form; `dx2_stats`: what the
+    producer of dx2 returned that way (None: dx2 takes the three-launch pass)."""
     x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved[:13]
     s3 = saved[13] if len(saved) > 13 and sp is not None else {}      # the forward's split operands (layer_fwd, keep_split)
     gr: Dict[str, torch.Tensor] = {}
@@ -353,39 +355,39 @@ def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, 
     ln1, ln2 = _remat_ln(ln1, x, p.ln1_w, p.ln1_b, eps), _remat_ln(ln2, x1, p.ln2_w, p.ln2_b, eps)
     if g is None:
         g = _Remat(h.shape, lambda: ops.quick_gelu(h))
-    rows = linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc, sp, "g", s3.get("g"))
-    dh = _dgrad(dx2, p.fc2_w, sp, "fc2", aux=h, rows=rows,
-                out_stats=dystats and _split_wgrad_taken(bool(need.get("fc1_w")), sp, s3.get("ln2"), I, D, T))
+    rows = linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc, sp, "g", s3.get("g"),
+                              stats=dx2_stats)
+    dh, dh_stats = _dgrad(dx2, p.fc2_w, sp, "fc2", aux=h, rows=rows,
+                          out_stats=dystats and _split_wgrad_taken(bool(need.get("fc1_w")), sp, s3.get("ln2"), I, D, T))
     rows = linear_param_grads(dh, ln2, bool(need.get("fc1_w")), bool(need.get("fc1_b")), gr, "fc1_w", "fc1_b", alloc, sp, "ln2",
-                              s3.get("ln2"))
-    dln2 = _dgrad(dh, p.fc1_w, sp, "fc1", rows=rows)
+                              s3.get("ln2"), stats=dh_stats)
+    dln2, _ = _dgrad(dh, p.fc1_w, sp, "fc1", rows=rows)
     del dh
-    dx1 = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc,
-                  dx_stats=dystats and _split_wgrad_taken(bool(need.get("out_w")), sp, s3.get("ctx"), D, D, T))
+    dx1, dx1_stats = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc,
+                             dx_stats=dystats and _split_wgrad_taken(bool(need.get("out_w")), sp, s3.get("ctx"), D, D, T))
     rows = linear_param_grads(dx1, attn, bool(need.get("out_w")), bool(need.get("out_b")), gr, "out_w", "out_b", alloc, sp, "ctx",
-                              s3.get("ctx"))
-    dattn = _dgrad(dx1, p.out_w, sp, "out", rows=rows)
+                              s3.get("ctx"), stats=dx1_stats)
+    dattn, _ = _dgrad(dx1, p.out_w, sp, "out", rows=rows)
     qkv_stats = dystats and _split_wgrad_taken(bool(need.get("qkv_w")), sp, s3.get("ln1"), 3 * D, D, T)
+    db_segments = None
     if varlen is None:
         form, P = _attention_bwd_stats_form(B, S, H, causal) if qkv_stats else (None, 0)
         st = _with_stats(qkv_stats, P, 3 * D, dattn.device)
         dqkv = ops.attention_bwd(qkv, attn, dattn, lse, B, S, H, causal, **({form: st} if st is not None else {}))
         if form == "segments" and _VSPLIT16_DYSTATS:
-            dqkv.db_segments = (B, S)
+            db_segments = (B, S)
     else:
         if not causal:
             raise ValueError("layer_bwd: the packed layer is causal")
         st = None      # the tiled ragged kernels have no statistics form: dqkv takes the three-launch split (§30)
         dqkv = ops.attention_varlen_causal_bwd(qkv, varlen[0], attn, dattn, lse, varlen[1], H)
-    if st is not None:
-        dqkv.dystats = st
     rows = linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc, sp, "ln1",
-                              s3.get("ln1"))
-    dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv", rows=rows)
+                              s3.get("ln1"), stats=st, db_segments=db_segments)
+    dln1, _ = _dgrad(dqkv, p.qkv_w, sp, "qkv", rows=rows)
     del dqkv, rows
-    dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dx1, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc,
-                 dx_stats=dx_stats)
-    return dx, gr
+    dx, stats = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dx1, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc,
+                        dx_stats=dx_stats)
+    return dx, gr, stats
 
 
 # --------------------------------------------------------------------------------------------- last vision layer
@@ -421,8 +423,9 @@ def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, sa
 
 def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need: Dict[str, bool], alloc=None,
                        sp: Optional[Split16Layer] = None, dx_stats: bool = False, eps: Optional[float] = None):
-    """dx2 [B, D] is the gradient w.r.t. the CLS rows of the final hidden state; returns (dx [B*S, D], grads).  `sp`: the
-    full-size qkv data gradient takes the split-fp16 path (_dgrad); the M = B GEMMs stay on ops.gemm."""
+    """dx2 [B, D] is the gradient w.r.t. the CLS rows of the final hidden state; returns (dx [B*S, D], grads, stats) — `stats`:
+    dx's column partials when `dx_stats` asked for them, as layer_bwd's.  `sp`: the full-size qkv data gradient takes the
+    split-fp16 path (_dgrad); the M = B GEMMs stay on ops.gemm."""
     x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g = saved[:13]
     s3 = saved[13] if len(saved) > 13 and sp is not None else {}
     D = x.shape[1]
@@ -432,18 +435,18 @@ def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need:
     dh = ops.gemm(dx2, p.fc2_w, ops.LAYOUT_NN, aux=h, epilogue=ops.EPI_DGELU)
     linear_param_grads(dh, ln2, bool(need.get("fc1_w")), bool(need.get("fc1_b")), gr, "fc1_w", "fc1_b", alloc)
     dln2 = ops.gemm(dh, p.fc1_w, ops.LAYOUT_NN)
-    dx1 = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc)
+    dx1, _ = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc)
     linear_param_grads(dx1, attn, bool(need.get("out_w")), bool(need.get("out_b")), gr, "out_w", "out_b", alloc)
     dattn = ops.gemm(dx1, p.out_w, ops.LAYOUT_NN)
     dqkv = ops.attention_cls_bwd(qkv, attn, dattn, lse, B, S, H)          # [B*S, 3D]; d q only on the CLS rows
     rows = linear_param_grads(dqkv, ln1, bool(need.get("qkv_w")), bool(need.get("qkv_b")), gr, "qkv_w", "qkv_b", alloc, sp, "ln1",
                               s3.get("ln1"))
-    dln1 = _dgrad(dqkv, p.qkv_w, sp, "qkv", rows=rows)
+    dln1, _ = _dgrad(dqkv, p.qkv_w, sp, "qkv", rows=rows)
     del dqkv, rows
     dres = ops.scatter_rows(dx1, None, B, S, D)                           # the skip connection carries dx1 on CLS rows only
-    dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dres, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc,
-                 dx_stats=dx_stats)       # (dqkv comes from attention_cls_bwd, which has no statistics form: three launches)
-    return dx, gr
+    dx, stats = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dres, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc,
+                        dx_stats=dx_stats)      # (dqkv comes from attention_cls_bwd, which has no statistics form: three launches)
+    return dx, gr, stats
 
 
 # --------------------------------------------------------------------------------------------- vision tower
@@ -531,11 +534,7 @@ def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hid
         hidden_out.append(x)
     saved_layers = []
     prune = hidden_out is None and len(p.layers) > 0          # full hidden states are only materialised on request
-    plan = _vision_split16_plan(p.layers, v, split16_cache) if save and split16_cache is not None and _VSPLIT16 else None
-    keep = False
-    if plan is not None and split16_out is not None and _VSPLIT16_BWD and plan[0].wt is not None:
-        split16_out.append(Split16Bwd(plan, split16_cache["__vsplit16__"], p.layers))
-        keep = _VSPLIT16_WGRAD            # that backward's weight gradients take the forward's split operands (§9f)
+    plan, keep = _train_split16(p.layers, v, save, split16_cache, split16_out, _VSPLIT16)
     for li, lp in enumerate(p.layers):
         sp = plan[li] if plan is not None else None
         if prune and li == len(p.layers) - 1:
@@ -554,6 +553,101 @@ def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hid
     return out, saved
 
 
+# The backward of the fp32 / split-fp16 towers is assembled from the pieces below, each written once: _lowest_needed (all four
+# backwards), _layers_bwd (the encoder stack of vision_bwd, text_bwd and text_bwd_packed), _vision_tail_bwd / _vision_head_bwd
+# (vision_bwd and vision_bwd_bf16) and, next to the text tower, _text_tail_bwd (text_bwd and text_bwd_packed).  A schedule keeps
+# what is its own: how dx enters the stack and what happens below layer 0.
+
+def _lowest_needed(names, needd: Dict[str, bool], head, tail) -> Optional[int]:
+    """The lowest layer that still needs a gradient: -1 for a parameter of the `head`, None when nothing but the `tail` does —
+    the backward stops as soon as nothing below still needs one (e.g. only visual_projection trainable)."""
+    lowest = None
+    for n in names:
+        if needd[n] and n not in tail:
+            li = -1 if n in head else int(n.split(".")[1])
+            lowest = li if lowest is None else min(lowest, li)
+    return lowest
+
+
+def _layers_bwd(dx, layers: List[LayerParams], saved_layers, needd: Dict[str, bool], grads, lowest: int, rows: int, B: int, S: int,
+                H: int, causal: bool, eps: float, split16=None, varlen=None, alloc=None, on_ready=None, dcls=None):
+    """The encoder stack's backward from the top layer down to max(lowest, 0), fp32 or split-fp16 -> dx below the last layer
+    run.  `rows`: the token rows of a full-size layer (B S, or Tp with `varlen`, layer_bwd's).  `split16`: the forward's
+    Split16Bwd — the full-size data- and weight-gradient GEMMs run on its plan unless a watched parameter has changed since;
+    None = the plain fp32 GEMMs (eps: what a forward on the plan left out, §9j).  `dcls` [B, D] (vision): the top layer is the
+    pruned one and takes it (last_layer_bwd_cls); `dx` is not read then.  Each layer's gradients go to `grads` under
+    "layers.<i>.<field>", are written where `alloc` says and reported to `on_ready` as soon as the layer is done; its saved
+    activations are released.  A top layer's incoming dx may be zero in all but one row per sequence (scatter_rows): a
+    row-scaled split of an all-zero row gives zero pieces and alpha = 1 (split16_row_exp(0) = 0)."""
+    n_layers, bottom = len(layers), max(lowest, 0)
+    D = (dx if dcls is None else dcls).shape[1]
+    plan = split16.layers if split16 is not None and _VSPLIT16_BWD and split16.fresh() else None
+    dystats = plan is not None and _dystats_regime(rows, D, layers[0].fc1_w.shape[0])
+    dx_stats = None                                   # the column partials that came with dx (§9g): a value, layer to layer
+    for i in range(n_layers - 1, bottom - 1, -1):
+        lneed = {f: needd[f"layers.{i}.{f}"] for f in LayerParams.FIELDS}
+        lalloc = None if alloc is None else (lambda f, shape, i=i: alloc(f"layers.{i}.{f}", shape))
+        sp = plan[i] if plan is not None else None
+        # dx is the dY of the layer below's fc2: its producer is asked for the column partials when that weight gradient will
+        # take the split path (§9g)
+        below = dystats and i - 1 >= bottom and len(saved_layers[i - 1]) > 13
+        dxs = below and _split_wgrad_taken(bool(needd[f"layers.{i - 1}.fc2_w"]), plan[i - 1], saved_layers[i - 1][13].get("g"),
+                                           D, layers[i - 1].fc1_w.shape[0], rows)
+        if dcls is not None and i == n_layers - 1:
+            dx, gr, dx_stats = last_layer_bwd_cls(dcls, layers[i], saved_layers[i], B, S, H, lneed, lalloc, sp, dxs, eps=eps)
+        else:
+            dx, gr, dx_stats = layer_bwd(dx, layers[i], saved_layers[i], B, S, H, causal, lneed, lalloc, sp, dxs, dystats, eps=eps,
+                                         varlen=varlen, dx2_stats=dx_stats)
+        saved_layers[i] = None
+        for f, t in gr.items():
+            grads[f"layers.{i}.{f}"] = t
+        if on_ready is not None:
+            on_ready({f"layers.{i}.{f}": t for f, t in gr.items()})
+    return dx
+
+
+def _vision_tail_bwd(p: VisionParams, d_out, cls_tok, mp, rp, pooled, needd: Dict[str, bool], grads, alloc, on_ready):
+    """proj_w's gradient, dpooled and the post-LayerNorm backward -> dcls [B, D]; the tail group is reported to `on_ready`."""
+    if needd["proj_w"]:
+        grads["proj_w"] = ops.gemm(d_out, pooled, ops.LAYOUT_TN, out=_galloc(alloc, "proj_w", tuple(p.proj_w.shape), d_out.device))
+    dpooled = ops.gemm(d_out, p.proj_w, ops.LAYOUT_NN)
+    dcls, _ = _ln_bwd(dpooled, cls_tok, p.post_w, mp, rp, None, bool(needd["post_w"] or needd["post_b"]), grads, "post_w", "post_b",
+                      alloc)
+    if on_ready is not None:
+        on_ready({n: grads[n] for n in VisionParams.TAIL if grads[n] is not None})
+    return dcls
+
+
+def _vision_head_bwd(p: VisionParams, dx, emb, m0, r0, cols, B: int, S: int, v, grid, needd: Dict[str, bool], grads, alloc, on_ready,
+                     k16=None):
+    """Below layer 0: the pre-LayerNorm backward, the gradients of pos / class_embedding (a column sum of demb; on another
+    `grid` the transpose of the resample, _grid_pos_grad) and of patch_w; the head group is reported to `on_ready`.  `k16` (the
+    _Train16 of a 16-bit forward): columns saved in that type give patch_w's gradient on its token-major split-K kernel."""
+    D, dev = v.hidden_size, dx.device
+    demb, _ = _ln_bwd(dx, emb, p.pre_w, m0, r0, None, bool(needd["pre_w"] or needd["pre_b"]), grads, "pre_w", "pre_b", alloc)
+    if needd["pos"] or needd["class_embedding"]:
+        dpos = ops.colsum(demb.view(B, S * D),
+                          out=(_galloc(alloc, "pos", (S * D,), dev) if needd["pos"] and grid is None else None))
+        if needd["pos"]:
+            grads["pos"] = dpos.view(S, D) if grid is None else _grid_pos_grad(dpos, p, v, grid, alloc, dev)
+        if needd["class_embedding"]:
+            ce = _galloc(alloc, "class_embedding", (D,), dev)
+            ce.copy_(dpos[:D])
+            grads["class_embedding"] = ce
+    if needd["patch_w"]:
+        dpatch = ops.vision_assemble_bwd(demb, B, S, D)
+        pw = _galloc(alloc, "patch_w", (D, p.patch_w.numel() // D), dev)
+        if cols.dtype != torch.float32:           # token-major split-K weight gradient from the saved 16-bit columns
+            got = k16.wgrad_tokmajor(k16.cast(dpatch), cols, out=pw)
+            if got is None:
+                raise RuntimeError("patch-embedding weight gradient: the token-major 16-bit kernel refused a shape its plan accepted")
+            grads["patch_w"] = got.view_as(p.patch_w)
+        else:
+            grads["patch_w"] = ops.gemm(dpatch, cols, ops.LAYOUT_TN, out=pw).view_as(p.patch_w)
+    if on_ready is not None:
+        on_ready({n: grads[n] for n in VisionParams.HEAD if grads[n] is not None})
+
+
 def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool], on_ready=None, alloc=None, split16=None):
     """Gradients for VisionParams.tensors() order (None where not needed).  `split16`: the forward's Split16Bwd — the
     full-size data-gradient GEMMs then run on its split-fp16 weights, unless a watched parameter has changed since.  `on_ready(dict name -> grad)` is called as
@@ -567,62 +661,15 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
     names = p.names()
     needd = dict(zip(names, need))
     grads: Dict[str, Optional[torch.Tensor]] = {n: None for n in names}
-    dev = d_out.device
-    if needd["proj_w"]:
-        grads["proj_w"] = ops.gemm(d_out, pooled, ops.LAYOUT_TN, out=_galloc(alloc, "proj_w", tuple(p.proj_w.shape), dev))
-    dpooled = ops.gemm(d_out, p.proj_w, ops.LAYOUT_NN)
-    dcls = _ln_bwd(dpooled, cls_tok, p.post_w, mp, rp, None, bool(needd["post_w"] or needd["post_b"]), grads, "post_w", "post_b",
-                   alloc)
-    if on_ready is not None:
-        on_ready({n: grads[n] for n in VisionParams.TAIL if grads[n] is not None})
-    n_layers = len(p.layers)
-    # stop as soon as nothing below still needs a gradient (e.g. only visual_projection trainable)
-    lowest = None
-    for i, n in enumerate(names):
-        if needd[n] and n not in VisionParams.TAIL:
-            li = -1 if n in VisionParams.HEAD else int(n.split(".")[1])
-            lowest = li if lowest is None else min(lowest, li)
+    dcls = _vision_tail_bwd(p, d_out, cls_tok, mp, rp, pooled, needd, grads, alloc, on_ready)
+    lowest = _lowest_needed(names, needd, VisionParams.HEAD, VisionParams.TAIL)
     if lowest is None:
         return [grads[n] for n in names]
     dx = None if pruned else ops.scatter_rows(dcls, None, B, S, D)
-    plan = split16.layers if split16 is not None and _VSPLIT16_BWD and split16.fresh() else None
-    dystats = plan is not None and _dystats_regime(B * S, D, p.layers[0].fc1_w.shape[0])
-    for i in range(n_layers - 1, max(lowest, 0) - 1, -1):
-        lneed = {f: needd[f"layers.{i}.{f}"] for f in LayerParams.FIELDS}
-        lalloc = None if alloc is None else (lambda f, shape, i=i: alloc(f"layers.{i}.{f}", shape))
-        sp = plan[i] if plan is not None else None
-        # dx is the dY of the layer below's fc2: its producer is asked for the column partials when that weight gradient will
-        # take the split path (§9g)
-        below = dystats and i - 1 >= max(lowest, 0) and len(saved_layers[i - 1]) > 13
-        dxs = below and _split_wgrad_taken(bool(needd[f"layers.{i - 1}.fc2_w"]), plan[i - 1], saved_layers[i - 1][13].get("g"),
-                                           D, p.layers[i - 1].fc1_w.shape[0], B * S)
-        if pruned and i == n_layers - 1:
-            dx, gr = last_layer_bwd_cls(dcls, p.layers[i], saved_layers[i], B, S, H, lneed, lalloc, sp, dxs, eps=v.layer_norm_eps)
-        else:
-            dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, S, H, False, lneed, lalloc, sp, dxs, dystats,
-                               eps=v.layer_norm_eps)
-        saved_layers[i] = None
-        for f, t in gr.items():
-            grads[f"layers.{i}.{f}"] = t
-        if on_ready is not None:
-            on_ready({f"layers.{i}.{f}": t for f, t in gr.items()})
+    dx = _layers_bwd(dx, p.layers, saved_layers, needd, grads, lowest, B * S, B, S, H, False, v.layer_norm_eps, split16,
+                     alloc=alloc, on_ready=on_ready, dcls=dcls if pruned else None)
     if lowest < 0:
-        demb = _ln_bwd(dx, emb, p.pre_w, m0, r0, None, bool(needd["pre_w"] or needd["pre_b"]), grads, "pre_w", "pre_b", alloc)
-        if needd["pos"] or needd["class_embedding"]:
-            dpos = ops.colsum(demb.view(B, S * D),
-                              out=(_galloc(alloc, "pos", (S * D,), dev) if needd["pos"] and grid is None else None))
-            if needd["pos"]:
-                grads["pos"] = dpos.view(S, D) if grid is None else _grid_pos_grad(dpos, p, v, grid, alloc, dev)
-            if needd["class_embedding"]:
-                ce = _galloc(alloc, "class_embedding", (D,), dev)
-                ce.copy_(dpos[:D])
-                grads["class_embedding"] = ce
-        if needd["patch_w"]:
-            dpatch = ops.vision_assemble_bwd(demb, B, S, D)
-            pw = _galloc(alloc, "patch_w", (D, p.patch_w.numel() // D), dev)
-            grads["patch_w"] = ops.gemm(dpatch, cols, ops.LAYOUT_TN, out=pw).view_as(p.patch_w)
-        if on_ready is not None:
-            on_ready({n: grads[n] for n in VisionParams.HEAD if grads[n] is not None})
+        _vision_head_bwd(p, dx, emb, m0, r0, cols, B, S, v, grid, needd, grads, alloc, on_ready)
     return [grads[n] for n in names]
 
 
@@ -1134,7 +1181,7 @@ def layer_bwd_bf16(dx2, p: LayerParams, c: dict, pre: str, saved, B: int, S: int
         gr["fc1_b"] = k.rowsum(dhT, M, out=_galloc(alloc, "fc1_b", (I,), dev))
     dln2 = k.gemm(dh16, _w16t(c, pre + "fc1", p.fc1_w, dtype), k=dh16.shape[1])                          # [M, D] fp32
     del dh16, dhT
-    dx1 = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc)
+    dx1, _ = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc)
     # ---- out_proj
     dx1T, dx1_16 = k.transpose(dx1, want_copy=True)
     if need.get("out_w"):
@@ -1152,7 +1199,7 @@ def layer_bwd_bf16(dx2, p: LayerParams, c: dict, pre: str, saved, B: int, S: int
         gr["qkv_b"] = ops.colsum(dqkv, out=_galloc(alloc, "qkv_b", (3 * D,), dev))
     dln1 = k.gemm(dqkv16, _w16t(c, pre + "qkv", p.qkv_w, dtype), k=3 * D)
     del dqkv, dqkvT, dqkv16
-    dx = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dx1, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc)
+    dx, _ = _ln_bwd(dln1, x, p.ln1_w, m1, r1, dx1, bool(need.get("ln1_w") or need.get("ln1_b")), gr, "ln1_w", "ln1_b", alloc)
     if below_fc2_b is not None:
         ops.colsum(dx, out=below_fc2_b)
     return dx, None, gr
@@ -1217,18 +1264,8 @@ def vision_bwd_bf16(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List
     needd = dict(zip(names, need))
     grads: Dict[str, Optional[torch.Tensor]] = {n: None for n in names}
     dev = d_out.device
-    if needd["proj_w"]:
-        grads["proj_w"] = ops.gemm(d_out, pooled, ops.LAYOUT_TN, out=_galloc(alloc, "proj_w", tuple(p.proj_w.shape), dev))
-    dpooled = ops.gemm(d_out, p.proj_w, ops.LAYOUT_NN)
-    dcls = _ln_bwd(dpooled, cls_tok, p.post_w, mp, rp, None, bool(needd["post_w"] or needd["post_b"]), grads, "post_w", "post_b",
-                   alloc)
-    if on_ready is not None:
-        on_ready({n: grads[n] for n in VisionParams.TAIL if grads[n] is not None})
-    lowest = None
-    for n in names:
-        if needd[n] and n not in VisionParams.TAIL:
-            li = -1 if n in VisionParams.HEAD else int(n.split(".")[1])
-            lowest = li if lowest is None else min(lowest, li)
+    dcls = _vision_tail_bwd(p, d_out, cls_tok, mp, rp, pooled, needd, grads, alloc, on_ready)
+    lowest = _lowest_needed(names, needd, VisionParams.HEAD, VisionParams.TAIL)
     if lowest is None:
         return [grads[n] for n in names]
     dx = ops.scatter_rows(dcls, None, B, S, D)
@@ -1251,28 +1288,7 @@ def vision_bwd_bf16(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List
         if on_ready is not None:
             on_ready({f"layers.{i}.{f}": t for f, t in gr.items()})
     if lowest < 0:
-        demb = _ln_bwd(dx, emb, p.pre_w, m0, r0, None, bool(needd["pre_w"] or needd["pre_b"]), grads, "pre_w", "pre_b", alloc)
-        if needd["pos"] or needd["class_embedding"]:
-            dpos = ops.colsum(demb.view(B, S * D),
-                              out=(_galloc(alloc, "pos", (S * D,), dev) if needd["pos"] and grid is None else None))
-            if needd["pos"]:
-                grads["pos"] = dpos.view(S, D) if grid is None else _grid_pos_grad(dpos, p, v, grid, alloc, dev)
-            if needd["class_embedding"]:
-                ce = _galloc(alloc, "class_embedding", (D,), dev)
-                ce.copy_(dpos[:D])
-                grads["class_embedding"] = ce
-        if needd["patch_w"]:
-            dpatch = ops.vision_assemble_bwd(demb, B, S, D)
-            pw = _galloc(alloc, "patch_w", (D, p.patch_w.numel() // D), dev)
-            if cols.dtype != torch.float32:           # token-major split-K weight gradient from the saved 16-bit columns
-                got = k.wgrad_tokmajor(k.cast(dpatch), cols, out=pw)
-                if got is None:
-                    raise RuntimeError("patch-embedding weight gradient: the token-major 16-bit kernel refused a shape its plan accepted")
-                grads["patch_w"] = got.view_as(p.patch_w)
-            else:
-                grads["patch_w"] = ops.gemm(dpatch, cols, ops.LAYOUT_TN, out=pw).view_as(p.patch_w)
-        if on_ready is not None:
-            on_ready({n: grads[n] for n in VisionParams.HEAD if grads[n] is not None})
+        _vision_head_bwd(p, dx, emb, m0, r0, cols, B, S, v, grid, needd, grads, alloc, on_ready, k16=k)
     return [grads[n] for n in names]
 
 
@@ -1345,12 +1361,37 @@ def text_fwd_frozen(p: TextParams, input_ids: torch.Tensor, cfg):
     ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, t.layer_norm_eps, save_stats=False)
     qkv = ops.gemm(ln1, lp.qkv_w, ops.LAYOUT_NT, bias=lp.qkv_b)
     attn = ops.attention_row_fwd(qkv, eos, B, T, H)
-    x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows(x, eos, B, T, D))
-    ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, t.layer_norm_eps, save_stats=False)
+    rows = _pruned_tail_f32(attn, ops.gather_rows(x, eos, B, T, D), lp, t.layer_norm_eps)
+    return _text_head(rows, p, t.layer_norm_eps)[0]
+
+
+def _pruned_tail_f32(ctx_rows, x_rows, lp: LayerParams, eps: float):
+    """What follows the attention in the pruned last layer of a frozen fp32 (or split-fp16) tower, on the pooled rows only
+    (M = batch, ops.gemm): out-projection + residual, LayerNorm 2, fc1 with quick-GELU, fc2 + residual.  `ctx_rows`: those rows'
+    attention context, `x_rows`: their rows of the layer's input — the caller launches the one-row attention first and the row
+    gather second.  Returns the final hidden state of the rows.  Used by text_fwd_frozen, text_fwd_frozen_split16,
+    text_fwd_frozen_packed ("fp32" / split16) and _frozen_split16_last_cls (last_layer_fwd_cls, which saves for a backward, is
+    not a copy)."""
+    x1 = ops.gemm(ctx_rows, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=x_rows)
+    ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
     g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
-    rows = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
-    pooled, _, _ = ops.layernorm_fwd(rows, p.final_w, p.final_b, t.layer_norm_eps, save_stats=False)
-    return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+    return ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
+
+
+def _text_head(rows, p: TextParams, eps: float, save: bool = False):
+    """final_layer_norm and the projection of the pooled (first-EOS) rows [B, D] -> (out [B, P], pooled, mean, rstd); the
+    statistics only with `save`.  M = B: always ops.gemm, whatever ran the layers."""
+    pooled, mp, rp = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=save)
+    return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT), pooled, mp, rp
+
+
+def _text_token_tail(x, p: TextParams, input_ids: torch.Tensor, cfg):
+    """final_layer_norm on ALL rows, the projection and the first-EOS gather -> (sentence [B,P], tokens [B*T,P], eos [B])."""
+    B, T = input_ids.shape
+    ln, _, _ = ops.layernorm_fwd(x, p.final_w, p.final_b, cfg.layer_norm_eps, save_stats=False)
+    tokens = ops.gemm(ln, p.proj_w, ops.LAYOUT_NT)
+    eos = ops.first_eos(input_ids, cfg.eos_token_id)
+    return ops.gather_rows(tokens, eos, B, T, tokens.shape[1]), tokens, eos
 
 
 # --------------------------------------------------------------------------------------------- frozen fp32 text tower, split fp16
@@ -1479,6 +1520,14 @@ def _split16_plan(layers_p: List[LayerParams], cache: dict, what: str = "split-f
     return layers
 
 
+def _text_frozen_split16_plan(p: TextParams, cfg, cache: dict):
+    """The frozen text tower's host plan (_split16_plan's layers), or None — the plain fp32 path — when DCLIP_TEXT_SPLIT16 is
+    off, the tower has no layer, a width is no multiple of 8 or the plan's own guard trips."""
+    if not (_SPLIT16 and len(p.layers) > 0 and cfg.hidden_size % 8 == 0 and cfg.intermediate_size % 8 == 0):
+        return None
+    return _split16_plan(p.layers, cache)
+
+
 def _split16_gemm(a3, ent, short: str, akey: str, **kw):
     """epilogue(A W^T) from the split operands; alpha undoes the operand scales."""
     alpha = 2.0 ** -(ent["e"][akey] + ent["f"][short])
@@ -1533,7 +1582,7 @@ def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: 
     between calls.  Falls back to text_fwd_frozen when the switch is off or the guard trips."""
     t = cfg
     D = t.hidden_size
-    plan = _split16_plan(p.layers, cache) if _SPLIT16 and len(p.layers) > 0 and D % 8 == 0 and t.intermediate_size % 8 == 0 else None
+    plan = _text_frozen_split16_plan(p, t, cache)
     if plan is None:
         return text_fwd_frozen(p, input_ids, cfg)
     B, T = input_ids.shape
@@ -1548,12 +1597,8 @@ def text_fwd_frozen_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: 
     ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"], pieces=pc["ln1"])
     qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
     attn = ops.attention_row_fwd(qkv, eos, B, T, H)
-    x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows(x, eos, B, T, D))
-    ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
-    g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
-    rows = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
-    pooled, _, _ = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=False)
-    return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+    rows = _pruned_tail_f32(attn, ops.gather_rows(x, eos, B, T, D), lp, eps)
+    return _text_head(rows, p, eps)[0]
 
 
 # --------------------------------------------------------------------------------------------- frozen fp32 vision tower, split fp16
@@ -1579,10 +1624,7 @@ def _frozen_split16_last_cls(x, lp: LayerParams, ent, eps: float, ctx_rows, x_ro
     D = x.shape[1]
     ln1 = ops.layernorm_fwd_f16x3(x, lp.ln1_w, lp.ln1_b, eps, 2.0 ** ent["e"]["ln1"], pieces=split16_pieces([(x.shape[0], 3 * D, D)]))
     qkv = _split16_gemm(ln1, ent, "qkv", "ln1", bias=lp.qkv_b)
-    x1 = ops.gemm(ctx_rows(qkv), lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=x_rows(x))
-    ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
-    g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
-    return ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
+    return _pruned_tail_f32(ctx_rows(qkv), x_rows(x), lp, eps)
 
 
 def vision_fwd_frozen_split16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict, grid=None,
@@ -1816,23 +1858,35 @@ def _vision_split16_plan(layers: List[LayerParams], cfg, cache: dict, key: str =
     return ent["layers"]
 
 
-def _text_train_split16(p: TextParams, cfg, save: bool, split16_cache: Optional[dict], split16_out: Optional[list]):
-    """(plan, keep_split) of a trainable text forward: the tower's own device plan — _vision_split16_plan under
-    the text key, so neither tower's refresh touches the other's pending backward — when the forward saves for a backward and
-    the caller handed the model's cache; (None, False) = the plain fp32 schedule, the parent's launch for launch.  The forward's
-    Split16Bwd goes to `split16_out` as in vision_fwd."""
-    if not (save and split16_cache is not None):
+def _train_split16(layers: List[LayerParams], cfg, save: bool, split16_cache: Optional[dict], split16_out: Optional[list],
+                   on: bool = True, key: str = "__vsplit16__", what: str = "split-fp16 vision tower",
+                   off: str = "DCLIP_VISION_SPLIT16=0", log_declined: bool = False):
+    """(plan, keep_split) of a trainable tower's forward: the tower's device plan (_vision_split16_plan under `key`, with the
+    log label `what` and the way back `off`) when the switch `on` is set, the forward saves for a backward and the caller
+    handed the model's cache; (None, False) = the plain fp32 schedule.  What the backward needs to run on the same plan (a
+    Split16Bwd, §9e) goes to `split16_out` when DCLIP_VISION_SPLIT16_BWD is on; keep_split: that backward's weight gradients
+    take the forward's split operands (§9f).  The defaults are the vision tower's; the trainable text tower
+    keeps its own plan under its own key, so neither tower's refresh touches the other's pending backward, and logs a plan that
+    declined (`log_declined`)."""
+    if not (on and save and split16_cache is not None):
         return None, False
-    plan = _vision_split16_plan(p.layers, cfg, split16_cache, _TSPLIT16_KEY, _TSPLIT16_WHAT, "text_train_split16 = False")
+    plan = _vision_split16_plan(layers, cfg, split16_cache, key, what, off)
     if plan is None:
-        _split16_log_once(_TSPLIT16_WHAT + ": the plan declined (widths not multiples of 8, or first use inside a graph capture); "
-                          "the tower takes the plain fp32 path")
+        if log_declined:
+            _split16_log_once(what + ": the plan declined (widths not multiples of 8, or first use inside a graph capture); "
+                              "the tower takes the plain fp32 path")
         return None, False
     keep = False
     if split16_out is not None and _VSPLIT16_BWD and plan[0].wt is not None:
-        split16_out.append(Split16Bwd(plan, split16_cache[_TSPLIT16_KEY], p.layers))
+        split16_out.append(Split16Bwd(plan, split16_cache[key], layers))
         keep = _VSPLIT16_WGRAD
     return plan, keep
+
+
+def _text_train_split16(p: TextParams, cfg, save: bool, split16_cache: Optional[dict], split16_out: Optional[list]):
+    """_train_split16 for the trainable text tower: its own key, label and advice, and a logged decline."""
+    return _train_split16(p.layers, cfg, save, split16_cache, split16_out, True, _TSPLIT16_KEY, _TSPLIT16_WHAT,
+                          "text_train_split16 = False", log_declined=True)
 
 
 def text_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hidden_out: Optional[list] = None,
@@ -1847,10 +1901,21 @@ def text_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hidden_out
     x, saved_layers = text_encoder_fwd(p, input_ids, cfg, save, hidden_out, split16_cache, split16_out)
     eos = ops.first_eos(input_ids, t.eos_token_id)
     rows = ops.gather_rows(x, eos, B, T, D)
-    pooled, mp, rp = ops.layernorm_fwd(rows, p.final_w, p.final_b, t.layer_norm_eps, save_stats=save)
-    out = ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+    out, pooled, mp, rp = _text_head(rows, p, t.layer_norm_eps, save)
     saved = (input_ids, saved_layers, eos, rows, mp, rp, pooled) if save else None
     return out, saved
+
+
+def _text_tail_bwd(p: TextParams, d_out, rows, mp, rp, pooled, needd: Dict[str, bool], grads):
+    """proj_w's gradient, dpooled and final_layer_norm's backward -> drows [B, D], the gradient of the pooled rows."""
+    if needd["proj_w"]:
+        grads["proj_w"] = ops.gemm(d_out, pooled, ops.LAYOUT_TN)
+    dpooled = ops.gemm(d_out, p.proj_w, ops.LAYOUT_NN)
+    want = needd["final_w"] or needd["final_b"]
+    drows, dg, db = ops.layernorm_bwd(dpooled, rows, p.final_w, mp, rp, need_param_grads=want)
+    if want:
+        grads["final_w"], grads["final_b"] = dg, db
+    return drows
 
 
 def text_bwd(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool], split16=None):
@@ -1862,36 +1927,12 @@ def text_bwd(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool], s
     names = p.names()
     needd = dict(zip(names, need))
     grads: Dict[str, Optional[torch.Tensor]] = {n: None for n in names}
-    if needd["proj_w"]:
-        grads["proj_w"] = ops.gemm(d_out, pooled, ops.LAYOUT_TN)
-    dpooled = ops.gemm(d_out, p.proj_w, ops.LAYOUT_NN)
-    want = needd["final_w"] or needd["final_b"]
-    drows, dg, db = ops.layernorm_bwd(dpooled, rows, p.final_w, mp, rp, need_param_grads=want)
-    if want:
-        grads["final_w"], grads["final_b"] = dg, db
-    lowest = None
-    for n in names:
-        if needd[n] and n not in TextParams.TAIL:
-            li = -1 if n in TextParams.HEAD else int(n.split(".")[1])
-            lowest = li if lowest is None else min(lowest, li)
+    drows = _text_tail_bwd(p, d_out, rows, mp, rp, pooled, needd, grads)
+    lowest = _lowest_needed(names, needd, TextParams.HEAD, TextParams.TAIL)
     if lowest is None:
         return [grads[n] for n in names]
     dx = ops.scatter_rows(drows, eos, B, T, D)
-    # sp, the dY-statistics regime and the per-layer dx_stats decision as vision_bwd derives them.  The top
-    # layer's incoming dx is zero in all but one row per caption: a row-scaled split of an all-zero row gives zero pieces and
-    # alpha = 1 (split16_row_exp(0) = 0)
-    plan = split16.layers if split16 is not None and _VSPLIT16_BWD and split16.fresh() else None
-    dystats = plan is not None and _dystats_regime(B * T, D, p.layers[0].fc1_w.shape[0])
-    for i in range(len(p.layers) - 1, max(lowest, 0) - 1, -1):
-        lneed = {f: needd[f"layers.{i}.{f}"] for f in LayerParams.FIELDS}
-        sp = plan[i] if plan is not None else None      # None: the plain fp32 GEMMs (eps: what a forward on the plan left out, §9j)
-        below = dystats and i - 1 >= max(lowest, 0) and len(saved_layers[i - 1]) > 13
-        dxs = below and _split_wgrad_taken(bool(needd[f"layers.{i - 1}.fc2_w"]), plan[i - 1], saved_layers[i - 1][13].get("g"),
-                                           D, p.layers[i - 1].fc1_w.shape[0], B * T)
-        dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], B, T, H, True, lneed, None, sp, dxs, dystats, eps=t.layer_norm_eps)
-        saved_layers[i] = None
-        for f, tn in gr.items():
-            grads[f"layers.{i}.{f}"] = tn
+    dx = _layers_bwd(dx, p.layers, saved_layers, needd, grads, lowest, B * T, B, T, H, True, t.layer_norm_eps, split16)
     if lowest < 0:
         if needd["pos"]:
             dpos = torch.zeros_like(p.pos)
@@ -1933,8 +1974,7 @@ def text_fwd_frozen_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dic
     ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, t.layer_norm_eps)
     g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
     rows = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
-    pooled, _, _ = ops.layernorm_fwd(rows, p.final_w, p.final_b, t.layer_norm_eps, save_stats=False)
-    return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+    return _text_head(rows, p, t.layer_norm_eps)[0]
 
 
 def text_token_level_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16):
@@ -1956,15 +1996,8 @@ def text_token_level(p: TextParams, input_ids: torch.Tensor, cfg):
       sentence [B,P]   = text_projection(final_LN(h)[first EOS])                 (text_tokenizer.py:193,:216)
       tokens   [B*T,P] = text_projection(final_LN(h)) for every position          (text_tokenizer.py:202-207)
       eos [B] int32    = first-EOS index; word tokens of caption b are rows 1 .. eos[b]-1."""
-    t = cfg
-    B, T = input_ids.shape
-    D = t.hidden_size
     x, _ = text_encoder_fwd(p, input_ids, cfg, save=False)
-    ln, _, _ = ops.layernorm_fwd(x, p.final_w, p.final_b, t.layer_norm_eps, save_stats=False)
-    tokens = ops.gemm(ln, p.proj_w, ops.LAYOUT_NT)
-    eos = ops.first_eos(input_ids, t.eos_token_id)
-    sentence = ops.gather_rows(tokens, eos, B, T, tokens.shape[1])
-    return sentence, tokens, eos
+    return _text_token_tail(x, p, input_ids, cfg)
 
 
 def text_token_level_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict):
@@ -1974,7 +2007,7 @@ def text_token_level_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache:
     projection stay fp32.  The plain fp32 pass, bit for bit, when the guard trips."""
     t = cfg
     D = t.hidden_size
-    plan = _split16_plan(p.layers, cache) if _SPLIT16 and len(p.layers) > 0 and D % 8 == 0 and t.intermediate_size % 8 == 0 else None
+    plan = _text_frozen_split16_plan(p, t, cache)
     if plan is None:
         return text_token_level(p, input_ids, cfg)
     B, T = input_ids.shape
@@ -1983,10 +2016,7 @@ def text_token_level_split16(p: TextParams, input_ids: torch.Tensor, cfg, cache:
     ctx3 = _dense_ctx3(B, T, t.num_attention_heads, True, True)
     for lp, ent in zip(p.layers, plan):
         x = _frozen_split16_layer(x, lp, ent, pc, t.layer_norm_eps, ctx3)
-    ln, _, _ = ops.layernorm_fwd(x, p.final_w, p.final_b, t.layer_norm_eps, save_stats=False)
-    tokens = ops.gemm(ln, p.proj_w, ops.LAYOUT_NT)
-    eos = ops.first_eos(input_ids, t.eos_token_id)
-    return ops.gather_rows(tokens, eos, B, T, tokens.shape[1]), tokens, eos
+    return _text_token_tail(x, p, input_ids, t)
 
 
 # --------------------------------------------------------------------------------------------- packed frozen text forward
@@ -2037,10 +2067,7 @@ def _packed_text_mode(p: TextParams, cfg, precision: str, cache: Optional[dict],
     """(mode, plan): "fp32" takes the split-fp16 plan exactly when the padded frozen forward would (text_fwd_frozen_split16);
     "fp32-split16" (the token-level pass) whenever the guard lets it, whatever `split16` says."""
     if precision in ("fp32", "fp32-split16"):
-        plan = None
-        if (split16 or precision == "fp32-split16") and cache is not None and _SPLIT16 and len(p.layers) > 0 and cfg.hidden_size % 8 == 0 \
-                and cfg.intermediate_size % 8 == 0:
-            plan = _split16_plan(p.layers, cache)
+        plan = _text_frozen_split16_plan(p, cfg, cache) if (split16 or precision == "fp32-split16") and cache is not None else None
         return ("split16" if plan is not None else "fp32"), plan
     if precision not in ("bf16", "fp16") or cache is None:
         raise ValueError(f"{what}: precision {precision!r} (16-bit precisions need the model's weight cache)")
@@ -2073,10 +2100,7 @@ def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict,
             ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, eps, save_stats=False)
             qkv = ops.gemm(ln1, lp.qkv_w, ops.LAYOUT_NT, bias=lp.qkv_b)
         attn = ops.attention_varlen_causal_fwd(qkv, cu, max_S, H, last_only=True)
-        x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows_at(x, last_rows))
-        ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
-        g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
-        rows = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
+        rows = _pruned_tail_f32(attn, ops.gather_rows_at(x, last_rows), lp, eps)
     else:
         k, pre = _OPS16[torch.bfloat16 if mode == "bf16" else torch.float16], f"t{li}."
         ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, eps)
@@ -2090,8 +2114,7 @@ def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict,
         ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
         g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
         rows = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
-    pooled, _, _ = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=False)
-    return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+    return _text_head(rows, p, eps)[0]
 
 
 def text_token_level_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, precision: str = "fp32",
@@ -2136,8 +2159,7 @@ def text_fwd_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, s
                           varlen=(cu, max_S))
         saved_layers.append(sv)
     rows = ops.gather_rows_at(x, last_rows)
-    pooled, mp, rp = ops.layernorm_fwd(rows, p.final_w, p.final_b, eps, save_stats=save)
-    out = ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
+    out, pooled, mp, rp = _text_head(rows, p, eps, save)
     saved = (input_ids, saved_layers, cu, max_S, tables["Tp"], rows, mp, rp, pooled) if save else None
     return out, saved
 
@@ -2148,41 +2170,16 @@ def text_bwd_packed(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[b
     t = cfg
     input_ids, saved_layers, cu, max_S, Tp, rows, mp, rp, pooled = saved
     N = input_ids.shape[0]
-    D, H = t.hidden_size, t.num_attention_heads
     names = p.names()
     needd = dict(zip(names, need))
     grads: Dict[str, Optional[torch.Tensor]] = {n: None for n in names}
-    if needd["proj_w"]:
-        grads["proj_w"] = ops.gemm(d_out, pooled, ops.LAYOUT_TN)
-    dpooled = ops.gemm(d_out, p.proj_w, ops.LAYOUT_NN)
-    want = needd["final_w"] or needd["final_b"]
-    drows, dg, db = ops.layernorm_bwd(dpooled, rows, p.final_w, mp, rp, need_param_grads=want)
-    if want:
-        grads["final_w"], grads["final_b"] = dg, db
-    lowest = None
-    for n in names:
-        if needd[n] and n not in TextParams.TAIL:
-            li = -1 if n in TextParams.HEAD else int(n.split(".")[1])
-            lowest = li if lowest is None else min(lowest, li)
+    drows = _text_tail_bwd(p, d_out, rows, mp, rp, pooled, needd, grads)
+    lowest = _lowest_needed(names, needd, TextParams.HEAD, TextParams.TAIL)
     if lowest is None:
         return [grads[n] for n in names]
     dx = ops.scatter_last_rows(drows, cu, Tp)
-    # sp, the dY-statistics regime and the per-layer dx_stats decision as vision_bwd derives them.  The top
-    # layer's incoming dx is zero in all but one row per caption: a row-scaled split of an all-zero row gives zero pieces and
-    # alpha = 1 (split16_row_exp(0) = 0)
-    plan = split16.layers if split16 is not None and _VSPLIT16_BWD and split16.fresh() else None
-    dystats = plan is not None and _dystats_regime(Tp, D, p.layers[0].fc1_w.shape[0])
-    for i in range(len(p.layers) - 1, max(lowest, 0) - 1, -1):
-        lneed = {f: needd[f"layers.{i}.{f}"] for f in LayerParams.FIELDS}
-        sp = plan[i] if plan is not None else None      # None: the plain fp32 GEMMs (eps: what a forward on the plan left out, §9j)
-        below = dystats and i - 1 >= max(lowest, 0) and len(saved_layers[i - 1]) > 13
-        dxs = below and _split_wgrad_taken(bool(needd[f"layers.{i - 1}.fc2_w"]), plan[i - 1], saved_layers[i - 1][13].get("g"),
-                                           D, p.layers[i - 1].fc1_w.shape[0], Tp)
-        dx, gr = layer_bwd(dx, p.layers[i], saved_layers[i], N, max_S, H, True, lneed, None, sp, dxs, dystats, eps=t.layer_norm_eps,
-                           varlen=(cu, max_S))
-        saved_layers[i] = None
-        for f, tn in gr.items():
-            grads[f"layers.{i}.{f}"] = tn
+    dx = _layers_bwd(dx, p.layers, saved_layers, needd, grads, lowest, Tp, N, max_S, t.num_attention_heads, True, t.layer_norm_eps,
+                     split16, varlen=(cu, max_S))
     if lowest < 0:
         dpos = torch.zeros_like(p.pos) if needd["pos"] else None
         dtok = torch.zeros_like(p.tok) if needd["tok"] else None

@@ -325,23 +325,28 @@ def test_declined_wgrad_plan_takes_the_fp32_wgrads(prob4, monkeypatch):
     grad_bars(prob4, grads, grads_off, "text tiny B 4 (declined)")
 
 
-def test_partially_frozen_tower(prob, monkeypatch):
+@pytest.mark.parametrize("which", ["padded", "packed"])
+def test_partially_frozen_tower(which, prob, packed, monkeypatch):
     """only the top layer and the projection train: frozen tensors get no gradient, the bars hold for the rest, and the backward
-    stops above layer 0"""
+    stops above layer 0 — on the padded tower (B = 64) and on the packed one (PACKED_LENS, 256 rows), whose layer loop is the
+    same one"""
     monkeypatch.setenv("DCLIP_BF16_BIG_MIN", "1")
-    live = [n for n in prob.names if n.startswith(f"layers.{L - 1}.") or n == "proj_w"]
+    pr = prob if which == "padded" else packed
+    kw = {} if which == "padded" else {"packed_lens": packed_text_tables(pr.ids, pr.t.eos_token_id)["lens"]}
+    tag = ("text tiny B 64" if which == "padded" else "packed text tiny, 256 rows") + ", top layer + projection"
+    live = [n for n in pr.names if n.startswith(f"layers.{L - 1}.") or n == "proj_w"]
     out = {}
     for on in (True, False):
-        m = prob.model(on)
+        m = pr.model(on)
         p = m.text_params()
         for n, t in zip(p.names(), p.tensors()):
             t.requires_grad_(n in live)
-        out[on] = run(prob, m)
+        out[on] = run(pr, m, **kw)
     (_, g_on, spy), (_, g_off, _) = out[True], out[False]
-    assert all((g_on[n] is None) == (n not in live) for n in prob.names), [n for n in prob.names if g_on[n] is not None]
+    assert all((g_on[n] is None) == (n not in live) for n in pr.names), [n for n in pr.names if g_on[n] is not None]
     assert spy.n(FWD) == 4 * L and spy.n(DGRAD) == 4 and spy.n(WGRAD) == 4, spy.calls     # the backward stops below the top layer
-    grad_bars(prob, g_on, g_off, "text tiny B 64, top layer + projection", live)
-    row_bars(prob, g_on, g_off, "text tiny B 64, top layer + projection", live)
+    grad_bars(pr, g_on, g_off, tag, live)
+    row_bars(pr, g_on, g_off, tag, live)
 
 
 def test_parameter_written_between_forward_and_backward(prob, monkeypatch):

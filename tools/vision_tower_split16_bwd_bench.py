@@ -89,7 +89,7 @@ def main():
               "dln1 (qkv)": ("qkv", 3 * D, lp.qkv_w, None)}
     for label, (name, width, w, aux) in shapes.items():
         dy, (dy3, ra) = dys[width], split[width]
-        fns = {"fp32": (lambda dy=dy, w=w, aux=aux: engine._dgrad(dy, w, None, name, aux))}
+        fns = {"fp32": (lambda dy=dy, w=w, aux=aux: engine._dgrad(dy, w, None, name, aux)[0])}
         for kn, env in kernels.items():
             def f(env=env, dy3=dy3, ra=ra, name=name, aux=aux):
                 with Env(**env):
