@@ -554,3 +554,141 @@ class ReadyLog:
                 assert got[n] is not None and g[n].data_ptr() == got[n].data_ptr(), f"{what}: {n} was reported in another tensor than the one returned"
                 assert torch.equal(*_flat_pair(c[n], got[n])), \
                     f"{what}: {n} was reported before its last write (the value seen in the callback is not the final one)"
+
+
+# ------------------------------------------------------------------------------------------------ the single-pass census
+# What the split-fp16 backward (engine._layers_bwd / layer_bwd / last_layer_bwd_cls / linear_param_grads) calls for the four
+# linears of every layer it runs, written down from the documented rules (§9f, §9g, §30) and NOT from running the engine:
+#
+#   * a linear whose weight is needed, at full row count, whose shape the weight-gradient plan takes -> the split pass;
+#     it is the SINGLE pass (ops.split_f16x3_rows_cols_stats) iff the statistics regime is on and the kernel that produces its dY
+#     has a statistics form on this route, the THREE-launch pass (ops.split_f16x3_rows_colstats) otherwise.  Producers:
+#       fc2   the ln1 backward of the layer ABOVE (layer_bwd's or last_layer_bwd_cls's) — none for the top layer, whose dY comes
+#             from scatter_rows / scatter_last_rows;
+#       fc1   fc2's data-gradient GEMM;          out   the ln2 backward;
+#       qkv   the dense attention backward in its "stats" (S <= 64) or "rows_stats" (causal, 65 .. 80) form — none for the pruned
+#             vision top layer (attention_cls_bwd), none on the packed tower, none in the "segments" form (the twin switched off);
+#     its bias comes out of that pass (db), except in the "segments" form with the regime on: ops.colsum_segments;
+#   * a weight needed where the plan does not take it (rows not a multiple of 64, a stale plan) -> the fp32 GEMM (LAYOUT_TN);
+#     the bias, if needed too, is its A_ROWSUM epilogue: no column sum.  The M = B linears of the pruned top layer are such
+#     GEMMs too, but not at full row count: not counted;
+#   * a bias needed without its weight -> one ops.colsum, whatever the plan says.
+
+PASS_KEYS = ("single", "three", "plain_w", "colsum", "segments")
+PRODUCER_KINDS = ("gemm", "ln", "attn")
+
+
+def split_census(tower: str, mask: Iterable[str], L: int, *, pruned: bool, packed: bool, dystats: bool, attn_form: Optional[str],
+                 wgrad_plan_ok: bool) -> List[Dict[str, object]]:
+    """One record per (layer run, linear), top down, fc2 / fc1 / out / qkv: {"layer", "linear", "pass": "single" / "three" / None,
+    "producer": "gemm" / "ln" / "attn" / None (of a single pass), "produced_in": the layer whose backward launches that producer,
+    "plain_w", "colsum", "segments": bool, "db": where a needed bias comes from ("pass" / "segments" / "rowsum" / "colsum" / None)}.
+    `pruned`: the vision tower's top layer is last_layer_bwd_cls; `packed`: the ragged text tower; `dystats`: the switch is on and
+    _dystats_regime holds for the tower; `attn_form`: _attention_bwd_stats_form's first answer for the dense tower ("stats",
+    "rows_stats", "segments", None); `wgrad_plan_ok`: the plan is fresh and takes the four weight-gradient shapes."""
+    mask = frozenset(mask)
+    assert attn_form in ("stats", "rows_stats", "segments", None), attn_form
+    assert not (packed and tower != "text") and not (pruned and tower != "vision")
+    out = []
+    for i in layers_run(tower, mask, L):
+        top = i == L - 1
+        cls = pruned and top
+        for l in LINEARS:
+            w, b = f"layers.{i}.{l}_w" in mask, f"layers.{i}.{l}_b" in mask
+            full_size = l == "qkv" or not cls
+            d = {"layer": i, "linear": l, "pass": None, "producer": None, "produced_in": None, "plain_w": False, "colsum": False,
+                 "segments": False, "db": None}
+            if w and full_size and wgrad_plan_ok:
+                if l == "fc2":
+                    form = None if top else "ln"
+                elif l == "fc1":
+                    form = "gemm"
+                elif l == "out":
+                    form = "ln"
+                else:
+                    form = "attn" if not cls and not packed and attn_form in ("stats", "rows_stats") else None
+                if not dystats:
+                    form = None
+                d["pass"], d["producer"] = ("single" if form else "three"), form
+                if form:
+                    d["produced_in"] = i + 1 if l == "fc2" else i
+                d["segments"] = bool(l == "qkv" and b and dystats and not cls and not packed and attn_form == "segments")
+                d["db"] = ("segments" if d["segments"] else "pass") if b else None
+            elif w:
+                d["plain_w"] = full_size
+                d["db"] = "rowsum" if b else None
+            elif b:
+                d["colsum"], d["db"] = True, "colsum"
+            out.append(d)
+    return out
+
+
+def expected_passes(tower: str, mask: Iterable[str], L: int, *, pruned: bool, packed: bool, dystats: bool, attn_form: Optional[str],
+                    wgrad_plan_ok: bool) -> Dict[str, int]:
+    """Calls inside linear_param_grads during one backward: "single" ops.split_f16x3_rows_cols_stats, "three"
+    ops.split_f16x3_rows_colstats, "plain_w" fp32 weight-gradient ops.gemm(.., LAYOUT_TN) at full row count, "colsum" ops.colsum
+    for a bias, "segments" ops.colsum_segments (split_census, summed)."""
+    c = split_census(tower, mask, L, pruned=pruned, packed=packed, dystats=dystats, attn_form=attn_form, wgrad_plan_ok=wgrad_plan_ok)
+    return {"single": sum(d["pass"] == "single" for d in c), "three": sum(d["pass"] == "three" for d in c),
+            "plain_w": sum(d["plain_w"] for d in c), "colsum": sum(d["colsum"] for d in c), "segments": sum(d["segments"] for d in c)}
+
+
+def expected_producers(tower: str, mask: Iterable[str], L: int, **route) -> Dict[int, Dict[str, int]]:
+    """{layer whose backward launches them: {"gemm", "ln", "attn": statistics-producing launches}} — one per single pass and none
+    else: statistics are never produced without a consumer.  Layers without any are left out."""
+    out: Dict[int, Dict[str, int]] = {}
+    for d in split_census(tower, mask, L, **route):
+        if d["producer"]:
+            k = out.setdefault(d["produced_in"], {k: 0 for k in PRODUCER_KINDS})
+            k[d["producer"]] += 1
+    return out
+
+
+def check_census(calls: Dict[str, int], producers: Dict[int, Dict[str, int]], tower: str, mask: Iterable[str], L: int, what: str,
+                 **route):
+    """The counted calls and the statistics-producing launches per layer against the census."""
+    want = expected_passes(tower, mask, L, **route)
+    assert {k: calls.get(k, 0) for k in PASS_KEYS} == want, f"{what}: calls {dict(calls)}, the census says {want}"
+    wantp = expected_producers(tower, mask, L, **route)
+    gotp = {i: {k: v.get(k, 0) for k in PRODUCER_KINDS} for i, v in producers.items() if any(v.values())}
+    assert gotp == wantp, f"{what}: statistics were produced in {gotp} (layer: kind: launches), the single passes need {wantp}"
+
+
+SPLIT_SITUATIONS = ("split.w_only", "split.both", "split.b_only_live_plan", "producer.consumer_below", "producer.consumer_not_run",
+                    "producer.in_layer_without_split_pass", "regime_on.nothing_asked", "segments.with_b", "segments.without_b")
+
+
+def split_situations(tower: str, mask: Iterable[str], L: int, **route) -> FrozenSet[str]:
+    """The branch situations of the split-fp16 backward that a mask reaches on a route (split_census's keywords): weight without
+    bias on the split pass (the kernels are handed db=None) and with it; a bias without its weight while the layer's plan is live;
+    a producer whose consumer is the fc2 of the layer below; a layer that is the lowest run although a layer lies below it (its
+    ln1 backward must NOT be asked: i - 1 < bottom); a layer that produces for the layer below and takes no split pass itself; a
+    backward in the regime that asks no producer at all; the "segments" form with and without the bias."""
+    mask = frozenset(mask)
+    c = split_census(tower, mask, L, **route)
+    run = layers_run(tower, mask, L)
+    s = set()
+    for d in c:
+        b = f"layers.{d['layer']}.{d['linear']}_b" in mask
+        if d["pass"]:
+            s.add("split.both" if b else "split.w_only")
+        if d["colsum"] and route["wgrad_plan_ok"]:
+            s.add("split.b_only_live_plan")
+        if d["linear"] == "fc2" and d["producer"]:
+            s.add("producer.consumer_below")
+            if not any(e["pass"] for e in c if e["layer"] == d["produced_in"]):
+                s.add("producer.in_layer_without_split_pass")
+        if d["linear"] == "qkv" and route["attn_form"] == "segments" and d["pass"] and route["dystats"]:
+            s.add("segments.with_b" if b else "segments.without_b")
+    if run and run[-1] > 0 and route["dystats"] and route["wgrad_plan_ok"]:
+        s.add("producer.consumer_not_run")
+    if run and route["dystats"] and route["wgrad_plan_ok"] and not any(d["producer"] for d in c):
+        s.add("regime_on.nothing_asked")
+    assert s <= set(SPLIT_SITUATIONS)
+    return frozenset(s)
+
+
+def split_masks(tower: str, L: int) -> Dict[str, FrozenSet[str]]:
+    """Masks the split-fp16 routes add to masks(): (m) the top layer's fc2_b and the bottom layer's fc2_w alone — the top layer takes
+    no split pass and still has to produce the partials of the fc2 below, which gets no bias (db=None)."""
+    return {"m_top_fc2_b_bottom_fc2_w": frozenset([f"layers.{L - 1}.fc2_b", "layers.0.fc2_w"])}

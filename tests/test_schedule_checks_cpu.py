@@ -435,3 +435,263 @@ def test_embed_atomic_bound_is_zero_where_nothing_is_summed():
     other["tok"][1, 2] = 1e-30                                   # a row no token names
     with pytest.raises(AssertionError, match="column-sum bound"):
         sc.check_mask_consistency(other, full, {"tok"}, {"tok": b}, "planted")
+
+
+# ------------------------------------------------------------------------------------------------ the single-pass census
+
+V_PRUNED = dict(pruned=True, packed=False, dystats=True, attn_form="stats", wgrad_plan_ok=True)          # vision, tiny B = 64
+V_UNPRUNED = dict(V_PRUNED, pruned=False)
+V_OFF = dict(V_PRUNED, dystats=False)
+T_TWIN = dict(pruned=False, packed=False, dystats=True, attn_form="rows_stats", wgrad_plan_ok=True)     # text, T = 77, B = 64
+T_SEG = dict(T_TWIN, attn_form="segments")
+T_PACKED = dict(T_TWIN, packed=True, attn_form=None)
+T_DECLINED = dict(T_PACKED, wgrad_plan_ok=False)                                                        # 249 rows
+T_STALE = dict(T_TWIN, dystats=False, attn_form=None, wgrad_plan_ok=False)
+CENSUS_ROUTES = {"v_pruned": ("vision", V_PRUNED), "v_unpruned": ("vision", V_UNPRUNED), "v_off": ("vision", V_OFF), "t_twin": ("text", T_TWIN),
+                 "t_seg": ("text", T_SEG), "t_packed": ("text", T_PACKED), "t_declined": ("text", T_DECLINED), "t_stale": ("text", T_STALE)}
+
+
+def _passes(single=0, three=0, plain_w=0, colsum=0, segments=0):
+    return {"single": single, "three": three, "plain_w": plain_w, "colsum": colsum, "segments": segments}
+
+
+def _split_masks(tower, L):
+    m = dict(sc.masks(tower, L))
+    m.update(sc.split_masks(tower, L))
+    return m
+
+
+def test_expected_passes_on_hand_worked_masks():
+    """Vision, pruned top layer, L = 2 (L = 3 for (k)), the regime on, the plan live.  Layer 1 is last_layer_bwd_cls: only its qkv
+    is a full-size linear, and attention_cls_bwd has no statistics form; its fc2 / fc1 / out run at M = B on ops.gemm and are not
+    counted, but a bias of theirs without its weight still costs a colsum."""
+    m = _split_masks("vision", 2)
+    ep = lambda mask, L=2, **kw: sc.expected_passes("vision", mask, L, **dict(V_PRUNED, **kw))        # noqa: E731
+    # (a) layer 1: qkv three.  layer 0: fc2 (partials from layer 1's ln1 backward), fc1 (fc2's dgrad), out (ln2 backward), qkv
+    #     (attention_bwd.lean.stats): four single passes; every bias comes out of its pass or its GEMM's A_ROWSUM
+    assert ep(m["a_everything"]) == _passes(single=4, three=1)
+    # (e) layers.0.fc2_b alone: layers 1 and 0 run, no weight anywhere: one colsum, no pass, no producer
+    assert ep(m["e_bottom_fc2_b"]) == _passes(colsum=1)
+    assert sc.expected_producers("vision", m["e_bottom_fc2_b"], 2, **V_PRUNED) == {}
+    # (f) the weights without their biases: the passes of (a), each handed db=None
+    assert ep(m["f_weights"]) == _passes(single=4, three=1)
+    # (g) every bias, no weight: four colsums per layer (the top layer's three M = B biases included)
+    assert ep(m["g_biases_ln"]) == _passes(colsum=8)
+    # top layer only: layer 0 is not run; layer 1's qkv three, its ln1 backward is NOT asked (i - 1 < bottom)
+    assert ep(m["i_top_layer"]) == _passes(three=1)
+    assert sc.expected_producers("vision", m["i_top_layer"], 2, **V_PRUNED) == {}
+    # (k) L = 3, the middle layer's fc2_b and out_b: layers 2 and 1 run, two colsums
+    assert ep(sc.masks("vision", 3)["k_middle_fc2_b_out_b"], L=3) == _passes(colsum=2)
+    # (m) layers.1.fc2_b and layers.0.fc2_w only: layer 1 one colsum (its fc2 at M = B) and its ln1 backward produces for layer 0's
+    #     fc2, which takes the single pass without a bias
+    assert ep(m["m_top_fc2_b_bottom_fc2_w"]) == _passes(single=1, colsum=1)
+    assert sc.expected_producers("vision", m["m_top_fc2_b_bottom_fc2_w"], 2, **V_PRUNED) == {1: {"gemm": 0, "ln": 1, "attn": 0}}
+    # (a) again: who produces where — layer 1's ln1 backward for layer 0's fc2; in layer 0 the dgrad, the ln2 backward, the attention
+    assert sc.expected_producers("vision", m["a_everything"], 2, **V_PRUNED) == {1: {"gemm": 0, "ln": 1, "attn": 0}, 0: {"gemm": 1, "ln": 1, "attn": 1}}
+    # the switch off: the same five passes, all three-launch; L = 3: 4 (L - 1) single and 1 three
+    assert ep(m["a_everything"], dystats=False) == _passes(three=5)
+    assert sc.expected_passes("vision", sc.names("vision", 3), 3, **V_PRUNED) == _passes(single=8, three=1)
+    # unpruned: the top layer is a layer_bwd; its fc2's dY comes from scatter_rows (three), its qkv gets partials too
+    assert ep(m["a_everything"], pruned=False) == _passes(single=7, three=1)
+    assert ep(m["i_top_layer"], pruned=False) == _passes(single=3, three=1)
+
+
+def test_expected_passes_of_the_text_routes():
+    m = _split_masks("text", 2)
+    ep = lambda mask, kw: sc.expected_passes("text", mask, 2, **kw)                                  # noqa: E731
+    # the twin: layer 1's fc2 three (scatter_rows), everything else single — 4 L passes, dqkv's L among the single ones
+    assert ep(m["a_everything"], T_TWIN) == ep(m["f_weights"], T_TWIN) == _passes(single=7, three=1)
+    assert ep(m["g_biases_ln"], T_TWIN) == _passes(colsum=8)
+    assert ep(m["i_top_layer"], T_TWIN) == _passes(single=3, three=1)
+    # the twin switched off: both qkv three, and ops.colsum_segments where qkv_b is needed beside qkv_w
+    assert ep(m["a_everything"], T_SEG) == _passes(single=5, three=3, segments=2)
+    assert ep(m["f_weights"], T_SEG) == _passes(single=5, three=3)
+    assert ep(m["g_biases_ln"], T_SEG) == _passes(colsum=8)
+    # packed: no statistics form for dqkv, no segments either
+    assert ep(m["a_everything"], T_PACKED) == _passes(single=5, three=3)
+    assert ep(m["m_top_fc2_b_bottom_fc2_w"], T_PACKED) == _passes(single=1, colsum=1)
+    # 249 rows / a stale plan: the fp32 GEMMs, a colsum only for a bias without its weight
+    for kw in (T_DECLINED, T_STALE):
+        assert ep(m["a_everything"], kw) == ep(m["f_weights"], kw) == _passes(plain_w=8)
+        assert ep(m["g_biases_ln"], kw) == _passes(colsum=8)
+        assert ep(m["e_bottom_fc2_b"], kw) == _passes(colsum=1)
+        assert sc.expected_producers("text", m["a_everything"], 2, **kw) == {}
+
+
+def standin_schedule(tower, mask, L, *, pruned, packed, dystats, attn_form, wgrad_plan_ok, fault=None):
+    """The split-fp16 backward walked the way engine._layers_bwd walks it — top down, each producer's decision taken where the
+    engine takes it — counting what it would call: (calls, {layer: producers}, [biases written]).  Written on its own, not from
+    split_census; `fault` plants one scheduling error."""
+    mask = frozenset(mask)
+    need = lambda i, f: f"layers.{i}.{f}" in mask                                                    # noqa: E731
+    calls, producers, written = _passes(), {}, []
+    low = sc.lowest_of(tower, mask)
+    if low is None:
+        return calls, producers, written
+    bottom = max(low, 0)
+
+    def produce(i, kind):
+        producers.setdefault(i, {k: 0 for k in sc.PRODUCER_KINDS})[kind] += 1
+
+    def taken(i, l, full=True):
+        return need(i, l + "_w") and wgrad_plan_ok and full
+
+    def lpg(i, l, stats, full=True, segments=False):
+        w, b = need(i, l + "_w"), need(i, l + "_b")
+        if taken(i, l, full):
+            if stats and fault != "consumer_ignores_stats":
+                calls["single"] += 1
+            else:
+                calls["three"] += 1
+                calls["segments"] += int(b and segments)
+            if b or fault == "db_without_need_b":
+                written.append(f"layers.{i}.{l}_b")
+        elif w:
+            calls["plain_w"] += int(full)
+            if b:
+                written.append(f"layers.{i}.{l}_b")
+        elif b:
+            calls["colsum"] += 1
+            written.append(f"layers.{i}.{l}_b")
+
+    dx_stats = False
+    for i in range(L - 1, bottom - 1, -1):
+        below = dystats and i - 1 >= (0 if fault == "producer_below_bottom" else bottom)
+        dxs = below and (taken(i - 1, "fc2") or (fault in ("stats_for_frozen_weight", "producer_below_bottom") and wgrad_plan_ok))
+        cls = pruned and i == L - 1
+        lpg(i, "fc2", dx_stats, not cls)
+        if cls:
+            lpg(i, "fc1", False, False)
+            lpg(i, "out", False, False)
+            lpg(i, "qkv", False)
+        else:
+            st = dystats and taken(i, "fc1")
+            if st:
+                produce(i, "gemm")
+            lpg(i, "fc1", st)
+            st = dystats and taken(i, "out")
+            if st:
+                produce(i, "ln")
+            lpg(i, "out", st)
+            q = dystats and taken(i, "qkv") and not packed
+            st = q and attn_form in ("stats", "rows_stats")
+            if st:
+                produce(i, "attn")
+            lpg(i, "qkv", st, segments=q and attn_form == "segments")
+        if dxs:
+            produce(i, "ln")
+        dx_stats = dxs
+    return calls, producers, written
+
+
+@pytest.mark.parametrize("route", sorted(CENSUS_ROUTES))
+def test_standin_schedule_agrees_with_the_census_on_every_mask(route):
+    tower, kw = CENSUS_ROUTES[route]
+    for L in (2, 3):
+        for mid, mask in _split_masks(tower, L).items():
+            calls, producers, written = standin_schedule(tower, mask, L, **kw)
+            sc.check_census(calls, producers, tower, mask, L, f"{route} {mid} L{L}", **kw)
+            assert sorted(written) == sorted(n for n in mask if "." in n and n.split(".")[-1] in ("fc2_b", "fc1_b", "out_b", "qkv_b"))
+            assert sum(sum(v.values()) for v in producers.values()) == calls["single"]              # nothing produced without a consumer
+
+
+@pytest.mark.parametrize("fault,tower,kw,mid,match", [
+    ("stats_for_frozen_weight", "vision", V_PRUNED, "g_biases_ln", "statistics were produced"),
+    ("stats_for_frozen_weight", "text", T_TWIN, "e_bottom_fc2_b", "statistics were produced"),
+    ("consumer_ignores_stats", "vision", V_PRUNED, "a_everything", "calls .*the census says"),
+    ("consumer_ignores_stats", "text", T_PACKED, "m_top_fc2_b_bottom_fc2_w", "calls .*the census says"),
+    ("producer_below_bottom", "vision", V_PRUNED, "i_top_layer", "statistics were produced"),
+    ("producer_below_bottom", "text", T_TWIN, "d_top_fc2_b", "statistics were produced")])
+def test_fault_census(fault, tower, kw, mid, match):
+    mask = _split_masks(tower, 2)[mid]
+    calls, producers, _ = standin_schedule(tower, mask, 2, **kw)
+    sc.check_census(calls, producers, tower, mask, 2, "ok", **kw)
+    calls, producers, _ = standin_schedule(tower, mask, 2, fault=fault, **kw)
+    with pytest.raises(AssertionError, match=match):
+        sc.check_census(calls, producers, tower, mask, 2, "planted", **kw)
+
+
+def test_fault_db_written_although_the_bias_is_not_needed(tiny):
+    """A split pass that writes db under a mask without the bias (f): the gradient comes back, and completeness names it."""
+    mask = sc.masks("vision", 2)["f_weights"]
+    _, _, written = standin_schedule("vision", mask, 2, fault="db_without_need_b", **V_PRUNED)
+    assert "layers.0.fc2_b" in written and not standin_schedule("vision", mask, 2, **V_PRUNED)[2]
+    got = standin(tiny["vision"]["r32"], "vision", mask, 2)
+    sc.check_completeness(got, mask, sc.names("vision", 2), "ok")
+    for n in written:
+        got[n] = tiny["vision"]["r32"][n].float().clone()
+    with pytest.raises(AssertionError, match="not needed.*layers.0.fc2_b"):
+        sc.check_completeness(got, mask, sc.names("vision", 2), "planted")
+
+
+def test_fault_fc1_b_finished_from_the_partials_of_dx2(tiny):
+    """The finish over a producer's partials handed the wrong ColStats: fc1_b's first D columns are the column sums of dx2 (that is
+    fc2_b), the rest is what the buffer held.  The anchor names it under the full mask (all three gates); under a mask without
+    fc1_w the bias is a plain colsum of the right tensor, and mask consistency finds the full-mask value far outside the
+    column-sum bound of dh."""
+    cfg, sd, D = tiny["cfg"], tiny["sd"], tiny["cfg"].vision.hidden_size
+
+    def f(g):
+        b = torch.zeros_like(g["layers.0.fc1_b"])
+        b[:D] = g["layers.0.fc2_b"]
+        g["layers.0.fc1_b"] = b
+    _caught_by_all_three_anchors(tiny, "vision", f, "layers.0.fc1_b")
+    # |dh| of layer 0, summed per column: dh is the gradient of quick_gelu's input
+    seen, saved = [], O.quick_gelu
+
+    def spy(x):
+        x.retain_grad()
+        seen.append(x)
+        return saved(x)
+    p = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    O.quick_gelu = spy
+    try:
+        out = O.vision_tower(p, tiny["pix"].double(), cfg.vision)
+    finally:
+        O.quick_gelu = saved
+    (out * tiny["W"]).sum().backward()
+    dh = seen[0].grad.reshape(-1, seen[0].shape[-1])
+    assert sc.rel_err(dh.sum(0), tiny["vision"]["r64"]["layers.0.fc1_b"]) < 1e-12
+    bound = {"layers.0.fc1_b": sc.colsum_bound(dh.shape[0], dh.abs().sum(0))}
+    names2 = sc.names("vision", 2)
+    mask = sc.masks("vision", 2)["g_biases_ln"]
+    exc = sc.bias_exceptions(True, mask, names2)
+    assert "layers.0.fc1_b" in exc
+    bounds = {n: (bound[n] if n in bound else torch.full_like(tiny["vision"]["r64"][n], float("inf"))) for n in exc}
+    right = standin(tiny["vision"]["r32"], "vision", names2, 2)
+    part = standin(tiny["vision"]["r32"], "vision", mask, 2)
+    sc.check_mask_consistency(part, right, exc, bounds, "ok")
+    wrong = dict(right)
+    f(wrong)
+    with pytest.raises(AssertionError, match=r"layers\.0\.fc1_b: another launch.*column-sum bound"):
+        sc.check_mask_consistency(part, wrong, exc, bounds, "planted")
+
+
+def test_split_masks_reach_every_split_situation(freeze):
+    """masks() + split_masks() reach every situation the split-fp16 backward's own branches create (schedule_checks.SPLIT_SITUATIONS)
+    on the routes of §31, and every mask still reaches a situation — of §26's or of these — that no other mask does."""
+    reach = {}
+    for tower in ("vision", "text"):
+        ms = _all_masks(tower, freeze[tower])
+        ms.update({(mid, 2): mk for mid, mk in sc.split_masks(tower, 2).items()})
+        for k, mk in ms.items():
+            r = set(sc.mask_situations(tower, mk, k[1]))
+            for route, (t, kw) in CENSUS_ROUTES.items():
+                if t == tower:
+                    r |= {f"{route}:{s}" for s in sc.split_situations(tower, mk, k[1], **kw)}
+            reach[(tower,) + k] = r
+    bare = {s.split(":", 1)[1] for r in reach.values() for s in r if ":" in s}
+    assert bare == set(sc.SPLIT_SITUATIONS), (sorted(set(sc.SPLIT_SITUATIONS) - bare), sorted(bare - set(sc.SPLIT_SITUATIONS)))
+    for tower in ("vision", "text"):
+        mine = {k: r for k, r in reach.items() if k[0] == tower}
+        for k in mine:
+            rest = set().union(*(r for kk, r in mine.items() if kk != k))
+            assert mine[k] - rest, f"mask {k} reaches nothing the other masks do not"
+    # the situations by name, where they are expected
+    v = lambda mid, L=2: sc.split_situations("vision", _split_masks("vision", L)[mid], L, **V_PRUNED)        # noqa: E731
+    assert "split.w_only" in v("f_weights") and "split.both" in v("a_everything") and "split.b_only_live_plan" in v("e_bottom_fc2_b")
+    assert "producer.consumer_below" in v("a_everything") and "producer.consumer_not_run" in v("i_top_layer")
+    assert "producer.consumer_not_run" in v("k_middle_fc2_b_out_b", 3) and "regime_on.nothing_asked" in v("g_biases_ln")
+    assert "producer.in_layer_without_split_pass" in v("m_top_fc2_b_bottom_fc2_w")
+    t = lambda mid: sc.split_situations("text", _split_masks("text", 2)[mid], 2, **T_SEG)                    # noqa: E731
+    assert "segments.with_b" in t("a_everything") and "segments.without_b" in t("f_weights") and "segments.with_b" not in t("f_weights")
