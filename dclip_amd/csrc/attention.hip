@@ -1564,6 +1564,8 @@ DCLIP_API int dclip_attention_fwd(const float* qkv, float* out, float* lse, int 
                                   void* stream) {
   DCLIP_REQUIRE(qkv && out && lse, "attention_fwd: null pointer");
   DCLIP_REQUIRE(B > 0 && S > 0 && H > 0, "attention_fwd: bad shape B=%d S=%d H=%d", B, S, H);
+  // B * H is the grid's x dimension and the row length 3 * H * 64 an int inside the kernels
+  DCLIP_REQUIRE((long)B * H <= 0x7fffffffL && H <= 0x7fffffff / (3 * HD), "attention_fwd: B * H or 3 * H * 64 does not fit in an int");
   const int D = H * HD;
   AttnArgs a{qkv, qkv + D, qkv + 2 * D, 3 * D, 3 * D, S, S, H, nullptr};
   return launch_fwd(a, out, lse, B, causal, (hipStream_t)stream);
@@ -1767,6 +1769,9 @@ DCLIP_API int dclip_attention_bwd_io16(const void* qkv16, const void* out16, con
 DCLIP_API int dclip_attention_cls_fwd(const float* qkv, float* out, float* lse, int B, int S, int H, void* stream) {
   DCLIP_REQUIRE(qkv && out && lse, "attention_cls_fwd: null pointer");
   DCLIP_REQUIRE(B > 0 && S > 0 && H > 0, "attention_cls_fwd: bad shape");
+  // the query stride of one image, S * 3 * H * 64 floats, is an int member of AttnArgs
+  DCLIP_REQUIRE((long)B * H <= 0x7fffffffL && (long)S * 3 * H * HD <= 0x7fffffffL,
+                "attention_cls_fwd: B * H or S * 3 * H * 64 does not fit in an int");
   const int D = H * HD;
   AttnArgs a{qkv, qkv + D, qkv + 2 * D, S * 3 * D, 3 * D, 1, S, H, nullptr};
   return launch_fwd(a, out, lse, B, 0, (hipStream_t)stream);
@@ -1777,6 +1782,8 @@ DCLIP_API int dclip_attention_cls_bwd(const float* qkv, const float* out, const 
                                       float* delta, int B, int S, int H, void* stream) {
   DCLIP_REQUIRE(qkv && out && dout && lse && dqkv && delta, "attention_cls_bwd: null pointer");
   DCLIP_REQUIRE(B > 0 && S > 0 && H > 0, "attention_cls_bwd: bad shape");
+  DCLIP_REQUIRE((long)B * H <= 0x7fffffffL && (long)S * 3 * H * HD <= 0x7fffffffL,
+                "attention_cls_bwd: B * H or S * 3 * H * 64 does not fit in an int");
   const int D = H * HD;
   AttnArgs a{qkv, qkv + D, qkv + 2 * D, S * 3 * D, 3 * D, 1, S, H, nullptr};
   return launch_bwd(a, out, dout, lse, dqkv, S * 3 * D, dqkv + D, dqkv + 2 * D, 3 * D, delta, B, 0, (hipStream_t)stream);

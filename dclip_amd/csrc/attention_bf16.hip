@@ -727,6 +727,8 @@ template <class T>
 int attention_row16(const char* name, const void* qkv, const int32_t* rows, void* out, int B, int S, int H, void* stream) {
   DCLIP_REQUIRE(qkv && out, "%s: null pointer", name);
   DCLIP_REQUIRE(B > 0 && S > 0 && S <= 64 * ROW_MAXI && H > 0, "%s: B=%d S=%d (<= 512) H=%d", name, B, S, H);
+  // B * H (the wave index, rounded up to whole workgroups) and the row length 3 * H * 64 are formed in int
+  DCLIP_REQUIRE((long)B * H <= 0x7fffffffL - 4 && H <= 0x7fffffff / (3 * HD), "%s: B * H or 3 * H * 64 does not fit in an int", name);
   DCLIP_REQUIRE((uintptr_t)qkv % 16 == 0, "%s: 16-byte alignment", name);
   hipLaunchKernelGGL(attn_row_fwd_bf16_kernel<T>, dim3(cdiv(B * H, 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)qkv,
                      (const int*)rows, (unsigned short*)out, B, S, H);
@@ -837,6 +839,8 @@ template <class T>
 int attention_fwd16(const char* name, const void* qkv, void* out, int B, int S, int H, int causal, void* stream) {
   DCLIP_REQUIRE(qkv && out, "%s: null pointer", name);
   DCLIP_REQUIRE(B > 0 && S > 0 && H > 0, "%s: bad shape B=%d S=%d H=%d", name, B, S, H);
+  // B * H is the grid's x dimension and the row length 3 * H * 64 an int inside the kernels
+  DCLIP_REQUIRE((long)B * H <= 0x7fffffffL && H <= 0x7fffffff / (3 * HD), "%s: B * H or 3 * H * 64 does not fit in an int", name);
   DCLIP_REQUIRE(((uintptr_t)qkv | (uintptr_t)out) % 16 == 0, "%s: 16-byte alignment", name);
   hipStream_t st = (hipStream_t)stream;
   static const bool tiled_only = getenv("DCLIP_ATTN16_TILED") && atoi(getenv("DCLIP_ATTN16_TILED")) != 0;   // A/B switch

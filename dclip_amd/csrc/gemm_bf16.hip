@@ -1501,6 +1501,9 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
   DCLIP_REQUIRE(A && W && C, "%s: null operand", name);
   DCLIP_REQUIRE(M > 0 && N > 0 && K > 0, "%s: bad shape M=%d N=%d K=%d", name, M, N, K);
   DCLIP_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "%s: lda/ldw must be multiples of 8 and >= K", name);
+  // a tile's operand loads are buffer loads with an int byte offset (tile row * ld + k) * 2 from the tile's origin and a
+  // descriptor of at most 2^31 - 1 bytes: up to 256 rows of a tile must fit
+  DCLIP_REQUIRE(256L * lda * 2 < 0x7fffffffL && 256L * ldw * 2 < 0x7fffffffL, "%s: leading dimension too large", name);
   DCLIP_REQUIRE(N % 4 == 0 && ldc % 4 == 0 && ldc >= N, "%s: N / ldc must be multiples of 4", name);
   DCLIP_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 == 0, "%s: operands must be 16-byte aligned", name);
   DCLIP_REQUIRE(!(epilogue & ~(DCLIP_EPI_BIAS | DCLIP_EPI_GELU | DCLIP_EPI_DGELU | DCLIP_EPI_RESIDUAL)),
@@ -1527,8 +1530,10 @@ int gemm16(const char* name, const void* A, const void* W, void* C, const float*
     if constexpr (!kTrain16<T>) {
       const int persist_min = getenv("DCLIP_BF16_PERSIST_MIN") ? atoi(getenv("DCLIP_BF16_PERSIST_MIN")) : 512;
       const bool gelu_f32 = (epilogue & DCLIP_EPI_GELU) && !out_bf16;
+      // (its C tile is stored through a buffer descriptor with int element offsets: 256 rows of ldc floats stay below 2^31
+      // bytes, or the one-tile kernel, which addresses C with size_t, takes the call)
       if (persistent_enabled() && !(epilogue & DCLIP_EPI_DGELU) && !gelu_f32 && out_scale == 0.f && !dev && ldc % 8 == 0 &&
-          N % 8 == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min) {
+          256L * ldc * 4 < 0x7fffffffL && N % 8 == 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= persist_min) {
         launch_ppp<T>(pb, st);
         DCLIP_CHECK_LAUNCH_V(name, ".ppp");
         return DCLIP_OK;
