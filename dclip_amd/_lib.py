@@ -204,6 +204,10 @@ SIGNATURES = {
     "dclip_clip_coef_scaled": (I, [P, I, F, P, P, P]),
     "dclip_mt_adamw_f32_skip": (I, [P, I, I, F, F, F, F, F, P, P]),
     "dclip_amp_update_scale": (I, [P, P, P, F, F, I, P]),
+    "dclip_gelu_erf_f32": (I, [P, P, Z, P]),
+    "dclip_gelu_erf_bf16": (I, [P, P, Z, P]),
+    "dclip_gelu_erf_f16": (I, [P, P, Z, P]),
+    "dclip_gelu_erf_bwd_f32": (I, [P, P, P, Z, P]),
 }
 
 _lib = None

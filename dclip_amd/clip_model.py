@@ -287,6 +287,7 @@ class HipCLIPModel(nn.Module):
             if torch.is_grad_enabled() and any(t.requires_grad for t in p.tensors()):
                 # TRAINING in bf16 (configs c3 / c5): forward, dgrad and wgrad GEMMs on the bf16 MFMA kernels, fp32
                 # master weights and fp32 everything else (engine.vision_fwd_bf16_train)
+                engine.refuse_train16(v)                 # hidden_act="gelu": NotImplementedError, nothing launched
                 return functional.VisionTowerBf16Fn.apply(pixel_values.float(), v, v.num_hidden_layers, self._bf16_cache(),
                                                           torch.bfloat16, grid, *p.tensors())
             pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)
@@ -296,6 +297,7 @@ class HipCLIPModel(nn.Module):
                 if precision == "fp16":
                     raise RuntimeError("precision='fp16' is a forward-only path for frozen towers: call it under torch.no_grad()"
                                        " (training: precision='fp16-mixed')")
+                engine.refuse_train16(v)
                 return functional.VisionTowerBf16Fn.apply(pixel_values.float(), v, v.num_hidden_layers, self._f16_cache(),
                                                           torch.float16, grid, *p.tensors())
             pd = engine.VisionParams.from_tensors([t.detach() for t in p.tensors()], v.num_hidden_layers)

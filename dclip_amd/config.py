@@ -20,6 +20,7 @@ class VisionConfig:
     patch_size: int = 32
     num_channels: int = 3
     layer_norm_eps: float = 1e-5
+    hidden_act: str = "quick_gelu"      # or "gelu" (exact erf GELU: the LAION / OpenCLIP conversions); last: old dicts lack it
 
     @property
     def grid(self) -> int:
@@ -53,6 +54,7 @@ class TextConfig:
     bos_token_id: int = 49406
     eos_token_id: int = 49407
     layer_norm_eps: float = 1e-5
+    hidden_act: str = "quick_gelu"      # as VisionConfig's: HF keeps one per tower
 
     @property
     def head_dim(self) -> int:
@@ -69,6 +71,15 @@ class ClipConfig:
 
     def to_dict(self) -> dict:
         return asdict(self)
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "ClipConfig":
+        """The inverse of to_dict.  A dict written before a field existed takes that field's default: a checkpoint without
+        `hidden_act` is a quick-GELU model."""
+        d = dict(d)
+        v, t = VisionConfig(**d.pop("vision", {})), TextConfig(**d.pop("text", {}))
+        hidden_act_of(v, "vision"), hidden_act_of(t, "text")
+        return cls(vision=v, text=t, **d)
 
 
 def vit_b32() -> ClipConfig:
@@ -102,15 +113,29 @@ def tiny(image_size: int = 64, patch_size: int = 16, layers: int = 2, seq: int =
 NAMED = {"ViT-B/32": vit_b32, "ViT-B/16": vit_b16, "ViT-L/14": vit_l14, "tiny": tiny}
 
 
+HIDDEN_ACTS = ("quick_gelu", "gelu")
+
+
+def hidden_act_of(tower_config, what: str = "config") -> str:
+    """The MLP activation a tower configuration names: "quick_gelu" (x sigmoid(1.702 x), OpenAI's release; also what a
+    configuration without the field means) or "gelu" (exact erf GELU).  Anything else is a ValueError: the towers have no other
+    activation and must not run a different network in silence."""
+    act = getattr(tower_config, "hidden_act", None)
+    act = "quick_gelu" if act is None else act
+    if act not in HIDDEN_ACTS:
+        raise ValueError(f"{what}: hidden_act {act!r} is not supported (one of {HIDDEN_ACTS})")
+    return act
+
+
 def from_hf(hf_config) -> ClipConfig:
-    """Build from an HF `CLIPConfig` object (duck-typed; transformers is optional)."""
+    """Build from an HF `CLIPConfig` object (duck-typed; transformers is optional).  Each tower's own `hidden_act` is kept."""
     v, t = hf_config.vision_config, hf_config.text_config
     return ClipConfig(
         vision=VisionConfig(v.hidden_size, v.intermediate_size, v.num_hidden_layers,
                             v.num_attention_heads, v.image_size, v.patch_size, v.num_channels,
-                            v.layer_norm_eps),
+                            v.layer_norm_eps, hidden_act_of(v, "vision_config")),
         text=TextConfig(t.hidden_size, t.intermediate_size, t.num_hidden_layers,
                         t.num_attention_heads, t.max_position_embeddings, t.vocab_size,
-                        t.bos_token_id, t.eos_token_id, t.layer_norm_eps),
+                        t.bos_token_id, t.eos_token_id, t.layer_norm_eps, hidden_act_of(t, "text_config")),
         projection_dim=hf_config.projection_dim,
         logit_scale_init_value=hf_config.logit_scale_init_value, name="hf")

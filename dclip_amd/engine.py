@@ -134,14 +134,68 @@ def _linear(a, w, sp: Optional[Split16Layer], name: str, bias, residual=None):
     return _gemm_f16_dev(a, sp.w[name], sp.alpha(name), bias=bias, residual=residual)
 
 
-def _fc1_gelu(a, p: LayerParams, save: bool, sp: Optional[Split16Layer], pieces: int = 3, save_g32: bool = True):
-    """(operand of fc2, h, g): g = quick_gelu(h), h = a fc1_w^T + b kept only with `save`.  `pieces`: of the split operand;
-    `save_g32` False (`sp` only): the fp32 g is not kept (None)."""
+# The MLP activation of a tower (cfg.hidden_act).  "quick_gelu" is what every GEMM epilogue computes and what every
+# call below was before the field existed, launch for launch.  "gelu" (exact erf GELU) has no epilogue: fc1 is a bias-only GEMM
+# and the activation a stand-alone pass (ops.gelu_erf / ops.gelu_erf_bwd).  The choice is made in three places — _fc1_act_f32 and
+# _dgelu_f32 for the fp32 schedules, _fc1_act16 for the frozen 16-bit ones; the split-fp16 plans, whose fused epilogues and
+# rematerialised g are quick-GELU, decline a "gelu" tower (_split16_declines_act) and the 16-bit TRAINING path refuses it.
+QUICK_GELU, GELU_ERF = "quick_gelu", "gelu"
+
+
+def hidden_act(cfg) -> str:
+    """A tower configuration's activation; a configuration without the field is a quick-GELU tower."""
+    act = getattr(cfg, "hidden_act", QUICK_GELU)
+    if act not in (QUICK_GELU, GELU_ERF):
+        raise ValueError(f"hidden_act {act!r} is not supported (one of {(QUICK_GELU, GELU_ERF)})")
+    return act
+
+
+def _fc1_act_f32(a, p: LayerParams, act: str, save: bool = False):
+    """(g, h) of the fp32 MLP: h = a fc1_w^T + b (kept only with `save`, else None), g = act(h)."""
+    h = torch.empty((a.shape[0], p.fc1_w.shape[0]), dtype=torch.float32, device=a.device) if save else None
+    if act == GELU_ERF:
+        pre = ops.gemm(a, p.fc1_w, ops.LAYOUT_NT, bias=p.fc1_b, out=h)
+        return ops.gelu_erf(pre, out=None if save else pre), h      # in place when nothing is saved
+    return ops.gemm(a, p.fc1_w, ops.LAYOUT_NT, bias=p.fc1_b, aux=h, epilogue=ops.EPI_GELU), h
+
+
+def _dgelu_f32(dy, w, h, act: str):
+    """dh = (dy w) act'(h): the fp32 data gradient of fc2 through the activation."""
+    if act == GELU_ERF:
+        dg = ops.gemm(dy, w, ops.LAYOUT_NN)
+        return ops.gelu_erf_bwd(h, dg, out=dg)
+    return ops.gemm(dy, w, ops.LAYOUT_NN, aux=h, epilogue=ops.EPI_DGELU)
+
+
+def _fc1_act16(k, a16, w16, bias, act: str):
+    """16-bit g = act(a16 w16^T + bias) of a frozen 16-bit schedule (k: its _Ops16).  "gelu": the activation of the STORED 16-bit
+    pre-activation, in place — the statement of the quick-GELU 16-bit epilogue (include/dclip_hip.h, 16-bit output)."""
+    if act == GELU_ERF:
+        h16 = k.gemm(a16, w16, bias=bias, out16=True)
+        return ops.gelu_erf(h16, out=h16)
+    return k.gemm(a16, w16, bias=bias, gelu=True, out16=True)
+
+
+def _split16_declines_act(cfg, what: str) -> bool:
+    """True — logged once — for a "gelu" tower at a split-fp16 switch: the plans' fused fc1 epilogues and the g a backward makes
+    again are quick-GELU, so such a tower takes the plain fp32 path, the way a tripped weight guard falls back."""
+    if hidden_act(cfg) != GELU_ERF:
+        return False
+    _split16_log_once(f"{what}: hidden_act='gelu' has no split-fp16 form; the tower takes the plain fp32 path")
+    return True
+
+
+def _fc1_gelu(a, p: LayerParams, save: bool, sp: Optional[Split16Layer], pieces: int = 3, save_g32: bool = True,
+              act: str = QUICK_GELU):
+    """(operand of fc2, h, g): g = act(h), h = a fc1_w^T + b kept only with `save`.  `pieces`: of the split operand;
+    `save_g32` False (`sp` only): the fp32 g is not kept (None).  `sp` is quick-GELU only."""
     M, I = a.shape[0], p.fc1_w.shape[0]
-    h = torch.empty((M, I), dtype=torch.float32, device=a.device) if save else None
     if sp is None:
-        g = ops.gemm(a, p.fc1_w, ops.LAYOUT_NT, bias=p.fc1_b, aux=h, epilogue=ops.EPI_GELU)
+        g, h = _fc1_act_f32(a, p, act, save)
         return g, h, g
+    if act != QUICK_GELU:
+        raise RuntimeError(f"the split-fp16 fc1 epilogue is quick-GELU: a {act!r} layer must not reach it")
+    h = torch.empty((M, I), dtype=torch.float32, device=a.device) if save else None
     g = torch.empty((M, I), dtype=torch.float32, device=a.device) if save and save_g32 else None
     if _VSPLIT16_FC1_EPI:
         g3 = _gemm_f16_dev(a, sp.w["fc1"], sp.alpha("fc1"), out_pieces=pieces, bias=p.fc1_b, gelu=True,
@@ -163,8 +217,8 @@ def _layer_pieces(T: int, D: int, I: int, fc1_epi: bool) -> Dict[str, int]:
 
 
 def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: float, save: bool, sp: Optional[Split16Layer] = None,
-              keep_split: bool = False, varlen=None):
-    """`keep_split` (with `save` and `sp`): the four [hi|lo|hi] (or [hi|lo], §9j) operands this forward produced anyway — of ln1,
+              keep_split: bool = False, varlen=None, act: str = QUICK_GELU):
+    """`act`: the MLP activation (hidden_act).  `keep_split` (with `save` and `sp`): the four [hi|lo|hi] (or [hi|lo], §9j) operands this forward produced anyway — of ln1,
     the attention context, ln2 and g — are kept as a 14th entry of `saved`, the X operands of the split-fp16 weight gradients
     (DESIGN.md §9f).  The fp32 ln1, ln2 and g are then None in `saved` wherever that weight gradient has a split plan (_drops32,
     §9j): layer_bwd makes them again if it lands on the fp32 weight gradient after all.
@@ -186,7 +240,7 @@ def layer_fwd(x, p: LayerParams, B: int, S: int, H: int, causal: bool, eps: floa
     x1 = _linear(ac, p.out_w, sp, "out", p.out_b, residual=x)
     a2, ln2, m2, r2 = _ln_operand(x1, p.ln2_w, p.ln2_b, eps, save, sp, "ln2", pc.get("ln2", 3),
                                   not _drops32(keep_split, save, sp, I, D, T))
-    ag, h, g = _fc1_gelu(a2, p, save, sp, pc.get("g", 3), not _drops32(keep_split, save, sp, D, I, T))
+    ag, h, g = _fc1_gelu(a2, p, save, sp, pc.get("g", 3), not _drops32(keep_split, save, sp, D, I, T), act)
     x2 = _linear(ag, p.fc2_w, sp, "fc2", p.fc2_b, residual=x1)
     saved = (x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g) if save else None
     if save and keep_split and sp is not None:
@@ -302,8 +356,8 @@ def _ln_bwd(dy, x, gamma, mean, rstd, dresidual, want: bool, gr, wkey: str, bkey
     return dx, st
 
 
-def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None, out_stats: bool = False):
-    """(dX, stats): dX = dy w (times quick_gelu'(aux) when given), the data gradient of a linear layer.  `sp` (a Split16Layer with
+def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None, out_stats: bool = False, act: str = QUICK_GELU):
+    """(dX, stats): dX = dy w (times act'(aux) when given; `sp` is quick-GELU only), the data gradient of a linear layer.  `sp` (a Split16Layer with
     transposed copies): dy is split with one scale per row and meets the [hi|hi|lo] copy of w^T on the fp16 MFMAs (DESIGN.md
     §9e); None = the plain fp32 GEMM.  dy itself stays fp32 for the weight and bias gradients.  `rows`: the row pieces
     (dy3, row_alpha) when linear_param_grads has already made them in its fused pass (§9f).  `out_stats`: dX is itself the dY of
@@ -312,7 +366,9 @@ def _dgrad(dy, w, sp: Optional[Split16Layer], name: str, aux=None, rows=None, ou
     if sp is None:
         if aux is None:
             return ops.gemm(dy, w, ops.LAYOUT_NN), None
-        return ops.gemm(dy, w, ops.LAYOUT_NN, aux=aux, epilogue=ops.EPI_DGELU), None
+        return _dgelu_f32(dy, w, aux, act), None
+    if aux is not None and act != QUICK_GELU:
+        raise RuntimeError(f"the split-fp16 data gradient's epilogue is quick-GELU: a {act!r} layer must not reach it")
     wt = sp.wt[name]
     dy3, row_alpha = rows if rows is not None else ops.split_f16x3_rows(
         dy, pieces=split16_pieces([(dy.shape[0], wt.shape[0], wt.shape[1] // 3)]))
@@ -340,8 +396,8 @@ def _remat_ln(ln, x, w, b, eps: Optional[float]):
 
 def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, need: Dict[str, bool], alloc=None,
               sp: Optional[Split16Layer] = None, dx_stats: bool = False, dystats: bool = False, eps: Optional[float] = None,
-              varlen=None, dx2_stats=None):
-    """Returns (dx, grads, stats) with grads keyed like LayerParams.FIELDS (missing = not needed).  `varlen`: as in layer_fwd.
+              varlen=None, dx2_stats=None, act: str = QUICK_GELU):
+    """Returns (dx, grads, stats) with grads keyed like LayerParams.FIELDS (missing = not needed).  `varlen`, `act`: as in layer_fwd.
     `alloc(field, shape)`: see _galloc.  `sp`: the four data-gradient GEMMs take the split-fp16 path (_dgrad).  `eps`: the layer's,
     for an fp32 LayerNorm output the forward did not keep (_remat_ln, §9j).  `dystats` (the caller's decision for the whole
     tower, _dystats_regime): each kernel that produces the dY of a weight gradient that will take the split path is asked for
@@ -358,7 +414,7 @@ def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, 
     rows = linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc, sp, "g", s3.get("g"),
                               stats=dx2_stats)
     dh, dh_stats = _dgrad(dx2, p.fc2_w, sp, "fc2", aux=h, rows=rows,
-                          out_stats=dystats and _split_wgrad_taken(bool(need.get("fc1_w")), sp, s3.get("ln2"), I, D, T))
+                          out_stats=dystats and _split_wgrad_taken(bool(need.get("fc1_w")), sp, s3.get("ln2"), I, D, T), act=act)
     rows = linear_param_grads(dh, ln2, bool(need.get("fc1_w")), bool(need.get("fc1_b")), gr, "fc1_w", "fc1_b", alloc, sp, "ln2",
                               s3.get("ln2"), stats=dh_stats)
     dln2, _ = _dgrad(dh, p.fc1_w, sp, "fc1", rows=rows)
@@ -400,7 +456,7 @@ def layer_bwd(dx2, p: LayerParams, saved, B: int, S: int, H: int, causal: bool, 
 # to the unpruned schedule (tests/test_model_gpu.py); 9/12 of that layer's GEMM work disappears.
 
 def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, save: bool, sp: Optional[Split16Layer] = None,
-                       keep_split: bool = False):
+                       keep_split: bool = False, act: str = QUICK_GELU):
     """`sp`: the full-size qkv projection takes the split-fp16 path (layer_fwd); the M = B GEMMs stay on ops.gemm.
     `keep_split`: ln1's split is kept for the qkv weight gradient (layer_fwd)."""
     D = x.shape[1]
@@ -412,8 +468,7 @@ def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, sa
     x_cls = ops.gather_rows(x, None, B, S, D)
     x1 = ops.gemm(attn, p.out_w, ops.LAYOUT_NT, bias=p.out_b, residual=x_cls)
     ln2, m2, r2 = ops.layernorm_fwd(x1, p.ln2_w, p.ln2_b, eps, save_stats=save)
-    h = torch.empty((B, p.fc1_w.shape[0]), dtype=torch.float32, device=x.device) if save else None
-    g = ops.gemm(ln2, p.fc1_w, ops.LAYOUT_NT, bias=p.fc1_b, aux=h, epilogue=ops.EPI_GELU)
+    g, h = _fc1_act_f32(ln2, p, act, save)
     x2 = ops.gemm(g, p.fc2_w, ops.LAYOUT_NT, bias=p.fc2_b, residual=x1)   # [B, D] = final hidden state, CLS rows
     saved = (x, m1, r1, ln1, qkv, attn, lse, x1, m2, r2, ln2, h, g) if save else None
     if save and keep_split and sp is not None:
@@ -422,7 +477,8 @@ def last_layer_fwd_cls(x, p: LayerParams, B: int, S: int, H: int, eps: float, sa
 
 
 def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need: Dict[str, bool], alloc=None,
-                       sp: Optional[Split16Layer] = None, dx_stats: bool = False, eps: Optional[float] = None):
+                       sp: Optional[Split16Layer] = None, dx_stats: bool = False, eps: Optional[float] = None,
+                       act: str = QUICK_GELU):
     """dx2 [B, D] is the gradient w.r.t. the CLS rows of the final hidden state; returns (dx [B*S, D], grads, stats) — `stats`:
     dx's column partials when `dx_stats` asked for them, as layer_bwd's.  `sp`: the full-size qkv data gradient takes the
     split-fp16 path (_dgrad); the M = B GEMMs stay on ops.gemm."""
@@ -432,7 +488,7 @@ def last_layer_bwd_cls(dx2, p: LayerParams, saved, B: int, S: int, H: int, need:
     ln1 = _remat_ln(ln1, x, p.ln1_w, p.ln1_b, eps)
     gr: Dict[str, torch.Tensor] = {}
     linear_param_grads(dx2, g, bool(need.get("fc2_w")), bool(need.get("fc2_b")), gr, "fc2_w", "fc2_b", alloc)
-    dh = ops.gemm(dx2, p.fc2_w, ops.LAYOUT_NN, aux=h, epilogue=ops.EPI_DGELU)
+    dh = _dgelu_f32(dx2, p.fc2_w, h, act)
     linear_param_grads(dh, ln2, bool(need.get("fc1_w")), bool(need.get("fc1_b")), gr, "fc1_w", "fc1_b", alloc)
     dln2 = ops.gemm(dh, p.fc1_w, ops.LAYOUT_NN)
     dx1, _ = _ln_bwd(dln2, x1, p.ln2_w, m2, r2, dx2, bool(need.get("ln2_w") or need.get("ln2_b")), gr, "ln2_w", "ln2_b", alloc)
@@ -535,13 +591,14 @@ def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hid
     saved_layers = []
     prune = hidden_out is None and len(p.layers) > 0          # full hidden states are only materialised on request
     plan, keep = _train_split16(p.layers, v, save, split16_cache, split16_out, _VSPLIT16)
+    act = hidden_act(v)
     for li, lp in enumerate(p.layers):
         sp = plan[li] if plan is not None else None
         if prune and li == len(p.layers) - 1:
-            cls_tok, sv = last_layer_fwd_cls(x, lp, B, S, H, v.layer_norm_eps, save, sp, keep)
+            cls_tok, sv = last_layer_fwd_cls(x, lp, B, S, H, v.layer_norm_eps, save, sp, keep, act=act)
             saved_layers.append(sv)
             break
-        x, sv = layer_fwd(x, lp, B, S, H, False, v.layer_norm_eps, save, sp, keep)
+        x, sv = layer_fwd(x, lp, B, S, H, False, v.layer_norm_eps, save, sp, keep, act=act)
         saved_layers.append(sv)
         if hidden_out is not None:
             hidden_out.append(x)
@@ -570,7 +627,8 @@ def _lowest_needed(names, needd: Dict[str, bool], head, tail) -> Optional[int]:
 
 
 def _layers_bwd(dx, layers: List[LayerParams], saved_layers, needd: Dict[str, bool], grads, lowest: int, rows: int, B: int, S: int,
-                H: int, causal: bool, eps: float, split16=None, varlen=None, alloc=None, on_ready=None, dcls=None):
+                H: int, causal: bool, eps: float, split16=None, varlen=None, alloc=None, on_ready=None, dcls=None,
+                act: str = QUICK_GELU):
     """The encoder stack's backward from the top layer down to max(lowest, 0), fp32 or split-fp16 -> dx below the last layer
     run.  `rows`: the token rows of a full-size layer (B S, or Tp with `varlen`, layer_bwd's).  `split16`: the forward's
     Split16Bwd — the full-size data- and weight-gradient GEMMs run on its plan unless a watched parameter has changed since;
@@ -594,10 +652,10 @@ def _layers_bwd(dx, layers: List[LayerParams], saved_layers, needd: Dict[str, bo
         dxs = below and _split_wgrad_taken(bool(needd[f"layers.{i - 1}.fc2_w"]), plan[i - 1], saved_layers[i - 1][13].get("g"),
                                            D, layers[i - 1].fc1_w.shape[0], rows)
         if dcls is not None and i == n_layers - 1:
-            dx, gr, dx_stats = last_layer_bwd_cls(dcls, layers[i], saved_layers[i], B, S, H, lneed, lalloc, sp, dxs, eps=eps)
+            dx, gr, dx_stats = last_layer_bwd_cls(dcls, layers[i], saved_layers[i], B, S, H, lneed, lalloc, sp, dxs, eps=eps, act=act)
         else:
             dx, gr, dx_stats = layer_bwd(dx, layers[i], saved_layers[i], B, S, H, causal, lneed, lalloc, sp, dxs, dystats, eps=eps,
-                                         varlen=varlen, dx2_stats=dx_stats)
+                                         varlen=varlen, dx2_stats=dx_stats, act=act)
         saved_layers[i] = None
         for f, t in gr.items():
             grads[f"layers.{i}.{f}"] = t
@@ -667,7 +725,7 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
         return [grads[n] for n in names]
     dx = None if pruned else ops.scatter_rows(dcls, None, B, S, D)
     dx = _layers_bwd(dx, p.layers, saved_layers, needd, grads, lowest, B * S, B, S, H, False, v.layer_norm_eps, split16,
-                     alloc=alloc, on_ready=on_ready, dcls=dcls if pruned else None)
+                     alloc=alloc, on_ready=on_ready, dcls=dcls if pruned else None, act=hidden_act(v))
     if lowest < 0:
         _vision_head_bwd(p, dx, emb, m0, r0, cols, B, S, v, grid, needd, grads, alloc, on_ready)
     return [grads[n] for n in names]
@@ -744,14 +802,14 @@ def _w16(cache: dict, key: str, w: torch.Tensor, cast=ops.cast_bf16) -> torch.Te
 
 
 def _layer_fwd_bf16(x, p: LayerParams, c: dict, pre: str, B: int, S: int, H: int, causal: bool, eps: float,
-                    dtype=torch.bfloat16):
+                    dtype=torch.bfloat16, act: str = QUICK_GELU):
     k = _OPS16[dtype]
     ln1 = k.layernorm(x, p.ln1_w, p.ln1_b, eps)
     qkv = k.gemm(ln1, _w16(c, pre + "qkv", p.qkv_w, k.cast), bias=p.qkv_b, out16=True)
     attn = k.attention(qkv, B, S, H, causal)                  # 16-bit q/k/v in, 16-bit context out: no cast pass
     x1 = k.gemm(attn, _w16(c, pre + "out", p.out_w, k.cast), bias=p.out_b, residual=x)
     ln2 = k.layernorm(x1, p.ln2_w, p.ln2_b, eps)
-    g = k.gemm(ln2, _w16(c, pre + "fc1", p.fc1_w, k.cast), bias=p.fc1_b, gelu=True, out16=True)
+    g = _fc1_act16(k, ln2, _w16(c, pre + "fc1", p.fc1_w, k.cast), p.fc1_b, act)
     return k.gemm(g, _w16(c, pre + "fc2", p.fc2_w, k.cast), bias=p.fc2_b, residual=x1)
 
 
@@ -775,7 +833,7 @@ def vision_fwd_bf16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dic
     x, _, _ = ops.layernorm_fwd(ops.vision_assemble_fwd(patch, p.class_embedding, pos, B, S, D), p.pre_w, p.pre_b,
                                 v.layer_norm_eps, save_stats=False)
     for li, lp in enumerate(p.layers[:-1]):
-        x = _layer_fwd_bf16(x, lp, cache, f"v{li}.", B, S, H, False, v.layer_norm_eps, dtype)
+        x = _layer_fwd_bf16(x, lp, cache, f"v{li}.", B, S, H, False, v.layer_norm_eps, dtype, hidden_act(v))
     lp, pre = p.layers[-1], f"v{len(p.layers) - 1}."
     # last layer on the CLS rows only (see last_layer_fwd_cls)
     ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, v.layer_norm_eps)
@@ -789,7 +847,7 @@ def vision_fwd_bf16(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dic
     x1 = k.gemm(attn16, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b,
                 residual=ops.gather_rows(x, None, B, S, D))
     ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, v.layer_norm_eps)
-    g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+    g = _fc1_act16(k, ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), lp.fc1_b, hidden_act(v))
     cls_tok = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
     pooled, _, _ = ops.layernorm_fwd(cls_tok, p.post_w, p.post_b, v.layer_norm_eps, save_stats=False)
     return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)          # [B,D] x [P,D]: tiny, kept in exact fp32
@@ -813,7 +871,7 @@ def vision_fwd_packed(p: VisionParams, cols: torch.Tensor, grids: torch.Tensor, 
     0 .. L-2 on split-fp16 operands with the context written split by the packed attention entry, the last layer's full-size qkv
     projection too, its CLS-row steps in fp32; the "fp32" schedule, bit for bit, when the guard trips.  `attn16` has no effect."""
     v = cfg
-    D, H, eps = v.hidden_size, v.num_attention_heads, v.layer_norm_eps
+    D, H, eps, act = v.hidden_size, v.num_attention_heads, v.layer_norm_eps, hidden_act(v)
     if not p.layers:
         raise ValueError("vision_fwd_packed: the tower has no encoder layer")
     if precision in ("fp32", "fp32-split16"):
@@ -840,7 +898,7 @@ def vision_fwd_packed(p: VisionParams, cols: torch.Tensor, grids: torch.Tensor, 
                 attn = ops.attention_varlen_fwd(qkv, cu_seqlens, max_S, H, cls_only=last)
                 x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=ops.gather_rows_at(x, cls_rows) if last else x)
                 ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
-                g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
+                g, _ = _fc1_act_f32(ln2, lp, act)
                 x = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)    # the last layer: [N, D], the CLS rows
     else:
         if precision not in ("bf16", "fp16") or cache is None:
@@ -864,7 +922,7 @@ def vision_fwd_packed(p: VisionParams, cols: torch.Tensor, grids: torch.Tensor, 
             x1 = k.gemm(attn, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b,
                         residual=ops.gather_rows_at(x, cls_rows) if last else x)
             ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
-            g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+            g = _fc1_act16(k, ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), lp.fc1_b, act)
             x = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
     pooled, _, _ = ops.layernorm_fwd(x, p.post_w, p.post_b, eps, save_stats=False)
     return ops.gemm(pooled, p.proj_w, ops.LAYOUT_NT)
@@ -1222,10 +1280,20 @@ def _patch_embed_bf16(v, rows: int, dtype=torch.bfloat16) -> bool:
     return hit
 
 
+def refuse_train16(cfg) -> None:
+    """16-bit TRAINING of a "gelu" tower is not built: its fc1 / fc2 GEMMs carry quick-GELU and its derivative in their epilogues
+    (layer_fwd_bf16_train, layer_bwd_bf16*).  Raised before anything is launched; the frozen 16-bit forward of the same model works."""
+    if hidden_act(cfg) != QUICK_GELU:
+        raise NotImplementedError(f"hidden_act={hidden_act(cfg)!r}: 16-bit training (precision 'bf16' / 'fp16-mixed' with gradients, "
+                                  "student_precision 'bf16' / 'fp16') is built for hidden_act='quick_gelu' only; train this tower "
+                                  "at precision 'fp32', or use the 16-bit precisions under torch.no_grad()")
+
+
 def vision_fwd_bf16_train(p: VisionParams, pixel_values: torch.Tensor, cfg, cache: dict, dtype=torch.bfloat16, grid=None):
     """get_image_features with gradients, 16-bit GEMM inputs (`dtype` bf16, or fp16 with IEEE rounding) in the patch
     embedding and the encoder layers; `cache` holds the weight copies of that type.  `grid`: as in vision_fwd."""
     v = cfg
+    refuse_train16(v)
     k = _TRAIN16[dtype]
     B = pixel_values.shape[0]
     S, D, H = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads
@@ -1339,7 +1407,8 @@ def text_encoder_fwd(p: TextParams, input_ids: torch.Tensor, cfg, save: bool, hi
     saved_layers = []
     plan, keep = _text_train_split16(p, cfg, save, split16_cache, split16_out)
     for li, lp in enumerate(p.layers):
-        x, sv = layer_fwd(x, lp, B, T, H, True, t.layer_norm_eps, save, plan[li] if plan is not None else None, keep)
+        x, sv = layer_fwd(x, lp, B, T, H, True, t.layer_norm_eps, save, plan[li] if plan is not None else None, keep,
+                          act=hidden_act(t))
         saved_layers.append(sv)
         if hidden_out is not None:
             hidden_out.append(x)
@@ -1356,25 +1425,25 @@ def text_fwd_frozen(p: TextParams, input_ids: torch.Tensor, cfg):
     eos = ops.first_eos(input_ids, t.eos_token_id)
     x = ops.text_embed_fwd(input_ids, p.tok, p.pos)
     for lp in p.layers[:-1]:
-        x, _ = layer_fwd(x, lp, B, T, H, True, t.layer_norm_eps, False)
+        x, _ = layer_fwd(x, lp, B, T, H, True, t.layer_norm_eps, False, act=hidden_act(t))
     lp = p.layers[-1]
     ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, t.layer_norm_eps, save_stats=False)
     qkv = ops.gemm(ln1, lp.qkv_w, ops.LAYOUT_NT, bias=lp.qkv_b)
     attn = ops.attention_row_fwd(qkv, eos, B, T, H)
-    rows = _pruned_tail_f32(attn, ops.gather_rows(x, eos, B, T, D), lp, t.layer_norm_eps)
+    rows = _pruned_tail_f32(attn, ops.gather_rows(x, eos, B, T, D), lp, t.layer_norm_eps, hidden_act(t))
     return _text_head(rows, p, t.layer_norm_eps)[0]
 
 
-def _pruned_tail_f32(ctx_rows, x_rows, lp: LayerParams, eps: float):
+def _pruned_tail_f32(ctx_rows, x_rows, lp: LayerParams, eps: float, act: str = QUICK_GELU):
     """What follows the attention in the pruned last layer of a frozen fp32 (or split-fp16) tower, on the pooled rows only
-    (M = batch, ops.gemm): out-projection + residual, LayerNorm 2, fc1 with quick-GELU, fc2 + residual.  `ctx_rows`: those rows'
+    (M = batch, ops.gemm): out-projection + residual, LayerNorm 2, fc1 with the activation `act`, fc2 + residual.  `ctx_rows`: those rows'
     attention context, `x_rows`: their rows of the layer's input — the caller launches the one-row attention first and the row
     gather second.  Returns the final hidden state of the rows.  Used by text_fwd_frozen, text_fwd_frozen_split16,
     text_fwd_frozen_packed ("fp32" / split16) and _frozen_split16_last_cls (last_layer_fwd_cls, which saves for a backward, is
     not a copy)."""
     x1 = ops.gemm(ctx_rows, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=x_rows)
     ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
-    g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
+    g, _ = _fc1_act_f32(ln2, lp, act)
     return ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
 
 
@@ -1525,6 +1594,8 @@ def _text_frozen_split16_plan(p: TextParams, cfg, cache: dict):
     off, the tower has no layer, a width is no multiple of 8 or the plan's own guard trips."""
     if not (_SPLIT16 and len(p.layers) > 0 and cfg.hidden_size % 8 == 0 and cfg.intermediate_size % 8 == 0):
         return None
+    if _split16_declines_act(cfg, "split-fp16 text tower"):
+        return None
     return _split16_plan(p.layers, cache)
 
 
@@ -1613,6 +1684,8 @@ _VFROZEN_WHAT = "split-fp16 frozen vision tower"
 def _vision_frozen_split16_plan(layers: List[LayerParams], cfg, cache: Optional[dict]):
     """The frozen vision tower's host plan (_split16_plan's layers), or None: the plain fp32 path."""
     if cache is None or not layers or cfg.hidden_size % 8 or cfg.intermediate_size % 8:
+        return None
+    if _split16_declines_act(cfg, _VFROZEN_WHAT):
         return None
     return _split16_plan(layers, cache, _VFROZEN_WHAT, 'use precision="fp32"')
 
@@ -1870,6 +1943,8 @@ def _train_split16(layers: List[LayerParams], cfg, save: bool, split16_cache: Op
     declined (`log_declined`)."""
     if not (on and save and split16_cache is not None):
         return None, False
+    if _split16_declines_act(cfg, what):
+        return None, False
     plan = _vision_split16_plan(layers, cfg, split16_cache, key, what, off)
     if plan is None:
         if log_declined:
@@ -1932,7 +2007,8 @@ def text_bwd(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[bool], s
     if lowest is None:
         return [grads[n] for n in names]
     dx = ops.scatter_rows(drows, eos, B, T, D)
-    dx = _layers_bwd(dx, p.layers, saved_layers, needd, grads, lowest, B * T, B, T, H, True, t.layer_norm_eps, split16)
+    dx = _layers_bwd(dx, p.layers, saved_layers, needd, grads, lowest, B * T, B, T, H, True, t.layer_norm_eps, split16,
+                     act=hidden_act(t))
     if lowest < 0:
         if needd["pos"]:
             dpos = torch.zeros_like(p.pos)
@@ -1949,7 +2025,7 @@ def _text_stack_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dict, n
     B, T = input_ids.shape
     x = ops.text_embed_fwd(input_ids, p.tok, p.pos)
     for li, lp in enumerate(p.layers[:n_layers]):
-        x = _layer_fwd_bf16(x, lp, cache, f"t{li}.", B, T, t.num_attention_heads, True, t.layer_norm_eps, dtype)
+        x = _layer_fwd_bf16(x, lp, cache, f"t{li}.", B, T, t.num_attention_heads, True, t.layer_norm_eps, dtype, hidden_act(t))
     return x
 
 
@@ -1972,7 +2048,7 @@ def text_fwd_frozen_bf16(p: TextParams, input_ids: torch.Tensor, cfg, cache: dic
     x1 = k.gemm(attn16, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b,
                 residual=ops.gather_rows(x, eos, B, T, D))
     ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, t.layer_norm_eps)
-    g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+    g = _fc1_act16(k, ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), lp.fc1_b, hidden_act(t))
     rows = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
     return _text_head(rows, p, t.layer_norm_eps)[0]
 
@@ -2034,7 +2110,7 @@ def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str
     leaves the attention kernel split, _packed_ctx3) / "bf16" / "fp16" (cache: the model's weight cache of that type; fp32
     q | k | v for the fp32 packed core, the context is cast — or, with `attn16`, 16-bit q | k | v and context around the packed
     MFMA core, packed_attn16_route)."""
-    H, eps = cfg.num_attention_heads, cfg.layer_norm_eps
+    H, eps, act = cfg.num_attention_heads, cfg.layer_norm_eps, hidden_act(cfg)
     pc = _layer_pieces(x.shape[0], cfg.hidden_size, cfg.intermediate_size, _SPLIT16_FC1_EPI) if mode == "split16" else None
     for li, lp in enumerate(layers[:n_layers]):
         if mode == "fp32":
@@ -2043,7 +2119,7 @@ def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str
             attn = ops.attention_varlen_causal_fwd(qkv, cu, max_S, H)
             x1 = ops.gemm(attn, lp.out_w, ops.LAYOUT_NT, bias=lp.out_b, residual=x)
             ln2, _, _ = ops.layernorm_fwd(x1, lp.ln2_w, lp.ln2_b, eps, save_stats=False)
-            g = ops.gemm(ln2, lp.fc1_w, ops.LAYOUT_NT, bias=lp.fc1_b, epilogue=ops.EPI_GELU)
+            g, _ = _fc1_act_f32(ln2, lp, act)
             x = ops.gemm(g, lp.fc2_w, ops.LAYOUT_NT, bias=lp.fc2_b, residual=x1)
         elif mode == "split16":
             x = _frozen_split16_layer(x, lp, plan[li], pc, eps, _packed_ctx3(cu, max_S, H, True, ctx_fused))
@@ -2058,7 +2134,7 @@ def _packed_text_layers(x, layers, n_layers: int, cu, max_S: int, cfg, mode: str
                 attn = k.cast(ops.attention_varlen_causal_fwd(qkv, cu, max_S, H))
             x1 = k.gemm(attn, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b, residual=x)
             ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
-            g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+            g = _fc1_act16(k, ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), lp.fc1_b, act)
             x = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
     return x
 
@@ -2100,7 +2176,7 @@ def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict,
             ln1, _, _ = ops.layernorm_fwd(x, lp.ln1_w, lp.ln1_b, eps, save_stats=False)
             qkv = ops.gemm(ln1, lp.qkv_w, ops.LAYOUT_NT, bias=lp.qkv_b)
         attn = ops.attention_varlen_causal_fwd(qkv, cu, max_S, H, last_only=True)
-        rows = _pruned_tail_f32(attn, ops.gather_rows_at(x, last_rows), lp, eps)
+        rows = _pruned_tail_f32(attn, ops.gather_rows_at(x, last_rows), lp, eps, hidden_act(t))
     else:
         k, pre = _OPS16[torch.bfloat16 if mode == "bf16" else torch.float16], f"t{li}."
         ln1 = k.layernorm(x, lp.ln1_w, lp.ln1_b, eps)
@@ -2112,7 +2188,7 @@ def text_fwd_frozen_packed(p: TextParams, input_ids: torch.Tensor, tables: dict,
             ctx16 = k.cast(ops.attention_varlen_causal_fwd(qkv, cu, max_S, H, last_only=True))
         x1 = k.gemm(ctx16, _w16(cache, pre + "out", lp.out_w, k.cast), bias=lp.out_b, residual=ops.gather_rows_at(x, last_rows))
         ln2 = k.layernorm(x1, lp.ln2_w, lp.ln2_b, eps)
-        g = k.gemm(ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), bias=lp.fc1_b, gelu=True, out16=True)
+        g = _fc1_act16(k, ln2, _w16(cache, pre + "fc1", lp.fc1_w, k.cast), lp.fc1_b, hidden_act(t))
         rows = k.gemm(g, _w16(cache, pre + "fc2", lp.fc2_w, k.cast), bias=lp.fc2_b, residual=x1)
     return _text_head(rows, p, eps)[0]
 
@@ -2156,7 +2232,7 @@ def text_fwd_packed(p: TextParams, input_ids: torch.Tensor, tables: dict, cfg, s
     plan, keep = _text_train_split16(p, cfg, save, split16_cache, split16_out)
     for li, lp in enumerate(p.layers):
         x, sv = layer_fwd(x, lp, input_ids.shape[0], max_S, H, True, eps, save, plan[li] if plan is not None else None, keep,
-                          varlen=(cu, max_S))
+                          varlen=(cu, max_S), act=hidden_act(t))
         saved_layers.append(sv)
     rows = ops.gather_rows_at(x, last_rows)
     out, pooled, mp, rp = _text_head(rows, p, eps, save)
@@ -2179,7 +2255,7 @@ def text_bwd_packed(p: TextParams, saved, d_out: torch.Tensor, cfg, need: List[b
         return [grads[n] for n in names]
     dx = ops.scatter_last_rows(drows, cu, Tp)
     dx = _layers_bwd(dx, p.layers, saved_layers, needd, grads, lowest, Tp, N, max_S, t.num_attention_heads, True, t.layer_norm_eps,
-                     split16, varlen=(cu, max_S))
+                     split16, varlen=(cu, max_S), act=hidden_act(t))
     if lowest < 0:
         dpos = torch.zeros_like(p.pos) if needd["pos"] else None
         dtok = torch.zeros_like(p.tok) if needd["tok"] else None

@@ -1360,6 +1360,42 @@ def quick_gelu(h: torch.Tensor) -> torch.Tensor:
     return g
 
 
+_GELU_ERF = {torch.float32: "dclip_gelu_erf_f32", torch.bfloat16: "dclip_gelu_erf_bf16", torch.float16: "dclip_gelu_erf_f16"}
+
+
+def _same(t: torch.Tensor, like: torch.Tensor, name: str) -> torch.Tensor:
+    if not (t.is_cuda and t.device == like.device and t.dtype == like.dtype and t.is_contiguous() and t.shape == like.shape):
+        raise ValueError(f"{name}: expected a contiguous {like.dtype} tensor of shape {tuple(like.shape)} on {like.device}, got "
+                         f"{t.dtype} {tuple(t.shape)} {t.device} contiguous={t.is_contiguous()}")
+    return t
+
+
+def gelu_erf(h: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact GELU h Phi(h) of a contiguous fp32, bf16 or fp16 tensor of any size (hidden_act="gelu"): fp32
+    arithmetic; a 16-bit result is the activation of the stored 16-bit value, rounded to nearest even.  `out`: where it goes — a
+    tensor like h, which may be h itself (in place); None: a new one."""
+    lib = _lib.load()
+    name = _GELU_ERF.get(h.dtype)
+    if name is None or not (h.is_cuda and h.is_contiguous()) or h.numel() == 0:
+        raise ValueError(f"gelu_erf: expected a non-empty contiguous fp32 / bf16 / fp16 CUDA tensor, got {h.dtype} {h.device} "
+                         f"{tuple(h.shape)} contiguous={h.is_contiguous()}")
+    g = torch.empty_like(h) if out is None else _same(out, h, "gelu_erf: out")
+    _lib.check(getattr(lib, name)(h.data_ptr(), g.data_ptr(), h.numel(), _stream()), name[6:])
+    return g
+
+
+def gelu_erf_bwd(h: torch.Tensor, dg: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dh = dg gelu'(h), gelu'(h) = Phi(h) + h phi(h), of contiguous fp32 tensors of one shape (the backward of gelu_erf).
+    `out`: a tensor like dg, which may be dg itself (in place); None: a new one."""
+    lib = _lib.load()
+    if _f32(h, "h").numel() == 0:
+        raise ValueError("gelu_erf_bwd: empty tensor")
+    _same(dg, h, "gelu_erf_bwd: dg")
+    dh = torch.empty_like(dg) if out is None else _same(out, h, "gelu_erf_bwd: out")
+    _lib.check(lib.dclip_gelu_erf_bwd_f32(h.data_ptr(), dg.data_ptr(), dh.data_ptr(), h.numel(), _stream()), "gelu_erf_bwd_f32")
+    return dh
+
+
 def gemm_f16_dev(a: torch.Tensor, w: torch.Tensor, alpha_ptr: int, *, bias: Optional[torch.Tensor] = None,
                  residual: Optional[torch.Tensor] = None, gelu: bool = False, out_f16: bool = False,
                  split_out_scale_ptr: Optional[int] = None, h32: Optional[torch.Tensor] = None,

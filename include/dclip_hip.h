@@ -907,6 +907,21 @@ int dclip_amp_update_scale(float* scale, int* growth_tracker, const float* found
 int dclip_axpby(const float* x, float* y, float a, float b, size_t n, void* stream); /* y = a*x + b*y */
 int dclip_fill(float* y, float v, size_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact (erf) GELU for hidden_act = "gelu" towers: stand-alone element-wise passes behind a bias-only fc1 GEMM;
+ * every GEMM epilogue stays quick-GELU.  gelu(h) = h Phi(h) with Phi(h) = 0.5 (1 + erf(h / sqrt 2)), evaluated as 0.5 erfc(-h /
+ * sqrt 2) for h < 0; gelu'(h) = Phi(h) + h phi(h), phi(h) = exp(-h^2 / 2) / sqrt(2 pi).  All arithmetic fp32; finite inputs only.
+ * Any n >= 1 (16-byte vector body, scalar tail, size_t indexing: n may exceed 2^32); every pointer 16-byte aligned.
+ *   gelu_erf_f32            g[i] = gelu(h[i]); g may be h.
+ *   gelu_erf_bf16 / _f16    the same of n 16-bit values: gelu of the stored 16-bit value in fp32, rounded to nearest even (fp16:
+ *                           IEEE, no saturation — |gelu(h)| <= |h|); g may be h.
+ *   gelu_erf_bwd_f32        dh[i] = dg[i] gelu'(h[i]); dh may be dg.
+ */
+int dclip_gelu_erf_f32(const float* h, float* g, size_t n, void* stream);
+int dclip_gelu_erf_bf16(const void* h, void* g, size_t n, void* stream);
+int dclip_gelu_erf_f16(const void* h, void* g, size_t n, void* stream);
+int dclip_gelu_erf_bwd_f32(const float* h, const float* dg, float* dh, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
