@@ -184,6 +184,14 @@ SIGNATURES = {
     "dclip_split_f32_f16x2_rows_cols_stats": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "dclip_gemm_f16x3_scaled_split2": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, F, P]),
     "dclip_gemm_f16x3_scaled_split2_dev": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P, P]),
+    "dclip_im2col_f16x2": (I, [P, P, I, I, I, I, I, F, P, P]),
+    "dclip_split16_front_rec_floats": (I, []),
+    "dclip_split16_front_wrec_floats": (I, []),
+    "dclip_split16_front_workspace": (Z, []),
+    "dclip_split16_front": (I, [P, Z, P, I, I, P, P, P, P, Z, I, P]),
+    "dclip_split_f32_f16x2_cols_workspace": (Z, [I, I]),
+    "dclip_split_f32_f16x2_cols": (I, [P, P, P, P, I, I, I, P, Z, P]),
+    "dclip_split16_patch_plan": (I, [I, I, I]),
     "dclip_gemm_f16_wgrad_tokmajor_seg3_plan": (I, [I, I, I]),
     "dclip_gemm_f16_wgrad_tokmajor_seg3": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, Z, P]),
     "dclip_gemm_f16_ex": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),

@@ -47,6 +47,37 @@ __global__ void __launch_bounds__(256) im2col_vec_kernel(const float* __restrict
   }
 }
 
+// im2col_vec_kernel's gather with the split-fp16 operand of the student's patch embedding as its output: a thread
+// moves 8 consecutive px (patch % 8 == 0) — two 16-byte loads, two 16-byte stores — and writes cols[row] = [hi | lo] of
+// pixel * scale, fp16 [rows][2 kdim]: dclip_split_f32_f16x2's arithmetic on what dclip_im2col would have stored, element for
+// element.  The fp32 columns never exist.  The scale is the device float scale_p when given.
+typedef unsigned short u16x8_e __attribute__((ext_vector_type(8)));
+__global__ void __launch_bounds__(256) im2col_f16x2_kernel(const float* __restrict__ pix, unsigned short* __restrict__ cols, int B,
+                                                           int C, int Himg, int Wimg, int p, int g, float scale_v,
+                                                           const float* __restrict__ scale_p, size_t total8) {
+  const float scale = scale_p ? *scale_p : scale_v;
+  const int kdim = C * p * p, kdim8 = kdim / 8, p8 = p / 8;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total8; i += (size_t)gridDim.x * blockDim.x) {
+    const int k8 = (int)(i % kdim8);
+    const size_t row = i / kdim8;
+    const int gx = (int)(row % g), gy = (int)((row / g) % g), b = (int)(row / ((size_t)g * g));
+    const int px = (k8 % p8) * 8, py = (k8 / p8) % p, c = k8 / (p8 * p);
+    const float* src = pix + (((size_t)b * C + c) * Himg + gy * p + py) * Wimg + gx * p + px;
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
+    u16x8_e hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      unsigned short h0, l0, h1, l1;
+      split1(v0[e] * scale, h0, l0);
+      split1(v1[e] * scale, h1, l1);
+      hi[e] = h0, lo[e] = l0, hi[4 + e] = h1, lo[4 + e] = l1;
+    }
+    unsigned short* dst = cols + row * 2 * kdim + (size_t)k8 * 8;
+    *reinterpret_cast<u16x8_e*>(dst) = hi;
+    *reinterpret_cast<u16x8_e*>(dst + kdim) = lo;
+  }
+}
+
 __global__ void __launch_bounds__(256) vision_assemble_fwd_kernel(const float* __restrict__ patch, const float* __restrict__ cls,
                                                                   const float* __restrict__ pos, float* __restrict__ x, int B,
                                                                   int S, int D4, size_t total4) {
@@ -269,6 +300,22 @@ DCLIP_API int dclip_im2col_bf16(const float* pixels, void* cols, int B, int C, i
 DCLIP_API int dclip_im2col_f16(const float* pixels, void* cols, int B, int C, int Himg, int Wimg, int patch, int ldc,
                                void* stream) {
   return im2col16<F16T>("im2col_f16", pixels, cols, B, C, Himg, Wimg, patch, ldc, stream);
+}
+
+DCLIP_API int dclip_im2col_f16x2(const float* pixels, void* cols, int B, int C, int Himg, int Wimg, int patch, float scale,
+                                 const float* scale_dev, void* stream) {
+  DCLIP_REQUIRE(pixels && cols, "im2col_f16x2: null pointer");
+  DCLIP_REQUIRE(B > 0 && C > 0 && patch > 0 && patch % 8 == 0 && Himg == Wimg && Himg % patch == 0,
+                "im2col_f16x2: bad shape %dx%d patch %d (patch must be a multiple of 8)", Himg, Wimg, patch);
+  DCLIP_REQUIRE(((uintptr_t)pixels | (uintptr_t)cols) % 16 == 0 && (uintptr_t)scale_dev % 4 == 0, "im2col_f16x2: alignment");
+  DCLIP_REQUIRE(scale_dev || (scale > 0.f && scale - scale == 0.f && (__builtin_bit_cast(unsigned int, scale) & 0x007fffffu) == 0),
+                "im2col_f16x2: scale must be a power of two");
+  const int g = Himg / patch;
+  const size_t total8 = (size_t)B * g * g * C * patch * patch / 8;
+  hipLaunchKernelGGL(im2col_f16x2_kernel, dim3(grid_for(total8)), dim3(256), 0, (hipStream_t)stream, pixels, (unsigned short*)cols,
+                     B, C, Himg, Wimg, patch, g, scale_dev ? 1.f : scale, scale_dev, total8);
+  DCLIP_CHECK_LAUNCH("im2col_f16x2");
+  return DCLIP_OK;
 }
 
 DCLIP_API int dclip_vision_assemble_fwd(const float* patch, const float* cls, const float* pos, float* x, int B, int S, int D,

@@ -1772,6 +1772,15 @@ DCLIP_API int dclip_gemm_f16x3_plan(int M, int N, int K) {
   return (long)cdiv(M, 256) * cdiv(N, 256) >= tiles_min ? 1 : 0;
 }
 
+// Where the student's patch embedding [rows, K] x [D, K] takes the fused entry on split operands: where the plan
+// above holds AND the call has at least DCLIP_PATCH_SPLIT16_MIN tiles (default 128; read per call).  A threshold of its own, so
+// that lowering the two above moves the encoder layers' GEMMs onto their fused entries and leaves the patch embedding where it was.
+DCLIP_API int dclip_split16_patch_plan(int rows, int D, int K) {
+  if (dclip_gemm_f16x3_plan(rows, D, K) == 0) return 0;
+  const int tiles_min = getenv("DCLIP_PATCH_SPLIT16_MIN") ? atoi(getenv("DCLIP_PATCH_SPLIT16_MIN")) : 128;
+  return (long)cdiv(rows, 256) * cdiv(D, 256) >= tiles_min ? 1 : 0;
+}
+
 // The tile height a fused fp32-output call of this shape takes now (192 or 256): rows_form = the row-scaled entry, stats_form = its
 // statistics twin (always 256).  Split-output and 16-bit-output calls always take 256.
 DCLIP_API int dclip_gemm_f16x3_tile_rows(int M, int N, int K, int rows_form, int stats_form) {

@@ -1133,6 +1133,221 @@ DCLIP_API int dclip_split16_weights(const void* refs, int nrefs, int tiles, cons
   return DCLIP_OK;
 }
 
+// ---- the front plan: the student's patch embedding on split operands.  Pixels have no bound derivable from a
+// weight, so the activation scale comes from the data: max|pixels| every call, max|patch_w| when the weight changed, both as
+// maxima of the bit patterns of |x| (NaN above inf) — block partials, then one workgroup that folds them and applies the rules
+// of split16_plan_kernel (act_exp / weight_exp in double, the same clamps and flag bits).  No atomics; a maximum does not depend
+// on the order of its operands, so every run gives the same bits.
+//   wrec  float [4], kept by the caller between calls: 2^f | f (an int) | max|patch_w| | the weight's flag bits
+//   rec   float [8], one per forward: 2^e | 2^f | alpha = 2^-(e+f) | flags | max|pixels| | max|patch_w| | e | f (ints)
+namespace {
+constexpr int FRONT_REC_FLOATS = 8, FRONT_WREC_FLOATS = 4, FRONT_PIX_BLOCKS = 1024, FRONT_W_BLOCKS = 64;
+
+// blocks [0, FRONT_PIX_BLOCKS) fold the pixels, the others (if any) the weight; one partial per block
+__global__ void __launch_bounds__(256) front_absmax_kernel(const float* __restrict__ pix, size_t npix, const float* __restrict__ w,
+                                                           size_t nw, unsigned* __restrict__ partial) {
+  __shared__ unsigned sm[4];
+  const bool is_w = blockIdx.x >= FRONT_PIX_BLOCKS;
+  const float* x = is_w ? w : pix;
+  const size_t n = is_w ? nw : npix, n4 = n / 4;
+  const size_t blk = is_w ? blockIdx.x - FRONT_PIX_BLOCKS : blockIdx.x, nblk = is_w ? FRONT_W_BLOCKS : FRONT_PIX_BLOCKS;
+  unsigned m = 0u;
+  for (size_t i = blk * 256 + threadIdx.x; i < n4; i += nblk * 256) {
+    const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float f = v[e];
+      const unsigned u = __builtin_bit_cast(unsigned, f) & 0x7fffffffu;
+      m = m > u ? m : u;
+    }
+  }
+  if (blk == 0 && n4 * 4 + threadIdx.x < n) {          // up to three values past the last whole group of four
+    const unsigned u = __builtin_bit_cast(unsigned, x[n4 * 4 + threadIdx.x]) & 0x7fffffffu;
+    m = m > u ? m : u;
+  }
+  m = wave_umax(m);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 4; ++k) m = m > sm[k] ? m : sm[k];
+    partial[blockIdx.x] = m;
+  }
+}
+
+__device__ __forceinline__ unsigned block_umax(unsigned m, unsigned* sm) {      // the result in thread 0
+  m = wave_umax(m);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int k = 1; k < 4; ++k) m = m > sm[k] ? m : sm[k];
+  return m;
+}
+
+__global__ void __launch_bounds__(256) front_plan_kernel(const unsigned* __restrict__ partial, int have_w, float* __restrict__ wrec,
+                                                         float* __restrict__ rec) {
+  __shared__ unsigned sm[4];
+  unsigned mp = 0u, mw = 0u;
+  for (int i = threadIdx.x; i < FRONT_PIX_BLOCKS; i += 256) mp = mp > partial[i] ? mp : partial[i];
+  mp = block_umax(mp, sm);
+  if (have_w) {
+    if (threadIdx.x < FRONT_W_BLOCKS) mw = partial[FRONT_PIX_BLOCKS + threadIdx.x];
+    mw = block_umax(mw, sm);
+  }
+  if (threadIdx.x != 0) return;
+  int f;
+  unsigned wflags;
+  float wmax;
+  if (have_w) {
+    wflags = 0u;
+    wmax = __builtin_bit_cast(float, mw);
+    f = weight_exp((double)wmax, wflags);
+    if (f > 127) f = 127, wflags |= 4u;
+    wrec[0] = pow2f(f);
+    wrec[1] = __builtin_bit_cast(float, f);
+    wrec[2] = wmax;
+    wrec[3] = __builtin_bit_cast(float, wflags);
+  } else {
+    f = __builtin_bit_cast(int, wrec[1]);
+    wmax = wrec[2];
+    wflags = __builtin_bit_cast(unsigned, wrec[3]);
+  }
+  unsigned flags = wflags;
+  const float pmax = __builtin_bit_cast(float, mp);
+  int e = act_exp((double)pmax, flags);
+  if (e < -126) e = -126, flags |= 4u;
+  if (-(e + f) > 127 || -(e + f) < -126) flags |= 4u;
+  rec[0] = pow2f(e);
+  rec[1] = pow2f(f);
+  rec[2] = pow2f(-(e + f));
+  rec[3] = __builtin_bit_cast(float, flags);
+  rec[4] = pmax;
+  rec[5] = wmax;
+  rec[6] = __builtin_bit_cast(float, e);
+  rec[7] = __builtin_bit_cast(float, f);
+}
+}  // namespace
+
+DCLIP_API int dclip_split16_front_rec_floats(void) { return FRONT_REC_FLOATS; }
+DCLIP_API int dclip_split16_front_wrec_floats(void) { return FRONT_WREC_FLOATS; }
+DCLIP_API size_t dclip_split16_front_workspace(void) { return (size_t)(FRONT_PIX_BLOCKS + FRONT_W_BLOCKS) * sizeof(unsigned); }
+
+// Two launches (the maxima, the plan), three with `refresh_w`: the weight's maximum is then taken too and w3 fp16 [wrows][3 wcols]
+// receives [hi|hi|lo] of w 2^f — split_f16x3_kernel<1> with the scale read from wrec, bit-equal to dclip_split_f32_f16x3(order 1)
+// at that scale.  Without `refresh_w` wrec is read as the last such call left it, and w / w3 are not touched.
+DCLIP_API int dclip_split16_front(const float* pixels, size_t npix, const float* w, int wrows, int wcols, void* w3, float* wrec,
+                                  float* rec, void* workspace, size_t workspace_bytes, int refresh_w, void* stream) {
+  dclip_note_first_launch("", "");
+  DCLIP_REQUIRE(pixels && npix > 0 && wrec && rec, "split16_front: bad arguments");
+  DCLIP_REQUIRE(!refresh_w || (w && w3 && wrows > 0 && wcols > 0 && wcols % 8 == 0), "split16_front: weight [rows][cols % 8 == 0]");
+  DCLIP_REQUIRE(((uintptr_t)pixels | (uintptr_t)workspace) % 16 == 0 && ((uintptr_t)wrec | (uintptr_t)rec) % 4 == 0 &&
+                    (!refresh_w || ((uintptr_t)w | (uintptr_t)w3) % 16 == 0),
+                "split16_front: alignment");
+  if (!workspace || workspace_bytes < dclip_split16_front_workspace()) {
+    dclip_set_error("split16_front: needs %zu workspace bytes, got %zu", dclip_split16_front_workspace(), workspace_bytes);
+    return DCLIP_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t nw = refresh_w ? (size_t)wrows * wcols : 0;
+  hipLaunchKernelGGL(front_absmax_kernel, dim3(FRONT_PIX_BLOCKS + (refresh_w ? FRONT_W_BLOCKS : 0)), dim3(256), 0, st, pixels, npix,
+                     refresh_w ? w : nullptr, nw, (unsigned*)workspace);
+  DCLIP_CHECK_LAUNCH_V("split16_front", ".max");
+  dclip_note_first_launch("split16_front", ".max");
+  hipLaunchKernelGGL(front_plan_kernel, dim3(1), dim3(256), 0, st, (const unsigned*)workspace, refresh_w ? 1 : 0, wrec, rec);
+  DCLIP_CHECK_LAUNCH_V("split16_front", ".plan");
+  if (!refresh_w) return DCLIP_OK;
+  return split_launch("split16_front", w, w3, wrows, wcols, wcols, 3 * wcols, 1.f, wrec, 1, stream);
+}
+
+// ---- the column-only split of a dY whose weight gradient has no data gradient beside it (the patch embedding's, DESIGN.md
+// §35): col_exp, col_alpha and yc of dclip_split_f32_f16x2_rows_colstats on the same x, bit for bit — a column maximum does not
+// depend on how the rows were grouped — without the row pieces, row_alpha and db.  Three launches: the column maxima of row
+// strips (one partial row per workgroup, no atomics), their fold, then split_cols_f16x2_kernel as it is.
+namespace {
+constexpr int COLMAX_MAX_BLOCKS = 1024, COLMAX_ROWS_PER_BLOCK = 8;
+inline int colmax_blocks(int rows) {
+  const int b = cdiv(rows, COLMAX_ROWS_PER_BLOCK);
+  return b < COLMAX_MAX_BLOCKS ? b : COLMAX_MAX_BLOCKS;
+}
+
+// workgroup b folds rows b, b + gridDim.x, ...; a thread owns 4 columns at a time (a wave reads 1 KiB of a row per instruction)
+__global__ void __launch_bounds__(256) colmax_partial_kernel(const float* __restrict__ x, unsigned* __restrict__ pmax, int rows,
+                                                             int cols, int ldx) {
+  const int c4n = cols >> 2;
+  for (int c4 = threadIdx.x; c4 < c4n; c4 += 256) {
+    unsigned m[4] = {0u, 0u, 0u, 0u};
+    for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(x + (size_t)r * ldx + c4 * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float f = v[e];
+        const unsigned u = __builtin_bit_cast(unsigned, f) & 0x7fffffffu;
+        m[e] = m[e] > u ? m[e] : u;
+      }
+    }
+    *reinterpret_cast<u32x4s*>(pmax + (size_t)blockIdx.x * cols + c4 * 4) = u32x4s{m[0], m[1], m[2], m[3]};
+  }
+}
+
+// colstats_finish_kernel's fold of the maxima alone: 8 columns x 32 groups of partial rows per workgroup
+__global__ void __launch_bounds__(256) colmax_finish_kernel(const unsigned* __restrict__ pmax, int* __restrict__ col_exp,
+                                                            float* __restrict__ col_alpha, int nb, int cols) {
+  __shared__ unsigned smax[FIN_GROUPS][FIN_COLS];
+  const int cl = threadIdx.x % FIN_COLS, g = threadIdx.x / FIN_COLS;
+  const int col = blockIdx.x * FIN_COLS + cl;
+  unsigned m = 0u;
+  if (col < cols) {
+#pragma unroll 4
+    for (int b = g; b < nb; b += FIN_GROUPS) {
+      const unsigned pm = pmax[(size_t)b * cols + col];
+      m = m > pm ? m : pm;
+    }
+  }
+  smax[g][cl] = m;
+  __syncthreads();
+  if (g == 0 && col < cols) {
+    for (int k = 1; k < FIN_GROUPS; ++k) m = m > smax[k][cl] ? m : smax[k][cl];
+    const int e = row_exp(m);
+    col_exp[col] = e;
+    col_alpha[col] = pow2f(-e);
+  }
+}
+}  // namespace
+
+DCLIP_API size_t dclip_split_f32_f16x2_cols_workspace(int rows, int cols) {
+  if (rows <= 0 || cols <= 0) return 0;
+  return (size_t)colmax_blocks(rows) * cols * sizeof(unsigned);
+}
+
+DCLIP_API int dclip_split_f32_f16x2_cols(const float* x, void* yc, int* col_exp, float* col_alpha, int rows, int cols, int ldx,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  const char* name = "split_f32_f16x2_cols";
+  dclip_note_first_launch("", "");
+  DCLIP_REQUIRE(x && yc && col_exp && col_alpha && rows > 0 && cols > 0, "%s: bad arguments", name);
+  DCLIP_REQUIRE(cols % 8 == 0, "%s: cols=%d must be a multiple of 8", name, cols);
+  DCLIP_REQUIRE(ldx >= cols && ldx % 4 == 0, "%s: ldx must be a multiple of 4 and >= cols", name);
+  DCLIP_REQUIRE(((uintptr_t)x | (uintptr_t)yc | (uintptr_t)col_exp | (uintptr_t)workspace) % 16 == 0 && (uintptr_t)col_alpha % 4 == 0,
+                "%s: alignment", name);
+  const size_t need = dclip_split_f32_f16x2_cols_workspace(rows, cols);
+  if (!workspace || workspace_bytes < need) {
+    dclip_set_error("%s: needs %zu workspace bytes, got %zu", name, need, workspace_bytes);
+    return DCLIP_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = colmax_blocks(rows);
+  hipLaunchKernelGGL(colmax_partial_kernel, dim3(nb), dim3(256), 0, st, x, (unsigned*)workspace, rows, cols, ldx);
+  DCLIP_CHECK_LAUNCH_V(name, ".max");
+  dclip_note_first_launch(name, ".max");
+  hipLaunchKernelGGL(colmax_finish_kernel, dim3(cdiv(cols, FIN_COLS)), dim3(256), 0, st, (const unsigned*)workspace, col_exp, col_alpha,
+                     nb, cols);
+  DCLIP_CHECK_LAUNCH_V(name, ".finish");
+  const size_t blocks = ((size_t)rows * (cols / 8) + 255) / 256;
+  hipLaunchKernelGGL(split_cols_f16x2_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, st, x, (const int*)col_exp,
+                     (unsigned short*)yc, rows, cols, ldx);
+  DCLIP_CHECK_LAUNCH_V(name, ".cols");
+  return DCLIP_OK;
+}
+
 // dclip_split16_weights that also writes, in the same launch and from the same plan scale, the TRANSPOSED copies: dst_t is a
 // device array of nrefs pointers, entry i = fp16 [cols][3 rows] for record i ([hi|hi|lo] of (src scale)^T, bit-equal to
 // dclip_split_f32_f16x3 of the transposed weight) or null; records with one need rows % 8 == 0 (the caller's check).

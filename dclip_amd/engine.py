@@ -311,6 +311,34 @@ def _split_wgrad_taken(need_w: bool, sp: Optional[Split16Layer], x3, out_f: int,
                 ops.gemm_f16_wgrad_tokmajor_seg3_plan(out_f, in_f, tokens) > 0)
 
 
+def patch_split16_taken(save_with_cache: bool, grid, rows: int, D: int, patch_dim: int, backward: bool = False,
+                        on: Optional[bool] = None, plan=None, wplan=None) -> bool:
+    """Whether a vision forward runs its patch embedding [rows, patch_dim] x [D, patch_dim] on split-fp16 operands,
+    and with `backward` whether its backward may take patch_w's gradient from the same operands.  All of: the switches
+    (DCLIP_VISION_SPLIT16_PATCH under DCLIP_VISION_SPLIT16; for the backward half DCLIP_VISION_SPLIT16_BWD and _WGRAD too), a
+    forward that saves for a backward with the model's split cache (`save_with_cache`), the configuration's square grid (`grid`
+    None), patch_dim % 32 == 0 (ViT-L/14's 588 declines), rows % 64 == 0 and the plans: ops.split16_patch_plan (the fused K-major
+    entry's plan and a tile threshold of its own) and, for the backward half, ops.gemm_f16x3_wgrad_tokmajor_plan.  A pure function
+    of the shapes and the switches (`on`, `plan`, `wplan`: stand-ins for the switches and the two plans)."""
+    if on is None:
+        on = _VSPLIT16 and _VSPLIT16_PATCH and (not backward or (_VSPLIT16_BWD and _VSPLIT16_WGRAD))
+    if not (on and save_with_cache and grid is None and rows > 0 and patch_dim % 32 == 0 and rows % 64 == 0):
+        return False
+    if (ops.split16_patch_plan if plan is None else plan)(rows, D, patch_dim) <= 0:
+        return False
+    return not backward or (ops.gemm_f16x3_wgrad_tokmajor_plan if wplan is None else wplan)(D, patch_dim, rows) > 0
+
+
+class _PatchSplit:
+    """What a forward that took the split patch embedding saves in place of the fp32 columns: the fp16 [hi|lo]
+    columns (the same bytes; None where the backward half is not on), the forward's own front record (their scale lives in it) and
+    the pixels with the patch size, from which the fp32 columns are made again on the path that needs them."""
+    __slots__ = ("cols16", "rec", "pixels", "patch")
+
+    def __init__(self, cols16, rec, pixels, patch: int):
+        self.cols16, self.rec, self.pixels, self.patch = cols16, rec, pixels, patch
+
+
 def _dystats_regime(tokens: int, D: int, I: int) -> bool:
     """Whether a tower's backward asks its producers of dY for column partials at all: the switch is on and the
     step is large enough for its data-gradient GEMMs to run on the ping-pong kernel (fc2's, [tokens, 3 D] x [I, 3 D], stands for
@@ -571,18 +599,23 @@ def vision_fwd(p: VisionParams, pixel_values: torch.Tensor, cfg, save: bool, hid
     """get_image_features: [B,3,H,W] -> [B,P]  (hf:modeling_clip.py:202-218, :641-651, :744-751).  `grid` = (gh, gw): run on
     that patch grid with the position table resampled to it (None: the configuration's image size, as ever).
     `split16_cache` (the model's, HipCLIPModel._vsplit16_cache): a forward that saves for the backward runs the encoder
-    layers' full-size GEMMs on split-fp16 operands (DCLIP_VISION_SPLIT16); a no-grad forward never does.
+    layers' full-size GEMMs on split-fp16 operands (DCLIP_VISION_SPLIT16) and, where patch_split16_taken says so,
+    the patch embedding too (§35: the saved columns are then a _PatchSplit); a no-grad forward never does.
     `split16_out` (a list): receives what vision_bwd needs to run its data-gradient GEMMs on the same plan (Split16Bwd, §9e)
     when this forward took the split path and DCLIP_VISION_SPLIT16_BWD is on; nothing otherwise."""
     v = cfg
     B = pixel_values.shape[0]
     S, D, H = _grid_seq(v, grid), v.hidden_size, v.num_attention_heads
-    if grid is None:
-        cols, pos = ops.im2col(pixel_values, v.patch_size), p.pos
+    front = _patch_split16_front(p, pixel_values, v, save, grid, split16_cache)
+    if front is not None:                # the patch embedding on split-fp16 operands (DESIGN.md §35): no fp32 columns
+        cols, patch, pos = *_patch_split16_fwd(p, pixel_values, v, *front), p.pos
     else:
-        pos = _grid_front(p, pixel_values, v, grid)
-        cols = ops.im2col_rect(pixel_values, v.patch_size)
-    patch = ops.gemm(cols, p.patch_w.view(D, -1), ops.LAYOUT_NT)
+        if grid is None:
+            cols, pos = ops.im2col(pixel_values, v.patch_size), p.pos
+        else:
+            pos = _grid_front(p, pixel_values, v, grid)
+            cols = ops.im2col_rect(pixel_values, v.patch_size)
+        patch = ops.gemm(cols, p.patch_w.view(D, -1), ops.LAYOUT_NT)
     emb = ops.vision_assemble_fwd(patch, p.class_embedding, pos, B, S, D)
     del patch
     x, m0, r0 = ops.layernorm_fwd(emb, p.pre_w, p.pre_b, v.layer_norm_eps, save_stats=save)
@@ -676,11 +709,30 @@ def _vision_tail_bwd(p: VisionParams, d_out, cls_tok, mp, rp, pooled, needd: Dic
     return dcls
 
 
+def _patch_split16_wgrad(ps: _PatchSplit, dpatch: torch.Tensor, pw: torch.Tensor, split16) -> torch.Tensor:
+    """patch_w's gradient [D, patch_dim] into `pw` for a forward that took the split patch embedding: the
+    column-only split of dpatch, then fc2's fused token-major weight-gradient call on it and the saved [hi|lo] columns, whose
+    scale is the forward's own record.  Where the backward cannot take it after all — a switch flipped since the forward, no
+    Split16Bwd or one that is no longer fresh — the fp32 columns are made again from the saved pixels (the _Remat pattern of
+    §9j) and the gradient is the plain fp32 GEMM."""
+    D, K = pw.shape
+    if (ps.cols16 is not None and split16 is not None and
+            patch_split16_taken(True, None, dpatch.shape[0], D, K, backward=True) and split16.fresh()):
+        yc, _, col_alpha = ops.split_f16x2_cols(dpatch)
+        got = ops.gemm_f16x3_wgrad_tokmajor(yc, ps.cols16, D, K, col_alpha, ps.rec.data_ptr() + 4 * ops.FRONT_SCALE, out=pw)
+        if got is None:
+            raise RuntimeError("patch-embedding weight gradient: the fused token-major kernel refused a shape its plan accepted")
+        return got
+    return ops.gemm(dpatch, ops.im2col(ps.pixels, ps.patch), ops.LAYOUT_TN, out=pw)
+
+
 def _vision_head_bwd(p: VisionParams, dx, emb, m0, r0, cols, B: int, S: int, v, grid, needd: Dict[str, bool], grads, alloc, on_ready,
-                     k16=None):
+                     k16=None, split16=None):
     """Below layer 0: the pre-LayerNorm backward, the gradients of pos / class_embedding (a column sum of demb; on another
     `grid` the transpose of the resample, _grid_pos_grad) and of patch_w; the head group is reported to `on_ready`.  `k16` (the
-    _Train16 of a 16-bit forward): columns saved in that type give patch_w's gradient on its token-major split-K kernel."""
+    _Train16 of a 16-bit forward): columns saved in that type give patch_w's gradient on its token-major split-K kernel.
+    `split16` (vision_bwd's): a forward that took the split patch embedding (`cols` is a _PatchSplit) gets patch_w's gradient
+    from its split columns while that Split16Bwd is fresh."""
     D, dev = v.hidden_size, dx.device
     demb, _ = _ln_bwd(dx, emb, p.pre_w, m0, r0, None, bool(needd["pre_w"] or needd["pre_b"]), grads, "pre_w", "pre_b", alloc)
     if needd["pos"] or needd["class_embedding"]:
@@ -695,7 +747,9 @@ def _vision_head_bwd(p: VisionParams, dx, emb, m0, r0, cols, B: int, S: int, v, 
     if needd["patch_w"]:
         dpatch = ops.vision_assemble_bwd(demb, B, S, D)
         pw = _galloc(alloc, "patch_w", (D, p.patch_w.numel() // D), dev)
-        if cols.dtype != torch.float32:           # token-major split-K weight gradient from the saved 16-bit columns
+        if isinstance(cols, _PatchSplit):         # the forward took the split patch embedding
+            grads["patch_w"] = _patch_split16_wgrad(cols, dpatch, pw, split16).view_as(p.patch_w)
+        elif cols.dtype != torch.float32:         # token-major split-K weight gradient from the saved 16-bit columns
             got = k16.wgrad_tokmajor(k16.cast(dpatch), cols, out=pw)
             if got is None:
                 raise RuntimeError("patch-embedding weight gradient: the token-major 16-bit kernel refused a shape its plan accepted")
@@ -727,7 +781,7 @@ def vision_bwd(p: VisionParams, saved, d_out: torch.Tensor, cfg, need: List[bool
     dx = _layers_bwd(dx, p.layers, saved_layers, needd, grads, lowest, B * S, B, S, H, False, v.layer_norm_eps, split16,
                      alloc=alloc, on_ready=on_ready, dcls=dcls if pruned else None, act=hidden_act(v))
     if lowest < 0:
-        _vision_head_bwd(p, dx, emb, m0, r0, cols, B, S, v, grid, needd, grads, alloc, on_ready)
+        _vision_head_bwd(p, dx, emb, m0, r0, cols, B, S, v, grid, needd, grads, alloc, on_ready, split16=split16)
     return [grads[n] for n in names]
 
 
@@ -1750,6 +1804,11 @@ _VSPLIT16_WGRAD = os.environ.get("DCLIP_VISION_SPLIT16_WGRAD", "1") != "0"
 # ... and the kernels that produce those dY leave the column partials, so that dY is read once; 0 = the
 # three-launch pass of §9f for every dY, the parent's launch list and outputs bit for bit
 _VSPLIT16_DYSTATS = os.environ.get("DCLIP_VISION_SPLIT16_DYSTATS", "1") != "0"
+# The patch embedding and the gradient of its weight on split operands too: the activation scale from max|pixels|,
+# taken on the device every forward, im2col writing [hi|lo] directly, the GEMMs fc2's fused call forms.  The forward half under
+# DCLIP_VISION_SPLIT16, the weight-gradient half under _BWD and _WGRAD as well; 0 = ops.im2col and the two fp32 GEMMs, the
+# parent's launch list and outputs bit for bit.  Depends on no other switch (patch_split16_taken)
+_VSPLIT16_PATCH = os.environ.get("DCLIP_VISION_SPLIT16_PATCH", "1") != "0"
 # Every split GEMM above — both towers' forwards, the data and the weight gradients — on its fused twin, which stages the hi
 # pieces once, wherever that twin's plan takes the shape; 0 = the 3 K / three-segment entries everywhere, the
 # parent's launch list and outputs bit for bit.  "kmajor" / "tokmajor": one form alone (the A/B of §9h).
@@ -1888,6 +1947,100 @@ def vision_split16_check_flags(cache: Optional[dict]) -> None:
     ent = cache.get("__vsplit16__") if cache else None
     if ent is not None:
         _vision_split16_flags(ent)
+    ent = cache.get(_VPATCH16_KEY) if cache else None
+    if ent is not None:
+        _patch_split16_flags(ent)
+
+
+# The front plan of the split patch embedding lives BESIDE the layers' table, under a key of its own in the same
+# cache: what belongs to the weight (its record and [hi|hi|lo] copy, ops.split16_front_state) is kept there and made again when
+# patch_w's version or address moved — always while capturing; what belongs to the pixels is a record of its own per forward,
+# so that a backward finds the scale of ITS columns whatever forwards ran in between.
+_VPATCH16_KEY = "__vpatch16__"
+
+
+def split16_front_host(max_pixels: float, max_w: float) -> Dict[str, int]:
+    """What the device front plan (dclip_split16_front) makes of max|pixels| and max|patch_w|: e = split16_act_exp, f =
+    split16_weight_exp, a = -(e + f) and the flag bits of split16_plan_host (1: e < -14, 2: a non-finite maximum, 4: a scale
+    outside fp32's normal range, clamped).  The reference of tests/test_patch_split16_gpu.py."""
+    import math
+    flags = 0
+    if math.isfinite(max_w):
+        f = split16_weight_exp(max_w)
+    else:
+        flags, f = flags | 2, 0
+    if f > 127:
+        f, flags = 127, flags | 4
+    e = split16_act_exp(max_pixels)
+    if e is None:
+        if not math.isfinite(max_pixels) or max_pixels < 0.0:
+            flags, e = flags | 2, 0
+        else:
+            flags |= 1
+            m, ex = math.frexp(max_pixels)
+            e = _SPLIT16_TOP - (ex - 1 if m == 0.5 else ex)
+    if e < -126:
+        e, flags = -126, flags | 4
+    if not -126 <= -(e + f) <= 127:
+        flags |= 4
+    return {"e": e, "f": f, "a": max(-126, min(127, -(e + f))), "flags": flags}
+
+
+def _patch_split16_flags(ent: dict) -> None:
+    """_vision_split16_flags for the front record: the flags the LAST forward left in pinned memory, seen a step late."""
+    host = ent["host"]
+    if host is None:
+        return
+    flags = int(host[ops.FRONT_FLAGS:ops.FRONT_FLAGS + 1].view(torch.int32)[0])
+    if flags:
+        _split16_log_once(f"split-fp16 patch embedding: max|pixel_values| or max|patch_w| is non-finite, or the pixels need a scale "
+                          f"below 2^-14 (flags {flags}); the forward stays on the split path with that scale and may lose accuracy "
+                          "(DCLIP_VISION_SPLIT16_PATCH=0 selects the fp32 patch embedding)")
+
+
+def _patch_split16_front(p: "VisionParams", pixel_values: torch.Tensor, v, save: bool, grid, cache: Optional[dict]):
+    """(record, w3) of a forward that takes the split patch embedding — its front record (ops.split16_front, two launches, three
+    when patch_w changed or a stream is capturing) and the [hi|hi|lo] copy of patch_w — or None: the fp32 columns and GEMM, where
+    patch_split16_taken declines, the tower is a "gelu" one (it takes the plain path throughout) or the very first use arrives
+    inside a graph capture."""
+    D = v.hidden_size
+    K = p.patch_w.numel() // D
+    Bn, _, Hh, Ww = pixel_values.shape
+    if v.patch_size <= 0 or Hh != Ww or Hh % v.patch_size:
+        return None                                     # ops.im2col names the fault
+    rows = Bn * (Hh // v.patch_size) ** 2
+    if not patch_split16_taken(bool(save and cache is not None), grid, rows, D, K) or hidden_act(v) == GELU_ERF:
+        return None
+    w = p.patch_w.view(D, K)
+    capturing = torch.cuda.is_current_stream_capturing()
+    ent = cache.get(_VPATCH16_KEY)
+    if ent is None or ent["ptr"] != w.data_ptr() or tuple(ent["state"]["w3"].shape) != (D, 3 * K):
+        if capturing:
+            _split16_log_once("split-fp16 patch embedding: first use inside a graph capture; this capture takes the fp32 patch "
+                              "embedding (run one eager step first)")
+            return None
+        ent = {"ptr": w.data_ptr(), "version": None, "state": ops.split16_front_state(w), "host": None}
+        try:
+            ent["host"] = torch.zeros((8,), dtype=torch.float32).pin_memory()
+        except RuntimeError:
+            ent["host"] = None
+        cache[_VPATCH16_KEY] = ent
+    _patch_split16_flags(ent)
+    rec = ops.split16_front(pixel_values, w, ent["state"], capturing or ent["version"] != w._version)
+    ent["version"] = None if capturing else w._version
+    if ent["host"] is not None:
+        ent["host"].copy_(rec, non_blocking=True)
+    return rec, ent["state"]["w3"]
+
+
+def _patch_split16_fwd(p: "VisionParams", pixel_values: torch.Tensor, v, rec: torch.Tensor, w3: torch.Tensor):
+    """(what the backward keeps in place of the columns, patch [rows, D] fp32): im2col written as [hi|lo] of pixel 2^e, then fc2's
+    fused forward call on it and w3 with the record's alpha, no bias.  The columns are kept only where the backward half is on."""
+    base = rec.data_ptr()
+    cols16 = ops.im2col_f16x2(pixel_values, v.patch_size, scale_ptr=base + 4 * ops.FRONT_SCALE)
+    patch = ops.gemm_f16x3_dev(cols16, w3, base + 4 * ops.FRONT_ALPHA, pieces=2)
+    keep = patch_split16_taken(True, None, cols16.shape[0], w3.shape[0], w3.shape[1] // 3, backward=True)
+    return _PatchSplit(cols16 if keep else None, rec, pixel_values, v.patch_size), patch
 
 
 def _vision_split16_plan(layers: List[LayerParams], cfg, cache: dict, key: str = "__vsplit16__",

@@ -1845,6 +1845,80 @@ def gemm_f16x3_wgrad_tokmajor(dy: torch.Tensor, x: torch.Tensor, M: int, N: int,
     return out
 
 
+# ------------------------------------------------------------------------------------------- split-fp16 patch embedding
+# The operands of the student's patch embedding and of its weight gradient (include/dclip_hip.h, "the student's patch embedding"):
+# the GEMMs themselves are gemm_f16x3_dev and gemm_f16x3_wgrad_tokmajor above.
+
+FRONT_SCALE, FRONT_WSCALE, FRONT_ALPHA, FRONT_FLAGS, FRONT_PIX_MAX, FRONT_W_MAX, FRONT_E, FRONT_F = range(8)   # floats of a front record
+
+
+def split16_patch_plan(rows: int, D: int, K: int) -> int:
+    """1 where the step takes the split path for a patch embedding [rows, K] x [D, K] (gemm_f16x3_plan and a tile threshold of
+    its own, DCLIP_PATCH_SPLIT16_MIN), else 0."""
+    return int(_lib.load().dclip_split16_patch_plan(rows, D, K))
+
+
+def im2col_f16x2(pixels: torch.Tensor, patch: int, scale: float = 1.0, scale_ptr: Optional[int] = None) -> torch.Tensor:
+    """im2col written as the two-piece split: fp16 [B*g*g, 2 C p p] = [hi|lo] of pixel * scale (a power of two; `scale_ptr`: the
+    address of a device float instead), bit-equal to split_f16x3(im2col(pixels), scale, pieces=2) in one pass; patch % 8 == 0."""
+    lib = _lib.load()
+    _f32(pixels, "pixel_values")
+    B, Cc, Hh, Ww = pixels.shape
+    if patch <= 0 or Hh != Ww or Hh % patch or patch % 8:
+        raise ValueError(f"im2col_f16x2: image {Hh}x{Ww}, patch {patch} (a square image of whole patches, patch % 8 == 0)")
+    g = Hh // patch
+    cols = torch.empty((B * g * g, 2 * Cc * patch * patch), dtype=torch.float16, device=pixels.device)
+    _lib.check(lib.dclip_im2col_f16x2(pixels.data_ptr(), cols.data_ptr(), B, Cc, Hh, Ww, patch, float(scale), scale_ptr, _stream()),
+               "im2col_f16x2")
+    return cols
+
+
+def split16_front_state(w: torch.Tensor) -> dict:
+    """What split16_front keeps between calls for the weight w [D, K] (K % 8 == 0): the weight record and the [hi|hi|lo] copy."""
+    lib = _lib.load()
+    _f32(w, "w")
+    if w.dim() != 2 or w.shape[1] % 8:
+        raise ValueError("split16_front_state: w is [D, K] with K % 8 == 0")
+    return {"wrec": torch.zeros((lib.dclip_split16_front_wrec_floats(),), dtype=torch.float32, device=w.device),
+            "w3": torch.empty((w.shape[0], 3 * w.shape[1]), dtype=torch.float16, device=w.device)}
+
+
+def split16_front(pixels: torch.Tensor, w: torch.Tensor, state: dict, refresh_w: bool) -> torch.Tensor:
+    """The front plan of one forward -> its record, fp32 [8] on the device (FRONT_*): the scales 2^e from max|pixels| and 2^f from
+    max|w|, alpha = 2^-(e+f) and the guard flags.  `refresh_w`: w changed — its maximum, state["wrec"] and state["w3"] = [hi|hi|lo]
+    of w 2^f are made again; otherwise they are read as they stand.  Two launches, three with `refresh_w`; nothing is read back."""
+    lib = _lib.load()
+    _f32(pixels, "pixel_values"), _f32(w, "w")
+    rec = torch.empty((lib.dclip_split16_front_rec_floats(),), dtype=torch.float32, device=pixels.device)
+    w3 = state["w3"]
+    if tuple(w3.shape) != (w.shape[0], 3 * w.shape[1]):
+        raise ValueError("split16_front: the state was made for another weight shape")
+    nbytes = lib.dclip_split16_front_workspace()
+    ws = _ws.get(nbytes, pixels.device)
+    _lib.check(lib.dclip_split16_front(pixels.data_ptr(), pixels.numel(), w.data_ptr(), w.shape[0], w.shape[1], w3.data_ptr(),
+                                       state["wrec"].data_ptr(), rec.data_ptr(), _ptr(ws), nbytes, int(bool(refresh_w)), _stream()),
+               "split16_front")
+    return rec
+
+
+def split_f16x2_cols(x: torch.Tensor):
+    """The column-only split of a dY -> (yc, col_exp, col_alpha), bit-equal to the outputs of those names of
+    split_f16x3_rows_colstats on the same x; no row pieces, no column sums."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("split_f16x2_cols: x must be a 2-D fp32 device tensor with unit column stride")
+    rows, cols = x.shape
+    dev = x.device
+    yc = torch.empty((rows, 2 * cols), dtype=torch.float16, device=dev)
+    ce = torch.empty((cols,), dtype=torch.int32, device=dev)
+    ca = torch.empty((cols,), dtype=torch.float32, device=dev)
+    nbytes = lib.dclip_split_f32_f16x2_cols_workspace(rows, cols)
+    ws = _ws.get(nbytes, dev)
+    _lib.check(lib.dclip_split_f32_f16x2_cols(x.data_ptr(), yc.data_ptr(), ce.data_ptr(), ca.data_ptr(), rows, cols,
+                                              x.stride(0) if rows > 1 else cols, _ptr(ws), nbytes, _stream()), "split_f32_f16x2_cols")
+    return yc, ce, ca
+
+
 # ------------------------------------------------------------------------------------------- fp16 training path
 # The bf16 training wrappers above with fp16 tensors (include/dclip_hip.h, "fp16 TRAINING path"): same shapes and limits,
 # IEEE rounding — a value beyond +-65504 becomes +-inf (the frozen fp16 wrappers above saturate), so that the overflow of a

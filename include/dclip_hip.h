@@ -831,6 +831,41 @@ int dclip_gemm_f16x3_scaled_split2_dev(const void* A, const void* W, void* C, co
                                        int K, int lda, int ldw, int ldc, int a_hi, int a_lo, int w_hi, int w_lo, int epilogue,
                                        const float* alpha, const float* out_scale, void* stream);
 
+/* ---- the student's patch embedding and its weight gradient on split operands.  No GEMM of their own: the forward
+ * is dclip_gemm_f16x3_scaled_dev with lda = 2 K and offsets (0, K, 0, 2 K), the weight gradient dclip_gemm_f16x3_wgrad_tokmajor
+ * with (0, D), (0, K) — fc2's call forms — on the operands these entries write.
+ *   im2col_f16x2           dclip_im2col's gather written as fp16 [rows][2 C p p] = [hi|lo] of pixel * scale (a power of two) or,
+ *                          when not NULL, * the device float scale_dev: bit-equal to dclip_split_f32_f16x2 of dclip_im2col's
+ *                          output, one pass, no fp32 columns.  Square images, patch % 8 == 0, both operands 16-byte aligned.
+ *                          Launch name "im2col_f16x2".
+ *   split16_front          the front plan: rec float [split16_front_rec_floats] = 2^e | 2^f | alpha = 2^-(e+f) | flag bits | max|pixels| |
+ *                          max|w| | e | f (ints), e = engine.split16_act_exp(max|pixels|), f = engine.split16_weight_exp(max|w|),
+ *                          evaluated in double as dclip_split16_plan does, with its flag bits (1: e < -14; 2: a non-finite maximum —
+ *                          e resp. f is then 0; 4: a scale outside fp32's normal range, clamped).  refresh_w != 0: max|w| is taken
+ *                          too, wrec float [split16_front_wrec_floats] = 2^f | f | max|w| | the weight's flags is rewritten and w3 fp16
+ *                          [wrows][3 wcols] = [hi|hi|lo] of w 2^f, bit-equal to dclip_split_f32_f16x3(order 1) at that scale
+ *                          (wcols % 8 == 0; w, w3 16-byte aligned); refresh_w == 0: wrec is read as the last such call left it and
+ *                          w / w3 may be NULL.  npix values at pixels (16-byte aligned), any count.  Two launches, three with
+ *                          refresh_w; no atomics, nothing read back, the same bits in every run.  workspace: split16_front_workspace
+ *                          bytes, 16-byte aligned.  Launch names "split16_front.max", ".plan", ".weight".
+ *   split_f32_f16x2_cols   the column-only split of a dY: col_exp, col_alpha and yc fp16 [rows][2 cols] bit-equal to the outputs of
+ *                          those names of dclip_split_f32_f16x2_rows_colstats on the same x; no row pieces, no db.  The same limits
+ *                          (cols % 8 == 0, ldx % 4 == 0, 16-byte alignment); three launches (".max", ".finish", ".cols"), no
+ *                          atomics.  workspace: split_f32_f16x2_cols_workspace(rows, cols) bytes.
+ *   split16_patch_plan     1 where the step takes this path for a patch embedding [rows, K] x [D, K]: dclip_gemm_f16x3_plan holds
+ *                          and the call has at least DCLIP_PATCH_SPLIT16_MIN (default 128; read per call) tiles of 256 x 256. */
+int dclip_im2col_f16x2(const float* pixels, void* cols, int B, int C, int Himg, int Wimg, int patch, float scale,
+                       const float* scale_dev, void* stream);
+int dclip_split16_front_rec_floats(void);
+int dclip_split16_front_wrec_floats(void);
+size_t dclip_split16_front_workspace(void);
+int dclip_split16_front(const float* pixels, size_t npix, const float* w, int wrows, int wcols, void* w3, float* wrec, float* rec,
+                        void* workspace, size_t workspace_bytes, int refresh_w, void* stream);
+size_t dclip_split_f32_f16x2_cols_workspace(int rows, int cols);
+int dclip_split_f32_f16x2_cols(const float* x, void* yc, int* col_exp, float* col_alpha, int rows, int cols, int ldx, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int dclip_split16_patch_plan(int rows, int D, int K);
+
 /* ---- attention forward that writes its context ALREADY SPLIT (the frozen towers at precision "fp32-split16"):
  * the context of a frozen split-fp16 layer is read by one consumer, the split out-projection, so the fp32 [T][D] round trip
  * through dclip_split_f32_f16x2 / _f16x3 is folded into the attention kernel's store.
